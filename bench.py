@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Benchmark of the hot path (one `next_step()` of the MI355X-native CityFlow engine = one "step").
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 Workload (BASELINE.json configs[2]): the reference generator's 30x30 grid (cityflow_amd/data/scenarios/grid_30x30,
 produced by /root/reference/tools/generator) with ~100k concurrently running vehicles.  The stock generator's demand never
@@ -17,10 +17,15 @@ tile per GPU / rank, one-lane ghost halo exchanged every step (cityflow_amd.tile
 "scaling": "strong".  With WORLD_SIZE unset, `--gpus N` re-launches this script under `torch.distributed.run` with N ranks
 (one per GPU; ranks share devices when the box has fewer); with WORLD_SIZE set it must equal N.  `value` = vehicle-steps of
 all tiles / the slowest rank's time.  `--weak` grows the grid with N instead (every rank a 30x30 block), `--replicas` runs
-N independent copies (no exchange).  An N > 1 line also carries `scale_100x100`: the 100x100 / 1 M-vehicle network
+N independent copies (no exchange).  With --full an N > 1 line also carries `scale_100x100`: the 100x100 / 1 M-vehicle network
 (BASELINE configs[4]) tiled the same way — the N = 1 line times the same network on one GPU as `roofline_at_scale`.
 
-Output: ONE JSON line on rank 0 with these extra objects:
+Output: ONE JSON line on rank 0.  A plain run does only what the headline needs: it sets up the workload, warms up, times
+the K steps, writes the outputs of the last timed step if asked to (--dump-outputs DIR: per-lane counts, every running
+vehicle's speed and distance by vehicle id, and the scalars, as float64 DIR/<name>.npy) and prints `value` and `ms_per_step`.
+--full measures and checks everything else as well; without it the following objects of the line are null:
+  timed_region_detail, ms_per_step_200 (+ sustained_windows): per-call stamps of the timed region; five more windows of 200
+                     steps behind it when the timed region itself is shorter
   roofline           car-following kernel (k_action / kr_action) of the headline workload: algorithmic bytes (48 B per
                      running vehicle) / average launch duration measured with HIP events on the engine's
                      stream (the dispatch's own start / stop events, hipExtLaunchKernel: what a rocprofv3 kernel trace
@@ -500,6 +505,10 @@ def parse_args():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline: roofline, sustained windows, CPU baseline, parity, RL loop, 100x100")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write the outputs of the last timed step to DIR/<name>.npy (float64)")
     ap.add_argument("--build-up-steps", type=int, default=BUILD_UP_STEPS, help=argparse.SUPPRESS)
     ap.add_argument("--profile-steps", type=int, default=100, help="instrumented steps for the roofline leg")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="wall-time budget of the 8-thread cpu_baseline leg (0 = skip)")
@@ -522,6 +531,8 @@ def parse_args():
     ap.add_argument("--tile-block", type=int, default=30, help=argparse.SUPPRESS)
     ap.add_argument("--cfx", default="", help=argparse.SUPPRESS)  # developer: implementation choices, "key=value,key=value"
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.scale_steps is None:
         args.scale_steps = 50 if args.backend_lib == "" else 0
     return args
@@ -668,6 +679,30 @@ def timed_steps(job, eng, n, detail=None):
 
 def lane_hash16(eng):
     return hashlib.sha256(eng.get_lane_vehicle_count_array().tobytes()).hexdigest()[:16]
+
+
+DUMP_MAX_VEHICLES = 3000000  # 2 x 8 B each: the dump stays under 64 MB; a larger run writes a fixed, seeded sample
+
+
+def dump_outputs(eng, rank, out_dir):
+    """What the last timed step computed, as a caller of the engine API receives it: per-lane vehicle and waiting counts
+    (lane_ids order), every running vehicle's speed and distance (ordered by vehicle id) and the scalars (time, vehicle
+    count, average travel time), each as DIR/<name>.npy in float64.  Every rank calls it (a tiled engine's getters are
+    collective); rank 0 writes."""
+    import numpy as np
+    lanes, waiting = eng.get_lane_vehicle_count_array(), eng.get_lane_waiting_vehicle_count_array()
+    speed, distance = eng.get_vehicle_speed(), eng.get_vehicle_distance()
+    scalars = [eng.get_current_time(), eng.get_vehicle_count(), eng.get_average_travel_time()]
+    if rank != 0:
+        return
+    ids = sorted(speed)
+    if len(ids) > DUMP_MAX_VEHICLES:
+        ids = [ids[i] for i in np.sort(np.random.default_rng(0).choice(len(ids), DUMP_MAX_VEHICLES, replace=False))]
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in (("lane_vehicle_count", lanes), ("lane_waiting_vehicle_count", waiting),
+                    ("vehicle_speed", [speed[k] for k in ids]), ("vehicle_distance", [distance[k] for k in ids]),
+                    ("time_vehicle_count_average_travel_time", scalars)):
+        np.save(os.path.join(out_dir, name + ".npy"), np.asarray(a, dtype=np.float64))
 
 
 # ------------------------------------------------------------------------------------------------ the legs
@@ -1006,6 +1041,7 @@ def main():
         eng.next_step()
     eng.sync()
     want_checks = args.cpu_seconds > 0 and not args.replicas and (world == 1 or strong)
+    # (a plain run writes and re-reads the file as well: its timed region starts from the very state a --full run checks)
     state_dump = os.path.join(workdir, "state_at_build_up.json")
     if want_checks:
         arch = eng.snapshot()  # (tiled: assembled from one part per rank, every rank takes part)
@@ -1026,9 +1062,9 @@ def main():
     sc0 = total_scalars(job, eng, tiled)
     host0 = eng._eng._host_seconds() if tiled else None
 
-    # (every call of the timed region is stamped with the host clock too — two clock reads per step beside a 40 us device step
-    # the host runs ahead of: a region that comes out slow says where, `timed_region_detail`)
-    timed_detail = {}
+    # (--full: every call of the timed region is stamped with the host clock too — two clock reads per step beside a 40 us
+    # device step the host runs ahead of: a region that comes out slow says where, `timed_region_detail`)
+    timed_detail = {} if args.full else None
     elapsed = timed_steps(job, eng, args.steps, timed_detail)
 
     host1 = eng._eng._host_seconds() if tiled else None  # this rank's host time inside the timed region
@@ -1036,9 +1072,12 @@ def main():
     veh_steps = sc1["vehicle_steps"] - sc0["vehicle_steps"]
     run0, run1 = sc0["active_vehicle_count"], sc1["active_vehicle_count"]
     ties_in_window = sc1.get("tie_events", 0) - sc0.get("tie_events", 0)
+    if args.dump_outputs:
+        dump_outputs(eng, rank, args.dump_outputs)
     lane_hash_end = lane_hash16(eng)  # (every rank takes part in a tiled run's getter)
     end_record = None
-    if want_checks and tiled:  # what the single engine of rank 0 is compared with below (collective getters)
+    checks = want_checks and args.full
+    if checks and tiled:  # what the single engine of rank 0 is compared with below (collective getters)
         sp, di = eng.get_vehicle_speed(), eng.get_vehicle_distance()
         end_arch = eng.snapshot()
         if rank == 0:
@@ -1057,7 +1096,7 @@ def main():
     # (not where several ranks share one device: their kernels take turns on it, so per-kernel times say nothing about a tile,
     # and the instrumented rank — every launch bracketed by events — falls behind its neighbour's bounded halo wait)
     roofline = None
-    if on_gpu and args.profile_steps > 0 and (rank == 0 or tiled) and not (tiled and job.shared_devices):
+    if args.full and on_gpu and args.profile_steps > 0 and (rank == 0 or tiled) and not (tiled and job.shared_devices):
         scp0 = eng.local_scalars() if tiled else eng._scalars()
         if rank == 0:
             (eng._eng._profile_enable(0, True) if tiled else eng._profile_enable(True))
@@ -1099,21 +1138,22 @@ def main():
     # All windows are reported, their MEAN is the named figure — not the best one: a stall inside a window is part of what
     # a caller sees.  Every window carries where its slowest call was and what the device library did in it
     # (`sustained_windows`), so that a window that disagrees with its neighbours names its cause in the line itself.
-    window_details = []
-    if args.steps >= 200:
-        ms_200_windows = [elapsed / args.steps * 1e3]
-    else:
-        ms_200_windows = []
-        for _ in range(5):
-            det = {}
-            ms_200_windows.append(timed_steps(job, eng, 200, det) / 200 * 1e3)
-            window_details.append(det)
-    ms_per_step_200 = sum(ms_200_windows) / len(ms_200_windows)
-    ms_per_step_200_median = sorted(ms_200_windows)[len(ms_200_windows) // 2]
+    window_details, ms_200_windows, ms_per_step_200, ms_per_step_200_median = [], None, None, None
+    if args.full:
+        if args.steps >= 200:
+            ms_200_windows = [elapsed / args.steps * 1e3]
+        else:
+            ms_200_windows = []
+            for _ in range(5):
+                det = {}
+                ms_200_windows.append(timed_steps(job, eng, 200, det) / 200 * 1e3)
+                window_details.append(det)
+        ms_per_step_200 = sum(ms_200_windows) / len(ms_200_windows)
+        ms_per_step_200_median = sorted(ms_200_windows)[len(ms_200_windows) // 2]
 
     # ---- in-run parity and the CPU baseline (rank 0; a tiled run is compared with ONE engine on rank 0's device)
     cpu, legs, parity_in_run, parity_excused, parity_detail = None, None, None, None, None
-    if want_checks and rank == 0:
+    if checks and rank == 0:
         threads = args.cpu_threads or min(8, usable_cpus())
         cps = checkpoints_of(args.steps)
         detail_dir = tempfile.mkdtemp(prefix="parity_", dir=workdir)
@@ -1168,7 +1208,7 @@ def main():
 
     # ---- the RL loop on the headline network and the bandwidth-regime network
     rl_loop = None
-    if rank == 0 and world == 1 and args.rl_seconds > 0 and want_checks:
+    if rank == 0 and world == 1 and args.rl_seconds > 0 and checks:
         rl_loop = rl_loop_leg(job, args, cfg, workdir, state_dump)
     halo_name = eng.halo_transport() if tiled else None
     # what every rank ended on, so that the first run across several physical GPUs describes itself: transport, the physical
@@ -1184,7 +1224,7 @@ def main():
     n_lanes = len(eng.lane_ids())
     del eng
     scale = None
-    if args.scale_steps > 0 and not args.replicas and (world == 1 or strong):
+    if args.full and args.scale_steps > 0 and not args.replicas and (world == 1 or strong):
         scale = scale_leg(job, args, args.scale_steps)
 
     if rank == 0:

@@ -59,7 +59,7 @@ def test_bench_gpus_flag_launches_the_ranks_itself(tmp_path):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env["TMPDIR"] = str(tmp_path)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "40", "--warmup", "10", "--build-up-steps", "150",
-           "--cpu-seconds", "1", "--cpu-leg-seconds", "1", "--scenario", "grid_6x6", "--extra-flows", "60", "--backend-lib", TWIN_LIB]
+           "--cpu-seconds", "1", "--cpu-leg-seconds", "1", "--scenario", "grid_6x6", "--extra-flows", "60", "--backend-lib", TWIN_LIB, "--full"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -86,7 +86,8 @@ def test_bench_single_engine_in_run_parity_twin(tmp_path):
     line names the backend that ran."""
     env = dict(os.environ, TMPDIR=str(tmp_path))
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "30", "--warmup", "5", "--build-up-steps", "120", "--cpu-seconds", "1",
-           "--cpu-leg-seconds", "1", "--rl-seconds", "0.5", "--scenario", "grid_6x6", "--extra-flows", "40", "--backend-lib", TWIN_LIB]
+           "--cpu-leg-seconds", "1", "--rl-seconds", "0.5", "--scenario", "grid_6x6", "--extra-flows", "40", "--backend-lib", TWIN_LIB,
+           "--full"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     d = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][0])
@@ -151,6 +152,31 @@ def test_bench_single_rank_twin(tmp_path):
     d = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][0])
     assert d["n_gpus"] == 1 and d["roofline"] is None and d["cpu_baseline"] is None
     assert d["warmup"] == 10 and "20 simulated seconds" in d["config"]["state"]  # the workload state does not depend on --warmup
+
+
+def test_bench_plain_run_dumps_the_same_outputs_every_time(tmp_path):
+    """A plain run (no --full) times the steps and nothing else; --dump-outputs writes the last timed step's outputs, and two
+    runs with the same arguments write the same arrays."""
+    import numpy as np
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "15", "--warmup", "5", "--build-up-steps", "60",
+           "--scenario", "grid_6x6", "--extra-flows", "40", "--backend-lib", TWIN_LIB]
+    dumps = []
+    for i in range(2):  # (each run builds its workload afresh, in a temporary directory of its own)
+        dumps.append(tmp_path / ("out%d" % i))
+        (tmp_path / ("tmp%d" % i)).mkdir()
+        out = subprocess.run(cmd + ["--dump-outputs", str(dumps[-1])], env=dict(os.environ, TMPDIR=str(tmp_path / ("tmp%d" % i))),
+                             capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-2000:]
+        d = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][0])
+        assert d["steps"] == 15 and d["ms_per_step"] > 0 and d["value"] > 0
+        assert d["cpu_baseline"] is None and d["parity"] is None and d["rl_loop"] is None and d["ms_per_step_200"] is None
+    names = sorted(p.name for p in dumps[0].iterdir())
+    assert names == sorted(p.name for p in dumps[1].iterdir())
+    assert "vehicle_speed.npy" in names and "lane_vehicle_count.npy" in names
+    for n in names:
+        a, b = np.load(dumps[0] / n), np.load(dumps[1] / n)
+        assert a.dtype == np.float64 and a.size > 0 and np.array_equal(a, b), n
+    assert np.load(dumps[0] / "vehicle_speed.npy").size == d["config"]["running_vehicles_end"]
 
 
 def test_bench_falls_back_to_replicas_when_no_halo_transport_comes_up(tmp_path):

@@ -3,8 +3,8 @@
 #   tools/profile_round.sh <tag> [workload] [extra bench.py flags]      e.g. r03_v2 bench | r03_v2 gen_100x100 | r03_v2 grid_6x6
 #   (extra flags, e.g. "--cfx layout=ring,ringLanesPerWave=30000", select a non-default form of the step; say so in the tag)
 # kernel trace of the bench command on that workload + FETCH_SIZE / WRITE_SIZE in separate PMC passes (MI355X_MICROARCH.md),
-# summaries written under gpurun_out/<tag>_<workload>_* (copy the ones to keep into profiles/).  The full default bench line
-# (all legs) is a separate call: `python bench.py > gpurun_out/<tag>_bench.json`.
+# summaries written to the script's output directory as <tag>_<workload>_* (copy the ones to keep into profiles/).  The bench line with all
+# legs is a separate call: `python bench.py --full > <tag>_bench.json`.
 set -u
 tag=${1:-r04}
 wl=${2:-bench}
