@@ -572,6 +572,10 @@ void EngineHost::load(const Archive &a) {
     step_ = (size_t) d.step;
     waitingCustom_.clear();  // (compactVehicles puts back what it carries over)
     vehicleEpoch_ += 1;  // vehicle numbers of the archive replace the current ones
+    // An archive taken earlier holds fewer vehicle numbers than the state it replaces: the next compaction is due that many
+    // numbers after what it holds, not at the schedule of the state before (which would let the tables grow back to it first).
+    const size_t held = spawner_.vehicles.size();
+    nextCompactAt_ = std::min(nextCompactAt_, compactAuto_ ? std::max(compactAt_, 32 * held) : held + compactAt_);
 }
 
 // Archive(Engine&, filename) archive.cpp:345-550: rebuild an Archive from the reference's JSON format.
@@ -591,8 +595,12 @@ Archive readArchiveFile(const std::string &path, const std::shared_ptr<HostRoadN
 
     a.host = spawner_.saveState();  // flows' valid flags, manual counter; the rest is overwritten below
     a.host.vehicles.clear();
-    for (auto &v : a.host.flowVids) v.clear();
-    std::fill(a.host.manualVids.begin(), a.host.manualVids.end(), -1);
+    // the number -> vid tables are filled by absolute vehicle number below: their bases go back to 0 (a compaction before the
+    // load moved them up; the next compaction moves them up again from here)
+    a.host.flowVids.assign(spawner_.flows.size(), {});
+    a.host.flowVidBase.assign(spawner_.flows.size(), 0);
+    a.host.manualVids.clear();
+    a.host.manualVidBase = 0;
     std::fill(a.host.lastWaitVid.begin(), a.host.lastWaitVid.end(), -1);
     a.host.livePriority.clear();
 

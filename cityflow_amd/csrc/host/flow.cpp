@@ -9,6 +9,7 @@
 #include <map>
 #include <queue>
 #include <set>
+#include <stdexcept>
 
 #include "json.h"
 
@@ -478,6 +479,11 @@ void Spawner::step(size_t stepIndex, std::vector<cfx_spawn> &out) {
             {
                 std::vector<int32_t> &tbl = rec.flow >= 0 ? flowVids[rec.flow] : manualVids;
                 const int at = rec.number - (rec.flow >= 0 ? flowVidBase[rec.flow] : manualVidBase);  // (numbers only grow: never below the base)
+                if (at < 0)  // a base that does not belong to this table (a load that left it stale): never index below it
+                    throw std::logic_error("Spawner::step: vehicle number " + std::to_string(rec.number) + " of " +
+                                           (rec.flow >= 0 ? "flow '" + flows[rec.flow].id + "'" : std::string("push_vehicle")) +
+                                           " lies below its id table's base " +
+                                           std::to_string(rec.flow >= 0 ? flowVidBase[rec.flow] : manualVidBase));
                 if (journal_.active) journal_.vidTables.emplace_back(rec.flow >= 0 ? rec.flow : -1, tbl.size());
                 if ((int) tbl.size() <= at) tbl.resize(at + 1, -1);
                 tbl[at] = vid;

@@ -1650,6 +1650,8 @@ void TiledEngineHost::load(const Archive &a) {
     }
     numbersOut_ = spawner_.vehicles.size();
     step_ = (size_t) a.dev.step;
+    // (an archive taken earlier holds fewer vehicle numbers: the next compaction counts from them — EngineHost::load)
+    nextCompactAt_ = std::min(nextCompactAt_, compactAuto_ ? std::max(compactAt_, 32 * numbersOut_) : numbersOut_ + compactAt_);
 }
 
 void TiledEngineHost::loadFromFile(const std::string &path) {

@@ -327,11 +327,14 @@ def _comparable_dump(path, written_by_reference, keep_history=False):
     return d
 
 
-@pytest.mark.parametrize("seed,history", [(3, False), (4, False), (5, True), (6, True)])
-def test_archive_files_cross_loaded_in_the_middle_of_sequences(mod, ref_module, scen, workdir, tmp_path, seed, history):
+@pytest.mark.parametrize("seed,history,compact", [pytest.param(3, False, 0, id="3-False"), pytest.param(4, False, 0, id="4-False"),
+                                                  pytest.param(5, True, 0, id="5-True"), pytest.param(6, True, 0, id="6-True"),
+                                                  (3, False, 25), (6, True, 40)])
+def test_archive_files_cross_loaded_in_the_middle_of_sequences(mod, ref_module, scen, workdir, tmp_path, seed, history, compact):
     """`snapshot().dump()` of the reference and of this engine at random moments of a sequence with custom speeds, pushed
     vehicles and full waiting buffers: the files are equal (see _comparable_dump), both engines load one of the two files
-    and go on identically — again and again in one run (archive.cpp:153-550)."""
+    and go on identically — again and again in one run (archive.cpp:153-550).  With `compact`, this engine forgets its finished
+    vehicles in between: a file it loads names vehicles the last compaction renumbered (csrc/host/archive.cpp readArchiveFile)."""
     rl = seed % 2 == 0
     cfg = _config(scen, workdir, rl)
     if history:  # Lane::history kept ("cfx": {"laneHistory": true}) and compared too: it travels with the files (archive.cpp:286-294)
@@ -340,6 +343,7 @@ def test_archive_files_cross_loaded_in_the_middle_of_sequences(mod, ref_module, 
         cfg = cfg.replace(".json", "_history.json")
         with open(cfg, "w") as f:
             json.dump(c, f)
+    cfg = _compacting(cfg, compact)
     ref, tw = ref_module.Engine(cfg, 1), mod.Engine._with_backend(cfg, 1, TWIN_LIB)
     rng = np.random.default_rng(seed)
     exchanged = 0
@@ -381,5 +385,6 @@ def test_archive_files_cross_loaded_in_the_middle_of_sequences(mod, ref_module, 
                 tw.next_step()
         assert checkpoint_record(tw) == checkpoint_record(ref), (seed, round_)
     assert exchanged >= 2
+    assert (tw._vehicle_table()[1] > 3) == bool(compact), tw._vehicle_table()
     time.sleep(0.2)  # reference destructor race
     del ref

@@ -156,6 +156,17 @@ def test_two_ranks_compaction_gloo(scen, workdir, tmp_path, mailboxes):
     assert "TILED_OK 700" in out.stdout and "COMPACT_OK" in out.stdout
 
 
+def test_two_ranks_compaction_then_load_from_file_gloo(scen, workdir, tmp_path):
+    """... and an Archive file the single engine wrote before the compactions, loaded afterwards by every rank's tiles
+    (DistributedEngine.load_from_file: every rank reads the same file and keeps its tile's part) and by the single engine: every
+    id resolves to its vehicle and both go on equal through the next compaction (tests/tiled_worker.py: CFX_TEST_LOAD_FILE)."""
+    cfg = scen.generate_grid(6, 6, workdir, flow_interval=12.0)
+    out = _torchrun(tmp_path, cfg, TWIN_LIB, 1, 2, 700, 2, free_port(),
+                    {"CFX_TEST_MAILBOXES": "1", "CFX_TEST_COMPACT": "300", "CFX_TEST_LOAD_FILE": "1"})
+    assert out.returncode == 0, out.stdout[-1500:] + out.stderr[-3000:]
+    assert "TILED_OK 700" in out.stdout and "COMPACT_OK" in out.stdout and "LOAD_FILE_OK" in out.stdout
+
+
 def test_two_ranks_replay_gloo(scen, workdir, tmp_path):
     """saveReplay with one tile per process: the replay file rank 0 writes equals the single engine's (tests/tiled_worker.py)."""
     cfg = scen.materialize("grid_6x6", workdir)
@@ -280,12 +291,13 @@ def test_two_ranks_one_gpu(scen, workdir, tmp_path, mailboxes):
 def test_two_ranks_one_gpu_compaction_and_archive(scen, workdir, tmp_path):
     """Two processes sharing this box's GPU, HIP tiles, GPU-written mailboxes: the tiles forget their finished vehicles every 300
     vehicle numbers (a collective: every rank's part of the state on every rank, `Lane::history` in the parts) and stay equal,
-    id by id, to one engine that never forgets; then snapshot / dump (the single engine's file, history included) / load /
+    id by id, to one engine that never forgets, also after both load a file the single engine wrote before the compactions; then snapshot / dump (the single engine's file, history included) / load /
     setRoute over the ranks (tests/tiled_worker.py: CFX_TEST_COMPACT, CFX_TEST_ARCHIVE)."""
     cfg = scen.generate_grid(6, 6, workdir, flow_interval=12.0)
-    out = _torchrun(tmp_path, cfg, "", 1, 2, 700, 2, free_port(), {"CITYFLOW_AMD_DEVICE": "0", "CFX_TEST_MAILBOXES": "1", "CFX_TEST_COMPACT": "300"})
+    out = _torchrun(tmp_path, cfg, "", 1, 2, 700, 2, free_port(), {"CITYFLOW_AMD_DEVICE": "0", "CFX_TEST_MAILBOXES": "1", "CFX_TEST_COMPACT": "300",
+                                                                   "CFX_TEST_LOAD_FILE": "1"})
     assert out.returncode == 0, out.stdout[-1500:] + out.stderr[-3000:]
-    assert "TILED_OK 700" in out.stdout and "COMPACT_OK" in out.stdout
+    assert "TILED_OK 700" in out.stdout and "COMPACT_OK" in out.stdout and "LOAD_FILE_OK" in out.stdout
     cfg = dense_cfg(scen, workdir, "grid_6x6", 60, 5, 1.0)
     out = _torchrun(tmp_path, cfg, "", 2, 1, 120, 2, free_port(), {"CITYFLOW_AMD_DEVICE": "0", "CFX_TEST_MAILBOXES": "1", "CFX_TEST_ARCHIVE": "1"})
     assert out.returncode == 0, out.stdout[-1500:] + out.stderr[-3000:]

@@ -45,10 +45,15 @@ def main():
     if transport:
         assert eng.transport == transport, (eng.transport, transport)
     single = m.Engine._with_backend(single_cfg, 1, lib) if lib else m.Engine(single_cfg, 1)
+    # CFX_TEST_LOAD_FILE (with CFX_TEST_COMPACT): the single engine's Archive file of step 50, loaded after the compactions
+    load_file = compact and os.environ.get("CFX_TEST_LOAD_FILE") == "1"
+    early = os.path.join(os.path.dirname(cfg), "early_%s.json" % os.environ.get("MASTER_PORT", "0"))
     crossed = 0
     for s in range(steps):
         eng.next_step()
         single.next_step()
+        if load_file and s == 50 and rank == 0:
+            single.snapshot().dump(early)
         a = single.get_lane_vehicle_count_array()
         b = eng.get_lane_vehicle_count_array()
         assert np.array_equal(a, b), "rank %d step %d: lane counts differ" % (rank, s)
@@ -90,6 +95,32 @@ def main():
         assert eng.get_vehicle_speed() == single.get_vehicle_speed()
         if rank == 0:
             print("COMPACT_OK", times + 1, "compactions,", held, "of", single._vehicle_table()[0], "vehicle numbers held")
+    if load_file:
+        # every rank's tiles and its single engine load the file written before the compactions (its vehicle numbers are
+        # not the renumbered ones: the loader's id tables start over) and go on equal, through the next compaction
+        dist.barrier()
+        eng.load_from_file(early)
+        single.load_from_file(early)
+        ids = single.get_vehicles(True)
+        assert eng.get_vehicles(True) == ids and ids, rank
+        for v in ids:
+            assert eng.get_vehicle_info(v) == single.get_vehicle_info(v), (rank, v)
+        times0 = eng._eng._vehicle_table()[1]
+        for s in range(400):
+            eng.next_step()
+            single.next_step()
+            assert np.array_equal(eng.get_lane_vehicle_count_array(), single.get_lane_vehicle_count_array()), (rank, s)
+            if s % 50 == 49:
+                assert eng.get_vehicle_speed() == single.get_vehicle_speed(), (rank, s)
+                assert eng.get_vehicle_distance() == single.get_vehicle_distance(), (rank, s)
+                assert eng.get_vehicles(True) == single.get_vehicles(True), (rank, s)
+        some = single.get_vehicles(True)
+        for v in some[:20] + some[-20:]:
+            assert eng.get_vehicle_info(v) == single.get_vehicle_info(v), (rank, v)
+            assert eng.get_leader(v) == single.get_leader(v), (rank, v)
+        assert eng._eng._vehicle_table()[1] > times0, (rank, eng._eng._vehicle_table(), times0)
+        if rank == 0:
+            print("LOAD_FILE_OK", len(ids), "vehicles loaded,", eng._eng._vehicle_table()[1] - times0, "compactions since")
     if os.environ.get("CFX_TEST_ARCHIVE") == "1":
         # archive and routes over ranks: the snapshot assembled from every rank's part is the single engine's; after a load
         # (no communication: every rank keeps its tile's part) both go on identically; setRoute gives the same verdicts
