@@ -23,7 +23,7 @@ from . import torch_io as _torch_io  # (does not import torch: its first call do
 Engine = _cityflow.Engine
 Archive = _cityflow.Archive
 VectorEngine = _cityflow.VectorEngine
-_torch_io.install(Engine, VectorEngine)  # get_lane_*_tensor / set_tl_phases_tensor
+_torch_io.install(Engine, VectorEngine)  # get_lane_*_tensor / set_tl_phases_tensor / observe_lanes_tensor
 TiledEngine = _cityflow.TiledEngine  # one network over several engines; cityflow_amd.tiled.DistributedEngine = one per GPU
 __version__ = _cityflow.__version__
 

@@ -140,6 +140,10 @@ struct cfx_engine {
     bool devObserving = false;
     int devObserveIdle = 0;
     int32_t *hPhaseErr = nullptr;  // pinned, host-mapped: {intersection, phase} of the first rejected device-side entry, {-1, 0}
+    // cfx_get_lane_features: device scratch kept between calls (grown to the largest request seen; in `owned`)
+    double *featSum = nullptr, *featEdges = nullptr;
+    int32_t *featBins = nullptr;
+    size_t featBinsCap = 0, featEdgesCap = 0;
     int cross2 = -1;                // cross phase: 1 = k_cross2 (throughput), 0 = k_cross (latency), -1 = by size
     HostMirror *hMirror = nullptr;  // pinned; valid while the last thing that changed the scalars was a step
     bool mirrorValid = false;
@@ -3221,6 +3225,100 @@ int32_t cfx_device_error(cfx_engine *e, int32_t *inter, int32_t *phase) {
     if (phase) *phase = rec[1];
     rec[0] = -1;
     return 1;
+}
+
+// ---- per-lane speed and position features (optional entry points of include/cityflow_amd.h, as above)
+int32_t cfx_observe_lanes_device(cfx_engine *e, int32_t *counts, int32_t *waiting, double *speedSum, int32_t *bins,
+                                 const double *edges, int32_t nBins, int32_t perLaneEdges, void *consumerStream);
+int32_t cfx_get_lane_features(cfx_engine *e, double *speedSum, int32_t *bins, const double *edges, int32_t nBins,
+                              int32_t perLaneEdges);
+static_assert(std::is_same<decltype(&cfx_observe_lanes_device), cfx_observe_lanes_device_fn>::value, "cfx_observe_lanes_device");
+static_assert(std::is_same<decltype(&cfx_get_lane_features), cfx_get_lane_features_fn>::value, "cfx_get_lane_features");
+
+static bool laneFeatureArgs(cfx_engine *e, const int32_t *bins, const double *edges, int32_t nBins, const char *what) {
+    if (!bins) return true;
+    if (!edges || nBins < 1 || nBins > CFX_MAX_LANE_BINS) {
+        e->err = std::string(what) + ": bins need edges and 1 <= n_bins <= " + std::to_string(CFX_MAX_LANE_BINS);
+        return false;
+    }
+    return true;
+}
+
+static LaneFeatOut laneFeatOut(const cfx_engine *e, int32_t *counts, int32_t *waiting, double *speedSum, int32_t *bins,
+                               const double *edges, int32_t nBins, int32_t perLaneEdges) {
+    const int nEnvs = e->cfg.n_envs > 1 ? e->cfg.n_envs : 1;
+    LaneFeatOut o{counts, waiting, speedSum, bins, bins ? edges : nullptr, bins ? nBins : 0, 0, std::max(e->L / nEnvs, 1)};
+    o.edgeStride = (bins && perLaneEdges) ? nBins + 1 : 0;
+    return o;
+}
+
+static void launchLaneFeatures(cfx_engine *e, const LaneFeatOut &o) {
+    const size_t threads = (size_t) e->L * kFeatGroup;
+    if (e->ring) hipLaunchKernelGGL(kr_lane_features, dim3(gridFor(threads)), dim3(kBlock), 0, e->stream, e->rctx(), o);
+    else hipLaunchKernelGGL(kd_lane_features, dim3(gridFor(threads)), dim3(kBlock), 0, e->stream, e->ctx(), o);
+}
+
+int32_t cfx_observe_lanes_device(cfx_engine *e, int32_t *counts, int32_t *waiting, double *speedSum, int32_t *bins,
+                                 const double *edges, int32_t nBins, int32_t perLaneEdges, void *consumerStream) {
+    if (!e || (!counts && !waiting && !speedSum && !bins)) return CFX_ERR_INVALID;
+    if (!laneFeatureArgs(e, bins, edges, nBins, "cfx_observe_lanes_device")) return CFX_ERR_INVALID;
+    auto fail = [e](const std::string &m) { return e->fail(m); };
+    HIP_TRY(hipSetDevice(e->device));
+    int rc;
+    if (counts && (rc = checkDevicePointer(e, counts, "cfx_observe_lanes_device: counts"))) return rc;
+    if (waiting && (rc = checkDevicePointer(e, waiting, "cfx_observe_lanes_device: waiting"))) return rc;
+    if (speedSum && (rc = checkDevicePointer(e, speedSum, "cfx_observe_lanes_device: speed_sum"))) return rc;
+    if (bins && (rc = checkDevicePointer(e, bins, "cfx_observe_lanes_device: bins"))) return rc;
+    if (bins && (rc = checkDevicePointer(e, edges, "cfx_observe_lanes_device: edges"))) return rc;
+    if ((rc = e->settle(false))) return rc;  // (ring layout: a commit deferred to the next step's admission; Lane::history is not read here)
+    if ((rc = e->syncTables())) return rc;
+    if (e->ring && (rc = e->ringEnsure())) return rc;
+    const hipStream_t cs = (hipStream_t) consumerStream;
+    if (cs != e->stream) {  // the buffers may still be read by what the caller enqueued before (a reused output)
+        HIP_TRY(hipEventRecord(e->devInEvent, cs));
+        HIP_TRY(hipStreamWaitEvent(e->stream, e->devInEvent, 0));
+    }
+    launchLaneFeatures(e, laneFeatOut(e, counts, waiting, speedSum, bins, edges, nBins, perLaneEdges));
+    HIP_TRY(hipGetLastError());
+    if (cs != e->stream) {
+        HIP_TRY(hipEventRecord(e->devOutEvent, e->stream));
+        HIP_TRY(hipStreamWaitEvent(cs, e->devOutEvent, 0));
+    }
+    e->devObserving = !e->tiled;
+    e->devObserveIdle = 0;
+    return CFX_OK;
+}
+
+int32_t cfx_get_lane_features(cfx_engine *e, double *speedSum, int32_t *bins, const double *edges, int32_t nBins,
+                              int32_t perLaneEdges) {
+    if (!e || (!speedSum && !bins)) return CFX_ERR_INVALID;
+    if (!laneFeatureArgs(e, bins, edges, nBins, "cfx_get_lane_features")) return CFX_ERR_INVALID;
+    auto fail = [e](const std::string &m) { return e->fail(m); };
+    HIP_TRY(hipSetDevice(e->device));
+    int rc;
+    if ((rc = e->settle(false))) return rc;
+    if ((rc = e->syncTables())) return rc;
+    if (e->ring && (rc = e->ringEnsure())) return rc;
+    const LaneFeatOut shape = laneFeatOut(e, nullptr, nullptr, nullptr, bins, edges, nBins, perLaneEdges);
+    const size_t nSum = (size_t) e->L, nOut = bins ? (size_t) e->L * nBins : 0,
+                 nEdges = bins ? (perLaneEdges ? (size_t) shape.lanesPerEnv : 1) * (nBins + 1) : 0;
+    if (speedSum && !e->featSum && (rc = e->allocRaw(&e->featSum, nSum))) return rc;
+    if (nOut > e->featBinsCap) {
+        if ((rc = e->grow(&e->featBins, 0, nOut))) return rc;
+        e->featBinsCap = nOut;
+    }
+    if (nEdges > e->featEdgesCap) {
+        if ((rc = e->grow(&e->featEdges, 0, nEdges))) return rc;
+        e->featEdgesCap = nEdges;
+    }
+    if (nEdges) HIP_TRY(hipMemcpyAsync(e->featEdges, edges, nEdges * sizeof(double), hipMemcpyHostToDevice, e->stream));
+    launchLaneFeatures(e, laneFeatOut(e, nullptr, nullptr, speedSum ? e->featSum : nullptr, bins ? e->featBins : nullptr,
+                                      e->featEdges, nBins, perLaneEdges));
+    HIP_TRY(hipGetLastError());
+    if (speedSum) HIP_TRY(hipMemcpyAsync(speedSum, e->featSum, nSum * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+    if (bins) HIP_TRY(hipMemcpyAsync(bins, e->featBins, nOut * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    return CFX_OK;
 }
 
 int32_t cfx_profile_kernel_count(void) { return kNumProfKernels; }

@@ -2234,6 +2234,86 @@ __global__ void kd_observe(StepCtx c, int32_t *counts, int32_t *waiting) {
     }
 }
 
+// cfx_observe_lanes_device / cfx_get_lane_features: every per-lane observation in one launch (any pointer may be null).  A GROUP of
+// kFeatGroup threads reads one lane: its records are contiguous, so one chunk of 16 vehicles is one set of neighbouring loads
+// instead of a serial walk.  Integers (waiting, bins) are counted per thread; the speed sum must be added front to back, so
+// each chunk is staged in LDS and every thread of the group runs the same chain of adds over it (the reads are independent,
+// only the adds are serial).  Bins: thread `sub` owns bins sub and sub + 16 — two counters with fixed indices, no per-thread
+// array indexed at run time (it would live in scratch).
+constexpr int kFeatGroup = 16;
+struct LaneFeatOut {
+    int32_t *counts, *waiting;
+    double *speedSum;
+    int32_t *bins;        // [lane * nBins + b]
+    const double *edges;  // [rows][nBins + 1], row = (lane % lanesPerEnv) * edgeStride
+    int nBins;            // 0: no bins
+    int edgeStride;       // nBins + 1 for per-lane edges, 0 for one shared row
+    int lanesPerEnv;
+};
+
+// (the group's LDS chunk is written and read by lanes of one wavefront: a wavefront's LDS accesses complete in order, so a
+// fence that keeps the compiler from moving them across each other is all the synchronisation needed)
+__device__ __forceinline__ void waveLdsOrder() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// rec(i) = {dis, speed} of the lane's i-th vehicle from the front; stage = the group's kFeatGroup LDS records
+template <typename Rec>
+__device__ __forceinline__ void laneFeatures(const LaneFeatOut &o, int lane, int n, int sub, double2 *stage, Rec rec) {
+    if (o.counts && sub == 0) o.counts[lane] = n;
+    const bool staged = o.speedSum || o.nBins;
+    double lo0 = 1.0, hi0 = 0.0, lo1 = 1.0, hi1 = 0.0;  // (an empty interval: counts nothing)
+    if (o.nBins) {
+        const double *e = o.edges + (size_t) (lane % o.lanesPerEnv) * o.edgeStride;
+        if (sub < o.nBins) lo0 = e[sub], hi0 = e[sub + 1];
+        if (sub + kFeatGroup < o.nBins) lo1 = e[sub + kFeatGroup], hi1 = e[sub + kFeatGroup + 1];
+    }
+    int w = 0, b0 = 0, b1 = 0;
+    double sum = 0.0;
+    for (int first = 0; first < n; first += kFeatGroup) {  // (the trip count is the group's: n is the same in all its threads)
+        double2 r = make_double2(0.0, 0.0);
+        if (first + sub < n) {
+            r = rec(first + sub);
+            w += r.y < 0.1;
+        }
+        if (staged) {
+            stage[sub] = r;
+            waveLdsOrder();
+            const int m = min(n - first, kFeatGroup);
+            for (int j = 0; j < m; ++j) {
+                const double2 v = stage[j];  // (the same address in every thread of the group: a broadcast)
+                sum += v.y;
+                b0 += lo0 <= v.x && v.x < hi0;
+                b1 += lo1 <= v.x && v.x < hi1;
+            }
+            waveLdsOrder();  // (the next chunk overwrites the stage)
+        }
+    }
+    if (o.waiting) {
+        for (int off = kFeatGroup / 2; off > 0; off >>= 1) w += __shfl_xor(w, off, kFeatGroup);
+        if (sub == 0) o.waiting[lane] = w;
+    }
+    if (o.speedSum && sub == 0) o.speedSum[lane] = sum;
+    if (o.nBins) {
+        int32_t *out = o.bins + (size_t) lane * o.nBins;
+        if (sub < o.nBins) out[sub] = b0;
+        if (sub + kFeatGroup < o.nBins) out[sub + kFeatGroup] = b1;
+    }
+}
+
+// dense layout: the lane's segment [segStart, segStart + cnt) of the current generation, front to back
+__global__ void __launch_bounds__(kBlock) kd_lane_features(StepCtx c, LaneFeatOut o) {
+    __shared__ double2 stage[kBlock];
+    const int lane = (int) ((blockIdx.x * (size_t) blockDim.x + threadIdx.x) / kFeatGroup);
+    if (lane >= c.n.L) return;  // (whole groups)
+    const int sub = threadIdx.x % kFeatGroup;
+    const int base = c.segStart[lane], n = c.cnt[lane];
+    laneFeatures(o, lane, n, sub, stage + (threadIdx.x - sub),
+                 [&](int i) { return make_double2(c.s.dis[base + i], c.s.speed[base + i]); });
+}
+
 // Initial / reset layout: every lane owns just its spare slot, laneLinks are empty.
 __global__ void k_init_layout(int D, int L, int32_t *segStart, int32_t *cnt, int32_t *vid, int32_t *drv) {
     int d = blockIdx.x * blockDim.x + threadIdx.x;

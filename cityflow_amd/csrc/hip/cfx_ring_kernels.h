@@ -2365,6 +2365,19 @@ __global__ void kr_observe(RingCtx c, int32_t *counts, int32_t *waiting) {
     }
 }
 
+// cfx_observe_lanes_device / cfx_get_lane_features, ring layout: laneFeatures (cfx_kernels.h) over the lane's ring, front to
+// back from `head`, reading the {dis, speed} record kr_observe reads
+__global__ void __launch_bounds__(kBlock) kr_lane_features(RingCtx c, LaneFeatOut o) {
+    __shared__ double2 stage[kBlock];
+    const int lane = (int) ((blockIdx.x * (size_t) blockDim.x + threadIdx.x) / kFeatGroup);
+    if (lane >= c.n.L) return;  // (whole groups)
+    const int sub = threadIdx.x % kFeatGroup;
+    const int n = c.cnt[lane];
+    const int2 geo = c.ringGeo[lane];
+    const int head = c.head[lane];
+    laneFeatures(o, lane, n, sub, stage + (threadIdx.x - sub), [&](int i) { return c.kin[ringSlot(geo, head, i)]; });
+}
+
 // Vehicle::setCustomSpeed / Router::setRoute / lookup of one running vehicle: its slot is known
 __global__ void kr_set_speed(RingCtx c, int vid) {
     const int s = c.slotOf[vid];

@@ -92,6 +92,8 @@ void Backend::open(const std::string &libPath) {
     CFX_FN_OPTIONAL(cfx_observe_device)
     CFX_FN_OPTIONAL(cfx_set_tl_phases_device)
     CFX_FN_OPTIONAL(cfx_device_error)
+    CFX_FN_OPTIONAL(cfx_observe_lanes_device)
+    CFX_FN_OPTIONAL(cfx_get_lane_features)
 #undef CFX_FN_OPTIONAL
     if (cfx_abi_version() != CFX_ABI_VERSION)
         throw std::runtime_error("cityflow_amd: ABI version mismatch in '" + libPath + "'");
@@ -470,6 +472,76 @@ void EngineHost::setTrafficLightPhasesDevice(uintptr_t phases, size_t n, uintptr
     check(be_.cfx_set_tl_phases_device(dev_, (const int32_t *) phases, (int32_t) n, (void *) producerStream),
           "cfx_set_tl_phases_device");
     devicePhaseUnchecked_ = true;
+}
+
+std::vector<double> EngineHost::laneLengths() const {
+    const cfx_net &f = net_->flat();
+    return std::vector<double>(f.drv_length, f.drv_length + f.n_lanes);
+}
+
+// (like the count getters, these leave the step prepared ahead in place: they read the device's vehicles, not the spawner)
+void EngineHost::laneFeatures(double *speedSum, int32_t *bins, const double *edges, int nBins, bool perLaneEdges) {
+    const int L = (int) net_->lanes.size();
+    laneFeaturesOf(be_, dev_, L, L, speedSum, bins, edges, nBins, perLaneEdges);
+    raiseDeviceError();
+}
+
+void EngineHost::observeLanesDevice(uintptr_t counts, uintptr_t waiting, uintptr_t speedSum, uintptr_t bins, uintptr_t edges,
+                                    int nBins, bool perLaneEdges, uintptr_t consumerStream) {
+    if (!laneFeaturesOnDevice()) throw std::runtime_error("cityflow_amd: '" + be_.path + "' has no device lane features");
+    check(be_.cfx_observe_lanes_device(dev_, (int32_t *) counts, (int32_t *) waiting, (double *) speedSum, (int32_t *) bins,
+                                       (const double *) edges, nBins, perLaneEdges ? 1 : 0, (void *) consumerStream),
+          "cfx_observe_lanes_device");
+}
+
+void laneFeaturesFromView(int nLanes, int lanesPerEnv, int count, const int32_t *drivable, const double *dis, const double *speed,
+                          double *speedSum, int32_t *bins, const double *edges, int nBins, bool perLaneEdges) {
+    if (speedSum) std::fill(speedSum, speedSum + nLanes, 0.0);
+    if (bins) std::fill(bins, bins + (size_t) nLanes * nBins, 0);
+    for (int i = 0; i < count; ++i) {  // (front to back inside a lane: the sum is the reference's curSpeedSum)
+        const int l = drivable[i];
+        if (l < 0 || l >= nLanes) continue;
+        if (speedSum) speedSum[l] += speed[i];
+        if (!bins) continue;
+        const double *e = edges + (perLaneEdges ? (size_t) (l % lanesPerEnv) * (nBins + 1) : 0);
+        for (int b = 0; b < nBins; ++b) bins[(size_t) l * nBins + b] += e[b] <= dis[i] && dis[i] < e[b + 1];
+    }
+}
+
+void laneFeaturesOf(const Backend &be, cfx_engine *dev, int nLanes, int lanesPerEnv, double *speedSum, int32_t *bins,
+                    const double *edges, int nBins, bool perLaneEdges) {
+    auto fail = [&](const char *what) {
+        const char *msg = be.cfx_last_error(dev);
+        throw std::runtime_error(std::string("cityflow_amd: ") + what + " failed: " + (msg ? msg : ""));
+    };
+    if (be.cfx_get_lane_features) {
+        if (be.cfx_get_lane_features(dev, speedSum, bins, edges, nBins, perLaneEdges ? 1 : 0) != CFX_OK) fail("cfx_get_lane_features");
+        return;
+    }
+    cfx_scalars sc{};
+    if (be.cfx_get_scalars(dev, &sc) != CFX_OK) fail("cfx_get_scalars");
+    std::vector<int32_t> drv;
+    std::vector<double> dis, speed;
+    cfx_vehicle_view v{};
+    for (int cap = (int) sc.active_vehicle_count + 16;;) {
+        drv.resize((size_t) cap);
+        dis.resize((size_t) cap);
+        speed.resize((size_t) cap);
+        v = cfx_vehicle_view{};
+        v.capacity = cap;
+        v.drivable = drv.data();
+        v.dis = dis.data();
+        v.speed = speed.data();
+        const int32_t rc = be.cfx_get_vehicles(dev, &v);
+        if (rc == CFX_ERR_CAPACITY && v.count > cap) {
+            cap = v.count + 16;
+            continue;
+        }
+        if (rc != CFX_OK) fail("cfx_get_vehicles");
+        break;
+    }
+    laneFeaturesFromView(nLanes, lanesPerEnv, v.count, drv.data(), dis.data(), speed.data(), speedSum, bins, edges, nBins,
+                         perLaneEdges);
 }
 
 std::vector<int32_t> EngineHost::phaseCounts() const {

@@ -80,6 +80,10 @@ struct Backend {
     cfx_set_tl_phases_device_fn cfx_set_tl_phases_device = nullptr;
     cfx_device_error_fn cfx_device_error = nullptr;
     bool hasDeviceBuffers() const { return cfx_stream_handle && cfx_observe_device && cfx_set_tl_phases_device && cfx_device_error; }
+    // optional: per-lane speed and position features (without them the host computes the arrays from cfx_get_vehicles)
+    cfx_observe_lanes_device_fn cfx_observe_lanes_device = nullptr;
+    cfx_get_lane_features_fn cfx_get_lane_features = nullptr;
+    bool hasLaneFeatures() const { return cfx_observe_lanes_device && cfx_get_lane_features; }
     void open(const std::string &libPath);  // throws std::runtime_error
     ~Backend();
 };
@@ -162,6 +166,13 @@ public:
     void setTrafficLightPhasesDevice(uintptr_t phases, size_t n, uintptr_t producerStream);
     bool rlTrafficLight() const { return rlTrafficLight_; }
     std::vector<int32_t> phaseCounts() const;  // [n_intersections] phases per intersection, -1 for virtual ones
+    // ---- per-lane speed and position features (cfx_observe_lanes_device / cfx_get_lane_features; the twin: from the vehicles)
+    bool laneFeaturesOnDevice() const { return be_.hasDeviceBuffers() && be_.hasLaneFeatures(); }
+    std::vector<double> laneLengths() const;  // [n_lanes] Lane::getLength
+    // speedSum [n_lanes], bins [n_lanes * nBins] (either may be null), edges: [n_lanes][nBins + 1] or [nBins + 1]
+    void laneFeatures(double *speedSum, int32_t *bins, const double *edges, int nBins, bool perLaneEdges);
+    void observeLanesDevice(uintptr_t counts, uintptr_t waiting, uintptr_t speedSum, uintptr_t bins, uintptr_t edges, int nBins,
+                            bool perLaneEdges, uintptr_t consumerStream);
     // Lane::history as the device keeps it ("cfx": {"laneHistory": true}; cfx_get_lane_history): lane-major, oldest record first
     void laneHistory(std::vector<int32_t> &len, std::vector<int32_t> &vehicleNum, std::vector<double> &averageSpeed,
                      std::vector<int32_t> &historyVehicleNum, std::vector<double> &historyAverageSpeed);
@@ -289,5 +300,15 @@ struct EngineConfig {  // Engine::loadConfig engine.cpp:37-84
 EngineConfig readEngineConfig(const std::string &configFile);  // throws std::runtime_error("load config failed! ...")
 
 std::string defaultBackendPath();  // <dir of this shared object>/lib/libcfx_hip.so
+
+// Per-lane speed sum and position bins (cfx_get_lane_features's semantics) of every lane, on the host: from a vehicle view of
+// `count` running vehicles ordered by drivable, front to back (cfx_get_vehicles).  Lane l's edge row: l % lanesPerEnv when
+// perLaneEdges, else the one row.  Either output may be null.
+void laneFeaturesFromView(int nLanes, int lanesPerEnv, int count, const int32_t *drivable, const double *dis, const double *speed,
+                          double *speedSum, int32_t *bins, const double *edges, int nBins, bool perLaneEdges);
+// the same on any backend: cfx_get_lane_features where it exists, otherwise cfx_get_vehicles + laneFeaturesFromView
+// (throws std::runtime_error with the backend's message)
+void laneFeaturesOf(const Backend &be, cfx_engine *dev, int nLanes, int lanesPerEnv, double *speedSum, int32_t *bins,
+                    const double *edges, int nBins, bool perLaneEdges);
 
 }  // namespace cfa

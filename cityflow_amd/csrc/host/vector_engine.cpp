@@ -619,6 +619,26 @@ void VectorEngineHost::setTrafficLightPhasesDevice(uintptr_t phases, size_t n, u
     devicePhaseUnchecked_ = true;
 }
 
+std::vector<double> VectorEngineHost::laneLengths() const {
+    const cfx_net &f = net_->flat();
+    return std::vector<double>(f.drv_length, f.drv_length + f.n_lanes);
+}
+
+void VectorEngineHost::laneFeatures(double *speedSum, int32_t *bins, const double *edges, int nBins, bool perLaneEdges) {
+    std::lock_guard<std::mutex> guard(queryMutex_);  // (the ABI is not re-entrant: the ahead thread may be asking the device)
+    laneFeaturesOf(be_, dev_, R_ * L_, L_, speedSum, bins, edges, nBins, perLaneEdges);
+    raiseDeviceError();
+}
+
+void VectorEngineHost::observeLanesDevice(uintptr_t counts, uintptr_t waiting, uintptr_t speedSum, uintptr_t bins, uintptr_t edges,
+                                          int nBins, bool perLaneEdges, uintptr_t consumerStream) {
+    if (!laneFeaturesOnDevice()) throw std::runtime_error("cityflow_amd: '" + be_.path + "' has no device lane features");
+    std::lock_guard<std::mutex> guard(queryMutex_);
+    check(be_.cfx_observe_lanes_device(dev_, (int32_t *) counts, (int32_t *) waiting, (double *) speedSum, (int32_t *) bins,
+                                       (const double *) edges, nBins, perLaneEdges ? 1 : 0, (void *) consumerStream),
+          "cfx_observe_lanes_device");
+}
+
 std::vector<int32_t> VectorEngineHost::phaseCounts() const {
     std::vector<int32_t> out((size_t) I_);
     for (int i = 0; i < I_; ++i) out[(size_t) i] = net_->inters[(size_t) i].isVirtual ? -1 : (int32_t) net_->inters[(size_t) i].phases.size();

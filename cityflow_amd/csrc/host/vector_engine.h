@@ -46,6 +46,13 @@ public:
     void setTrafficLightPhasesDevice(uintptr_t phases, size_t n, uintptr_t producerStream);
     bool rlTrafficLight() const { return rlTrafficLight_; }
     std::vector<int32_t> phaseCounts() const;  // [I] phases per intersection of one environment, -1 for virtual ones
+    // per-lane speed and position features over every environment (EngineHost::laneFeatures and its kin): outputs [R * L] /
+    // [R * L * nBins], edges [L][nBins + 1] or [nBins + 1], shared by the environments
+    bool laneFeaturesOnDevice() const { return be_.hasDeviceBuffers() && be_.hasLaneFeatures(); }
+    std::vector<double> laneLengths() const;  // [L] of one environment
+    void laneFeatures(double *speedSum, int32_t *bins, const double *edges, int nBins, bool perLaneEdges);
+    void observeLanesDevice(uintptr_t counts, uintptr_t waiting, uintptr_t speedSum, uintptr_t bins, uintptr_t edges, int nBins,
+                            bool perLaneEdges, uintptr_t consumerStream);
     std::vector<std::string> laneIds() const;
     std::vector<std::string> intersectionIds() const;
     cfx_scalars scalars();

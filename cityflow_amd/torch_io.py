@@ -3,6 +3,10 @@
     eng.get_lane_vehicle_count_tensor(out=None)          int32 [L]   (VectorEngine: [R, L])
     eng.get_lane_waiting_vehicle_count_tensor(out=None)  int32 [L]   (VectorEngine: [R, L])
     eng.set_tl_phases_tensor(phases)                     integer [I] (VectorEngine: [R, I])
+    eng.get_lane_speed_sum_tensor(out=None)              float64 [L] (VectorEngine: [R, L])
+    eng.get_lane_vehicle_bins_tensor(edges, out=None)    int32 [L, B] (VectorEngine: [R, L, B])
+    eng.observe_lanes_tensor(counts=None, waiting=None, speed_sum=None, bins=None, edges=None)
+                                                         fills every given tensor with one kernel launch
 
 On the HIP engine the tensors live on the engine's GPU and nothing here waits for the device:
   * a getter's kernel writes the caller's tensor on the engine's stream after everything already enqueued there and on the
@@ -126,8 +130,113 @@ def set_tl_phases_tensor(self, phases):
     self._set_tl_phases_device(p.data_ptr(), p.numel(), torch.cuda.current_stream(device).cuda_stream)
 
 
+MAX_BINS = 32  # CFX_MAX_LANE_BINS
+
+
+def _engine_device(torch, eng):
+    return torch.device("cuda", eng._stream_handle()[1]) if eng._device_buffers() else torch.device("cpu")
+
+
+def _check_buf(torch, t, name, shape, dtype, device):
+    if not isinstance(t, torch.Tensor):
+        raise TypeError("%s must be a torch.Tensor, not %s" % (name, type(t).__name__))
+    if t.device != device:
+        raise TypeError("%s is on %s; this engine's tensors live on %s" % (name, t.device, device))
+    if t.dtype != dtype:
+        raise TypeError("%s must be %s, not %s" % (name, dtype, t.dtype))
+    if tuple(t.shape) != shape:
+        raise ValueError("%s must have shape %s, not %s" % (name, shape, tuple(t.shape)))
+    if not t.is_contiguous():
+        raise ValueError("%s must be contiguous" % name)
+
+
+def _check_edges(torch, edges, n_lanes, device):
+    """-> (float64 contiguous edges, B, per_lane).  edges: [L, B+1] (a row per lane) or [B+1] (shared), 1 <= B <= 32."""
+    if not isinstance(edges, torch.Tensor):
+        raise TypeError("edges must be a torch.Tensor, not %s" % type(edges).__name__)
+    if edges.device != device:
+        raise TypeError("edges is on %s; this engine's tensors live on %s" % (edges.device, device))
+    if not edges.is_floating_point():
+        raise TypeError("edges must be a floating tensor, not %s" % edges.dtype)
+    if edges.dim() == 1:
+        per_lane = False
+    elif edges.dim() == 2 and edges.shape[0] == n_lanes:
+        per_lane = True
+    else:
+        raise ValueError("edges must have shape [B+1] or [%d, B+1], not %s" % (n_lanes, tuple(edges.shape)))
+    n_bins = edges.shape[-1] - 1
+    if not 1 <= n_bins <= MAX_BINS:
+        raise ValueError("edges must give 1 to %d bins (B+1 edges), not %d" % (MAX_BINS, n_bins))
+    return edges.to(torch.float64).contiguous(), n_bins, per_lane
+
+
+def observe_lanes_tensor(self, counts=None, waiting=None, speed_sum=None, bins=None, edges=None):
+    """Fill every given tensor with one kernel launch on the engine's stream, ordered against the current torch stream:
+    counts / waiting (int32 [L], as get_lane_vehicle_count_tensor / get_lane_waiting_vehicle_count_tensor), speed_sum
+    (float64 [L], as get_lane_speed_sum_tensor) and bins (int32 [L, B], as get_lane_vehicle_bins_tensor, with `edges`).
+    VectorEngine: a leading [R] on every output.  At least one output; every argument is checked before anything is enqueued."""
+    torch = _torch()
+    shape = tuple(self._tensor_shapes()[0])
+    if counts is None and waiting is None and speed_sum is None and bins is None:
+        raise ValueError("observe_lanes_tensor: give at least one of counts, waiting, speed_sum, bins")
+    if bins is not None and edges is None:
+        raise ValueError("observe_lanes_tensor: bins requires edges")
+    device = _engine_device(torch, self)
+    n_bins, per_lane = 0, False
+    if edges is not None:
+        edges, n_bins, per_lane = _check_edges(torch, edges, shape[-1], device)
+    if counts is not None:
+        _check_buf(torch, counts, "counts", shape, torch.int32, device)
+    if waiting is not None:
+        _check_buf(torch, waiting, "waiting", shape, torch.int32, device)
+    if speed_sum is not None:
+        _check_buf(torch, speed_sum, "speed_sum", shape, torch.float64, device)
+    if bins is not None:
+        _check_buf(torch, bins, "bins", shape + (n_bins,), torch.int32, device)
+    if not self._device_buffers():  # (the twin: over the array calls)
+        if counts is not None:
+            counts.copy_(torch.from_numpy(self.get_lane_vehicle_count_array().reshape(shape)))
+        if waiting is not None:
+            waiting.copy_(torch.from_numpy(self.get_lane_waiting_vehicle_count_array().reshape(shape)))
+        if speed_sum is not None:
+            speed_sum.copy_(torch.from_numpy(self.get_lane_speed_sum_array()))
+        if bins is not None:
+            bins.copy_(torch.from_numpy(self.get_lane_vehicle_bins_array(edges.detach().numpy())))
+        return
+    ptr = lambda t: 0 if t is None else t.data_ptr()  # noqa: E731
+    self._observe_lanes_device(ptr(counts), ptr(waiting), ptr(speed_sum), ptr(bins), ptr(edges) if bins is not None else 0,
+                               n_bins, per_lane, torch.cuda.current_stream(device).cuda_stream)
+
+
+def get_lane_speed_sum_tensor(self, out=None):
+    """Sum of the speeds of every lane's vehicles, front to back (mean speed = sum / count), as a float64 tensor on the
+    engine's device, valid on the current torch stream; `out`: a contiguous float64 tensor of that shape, filled in place."""
+    torch = _torch()
+    if out is None:
+        out = torch.empty(tuple(self._tensor_shapes()[0]), dtype=torch.float64, device=_engine_device(torch, self))
+    observe_lanes_tensor(self, speed_sum=out)
+    return out
+
+
+def get_lane_vehicle_bins_tensor(self, edges, out=None):
+    """Vehicles of every lane with edges[l, b] <= distance < edges[l, b+1] (distance from the lane's start, as
+    get_vehicle_distance), as an int32 tensor [L, B] on the engine's device; `edges`: a floating tensor [L, B+1] or [B+1] on
+    that device, 1 <= B <= 32 (VectorEngine: the same edges for every environment)."""
+    torch = _torch()
+    if out is None:
+        shape = tuple(self._tensor_shapes()[0])
+        device = _engine_device(torch, self)
+        _, n_bins, _ = _check_edges(torch, edges, shape[-1], device)
+        out = torch.empty(shape + (n_bins,), dtype=torch.int32, device=device)
+    observe_lanes_tensor(self, bins=out, edges=edges)
+    return out
+
+
 def install(*classes):
     for cls in classes:
         cls.get_lane_vehicle_count_tensor = get_lane_vehicle_count_tensor
         cls.get_lane_waiting_vehicle_count_tensor = get_lane_waiting_vehicle_count_tensor
         cls.set_tl_phases_tensor = set_tl_phases_tensor
+        cls.get_lane_speed_sum_tensor = get_lane_speed_sum_tensor
+        cls.get_lane_vehicle_bins_tensor = get_lane_vehicle_bins_tensor
+        cls.observe_lanes_tensor = observe_lanes_tensor

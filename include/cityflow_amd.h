@@ -526,6 +526,23 @@ typedef int32_t (*cfx_observe_device_fn)(cfx_engine *e, int32_t *counts, int32_t
 typedef int32_t (*cfx_set_tl_phases_device_fn)(cfx_engine *e, const int32_t *phases, int32_t n, void *producer_stream);
 typedef int32_t (*cfx_device_error_fn)(cfx_engine *e, int32_t *inter, int32_t *phase);
 
+/* ---- Per-lane speed and position features (OPTIONAL entry points, as above).  The population of lane l is the vehicles on it,
+ * front to back, as cfx_get_lane_counts counts them (lane-change shadows included; vehicles on laneLinks belong to no lane).
+ *   speed_sum[l]     double: 0.0 + v0 + v1 + ... summed front to back (Lane::updateHistory's curSpeedSum)
+ *   bins[l * n + b]  int32: vehicles with edges[row, b] <= dis < edges[row, b + 1], every bin on its own (an inverted or a NaN
+ *                    edge counts nothing); 1 <= n_bins <= 32.  per_lane_edges = 0: edges[n_bins + 1], the same for every lane;
+ *                    1: edges[lanes per environment][n_bins + 1], row l % (n_lanes / n_envs) for lane l (cfx_config::n_envs)
+ *   "cfx_observe_lanes_device"  counts / waiting (as cfx_observe_device), speed_sum and bins in device memory, any of them NULL
+ *                               (at least one given; bins needs edges, in device memory too), written by ONE kernel on the
+ *                               engine's stream, ordered against consumer_stream as cfx_observe_device.
+ *   "cfx_get_lane_features"     speed_sum and / or bins into host memory, edges read from host memory; synchronous (engine-owned
+ *                               device scratch, kept between calls; only [n_lanes] / [n_lanes * n_bins] is copied back). */
+typedef int32_t (*cfx_observe_lanes_device_fn)(cfx_engine *e, int32_t *counts, int32_t *waiting, double *speed_sum, int32_t *bins,
+                                               const double *edges, int32_t n_bins, int32_t per_lane_edges, void *consumer_stream);
+typedef int32_t (*cfx_get_lane_features_fn)(cfx_engine *e, double *speed_sum, int32_t *bins, const double *edges, int32_t n_bins,
+                                            int32_t per_lane_edges);
+#define CFX_MAX_LANE_BINS 32
+
 #ifdef __cplusplus
 }
 #endif

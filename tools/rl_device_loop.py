@@ -1,7 +1,10 @@
 """RL loop with a torch policy on the GPU: the numpy calls (observation to the host and into torch, phases back through the
 host) against the tensor calls (get_lane_*_tensor / set_tl_phases_tensor: no host wait).  us per iteration, on the headline
 RL network (bench.py's 30x30 workload, rlTrafficLight) and on VectorEngine 16 x the same.
-usage: python tools/rl_device_loop.py [--iters N] [--envs R]      (the probe tools/rl_probe.py is the numpy side's own story)"""
+usage: python tools/rl_device_loop.py [--iters N] [--envs R]      (the probe tools/rl_probe.py is the numpy side's own story)
+       python tools/rl_device_loop.py --features [--features-only all|counts_waiting]
+--features: observe_lanes_tensor (one launch of kr_lane_features) against the two count getters, on the Engine only;
+--features-only runs just that observe_lanes_tensor loop (with all four outputs, B = 3, or counts + waiting), for a kernel trace."""
 import argparse
 import os
 import sys
@@ -15,6 +18,8 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--iters", type=int, default=400)
 ap.add_argument("--envs", type=int, default=16)
 ap.add_argument("--skip-vector", action="store_true")
+ap.add_argument("--features", action="store_true")
+ap.add_argument("--features-only", choices=["all", "counts_waiting"], default=None)
 args = ap.parse_args()
 sys.argv = [sys.argv[0]]
 import bench  # noqa: E402
@@ -87,6 +92,63 @@ def loops(name, eng, n):
     measure("torch policy alone", eng, lambda s: policy(out_c, out_w, s), n)
     print("%-66s %8.2fx" % ("numpy loop / tensor loop", a / b), flush=True)
 
+
+def features(name, eng, n, only):
+    device = torch.device("cuda", eng._stream_handle()[1])
+    n_phases = torch.from_numpy(eng._phase_counts()).to(device).long()
+    npos = torch.clamp(n_phases, min=1)
+    L = len(eng.lane_ids())
+    idx = (torch.arange(n_phases.shape[0], device=device) * 7) % L
+    edges = torch.from_numpy(eng.lane_lengths()[:, None] * np.array([0.0, 1.0 / 3.0, 2.0 / 3.0, np.inf])).to(device)
+
+    def policy(c, w, s):  # as loops(): the same few eager ops whichever call produced c and w
+        return torch.where(n_phases >= 0, (c[idx].long() + w[idx].long() + s) % npos, -1)
+
+    out_c = torch.empty(L, dtype=torch.int32, device=device)
+    out_w = torch.empty(L, dtype=torch.int32, device=device)
+    out_s = torch.empty(L, dtype=torch.float64, device=device)
+    out_b = torch.empty((L, 3), dtype=torch.int32, device=device)
+
+    def obs_cw():
+        eng.observe_lanes_tensor(counts=out_c, waiting=out_w)
+
+    def obs_all():
+        eng.observe_lanes_tensor(counts=out_c, waiting=out_w, speed_sum=out_s, bins=out_b, edges=edges)
+
+    def getters():
+        eng.get_lane_vehicle_count_tensor(out=out_c)
+        eng.get_lane_waiting_vehicle_count_tensor(out=out_w)
+
+    def loop(observe):
+        def body(s):
+            observe()
+            eng.set_tl_phases_tensor(policy(out_c, out_w, s))
+            eng.next_step()
+        return body
+
+    for _ in range(300):
+        eng.next_step()
+    eng.sync()
+    print("# %s" % name, flush=True)
+    if only:
+        measure("observe_lanes_tensor loop, outputs: %s" % only, eng, loop(obs_all if only == "all" else obs_cw), n)
+        return
+    measure("next_step alone", eng, lambda s: eng.next_step(), n)
+    a = measure("2 count getters -> torch policy -> set_tl_phases_tensor -> next_step", eng, loop(getters), n)
+    b = measure("observe_lanes_tensor(counts, waiting) -> policy -> set -> next_step", eng, loop(obs_cw), n)
+    c = measure("observe_lanes_tensor(all four, B=3) -> policy -> set -> next_step", eng, loop(obs_all), n)
+    measure("2 count getters alone (2 launches + events, no step)", eng, lambda s: getters(), n)
+    measure("observe_lanes_tensor(counts, waiting) alone (1 launch + events)", eng, lambda s: obs_cw(), n)
+    measure("observe_lanes_tensor(all four, B=3) alone (1 launch + events)", eng, lambda s: obs_all(), n)
+    print("%-66s %8.2fx" % ("2 getters loop / observe_lanes_tensor(counts, waiting) loop", a / b), flush=True)
+    print("%-66s %8.2fx" % ("2 getters loop / observe_lanes_tensor(all four) loop", a / c), flush=True)
+
+
+if args.features or args.features_only:
+    e = _cityflow.Engine(cfg, 1)
+    features("Engine, 30x30 RL workload (%d signals, %d lanes)" % (len(e.intersection_ids()), len(e.lane_ids())), e, args.iters,
+             args.features_only)
+    sys.exit(0)
 
 e = _cityflow.Engine(cfg, 1)
 loops("Engine, 30x30 RL workload (%d signals, %d lanes)" % (len(e.intersection_ids()), len(e.lane_ids())), e, args.iters)
