@@ -133,7 +133,7 @@ struct cfx_engine {
     int observeIdle = 0;
     static constexpr int kObserveIdle = 8;
     int32_t *publishTo() const { return (observing && hCntValid && !tiled) ? hCnt : nullptr; }
-    // cfx_observe_device / cfx_set_tl_phases_device (observations and signals in the caller's device buffers, ordered against
+    // cfx_observe_lanes_device / cfx_set_tl_phases_device (observations and signals in the caller's device buffers, ordered against
     // the caller's stream with these events).  `devObserving`: someone observes on the device after every step, so the step
     // does not defer its commit (the observation would launch it anyway); dropped after kObserveIdle steps without one.
     hipEvent_t devInEvent = nullptr, devOutEvent = nullptr;
@@ -342,6 +342,23 @@ struct cfx_engine {
     int fail(const std::string &m) {
         err = m;
         return CFX_ERR_DEVICE;
+    }
+
+    // Device buffers of a caller that works on a stream of its own (cfx_observe_lanes_device / cfx_set_tl_phases_device), around
+    // the engine's kernel.  Before it: the engine's stream waits for what the caller has enqueued so far — an output may still
+    // be read there (a reused tensor), an input is still being produced there.  After it: the caller's stream waits for the
+    // kernel, so what is enqueued there next sees the outputs, and may free or overwrite an input the kernel has read.
+    int orderAfterCaller(hipStream_t caller) {
+        if (caller == stream) return CFX_OK;
+        HIP_TRY(hipEventRecord(devInEvent, caller));
+        HIP_TRY(hipStreamWaitEvent(stream, devInEvent, 0));
+        return CFX_OK;
+    }
+    int orderCallerAfter(hipStream_t caller) {
+        if (caller == stream) return CFX_OK;
+        HIP_TRY(hipEventRecord(devOutEvent, stream));
+        HIP_TRY(hipStreamWaitEvent(caller, devOutEvent, 0));
+        return CFX_OK;
     }
 
     template <typename T> int allocRaw(T **p, size_t n) {
@@ -2092,6 +2109,13 @@ int32_t cfx_get_lane_counts(cfx_engine *e, int32_t *out) {
     return CFX_OK;
 }
 
+// the one walk over a lane's vehicles (laneFeatures, cfx_kernels.h): a group of kFeatGroup threads per lane
+static void launchLaneFeatures(cfx_engine *e, const LaneFeatOut &o) {
+    const size_t threads = (size_t) e->L * kFeatGroup;
+    if (e->ring) hipLaunchKernelGGL(kr_lane_features, dim3(gridFor(threads)), dim3(kBlock), 0, e->stream, e->rctx(), o);
+    else hipLaunchKernelGGL(kd_lane_features, dim3(gridFor(threads)), dim3(kBlock), 0, e->stream, e->ctx(), o);
+}
+
 int32_t cfx_get_lane_waiting_counts(cfx_engine *e, int32_t *out) {
     if (!e || !out) return CFX_ERR_INVALID;
     auto fail = [e](const std::string &m) { return e->fail(m); };
@@ -2100,8 +2124,9 @@ int32_t cfx_get_lane_waiting_counts(cfx_engine *e, int32_t *out) {
     int rc;
     if ((rc = e->syncTables())) return rc;
     if (e->ring && (rc = e->ringEnsure())) return rc;
-    if (e->ring) hipLaunchKernelGGL(kr_lane_waiting, dim3(gridFor(e->L)), dim3(kBlock), 0, e->stream, e->rctx(), e->laneOut);
-    else hipLaunchKernelGGL(k_lane_waiting, dim3(gridFor(e->L)), dim3(kBlock), 0, e->stream, e->ctx(), e->laneOut);
+    LaneFeatOut o{};
+    o.waiting = e->laneOut;
+    launchLaneFeatures(e, o);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(e->hLaneOut, e->laneOut, e->L * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
@@ -3166,33 +3191,6 @@ int32_t cfx_stream_handle(cfx_engine *e, void **stream, int32_t *device) {
     return CFX_OK;
 }
 
-int32_t cfx_observe_device(cfx_engine *e, int32_t *counts, int32_t *waiting, void *consumerStream) {
-    if (!e || (!counts && !waiting)) return CFX_ERR_INVALID;
-    auto fail = [e](const std::string &m) { return e->fail(m); };
-    HIP_TRY(hipSetDevice(e->device));
-    int rc;
-    if (counts && (rc = checkDevicePointer(e, counts, "cfx_observe_device: counts"))) return rc;
-    if (waiting && (rc = checkDevicePointer(e, waiting, "cfx_observe_device: waiting"))) return rc;
-    if ((rc = e->settle(false))) return rc;  // (ring layout: a commit deferred to the next step's admission; Lane::history is not read here)
-    if ((rc = e->syncTables())) return rc;
-    if (e->ring && (rc = e->ringEnsure())) return rc;
-    const hipStream_t cs = (hipStream_t) consumerStream;
-    if (cs != e->stream) {  // the buffers may still be read by what the caller enqueued before (a reused output)
-        HIP_TRY(hipEventRecord(e->devInEvent, cs));
-        HIP_TRY(hipStreamWaitEvent(e->stream, e->devInEvent, 0));
-    }
-    if (e->ring) hipLaunchKernelGGL(kr_observe, dim3(gridFor(e->L)), dim3(kBlock), 0, e->stream, e->rctx(), counts, waiting);
-    else hipLaunchKernelGGL(kd_observe, dim3(gridFor(e->L)), dim3(kBlock), 0, e->stream, e->ctx(), counts, waiting);
-    HIP_TRY(hipGetLastError());
-    if (cs != e->stream) {
-        HIP_TRY(hipEventRecord(e->devOutEvent, e->stream));
-        HIP_TRY(hipStreamWaitEvent(cs, e->devOutEvent, 0));
-    }
-    e->devObserving = !e->tiled;
-    e->devObserveIdle = 0;
-    return CFX_OK;
-}
-
 int32_t cfx_set_tl_phases_device(cfx_engine *e, const int32_t *phases, int32_t n, void *producerStream) {
     if (!e || !phases || n != e->I) return CFX_ERR_INVALID;
     auto fail = [e](const std::string &m) { return e->fail(m); };
@@ -3200,19 +3198,11 @@ int32_t cfx_set_tl_phases_device(cfx_engine *e, const int32_t *phases, int32_t n
     int rc;
     if ((rc = checkDevicePointer(e, phases, "cfx_set_tl_phases_device: phases"))) return rc;
     if ((rc = e->settle(false))) return rc;  // (as cfx_set_tl_phases: the deferred commit advances the lights of the last step first)
-    const hipStream_t ps = (hipStream_t) producerStream;
-    if (ps != e->stream) {
-        HIP_TRY(hipEventRecord(e->devInEvent, ps));
-        HIP_TRY(hipStreamWaitEvent(e->stream, e->devInEvent, 0));
-    }
+    if ((rc = e->orderAfterCaller((hipStream_t) producerStream))) return rc;
     hipLaunchKernelGGL(k_set_phases_dense, dim3(1), dim3(1024), 0, e->stream, phases, n, e->net.interPhaseStart,
                        e->net.interVirtual, e->curPhase, e->hPhaseErr);
     HIP_TRY(hipGetLastError());
-    if (ps != e->stream) {  // (the caller's stream may free or overwrite `phases` once the kernel has read it)
-        HIP_TRY(hipEventRecord(e->devOutEvent, e->stream));
-        HIP_TRY(hipStreamWaitEvent(ps, e->devOutEvent, 0));
-    }
-    return CFX_OK;
+    return e->orderCallerAfter((hipStream_t) producerStream);
 }
 
 int32_t cfx_device_error(cfx_engine *e, int32_t *inter, int32_t *phase) {
@@ -3252,12 +3242,6 @@ static LaneFeatOut laneFeatOut(const cfx_engine *e, int32_t *counts, int32_t *wa
     return o;
 }
 
-static void launchLaneFeatures(cfx_engine *e, const LaneFeatOut &o) {
-    const size_t threads = (size_t) e->L * kFeatGroup;
-    if (e->ring) hipLaunchKernelGGL(kr_lane_features, dim3(gridFor(threads)), dim3(kBlock), 0, e->stream, e->rctx(), o);
-    else hipLaunchKernelGGL(kd_lane_features, dim3(gridFor(threads)), dim3(kBlock), 0, e->stream, e->ctx(), o);
-}
-
 int32_t cfx_observe_lanes_device(cfx_engine *e, int32_t *counts, int32_t *waiting, double *speedSum, int32_t *bins,
                                  const double *edges, int32_t nBins, int32_t perLaneEdges, void *consumerStream) {
     if (!e || (!counts && !waiting && !speedSum && !bins)) return CFX_ERR_INVALID;
@@ -3273,20 +3257,19 @@ int32_t cfx_observe_lanes_device(cfx_engine *e, int32_t *counts, int32_t *waitin
     if ((rc = e->settle(false))) return rc;  // (ring layout: a commit deferred to the next step's admission; Lane::history is not read here)
     if ((rc = e->syncTables())) return rc;
     if (e->ring && (rc = e->ringEnsure())) return rc;
-    const hipStream_t cs = (hipStream_t) consumerStream;
-    if (cs != e->stream) {  // the buffers may still be read by what the caller enqueued before (a reused output)
-        HIP_TRY(hipEventRecord(e->devInEvent, cs));
-        HIP_TRY(hipStreamWaitEvent(e->stream, e->devInEvent, 0));
-    }
+    if ((rc = e->orderAfterCaller((hipStream_t) consumerStream))) return rc;
     launchLaneFeatures(e, laneFeatOut(e, counts, waiting, speedSum, bins, edges, nBins, perLaneEdges));
     HIP_TRY(hipGetLastError());
-    if (cs != e->stream) {
-        HIP_TRY(hipEventRecord(e->devOutEvent, e->stream));
-        HIP_TRY(hipStreamWaitEvent(cs, e->devOutEvent, 0));
-    }
+    if ((rc = e->orderCallerAfter((hipStream_t) consumerStream))) return rc;
     e->devObserving = !e->tiled;
     e->devObserveIdle = 0;
     return CFX_OK;
+}
+
+// (the two counts alone: cfx_observe_lanes_device with the other outputs null)
+int32_t cfx_observe_device(cfx_engine *e, int32_t *counts, int32_t *waiting, void *consumerStream) {
+    if (!e || (!counts && !waiting)) return CFX_ERR_INVALID;
+    return cfx_observe_lanes_device(e, counts, waiting, nullptr, nullptr, nullptr, 0, 0, consumerStream);
 }
 
 int32_t cfx_get_lane_features(cfx_engine *e, double *speedSum, int32_t *bins, const double *edges, int32_t nBins,

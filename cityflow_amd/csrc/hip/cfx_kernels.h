@@ -2212,28 +2212,6 @@ __global__ void k_lane_history(StepCtx c, LaneHistDev h) {
     laneHistoryStep(h, lane, cntNow(c, lane), [&](int i) { return c.s.speed[base + i]; });
 }
 
-__global__ void k_lane_waiting(StepCtx c, int32_t *out) {  // Engine::getLaneWaitingVehicleCount engine.cpp:636-648
-    int lane = blockIdx.x * blockDim.x + threadIdx.x;
-    if (lane >= c.n.L) return;
-    int base = c.segStart[lane], n = c.cnt[lane], k = 0;
-    for (int i = 0; i < n; ++i) k += c.s.speed[base + i] < 0.1;
-    out[lane] = k;
-}
-
-// cfx_observe_device, dense layout: both per-lane observations in one launch, straight into the caller's device buffers (either
-// may be null) — the counts of cfx_get_lane_counts, the walk of k_lane_waiting
-__global__ void kd_observe(StepCtx c, int32_t *counts, int32_t *waiting) {
-    const int lane = blockIdx.x * blockDim.x + threadIdx.x;
-    if (lane >= c.n.L) return;
-    const int base = c.segStart[lane], n = c.cnt[lane];
-    if (counts) counts[lane] = n;
-    if (waiting) {
-        int k = 0;
-        for (int i = 0; i < n; ++i) k += c.s.speed[base + i] < 0.1;
-        waiting[lane] = k;
-    }
-}
-
 // cfx_observe_lanes_device / cfx_get_lane_features: every per-lane observation in one launch (any pointer may be null).  A GROUP of
 // kFeatGroup threads reads one lane: its records are contiguous, so one chunk of 16 vehicles is one set of neighbouring loads
 // instead of a serial walk.  Integers (waiting, bins) are counted per thread; the speed sum must be added front to back, so
@@ -2272,7 +2250,8 @@ __device__ __forceinline__ void laneFeatures(const LaneFeatOut &o, int lane, int
     }
     int w = 0, b0 = 0, b1 = 0;
     double sum = 0.0;
-    for (int first = 0; first < n; first += kFeatGroup) {  // (the trip count is the group's: n is the same in all its threads)
+    const int walk = (o.waiting || staged) ? n : 0;  // (counts alone are a copy of cnt: no record is loaded)
+    for (int first = 0; first < walk; first += kFeatGroup) {  // (the trip count is the group's: n is the same in all its threads)
         double2 r = make_double2(0.0, 0.0);
         if (first + sub < n) {
             r = rec(first + sub);

@@ -2339,34 +2339,8 @@ __global__ void kr_reset(int D, int32_t *head, int32_t *cnt, int4 *scratch) {
 // Lane::history of the last committed step as a launch of its own (the action launch of the NEXT step takes it otherwise: RingHist)
 __global__ void kr_lane_history(RingCtx c, LaneHistDev h) { ringLaneHistory(c, h, blockIdx.x * blockDim.x + threadIdx.x); }
 
-__global__ void kr_lane_waiting(RingCtx c, int32_t *out) {  // Engine::getLaneWaitingVehicleCount engine.cpp:636-648
-    const int lane = blockIdx.x * blockDim.x + threadIdx.x;
-    if (lane >= c.n.L) return;
-    const int2 geo = c.ringGeo[lane];
-    const int head = c.head[lane], n = c.cnt[lane];
-    int k = 0;
-    for (int i = 0; i < n; ++i) k += c.kin[ringSlot(geo, head, i)].y < 0.1;
-    out[lane] = k;
-}
-
-// cfx_observe_device, ring layout: the counts of cfx_get_lane_counts (rCnt) and the walk of kr_lane_waiting in one launch, straight
-// into the caller's device buffers (either may be null)
-__global__ void kr_observe(RingCtx c, int32_t *counts, int32_t *waiting) {
-    const int lane = blockIdx.x * blockDim.x + threadIdx.x;
-    if (lane >= c.n.L) return;
-    const int n = c.cnt[lane];
-    if (counts) counts[lane] = n;
-    if (waiting) {
-        const int2 geo = c.ringGeo[lane];
-        const int head = c.head[lane];
-        int k = 0;
-        for (int i = 0; i < n; ++i) k += c.kin[ringSlot(geo, head, i)].y < 0.1;
-        waiting[lane] = k;
-    }
-}
-
 // cfx_observe_lanes_device / cfx_get_lane_features, ring layout: laneFeatures (cfx_kernels.h) over the lane's ring, front to
-// back from `head`, reading the {dis, speed} record kr_observe reads
+// back from `head`, over the {dis, speed} records
 __global__ void __launch_bounds__(kBlock) kr_lane_features(RingCtx c, LaneFeatOut o) {
     __shared__ double2 stage[kBlock];
     const int lane = (int) ((blockIdx.x * (size_t) blockDim.x + threadIdx.x) / kFeatGroup);

@@ -89,7 +89,6 @@ void Backend::open(const std::string &libPath) {
 #undef CFX_FN
 #define CFX_FN_OPTIONAL(name) name = reinterpret_cast<decltype(name)>(dlsym(handle, #name));
     CFX_FN_OPTIONAL(cfx_stream_handle)
-    CFX_FN_OPTIONAL(cfx_observe_device)
     CFX_FN_OPTIONAL(cfx_set_tl_phases_device)
     CFX_FN_OPTIONAL(cfx_device_error)
     CFX_FN_OPTIONAL(cfx_observe_lanes_device)
@@ -456,10 +455,6 @@ std::pair<uintptr_t, int> EngineHost::streamHandle() {
     return {(uintptr_t) st, (int) dev};
 }
 
-void EngineHost::observeDevice(uintptr_t counts, uintptr_t waiting, uintptr_t consumerStream) {
-    check(be_.cfx_observe_device(dev_, (int32_t *) counts, (int32_t *) waiting, (void *) consumerStream), "cfx_observe_device");
-}
-
 // (the host's own record of the lights is forgotten: what the device holds now depends on numbers the host never sees)
 void EngineHost::setTrafficLightPhasesDevice(uintptr_t phases, size_t n, uintptr_t producerStream) {
     if (!rlTrafficLight_) {
@@ -488,7 +483,7 @@ void EngineHost::laneFeatures(double *speedSum, int32_t *bins, const double *edg
 
 void EngineHost::observeLanesDevice(uintptr_t counts, uintptr_t waiting, uintptr_t speedSum, uintptr_t bins, uintptr_t edges,
                                     int nBins, bool perLaneEdges, uintptr_t consumerStream) {
-    if (!laneFeaturesOnDevice()) throw std::runtime_error("cityflow_amd: '" + be_.path + "' has no device lane features");
+    if (!be_.hasDeviceBuffers()) throw std::runtime_error("cityflow_amd: '" + be_.path + "' has no device buffers");
     check(be_.cfx_observe_lanes_device(dev_, (int32_t *) counts, (int32_t *) waiting, (double *) speedSum, (int32_t *) bins,
                                        (const double *) edges, nBins, perLaneEdges ? 1 : 0, (void *) consumerStream),
           "cfx_observe_lanes_device");

@@ -76,14 +76,14 @@ struct Backend {
 #undef CFX_FN
     // optional (looked up without requiring them): observations and signals in device memory
     cfx_stream_handle_fn cfx_stream_handle = nullptr;
-    cfx_observe_device_fn cfx_observe_device = nullptr;
+    cfx_observe_lanes_device_fn cfx_observe_lanes_device = nullptr;
     cfx_set_tl_phases_device_fn cfx_set_tl_phases_device = nullptr;
     cfx_device_error_fn cfx_device_error = nullptr;
-    bool hasDeviceBuffers() const { return cfx_stream_handle && cfx_observe_device && cfx_set_tl_phases_device && cfx_device_error; }
-    // optional: per-lane speed and position features (without them the host computes the arrays from cfx_get_vehicles)
-    cfx_observe_lanes_device_fn cfx_observe_lanes_device = nullptr;
+    bool hasDeviceBuffers() const {
+        return cfx_stream_handle && cfx_observe_lanes_device && cfx_set_tl_phases_device && cfx_device_error;
+    }
+    // optional on its own: speed sums and bins into host memory (without it the host computes them from cfx_get_vehicles)
     cfx_get_lane_features_fn cfx_get_lane_features = nullptr;
-    bool hasLaneFeatures() const { return cfx_observe_lanes_device && cfx_get_lane_features; }
     void open(const std::string &libPath);  // throws std::runtime_error
     ~Backend();
 };
@@ -158,16 +158,14 @@ public:
     void setTrafficLightPhases(const std::vector<int32_t> &phases);  // [n_intersections]; virtual ones ignored
     void setTrafficLightPhases(const int32_t *phases, size_t n);
     void trafficLightState(std::vector<int32_t> &phase, std::vector<double> &remain);
-    // ---- observations and signals in device memory (cfx_observe_device / cfx_set_tl_phases_device; the torch layer is
+    // ---- observations and signals in device memory (cfx_observe_lanes_device / cfx_set_tl_phases_device; the torch layer is
     //      cityflow_amd/torch_io.py).  Pointers are device addresses, streams hipStream_t of the engine's HIP runtime.
     bool deviceBuffers() const { return be_.hasDeviceBuffers(); }
     std::pair<uintptr_t, int> streamHandle();  // {engine's stream, its device}
-    void observeDevice(uintptr_t counts, uintptr_t waiting, uintptr_t consumerStream);
     void setTrafficLightPhasesDevice(uintptr_t phases, size_t n, uintptr_t producerStream);
     bool rlTrafficLight() const { return rlTrafficLight_; }
     std::vector<int32_t> phaseCounts() const;  // [n_intersections] phases per intersection, -1 for virtual ones
     // ---- per-lane speed and position features (cfx_observe_lanes_device / cfx_get_lane_features; the twin: from the vehicles)
-    bool laneFeaturesOnDevice() const { return be_.hasDeviceBuffers() && be_.hasLaneFeatures(); }
     std::vector<double> laneLengths() const;  // [n_lanes] Lane::getLength
     // speedSum [n_lanes], bins [n_lanes * nBins] (either may be null), edges: [n_lanes][nBins + 1] or [nBins + 1]
     void laneFeatures(double *speedSum, int32_t *bins, const double *edges, int nBins, bool perLaneEdges);

@@ -269,6 +269,18 @@ template <typename E> py::array_t<int32_t> laneBinsArray(E &e, const EdgesArray 
     return out;
 }
 
+// Device buffers: raw pointers and streams under the tensor methods of cityflow_amd/torch_io.py (Engine and VectorEngine alike)
+template <typename E> void defDeviceBuffers(py::class_<E> &c) {
+    c.def("_device_buffers", &E::deviceBuffers, "the backend takes observations / signals in device memory")
+        .def("_stream_handle", &E::streamHandle, "(engine's hipStream_t as an int, HIP device ordinal)")
+        .def("_set_tl_phases_device", &E::setTrafficLightPhasesDevice, "phases_ptr"_a, "n"_a, "producer_stream"_a)
+        .def("_rl_traffic_light", &E::rlTrafficLight)
+        .def("_phase_counts", [](E &e) { return toArray(e.phaseCounts()); }, "phases per intersection, -1 = virtual")
+        .def("lane_lengths", [](E &e) { return toArray(e.laneLengths()); }, "float64 [L]: Lane::getLength (of one environment)")
+        .def("_observe_lanes_device", &E::observeLanesDevice, "counts_ptr"_a, "waiting_ptr"_a, "speed_sum_ptr"_a, "bins_ptr"_a,
+             "edges_ptr"_a, "n_bins"_a, "per_lane_edges"_a, "consumer_stream"_a);
+}
+
 // Engine.set_tl_phase(intersection_id, phase_id) (reference src/cityflow.cpp:35, engine.cpp:719-725) as a vectorcall method of its
 // own.  An RL agent written for the reference calls it once per signal and step — 900 calls per step on the 30x30 grid — and
 // the generic binding path (argument records, a std::string per call, a std::map lookup by string comparison) costs ~0.35 us
@@ -495,27 +507,16 @@ PYBIND11_MODULE(_cityflow, m) {
              "phases"_a, "int array [len(intersection_ids())]; one asynchronous call sets every signal")
         .def("sync", &EngineHost::sync)
         .def("backend_name", &EngineHost::backendName)
-        // ---- device buffers: raw pointers and streams under the tensor methods of cityflow_amd/torch_io.py ----
-        .def("_device_buffers", &EngineHost::deviceBuffers, "the backend takes observations / signals in device memory")
-        .def("_stream_handle", &EngineHost::streamHandle, "(engine's hipStream_t as an int, HIP device ordinal)")
-        .def("_observe_device", &EngineHost::observeDevice, "counts_ptr"_a, "waiting_ptr"_a, "consumer_stream"_a)
-        .def("_set_tl_phases_device", &EngineHost::setTrafficLightPhasesDevice, "phases_ptr"_a, "n"_a, "producer_stream"_a)
-        .def("_rl_traffic_light", &EngineHost::rlTrafficLight)
-        .def("_phase_counts", [](EngineHost &e) { return toArray(e.phaseCounts()); }, "phases per intersection, -1 = virtual")
         .def("_tensor_shapes", [](EngineHost &e) {
             return py::make_tuple(py::make_tuple(e.net().lanes.size()), py::make_tuple(e.net().inters.size()));
         }, "(shape of an observation, shape of the signals)")
         // ---- per-lane speed and position features (index order == lane_ids()) ----
-        .def("lane_lengths", [](EngineHost &e) { return toArray(e.laneLengths()); }, "float64 [L]: Lane::getLength")
         .def("get_lane_speed_sum_array",
              [](EngineHost &e) { return laneSpeedSumArray(e, {(py::ssize_t) e.net().lanes.size()}); },
              "float64 [L]: the speeds of each lane's vehicles summed front to back (mean speed = sum / count)")
         .def("get_lane_vehicle_bins_array",
              [](EngineHost &e, const EdgesArray &edges) { return laneBinsArray(e, edges, {(py::ssize_t) e.net().lanes.size()}); },
              "edges"_a, "int32 [L, B]: vehicles with edges[l, b] <= distance < edges[l, b+1]; edges [L, B+1] or [B+1]")
-        .def("_lane_features_on_device", &EngineHost::laneFeaturesOnDevice)
-        .def("_observe_lanes_device", &EngineHost::observeLanesDevice, "counts_ptr"_a, "waiting_ptr"_a, "speed_sum_ptr"_a,
-             "bins_ptr"_a, "edges_ptr"_a, "n_bins"_a, "per_lane_edges"_a, "consumer_stream"_a)
         // ---- introspection used by the parity tests ----
         .def("_vehicle_state",
              [](EngineHost &e) {
@@ -638,6 +639,7 @@ PYBIND11_MODULE(_cityflow, m) {
                  return ids;
              })
         .def("_flat_net", [](EngineHost &e) { return flatNetToDict(e.net()); });
+    defDeviceBuffers(engineClass);
     {
         PyObject *descr = PyDescr_NewMethod((PyTypeObject *) engineClass.ptr(), &kEngineSetTlPhaseDef);
         if (!descr) throw py::error_already_set();
@@ -645,9 +647,11 @@ PYBIND11_MODULE(_cityflow, m) {
     }
 
     using cfa::VectorEngineHost;
-    py::class_<VectorEngineHost>(m, "VectorEngine",
-                                 "num_envs independent copies of one scenario (env e uses seed + e) advanced in lock-step by "
-                                 "one device engine; observations and actions are arrays of shape [num_envs, ...].")
+    py::class_<VectorEngineHost> vectorClass(m, "VectorEngine",
+                                             "num_envs independent copies of one scenario (env e uses seed + e) advanced in "
+                                             "lock-step by one device engine; observations and actions are arrays of shape "
+                                             "[num_envs, ...].");
+    vectorClass
         .def(py::init<const std::string &, int, int>(), "config_file"_a, "num_envs"_a, "thread_num"_a = 1)
         .def_static(
             "_with_backend",
@@ -698,16 +702,9 @@ PYBIND11_MODULE(_cityflow, m) {
                  return py::make_tuple(pa, ra);
              },
              "(current phase, remaining time), each [num_envs, num_intersections]")
-        .def("_device_buffers", &VectorEngineHost::deviceBuffers)
-        .def("_stream_handle", &VectorEngineHost::streamHandle)
-        .def("_observe_device", &VectorEngineHost::observeDevice, "counts_ptr"_a, "waiting_ptr"_a, "consumer_stream"_a)
-        .def("_set_tl_phases_device", &VectorEngineHost::setTrafficLightPhasesDevice, "phases_ptr"_a, "n"_a, "producer_stream"_a)
-        .def("_rl_traffic_light", &VectorEngineHost::rlTrafficLight)
-        .def("_phase_counts", [](VectorEngineHost &e) { return toArray(e.phaseCounts()); })
         .def("_tensor_shapes", [](VectorEngineHost &e) {
             return py::make_tuple(py::make_tuple(e.numEnvs(), e.numLanes()), py::make_tuple(e.numEnvs(), e.numIntersections()));
         })
-        .def("lane_lengths", [](VectorEngineHost &e) { return toArray(e.laneLengths()); }, "float64 [L] (one environment)")
         .def("get_lane_speed_sum_array",
              [](VectorEngineHost &e) { return laneSpeedSumArray(e, {(py::ssize_t) e.numEnvs(), (py::ssize_t) e.numLanes()}); },
              "float64 [num_envs, L]")
@@ -716,9 +713,6 @@ PYBIND11_MODULE(_cityflow, m) {
                  return laneBinsArray(e, edges, {(py::ssize_t) e.numEnvs(), (py::ssize_t) e.numLanes()});
              },
              "edges"_a, "int32 [num_envs, L, B]; edges [L, B+1] or [B+1], the same for every environment")
-        .def("_lane_features_on_device", &VectorEngineHost::laneFeaturesOnDevice)
-        .def("_observe_lanes_device", &VectorEngineHost::observeLanesDevice, "counts_ptr"_a, "waiting_ptr"_a, "speed_sum_ptr"_a,
-             "bins_ptr"_a, "edges_ptr"_a, "n_bins"_a, "per_lane_edges"_a, "consumer_stream"_a)
         .def("_profile_enable", &VectorEngineHost::profileEnable, "on"_a)
         .def("_profile_read", &VectorEngineHost::profileRead)
         .def("_scalars", [](VectorEngineHost &e) {
@@ -733,6 +727,7 @@ PYBIND11_MODULE(_cityflow, m) {
             d["cumulative_travel_time"] = s.cumulative_travel_time;
             return d;
         });
+    defDeviceBuffers(vectorClass);
 
     using cfa::TiledEngineHost;
     py::class_<TiledEngineHost>(m, "TiledEngine",

@@ -602,11 +602,6 @@ std::pair<uintptr_t, int> VectorEngineHost::streamHandle() {
     return {(uintptr_t) st, (int) dev};
 }
 
-void VectorEngineHost::observeDevice(uintptr_t counts, uintptr_t waiting, uintptr_t consumerStream) {
-    std::lock_guard<std::mutex> guard(queryMutex_);
-    check(be_.cfx_observe_device(dev_, (int32_t *) counts, (int32_t *) waiting, (void *) consumerStream), "cfx_observe_device");
-}
-
 void VectorEngineHost::setTrafficLightPhasesDevice(uintptr_t phases, size_t n, uintptr_t producerStream) {
     if (!rlTrafficLight_) {
         std::cerr << "please set rlTrafficLight to true to enable traffic light control" << std::endl;
@@ -632,7 +627,7 @@ void VectorEngineHost::laneFeatures(double *speedSum, int32_t *bins, const doubl
 
 void VectorEngineHost::observeLanesDevice(uintptr_t counts, uintptr_t waiting, uintptr_t speedSum, uintptr_t bins, uintptr_t edges,
                                           int nBins, bool perLaneEdges, uintptr_t consumerStream) {
-    if (!laneFeaturesOnDevice()) throw std::runtime_error("cityflow_amd: '" + be_.path + "' has no device lane features");
+    if (!be_.hasDeviceBuffers()) throw std::runtime_error("cityflow_amd: '" + be_.path + "' has no device buffers");
     std::lock_guard<std::mutex> guard(queryMutex_);
     check(be_.cfx_observe_lanes_device(dev_, (int32_t *) counts, (int32_t *) waiting, (double *) speedSum, (int32_t *) bins,
                                        (const double *) edges, nBins, perLaneEdges ? 1 : 0, (void *) consumerStream),

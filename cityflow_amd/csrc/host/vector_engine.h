@@ -39,16 +39,14 @@ public:
     // phases: [R * I] (entries of virtual intersections are ignored); requires rlTrafficLight
     void setTrafficLightPhases(const std::vector<int32_t> &phases);
     void trafficLightState(std::vector<int32_t> &phase, std::vector<double> &remain);  // [R * I]
-    // observations and signals in device memory, [R * L] / [R * I] (EngineHost::observeDevice and its kin)
+    // observations and signals in device memory, [R * L] / [R * I] (EngineHost::observeLanesDevice and its kin)
     bool deviceBuffers() const { return be_.hasDeviceBuffers(); }
     std::pair<uintptr_t, int> streamHandle();
-    void observeDevice(uintptr_t counts, uintptr_t waiting, uintptr_t consumerStream);
     void setTrafficLightPhasesDevice(uintptr_t phases, size_t n, uintptr_t producerStream);
     bool rlTrafficLight() const { return rlTrafficLight_; }
     std::vector<int32_t> phaseCounts() const;  // [I] phases per intersection of one environment, -1 for virtual ones
     // per-lane speed and position features over every environment (EngineHost::laneFeatures and its kin): outputs [R * L] /
     // [R * L * nBins], edges [L][nBins + 1] or [nBins + 1], shared by the environments
-    bool laneFeaturesOnDevice() const { return be_.hasDeviceBuffers() && be_.hasLaneFeatures(); }
     std::vector<double> laneLengths() const;  // [L] of one environment
     void laneFeatures(double *speedSum, int32_t *bins, const double *edges, int nBins, bool perLaneEdges);
     void observeLanesDevice(uintptr_t counts, uintptr_t waiting, uintptr_t speedSum, uintptr_t bins, uintptr_t edges, int nBins,

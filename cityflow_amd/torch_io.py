@@ -34,53 +34,6 @@ def _torch():
     return torch
 
 
-def _check_out(torch, out, shape, device):
-    if not isinstance(out, torch.Tensor):
-        raise TypeError("out must be a torch.Tensor, not %s" % type(out).__name__)
-    if out.device != device:
-        raise TypeError("out is on %s; this engine's tensors live on %s" % (out.device, device))
-    if out.dtype != torch.int32:
-        raise TypeError("out must be int32, not %s" % out.dtype)
-    if tuple(out.shape) != shape:
-        raise ValueError("out must have shape %s, not %s" % (shape, tuple(out.shape)))
-    if not out.is_contiguous():
-        raise ValueError("out must be contiguous")
-
-
-def _observe(eng, out, waiting):
-    torch = _torch()
-    shape = tuple(eng._tensor_shapes()[0])
-    if not eng._device_buffers():
-        if out is not None:
-            _check_out(torch, out, shape, torch.device("cpu"))
-        arr = eng.get_lane_waiting_vehicle_count_array() if waiting else eng.get_lane_vehicle_count_array()
-        t = torch.from_numpy(arr.reshape(shape))
-        if out is None:
-            return t
-        out.copy_(t)
-        return out
-    dev = eng._stream_handle()[1]
-    device = torch.device("cuda", dev)
-    if out is None:
-        out = torch.empty(shape, dtype=torch.int32, device=device)
-    else:
-        _check_out(torch, out, shape, device)
-    ptr = out.data_ptr()
-    eng._observe_device(0 if waiting else ptr, ptr if waiting else 0, torch.cuda.current_stream(device).cuda_stream)
-    return out
-
-
-def get_lane_vehicle_count_tensor(self, out=None):
-    """Vehicles on every lane (get_lane_vehicle_count_array's order) as an int32 tensor on the engine's device, valid on the
-    current torch stream; `out`: a contiguous int32 tensor of that shape on that device, filled in place."""
-    return _observe(self, out, False)
-
-
-def get_lane_waiting_vehicle_count_tensor(self, out=None):
-    """Vehicles with speed < 0.1 on every lane, as get_lane_vehicle_count_tensor."""
-    return _observe(self, out, True)
-
-
 def _check_phases(torch, phases, shape, device):
     if not isinstance(phases, torch.Tensor):
         raise TypeError("phases must be a torch.Tensor, not %s" % type(phases).__name__)
@@ -208,12 +161,33 @@ def observe_lanes_tensor(self, counts=None, waiting=None, speed_sum=None, bins=N
                                n_bins, per_lane, torch.cuda.current_stream(device).cuda_stream)
 
 
+def _lane_out(eng, dtype_name):
+    torch = _torch()
+    return torch.empty(tuple(eng._tensor_shapes()[0]), dtype=getattr(torch, dtype_name), device=_engine_device(torch, eng))
+
+
+def get_lane_vehicle_count_tensor(self, out=None):
+    """Vehicles on every lane (get_lane_vehicle_count_array's order) as an int32 tensor on the engine's device, valid on the
+    current torch stream; `out`: a contiguous int32 tensor of that shape on that device, filled in place."""
+    if out is None:
+        out = _lane_out(self, "int32")
+    observe_lanes_tensor(self, counts=out)
+    return out
+
+
+def get_lane_waiting_vehicle_count_tensor(self, out=None):
+    """Vehicles with speed < 0.1 on every lane, as get_lane_vehicle_count_tensor."""
+    if out is None:
+        out = _lane_out(self, "int32")
+    observe_lanes_tensor(self, waiting=out)
+    return out
+
+
 def get_lane_speed_sum_tensor(self, out=None):
     """Sum of the speeds of every lane's vehicles, front to back (mean speed = sum / count), as a float64 tensor on the
     engine's device, valid on the current torch stream; `out`: a contiguous float64 tensor of that shape, filled in place."""
-    torch = _torch()
     if out is None:
-        out = torch.empty(tuple(self._tensor_shapes()[0]), dtype=torch.float64, device=_engine_device(torch, self))
+        out = _lane_out(self, "float64")
     observe_lanes_tensor(self, speed_sum=out)
     return out
 

@@ -513,6 +513,7 @@ int32_t cfx_device_spin(cfx_engine *e, int64_t microseconds);
  *   "cfx_observe_device"        counts[n_lanes] (as cfx_get_lane_counts) and waiting[n_lanes] (as cfx_get_lane_waiting_counts),
  *                               either may be NULL, written by one kernel on the engine's stream after everything enqueued on
  *                               it (every cfx_step / set call made before); work enqueued on consumer_stream afterwards sees them.
+ *                               The same call as "cfx_observe_lanes_device" below with speed_sum and bins NULL.
  *   "cfx_set_tl_phases_device"  phases[n], n == n_inters: cfx_set_tl_phases of every intersection, read after everything
  *                               enqueued on producer_stream before the call.  -1 keeps an intersection's phase, entries of
  *                               virtual intersections are ignored; any other entry outside [0, its phase count) rejects the

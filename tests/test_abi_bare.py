@@ -139,6 +139,12 @@ class Corridor:
         self.ok(self.dll.cfx_get_lane_counts(self.h, _ptr(out, c_i32p)))
         return out.tolist()
 
+    def lane_waiting_counts(self):
+        out = np.zeros(2, dtype=np.int32)
+        self.dll.cfx_get_lane_waiting_counts.argtypes = [C.c_void_p, c_i32p]
+        self.ok(self.dll.cfx_get_lane_waiting_counts(self.h, _ptr(out, c_i32p)))
+        return out.tolist()
+
     def scalars(self):
         s = CfxScalars()
         self.ok(self.dll.cfx_get_scalars(self.h, C.byref(s)))
@@ -217,6 +223,23 @@ def test_bare_abi_on_the_cpu_twin():
         e.close()
 
 
+def _check_device_counts(e):
+    """cfx_observe_device (an optional entry point, resolved by name; the twin has none): both counts into device memory, equal
+    to what the host getters return; no output at all is CFX_ERR_INVALID."""
+    import torch
+
+    observe = e.dll.cfx_observe_device
+    observe.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    counts = torch.full((2,), -1, dtype=torch.int32, device="cuda:0")  # (CfxConfig.device = 0)
+    waiting = torch.full((2,), -1, dtype=torch.int32, device="cuda:0")
+    e.ok(observe(e.h, counts.data_ptr(), waiting.data_ptr(), None))  # (consumer stream: the null stream)
+    torch.cuda.synchronize()
+    assert counts.tolist() == e.lane_counts()
+    assert waiting.tolist() == e.lane_waiting_counts()
+    assert observe(e.h, None, None, None) == -1  # CFX_ERR_INVALID
+    return counts.tolist()
+
+
 @pytest.mark.gpu
 def test_bare_abi_on_the_hip_library_equals_twin(mod):
     path = mod._default_backend_path()
@@ -233,6 +256,13 @@ def test_bare_abi_on_the_hip_library_equals_twin(mod):
         again = _drive([hip, twin])
         for (lc_a, v_a, *_), (lc_b, v_b, *_) in zip(trace, again):
             assert lc_a == lc_b and all(np.array_equal(v_a[k], v_b[k]) for k in v_a)
+        hip.ok(hip.dll.cfx_reset(hip.h))
+        hip.spawned, hip.last_on_lane0 = 0, -1
+        seen = []
+        for s in range(12):  # (the corridor filling up: the lane counts are those of the trace)
+            hip.step(spawn_priority=1000 + s if s in (0, 3, 6) else None, time=float(s))
+            seen.append(_check_device_counts(hip))
+        assert seen == [t[0] for t in trace[:12]] and max(map(max, seen)) >= 2
     finally:
         hip.close()
         twin.close()

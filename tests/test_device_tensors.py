@@ -1,8 +1,8 @@
 """Lane observations and signal control as torch tensors (cityflow_amd/torch_io.py): get_lane_vehicle_count_tensor,
 get_lane_waiting_vehicle_count_tensor, set_tl_phases_tensor on Engine and VectorEngine.
 
-CPU tests pin the semantics on the twin (CPU tensors over the array calls); gpu tests run the device path (kd_observe /
-kr_observe, k_set_phases_dense) against HIP engines driven through the numpy calls, and against the twin."""
+CPU tests pin the semantics on the twin (CPU tensors over the array calls); gpu tests run the device path (kd_lane_features /
+kr_lane_features, k_set_phases_dense) against HIP engines driven through the numpy calls, and against the twin."""
 import time
 
 import numpy as np
