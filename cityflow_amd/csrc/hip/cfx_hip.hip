@@ -144,6 +144,12 @@ struct cfx_engine {
     double *featSum = nullptr, *featEdges = nullptr;
     int32_t *featBins = nullptr;
     size_t featBinsCap = 0, featEdgesCap = 0;
+    // cfx_observe_intersections_device / cfx_get_intersection_features: the intersection -> roadLink -> {start lanes, end lanes,
+    // laneLinks} index, built and uploaded by the first call (interTables), and the host getter's device scratch; in `owned`
+    bool interBuilt = false;
+    InterFeatOut interTab{};        // the table pointers and M / P; the output pointers stay null here
+    int32_t *interOutI = nullptr;   // [I * (1 + 4 M + P)] phase, in, in_waiting, out, inside, phase_pressure
+    double *interOutD = nullptr;    // [I]
     int cross2 = -1;                // cross phase: 1 = k_cross2 (throughput), 0 = k_cross (latency), -1 = by size
     HostMirror *hMirror = nullptr;  // pinned; valid while the last thing that changed the scalars was a step
     bool mirrorValid = false;
@@ -3300,6 +3306,189 @@ int32_t cfx_get_lane_features(cfx_engine *e, double *speedSum, int32_t *bins, co
     HIP_TRY(hipGetLastError());
     if (speedSum) HIP_TRY(hipMemcpyAsync(speedSum, e->featSum, nSum * sizeof(double), hipMemcpyDeviceToHost, e->stream));
     if (bins) HIP_TRY(hipMemcpyAsync(bins, e->featBins, nOut * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    return CFX_OK;
+}
+
+// ---- per-intersection movement and phase observations (optional entry points of include/cityflow_amd.h, as above)
+int32_t cfx_observe_intersections_device(cfx_engine *e, int32_t *phase, double *remain, int32_t *in, int32_t *inWaiting, int32_t *out,
+                                         int32_t *inside, int32_t *pressure, int32_t maxRoadLinks, int32_t maxPhases,
+                                         void *consumerStream);
+int32_t cfx_get_intersection_features(cfx_engine *e, int32_t *phase, double *remain, int32_t *in, int32_t *inWaiting, int32_t *out,
+                                      int32_t *inside, int32_t *pressure, int32_t maxRoadLinks, int32_t maxPhases);
+static_assert(std::is_same<decltype(&cfx_observe_intersections_device), cfx_observe_intersections_device_fn>::value,
+              "cfx_observe_intersections_device");
+static_assert(std::is_same<decltype(&cfx_get_intersection_features), cfx_get_intersection_features_fn>::value,
+              "cfx_get_intersection_features");
+
+// The static index of InterFeatOut from the network tables the device holds (read back once: the engine keeps no host copy of
+// them).  Device memory: 16 (I M + 1) bytes of rows, 4 bytes per in-lane, out-lane and laneLink entry, 4 I P ceil(M / 32) of masks.
+static int interTables(cfx_engine *e) {
+    if (e->interBuilt) return CFX_OK;
+    auto fail = [e](const std::string &m) { return e->fail(m); };
+    const int K = e->K, I = e->I;
+    std::vector<int32_t> llStart((size_t) K), llEnd((size_t) K), llInter((size_t) K), llRL((size_t) K), nRL((size_t) I),
+        phStart((size_t) I + 1), virt((size_t) I), availStart((size_t) I);
+    auto down = [&](std::vector<int32_t> &h, const int32_t *d) {
+        return h.empty() ? hipSuccess : hipMemcpy(h.data(), d, h.size() * sizeof(int32_t), hipMemcpyDeviceToHost);
+    };
+    HIP_TRY(down(llStart, e->net.llStartLane));
+    HIP_TRY(down(llEnd, e->net.llEndLane));
+    HIP_TRY(down(llInter, e->net.llInter));
+    HIP_TRY(down(llRL, e->net.llRoadLink));
+    HIP_TRY(down(nRL, e->net.interNRL));
+    HIP_TRY(down(phStart, e->net.interPhaseStart));
+    HIP_TRY(down(virt, e->net.interVirtual));
+    HIP_TRY(down(availStart, e->net.interAvailStart));
+    int M = 0, P = 0;
+    size_t availEnd = 0;
+    for (int i = 0; i < I; ++i) {
+        M = std::max(M, nRL[(size_t) i]);
+        if (virt[(size_t) i]) continue;
+        const int nPh = phStart[(size_t) i + 1] - phStart[(size_t) i];
+        P = std::max(P, nPh);
+        availEnd = std::max(availEnd, (size_t) availStart[(size_t) i] + (size_t) nPh * nRL[(size_t) i]);
+    }
+    if ((size_t) M * sizeof(int32_t) > 32768) {  // (the kernel keeps M words of LDS per block)
+        e->err = "intersection features: an intersection with " + std::to_string(M) + " roadLinks is beyond the kernel's LDS row";
+        return CFX_ERR_INVALID;
+    }
+    std::vector<uint8_t> avail(availEnd);
+    if (availEnd) HIP_TRY(hipMemcpy(avail.data(), e->net.phaseAvail, availEnd, hipMemcpyDeviceToHost));
+    const size_t rows = (size_t) I * M;
+    std::vector<std::vector<int32_t>> inOf(rows), outOf(rows), llOf(rows);
+    for (int k = 0; k < K; ++k) {
+        const int i = llInter[(size_t) k], m = llRL[(size_t) k];
+        if (i < 0 || i >= I || m < 0 || m >= nRL[(size_t) i] || llStart[(size_t) k] < 0 || llStart[(size_t) k] >= e->L ||
+            llEnd[(size_t) k] < 0 || llEnd[(size_t) k] >= e->L) {
+            e->err = "intersection features: laneLink " + std::to_string(k) + " names no roadLink / lane of the network";
+            return CFX_ERR_INVALID;
+        }
+        const size_t row = (size_t) i * M + m;
+        inOf[row].push_back(llStart[(size_t) k]);
+        outOf[row].push_back(llEnd[(size_t) k]);
+        llOf[row].push_back(k);
+    }
+    std::vector<int4> off(rows + 1);
+    std::vector<int32_t> inL, outL, links;
+    auto distinct = [](std::vector<int32_t> &v) {
+        std::sort(v.begin(), v.end());
+        v.erase(std::unique(v.begin(), v.end()), v.end());
+    };
+    for (size_t row = 0; row < rows; ++row) {
+        off[row] = make_int4((int) inL.size(), (int) outL.size(), (int) links.size(), 0);
+        distinct(inOf[row]);
+        distinct(outOf[row]);
+        inL.insert(inL.end(), inOf[row].begin(), inOf[row].end());
+        outL.insert(outL.end(), outOf[row].begin(), outOf[row].end());
+        links.insert(links.end(), llOf[row].begin(), llOf[row].end());
+    }
+    off[rows] = make_int4((int) inL.size(), (int) outL.size(), (int) links.size(), 0);
+    const int W = (M + 31) / 32;
+    std::vector<uint32_t> mask((size_t) I * P * W, 0u);
+    for (int i = 0; i < I; ++i) {
+        if (virt[(size_t) i]) continue;
+        const int nPh = phStart[(size_t) i + 1] - phStart[(size_t) i], nr = nRL[(size_t) i];
+        for (int p = 0; p < nPh; ++p)
+            for (int m = 0; m < nr; ++m)
+                if (avail[(size_t) availStart[(size_t) i] + (size_t) p * nr + m]) mask[((size_t) i * P + p) * W + m / 32] |= 1u << (m % 32);
+    }
+    InterFeatOut &t = e->interTab;
+    int rc;
+    if ((rc = e->uploadConst(t.rlOff, off.data(), off.size()))) return rc;
+    if ((rc = e->uploadConst(t.inLanes, inL.data(), inL.size()))) return rc;
+    if ((rc = e->uploadConst(t.outLanes, outL.data(), outL.size()))) return rc;
+    if ((rc = e->uploadConst(t.rlLinks, links.data(), links.size()))) return rc;
+    if ((rc = e->uploadConst(t.phaseMask, mask.data(), mask.size()))) return rc;
+    t.M = M;
+    t.P = P;
+    t.maskWords = W;
+    e->interBuilt = true;
+    return CFX_OK;
+}
+
+// one block per intersection (interFeatures, cfx_kernels.h)
+static void launchInterFeatures(cfx_engine *e, int32_t *phase, double *remain, int32_t *in, int32_t *inWaiting, int32_t *out,
+                                int32_t *inside, int32_t *pressure) {
+    if (e->I <= 0) return;
+    InterFeatOut o = e->interTab;
+    o.phase = phase;
+    o.remain = remain;
+    o.in = in;
+    o.inWaiting = inWaiting;
+    o.out = out;
+    o.inside = inside;
+    o.pressure = pressure;
+    o.remainSrc = e->remain;
+    const size_t lds = (size_t) o.M * sizeof(int32_t);
+    if (e->ring) hipLaunchKernelGGL(kr_intersection_features, dim3((unsigned) e->I), dim3(kBlock), lds, e->stream, e->rctx(), o);
+    else hipLaunchKernelGGL(kd_intersection_features, dim3((unsigned) e->I), dim3(kBlock), lds, e->stream, e->ctx(), o);
+}
+
+// what both entry points do before their launch: the deferred commit, tables, rings, the index, the caller's row lengths
+static int interPrepare(cfx_engine *e, int32_t maxRoadLinks, int32_t maxPhases, const char *what) {
+    int rc;
+    if ((rc = e->settle(false))) return rc;  // (ring layout: a commit deferred to the next step's admission; Lane::history is not read here)
+    if ((rc = e->syncTables())) return rc;
+    if (e->ring && (rc = e->ringEnsure())) return rc;
+    if ((rc = interTables(e))) return rc;
+    if (maxRoadLinks != e->interTab.M || maxPhases != e->interTab.P) {
+        e->err = std::string(what) + ": max_roadlinks / max_phases must be the network's " + std::to_string(e->interTab.M) + " / " +
+                 std::to_string(e->interTab.P) + ", not " + std::to_string(maxRoadLinks) + " / " + std::to_string(maxPhases);
+        return CFX_ERR_INVALID;
+    }
+    return CFX_OK;
+}
+
+int32_t cfx_observe_intersections_device(cfx_engine *e, int32_t *phase, double *remain, int32_t *in, int32_t *inWaiting, int32_t *out,
+                                         int32_t *inside, int32_t *pressure, int32_t maxRoadLinks, int32_t maxPhases,
+                                         void *consumerStream) {
+    if (!e || (!phase && !remain && !in && !inWaiting && !out && !inside && !pressure)) return CFX_ERR_INVALID;
+    auto fail = [e](const std::string &m) { return e->fail(m); };
+    HIP_TRY(hipSetDevice(e->device));
+    int rc;
+    if (phase && (rc = checkDevicePointer(e, phase, "cfx_observe_intersections_device: phase"))) return rc;
+    if (remain && (rc = checkDevicePointer(e, remain, "cfx_observe_intersections_device: remain"))) return rc;
+    if (in && (rc = checkDevicePointer(e, in, "cfx_observe_intersections_device: in"))) return rc;
+    if (inWaiting && (rc = checkDevicePointer(e, inWaiting, "cfx_observe_intersections_device: in_waiting"))) return rc;
+    if (out && (rc = checkDevicePointer(e, out, "cfx_observe_intersections_device: out"))) return rc;
+    if (inside && (rc = checkDevicePointer(e, inside, "cfx_observe_intersections_device: inside"))) return rc;
+    if (pressure && (rc = checkDevicePointer(e, pressure, "cfx_observe_intersections_device: phase_pressure"))) return rc;
+    if ((rc = interPrepare(e, maxRoadLinks, maxPhases, "cfx_observe_intersections_device"))) return rc;
+    if ((rc = e->orderAfterCaller((hipStream_t) consumerStream))) return rc;
+    launchInterFeatures(e, phase, remain, in, inWaiting, out, inside, pressure);
+    HIP_TRY(hipGetLastError());
+    if ((rc = e->orderCallerAfter((hipStream_t) consumerStream))) return rc;
+    e->devObserving = !e->tiled;
+    e->devObserveIdle = 0;
+    return CFX_OK;
+}
+
+int32_t cfx_get_intersection_features(cfx_engine *e, int32_t *phase, double *remain, int32_t *in, int32_t *inWaiting, int32_t *out,
+                                      int32_t *inside, int32_t *pressure, int32_t maxRoadLinks, int32_t maxPhases) {
+    if (!e || (!phase && !remain && !in && !inWaiting && !out && !inside && !pressure)) return CFX_ERR_INVALID;
+    auto fail = [e](const std::string &m) { return e->fail(m); };
+    HIP_TRY(hipSetDevice(e->device));
+    int rc;
+    if ((rc = interPrepare(e, maxRoadLinks, maxPhases, "cfx_get_intersection_features"))) return rc;
+    const size_t nI = (size_t) e->I, nM = nI * e->interTab.M, nP = nI * e->interTab.P;
+    if (!e->interOutI && (rc = e->allocRaw(&e->interOutI, nI + 4 * nM + nP))) return rc;
+    if (!e->interOutD && (rc = e->allocRaw(&e->interOutD, nI))) return rc;
+    int32_t *dPhase = e->interOutI, *dIn = dPhase + nI, *dWait = dIn + nM, *dOut = dWait + nM, *dInside = dOut + nM,
+            *dPressure = dInside + nM;
+    launchInterFeatures(e, phase ? dPhase : nullptr, remain ? e->interOutD : nullptr, in ? dIn : nullptr, inWaiting ? dWait : nullptr,
+                        out ? dOut : nullptr, inside ? dInside : nullptr, pressure ? dPressure : nullptr);
+    HIP_TRY(hipGetLastError());
+    auto back = [&](void *dst, const void *src, size_t bytes) {
+        return (dst && bytes) ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, e->stream) : hipSuccess;
+    };
+    HIP_TRY(back(phase, dPhase, nI * sizeof(int32_t)));
+    HIP_TRY(back(remain, e->interOutD, nI * sizeof(double)));
+    HIP_TRY(back(in, dIn, nM * sizeof(int32_t)));
+    HIP_TRY(back(inWaiting, dWait, nM * sizeof(int32_t)));
+    HIP_TRY(back(out, dOut, nM * sizeof(int32_t)));
+    HIP_TRY(back(inside, dInside, nM * sizeof(int32_t)));
+    HIP_TRY(back(pressure, dPressure, nP * sizeof(int32_t)));
     HIP_TRY(hipStreamSynchronize(e->stream));
     return CFX_OK;
 }

@@ -2283,14 +2283,123 @@ __device__ __forceinline__ void laneFeatures(const LaneFeatOut &o, int lane, int
 }
 
 // dense layout: the lane's segment [segStart, segStart + cnt) of the current generation, front to back
+struct DenseLaneRec {  // {dis, speed} of the lane's i-th vehicle from the front
+    const double *dis, *speed;
+    int base;
+    __device__ __forceinline__ double2 operator()(int i) const { return make_double2(dis[base + i], speed[base + i]); }
+};
+__device__ __forceinline__ DenseLaneRec laneRec(const StepCtx &c, int lane) { return DenseLaneRec{c.s.dis, c.s.speed, c.segStart[lane]}; }
+
 __global__ void __launch_bounds__(kBlock) kd_lane_features(StepCtx c, LaneFeatOut o) {
     __shared__ double2 stage[kBlock];
     const int lane = (int) ((blockIdx.x * (size_t) blockDim.x + threadIdx.x) / kFeatGroup);
     if (lane >= c.n.L) return;  // (whole groups)
     const int sub = threadIdx.x % kFeatGroup;
-    const int base = c.segStart[lane], n = c.cnt[lane];
-    laneFeatures(o, lane, n, sub, stage + (threadIdx.x - sub),
-                 [&](int i) { return make_double2(c.s.dis[base + i], c.s.speed[base + i]); });
+    laneFeatures(o, lane, c.cnt[lane], sub, stage + (threadIdx.x - sub), laneRec(c, lane));
+}
+
+// cfx_observe_intersections_device / cfx_get_intersection_features: what a signal policy observes, per intersection, in one
+// launch (any output may be null; every element of a given output has exactly one writer, padding included, so the caller's
+// buffers need no zeroing and there is no atomic).  One BLOCK owns one intersection; its sixteen groups of kFeatGroup threads
+// take the intersection's roadLinks (one pass up to sixteen of them).  A group adds the counts of the roadLink's lanes (its
+// distinct start lanes, its distinct end lanes, its laneLinks: three short index lists of the static table below, one entry per
+// thread) and, only when waiting counts are asked for, reads the records of each start lane sixteen neighbouring vehicles at
+// a time, as laneFeatures does — without them no vehicle record is loaded.  Each roadLink's in - out goes to LDS; behind a
+// barrier thread p adds it up over the roadLinks phase p serves (a bit mask per phase, requested before the barrier).  Loops
+// over M_i and P_i, no per-thread arrays.
+struct InterFeatOut {
+    int32_t *phase;      // [I]
+    double *remain;      // [I]
+    int32_t *in, *inWaiting, *out, *inside;  // [I * M]
+    int32_t *pressure;   // [I * P]
+    int M, P;            // row lengths: the network's largest roadLink / phase count
+    int maskWords;       // (M + 31) / 32
+    const double *remainSrc;   // [I] TrafficLight::remainDuration
+    // static index (built by the first call, cfx_hip.hip interTables), roadLink (i, m) = row i * M + m
+    const int4 *rlOff;         // [I * M + 1] {first in-lane entry, first out-lane entry, first laneLink entry, 0}; a row's
+                               // lists end where the next row's begin (padding rows are empty)
+    const int32_t *inLanes, *outLanes, *rlLinks;  // lanes ascending and distinct per roadLink; laneLink numbers
+    const uint32_t *phaseMask; // [(i * P + p) * maskWords + w] bit m % 32 of word m / 32: phase p serves roadLink m
+};
+constexpr int kInterGroups = kBlock / kFeatGroup;
+constexpr int kInterPad = (int) 0x80000000;  // phase_pressure where there is no phase
+
+template <typename RecOf>
+__device__ __forceinline__ void interFeatures(const InterFeatOut &o, const DevNet &n, const int32_t *cnt, const int32_t *curPhase,
+                                              int i, int32_t *diff /*[o.M], the block's*/, RecOf recOf) {
+    const int t = threadIdx.x;
+    if (t == 0) {
+        if (o.phase) o.phase[i] = curPhase[i];
+        if (o.remain) o.remain[i] = o.remainSrc[i];
+    }
+    if (!(o.in || o.inWaiting || o.out || o.inside || o.pressure)) return;  // (the same in every thread)
+    const int nRL = n.interNRL[i];
+    int nPh = 0;
+    uint32_t mask0 = 0;
+    if (o.pressure && t < o.P) {  // (requested now, used behind the barrier)
+        nPh = n.interVirtual[i] ? 0 : n.interPhaseStart[i + 1] - n.interPhaseStart[i];
+        if (t < nPh && o.maskWords) mask0 = o.phaseMask[((size_t) i * o.P + t) * o.maskWords];
+    }
+    const int grp = t / kFeatGroup, sub = t % kFeatGroup;
+    for (int m = grp; m < nRL; m += kInterGroups) {  // (m and every bound below are the same in all threads of a group)
+        const size_t row = (size_t) i * o.M + m;
+        const int4 a = o.rlOff[row], b = o.rlOff[row + 1];
+        int vin = 0, vout = 0, vins = 0, w = 0;
+        for (int j = a.x + sub; j < b.x; j += kFeatGroup) vin += cnt[o.inLanes[j]];
+        for (int j = a.y + sub; j < b.y; j += kFeatGroup) vout += cnt[o.outLanes[j]];
+        if (o.inside)
+            for (int j = a.z + sub; j < b.z; j += kFeatGroup) vins += cnt[n.L + o.rlLinks[j]];
+        if (o.inWaiting)
+            for (int j = a.x; j < b.x; ++j) {
+                const int lane = o.inLanes[j], nv = cnt[lane];
+                const auto rec = recOf(lane);
+                for (int first = sub; first < nv; first += kFeatGroup) w += rec(first).y < 0.1;
+            }
+        for (int off = kFeatGroup / 2; off > 0; off >>= 1) {
+            vin += __shfl_xor(vin, off, kFeatGroup);
+            vout += __shfl_xor(vout, off, kFeatGroup);
+            vins += __shfl_xor(vins, off, kFeatGroup);
+            w += __shfl_xor(w, off, kFeatGroup);
+        }
+        if (sub == 0) {
+            if (o.in) o.in[row] = vin;
+            if (o.inWaiting) o.inWaiting[row] = w;
+            if (o.out) o.out[row] = vout;
+            if (o.inside) o.inside[row] = vins;
+            diff[m] = vin - vout;
+        }
+    }
+    for (int m = nRL + t; m < o.M; m += kBlock) {  // padding
+        const size_t row = (size_t) i * o.M + m;
+        if (o.in) o.in[row] = 0;
+        if (o.inWaiting) o.inWaiting[row] = 0;
+        if (o.out) o.out[row] = 0;
+        if (o.inside) o.inside[row] = 0;
+    }
+    if (!o.pressure) return;
+    __syncthreads();  // (every thread of the block arrives: nothing above returns thread by thread)
+    for (int p = t; p < o.P; p += kBlock) {
+        if (p != t) nPh = n.interVirtual[i] ? 0 : n.interPhaseStart[i + 1] - n.interPhaseStart[i];  // (more than kBlock phases)
+        int sum = kInterPad;
+        if (p < nPh) {
+            sum = 0;
+            const uint32_t *mask = o.phaseMask + ((size_t) i * o.P + p) * o.maskWords;
+            for (int wd = 0; wd * 32 < nRL; ++wd) {
+                uint32_t bits = (wd == 0 && p == t) ? mask0 : mask[wd];
+                while (bits) {
+                    sum += diff[wd * 32 + __ffs((int) bits) - 1];
+                    bits &= bits - 1;
+                }
+            }
+        }
+        o.pressure[(size_t) i * o.P + p] = sum;
+    }
+}
+
+// (dynamic LDS: o.M words)
+__global__ void __launch_bounds__(kBlock) kd_intersection_features(StepCtx c, InterFeatOut o) {
+    extern __shared__ int32_t interDiff[];
+    interFeatures(o, c.n, c.cnt, c.curPhase, (int) blockIdx.x, interDiff, [&](int lane) { return laneRec(c, lane); });
 }
 
 // Initial / reset layout: every lane owns just its spare slot, laneLinks are empty.

@@ -2341,15 +2341,26 @@ __global__ void kr_lane_history(RingCtx c, LaneHistDev h) { ringLaneHistory(c, h
 
 // cfx_observe_lanes_device / cfx_get_lane_features, ring layout: laneFeatures (cfx_kernels.h) over the lane's ring, front to
 // back from `head`, over the {dis, speed} records
+struct RingLaneRec {  // {dis, speed} of the lane's i-th vehicle from the front
+    const double2 *kin;
+    int2 geo;
+    int head;
+    __device__ __forceinline__ double2 operator()(int i) const { return kin[ringSlot(geo, head, i)]; }
+};
+__device__ __forceinline__ RingLaneRec laneRec(const RingCtx &c, int lane) { return RingLaneRec{c.kin, c.ringGeo[lane], c.head[lane]}; }
+
 __global__ void __launch_bounds__(kBlock) kr_lane_features(RingCtx c, LaneFeatOut o) {
     __shared__ double2 stage[kBlock];
     const int lane = (int) ((blockIdx.x * (size_t) blockDim.x + threadIdx.x) / kFeatGroup);
     if (lane >= c.n.L) return;  // (whole groups)
     const int sub = threadIdx.x % kFeatGroup;
-    const int n = c.cnt[lane];
-    const int2 geo = c.ringGeo[lane];
-    const int head = c.head[lane];
-    laneFeatures(o, lane, n, sub, stage + (threadIdx.x - sub), [&](int i) { return c.kin[ringSlot(geo, head, i)]; });
+    laneFeatures(o, lane, c.cnt[lane], sub, stage + (threadIdx.x - sub), laneRec(c, lane));
+}
+
+// cfx_observe_intersections_device / cfx_get_intersection_features, ring layout: interFeatures (cfx_kernels.h) over the rings
+__global__ void __launch_bounds__(kBlock) kr_intersection_features(RingCtx c, InterFeatOut o) {
+    extern __shared__ int32_t interDiff[];
+    interFeatures(o, c.n, c.cnt, c.curPhase, (int) blockIdx.x, interDiff, [&](int lane) { return laneRec(c, lane); });
 }
 
 // Vehicle::setCustomSpeed / Router::setRoute / lookup of one running vehicle: its slot is known

@@ -93,6 +93,8 @@ void Backend::open(const std::string &libPath) {
     CFX_FN_OPTIONAL(cfx_device_error)
     CFX_FN_OPTIONAL(cfx_observe_lanes_device)
     CFX_FN_OPTIONAL(cfx_get_lane_features)
+    CFX_FN_OPTIONAL(cfx_observe_intersections_device)
+    CFX_FN_OPTIONAL(cfx_get_intersection_features)
 #undef CFX_FN_OPTIONAL
     if (cfx_abi_version() != CFX_ABI_VERSION)
         throw std::runtime_error("cityflow_amd: ABI version mismatch in '" + libPath + "'");
@@ -537,6 +539,171 @@ void laneFeaturesOf(const Backend &be, cfx_engine *dev, int nLanes, int lanesPer
     }
     laneFeaturesFromView(nLanes, lanesPerEnv, v.count, drv.data(), dis.data(), speed.data(), speedSum, bins, edges, nBins,
                          perLaneEdges);
+}
+
+InterLayout intersectionLayoutOf(const HostRoadNet &net) {
+    InterLayout y;
+    y.I = (int) net.inters.size();
+    y.nRoadLinks.resize((size_t) y.I);
+    y.nPhases.resize((size_t) y.I);
+    std::vector<std::vector<int32_t>> inOf, outOf;  // per roadLink, in intersection order
+    for (int i = 0; i < y.I; ++i) {
+        const HostInter &in = net.inters[(size_t) i];
+        y.nRoadLinks[(size_t) i] = (int32_t) in.roadLinks.size();
+        y.nPhases[(size_t) i] = in.isVirtual ? -1 : (int32_t) in.phases.size();
+        y.M = std::max(y.M, (int) in.roadLinks.size());
+        if (!in.isVirtual) y.P = std::max(y.P, (int) in.phases.size());
+        for (const HostRoadLink &rl : in.roadLinks) {
+            std::vector<int32_t> a, b;
+            for (int k = rl.llStart; k < rl.llStart + rl.nLaneLinks; ++k) {
+                a.push_back(net.laneLinks[(size_t) k].startLane);
+                b.push_back(net.laneLinks[(size_t) k].endLane);
+            }
+            for (std::vector<int32_t> *v : {&a, &b}) {
+                std::sort(v->begin(), v->end());
+                v->erase(std::unique(v->begin(), v->end()), v->end());
+            }
+            y.Kin = std::max(y.Kin, (int) a.size());
+            y.Kout = std::max(y.Kout, (int) b.size());
+            inOf.push_back(std::move(a));
+            outOf.push_back(std::move(b));
+        }
+    }
+    y.phaseAvail.assign((size_t) y.I * y.P * y.M, 0);
+    y.roadLinkType.assign((size_t) y.I * y.M, 0);
+    y.inLanes.assign((size_t) y.I * y.M * y.Kin, -1);
+    y.outLanes.assign((size_t) y.I * y.M * y.Kout, -1);
+    y.llRow.assign(net.laneLinks.size(), -1);
+    size_t g = 0;
+    for (int i = 0; i < y.I; ++i) {
+        const HostInter &in = net.inters[(size_t) i];
+        for (size_t m = 0; m < in.roadLinks.size(); ++m, ++g) {
+            const size_t row = (size_t) i * y.M + m;
+            y.roadLinkType[row] = in.roadLinks[m].type;
+            std::copy(inOf[g].begin(), inOf[g].end(), y.inLanes.begin() + row * y.Kin);
+            std::copy(outOf[g].begin(), outOf[g].end(), y.outLanes.begin() + row * y.Kout);
+            for (int k = in.roadLinks[m].llStart; k < in.roadLinks[m].llStart + in.roadLinks[m].nLaneLinks; ++k)
+                y.llRow[(size_t) k] = (int32_t) row;
+        }
+        if (in.isVirtual) continue;
+        for (size_t p = 0; p < in.phases.size(); ++p)
+            for (size_t m = 0; m < in.roadLinks.size() && m < in.phases[p].avail.size(); ++m)
+                y.phaseAvail[((size_t) i * y.P + p) * y.M + m] = in.phases[p].avail[m] ? 1 : 0;
+    }
+    return y;
+}
+
+void intersectionFeaturesOf(const Backend &be, cfx_engine *dev, const InterLayout &lay, int nEnvs, int nLanes, int nLaneLinks,
+                            const InterFeatures &out) {
+    auto fail = [&](const char *what) {
+        const char *msg = be.cfx_last_error(dev);
+        throw std::runtime_error(std::string("cityflow_amd: ") + what + " failed: " + (msg ? msg : ""));
+    };
+    if (be.cfx_get_intersection_features) {
+        if (be.cfx_get_intersection_features(dev, out.phase, out.remain, out.in, out.inWaiting, out.out, out.inside, out.pressure,
+                                             lay.M, lay.P) != CFX_OK)
+            fail("cfx_get_intersection_features");
+        return;
+    }
+    const size_t I = (size_t) lay.I, M = (size_t) lay.M, P = (size_t) lay.P, rows = (size_t) nEnvs * I;
+    if (out.phase || out.remain) {
+        std::vector<int32_t> ph(rows);
+        std::vector<double> rem(rows);
+        if (be.cfx_get_tl_state(dev, ph.data(), rem.data()) != CFX_OK) fail("cfx_get_tl_state");
+        if (out.phase) std::copy(ph.begin(), ph.end(), out.phase);
+        if (out.remain) std::copy(rem.begin(), rem.end(), out.remain);
+    }
+    std::vector<int32_t> counts, waiting;
+    if (out.in || out.out || out.pressure) {
+        counts.resize((size_t) nEnvs * nLanes);
+        if (be.cfx_get_lane_counts(dev, counts.data()) != CFX_OK) fail("cfx_get_lane_counts");
+    }
+    if (out.inWaiting) {
+        waiting.resize((size_t) nEnvs * nLanes);
+        if (be.cfx_get_lane_waiting_counts(dev, waiting.data()) != CFX_OK) fail("cfx_get_lane_waiting_counts");
+    }
+    auto laneSum = [&](const std::vector<int32_t> &lanes, size_t K, const std::vector<int32_t> &per, int32_t *dst) {
+        if (!dst) return;
+        for (int r = 0; r < nEnvs; ++r)
+            for (size_t row = 0; row < I * M; ++row) {
+                int32_t s = 0;
+                for (size_t j = 0; j < K && lanes[row * K + j] >= 0; ++j) s += per[(size_t) r * nLanes + lanes[row * K + j]];
+                dst[(size_t) r * I * M + row] = s;
+            }
+    };
+    std::vector<int32_t> inSum, outSum;
+    if (out.pressure) {
+        inSum.resize(rows * M);
+        outSum.resize(rows * M);
+    }
+    laneSum(lay.inLanes, (size_t) lay.Kin, counts, out.pressure ? inSum.data() : out.in);
+    laneSum(lay.outLanes, (size_t) lay.Kout, counts, out.pressure ? outSum.data() : out.out);
+    if (out.pressure) {
+        if (out.in) std::copy(inSum.begin(), inSum.end(), out.in);
+        if (out.out) std::copy(outSum.begin(), outSum.end(), out.out);
+        for (int r = 0; r < nEnvs; ++r)
+            for (size_t i = 0; i < I; ++i)
+                for (size_t p = 0; p < P; ++p) {
+                    int32_t s = INT32_MIN;
+                    if ((int) p < lay.nPhases[i]) {
+                        s = 0;
+                        for (size_t m = 0; m < (size_t) lay.nRoadLinks[i]; ++m)
+                            if (lay.phaseAvail[(i * P + p) * M + m]) s += inSum[((size_t) r * I + i) * M + m] - outSum[((size_t) r * I + i) * M + m];
+                    }
+                    out.pressure[((size_t) r * I + i) * P + p] = s;
+                }
+    }
+    laneSum(lay.inLanes, (size_t) lay.Kin, waiting, out.inWaiting);
+    if (out.inside) {
+        std::fill(out.inside, out.inside + rows * M, 0);
+        cfx_scalars sc{};
+        if (be.cfx_get_scalars(dev, &sc) != CFX_OK) fail("cfx_get_scalars");
+        std::vector<int32_t> drv;
+        cfx_vehicle_view v{};
+        for (int cap = (int) sc.active_vehicle_count + 16;;) {
+            drv.resize((size_t) cap);
+            v = cfx_vehicle_view{};
+            v.capacity = cap;
+            v.drivable = drv.data();
+            const int32_t rc = be.cfx_get_vehicles(dev, &v);
+            if (rc == CFX_ERR_CAPACITY && v.count > cap) {
+                cap = v.count + 16;
+                continue;
+            }
+            if (rc != CFX_OK) fail("cfx_get_vehicles");
+            break;
+        }
+        const int allLanes = nEnvs * nLanes;  // (environments: lanes copy by copy, then laneLinks copy by copy)
+        for (int i = 0; i < v.count; ++i) {
+            const int k = drv[(size_t) i] - allLanes;
+            if (k < 0 || k >= nEnvs * nLaneLinks) continue;
+            out.inside[(size_t) (k / nLaneLinks) * I * M + lay.llRow[(size_t) (k % nLaneLinks)]] += 1;
+        }
+    }
+}
+
+const InterLayout &EngineHost::intersectionLayout() {
+    if (!interLayout_) interLayout_.reset(new InterLayout(intersectionLayoutOf(*net_)));
+    return *interLayout_;
+}
+
+// (like the count getters, these leave the step prepared ahead in place: they read the device, not the spawner)
+void EngineHost::intersectionFeatures(const InterFeatures &out) {
+    flushPhases();  // (single sets made before this call show in `phase`, as in trafficLightState)
+    intersectionFeaturesOf(be_, dev_, intersectionLayout(), 1, (int) net_->lanes.size(), (int) net_->laneLinks.size(), out);
+    raiseDeviceError();
+}
+
+void EngineHost::observeIntersectionsDevice(uintptr_t phase, uintptr_t remain, uintptr_t in, uintptr_t inWaiting, uintptr_t out,
+                                            uintptr_t inside, uintptr_t pressure, int maxRoadLinks, int maxPhases,
+                                            uintptr_t consumerStream) {
+    if (!be_.hasDeviceBuffers() || !be_.cfx_observe_intersections_device)
+        throw std::runtime_error("cityflow_amd: '" + be_.path + "' has no device-side intersection observations");
+    flushPhases();
+    check(be_.cfx_observe_intersections_device(dev_, (int32_t *) phase, (double *) remain, (int32_t *) in, (int32_t *) inWaiting,
+                                               (int32_t *) out, (int32_t *) inside, (int32_t *) pressure, maxRoadLinks, maxPhases,
+                                               (void *) consumerStream),
+          "cfx_observe_intersections_device");
 }
 
 std::vector<int32_t> EngineHost::phaseCounts() const {

@@ -84,6 +84,9 @@ struct Backend {
     }
     // optional on its own: speed sums and bins into host memory (without it the host computes them from cfx_get_vehicles)
     cfx_get_lane_features_fn cfx_get_lane_features = nullptr;
+    // optional as a pair: per-intersection observations (without them the host computes the arrays from the getters above)
+    cfx_observe_intersections_device_fn cfx_observe_intersections_device = nullptr;
+    cfx_get_intersection_features_fn cfx_get_intersection_features = nullptr;
     void open(const std::string &libPath);  // throws std::runtime_error
     ~Backend();
 };
@@ -104,6 +107,30 @@ struct VehicleSnapshot {
     int count = 0;
     bool isShadow(int i) const { return !lcFlags.empty() && (lcFlags[i] & CFX_LC_SHADOW); }
 };
+
+// The static tables behind the per-intersection observations, of ONE environment: intersection i has nRoadLinks[i] roadLinks
+// (rows padded to M) and nPhases[i] phases (-1 = virtual; rows padded to P); IN / OUT lanes of a roadLink are the distinct start /
+// end lanes of its laneLinks, ascending, -1 padded to Kin / Kout.
+struct InterLayout {
+    int I = 0, M = 0, P = 0, Kin = 0, Kout = 0;
+    std::vector<int32_t> nRoadLinks, nPhases;  // [I]
+    std::vector<uint8_t> phaseAvail;           // [I * P * M]
+    std::vector<int32_t> roadLinkType;         // [I * M] 0 = padding
+    std::vector<int32_t> inLanes, outLanes;    // [I * M * Kin], [I * M * Kout]
+    std::vector<int32_t> llRow;                // [n_lanelinks] i * M + m of the laneLink's roadLink
+};
+InterLayout intersectionLayoutOf(const HostRoadNet &net);
+// the seven outputs of cfx_observe_intersections_device in host memory ([nEnvs * I], [nEnvs * I * M], [nEnvs * I * P]; any may be null)
+struct InterFeatures {
+    int32_t *phase = nullptr;
+    double *remain = nullptr;
+    int32_t *in = nullptr, *inWaiting = nullptr, *out = nullptr, *inside = nullptr, *pressure = nullptr;
+};
+// ... on any backend: cfx_get_intersection_features where it exists, otherwise from cfx_get_lane_counts,
+// cfx_get_lane_waiting_counts, cfx_get_vehicles (drivable column) and cfx_get_tl_state (throws std::runtime_error with the
+// backend's message).  `lay`: one environment's layout, `nLanes` / `nLaneLinks`: of one environment
+void intersectionFeaturesOf(const Backend &be, cfx_engine *dev, const InterLayout &lay, int nEnvs, int nLanes, int nLaneLinks,
+                            const InterFeatures &out);
 
 class EngineHost {
 public:
@@ -171,6 +198,12 @@ public:
     void laneFeatures(double *speedSum, int32_t *bins, const double *edges, int nBins, bool perLaneEdges);
     void observeLanesDevice(uintptr_t counts, uintptr_t waiting, uintptr_t speedSum, uintptr_t bins, uintptr_t edges, int nBins,
                             bool perLaneEdges, uintptr_t consumerStream);
+    // ---- per-intersection movement and phase observations (cfx_observe_intersections_device / cfx_get_intersection_features;
+    //      the twin: from the count getters, the vehicles and the lights).  Rows of layout().M roadLinks / layout().P phases
+    const InterLayout &intersectionLayout();
+    void intersectionFeatures(const InterFeatures &out);  // any pointer may be null
+    void observeIntersectionsDevice(uintptr_t phase, uintptr_t remain, uintptr_t in, uintptr_t inWaiting, uintptr_t out,
+                                    uintptr_t inside, uintptr_t pressure, int maxRoadLinks, int maxPhases, uintptr_t consumerStream);
     // Lane::history as the device keeps it ("cfx": {"laneHistory": true}; cfx_get_lane_history): lane-major, oldest record first
     void laneHistory(std::vector<int32_t> &len, std::vector<int32_t> &vehicleNum, std::vector<double> &averageSpeed,
                      std::vector<int32_t> &historyVehicleNum, std::vector<double> &historyAverageSpeed);
@@ -276,6 +309,7 @@ private:
     void flushPhases();
     std::vector<int32_t> laneIdOrder_;
     uint64_t vehicleEpoch_ = 0;
+    std::unique_ptr<InterLayout> interLayout_;  // built by the first call that needs it
 };
 
 struct EngineConfig {  // Engine::loadConfig engine.cpp:37-84

@@ -269,6 +269,42 @@ template <typename E> py::array_t<int32_t> laneBinsArray(E &e, const EdgesArray 
     return out;
 }
 
+// ---- per-intersection observations (Engine and VectorEngine; the public calls are cityflow_amd/torch_io.py)
+template <typename E> py::tuple intersectionFeaturesTuple(E &e, py::ssize_t nEnvs) {
+    const cfa::InterLayout &y = e.intersectionLayout();
+    const py::ssize_t rows = nEnvs * y.I;
+    py::array_t<int32_t> phase(rows), in(rows * y.M), wait(rows * y.M), out(rows * y.M), inside(rows * y.M), pressure(rows * y.P);
+    py::array_t<double> remain(rows);
+    cfa::InterFeatures f;
+    f.phase = phase.mutable_data();
+    f.remain = remain.mutable_data();
+    f.in = in.mutable_data();
+    f.inWaiting = wait.mutable_data();
+    f.out = out.mutable_data();
+    f.inside = inside.mutable_data();
+    f.pressure = pressure.mutable_data();
+    e.intersectionFeatures(f);
+    return py::make_tuple(phase, remain, in, wait, out, inside, pressure);
+}
+
+template <typename E> py::dict intersectionLayoutDict(E &e) {
+    const cfa::InterLayout &y = e.intersectionLayout();
+    auto shaped = [](const auto &v, std::vector<py::ssize_t> shape) {
+        using T = typename std::decay<decltype(v)>::type::value_type;
+        py::array_t<T> a(shape);
+        std::copy(v.begin(), v.end(), a.mutable_data());
+        return a;
+    };
+    py::dict d;
+    d["n_roadlinks"] = shaped(y.nRoadLinks, {y.I});
+    d["n_phases"] = shaped(y.nPhases, {y.I});
+    d["phase_avail"] = shaped(y.phaseAvail, {y.I, y.P, y.M});
+    d["roadlink_type"] = shaped(y.roadLinkType, {y.I, y.M});
+    d["in_lanes"] = shaped(y.inLanes, {y.I, y.M, y.Kin});
+    d["out_lanes"] = shaped(y.outLanes, {y.I, y.M, y.Kout});
+    return d;
+}
+
 // Device buffers: raw pointers and streams under the tensor methods of cityflow_amd/torch_io.py (Engine and VectorEngine alike)
 template <typename E> void defDeviceBuffers(py::class_<E> &c) {
     c.def("_device_buffers", &E::deviceBuffers, "the backend takes observations / signals in device memory")
@@ -278,7 +314,12 @@ template <typename E> void defDeviceBuffers(py::class_<E> &c) {
         .def("_phase_counts", [](E &e) { return toArray(e.phaseCounts()); }, "phases per intersection, -1 = virtual")
         .def("lane_lengths", [](E &e) { return toArray(e.laneLengths()); }, "float64 [L]: Lane::getLength (of one environment)")
         .def("_observe_lanes_device", &E::observeLanesDevice, "counts_ptr"_a, "waiting_ptr"_a, "speed_sum_ptr"_a, "bins_ptr"_a,
-             "edges_ptr"_a, "n_bins"_a, "per_lane_edges"_a, "consumer_stream"_a);
+             "edges_ptr"_a, "n_bins"_a, "per_lane_edges"_a, "consumer_stream"_a)
+        .def("_intersection_dims", [](E &e) { return py::make_tuple(e.intersectionLayout().M, e.intersectionLayout().P); },
+             "(largest roadLink count, largest phase count) of an intersection: the row lengths of the intersection observations")
+        .def("_intersection_layout", [](E &e) { return intersectionLayoutDict(e); })
+        .def("_observe_intersections_device", &E::observeIntersectionsDevice, "phase_ptr"_a, "remain_ptr"_a, "in_ptr"_a,
+             "in_waiting_ptr"_a, "out_ptr"_a, "inside_ptr"_a, "pressure_ptr"_a, "max_roadlinks"_a, "max_phases"_a, "consumer_stream"_a);
 }
 
 // Engine.set_tl_phase(intersection_id, phase_id) (reference src/cityflow.cpp:35, engine.cpp:719-725) as a vectorcall method of its
@@ -640,6 +681,8 @@ PYBIND11_MODULE(_cityflow, m) {
              })
         .def("_flat_net", [](EngineHost &e) { return flatNetToDict(e.net()); });
     defDeviceBuffers(engineClass);
+    engineClass.def("_intersection_features", [](EngineHost &e) { return intersectionFeaturesTuple(e, 1); },
+                    "(phase, remain, in, in_waiting, out, inside, phase_pressure), flat");
     {
         PyObject *descr = PyDescr_NewMethod((PyTypeObject *) engineClass.ptr(), &kEngineSetTlPhaseDef);
         if (!descr) throw py::error_already_set();
@@ -728,6 +771,8 @@ PYBIND11_MODULE(_cityflow, m) {
             return d;
         });
     defDeviceBuffers(vectorClass);
+    vectorClass.def("_intersection_features", [](VectorEngineHost &e) { return intersectionFeaturesTuple(e, e.numEnvs()); },
+                    "(phase, remain, in, in_waiting, out, inside, phase_pressure), flat, env-major");
 
     using cfa::TiledEngineHost;
     py::class_<TiledEngineHost>(m, "TiledEngine",

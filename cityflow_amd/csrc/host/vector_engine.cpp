@@ -634,6 +634,30 @@ void VectorEngineHost::observeLanesDevice(uintptr_t counts, uintptr_t waiting, u
           "cfx_observe_lanes_device");
 }
 
+const InterLayout &VectorEngineHost::intersectionLayout() {
+    if (!interLayout_) interLayout_.reset(new InterLayout(intersectionLayoutOf(*net_)));
+    return *interLayout_;
+}
+
+void VectorEngineHost::intersectionFeatures(const InterFeatures &out) {
+    const InterLayout &lay = intersectionLayout();
+    std::lock_guard<std::mutex> guard(queryMutex_);  // (the ABI is not re-entrant: the ahead thread may be asking the device)
+    intersectionFeaturesOf(be_, dev_, lay, R_, L_, (int) net_->laneLinks.size(), out);
+    raiseDeviceError();
+}
+
+void VectorEngineHost::observeIntersectionsDevice(uintptr_t phase, uintptr_t remain, uintptr_t in, uintptr_t inWaiting, uintptr_t out,
+                                                  uintptr_t inside, uintptr_t pressure, int maxRoadLinks, int maxPhases,
+                                                  uintptr_t consumerStream) {
+    if (!be_.hasDeviceBuffers() || !be_.cfx_observe_intersections_device)
+        throw std::runtime_error("cityflow_amd: '" + be_.path + "' has no device-side intersection observations");
+    std::lock_guard<std::mutex> guard(queryMutex_);
+    check(be_.cfx_observe_intersections_device(dev_, (int32_t *) phase, (double *) remain, (int32_t *) in, (int32_t *) inWaiting,
+                                               (int32_t *) out, (int32_t *) inside, (int32_t *) pressure, maxRoadLinks, maxPhases,
+                                               (void *) consumerStream),
+          "cfx_observe_intersections_device");
+}
+
 std::vector<int32_t> VectorEngineHost::phaseCounts() const {
     std::vector<int32_t> out((size_t) I_);
     for (int i = 0; i < I_; ++i) out[(size_t) i] = net_->inters[(size_t) i].isVirtual ? -1 : (int32_t) net_->inters[(size_t) i].phases.size();

@@ -51,6 +51,12 @@ public:
     void laneFeatures(double *speedSum, int32_t *bins, const double *edges, int nBins, bool perLaneEdges);
     void observeLanesDevice(uintptr_t counts, uintptr_t waiting, uintptr_t speedSum, uintptr_t bins, uintptr_t edges, int nBins,
                             bool perLaneEdges, uintptr_t consumerStream);
+    // per-intersection observations over every environment (EngineHost::intersectionFeatures and its kin): outputs [R * I ...];
+    // the layout is one environment's
+    const InterLayout &intersectionLayout();
+    void intersectionFeatures(const InterFeatures &out);
+    void observeIntersectionsDevice(uintptr_t phase, uintptr_t remain, uintptr_t in, uintptr_t inWaiting, uintptr_t out,
+                                    uintptr_t inside, uintptr_t pressure, int maxRoadLinks, int maxPhases, uintptr_t consumerStream);
     std::vector<std::string> laneIds() const;
     std::vector<std::string> intersectionIds() const;
     cfx_scalars scalars();
@@ -69,6 +75,7 @@ public:
 
 private:
     void check(int32_t rc, const char *what);
+    std::unique_ptr<InterLayout> interLayout_;  // built by the first call that needs it
     bool devicePhaseUnchecked_ = false;  // as EngineHost: read by every call below that has waited for the device
     void raiseDeviceError();             // (the caller holds queryMutex_)
 

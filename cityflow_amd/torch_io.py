@@ -1,4 +1,4 @@
-"""Lane observations and signal control as torch tensors (Engine and VectorEngine).
+"""Lane and intersection observations and signal control as torch tensors (Engine and VectorEngine).
 
     eng.get_lane_vehicle_count_tensor(out=None)          int32 [L]   (VectorEngine: [R, L])
     eng.get_lane_waiting_vehicle_count_tensor(out=None)  int32 [L]   (VectorEngine: [R, L])
@@ -7,6 +7,12 @@
     eng.get_lane_vehicle_bins_tensor(edges, out=None)    int32 [L, B] (VectorEngine: [R, L, B])
     eng.observe_lanes_tensor(counts=None, waiting=None, speed_sum=None, bins=None, edges=None)
                                                          fills every given tensor with one kernel launch
+    eng.observe_intersections_tensor(phase=None, phase_remain=None, movement_in=None, movement_in_waiting=None,
+                                     movement_out=None, movement_inside=None, phase_pressure=None)
+                                                         per-intersection observations, one kernel launch (see its docstring)
+    eng.get_tl_phases_tensor(out=None)                   int32 [I]   (VectorEngine: [R, I]): the reading side of set_tl_phases_tensor
+    eng.observe_intersections_array()                    the same seven outputs as numpy arrays (waits for the device)
+    eng.intersection_layout()                            the static signal plan and movement tables (host only, numpy)
 
 On the HIP engine the tensors live on the engine's GPU and nothing here waits for the device:
   * a getter's kernel writes the caller's tensor on the engine's stream after everything already enqueued there and on the
@@ -206,6 +212,95 @@ def get_lane_vehicle_bins_tensor(self, edges, out=None):
     return out
 
 
+INTERSECTION_OUTPUTS = ("phase", "phase_remain", "movement_in", "movement_in_waiting", "movement_out", "movement_inside",
+                        "phase_pressure")
+
+
+def _intersection_shapes(eng):
+    """{output: shape} of the seven intersection outputs ([R] in front on a VectorEngine)."""
+    lead = tuple(eng._tensor_shapes()[1])
+    n_roadlinks, n_phases = eng._intersection_dims()
+    shapes = {name: lead + (n_roadlinks,) for name in INTERSECTION_OUTPUTS[2:6]}
+    shapes["phase"] = shapes["phase_remain"] = lead
+    shapes["phase_pressure"] = lead + (n_phases,)
+    return shapes
+
+
+def observe_intersections_tensor(self, phase=None, phase_remain=None, movement_in=None, movement_in_waiting=None,
+                                 movement_out=None, movement_inside=None, phase_pressure=None):
+    """Fill every given tensor with one kernel launch on the engine's stream, ordered against the current torch stream as
+    observe_lanes_tensor.  Intersections in intersection_ids() order (I, virtual ones included); the roadLinks ("movements")
+    of intersection i in the roadnet file's order, m < M_i; its phases p < P_i; M = max M_i, P = max P_i (intersection_layout()).
+    IN(i, m) / OUT(i, m): the distinct start / end lanes of the roadLink's laneLinks (a lane counts once).
+
+        phase                int32 [I]      the current phase (0 at a virtual intersection)
+        phase_remain         float64 [I]    seconds the phase still has (TrafficLight::remainDuration)
+        movement_in          int32 [I, M]   vehicles on the lanes of IN(i, m), as get_lane_vehicle_count_array counts them
+        movement_in_waiting  int32 [I, M]   ... of them the waiting ones (speed < 0.1), as get_lane_waiting_vehicle_count_array
+        movement_out         int32 [I, M]   vehicles on the lanes of OUT(i, m)
+        movement_inside      int32 [I, M]   vehicles inside the intersection, on a laneLink of roadLink (i, m)
+        phase_pressure       int32 [I, P]   sum of movement_in - movement_out over the roadLinks phase p serves
+
+    Lane-change shadows count like vehicles, as in the count getters.  Padding: movement_*[i, m] = 0 for m >= M_i (a virtual
+    intersection has no roadLinks); phase_pressure[i, p] = INT32_MIN for p >= P_i and for every p of a virtual intersection, so
+    phase_pressure.argmax(-1) is a valid phase wherever one exists and can be handed to set_tl_phases_tensor as it is (entries
+    of virtual intersections are ignored there).  A phase that serves no roadLink has pressure 0, not the padding value.  Every
+    element is written, so the tensors need no zeroing.  VectorEngine: a leading [R] on every output.  At least one output;
+    every argument is checked before anything is enqueued."""
+    torch = _torch()
+    given = dict(zip(INTERSECTION_OUTPUTS, (phase, phase_remain, movement_in, movement_in_waiting, movement_out,
+                                            movement_inside, phase_pressure)))
+    if all(t is None for t in given.values()):
+        raise ValueError("observe_intersections_tensor: give at least one of " + ", ".join(INTERSECTION_OUTPUTS))
+    shapes = _intersection_shapes(self)
+    device = _engine_device(torch, self)
+    for name, t in given.items():
+        if t is not None:
+            _check_buf(torch, t, name, shapes[name], torch.float64 if name == "phase_remain" else torch.int32, device)
+    if not self._device_buffers():  # (the twin: over the array call)
+        arrays = self.observe_intersections_array()
+        for name, t in given.items():
+            if t is not None:
+                t.copy_(torch.from_numpy(arrays[name]))
+        return
+    n_roadlinks, n_phases = self._intersection_dims()
+    self._observe_intersections_device(*[0 if given[name] is None else given[name].data_ptr() for name in INTERSECTION_OUTPUTS],
+                                       n_roadlinks, n_phases, torch.cuda.current_stream(device).cuda_stream)
+
+
+def get_tl_phases_tensor(self, out=None):
+    """The current phase of every intersection (0 at virtual ones) as an int32 tensor [I] ([R, I] for VectorEngine) on the
+    engine's device, valid on the current torch stream: the `phase` output of observe_intersections_tensor alone, the reading
+    side of set_tl_phases_tensor.  `out`: a contiguous int32 tensor of that shape on that device, filled in place."""
+    torch = _torch()
+    if out is None:
+        out = torch.empty(tuple(self._tensor_shapes()[1]), dtype=torch.int32, device=_engine_device(torch, self))
+    observe_intersections_tensor(self, phase=out)
+    return out
+
+
+def observe_intersections_array(self):
+    """The seven outputs of observe_intersections_tensor as a dict of numpy arrays (same names, dtypes, shapes and padding);
+    waits for the device."""
+    shapes = _intersection_shapes(self)
+    return {name: a.reshape(shapes[name]) for name, a in zip(INTERSECTION_OUTPUTS, self._intersection_features())}
+
+
+def intersection_layout(self):
+    """The static tables behind observe_intersections_tensor, of ONE environment, as numpy arrays (host only):
+        n_roadlinks    int32 [I]          M_i (0 at a virtual intersection)
+        n_phases       int32 [I]          P_i, -1 = virtual
+        phase_avail    bool [I, P, M]     phase p of intersection i serves roadLink m (False in the padding)
+        roadlink_type  int32 [I, M]       1 turn right, 2 turn left, 3 go straight, 0 = padding
+        in_lanes       int32 [I, M, Kin]  IN(i, m) as indices into lane_ids(), ascending, -1 = padding
+        out_lanes      int32 [I, M, Kout] OUT(i, m) likewise"""
+    import numpy as np
+
+    d = dict(self._intersection_layout())
+    d["phase_avail"] = d["phase_avail"].astype(np.bool_)
+    return d
+
+
 def install(*classes):
     for cls in classes:
         cls.get_lane_vehicle_count_tensor = get_lane_vehicle_count_tensor
@@ -214,3 +309,7 @@ def install(*classes):
         cls.get_lane_speed_sum_tensor = get_lane_speed_sum_tensor
         cls.get_lane_vehicle_bins_tensor = get_lane_vehicle_bins_tensor
         cls.observe_lanes_tensor = observe_lanes_tensor
+        cls.observe_intersections_tensor = observe_intersections_tensor
+        cls.get_tl_phases_tensor = get_tl_phases_tensor
+        cls.observe_intersections_array = observe_intersections_array
+        cls.intersection_layout = intersection_layout

@@ -544,6 +544,32 @@ typedef int32_t (*cfx_get_lane_features_fn)(cfx_engine *e, double *speed_sum, in
                                             int32_t per_lane_edges);
 #define CFX_MAX_LANE_BINS 32
 
+/* ---- Per-intersection movement and phase observations (OPTIONAL entry points, as above).  Intersection i (n_inters of them,
+ * virtual ones included) has its roadLinks m < M_i = inter_n_roadlinks[i] ("movements", ll_roadlink) and its phases p < P_i
+ * (inter_phase_start; 0 for a virtual intersection).  IN(i, m) / OUT(i, m) are the DISTINCT start / end lanes of the roadLink's
+ * laneLinks.  Rows are padded to max_roadlinks = max M_i and max_phases = max P_i over the network; the caller passes both and
+ * gets CFX_ERR_INVALID when they are not the network's.
+ *   phase[i]                         int32: as cfx_get_tl_state
+ *   remain[i]                        double: as cfx_get_tl_state, a copy
+ *   in[i * max_roadlinks + m]        int32: sum of cfx_get_lane_counts over IN(i, m)
+ *   in_waiting[...]                  int32: sum of cfx_get_lane_waiting_counts over IN(i, m)
+ *   out[...]                         int32: sum of cfx_get_lane_counts over OUT(i, m)
+ *   inside[...]                      int32: vehicles on the laneLinks of roadLink (i, m)
+ *   phase_pressure[i * max_phases + p]  int32: sum of in - out over the roadLinks m with phase_avail[i][p][m]
+ * Padding: 0 in the four movement outputs for m >= M_i; INT32_MIN in phase_pressure for p >= P_i (a phase that serves no roadLink
+ * has 0).  Every element of a given output is written.
+ *   "cfx_observe_intersections_device"  any of the seven NULL (at least one given), all in device memory, written by ONE kernel
+ *                               on the engine's stream, ordered against consumer_stream as cfx_observe_device.  The first call
+ *                               builds and uploads the roadLink index (it waits for the device once).
+ *   "cfx_get_intersection_features"     the same outputs into host memory; synchronous (engine-owned device scratch, kept
+ *                               between calls). */
+typedef int32_t (*cfx_observe_intersections_device_fn)(cfx_engine *e, int32_t *phase, double *remain, int32_t *in, int32_t *in_waiting,
+                                                       int32_t *out, int32_t *inside, int32_t *phase_pressure, int32_t max_roadlinks,
+                                                       int32_t max_phases, void *consumer_stream);
+typedef int32_t (*cfx_get_intersection_features_fn)(cfx_engine *e, int32_t *phase, double *remain, int32_t *in, int32_t *in_waiting,
+                                                    int32_t *out, int32_t *inside, int32_t *phase_pressure, int32_t max_roadlinks,
+                                                    int32_t max_phases);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,468 @@
+"""Per-intersection movement and phase observations: observe_intersections_tensor / observe_intersections_array /
+get_tl_phases_tensor / intersection_layout on Engine and VectorEngine (cityflow_amd/torch_io.py,
+cfx_observe_intersections_device / cfx_get_intersection_features).
+
+Every value is an integer or a copy, so each check is array_equal.  The oracle is built HERE from the roadnet JSON
+(intersections[*].roadLinks[*].laneLinks, lane id "<road>_<index>", trafficLight.lightphases[*].availableRoadLinks) and the
+getters that existed before the feature (the two lane count arrays, _tl_state(), _vehicle_state()["drivable"] with
+_flat_net()'s ll_inter / ll_roadlink) — never from intersection_layout() or the feature's own arrays.  CPU tests pin the
+semantics on the twin (the host computes the arrays there); gpu tests run kr_intersection_features / kd_intersection_features."""
+import json
+import os
+import time
+
+import numpy as np
+import pytest
+
+from conftest import TWIN_LIB, assert_same_state
+
+torch = pytest.importorskip("torch")
+
+from test_device_tensors import tensor_device  # noqa: E402
+from test_irregular import irregular  # noqa: E402
+from test_lane_features import twin  # noqa: E402
+
+PAD = np.iinfo(np.int32).min
+NAMES = ("phase", "phase_remain", "movement_in", "movement_in_waiting", "movement_out", "movement_inside", "phase_pressure")
+TYPES = {"turn_right": 1, "turn_left": 2, "go_straight": 3}
+
+
+# ------------------------------------------------------------------------------------------------------------------ oracle
+def roadnet_of(cfg):
+    with open(cfg) as f:
+        c = json.load(f)
+    with open(os.path.join(c["dir"], c["roadnetFile"])) as f:
+        return json.load(f)
+
+
+def edited_grid(scen, workdir, **config):
+    """grid_6x6 with phase 0 of every intersection serving no roadLink and the phase lists cut to 6, 7 or 8 phases."""
+    base = scen.materialize("grid_6x6", workdir)
+    net = roadnet_of(base)
+    for it in net["intersections"]:
+        if it["virtual"]:
+            continue
+        tl = it["trafficLight"]
+        tl["lightphases"] = tl["lightphases"][: 8 - (len(it["id"]) + int(it["id"][-1])) % 3]
+        tl["lightphases"][0]["availableRoadLinks"] = []
+    with open(os.path.join(os.path.dirname(base), "roadnet_edited.json"), "w") as f:
+        json.dump(net, f)
+    return scen.materialize("grid_6x6", workdir, roadnetFile="roadnet_edited.json", **config)
+
+
+class Tables:
+    """The static layout from the JSON, in the engine's intersection and lane order."""
+
+    def __init__(self, eng, cfg):
+        net = roadnet_of(cfg)
+        lane = {lid: i for i, lid in enumerate(eng.lane_ids())}
+        by_id = {it["id"]: it for it in net["intersections"]}
+        inters = [by_id[i] for i in eng.intersection_ids()]
+        self.I = len(inters)
+        self.ins, self.outs, self.types, self.phases = [], [], [], []
+        for it in inters:
+            rls = [] if it["virtual"] else it["roadLinks"]
+            self.ins.append([sorted({lane["%s_%d" % (rl["startRoad"], ll["startLaneIndex"])] for ll in rl["laneLinks"]}) for rl in rls])
+            self.outs.append([sorted({lane["%s_%d" % (rl["endRoad"], ll["endLaneIndex"])] for ll in rl["laneLinks"]}) for rl in rls])
+            self.types.append([TYPES[rl["type"]] for rl in rls])
+            self.phases.append(None if it["virtual"] else [sorted(set(ph["availableRoadLinks"])) for ph in it["trafficLight"]["lightphases"]])
+        self.M = max([len(x) for x in self.ins] + [0])
+        self.P = max([len(p) for p in self.phases if p is not None] + [0])
+
+    def layout(self):
+        kin = max([len(x) for rl in self.ins for x in rl] + [0])
+        kout = max([len(x) for rl in self.outs for x in rl] + [0])
+        d = {"n_roadlinks": np.array([len(x) for x in self.ins], dtype=np.int32),
+             "n_phases": np.array([-1 if p is None else len(p) for p in self.phases], dtype=np.int32),
+             "phase_avail": np.zeros((self.I, self.P, self.M), dtype=np.bool_),
+             "roadlink_type": np.zeros((self.I, self.M), dtype=np.int32),
+             "in_lanes": np.full((self.I, self.M, kin), -1, dtype=np.int32),
+             "out_lanes": np.full((self.I, self.M, kout), -1, dtype=np.int32)}
+        for i in range(self.I):
+            for m, (a, b, t) in enumerate(zip(self.ins[i], self.outs[i], self.types[i])):
+                d["roadlink_type"][i, m] = t
+                d["in_lanes"][i, m, :len(a)] = a
+                d["out_lanes"][i, m, :len(b)] = b
+            for p, served in enumerate(self.phases[i] or []):
+                d["phase_avail"][i, p, served] = True
+        return d
+
+    def observe(self, eng):
+        """The seven outputs from the getters that existed before the feature."""
+        counts = eng.get_lane_vehicle_count_array().astype(np.int64)
+        waiting = eng.get_lane_waiting_vehicle_count_array().astype(np.int64)
+        phase, remain = eng._tl_state()
+        flat = eng._flat_net()
+        o = {"phase": np.asarray(phase, dtype=np.int32), "phase_remain": np.asarray(remain, dtype=np.float64)}
+        for k in NAMES[2:6]:
+            o[k] = np.zeros((self.I, self.M), dtype=np.int32)
+        o["phase_pressure"] = np.full((self.I, self.P), PAD, dtype=np.int32)
+        for i in range(self.I):
+            for m, (a, b) in enumerate(zip(self.ins[i], self.outs[i])):
+                o["movement_in"][i, m] = counts[a].sum()
+                o["movement_in_waiting"][i, m] = waiting[a].sum()
+                o["movement_out"][i, m] = counts[b].sum()
+        L = len(counts)
+        for d in eng._vehicle_state()["drivable"]:
+            if d >= L:
+                o["movement_inside"][flat["ll_inter"][d - L], flat["ll_roadlink"][d - L]] += 1
+        diff = o["movement_in"].astype(np.int64) - o["movement_out"]
+        for i in range(self.I):
+            for p, served in enumerate(self.phases[i] or []):
+                o["phase_pressure"][i, p] = diff[i, served].sum()
+        return o
+
+
+def empty_outputs(eng, tables, lead=()):
+    device = tensor_device(eng)
+    shapes = {k: lead + (tables.I, tables.M) for k in NAMES[2:6]}
+    shapes["phase"] = shapes["phase_remain"] = lead + (tables.I,)
+    shapes["phase_pressure"] = lead + (tables.I, tables.P)
+    # (filled with a value no output takes: every element must be written)
+    return {k: torch.full(shapes[k], -7, dtype=torch.float64 if k == "phase_remain" else torch.int32, device=device) for k in NAMES}
+
+
+def check_outputs(eng, tables, where, want=None):
+    """array call and tensor call against the oracle; returns the oracle's outputs."""
+    want = tables.observe(eng) if want is None else want
+    got = eng.observe_intersections_array()
+    assert sorted(got) == sorted(NAMES)
+    for k in NAMES:
+        assert got[k].dtype == want[k].dtype and got[k].shape == want[k].shape, "%s: %s is %s %s" % (where, k, got[k].dtype, got[k].shape)
+        assert np.array_equal(got[k], want[k]), "%s: %s differs (array call)" % (where, k)
+    t = empty_outputs(eng, tables)
+    eng.observe_intersections_tensor(**t)
+    for k in NAMES:
+        assert np.array_equal(t[k].cpu().numpy(), want[k]), "%s: %s differs (tensor call)" % (where, k)
+    # a request without movement_in_waiting (no vehicle record is read), and the phase getter
+    t = empty_outputs(eng, tables)
+    part = {k: t[k] for k in ("movement_in", "movement_out", "movement_inside", "phase_pressure")}
+    eng.observe_intersections_tensor(**part)
+    for k in part:
+        assert np.array_equal(part[k].cpu().numpy(), want[k]), "%s: %s differs (counts-only call)" % (where, k)
+    ph = eng.get_tl_phases_tensor()
+    assert ph.dtype == torch.int32 and np.array_equal(ph.cpu().numpy(), want["phase"]), "%s: get_tl_phases_tensor" % where
+    assert eng.get_tl_phases_tensor(out=t["phase"]) is t["phase"]
+    return want
+
+
+class Seen:
+    """What a run must have looked at (asserted, never skipped on)."""
+
+    def __init__(self):
+        self.inside = self.waiting = self.pressure_varies = 0
+        self.phases = None
+
+    def add(self, want):
+        self.inside += int(want["movement_inside"].sum())
+        self.waiting += int(want["movement_in_waiting"].sum())
+        pp = want["phase_pressure"]
+        for row in pp:
+            real = row[row != PAD]
+            self.pressure_varies += int(real.size > 1 and real.min() != real.max())
+        if self.phases is None:
+            self.phases = [set() for _ in want["phase"]]
+        for s, p in zip(self.phases, want["phase"]):
+            s.add(int(p))
+
+    def check(self, phases_change=True):
+        assert self.inside > 0, "no vehicle was ever inside an intersection at a check"
+        assert self.waiting > 0, "no vehicle was ever waiting on an IN lane at a check"
+        assert self.pressure_varies > 0, "phase_pressure was constant along p everywhere"
+        if phases_change:
+            assert max(len(s) for s in self.phases) >= 2, "no intersection showed two phases"
+
+
+def run_against_oracle(eng, cfg, steps, every, where, phases_change=True):
+    tables = Tables(eng, cfg)
+    seen = Seen()
+    for s in range(steps):
+        eng.next_step()
+        if s % every == every - 1:
+            seen.add(check_outputs(eng, tables, "%s, step %d" % (where, s)))
+    seen.check(phases_change)
+    return seen
+
+
+# ---------------------------------------------------------------------------------------------------------------- CPU (twin)
+def layout_cases(scen, workdir):
+    return [("grid_6x6", scen.materialize("grid_6x6", workdir)), ("example_1x1", scen.materialize("example_1x1", workdir)),
+            ("irregular 11", irregular(scen, workdir, 11)), ("irregular 12", irregular(scen, workdir, 12)),
+            ("edited grid_6x6", edited_grid(scen, workdir))]
+
+
+def test_layout_equals_the_roadnet_json(mod, scen, workdir):
+    sizes, phase_counts = set(), set()
+    for name, cfg in layout_cases(scen, workdir):
+        eng = twin(mod, cfg)
+        want = Tables(eng, cfg).layout()
+        got = eng.intersection_layout()
+        assert sorted(got) == sorted(want), name
+        for k in want:
+            assert got[k].dtype == want[k].dtype and got[k].shape == want[k].shape, "%s: %s is %s %s, want %s %s" % (
+                name, k, got[k].dtype, got[k].shape, want[k].dtype, want[k].shape)
+            assert np.array_equal(got[k], want[k]), "%s: %s differs" % (name, k)
+        assert np.array_equal(got["n_phases"], eng._phase_counts()), name
+        if name.startswith("irregular"):
+            sizes |= set(int(x) for x in want["n_roadlinks"])
+        if name.startswith("edited"):
+            phase_counts = set(int(x) for x in want["n_phases"])
+            assert not want["phase_avail"][:, 0, :].any()
+    assert len(sizes - {0}) >= 3, sizes  # (roadLinks dropped: the rows are ragged)
+    assert phase_counts == {-1, 6, 7, 8}, phase_counts
+    vec = mod.VectorEngine._with_backend(scen.materialize("grid_6x6", workdir), 2, 1, TWIN_LIB)
+    one = twin(mod, scen.materialize("grid_6x6", workdir)).intersection_layout()
+    for k, v in vec.intersection_layout().items():  # (of ONE environment)
+        assert np.array_equal(v, one[k]), k
+
+
+def test_outputs_equal_the_oracle_twin(mod, scen, workdir):
+    cfg = scen.materialize("grid_6x6", workdir)
+    run_against_oracle(twin(mod, cfg), cfg, 60, 10, "grid_6x6")
+    cfg = irregular(scen, workdir, 11)
+    run_against_oracle(twin(mod, cfg), cfg, 200, 25, "irregular 11")
+    cfg = edited_grid(scen, workdir)
+    run_against_oracle(twin(mod, cfg), cfg, 150, 10, "edited grid_6x6")  # (phase 0 serves nobody for the first 30 s)
+
+
+def test_vector_engine_equals_standalone_twins(mod, scen, workdir):
+    vec = mod.VectorEngine._with_backend(scen.materialize("grid_6x6", workdir), 3, 1, TWIN_LIB)
+    cfgs = [scen.materialize("grid_6x6", workdir, seed=e) for e in range(3)]
+    singles = [twin(mod, c) for c in cfgs]
+    tables = Tables(singles[0], cfgs[0])
+    for s in range(60):
+        vec.next_step()
+        for e in singles:
+            e.next_step()
+        if s % 10 != 9:
+            continue
+        want = [tables.observe(e) for e in singles]
+        got = vec.observe_intersections_array()
+        t = empty_outputs(vec, tables, lead=(3,))
+        vec.observe_intersections_tensor(**t)
+        for k in NAMES:
+            w = np.stack([x[k] for x in want])
+            assert got[k].shape == w.shape and got[k].dtype == w.dtype, k
+            assert np.array_equal(got[k], w), "step %d: %s (array)" % (s, k)
+            assert np.array_equal(t[k].numpy(), w), "step %d: %s (tensor)" % (s, k)
+        assert np.array_equal(vec.get_tl_phases_tensor().numpy(), np.stack([x["phase"] for x in want]))
+
+
+def test_argument_errors_twin(mod, scen, workdir):
+    cfg = scen.materialize("grid_6x6", workdir)
+    eng = twin(mod, cfg)
+    vec = mod.VectorEngine._with_backend(cfg, 2, 1, TWIN_LIB)
+    tables = Tables(eng, cfg)
+    I, M, P = tables.I, tables.M, tables.P
+    for s in range(5):
+        eng.next_step()
+    with pytest.raises(ValueError):
+        eng.observe_intersections_tensor()
+    with pytest.raises(TypeError):
+        eng.observe_intersections_tensor(phase=torch.zeros(I, dtype=torch.int64))
+    with pytest.raises(TypeError):
+        eng.observe_intersections_tensor(phase_remain=torch.zeros(I, dtype=torch.float32))
+    with pytest.raises(TypeError):
+        eng.observe_intersections_tensor(movement_in=np.zeros((I, M), dtype=np.int32))
+    if torch.cuda.is_available():
+        with pytest.raises(TypeError):  # (the twin's tensors live on the CPU)
+            eng.observe_intersections_tensor(movement_in=torch.zeros((I, M), dtype=torch.int32, device="cuda"))
+    with pytest.raises(TypeError):
+        eng.observe_intersections_tensor(movement_in=torch.zeros((I, M), dtype=torch.int32, device="meta"))
+    with pytest.raises(ValueError):
+        eng.observe_intersections_tensor(movement_in=torch.zeros((I, M + 1), dtype=torch.int32))
+    with pytest.raises(ValueError):
+        eng.observe_intersections_tensor(phase_pressure=torch.zeros((I, P + 1), dtype=torch.int32))
+    with pytest.raises(ValueError):
+        eng.observe_intersections_tensor(movement_out=torch.zeros((M, I), dtype=torch.int32).t())  # not contiguous
+    with pytest.raises(ValueError):
+        vec.observe_intersections_tensor(movement_in=torch.zeros((I, M), dtype=torch.int32))  # [R, I, M] wanted
+    with pytest.raises(ValueError):
+        vec.get_tl_phases_tensor(out=torch.zeros(I, dtype=torch.int32))
+    # nothing is written when a later argument is wrong
+    good = torch.full((I, M), -7, dtype=torch.int32)
+    with pytest.raises(ValueError):
+        eng.observe_intersections_tensor(movement_in=good, phase_pressure=torch.zeros((I, P + 2), dtype=torch.int32))
+    assert bool((good == -7).all())
+
+
+def check_single_sets_show(eng, tables):
+    """set_tl_phase calls are buffered on the host until the next call that needs them: a phase read is such a call."""
+    real = [i for i, p in enumerate(tables.phases) if p is not None]
+    ids = eng.intersection_ids()
+    for s in range(3):
+        eng.next_step()
+    for n, i in enumerate(real[:5]):
+        eng.set_tl_phase(ids[i], 1 + n % 3)
+    got = eng.get_tl_phases_tensor().cpu().numpy()
+    for n, i in enumerate(real[:5]):
+        assert got[i] == 1 + n % 3, "intersection %s shows phase %d" % (ids[i], got[i])
+    eng.set_tl_phase(ids[real[0]], 4)
+    assert eng.observe_intersections_array()["phase"][real[0]] == 4
+    assert np.array_equal(eng.get_tl_phases_tensor().cpu().numpy(), eng._tl_state()[0])
+
+
+def test_phase_reads_see_pending_single_sets_twin(mod, scen, workdir):
+    cfg = scen.materialize("grid_6x6", workdir, rlTrafficLight=True)
+    eng = twin(mod, cfg)
+    check_single_sets_show(eng, Tables(eng, cfg))
+
+
+def test_import_does_not_import_torch():
+    import subprocess
+    import sys
+
+    from conftest import ROOT
+    code = ("import sys, cityflow_amd; assert 'torch' not in sys.modules, 'torch imported'; "
+            "assert hasattr(cityflow_amd.Engine, 'observe_intersections_tensor'); "
+            "assert hasattr(cityflow_amd.VectorEngine, 'get_tl_phases_tensor')")
+    subprocess.check_call([sys.executable, "-c", code], cwd=ROOT)
+
+
+# ---------------------------------------------------------------------------------------------------------------- GPU
+@pytest.mark.gpu
+@pytest.mark.parametrize("layout", ["auto", "dense"])
+@pytest.mark.parametrize("net", ["grid_6x6", "edited"])
+def test_outputs_equal_the_oracle_grid_6x6(mod, scen, workdir, layout, net):
+    extra = {} if layout == "auto" else {"cfx": {"layout": "dense"}}
+    cfg = scen.materialize("grid_6x6", workdir, **extra) if net == "grid_6x6" else edited_grid(scen, workdir, **extra)
+    eng = mod.Engine(cfg, 1)
+    if eng._device_buffers():
+        assert eng._layout() == ("ring" if layout == "auto" else "dense")
+    run_against_oracle(eng, cfg, 300, 25, "%s %s" % (net, layout))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("layout", ["ring", "dense"])
+def test_outputs_on_the_bench_workload(mod, workdir, layout):
+    import bench
+    extra = {} if layout == "ring" else {"cfx": {"layout": "dense"}}
+    cfg = bench.with_config(bench.build_workload(workdir, 0), "intersections_" + layout, **extra)
+    eng = mod.Engine(cfg, 1)
+    if eng._device_buffers():
+        assert eng._layout() == layout
+    run_against_oracle(eng, cfg, 100, 50, "bench %s" % layout, phases_change=False)  # (two checks only)
+    assert eng.get_vehicle_count() > 10000
+
+
+@pytest.mark.gpu
+def test_outputs_with_lane_change_dense(mod, scen, workdir):
+    cfg = scen.materialize("grid_6x6", workdir, laneChange=True)
+    eng = mod.Engine(cfg, 1)
+    if eng._device_buffers():
+        assert eng._layout() == "dense"
+    run_against_oracle(eng, cfg, 200, 20, "lane change")
+    assert eng.get_vehicle_count() > 0
+
+
+@pytest.mark.gpu
+def test_hip_outputs_equal_twin(mod, scen, workdir):
+    cfg = scen.materialize("grid_6x6", workdir)
+    eng, tw = mod.Engine(cfg, 1), twin(mod, cfg)
+    tables = Tables(tw, cfg)
+    for s in range(240):
+        eng.next_step()
+        tw.next_step()
+        if s % 30 != 29:
+            continue
+        want = tw.observe_intersections_array()
+        got = eng.observe_intersections_array()
+        t = empty_outputs(eng, tables)
+        eng.observe_intersections_tensor(**t)
+        for k in NAMES:
+            assert np.array_equal(got[k], want[k]), "step %d: %s (array)" % (s, k)
+            assert np.array_equal(t[k].cpu().numpy(), want[k]), "step %d: %s (tensor)" % (s, k)
+
+
+@pytest.mark.gpu
+def test_phase_reads_see_pending_single_sets(mod, scen, workdir):
+    cfg = scen.materialize("grid_6x6", workdir, rlTrafficLight=True)
+    eng = mod.Engine(cfg, 1)
+    check_single_sets_show(eng, Tables(eng, cfg))
+
+
+def first_argmax(pp):
+    """argmax along the last axis with the first maximum winning (numpy's rule, and torch's)."""
+    return np.argmax(pp, axis=-1).astype(np.int32)
+
+
+@pytest.mark.gpu
+def test_max_pressure_closed_loop(mod, scen, workdir):
+    cfg = scen.materialize("grid_6x6", workdir, rlTrafficLight=True)
+    dev, ref = mod.Engine(cfg, 1), mod.Engine(cfg, 1)
+    tables = Tables(ref, cfg)
+    device = tensor_device(dev)
+    pp = torch.empty((tables.I, tables.P), dtype=torch.int32, device=device)
+    seen = Seen()
+    for s in range(200):
+        dev.observe_intersections_tensor(phase_pressure=pp)
+        choice = pp.argmax(-1)
+        dev.set_tl_phases_tensor(choice)
+        want = tables.observe(ref)
+        seen.add(want)
+        assert np.array_equal(pp.cpu().numpy(), want["phase_pressure"]), "phase_pressure differs at step %d" % s
+        host_choice = first_argmax(want["phase_pressure"])
+        assert np.array_equal(choice.cpu().numpy(), host_choice), "argmax differs at step %d" % s
+        ref.set_tl_phases(host_choice)
+        dev.next_step()
+        ref.next_step()
+    seen.check()
+    assert_same_state(dev, ref, "after the max-pressure loop")
+
+
+@pytest.mark.gpu
+def test_vector_engine_tensors_equal_standalone(mod, scen, workdir):
+    vec = mod.VectorEngine(scen.materialize("grid_6x6", workdir), 4)
+    cfgs = [scen.materialize("grid_6x6", workdir, seed=e) for e in range(4)]
+    singles = [mod.Engine(c, 1) for c in cfgs]
+    tables = Tables(singles[0], cfgs[0])
+    for s in range(150):
+        vec.next_step()
+        for e in singles:
+            e.next_step()
+        if s % 30 != 29:
+            continue
+        want = [tables.observe(e) for e in singles]
+        t = empty_outputs(vec, tables, lead=(4,))
+        vec.observe_intersections_tensor(**t)
+        got = vec.observe_intersections_array()
+        for k in NAMES:
+            w = np.stack([x[k] for x in want])
+            assert np.array_equal(t[k].cpu().numpy(), w), "step %d: %s (tensor)" % (s, k)
+            assert np.array_equal(got[k], w), "step %d: %s (array)" % (s, k)
+
+
+@pytest.mark.gpu
+def test_intersections_on_a_side_stream_without_a_host_wait(mod, scen, workdir):
+    cfg = scen.materialize("grid_6x6", workdir, rlTrafficLight=True)
+    eng, ref = mod.Engine(cfg, 1), mod.Engine(cfg, 1)
+    if not eng._device_buffers():
+        pytest.skip("needs device buffers: torch streams do not exist on the twin")
+    tables = Tables(ref, cfg)
+    for s in range(20):  # warm: rings built, tables uploaded, the first observation taken
+        eng.next_step()
+        ref.next_step()
+    t = empty_outputs(eng, tables)
+    eng.observe_intersections_tensor(**t)
+    eng.sync()
+    device = tensor_device(eng)
+    torch.cuda.synchronize(device)
+    side = torch.cuda.Stream(device=device)
+    records = []
+    eng._device_spin(200000)  # 200 ms of device work in front of everything below
+    t0 = time.perf_counter()
+    with torch.cuda.stream(side):
+        for s in range(8):
+            eng.next_step()
+            eng.observe_intersections_tensor(**t)
+            records.append({k: v.clone() for k, v in t.items()})  # consumed on `side`, then the outputs are reused
+    elapsed = time.perf_counter() - t0
+    assert elapsed < 0.1, "the loop waited for the device (%.1f ms for 8 iterations behind a 200 ms spin)" % (elapsed * 1e3)
+    side.synchronize()
+    eng.sync()
+    for s in range(8):
+        ref.next_step()
+        want = tables.observe(ref)
+        for k in NAMES:
+            assert np.array_equal(records[s][k].cpu().numpy(), want[k]), "step %d: %s" % (s, k)
+    assert_same_state(eng, ref, "after the unsynchronised loop")

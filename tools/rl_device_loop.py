@@ -4,7 +4,12 @@ RL network (bench.py's 30x30 workload, rlTrafficLight) and on VectorEngine 16 x 
 usage: python tools/rl_device_loop.py [--iters N] [--envs R]      (the probe tools/rl_probe.py is the numpy side's own story)
        python tools/rl_device_loop.py --features [--features-only all|counts_waiting]
 --features: observe_lanes_tensor (one launch of kr_lane_features) against the two count getters, on the Engine only;
---features-only runs just that observe_lanes_tensor loop (with all four outputs, B = 3, or counts + waiting), for a kernel trace."""
+--features-only runs just that observe_lanes_tensor loop (with all four outputs, B = 3, or counts + waiting), for a kernel trace.
+       python tools/rl_device_loop.py --intersections [--runs N] [--intersections-only lanes|four|seven|no_waiting]
+--intersections: a max-pressure loop built two ways, alternated --runs times — A: observe_lanes_tensor(counts, waiting) and torch
+ops over index tensors made once (movement_in, movement_in_waiting, movement_out, phase_pressure); B: observe_intersections_tensor
+with the same four outputs (one launch of kr_intersection_features), and with all seven; A's tensors are asserted equal to B's
+first.  --intersections-only runs one of the loops alone, for a kernel trace."""
 import argparse
 import os
 import sys
@@ -20,6 +25,9 @@ ap.add_argument("--envs", type=int, default=16)
 ap.add_argument("--skip-vector", action="store_true")
 ap.add_argument("--features", action="store_true")
 ap.add_argument("--features-only", choices=["all", "counts_waiting"], default=None)
+ap.add_argument("--intersections", action="store_true")
+ap.add_argument("--intersections-only", choices=["lanes", "four", "seven", "no_waiting"], default=None)
+ap.add_argument("--runs", type=int, default=3)
 args = ap.parse_args()
 sys.argv = [sys.argv[0]]
 import bench  # noqa: E402
@@ -143,6 +151,94 @@ def features(name, eng, n, only):
     print("%-66s %8.2fx" % ("2 getters loop / observe_lanes_tensor(counts, waiting) loop", a / b), flush=True)
     print("%-66s %8.2fx" % ("2 getters loop / observe_lanes_tensor(all four) loop", a / c), flush=True)
 
+
+def intersections(name, eng, n, runs, only):
+    device = torch.device("cuda", eng._stream_handle()[1])
+    lay = eng.intersection_layout()
+    L = len(eng.lane_ids())
+    I, P, M = lay["phase_avail"].shape
+    pad = torch.iinfo(torch.int32).min
+    # loop A's tables: lane indices with the padding pointing at one extra, always-zero element behind the counts
+    in_idx = torch.from_numpy(np.where(lay["in_lanes"] >= 0, lay["in_lanes"], L)).to(device).long()
+    out_idx = torch.from_numpy(np.where(lay["out_lanes"] >= 0, lay["out_lanes"], L)).to(device).long()
+    avail = torch.from_numpy(lay["phase_avail"].astype(np.int32)).to(device)
+    no_phase = torch.from_numpy(np.arange(P)[None, :] >= np.maximum(lay["n_phases"], 0)[:, None]).to(device)
+    c1 = torch.zeros(L + 1, dtype=torch.int32, device=device)
+    w1 = torch.zeros(L + 1, dtype=torch.int32, device=device)
+    a_out = {}
+
+    def loop_a(s):
+        eng.observe_lanes_tensor(counts=c1[:L], waiting=w1[:L])
+        a_out["in"] = c1[in_idx].sum(-1, dtype=torch.int32)
+        a_out["wait"] = w1[in_idx].sum(-1, dtype=torch.int32)
+        a_out["out"] = c1[out_idx].sum(-1, dtype=torch.int32)
+        pp = (avail * (a_out["in"] - a_out["out"])[:, None, :]).sum(-1, dtype=torch.int32)
+        a_out["pp"] = pp.masked_fill(no_phase, pad)
+        eng.set_tl_phases_tensor(a_out["pp"].argmax(-1))
+        eng.next_step()
+
+    b = {k: torch.empty((I, M), dtype=torch.int32, device=device) for k in ("in", "wait", "out", "inside")}
+    b["pp"] = torch.empty((I, P), dtype=torch.int32, device=device)
+    b["phase"] = torch.empty(I, dtype=torch.int32, device=device)
+    b["remain"] = torch.empty(I, dtype=torch.float64, device=device)
+
+    def observe_four():
+        eng.observe_intersections_tensor(movement_in=b["in"], movement_in_waiting=b["wait"], movement_out=b["out"],
+                                         phase_pressure=b["pp"])
+
+    def loop_b(observe):
+        def body(s):
+            observe()
+            eng.set_tl_phases_tensor(b["pp"].argmax(-1))
+            eng.next_step()
+        return body
+
+    def observe_seven():
+        eng.observe_intersections_tensor(phase=b["phase"], phase_remain=b["remain"], movement_in=b["in"], movement_in_waiting=b["wait"],
+                                         movement_out=b["out"], movement_inside=b["inside"], phase_pressure=b["pp"])
+
+    def observe_no_waiting():
+        eng.observe_intersections_tensor(phase=b["phase"], phase_remain=b["remain"], movement_in=b["in"], movement_out=b["out"],
+                                         movement_inside=b["inside"], phase_pressure=b["pp"])
+
+    def lanes_only(s):  # (kr_lane_features beside the new kernel in one trace)
+        eng.observe_lanes_tensor(counts=c1[:L], waiting=w1[:L])
+        eng.next_step()
+
+    for _ in range(300):
+        eng.next_step()
+    eng.sync()
+    print("# %s" % name, flush=True)
+    if only:
+        body = {"lanes": lanes_only, "four": loop_b(observe_four), "seven": loop_b(observe_seven),
+                "no_waiting": loop_b(observe_no_waiting)}[only]
+        measure("intersections loop: %s" % only, eng, body, n)
+        return
+    observe_four()
+    loop_a(0)  # (observes the same state, then steps)
+    torch.cuda.synchronize()
+    for k in ("in", "wait", "out", "pp"):
+        assert torch.equal(a_out[k], b[k]), "loop A's %s differs from observe_intersections_tensor's" % k
+    print("loop A's four tensors equal loop B's", flush=True)
+    measure("next_step alone", eng, lambda s: eng.next_step(), n)
+    res = {"A": [], "B4": [], "B7": []}
+    for r in range(runs):
+        res["A"].append(measure("A  observe_lanes_tensor + torch ops -> argmax -> set -> next_step (run %d)" % r, eng, loop_a, n))
+        res["B4"].append(measure("B  observe_intersections_tensor(4) -> argmax -> set -> next_step (run %d)" % r, eng, loop_b(observe_four), n))
+        res["B7"].append(measure("B  observe_intersections_tensor(7) -> argmax -> set -> next_step (run %d)" % r, eng, loop_b(observe_seven), n))
+    measure("observe_intersections_tensor(7) alone (1 launch + events)", eng, lambda s: observe_seven(), n)
+    measure("observe_lanes_tensor(counts, waiting) alone (1 launch + events)", eng,
+            lambda s: eng.observe_lanes_tensor(counts=c1[:L], waiting=w1[:L]), n)
+    for k, v in res.items():
+        print("%-4s median %8.1f us   min %8.1f   max %8.1f   (spread %.1f)" % (k, float(np.median(v)), min(v), max(v), max(v) - min(v)),
+              flush=True)
+
+
+if args.intersections or args.intersections_only:
+    e = _cityflow.Engine(cfg, 1)
+    intersections("Engine, 30x30 RL workload (%d signals, %d lanes)" % (len(e.intersection_ids()), len(e.lane_ids())), e, args.iters,
+                  args.runs, args.intersections_only)
+    sys.exit(0)
 
 if args.features or args.features_only:
     e = _cityflow.Engine(cfg, 1)
