@@ -150,6 +150,11 @@ struct cfx_engine {
     InterFeatOut interTab{};        // the table pointers and M / P; the output pointers stay null here
     int32_t *interOutI = nullptr;   // [I * (1 + 4 M + P)] phase, in, in_waiting, out, inside, phase_pressure
     double *interOutD = nullptr;    // [I]
+    // cfx_lane_flow_enable: per-lane flow statistics across steps (laneFlowTick, cfx_kernels.h).  Nothing is allocated or launched
+    // while it is off.  `flow.rec` grows with the vehicle tables (ensureVidCap); `flow.tick` is the last tick taken and only
+    // ever counts up; `flowBaseline`: a baseline is due before the next step or read (enabling, reset, cfx_load_state)
+    bool flowOn = false, flowBaseline = false;
+    LaneFlowDev flow{};
     int cross2 = -1;                // cross phase: 1 = k_cross2 (throughput), 0 = k_cross (latency), -1 = by size
     HostMirror *hMirror = nullptr;  // pinned; valid while the last thing that changed the scalars was a step
     bool mirrorValid = false;
@@ -492,6 +497,10 @@ struct cfx_engine {
         // nextWait of not-yet-used vids must read -1 (k_spawn_link relies on it)
         HIP_TRY(hipMemsetAsync(vt.nextWait + spawned, 0xFF, (nc - (size_t) spawned) * sizeof(int32_t), stream));
         if (ring) HIP_TRY(hipMemsetAsync(slotOf + spawned, 0xFF, (nc - (size_t) spawned) * sizeof(int32_t), stream));
+        if (flowOn) {  // (records of numbers not used yet name lane -1: they match no lane)
+            if ((rc = growDeferred(&flow.rec, (size_t) spawned, nc))) return rc;
+            HIP_TRY(hipMemsetAsync(flow.rec + spawned, 0xFF, (nc - (size_t) spawned) * sizeof(int4), stream));
+        }
         vidCap = nc;
         return CFX_OK;
     }
@@ -761,6 +770,25 @@ struct cfx_engine {
         }
         return rh;
     }
+    // cfx_lane_flow_enable: one tick (or baseline) on the committed state, after everything enqueued so far
+    int flowTick(bool baseline) {
+        flow.tick += 1;
+        flow.step = (int32_t) step;
+        flow.baseline = baseline ? 1 : 0;
+        flow.vidCap = (int) vidCap;
+        if (L <= 0) return CFX_OK;
+        const size_t threads = (size_t) L * kFeatGroup;
+        if (ring) hipLaunchKernelGGL(kr_lane_flow, dim3(gridFor(threads)), dim3(kBlock), 0, stream, rctx(), flow);
+        else hipLaunchKernelGGL(kd_lane_flow, dim3(gridFor(threads)), dim3(kBlock), 0, stream, ctx(), flow);
+        HIP_TRY(hipGetLastError());
+        return CFX_OK;
+    }
+    // ... the baseline that enabling, a reset or a load left to the next step or read (the caller has settled the step and the rings)
+    int flowSettle() {
+        if (!flowOn || !flowBaseline) return CFX_OK;
+        flowBaseline = false;
+        return flowTick(true);
+    }
     int settle(bool withHistory = true) {
         if (haloImportPending) {
             haloImportPending = false;
@@ -945,6 +973,7 @@ struct cfx_engine {
         if (vidCap) HIP_TRY(hipMemsetAsync(vt.nextWait, 0xFF, vidCap * sizeof(int32_t), stream));
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipStreamSynchronize(stream));
+        flowBaseline = flowOn;  // (taken on the state the caller sets up, before the next step or read)
         return CFX_OK;
     }
 };
@@ -1321,6 +1350,7 @@ static int32_t stepImpl(cfx_engine *e, const cfx_spawn *recs, int32_t n) {
         if (e->mirrorValid && __atomic_load_n(&e->hMirror->sc.ringNearFull, __ATOMIC_RELAXED) != 0) e->ringGrowRequested = true;
         if ((rc = e->ringEnsure())) return rc;
     }
+    if ((rc = e->flowSettle())) return rc;  // (lane flow: a baseline that is due is taken on the state this step starts from)
     if (e->observing && ++e->observeIdle > cfx_engine::kObserveIdle) {  // nobody has read the lane counts for a while
         e->observing = false;
         e->hCntValid = false;
@@ -1568,7 +1598,7 @@ static int32_t stepImpl(cfx_engine *e, const cfx_spawn *recs, int32_t n) {
         const bool useBig = e->cross2 >= 0 ? e->cross2 == 1 : activeEst > 240000;  // which form of the cross phase (§4)
         // This step's commit rides with the next step's admission (one launch less per step) where the step runs kr_cross,
         // which then advances the lights; the previous step's, if it is still pending, goes with this step's admission.
-        const bool deferCommit = e->ringMerge && !dbg && !e->tiled && !e->observing && !e->devObserving;  // (a caller that reads the lane counts after every step wants the commit now)
+        const bool deferCommit = e->ringMerge && !dbg && !e->tiled && !e->observing && !e->devObserving && !e->flowOn;  // (a caller that reads the lane counts after every step wants the commit now; so does the lane-flow tick)
         // tiling: the previous step's halo import, if cfx_halo_wait left it to this launch
         const RingHaloIn hin = e->haloImportPending ? e->pendingImport : RingHaloIn{};
         e->haloImportPending = false;
@@ -1749,6 +1779,7 @@ static int32_t stepImpl(cfx_engine *e, const cfx_spawn *recs, int32_t n) {
         e->step += 1;
         e->mirrorValid = !e->tiled;
         e->histPending = e->hist.num != 0;  // (this step's Lane::history: with the next action launch, or settle() — on a tile behind the step's halo import)
+        if (e->flowOn) return e->flowTick(false);
         return CFX_OK;
     }
     const int64_t spare = e->tiled ? e->spareTotal : (int64_t) e->L;
@@ -1895,6 +1926,7 @@ static int32_t stepImpl(cfx_engine *e, const cfx_spawn *recs, int32_t n) {
         hipLaunchKernelGGL(k_lane_history, dim3(gridFor(e->L)), dim3(kBlock), 0, st, e->ctx(), e->hist);
         HIP_TRY(hipGetLastError());
     }
+    if (e->flowOn) return e->flowTick(false);
     return CFX_OK;
 }
 extern "C" {
@@ -3490,6 +3522,146 @@ int32_t cfx_get_intersection_features(cfx_engine *e, int32_t *phase, double *rem
     HIP_TRY(back(inside, dInside, nM * sizeof(int32_t)));
     HIP_TRY(back(pressure, dPressure, nP * sizeof(int32_t)));
     HIP_TRY(hipStreamSynchronize(e->stream));
+    return CFX_OK;
+}
+
+// ---- per-lane flow and waiting-time statistics across steps (optional entry points of include/cityflow_amd.h, as above)
+int32_t cfx_lane_flow_enable(cfx_engine *e, int32_t on);
+int32_t cfx_observe_lane_flow_device(cfx_engine *e, int32_t *entered, int32_t *left, int64_t *leftSteps, int64_t *leftWaitingSteps,
+                                     int64_t *waitingSteps, int32_t *maxWaitingSteps, int32_t reset, void *consumerStream);
+int32_t cfx_get_lane_flow(cfx_engine *e, int32_t *entered, int32_t *left, int64_t *leftSteps, int64_t *leftWaitingSteps,
+                          int64_t *waitingSteps, int32_t *maxWaitingSteps, int32_t reset);
+int32_t cfx_lane_flow_get_state(cfx_engine *e, int32_t *records, int32_t nVehicles, cfx_lane_flow_lane *lanes, int32_t *tick);
+int32_t cfx_lane_flow_set_state(cfx_engine *e, const int32_t *records, int32_t nVehicles, const cfx_lane_flow_lane *lanes, int32_t tick);
+static_assert(std::is_same<decltype(&cfx_lane_flow_enable), cfx_lane_flow_enable_fn>::value, "cfx_lane_flow_enable");
+static_assert(std::is_same<decltype(&cfx_observe_lane_flow_device), cfx_observe_lane_flow_device_fn>::value, "cfx_observe_lane_flow_device");
+static_assert(std::is_same<decltype(&cfx_get_lane_flow), cfx_get_lane_flow_fn>::value, "cfx_get_lane_flow");
+static_assert(std::is_same<decltype(&cfx_lane_flow_get_state), cfx_lane_flow_get_state_fn>::value, "cfx_lane_flow_get_state");
+static_assert(std::is_same<decltype(&cfx_lane_flow_set_state), cfx_lane_flow_set_state_fn>::value, "cfx_lane_flow_set_state");
+static_assert(sizeof(cfx_lane_flow_lane) == 48, "cfx_lane_flow_lane");
+
+// what every reader does first: the step's commit, the rings, a baseline that is due
+static int laneFlowPrepare(cfx_engine *e, const char *what) {
+    if (!e->flowOn) {
+        e->err = std::string(what) + ": lane-flow tracking is off (cfx_lane_flow_enable)";
+        return CFX_ERR_STATE;
+    }
+    int rc;
+    if ((rc = e->settle(false))) return rc;
+    if (e->ring && (rc = e->ringEnsure())) return rc;
+    return e->flowSettle();
+}
+
+int32_t cfx_lane_flow_enable(cfx_engine *e, int32_t on) {
+    if (!e) return CFX_ERR_INVALID;
+    auto fail = [e](const std::string &m) { return e->fail(m); };
+    HIP_TRY(hipSetDevice(e->device));
+    if (!on) {
+        if (!e->flowOn) return CFX_OK;
+        HIP_TRY(hipStreamSynchronize(e->stream));  // (a tick may still be running; a record array a growth retired stays with `retired`)
+        e->forget(e->flow.rec);
+        e->forget(e->flow.lane);
+        HIP_TRY(hipFree(e->flow.rec));
+        HIP_TRY(hipFree(e->flow.lane));
+        e->flow = LaneFlowDev{};
+        e->flowOn = e->flowBaseline = false;
+        return CFX_OK;
+    }
+    if (e->lc.on || e->tiled) {
+        e->err = "cfx_lane_flow_enable: not with lane change and not on a tile";
+        return CFX_ERR_STATE;
+    }
+    if (e->flowOn) return CFX_OK;
+    int rc;
+    if ((rc = e->settle(false))) return rc;
+    if (e->ring && (rc = e->ringEnsure())) return rc;
+    if ((rc = e->allocRaw(&e->flow.rec, e->vidCap))) return rc;
+    if ((rc = e->allocRaw(&e->flow.lane, (size_t) e->L))) return rc;
+    HIP_TRY(hipMemsetAsync(e->flow.rec, 0xFF, std::max<size_t>(e->vidCap, 1) * sizeof(int4), e->stream));
+    HIP_TRY(hipMemsetAsync(e->flow.lane, 0, std::max<size_t>((size_t) e->L, 1) * sizeof(cfx_lane_flow_lane), e->stream));
+    e->flow.tick = 0;
+    e->flowOn = e->flowBaseline = true;
+    return e->flowSettle();
+}
+
+static void launchLaneFlowDrain(cfx_engine *e, const LaneFlowOut &o, int32_t reset) {
+    if (e->L <= 0) return;
+    hipLaunchKernelGGL(k_lane_flow_drain, dim3(gridFor((size_t) e->L)), dim3(kBlock), 0, e->stream, e->flow.lane, e->L, o, reset ? 1 : 0);
+}
+
+int32_t cfx_observe_lane_flow_device(cfx_engine *e, int32_t *entered, int32_t *left, int64_t *leftSteps, int64_t *leftWaitingSteps,
+                                     int64_t *waitingSteps, int32_t *maxWaitingSteps, int32_t reset, void *consumerStream) {
+    if (!e || (!entered && !left && !leftSteps && !leftWaitingSteps && !waitingSteps && !maxWaitingSteps && !reset)) return CFX_ERR_INVALID;
+    auto fail = [e](const std::string &m) { return e->fail(m); };
+    HIP_TRY(hipSetDevice(e->device));
+    int rc;
+    if (entered && (rc = checkDevicePointer(e, entered, "cfx_observe_lane_flow_device: entered"))) return rc;
+    if (left && (rc = checkDevicePointer(e, left, "cfx_observe_lane_flow_device: left"))) return rc;
+    if (leftSteps && (rc = checkDevicePointer(e, leftSteps, "cfx_observe_lane_flow_device: left_steps"))) return rc;
+    if (leftWaitingSteps && (rc = checkDevicePointer(e, leftWaitingSteps, "cfx_observe_lane_flow_device: left_waiting_steps"))) return rc;
+    if (waitingSteps && (rc = checkDevicePointer(e, waitingSteps, "cfx_observe_lane_flow_device: waiting_steps"))) return rc;
+    if (maxWaitingSteps && (rc = checkDevicePointer(e, maxWaitingSteps, "cfx_observe_lane_flow_device: max_waiting_steps"))) return rc;
+    if ((rc = laneFlowPrepare(e, "cfx_observe_lane_flow_device"))) return rc;
+    if ((rc = e->orderAfterCaller((hipStream_t) consumerStream))) return rc;
+    launchLaneFlowDrain(e, LaneFlowOut{entered, left, leftSteps, leftWaitingSteps, waitingSteps, maxWaitingSteps}, reset);
+    HIP_TRY(hipGetLastError());
+    return e->orderCallerAfter((hipStream_t) consumerStream);
+}
+
+int32_t cfx_get_lane_flow(cfx_engine *e, int32_t *entered, int32_t *left, int64_t *leftSteps, int64_t *leftWaitingSteps,
+                          int64_t *waitingSteps, int32_t *maxWaitingSteps, int32_t reset) {
+    if (!e) return CFX_ERR_INVALID;
+    auto fail = [e](const std::string &m) { return e->fail(m); };
+    HIP_TRY(hipSetDevice(e->device));
+    int rc;
+    if ((rc = laneFlowPrepare(e, "cfx_get_lane_flow"))) return rc;
+    // (the records themselves come back, 48 bytes per lane: no device scratch, and the kernel only has to zero)
+    std::vector<cfx_lane_flow_lane> lanes((size_t) e->L);
+    if (e->L > 0) HIP_TRY(hipMemcpyAsync(lanes.data(), e->flow.lane, lanes.size() * sizeof(cfx_lane_flow_lane), hipMemcpyDeviceToHost, e->stream));
+    if (reset) {
+        launchLaneFlowDrain(e, LaneFlowOut{}, 1);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    for (size_t l = 0; l < lanes.size(); ++l) {
+        if (entered) entered[l] = lanes[l].entered;
+        if (left) left[l] = lanes[l].left;
+        if (leftSteps) leftSteps[l] = lanes[l].left_steps;
+        if (leftWaitingSteps) leftWaitingSteps[l] = lanes[l].left_waiting_steps;
+        if (waitingSteps) waitingSteps[l] = lanes[l].waiting_steps;
+        if (maxWaitingSteps) maxWaitingSteps[l] = lanes[l].max_waiting_steps;
+    }
+    return CFX_OK;
+}
+
+int32_t cfx_lane_flow_get_state(cfx_engine *e, int32_t *records, int32_t nVehicles, cfx_lane_flow_lane *lanes, int32_t *tick) {
+    if (!e || !lanes || !tick || nVehicles < 0 || (nVehicles > 0 && !records)) return CFX_ERR_INVALID;
+    auto fail = [e](const std::string &m) { return e->fail(m); };
+    HIP_TRY(hipSetDevice(e->device));
+    int rc;
+    if ((rc = laneFlowPrepare(e, "cfx_lane_flow_get_state"))) return rc;
+    if ((size_t) nVehicles > e->vidCap) return e->fail("cfx_lane_flow_get_state: n_vehicles beyond the vehicle tables"), CFX_ERR_INVALID;
+    if (nVehicles) HIP_TRY(hipMemcpyAsync(records, e->flow.rec, (size_t) nVehicles * sizeof(int4), hipMemcpyDeviceToHost, e->stream));
+    if (e->L > 0) HIP_TRY(hipMemcpyAsync(lanes, e->flow.lane, (size_t) e->L * sizeof(cfx_lane_flow_lane), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    *tick = e->flow.tick;
+    return CFX_OK;
+}
+
+int32_t cfx_lane_flow_set_state(cfx_engine *e, const int32_t *records, int32_t nVehicles, const cfx_lane_flow_lane *lanes, int32_t tick) {
+    if (!e || !lanes || nVehicles < 0 || (nVehicles > 0 && !records)) return CFX_ERR_INVALID;
+    auto fail = [e](const std::string &m) { return e->fail(m); };
+    HIP_TRY(hipSetDevice(e->device));
+    if (!e->flowOn) return e->fail("cfx_lane_flow_set_state: lane-flow tracking is off (cfx_lane_flow_enable)"), CFX_ERR_STATE;
+    if ((size_t) nVehicles > e->vidCap) return e->fail("cfx_lane_flow_set_state: n_vehicles beyond the vehicle tables"), CFX_ERR_INVALID;
+    int rc;
+    if ((rc = e->settle(false))) return rc;
+    HIP_TRY(hipMemsetAsync(e->flow.rec, 0xFF, std::max<size_t>(e->vidCap, 1) * sizeof(int4), e->stream));
+    if (nVehicles) HIP_TRY(hipMemcpyAsync(e->flow.rec, records, (size_t) nVehicles * sizeof(int4), hipMemcpyHostToDevice, e->stream));
+    if (e->L > 0) HIP_TRY(hipMemcpyAsync(e->flow.lane, lanes, (size_t) e->L * sizeof(cfx_lane_flow_lane), hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    e->flow.tick = tick;
+    e->flowBaseline = false;
     return CFX_OK;
 }
 

@@ -2298,6 +2298,120 @@ __global__ void __launch_bounds__(kBlock) kd_lane_features(StepCtx c, LaneFeatOu
     laneFeatures(o, lane, c.cnt[lane], sub, stage + (threadIdx.x - sub), laneRec(c, lane));
 }
 
+// cfx_lane_flow_enable: per-lane flow and waiting-time statistics across steps (include/cityflow_amd.h has the rules).  One TICK
+// after every step, on the committed state: a group of kFeatGroup threads walks one lane as laneFeatures does, sixteen
+// neighbouring vehicles at a time, and each thread does the read-modify-write of its vehicle's 16-byte record
+// rec[vid] = {lane, tick last seen on it, since, wait}.  "On this lane at the previous tick" is lane == this lane and tick ==
+// this tick - 1 (ticks only ever count up, so a record left by an earlier visit, an earlier episode or an unused vehicle number
+// never matches); a vehicle is on one lane, so its record has one writer.  The vehicles that LEFT are no longer here and are
+// not looked for: the lane keeps its previous count, sum of since and sum of wait, and what left is the difference —
+//   left = count' + entered - count,   sum over leavers of since = S' + s entered - S,   ... of wait = W' - (W - increments)
+// exact in integers, one writer per lane (the group's first thread, behind in-group shuffles).
+struct LaneFlowDev {
+    int4 *rec;                 // [vidCap]
+    cfx_lane_flow_lane *lane;  // [L]
+    int vidCap;
+    int32_t tick, step;
+    int baseline;              // every vehicle: since = step, wait = 0, not entered; accumulators zero
+};
+
+struct DenseLaneVid {  // vehicle number of the lane's i-th vehicle from the front
+    const int32_t *vid;
+    int base;
+    __device__ __forceinline__ int operator()(int i) const { return vid[base + i]; }
+};
+__device__ __forceinline__ DenseLaneVid laneVid(const StepCtx &c, int lane) { return DenseLaneVid{c.s.vid, c.segStart[lane]}; }
+
+// (a 64-bit sum goes through the group as two 32-bit shuffles: the library's 64-bit shuffle stages its halves in scratch)
+__device__ __forceinline__ long long featShflXor64(long long v, int off) {
+    const unsigned lo = (unsigned) __shfl_xor((int) (unsigned long long) v, off, kFeatGroup);
+    const unsigned hi = (unsigned) __shfl_xor((int) ((unsigned long long) v >> 32), off, kFeatGroup);
+    return (long long) (((unsigned long long) hi << 32) | lo);
+}
+
+// (`f` by value: taken by reference, the kernel argument is staged in scratch)
+template <typename Rec, typename Vid>
+__device__ __forceinline__ void laneFlowTick(const LaneFlowDev f, int lane, int n, int sub, Rec rec, Vid vidOf) {
+    cfx_lane_flow_lane a{};
+    if (sub == 0) a = f.lane[lane];  // (requested before the walk, used behind it)
+    int entered = 0, inc = 0, mx = 0;
+    long long S = 0, W = 0;
+    for (int i = sub; i < n; i += kFeatGroup) {
+        const int v = vidOf(i);
+        if ((unsigned) v >= (unsigned) f.vidCap) continue;  // (never: every vehicle on a lane has a number the tables hold)
+        const bool waiting = rec(i).y < 0.1;
+        const int4 r = f.rec[v];
+        int since = r.z, wait = r.w;
+        if (f.baseline || r.x != lane || r.y != f.tick - 1) {
+            since = f.step;
+            wait = 0;
+            entered += 1;
+        }
+        if (waiting && !f.baseline) {
+            wait += 1;
+            inc += 1;
+        }
+        f.rec[v] = make_int4(lane, f.tick, since, wait);
+        S += since;
+        W += wait;
+        mx = max(mx, wait);
+    }
+    for (int off = kFeatGroup / 2; off > 0; off >>= 1) {
+        entered += __shfl_xor(entered, off, kFeatGroup);
+        inc += __shfl_xor(inc, off, kFeatGroup);
+        mx = max(mx, __shfl_xor(mx, off, kFeatGroup));
+        S += featShflXor64(S, off);
+        W += featShflXor64(W, off);
+    }
+    if (sub != 0) return;
+    if (f.baseline) {
+        a.left_steps = a.left_waiting_steps = 0;
+        a.entered = a.left = 0;
+    } else {
+        const int left = a.count + entered - n;
+        a.entered += entered;
+        a.left += left;
+        a.left_steps += (long long) f.step * left - (a.since_sum + (long long) f.step * entered - S);
+        a.left_waiting_steps += a.waiting_steps - (W - inc);
+    }
+    a.since_sum = S;
+    a.waiting_steps = W;
+    a.count = n;
+    a.max_waiting_steps = mx;
+    f.lane[lane] = a;
+}
+
+__global__ void __launch_bounds__(kBlock) kd_lane_flow(StepCtx c, LaneFlowDev f) {
+    const int lane = (int) ((blockIdx.x * (size_t) blockDim.x + threadIdx.x) / kFeatGroup);
+    if (lane >= c.n.L) return;  // (whole groups)
+    laneFlowTick(f, lane, c.cnt[lane], threadIdx.x % kFeatGroup, laneRec(c, lane), laneVid(c, lane));
+}
+
+// cfx_observe_lane_flow_device / cfx_get_lane_flow: the tick left every output in the lane's record; this copies (any pointer may
+// be null) and, with `reset`, zeroes the four interval accumulators it has just read.  One thread per lane.
+struct LaneFlowOut {
+    int32_t *entered, *left;
+    int64_t *leftSteps, *leftWaitingSteps, *waitingSteps;
+    int32_t *maxWaitingSteps;
+};
+__global__ void __launch_bounds__(kBlock) k_lane_flow_drain(cfx_lane_flow_lane *lanes, int L, LaneFlowOut o, int reset) {
+    const int lane = (int) (blockIdx.x * (size_t) blockDim.x + threadIdx.x);
+    if (lane >= L) return;
+    const cfx_lane_flow_lane a = lanes[lane];
+    if (o.entered) o.entered[lane] = a.entered;
+    if (o.left) o.left[lane] = a.left;
+    if (o.leftSteps) o.leftSteps[lane] = a.left_steps;
+    if (o.leftWaitingSteps) o.leftWaitingSteps[lane] = a.left_waiting_steps;
+    if (o.waitingSteps) o.waitingSteps[lane] = a.waiting_steps;
+    if (o.maxWaitingSteps) o.maxWaitingSteps[lane] = a.max_waiting_steps;
+    if (reset) {
+        lanes[lane].left_steps = 0;
+        lanes[lane].left_waiting_steps = 0;
+        lanes[lane].entered = 0;
+        lanes[lane].left = 0;
+    }
+}
+
 // cfx_observe_intersections_device / cfx_get_intersection_features: what a signal policy observes, per intersection, in one
 // launch (any output may be null; every element of a given output has exactly one writer, padding included, so the caller's
 // buffers need no zeroing and there is no atomic).  One BLOCK owns one intersection; its sixteen groups of kFeatGroup threads

@@ -2357,6 +2357,21 @@ __global__ void __launch_bounds__(kBlock) kr_lane_features(RingCtx c, LaneFeatOu
     laneFeatures(o, lane, c.cnt[lane], sub, stage + (threadIdx.x - sub), laneRec(c, lane));
 }
 
+// cfx_lane_flow_enable, ring layout: laneFlowTick (cfx_kernels.h) over the lane's ring, the vehicle numbers from the cold `vid` column
+struct RingLaneVid {  // vehicle number of the lane's i-th vehicle from the front
+    const int32_t *vid;
+    int2 geo;
+    int head;
+    __device__ __forceinline__ int operator()(int i) const { return vid[ringSlot(geo, head, i)]; }
+};
+__device__ __forceinline__ RingLaneVid laneVid(const RingCtx &c, int lane) { return RingLaneVid{c.s.vid, c.ringGeo[lane], c.head[lane]}; }
+
+__global__ void __launch_bounds__(kBlock) kr_lane_flow(RingCtx c, LaneFlowDev f) {
+    const int lane = (int) ((blockIdx.x * (size_t) blockDim.x + threadIdx.x) / kFeatGroup);
+    if (lane >= c.n.L) return;  // (whole groups)
+    laneFlowTick(f, lane, c.cnt[lane], threadIdx.x % kFeatGroup, laneRec(c, lane), laneVid(c, lane));
+}
+
 // cfx_observe_intersections_device / cfx_get_intersection_features, ring layout: interFeatures (cfx_kernels.h) over the rings
 __global__ void __launch_bounds__(kBlock) kr_intersection_features(RingCtx c, InterFeatOut o) {
     extern __shared__ int32_t interDiff[];

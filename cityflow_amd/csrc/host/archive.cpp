@@ -492,12 +492,19 @@ void EngineHost::compactVehicles() {
         if (newOfOld[(size_t) v] >= 0) state[(size_t) newOfOld[(size_t) v]] = d.vState[(size_t) v];
     d.vState.swap(state);
     a.host = spawner_.compactedState(newOfOld, nLive);
+    // lane-flow statistics: a load takes a baseline, a compaction must not show — the tracker as it stands goes round the load
+    LaneFlowState flow;
+    if (flow_.on()) {
+        flow = flow_.state(nV);
+        flow.renumber(newOfOld, nLive);
+    }
     // custom speeds of vehicles that are STILL waiting (cfx_state carries those of running vehicles only)
     std::map<int32_t, double> stillWaiting;
     for (const auto &kv : waitingCustom_)
         if (kv.first >= 0 && kv.first < nV && newOfOld[(size_t) kv.first] >= 0 && d.vState[(size_t) newOfOld[(size_t) kv.first]] == 0)
             stillWaiting[newOfOld[(size_t) kv.first]] = kv.second;
     load(a);
+    if (flow_.on()) flow_.setState(flow);
     for (const auto &kv : stillWaiting) check(be_.cfx_set_vehicle_speed(dev_, kv.first, kv.second), "cfx_set_vehicle_speed");
     waitingCustom_.swap(stillWaiting);
     vehicleCompactions_ += 1;
@@ -570,6 +577,7 @@ void EngineHost::load(const Archive &a) {
         check(be_.cfx_set_lane_history(dev_, &h), "cfx_set_lane_history");
     }
     step_ = (size_t) d.step;
+    flow_.baseline((int64_t) step_);
     waitingCustom_.clear();  // (compactVehicles puts back what it carries over)
     vehicleEpoch_ += 1;  // vehicle numbers of the archive replace the current ones
     // An archive taken earlier holds fewer vehicle numbers than the state it replaces: the next compaction is due that many

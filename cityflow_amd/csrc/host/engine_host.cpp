@@ -95,6 +95,11 @@ void Backend::open(const std::string &libPath) {
     CFX_FN_OPTIONAL(cfx_get_lane_features)
     CFX_FN_OPTIONAL(cfx_observe_intersections_device)
     CFX_FN_OPTIONAL(cfx_get_intersection_features)
+    CFX_FN_OPTIONAL(cfx_lane_flow_enable)
+    CFX_FN_OPTIONAL(cfx_observe_lane_flow_device)
+    CFX_FN_OPTIONAL(cfx_get_lane_flow)
+    CFX_FN_OPTIONAL(cfx_lane_flow_get_state)
+    CFX_FN_OPTIONAL(cfx_lane_flow_set_state)
 #undef CFX_FN_OPTIONAL
     if (cfx_abi_version() != CFX_ABI_VERSION)
         throw std::runtime_error("cityflow_amd: ABI version mismatch in '" + libPath + "'");
@@ -241,6 +246,7 @@ EngineHost::EngineHost(const std::string &configFile, int threadNum, const std::
         return st == 2;
     });
     uploadNewTablesIfAny();
+    flow_.bind(&be_, dev_, (int) net_->lanes.size());
 }
 
 EngineHost::~EngineHost() {
@@ -379,6 +385,7 @@ void EngineHost::nextStep() {
         }
     } note{this, lap, step_};
     step_ += 1;
+    flow_.afterStep((int64_t) step_);  // (the host tracker's tick; a backend that keeps the tracker has ticked inside cfx_step)
     // The finished vehicles are forgotten once enough have been created since the last time (archive.cpp compactVehicles): the
     // reference frees a vehicle when it finishes; here host and device remember every vehicle number until then.
     // What it costs is proportional to the vehicles ALIVE (a snapshot and a load: ~0.15-0.3 us per vehicle), so the automatic
@@ -682,6 +689,29 @@ void intersectionFeaturesOf(const Backend &be, cfx_engine *dev, const InterLayou
     }
 }
 
+void EngineHost::trackLaneFlow(bool on) {
+    if (on && laneChange_) throw std::logic_error("track_lane_flow: not with laneChange (a shadow changes identity when its change finishes)");
+    flow_.enable(on, (int64_t) step_);
+}
+
+// (like the count getters, these leave the step prepared ahead in place)
+void EngineHost::laneFlowFeatures(const LaneFlowOut &out, bool reset) {
+    flow_.features(out, reset);
+    raiseDeviceError();
+}
+
+void EngineHost::observeLaneFlowDevice(uintptr_t entered, uintptr_t left, uintptr_t leftSteps, uintptr_t leftWaitingSteps,
+                                       uintptr_t waitingSteps, uintptr_t maxWaitingSteps, bool reset, uintptr_t consumerStream) {
+    LaneFlowOut o;
+    o.entered = (int32_t *) entered;
+    o.left = (int32_t *) left;
+    o.leftSteps = (int64_t *) leftSteps;
+    o.leftWaitingSteps = (int64_t *) leftWaitingSteps;
+    o.waitingSteps = (int64_t *) waitingSteps;
+    o.maxWaitingSteps = (int32_t *) maxWaitingSteps;
+    flow_.observeDevice(o, reset, consumerStream);
+}
+
 const InterLayout &EngineHost::intersectionLayout() {
     if (!interLayout_) interLayout_.reset(new InterLayout(intersectionLayoutOf(*net_)));
     return *interLayout_;
@@ -765,6 +795,7 @@ void EngineHost::reset(bool resetRnd) {
     nextCompactAt_ = compactAt_;
     step_ = 0;
     vehicleEpoch_ += 1;
+    flow_.baseline(0);
 }
 
 // ---------------------------------------------------------------- getters

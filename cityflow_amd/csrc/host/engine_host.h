@@ -15,6 +15,7 @@
 #include "archive.h"
 #include "cityflow_amd.h"
 #include "flow.h"
+#include "lane_flow.h"
 #include "replay.h"
 #include "roadnet.h"
 
@@ -87,6 +88,12 @@ struct Backend {
     // optional as a pair: per-intersection observations (without them the host computes the arrays from the getters above)
     cfx_observe_intersections_device_fn cfx_observe_intersections_device = nullptr;
     cfx_get_intersection_features_fn cfx_get_intersection_features = nullptr;
+    // optional as a set: per-lane flow statistics kept by the backend (without them the host keeps them: lane_flow.h)
+    cfx_lane_flow_enable_fn cfx_lane_flow_enable = nullptr;
+    cfx_observe_lane_flow_device_fn cfx_observe_lane_flow_device = nullptr;
+    cfx_get_lane_flow_fn cfx_get_lane_flow = nullptr;
+    cfx_lane_flow_get_state_fn cfx_lane_flow_get_state = nullptr;
+    cfx_lane_flow_set_state_fn cfx_lane_flow_set_state = nullptr;
     void open(const std::string &libPath);  // throws std::runtime_error
     ~Backend();
 };
@@ -204,6 +211,13 @@ public:
     void intersectionFeatures(const InterFeatures &out);  // any pointer may be null
     void observeIntersectionsDevice(uintptr_t phase, uintptr_t remain, uintptr_t in, uintptr_t inWaiting, uintptr_t out,
                                     uintptr_t inside, uintptr_t pressure, int maxRoadLinks, int maxPhases, uintptr_t consumerStream);
+    // ---- per-lane flow and waiting-time statistics across steps (lane_flow.h; the torch layer is cityflow_amd/torch_io.py).
+    //      Off by default; a baseline when it is turned on and after reset / load; vehicle compaction carries it along
+    void trackLaneFlow(bool on);
+    bool laneFlowTracking() const { return flow_.on(); }
+    void laneFlowFeatures(const LaneFlowOut &out, bool reset);  // any pointer may be null
+    void observeLaneFlowDevice(uintptr_t entered, uintptr_t left, uintptr_t leftSteps, uintptr_t leftWaitingSteps,
+                               uintptr_t waitingSteps, uintptr_t maxWaitingSteps, bool reset, uintptr_t consumerStream);
     // Lane::history as the device keeps it ("cfx": {"laneHistory": true}; cfx_get_lane_history): lane-major, oldest record first
     void laneHistory(std::vector<int32_t> &len, std::vector<int32_t> &vehicleNum, std::vector<double> &averageSpeed,
                      std::vector<int32_t> &historyVehicleNum, std::vector<double> &historyAverageSpeed);
@@ -310,6 +324,7 @@ private:
     std::vector<int32_t> laneIdOrder_;
     uint64_t vehicleEpoch_ = 0;
     std::unique_ptr<InterLayout> interLayout_;  // built by the first call that needs it
+    LaneFlow flow_;
 };
 
 struct EngineConfig {  // Engine::loadConfig engine.cpp:37-84

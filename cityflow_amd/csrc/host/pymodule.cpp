@@ -305,6 +305,24 @@ template <typename E> py::dict intersectionLayoutDict(E &e) {
     return d;
 }
 
+// ---- per-lane flow statistics across steps (Engine and VectorEngine; the public calls are cityflow_amd/torch_io.py)
+inline py::ssize_t laneFlowLanes(EngineHost &e) { return (py::ssize_t) e.net().lanes.size(); }
+inline py::ssize_t laneFlowLanes(cfa::VectorEngineHost &e) { return (py::ssize_t) e.numEnvs() * e.numLanes(); }
+template <typename E> py::tuple laneFlowTuple(E &e, bool reset) {
+    const py::ssize_t n = laneFlowLanes(e);
+    py::array_t<int32_t> entered(n), left(n), maxWait(n);
+    py::array_t<int64_t> leftSteps(n), leftWait(n), waitNow(n);
+    cfa::LaneFlowOut o;
+    o.entered = entered.mutable_data();
+    o.left = left.mutable_data();
+    o.leftSteps = leftSteps.mutable_data();
+    o.leftWaitingSteps = leftWait.mutable_data();
+    o.waitingSteps = waitNow.mutable_data();
+    o.maxWaitingSteps = maxWait.mutable_data();
+    e.laneFlowFeatures(o, reset);
+    return py::make_tuple(entered, left, leftSteps, leftWait, waitNow, maxWait);
+}
+
 // Device buffers: raw pointers and streams under the tensor methods of cityflow_amd/torch_io.py (Engine and VectorEngine alike)
 template <typename E> void defDeviceBuffers(py::class_<E> &c) {
     c.def("_device_buffers", &E::deviceBuffers, "the backend takes observations / signals in device memory")
@@ -319,7 +337,22 @@ template <typename E> void defDeviceBuffers(py::class_<E> &c) {
              "(largest roadLink count, largest phase count) of an intersection: the row lengths of the intersection observations")
         .def("_intersection_layout", [](E &e) { return intersectionLayoutDict(e); })
         .def("_observe_intersections_device", &E::observeIntersectionsDevice, "phase_ptr"_a, "remain_ptr"_a, "in_ptr"_a,
-             "in_waiting_ptr"_a, "out_ptr"_a, "inside_ptr"_a, "pressure_ptr"_a, "max_roadlinks"_a, "max_phases"_a, "consumer_stream"_a);
+             "in_waiting_ptr"_a, "out_ptr"_a, "inside_ptr"_a, "pressure_ptr"_a, "max_roadlinks"_a, "max_phases"_a, "consumer_stream"_a)
+        .def("_track_lane_flow",
+             [](E &e, bool on) {
+                 try {
+                     e.trackLaneFlow(on);
+                 } catch (const std::logic_error &x) {  // (lane change: out of scope, not a failure of the call)
+                     PyErr_SetString(PyExc_NotImplementedError, x.what());
+                     throw py::error_already_set();
+                 }
+             },
+             "on"_a)
+        .def("_lane_flow_tracking", &E::laneFlowTracking)
+        .def("_lane_flow_features", [](E &e, bool reset) { return laneFlowTuple(e, reset); }, "reset"_a,
+             "(entered, left, left_steps, left_waiting_steps, waiting_steps, max_waiting_steps), flat (env-major)")
+        .def("_observe_lane_flow_device", &E::observeLaneFlowDevice, "entered_ptr"_a, "left_ptr"_a, "left_steps_ptr"_a,
+             "left_waiting_steps_ptr"_a, "waiting_steps_ptr"_a, "max_waiting_steps_ptr"_a, "reset"_a, "consumer_stream"_a);
 }
 
 // Engine.set_tl_phase(intersection_id, phase_id) (reference src/cityflow.cpp:35, engine.cpp:719-725) as a vectorcall method of its

@@ -179,6 +179,7 @@ VectorEngineHost::VectorEngineHost(const std::string &configFile, int numEnvs, i
         check(be_.cfx_add_routes(dev_, routesPerEnv_, rt.routeStart.data(), roads.data(), rt.nextStart.data(), nextLL.data()),
               "cfx_add_routes");
     }
+    flow_.bind(&be_, dev_, R_ * L_);
 }
 
 VectorEngineHost::~VectorEngineHost() {
@@ -520,6 +521,10 @@ void VectorEngineHost::nextStep() {
     hostTranslateSec_ += translateSec;
     hostSubmitSec_ += std::chrono::duration<double>(t3 - t2).count();
     step_ += 1;
+    if (flow_.on() && !flow_.onDevice()) {  // (the host tracker's tick; a backend that keeps the tracker has ticked inside cfx_step)
+        std::lock_guard<std::mutex> guard(queryMutex_);
+        flow_.afterStep((int64_t) step_);
+    }
 }
 
 void VectorEngineHost::reset(bool resetRnd) {
@@ -537,6 +542,10 @@ void VectorEngineHost::reset(bool resetRnd) {
     for (auto &v : localToGlobal_) v.clear();
     globalToLocal_.clear();
     step_ = 0;
+    {
+        std::lock_guard<std::mutex> guard(queryMutex_);
+        flow_.baseline(0);
+    }
     submitted_.store(0, std::memory_order_release);
     hostSpawnSec_ = hostTranslateSec_ = hostSubmitSec_ = 0;
     hostAheadSec_.store(0.0, std::memory_order_relaxed);
@@ -632,6 +641,31 @@ void VectorEngineHost::observeLanesDevice(uintptr_t counts, uintptr_t waiting, u
     check(be_.cfx_observe_lanes_device(dev_, (int32_t *) counts, (int32_t *) waiting, (double *) speedSum, (int32_t *) bins,
                                        (const double *) edges, nBins, perLaneEdges ? 1 : 0, (void *) consumerStream),
           "cfx_observe_lanes_device");
+}
+
+void VectorEngineHost::trackLaneFlow(bool on) {
+    if (on && laneChange_) throw std::logic_error("track_lane_flow: not with laneChange (a shadow changes identity when its change finishes)");
+    std::lock_guard<std::mutex> guard(queryMutex_);
+    flow_.enable(on, (int64_t) step_);
+}
+
+void VectorEngineHost::laneFlowFeatures(const LaneFlowOut &out, bool reset) {
+    std::lock_guard<std::mutex> guard(queryMutex_);  // (the ABI is not re-entrant: the ahead thread may be asking the device)
+    flow_.features(out, reset);
+    raiseDeviceError();
+}
+
+void VectorEngineHost::observeLaneFlowDevice(uintptr_t entered, uintptr_t left, uintptr_t leftSteps, uintptr_t leftWaitingSteps,
+                                             uintptr_t waitingSteps, uintptr_t maxWaitingSteps, bool reset, uintptr_t consumerStream) {
+    LaneFlowOut o;
+    o.entered = (int32_t *) entered;
+    o.left = (int32_t *) left;
+    o.leftSteps = (int64_t *) leftSteps;
+    o.leftWaitingSteps = (int64_t *) leftWaitingSteps;
+    o.waitingSteps = (int64_t *) waitingSteps;
+    o.maxWaitingSteps = (int32_t *) maxWaitingSteps;
+    std::lock_guard<std::mutex> guard(queryMutex_);
+    flow_.observeDevice(o, reset, consumerStream);
 }
 
 const InterLayout &VectorEngineHost::intersectionLayout() {

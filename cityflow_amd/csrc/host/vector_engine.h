@@ -57,6 +57,12 @@ public:
     void intersectionFeatures(const InterFeatures &out);
     void observeIntersectionsDevice(uintptr_t phase, uintptr_t remain, uintptr_t in, uintptr_t inWaiting, uintptr_t out,
                                     uintptr_t inside, uintptr_t pressure, int maxRoadLinks, int maxPhases, uintptr_t consumerStream);
+    // per-lane flow statistics across steps over every environment (EngineHost::trackLaneFlow and its kin): outputs [R * L]
+    void trackLaneFlow(bool on);
+    bool laneFlowTracking() const { return flow_.on(); }
+    void laneFlowFeatures(const LaneFlowOut &out, bool reset);
+    void observeLaneFlowDevice(uintptr_t entered, uintptr_t left, uintptr_t leftSteps, uintptr_t leftWaitingSteps,
+                               uintptr_t waitingSteps, uintptr_t maxWaitingSteps, bool reset, uintptr_t consumerStream);
     std::vector<std::string> laneIds() const;
     std::vector<std::string> intersectionIds() const;
     cfx_scalars scalars();
@@ -76,6 +82,7 @@ public:
 private:
     void check(int32_t rc, const char *what);
     std::unique_ptr<InterLayout> interLayout_;  // built by the first call that needs it
+    LaneFlow flow_;                      // (every call with queryMutex_ held: it asks the device)
     bool devicePhaseUnchecked_ = false;  // as EngineHost: read by every call below that has waited for the device
     void raiseDeviceError();             // (the caller holds queryMutex_)
 

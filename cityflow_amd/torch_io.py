@@ -13,6 +13,12 @@
     eng.get_tl_phases_tensor(out=None)                   int32 [I]   (VectorEngine: [R, I]): the reading side of set_tl_phases_tensor
     eng.observe_intersections_array()                    the same seven outputs as numpy arrays (waits for the device)
     eng.intersection_layout()                            the static signal plan and movement tables (host only, numpy)
+    eng.track_lane_flow(on=True) / eng.lane_flow_tracking()
+                                                         per-lane flow and waiting-time statistics ACROSS steps (off by default)
+    eng.observe_lane_flow_tensor(entered=None, left=None, left_steps=None, left_waiting_steps=None, waiting_steps=None,
+                                 max_waiting_steps=None, reset=False)
+                                                         drains them into the given tensors, one kernel launch (see its docstring)
+    eng.observe_lane_flow_array(reset=False)             the same six outputs as numpy arrays (waits for the device)
 
 On the HIP engine the tensors live on the engine's GPU and nothing here waits for the device:
   * a getter's kernel writes the caller's tensor on the engine's stream after everything already enqueued there and on the
@@ -301,6 +307,73 @@ def intersection_layout(self):
     return d
 
 
+LANE_FLOW_OUTPUTS = ("entered", "left", "left_steps", "left_waiting_steps", "waiting_steps", "max_waiting_steps")
+_LANE_FLOW_INT64 = ("left_steps", "left_waiting_steps", "waiting_steps")
+
+
+def track_lane_flow(self, on=True):
+    """Turn the per-lane flow tracker on or off (off by default: nothing is allocated or launched, and it frees its memory when
+    turned off).  While it is on, every next_step() ends with one tracker update (one extra kernel launch on the HIP engine).
+    Turning it on takes a baseline: the vehicles then on a lane start with no waiting time and are not counted as entered, all
+    accumulators are zero; reset(), load() and load_from_file() take a new baseline and keep it on.  Not with laneChange
+    (NotImplementedError)."""
+    self._track_lane_flow(bool(on))
+
+
+def lane_flow_tracking(self):
+    """Whether track_lane_flow is on."""
+    return self._lane_flow_tracking()
+
+
+def observe_lane_flow_tensor(self, entered=None, left=None, left_steps=None, left_waiting_steps=None, waiting_steps=None,
+                             max_waiting_steps=None, reset=False):
+    """Fill every given tensor with one kernel launch on the engine's stream, ordered against the current torch stream as
+    observe_lanes_tensor (no host wait).  Lanes in lane_ids() order; s = steps taken, P(l) = the vehicles get_lane_vehicles()
+    lists on lane l (vehicles inside an intersection are on no lane).  After every step, per lane: a vehicle new on the lane
+    counts as entered and starts with since = s, wait = 0; a vehicle no longer on it (gone into the intersection, or finished)
+    counts as left, with the steps it spent there and the steps it spent waiting there; every vehicle on it with speed < 0.1 (the
+    criterion of get_lane_waiting_vehicle_count) waits one step more.
+
+        entered             int32 [L]  vehicles that entered      \
+        left                int32 [L]  vehicles that left          | accumulated since the last call with reset=True,
+        left_steps          int64 [L]  sum of their s - since      | or since the baseline (track_lane_flow)
+        left_waiting_steps  int64 [L]  sum of their wait          /
+        waiting_steps       int64 [L]  now: sum of wait over the vehicles on the lane
+        max_waiting_steps   int32 [L]  now: the largest wait on the lane (0 on an empty lane)
+
+    Seconds = steps * interval.  reset=True zeroes the four accumulators in the same launch, after they were read — all four,
+    whether or not they were asked for.  Every element is written.  VectorEngine: a leading [R] on every output.  At least one
+    output; every argument is checked before anything is enqueued; RuntimeError while tracking is off."""
+    torch = _torch()
+    given = dict(zip(LANE_FLOW_OUTPUTS, (entered, left, left_steps, left_waiting_steps, waiting_steps, max_waiting_steps)))
+    if all(t is None for t in given.values()):
+        raise ValueError("observe_lane_flow_tensor: give at least one of " + ", ".join(LANE_FLOW_OUTPUTS))
+    shape = tuple(self._tensor_shapes()[0])
+    device = _engine_device(torch, self)
+    for name, t in given.items():
+        if t is not None:
+            _check_buf(torch, t, name, shape, torch.int64 if name in _LANE_FLOW_INT64 else torch.int32, device)
+    if not self._lane_flow_tracking():
+        raise RuntimeError("observe_lane_flow_tensor: lane-flow tracking is off (track_lane_flow(True) turns it on)")
+    if not self._device_buffers():  # (the twin: over the array call)
+        arrays = observe_lane_flow_array(self, reset=reset)
+        for name, t in given.items():
+            if t is not None:
+                t.copy_(torch.from_numpy(arrays[name]))
+        return
+    self._observe_lane_flow_device(*[0 if given[name] is None else given[name].data_ptr() for name in LANE_FLOW_OUTPUTS],
+                                   bool(reset), torch.cuda.current_stream(device).cuda_stream)
+
+
+def observe_lane_flow_array(self, reset=False):
+    """The six outputs of observe_lane_flow_tensor as a dict of numpy arrays (same names, dtypes and shapes); waits for the
+    device.  RuntimeError while tracking is off."""
+    if not self._lane_flow_tracking():
+        raise RuntimeError("observe_lane_flow_array: lane-flow tracking is off (track_lane_flow(True) turns it on)")
+    shape = tuple(self._tensor_shapes()[0])
+    return {name: a.reshape(shape) for name, a in zip(LANE_FLOW_OUTPUTS, self._lane_flow_features(bool(reset)))}
+
+
 def install(*classes):
     for cls in classes:
         cls.get_lane_vehicle_count_tensor = get_lane_vehicle_count_tensor
@@ -313,3 +386,7 @@ def install(*classes):
         cls.get_tl_phases_tensor = get_tl_phases_tensor
         cls.observe_intersections_array = observe_intersections_array
         cls.intersection_layout = intersection_layout
+        cls.track_lane_flow = track_lane_flow
+        cls.lane_flow_tracking = lane_flow_tracking
+        cls.observe_lane_flow_tensor = observe_lane_flow_tensor
+        cls.observe_lane_flow_array = observe_lane_flow_array

@@ -570,6 +570,47 @@ typedef int32_t (*cfx_get_intersection_features_fn)(cfx_engine *e, int32_t *phas
                                                     int32_t *out, int32_t *inside, int32_t *phase_pressure, int32_t max_roadlinks,
                                                     int32_t max_phases);
 
+/* ---- Per-lane flow and waiting-time statistics accumulated across steps (OPTIONAL entry points, as above; not with lane
+ * change, not on a tile: CFX_ERR_STATE).  Off by default: nothing is allocated or launched.  While it is on, every cfx_step ends
+ * with one TICK on the state the step left (s = the step counter after it; P(l) = the vehicles cfx_get_lane_counts counts on
+ * lane l, P'(l) = the same at the previous tick or the baseline):
+ *   v in P(l) \ P'(l):  entered[l] += 1, since(v) = s, wait(v) = 0
+ *   v in P'(l) \ P(l):  left[l] += 1, left_steps[l] += s - since(v), left_waiting_steps[l] += wait(v)
+ *   v in P(l) with speed < 0.1 (the criterion of cfx_get_lane_waiting_counts):  wait(v) += 1
+ * A BASELINE (enabling, cfx_reset, cfx_load_state) gives every vehicle then on a lane since = s, wait = 0 without counting it as
+ * entered, and zeroes the accumulators.  Outputs, [n_lanes] each: entered, left (int32), left_steps, left_waiting_steps (int64):
+ * accumulated since the baseline or the last read with reset != 0; waiting_steps (int64) = sum of wait(v) over P(l) and
+ * max_waiting_steps (int32) = their maximum (0 on an empty lane), both as of the last tick.
+ *   "cfx_lane_flow_enable"         on != 0: allocate (16 bytes per vehicle number the tables hold, 48 per lane) and take a
+ *                                  baseline; 0: free.  While it is on the ring layout launches every step's commit with the step.
+ *   "cfx_observe_lane_flow_device" any of the six NULL (at least one given unless reset), all in device memory, copied by ONE
+ *                                  kernel on the engine's stream, ordered against consumer_stream as cfx_observe_device; reset
+ *                                  != 0 zeroes the four accumulators in that launch, after they were read.
+ *   "cfx_get_lane_flow"            the same into host memory; synchronous.
+ *   "cfx_lane_flow_get_state" / "cfx_lane_flow_set_state"  the tracker as it stands, for a host that renumbers the vehicles through
+ *                                  cfx_load_state (which takes a baseline): records[4 v ..] = {lane, tick last seen on it, since,
+ *                                  wait} of vehicle number v < n_vehicles (n_vehicles as cfx_load_state last set it plus the
+ *                                  vehicles spawned since), lanes[n_lanes], and the tick counter.  set replaces all three and
+ *                                  cancels a pending baseline.  Synchronous. */
+typedef struct cfx_lane_flow_lane {
+    int64_t since_sum;           /* sum of since(v) over the lane's vehicles at the last tick */
+    int64_t waiting_steps;       /* sum of wait(v) over them */
+    int64_t left_steps, left_waiting_steps;
+    int32_t count;               /* vehicles on the lane at the last tick */
+    int32_t entered, left;
+    int32_t max_waiting_steps;
+} cfx_lane_flow_lane;
+typedef int32_t (*cfx_lane_flow_enable_fn)(cfx_engine *e, int32_t on);
+typedef int32_t (*cfx_observe_lane_flow_device_fn)(cfx_engine *e, int32_t *entered, int32_t *left, int64_t *left_steps,
+                                                   int64_t *left_waiting_steps, int64_t *waiting_steps, int32_t *max_waiting_steps,
+                                                   int32_t reset, void *consumer_stream);
+typedef int32_t (*cfx_get_lane_flow_fn)(cfx_engine *e, int32_t *entered, int32_t *left, int64_t *left_steps,
+                                        int64_t *left_waiting_steps, int64_t *waiting_steps, int32_t *max_waiting_steps, int32_t reset);
+typedef int32_t (*cfx_lane_flow_get_state_fn)(cfx_engine *e, int32_t *records, int32_t n_vehicles, cfx_lane_flow_lane *lanes,
+                                              int32_t *tick);
+typedef int32_t (*cfx_lane_flow_set_state_fn)(cfx_engine *e, const int32_t *records, int32_t n_vehicles,
+                                              const cfx_lane_flow_lane *lanes, int32_t tick);
+
 #ifdef __cplusplus
 }
 #endif

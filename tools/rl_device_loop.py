@@ -9,7 +9,14 @@ usage: python tools/rl_device_loop.py [--iters N] [--envs R]      (the probe too
 --intersections: a max-pressure loop built two ways, alternated --runs times — A: observe_lanes_tensor(counts, waiting) and torch
 ops over index tensors made once (movement_in, movement_in_waiting, movement_out, phase_pressure); B: observe_intersections_tensor
 with the same four outputs (one launch of kr_intersection_features), and with all seven; A's tensors are asserted equal to B's
-first.  --intersections-only runs one of the loops alone, for a kernel trace."""
+first.  --intersections-only runs one of the loops alone, for a kernel trace.
+       python tools/rl_device_loop.py --lane-flow [--runs N] [--lane-flow-only trace]
+--lane-flow: what track_lane_flow costs and saves — next_step alone with tracking off and on, alternated --runs times; then a
+max-pressure loop whose reward (vehicles that left each lane, and the steps they waited there) comes from
+observe_lane_flow_tensor(left, left_waiting_steps, reset=True), against the same loop with the reward built from
+get_lane_vehicles() + get_vehicle_speed() and a Python diff every step; both rewards are asserted equal first.
+--lane-flow-only trace runs next_step + observe_lanes_tensor(counts, waiting) + observe_lane_flow_tensor(reset=True) alone, so
+that a kernel trace shows kr_lane_features, kr_lane_flow and k_lane_flow_drain side by side."""
 import argparse
 import os
 import sys
@@ -27,6 +34,8 @@ ap.add_argument("--features", action="store_true")
 ap.add_argument("--features-only", choices=["all", "counts_waiting"], default=None)
 ap.add_argument("--intersections", action="store_true")
 ap.add_argument("--intersections-only", choices=["lanes", "four", "seven", "no_waiting"], default=None)
+ap.add_argument("--lane-flow", action="store_true")
+ap.add_argument("--lane-flow-only", choices=["trace"], default=None)
 ap.add_argument("--runs", type=int, default=3)
 args = ap.parse_args()
 sys.argv = [sys.argv[0]]
@@ -233,6 +242,101 @@ def intersections(name, eng, n, runs, only):
         print("%-4s median %8.1f us   min %8.1f   max %8.1f   (spread %.1f)" % (k, float(np.median(v)), min(v), max(v), max(v) - min(v)),
               flush=True)
 
+
+def lane_flow(name, eng, n, runs, only):
+    device = torch.device("cuda", eng._stream_handle()[1])
+    lay = eng.intersection_layout()
+    L = len(eng.lane_ids())
+    I, P, M = lay["phase_avail"].shape
+    pp = torch.empty((I, P), dtype=torch.int32, device=device)
+    left = torch.empty(L, dtype=torch.int32, device=device)
+    left_wait = torch.empty(L, dtype=torch.int64, device=device)
+    c = torch.empty(L, dtype=torch.int32, device=device)
+    w = torch.empty(L, dtype=torch.int32, device=device)
+    reward = {}
+
+    def control():
+        eng.observe_intersections_tensor(phase_pressure=pp)
+        eng.set_tl_phases_tensor(pp.argmax(-1))
+        eng.next_step()
+
+    def tensor_loop(s):
+        control()
+        eng.observe_lane_flow_tensor(left=left, left_waiting_steps=left_wait, reset=True)
+        reward["tensor"] = torch.stack((left.sum(), left_wait.sum()))  # (stays on the device)
+
+    lanes = eng.lane_ids()
+    on = {}  # lane -> {vehicle: steps waited on it}
+
+    def python_reward():
+        lv, speed = eng.get_lane_vehicles(), eng.get_vehicle_speed()
+        n_left = waited = 0
+        for lane in lanes:
+            prev, now = on.get(lane, {}), lv[lane]
+            cur = {v: prev.get(v, 0) + (speed[v] < 0.1) for v in now}
+            gone = [v for v in prev if v not in cur]
+            n_left += len(gone)
+            waited += sum(prev[v] for v in gone)
+            on[lane] = cur
+        return n_left, waited
+
+    def python_loop(s):
+        control()
+        reward["python"] = python_reward()
+
+    def trace(s):
+        eng.next_step()
+        eng.observe_lanes_tensor(counts=c, waiting=w)
+        eng.observe_lane_flow_tensor(left=left, left_waiting_steps=left_wait, reset=True)
+
+    for _ in range(300):
+        eng.next_step()
+    eng.sync()
+    print("# %s" % name, flush=True)
+    if only:
+        eng.track_lane_flow(True)
+        measure("next_step + observe_lanes_tensor(counts, waiting) + observe_lane_flow_tensor(2, reset)", eng, trace, n)
+        return
+    res = {"off": [], "on": []}
+    for r in range(runs):
+        eng.track_lane_flow(False)
+        res["off"].append(measure("next_step alone, tracking off (run %d)" % r, eng, lambda s: eng.next_step(), n))
+        eng.track_lane_flow(True)
+        res["on"].append(measure("next_step alone, tracking on  (run %d)" % r, eng, lambda s: eng.next_step(), n))
+    for k, v in res.items():
+        print("%-4s median %8.1f us   min %8.1f   max %8.1f" % (k, float(np.median(v)), min(v), max(v)), flush=True)
+    print("tracking on - off (medians) %8.1f us per step" % (float(np.median(res["on"])) - float(np.median(res["off"]))), flush=True)
+    measure("observe_lane_flow_tensor(left, left_waiting_steps, reset) alone (1 launch + events)", eng,
+            lambda s: eng.observe_lane_flow_tensor(left=left, left_waiting_steps=left_wait, reset=True), n)
+    # both rewards from one engine, step by step, before anything is timed
+    eng.track_lane_flow(False)
+    eng.track_lane_flow(True)  # (a baseline for both)
+    on.clear()
+    on.update({lane: {v: 0 for v in vs} for lane, vs in eng.get_lane_vehicles().items()})
+    total = 0
+    for s in range(12):
+        control()
+        eng.observe_lane_flow_tensor(left=left, left_waiting_steps=left_wait, reset=True)
+        got, want = (int(left.sum()), int(left_wait.sum())), python_reward()
+        assert got == want, "step %d: the tensor reward %s is not the Python diff's %s" % (s, got, want)
+        total += want[0]
+    assert total > 0
+    print("the two rewards are equal over 12 steps (%d vehicles left a lane)" % total, flush=True)
+    n_py = max(n // 20, 10)
+    res = {"tensor": [], "python": []}
+    for r in range(runs):
+        res["tensor"].append(measure("observe_intersections -> argmax -> set -> next_step -> observe_lane_flow_tensor (run %d)" % r, eng, tensor_loop, n))
+        res["python"].append(measure("... -> next_step -> get_lane_vehicles + get_vehicle_speed + Python diff (run %d)" % r, eng, python_loop, n_py))
+    for k, v in res.items():
+        print("%-6s median %10.1f us   min %10.1f   max %10.1f" % (k, float(np.median(v)), min(v), max(v)), flush=True)
+    print("python loop / tensor loop %8.1fx" % (float(np.median(res["python"])) / float(np.median(res["tensor"]))), flush=True)
+
+
+if args.lane_flow or args.lane_flow_only:
+    e = _cityflow.Engine(cfg, 1)
+    lane_flow("Engine, 30x30 RL workload (%d signals, %d lanes)" % (len(e.intersection_ids()), len(e.lane_ids())), e, args.iters,
+              args.runs, args.lane_flow_only)
+    sys.exit(0)
 
 if args.intersections or args.intersections_only:
     e = _cityflow.Engine(cfg, 1)
