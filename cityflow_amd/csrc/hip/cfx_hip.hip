@@ -140,10 +140,13 @@ struct cfx_engine {
     bool devObserving = false;
     int devObserveIdle = 0;
     int32_t *hPhaseErr = nullptr;  // pinned, host-mapped: {intersection, phase} of the first rejected device-side entry, {-1, 0}
-    // cfx_get_lane_features: device scratch kept between calls (grown to the largest request seen; in `owned`)
+    // cfx_get_lane_obs / cfx_get_lane_features: device scratch kept between calls (grown to the largest request seen; in `owned`)
     double *featSum = nullptr, *featEdges = nullptr;
     int32_t *featBins = nullptr;
     size_t featBinsCap = 0, featEdgesCap = 0;
+    int32_t *obsI = nullptr;  // cfx_get_lane_obs: counts, waiting [L each], then front_lane_steps, front_waiting_steps [L * n_front each]
+    double *obsD = nullptr;   // ... front_distance, front_speed [L * n_front each]
+    size_t obsICap = 0, obsDCap = 0;
     // cfx_observe_intersections_device / cfx_get_intersection_features: the intersection -> roadLink -> {start lanes, end lanes,
     // laneLinks} index, built and uploaded by the first call (interTables), and the host getter's device scratch; in `owned`
     bool interBuilt = false;
@@ -3280,28 +3283,135 @@ static LaneFeatOut laneFeatOut(const cfx_engine *e, int32_t *counts, int32_t *wa
     return o;
 }
 
-int32_t cfx_observe_lanes_device(cfx_engine *e, int32_t *counts, int32_t *waiting, double *speedSum, int32_t *bins,
-                                 const double *edges, int32_t nBins, int32_t perLaneEdges, void *consumerStream) {
-    if (!e || (!counts && !waiting && !speedSum && !bins)) return CFX_ERR_INVALID;
-    if (!laneFeatureArgs(e, bins, edges, nBins, "cfx_observe_lanes_device")) return CFX_ERR_INVALID;
+// ---- every lane observation through one descriptor (optional entry points of include/cityflow_amd.h, as above); the three
+// entry points above it in the header are forwards onto laneObs
+int32_t cfx_observe_lane_obs_device(cfx_engine *e, const cfx_lane_obs *obs, void *consumerStream);
+int32_t cfx_get_lane_obs(cfx_engine *e, const cfx_lane_obs *obs);
+static_assert(std::is_same<decltype(&cfx_observe_lane_obs_device), cfx_observe_lane_obs_device_fn>::value, "cfx_observe_lane_obs_device");
+static_assert(std::is_same<decltype(&cfx_get_lane_obs), cfx_get_lane_obs_fn>::value, "cfx_get_lane_obs");
+
+// The one path of the lane observations.  toHost: the outputs and edges are host memory (engine-owned device scratch, a
+// synchronous copy back); otherwise device memory, ordered against the caller's stream.  `what` names the entry point in messages.
+static int laneObs(cfx_engine *e, const cfx_lane_obs *obs, bool toHost, void *consumerStream, const char *what) {
+    if (!e || !obs || obs->struct_size < (int32_t) sizeof(int32_t)) return CFX_ERR_INVALID;
+    if ((size_t) obs->struct_size > sizeof(cfx_lane_obs)) {
+        e->err = std::string(what) + ": struct_size names members this library does not know";
+        return CFX_ERR_INVALID;
+    }
+    cfx_lane_obs a{};
+    memcpy(&a, obs, (size_t) obs->struct_size);
+    const bool tracker = a.front_lane_steps || a.front_waiting_steps, front = a.front_distance || a.front_speed || tracker;
+    if (!a.counts && !a.waiting && !a.speed_sum && !a.bins && !front) return CFX_ERR_INVALID;
+    if (!laneFeatureArgs(e, a.bins, a.edges, a.n_bins, what)) return CFX_ERR_INVALID;
+    if (front && (a.n_front < 1 || a.n_front > CFX_MAX_LANE_FRONT)) {
+        e->err = std::string(what) + ": front outputs need 1 <= n_front <= " + std::to_string(CFX_MAX_LANE_FRONT);
+        return CFX_ERR_INVALID;
+    }
     auto fail = [e](const std::string &m) { return e->fail(m); };
     HIP_TRY(hipSetDevice(e->device));
     int rc;
-    if (counts && (rc = checkDevicePointer(e, counts, "cfx_observe_lanes_device: counts"))) return rc;
-    if (waiting && (rc = checkDevicePointer(e, waiting, "cfx_observe_lanes_device: waiting"))) return rc;
-    if (speedSum && (rc = checkDevicePointer(e, speedSum, "cfx_observe_lanes_device: speed_sum"))) return rc;
-    if (bins && (rc = checkDevicePointer(e, bins, "cfx_observe_lanes_device: bins"))) return rc;
-    if (bins && (rc = checkDevicePointer(e, edges, "cfx_observe_lanes_device: edges"))) return rc;
+    if (!toHost) {
+        const std::pair<const void *, const char *> bufs[] = {
+            {a.counts, "counts"}, {a.waiting, "waiting"}, {a.speed_sum, "speed_sum"}, {a.bins, "bins"}, {a.bins ? a.edges : nullptr, "edges"},
+            {a.front_distance, "front_distance"}, {a.front_speed, "front_speed"}, {a.front_lane_steps, "front_lane_steps"},
+            {a.front_waiting_steps, "front_waiting_steps"}};
+        for (const auto &b : bufs)
+            if (b.first && (rc = checkDevicePointer(e, b.first, (std::string(what) + ": " + b.second).c_str()))) return rc;
+    }
+    if (tracker && !e->flowOn) {
+        e->err = std::string(what) + ": front_lane_steps / front_waiting_steps need lane-flow tracking (cfx_lane_flow_enable)";
+        return CFX_ERR_STATE;
+    }
     if ((rc = e->settle(false))) return rc;  // (ring layout: a commit deferred to the next step's admission; Lane::history is not read here)
     if ((rc = e->syncTables())) return rc;
     if (e->ring && (rc = e->ringEnsure())) return rc;
-    if ((rc = e->orderAfterCaller((hipStream_t) consumerStream))) return rc;
-    launchLaneFeatures(e, laneFeatOut(e, counts, waiting, speedSum, bins, edges, nBins, perLaneEdges));
+    LaneFeatOut o = laneFeatOut(e, a.counts, a.waiting, a.speed_sum, a.bins, a.edges, a.n_bins, a.per_lane_edges);
+    if (front) {
+        o.nFront = a.n_front;
+        o.frontDis = a.front_distance;
+        o.frontSpeed = a.front_speed;
+        o.frontSteps = a.front_lane_steps;
+        o.frontWait = a.front_waiting_steps;
+    }
+    if (tracker) {
+        o.flowRec = e->flow.rec;
+        o.flowVidCap = (int) e->vidCap;
+        o.flowTick = e->flow.tick + (e->flowBaseline ? 1 : 0);  // (a baseline that is due: no record carries the tick it will take)
+        o.flowStep = e->flow.step;
+    }
+    if (!toHost) {
+        if ((rc = e->orderAfterCaller((hipStream_t) consumerStream))) return rc;
+        launchLaneFeatures(e, o);
+        HIP_TRY(hipGetLastError());
+        if ((rc = e->orderCallerAfter((hipStream_t) consumerStream))) return rc;
+        e->devObserving = !e->tiled;
+        e->devObserveIdle = 0;
+        return CFX_OK;
+    }
+    // host memory: the launch writes engine-owned scratch, kept between calls and grown to the largest request seen
+    const size_t nL = (size_t) e->L, nB = a.bins ? nL * a.n_bins : 0, nF = front ? nL * a.n_front : 0,
+                 nEdges = a.bins ? (a.per_lane_edges ? (size_t) o.lanesPerEnv : 1) * (a.n_bins + 1) : 0;
+    if (a.speed_sum && !e->featSum && (rc = e->allocRaw(&e->featSum, nL))) return rc;
+    auto atLeast = [&](auto **p, size_t &cap, size_t n) {
+        if (n <= cap) return (int) CFX_OK;
+        const int r = e->grow(p, 0, n);
+        if (!r) cap = n;
+        return r;
+    };
+    if ((rc = atLeast(&e->featBins, e->featBinsCap, nB))) return rc;
+    if ((rc = atLeast(&e->featEdges, e->featEdgesCap, nEdges))) return rc;
+    if ((rc = atLeast(&e->obsI, e->obsICap, ((a.counts || a.waiting) ? 2 * nL : 0) + (tracker ? 2 * nF : 0)))) return rc;
+    if ((rc = atLeast(&e->obsD, e->obsDCap, (a.front_distance || a.front_speed) ? 2 * nF : 0))) return rc;
+    if (nEdges) HIP_TRY(hipMemcpyAsync(e->featEdges, a.edges, nEdges * sizeof(double), hipMemcpyHostToDevice, e->stream));
+    int32_t *const dSteps = e->obsI + ((a.counts || a.waiting) ? 2 * nL : 0);
+    if (a.counts) o.counts = e->obsI;
+    if (a.waiting) o.waiting = e->obsI + nL;
+    if (a.speed_sum) o.speedSum = e->featSum;
+    if (a.bins) o.bins = e->featBins, o.edges = e->featEdges;
+    if (a.front_distance) o.frontDis = e->obsD;
+    if (a.front_speed) o.frontSpeed = e->obsD + nF;
+    if (a.front_lane_steps) o.frontSteps = dSteps;
+    if (a.front_waiting_steps) o.frontWait = dSteps + nF;
+    launchLaneFeatures(e, o);
     HIP_TRY(hipGetLastError());
-    if ((rc = e->orderCallerAfter((hipStream_t) consumerStream))) return rc;
-    e->devObserving = !e->tiled;
-    e->devObserveIdle = 0;
+    auto back = [&](void *dst, const void *src, size_t bytes) {
+        return (dst && bytes) ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, e->stream) : hipSuccess;
+    };
+    HIP_TRY(back(a.counts, o.counts, nL * sizeof(int32_t)));
+    HIP_TRY(back(a.waiting, o.waiting, nL * sizeof(int32_t)));
+    HIP_TRY(back(a.speed_sum, o.speedSum, nL * sizeof(double)));
+    HIP_TRY(back(a.bins, o.bins, nB * sizeof(int32_t)));
+    HIP_TRY(back(a.front_distance, o.frontDis, nF * sizeof(double)));
+    HIP_TRY(back(a.front_speed, o.frontSpeed, nF * sizeof(double)));
+    HIP_TRY(back(a.front_lane_steps, o.frontSteps, nF * sizeof(int32_t)));
+    HIP_TRY(back(a.front_waiting_steps, o.frontWait, nF * sizeof(int32_t)));
+    HIP_TRY(hipStreamSynchronize(e->stream));
     return CFX_OK;
+}
+
+int32_t cfx_observe_lane_obs_device(cfx_engine *e, const cfx_lane_obs *obs, void *consumerStream) {
+    return laneObs(e, obs, false, consumerStream, "cfx_observe_lane_obs_device");
+}
+int32_t cfx_get_lane_obs(cfx_engine *e, const cfx_lane_obs *obs) { return laneObs(e, obs, true, nullptr, "cfx_get_lane_obs"); }
+
+static cfx_lane_obs laneObsOf(int32_t *counts, int32_t *waiting, double *speedSum, int32_t *bins, const double *edges, int32_t nBins,
+                              int32_t perLaneEdges) {
+    cfx_lane_obs a{};
+    a.struct_size = (int32_t) sizeof a;
+    a.counts = counts;
+    a.waiting = waiting;
+    a.speed_sum = speedSum;
+    a.bins = bins;
+    a.edges = edges;
+    a.n_bins = nBins;
+    a.per_lane_edges = perLaneEdges;
+    return a;
+}
+
+int32_t cfx_observe_lanes_device(cfx_engine *e, int32_t *counts, int32_t *waiting, double *speedSum, int32_t *bins,
+                                 const double *edges, int32_t nBins, int32_t perLaneEdges, void *consumerStream) {
+    const cfx_lane_obs a = laneObsOf(counts, waiting, speedSum, bins, edges, nBins, perLaneEdges);
+    return laneObs(e, &a, false, consumerStream, "cfx_observe_lanes_device");
 }
 
 // (the two counts alone: cfx_observe_lanes_device with the other outputs null)
@@ -3312,34 +3422,8 @@ int32_t cfx_observe_device(cfx_engine *e, int32_t *counts, int32_t *waiting, voi
 
 int32_t cfx_get_lane_features(cfx_engine *e, double *speedSum, int32_t *bins, const double *edges, int32_t nBins,
                               int32_t perLaneEdges) {
-    if (!e || (!speedSum && !bins)) return CFX_ERR_INVALID;
-    if (!laneFeatureArgs(e, bins, edges, nBins, "cfx_get_lane_features")) return CFX_ERR_INVALID;
-    auto fail = [e](const std::string &m) { return e->fail(m); };
-    HIP_TRY(hipSetDevice(e->device));
-    int rc;
-    if ((rc = e->settle(false))) return rc;
-    if ((rc = e->syncTables())) return rc;
-    if (e->ring && (rc = e->ringEnsure())) return rc;
-    const LaneFeatOut shape = laneFeatOut(e, nullptr, nullptr, nullptr, bins, edges, nBins, perLaneEdges);
-    const size_t nSum = (size_t) e->L, nOut = bins ? (size_t) e->L * nBins : 0,
-                 nEdges = bins ? (perLaneEdges ? (size_t) shape.lanesPerEnv : 1) * (nBins + 1) : 0;
-    if (speedSum && !e->featSum && (rc = e->allocRaw(&e->featSum, nSum))) return rc;
-    if (nOut > e->featBinsCap) {
-        if ((rc = e->grow(&e->featBins, 0, nOut))) return rc;
-        e->featBinsCap = nOut;
-    }
-    if (nEdges > e->featEdgesCap) {
-        if ((rc = e->grow(&e->featEdges, 0, nEdges))) return rc;
-        e->featEdgesCap = nEdges;
-    }
-    if (nEdges) HIP_TRY(hipMemcpyAsync(e->featEdges, edges, nEdges * sizeof(double), hipMemcpyHostToDevice, e->stream));
-    launchLaneFeatures(e, laneFeatOut(e, nullptr, nullptr, speedSum ? e->featSum : nullptr, bins ? e->featBins : nullptr,
-                                      e->featEdges, nBins, perLaneEdges));
-    HIP_TRY(hipGetLastError());
-    if (speedSum) HIP_TRY(hipMemcpyAsync(speedSum, e->featSum, nSum * sizeof(double), hipMemcpyDeviceToHost, e->stream));
-    if (bins) HIP_TRY(hipMemcpyAsync(bins, e->featBins, nOut * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    return CFX_OK;
+    const cfx_lane_obs a = laneObsOf(nullptr, nullptr, speedSum, bins, edges, nBins, perLaneEdges);
+    return laneObs(e, &a, true, nullptr, "cfx_get_lane_features");
 }
 
 // ---- per-intersection movement and phase observations (optional entry points of include/cityflow_amd.h, as above)

@@ -2212,7 +2212,7 @@ __global__ void k_lane_history(StepCtx c, LaneHistDev h) {
     laneHistoryStep(h, lane, cntNow(c, lane), [&](int i) { return c.s.speed[base + i]; });
 }
 
-// cfx_observe_lanes_device / cfx_get_lane_features: every per-lane observation in one launch (any pointer may be null).  A GROUP of
+// cfx_observe_lane_obs_device / cfx_get_lane_obs: every per-lane observation in one launch (any pointer may be null).  A GROUP of
 // kFeatGroup threads reads one lane: its records are contiguous, so one chunk of 16 vehicles is one set of neighbouring loads
 // instead of a serial walk.  Integers (waiting, bins) are counted per thread; the speed sum must be added front to back, so
 // each chunk is staged in LDS and every thread of the group runs the same chain of adds over it (the reads are independent,
@@ -2227,6 +2227,14 @@ struct LaneFeatOut {
     int nBins;            // 0: no bins
     int edgeStride;       // nBins + 1 for per-lane edges, 0 for one shared row
     int lanesPerEnv;
+    // the first nFront vehicles from the front, [lane * nFront + k]; slots k >= n are padding (-1.0, 0.0, 0, 0)
+    int nFront;           // 0: no front outputs
+    double *frontDis, *frontSpeed;
+    int32_t *frontSteps, *frontWait;  // flowStep - since and wait of the vehicle's lane-flow record (LaneFlowDev::rec below)
+    const int4 *flowRec;  // read only when frontSteps / frontWait are given
+    int flowVidCap;
+    int32_t flowTick;     // a record counts when it is {this lane, flowTick, ..}: anything else reports 0, 0
+    int32_t flowStep;
 };
 
 // (the group's LDS chunk is written and read by lanes of one wavefront: a wavefront's LDS accesses complete in order, so a
@@ -2237,9 +2245,12 @@ __device__ __forceinline__ void waveLdsOrder() {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-// rec(i) = {dis, speed} of the lane's i-th vehicle from the front; stage = the group's kFeatGroup LDS records
-template <typename Rec>
-__device__ __forceinline__ void laneFeatures(const LaneFeatOut &o, int lane, int n, int sub, double2 *stage, Rec rec) {
+// rec(i) = {dis, speed} and vidOf(i) = vehicle number of the lane's i-th vehicle from the front; stage = the group's kFeatGroup
+// LDS records.  Front outputs: in chunk `first` thread `sub` holds record first + sub and stores it to slot first + sub of the
+// lane's row, so a chunk is one run of neighbouring stores; with nothing else asked for the walk ends behind slot nFront - 1.
+// (`o` by value, as laneFlowTick below takes its argument struct)
+template <typename Rec, typename Vid>
+__device__ __forceinline__ void laneFeatures(const LaneFeatOut o, int lane, int n, int sub, double2 *stage, Rec rec, Vid vidOf) {
     if (o.counts && sub == 0) o.counts[lane] = n;
     const bool staged = o.speedSum || o.nBins;
     double lo0 = 1.0, hi0 = 0.0, lo1 = 1.0, hi1 = 0.0;  // (an empty interval: counts nothing)
@@ -2250,12 +2261,27 @@ __device__ __forceinline__ void laneFeatures(const LaneFeatOut &o, int lane, int
     }
     int w = 0, b0 = 0, b1 = 0;
     double sum = 0.0;
-    const int walk = (o.waiting || staged) ? n : 0;  // (counts alone are a copy of cnt: no record is loaded)
+    const int nReal = min(n, o.nFront);  // front slots that hold a vehicle
+    const size_t row = (size_t) lane * o.nFront;
+    const int walk = (o.waiting || staged) ? n : nReal;  // (counts alone are a copy of cnt: no record is loaded)
     for (int first = 0; first < walk; first += kFeatGroup) {  // (the trip count is the group's: n is the same in all its threads)
         double2 r = make_double2(0.0, 0.0);
-        if (first + sub < n) {
-            r = rec(first + sub);
+        const int k = first + sub;
+        if (k < n) {
+            r = rec(k);
             w += r.y < 0.1;
+        }
+        if (k < nReal) {
+            if (o.frontDis) o.frontDis[row + k] = r.x;
+            if (o.frontSpeed) o.frontSpeed[row + k] = r.y;
+            if (o.frontSteps || o.frontWait) {
+                const int v = vidOf(k);
+                int4 q = make_int4(-1, 0, 0, 0);
+                if ((unsigned) v < (unsigned) o.flowVidCap) q = o.flowRec[v];
+                const bool mine = q.x == lane && q.y == o.flowTick;
+                if (o.frontSteps) o.frontSteps[row + k] = mine ? o.flowStep - q.z : 0;
+                if (o.frontWait) o.frontWait[row + k] = mine ? q.w : 0;
+            }
         }
         if (staged) {
             stage[sub] = r;
@@ -2269,6 +2295,12 @@ __device__ __forceinline__ void laneFeatures(const LaneFeatOut &o, int lane, int
             }
             waveLdsOrder();  // (the next chunk overwrites the stage)
         }
+    }
+    for (int k = nReal + sub; k < o.nFront; k += kFeatGroup) {  // padding
+        if (o.frontDis) o.frontDis[row + k] = -1.0;
+        if (o.frontSpeed) o.frontSpeed[row + k] = 0.0;
+        if (o.frontSteps) o.frontSteps[row + k] = 0;
+        if (o.frontWait) o.frontWait[row + k] = 0;
     }
     if (o.waiting) {
         for (int off = kFeatGroup / 2; off > 0; off >>= 1) w += __shfl_xor(w, off, kFeatGroup);
@@ -2290,12 +2322,19 @@ struct DenseLaneRec {  // {dis, speed} of the lane's i-th vehicle from the front
 };
 __device__ __forceinline__ DenseLaneRec laneRec(const StepCtx &c, int lane) { return DenseLaneRec{c.s.dis, c.s.speed, c.segStart[lane]}; }
 
+struct DenseLaneVid {  // vehicle number of the lane's i-th vehicle from the front
+    const int32_t *vid;
+    int base;
+    __device__ __forceinline__ int operator()(int i) const { return vid[base + i]; }
+};
+__device__ __forceinline__ DenseLaneVid laneVid(const StepCtx &c, int lane) { return DenseLaneVid{c.s.vid, c.segStart[lane]}; }
+
 __global__ void __launch_bounds__(kBlock) kd_lane_features(StepCtx c, LaneFeatOut o) {
     __shared__ double2 stage[kBlock];
     const int lane = (int) ((blockIdx.x * (size_t) blockDim.x + threadIdx.x) / kFeatGroup);
     if (lane >= c.n.L) return;  // (whole groups)
     const int sub = threadIdx.x % kFeatGroup;
-    laneFeatures(o, lane, c.cnt[lane], sub, stage + (threadIdx.x - sub), laneRec(c, lane));
+    laneFeatures(o, lane, c.cnt[lane], sub, stage + (threadIdx.x - sub), laneRec(c, lane), laneVid(c, lane));
 }
 
 // cfx_lane_flow_enable: per-lane flow and waiting-time statistics across steps (include/cityflow_amd.h has the rules).  One TICK
@@ -2314,13 +2353,6 @@ struct LaneFlowDev {
     int32_t tick, step;
     int baseline;              // every vehicle: since = step, wait = 0, not entered; accumulators zero
 };
-
-struct DenseLaneVid {  // vehicle number of the lane's i-th vehicle from the front
-    const int32_t *vid;
-    int base;
-    __device__ __forceinline__ int operator()(int i) const { return vid[base + i]; }
-};
-__device__ __forceinline__ DenseLaneVid laneVid(const StepCtx &c, int lane) { return DenseLaneVid{c.s.vid, c.segStart[lane]}; }
 
 // (a 64-bit sum goes through the group as two 32-bit shuffles: the library's 64-bit shuffle stages its halves in scratch)
 __device__ __forceinline__ long long featShflXor64(long long v, int off) {

@@ -2339,8 +2339,8 @@ __global__ void kr_reset(int D, int32_t *head, int32_t *cnt, int4 *scratch) {
 // Lane::history of the last committed step as a launch of its own (the action launch of the NEXT step takes it otherwise: RingHist)
 __global__ void kr_lane_history(RingCtx c, LaneHistDev h) { ringLaneHistory(c, h, blockIdx.x * blockDim.x + threadIdx.x); }
 
-// cfx_observe_lanes_device / cfx_get_lane_features, ring layout: laneFeatures (cfx_kernels.h) over the lane's ring, front to
-// back from `head`, over the {dis, speed} records
+// cfx_observe_lane_obs_device / cfx_get_lane_obs, ring layout: laneFeatures (cfx_kernels.h) over the lane's ring, front to
+// back from `head`, over the {dis, speed} records (and, for the tracker columns, the vehicle numbers of the cold `vid` column)
 struct RingLaneRec {  // {dis, speed} of the lane's i-th vehicle from the front
     const double2 *kin;
     int2 geo;
@@ -2349,15 +2349,6 @@ struct RingLaneRec {  // {dis, speed} of the lane's i-th vehicle from the front
 };
 __device__ __forceinline__ RingLaneRec laneRec(const RingCtx &c, int lane) { return RingLaneRec{c.kin, c.ringGeo[lane], c.head[lane]}; }
 
-__global__ void __launch_bounds__(kBlock) kr_lane_features(RingCtx c, LaneFeatOut o) {
-    __shared__ double2 stage[kBlock];
-    const int lane = (int) ((blockIdx.x * (size_t) blockDim.x + threadIdx.x) / kFeatGroup);
-    if (lane >= c.n.L) return;  // (whole groups)
-    const int sub = threadIdx.x % kFeatGroup;
-    laneFeatures(o, lane, c.cnt[lane], sub, stage + (threadIdx.x - sub), laneRec(c, lane));
-}
-
-// cfx_lane_flow_enable, ring layout: laneFlowTick (cfx_kernels.h) over the lane's ring, the vehicle numbers from the cold `vid` column
 struct RingLaneVid {  // vehicle number of the lane's i-th vehicle from the front
     const int32_t *vid;
     int2 geo;
@@ -2366,6 +2357,15 @@ struct RingLaneVid {  // vehicle number of the lane's i-th vehicle from the fron
 };
 __device__ __forceinline__ RingLaneVid laneVid(const RingCtx &c, int lane) { return RingLaneVid{c.s.vid, c.ringGeo[lane], c.head[lane]}; }
 
+__global__ void __launch_bounds__(kBlock) kr_lane_features(RingCtx c, LaneFeatOut o) {
+    __shared__ double2 stage[kBlock];
+    const int lane = (int) ((blockIdx.x * (size_t) blockDim.x + threadIdx.x) / kFeatGroup);
+    if (lane >= c.n.L) return;  // (whole groups)
+    const int sub = threadIdx.x % kFeatGroup;
+    laneFeatures(o, lane, c.cnt[lane], sub, stage + (threadIdx.x - sub), laneRec(c, lane), laneVid(c, lane));
+}
+
+// cfx_lane_flow_enable, ring layout: laneFlowTick (cfx_kernels.h) over the lane's ring, the vehicle numbers from the cold `vid` column
 __global__ void __launch_bounds__(kBlock) kr_lane_flow(RingCtx c, LaneFlowDev f) {
     const int lane = (int) ((blockIdx.x * (size_t) blockDim.x + threadIdx.x) / kFeatGroup);
     if (lane >= c.n.L) return;  // (whole groups)

@@ -93,6 +93,8 @@ void Backend::open(const std::string &libPath) {
     CFX_FN_OPTIONAL(cfx_device_error)
     CFX_FN_OPTIONAL(cfx_observe_lanes_device)
     CFX_FN_OPTIONAL(cfx_get_lane_features)
+    CFX_FN_OPTIONAL(cfx_observe_lane_obs_device)
+    CFX_FN_OPTIONAL(cfx_get_lane_obs)
     CFX_FN_OPTIONAL(cfx_observe_intersections_device)
     CFX_FN_OPTIONAL(cfx_get_intersection_features)
     CFX_FN_OPTIONAL(cfx_lane_flow_enable)
@@ -490,12 +492,86 @@ void EngineHost::laneFeatures(double *speedSum, int32_t *bins, const double *edg
     raiseDeviceError();
 }
 
-void EngineHost::observeLanesDevice(uintptr_t counts, uintptr_t waiting, uintptr_t speedSum, uintptr_t bins, uintptr_t edges,
-                                    int nBins, bool perLaneEdges, uintptr_t consumerStream) {
-    if (!be_.hasDeviceBuffers()) throw std::runtime_error("cityflow_amd: '" + be_.path + "' has no device buffers");
-    check(be_.cfx_observe_lanes_device(dev_, (int32_t *) counts, (int32_t *) waiting, (double *) speedSum, (int32_t *) bins,
-                                       (const double *) edges, nBins, perLaneEdges ? 1 : 0, (void *) consumerStream),
-          "cfx_observe_lanes_device");
+void EngineHost::observeLanesDevice(const cfx_lane_obs &obs, uintptr_t consumerStream) {
+    observeLanesDeviceOf(be_, dev_, obs, consumerStream);
+}
+
+void EngineHost::laneFronts(int k, const LaneFronts &out) {
+    if ((out.laneSteps || out.waitingSteps) && !flow_.on())
+        throw std::runtime_error("lane fronts: lane_steps / waiting_steps need lane-flow tracking (track_lane_flow(True) turns it on)");
+    if (out.distance || out.speed) laneFrontsOf(be_, dev_, (int) net_->lanes.size(), k, out.distance, out.speed);
+    if (out.laneSteps || out.waitingSteps) flow_.fronts(k, out.laneSteps, out.waitingSteps);
+    raiseDeviceError();
+}
+
+static void backendFail(const Backend &be, cfx_engine *dev, const char *what) {
+    const char *msg = be.cfx_last_error(dev);
+    throw std::runtime_error(std::string("cityflow_amd: ") + what + " failed: " + (msg ? msg : ""));
+}
+
+void observeLanesDeviceOf(const Backend &be, cfx_engine *dev, const cfx_lane_obs &obs, uintptr_t consumerStream) {
+    if (!be.hasDeviceBuffers()) throw std::runtime_error("cityflow_amd: '" + be.path + "' has no device buffers");
+    if (be.cfx_observe_lane_obs_device) {
+        if (be.cfx_observe_lane_obs_device(dev, &obs, (void *) consumerStream) != CFX_OK) backendFail(be, dev, "cfx_observe_lane_obs_device");
+        return;
+    }
+    if (obs.front_distance || obs.front_speed || obs.front_lane_steps || obs.front_waiting_steps)
+        throw std::runtime_error("cityflow_amd: '" + be.path + "' has no device-side front-vehicle observations");
+    if (be.cfx_observe_lanes_device(dev, obs.counts, obs.waiting, obs.speed_sum, obs.bins, obs.edges, obs.n_bins, obs.per_lane_edges,
+                                    (void *) consumerStream) != CFX_OK)
+        backendFail(be, dev, "cfx_observe_lanes_device");
+}
+
+VehicleColumns vehicleColumnsOf(const Backend &be, cfx_engine *dev, bool vid, bool dis, bool speed) {
+    cfx_scalars sc{};
+    if (be.cfx_get_scalars(dev, &sc) != CFX_OK) backendFail(be, dev, "cfx_get_scalars");
+    VehicleColumns c;
+    for (int cap = (int) sc.active_vehicle_count + 16;;) {
+        cfx_vehicle_view v{};
+        v.capacity = cap;
+        c.drivable.resize((size_t) cap);
+        v.drivable = c.drivable.data();
+        if (vid) c.vid.resize((size_t) cap), v.vid = c.vid.data();
+        if (dis) c.dis.resize((size_t) cap), v.dis = c.dis.data();
+        if (speed) c.speed.resize((size_t) cap), v.speed = c.speed.data();
+        const int32_t rc = be.cfx_get_vehicles(dev, &v);
+        if (rc == CFX_ERR_CAPACITY && v.count > cap) {
+            cap = v.count + 16;
+            continue;
+        }
+        if (rc != CFX_OK) backendFail(be, dev, "cfx_get_vehicles");
+        c.count = v.count;
+        return c;
+    }
+}
+
+void laneFrontsFromView(int nLanes, int k, int count, const int32_t *drivable, const double *dis, const double *speed,
+                        double *frontDis, double *frontSpeed) {
+    if (frontDis) std::fill(frontDis, frontDis + (size_t) nLanes * k, -1.0);
+    if (frontSpeed) std::fill(frontSpeed, frontSpeed + (size_t) nLanes * k, 0.0);
+    std::vector<int32_t> seen((size_t) nLanes, 0);
+    for (int i = 0; i < count; ++i) {  // (front to back inside a lane: the i-th of a lane seen is its i-th from the front)
+        const int l = drivable[i];
+        if (l < 0 || l >= nLanes) continue;
+        const int slot = seen[(size_t) l]++;
+        if (slot >= k) continue;
+        if (frontDis) frontDis[(size_t) l * k + slot] = dis[i];
+        if (frontSpeed) frontSpeed[(size_t) l * k + slot] = speed[i];
+    }
+}
+
+void laneFrontsOf(const Backend &be, cfx_engine *dev, int nLanes, int k, double *frontDis, double *frontSpeed) {
+    if (be.cfx_get_lane_obs) {
+        cfx_lane_obs a{};
+        a.struct_size = (int32_t) sizeof a;
+        a.n_front = k;
+        a.front_distance = frontDis;
+        a.front_speed = frontSpeed;
+        if (be.cfx_get_lane_obs(dev, &a) != CFX_OK) backendFail(be, dev, "cfx_get_lane_obs");
+        return;
+    }
+    const VehicleColumns v = vehicleColumnsOf(be, dev, false, frontDis != nullptr, frontSpeed != nullptr);
+    laneFrontsFromView(nLanes, k, v.count, v.drivable.data(), v.dis.data(), v.speed.data(), frontDis, frontSpeed);
 }
 
 void laneFeaturesFromView(int nLanes, int lanesPerEnv, int count, const int32_t *drivable, const double *dis, const double *speed,

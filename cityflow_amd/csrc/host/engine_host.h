@@ -85,6 +85,10 @@ struct Backend {
     }
     // optional on its own: speed sums and bins into host memory (without it the host computes them from cfx_get_vehicles)
     cfx_get_lane_features_fn cfx_get_lane_features = nullptr;
+    // optional, each on its own: every lane observation through one descriptor, the front vehicles among them (without the
+    // first the tensor calls have no front outputs; without the second the host takes them from cfx_get_vehicles)
+    cfx_observe_lane_obs_device_fn cfx_observe_lane_obs_device = nullptr;
+    cfx_get_lane_obs_fn cfx_get_lane_obs = nullptr;
     // optional as a pair: per-intersection observations (without them the host computes the arrays from the getters above)
     cfx_observe_intersections_device_fn cfx_observe_intersections_device = nullptr;
     cfx_get_intersection_features_fn cfx_get_intersection_features = nullptr;
@@ -138,6 +142,20 @@ struct InterFeatures {
 // backend's message).  `lay`: one environment's layout, `nLanes` / `nLaneLinks`: of one environment
 void intersectionFeaturesOf(const Backend &be, cfx_engine *dev, const InterLayout &lay, int nEnvs, int nLanes, int nLaneLinks,
                             const InterFeatures &out);
+
+// the four front-vehicle outputs in host memory ([n_lanes * k] each, of every environment; any may be null)
+struct LaneFronts {
+    double *distance = nullptr, *speed = nullptr;
+    int32_t *laneSteps = nullptr, *waitingSteps = nullptr;
+};
+
+// The running vehicles as cfx_get_vehicles lists them (ordered by drivable, front to back inside one): the columns asked for.
+struct VehicleColumns {
+    std::vector<int32_t> vid, drivable;
+    std::vector<double> dis, speed;
+    int count = 0;
+};
+VehicleColumns vehicleColumnsOf(const Backend &be, cfx_engine *dev, bool vid, bool dis, bool speed);  // (drivable always)
 
 class EngineHost {
 public:
@@ -203,8 +221,11 @@ public:
     std::vector<double> laneLengths() const;  // [n_lanes] Lane::getLength
     // speedSum [n_lanes], bins [n_lanes * nBins] (either may be null), edges: [n_lanes][nBins + 1] or [nBins + 1]
     void laneFeatures(double *speedSum, int32_t *bins, const double *edges, int nBins, bool perLaneEdges);
-    void observeLanesDevice(uintptr_t counts, uintptr_t waiting, uintptr_t speedSum, uintptr_t bins, uintptr_t edges, int nBins,
-                            bool perLaneEdges, uintptr_t consumerStream);
+    // every pointer of `obs` a device address (cfx_observe_lane_obs_device; without front outputs also cfx_observe_lanes_device)
+    void observeLanesDevice(const cfx_lane_obs &obs, uintptr_t consumerStream);
+    // ---- the first k vehicles of every lane from the front (cfx_get_lane_obs; the twin: from the vehicles and the host tracker).
+    //      [n_lanes * k] each, any may be null; the two tracker columns need trackLaneFlow(true) (std::runtime_error)
+    void laneFronts(int k, const LaneFronts &out);
     // ---- per-intersection movement and phase observations (cfx_observe_intersections_device / cfx_get_intersection_features;
     //      the twin: from the count getters, the vehicles and the lights).  Rows of layout().M roadLinks / layout().P phases
     const InterLayout &intersectionLayout();
@@ -357,5 +378,14 @@ void laneFeaturesFromView(int nLanes, int lanesPerEnv, int count, const int32_t 
 // (throws std::runtime_error with the backend's message)
 void laneFeaturesOf(const Backend &be, cfx_engine *dev, int nLanes, int lanesPerEnv, double *speedSum, int32_t *bins,
                     const double *edges, int nBins, bool perLaneEdges);
+
+// Distance and speed of the first k vehicles of every lane from the front (cfx_get_lane_obs's semantics: rows of k slots,
+// -1.0 / 0.0 behind a lane's last vehicle), from such a view.  Either output may be null.
+void laneFrontsFromView(int nLanes, int k, int count, const int32_t *drivable, const double *dis, const double *speed,
+                        double *frontDis, double *frontSpeed);
+// the same on any backend: cfx_get_lane_obs where it exists, otherwise cfx_get_vehicles + laneFrontsFromView
+void laneFrontsOf(const Backend &be, cfx_engine *dev, int nLanes, int k, double *frontDis, double *frontSpeed);
+// ... over every backend's cfx_observe_lanes_device / cfx_observe_lane_obs_device (throws std::runtime_error)
+void observeLanesDeviceOf(const Backend &be, cfx_engine *dev, const cfx_lane_obs &obs, uintptr_t consumerStream);
 
 }  // namespace cfa

@@ -88,6 +88,7 @@ void LaneFlow::walk(int64_t step, bool baseline) {
     since_.assign(L, 0);
     wait_.assign(L, 0);
     const int32_t tick = ++host_.tick, s = (int32_t) step;
+    hostStep_ = s;
     for (int i = 0; i < v.count; ++i) {
         const int32_t l = drv_[(size_t) i], id = vid_[(size_t) i];
         if (l < 0 || l >= nLanes_ || id < 0) continue;  // (on a laneLink: on no lane)
@@ -157,6 +158,35 @@ void LaneFlow::observeDevice(const LaneFlowOut &o, bool reset, uintptr_t consume
     if (be_->cfx_observe_lane_flow_device(dev_, o.entered, o.left, o.leftSteps, o.leftWaitingSteps, o.waitingSteps, o.maxWaitingSteps,
                                           reset ? 1 : 0, (void *) consumerStream) != CFX_OK)
         fail("cfx_observe_lane_flow_device");
+}
+
+void LaneFlow::fronts(int k, int32_t *laneSteps, int32_t *waitingSteps) {
+    requireOn("lane fronts");
+    if (onDevice()) {
+        if (!be_->cfx_get_lane_obs) throw std::runtime_error("cityflow_amd: '" + be_->path + "' has no front-vehicle observations");
+        cfx_lane_obs a{};
+        a.struct_size = (int32_t) sizeof a;
+        a.n_front = k;
+        a.front_lane_steps = laneSteps;
+        a.front_waiting_steps = waitingSteps;
+        if (be_->cfx_get_lane_obs(dev_, &a) != CFX_OK) fail("cfx_get_lane_obs");
+        return;
+    }
+    const size_t n = (size_t) nLanes_ * k;
+    if (laneSteps) std::fill(laneSteps, laneSteps + n, 0);
+    if (waitingSteps) std::fill(waitingSteps, waitingSteps + n, 0);
+    const VehicleColumns v = vehicleColumnsOf(*be_, dev_, true, false, false);
+    n_.assign((size_t) nLanes_, 0);  // (vehicles seen per lane: front to back inside one)
+    for (int i = 0; i < v.count; ++i) {
+        const int32_t l = v.drivable[(size_t) i], id = v.vid[(size_t) i];
+        if (l < 0 || l >= nLanes_) continue;
+        const int slot = n_[(size_t) l]++;
+        if (slot >= k || id < 0 || 4 * (size_t) id + 3 >= host_.records.size()) continue;
+        const int32_t *r = &host_.records[4 * (size_t) id];
+        if (r[0] != l || r[1] != host_.tick) continue;
+        if (laneSteps) laneSteps[(size_t) l * k + slot] = hostStep_ - r[2];
+        if (waitingSteps) waitingSteps[(size_t) l * k + slot] = r[3];
+    }
 }
 
 LaneFlowState LaneFlow::state(int nVehicles) {

@@ -44,6 +44,9 @@ public:
     void baseline(int64_t step);              // after a reset / load (host tracker; the device takes its own)
     void features(const LaneFlowOut &out, bool reset);
     void observeDevice(const LaneFlowOut &out, bool reset, uintptr_t consumerStream);
+    // s - since and wait of the first k vehicles of every lane from the front, as of the last tick ([n_lanes * k] each, either may
+    // be null; 0, 0 in the padding and for a vehicle whose record is not this lane's at that tick).  Changes nothing
+    void fronts(int k, int32_t *laneSteps, int32_t *waitingSteps);
     LaneFlowState state(int nVehicles);       // ... around a renumbering load
     void setState(const LaneFlowState &s);
 
@@ -56,6 +59,7 @@ private:
     int nLanes_ = 0;
     bool on_ = false;
     LaneFlowState host_;                      // the host tracker
+    int32_t hostStep_ = 0;                    // ... the step of its last tick
     std::vector<int32_t> vid_, drv_, n_, entered_, inc_, max_;  // scratch of a tick
     std::vector<double> speed_;
     std::vector<int64_t> since_, wait_;

@@ -323,6 +323,45 @@ template <typename E> py::tuple laneFlowTuple(E &e, bool reset) {
     return py::make_tuple(entered, left, leftSteps, leftWait, waitNow, maxWait);
 }
 
+// ---- the first k vehicles of every lane from the front (Engine and VectorEngine; the public calls are cityflow_amd/torch_io.py)
+template <typename E> py::tuple laneFrontsTuple(E &e, int k, bool tracker) {
+    if (k < 1 || k > CFX_MAX_LANE_FRONT)
+        throw py::value_error("k must be 1 to " + std::to_string(CFX_MAX_LANE_FRONT) + ", not " + std::to_string(k));
+    const py::ssize_t n = laneFlowLanes(e) * k;
+    py::array_t<double> dis(n), speed(n);
+    py::array_t<int32_t> steps(tracker ? n : 0), wait(tracker ? n : 0);
+    cfa::LaneFronts o;
+    o.distance = dis.mutable_data();
+    o.speed = speed.mutable_data();
+    if (tracker) {
+        o.laneSteps = steps.mutable_data();
+        o.waitingSteps = wait.mutable_data();
+    }
+    e.laneFronts(k, o);
+    return py::make_tuple(dis, speed, steps, wait);
+}
+
+template <typename E>
+void observeLanesDevice(E &e, uintptr_t counts, uintptr_t waiting, uintptr_t speedSum, uintptr_t bins, uintptr_t edges, int nBins,
+                        bool perLaneEdges, uintptr_t frontDistance, uintptr_t frontSpeed, uintptr_t frontLaneSteps,
+                        uintptr_t frontWaitingSteps, int nFront, uintptr_t consumerStream) {
+    cfx_lane_obs a{};
+    a.struct_size = (int32_t) sizeof a;
+    a.counts = (int32_t *) counts;
+    a.waiting = (int32_t *) waiting;
+    a.speed_sum = (double *) speedSum;
+    a.bins = (int32_t *) bins;
+    a.edges = (const double *) edges;
+    a.n_bins = nBins;
+    a.per_lane_edges = perLaneEdges ? 1 : 0;
+    a.front_distance = (double *) frontDistance;
+    a.front_speed = (double *) frontSpeed;
+    a.front_lane_steps = (int32_t *) frontLaneSteps;
+    a.front_waiting_steps = (int32_t *) frontWaitingSteps;
+    a.n_front = nFront;
+    e.observeLanesDevice(a, consumerStream);
+}
+
 // Device buffers: raw pointers and streams under the tensor methods of cityflow_amd/torch_io.py (Engine and VectorEngine alike)
 template <typename E> void defDeviceBuffers(py::class_<E> &c) {
     c.def("_device_buffers", &E::deviceBuffers, "the backend takes observations / signals in device memory")
@@ -331,8 +370,12 @@ template <typename E> void defDeviceBuffers(py::class_<E> &c) {
         .def("_rl_traffic_light", &E::rlTrafficLight)
         .def("_phase_counts", [](E &e) { return toArray(e.phaseCounts()); }, "phases per intersection, -1 = virtual")
         .def("lane_lengths", [](E &e) { return toArray(e.laneLengths()); }, "float64 [L]: Lane::getLength (of one environment)")
-        .def("_observe_lanes_device", &E::observeLanesDevice, "counts_ptr"_a, "waiting_ptr"_a, "speed_sum_ptr"_a, "bins_ptr"_a,
-             "edges_ptr"_a, "n_bins"_a, "per_lane_edges"_a, "consumer_stream"_a)
+        .def("_observe_lanes_device", &observeLanesDevice<E>, "counts_ptr"_a, "waiting_ptr"_a, "speed_sum_ptr"_a, "bins_ptr"_a,
+             "edges_ptr"_a, "n_bins"_a, "per_lane_edges"_a, "front_distance_ptr"_a, "front_speed_ptr"_a, "front_lane_steps_ptr"_a,
+             "front_waiting_steps_ptr"_a, "n_front"_a, "consumer_stream"_a)
+        .def("_lane_fronts", [](E &e, int k, bool tracker) { return laneFrontsTuple(e, k, tracker); }, "k"_a, "tracker"_a,
+             "(distance, speed, lane_steps, waiting_steps) of the first k vehicles of every lane, flat (env-major); the last two "
+             "empty unless `tracker`")
         .def("_intersection_dims", [](E &e) { return py::make_tuple(e.intersectionLayout().M, e.intersectionLayout().P); },
              "(largest roadLink count, largest phase count) of an intersection: the row lengths of the intersection observations")
         .def("_intersection_layout", [](E &e) { return intersectionLayoutDict(e); })

@@ -634,13 +634,18 @@ void VectorEngineHost::laneFeatures(double *speedSum, int32_t *bins, const doubl
     raiseDeviceError();
 }
 
-void VectorEngineHost::observeLanesDevice(uintptr_t counts, uintptr_t waiting, uintptr_t speedSum, uintptr_t bins, uintptr_t edges,
-                                          int nBins, bool perLaneEdges, uintptr_t consumerStream) {
-    if (!be_.hasDeviceBuffers()) throw std::runtime_error("cityflow_amd: '" + be_.path + "' has no device buffers");
+void VectorEngineHost::observeLanesDevice(const cfx_lane_obs &obs, uintptr_t consumerStream) {
     std::lock_guard<std::mutex> guard(queryMutex_);
-    check(be_.cfx_observe_lanes_device(dev_, (int32_t *) counts, (int32_t *) waiting, (double *) speedSum, (int32_t *) bins,
-                                       (const double *) edges, nBins, perLaneEdges ? 1 : 0, (void *) consumerStream),
-          "cfx_observe_lanes_device");
+    observeLanesDeviceOf(be_, dev_, obs, consumerStream);
+}
+
+void VectorEngineHost::laneFronts(int k, const LaneFronts &out) {
+    std::lock_guard<std::mutex> guard(queryMutex_);  // (the ABI is not re-entrant: the ahead thread may be asking the device)
+    if ((out.laneSteps || out.waitingSteps) && !flow_.on())
+        throw std::runtime_error("lane fronts: lane_steps / waiting_steps need lane-flow tracking (track_lane_flow(True) turns it on)");
+    if (out.distance || out.speed) laneFrontsOf(be_, dev_, R_ * L_, k, out.distance, out.speed);
+    if (out.laneSteps || out.waitingSteps) flow_.fronts(k, out.laneSteps, out.waitingSteps);
+    raiseDeviceError();
 }
 
 void VectorEngineHost::trackLaneFlow(bool on) {

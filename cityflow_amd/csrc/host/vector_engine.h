@@ -49,8 +49,8 @@ public:
     // [R * L * nBins], edges [L][nBins + 1] or [nBins + 1], shared by the environments
     std::vector<double> laneLengths() const;  // [L] of one environment
     void laneFeatures(double *speedSum, int32_t *bins, const double *edges, int nBins, bool perLaneEdges);
-    void observeLanesDevice(uintptr_t counts, uintptr_t waiting, uintptr_t speedSum, uintptr_t bins, uintptr_t edges, int nBins,
-                            bool perLaneEdges, uintptr_t consumerStream);
+    void observeLanesDevice(const cfx_lane_obs &obs, uintptr_t consumerStream);
+    void laneFronts(int k, const LaneFronts &out);  // [R * L * k] each
     // per-intersection observations over every environment (EngineHost::intersectionFeatures and its kin): outputs [R * I ...];
     // the layout is one environment's
     const InterLayout &intersectionLayout();

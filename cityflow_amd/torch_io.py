@@ -5,8 +5,12 @@
     eng.set_tl_phases_tensor(phases)                     integer [I] (VectorEngine: [R, I])
     eng.get_lane_speed_sum_tensor(out=None)              float64 [L] (VectorEngine: [R, L])
     eng.get_lane_vehicle_bins_tensor(edges, out=None)    int32 [L, B] (VectorEngine: [R, L, B])
-    eng.observe_lanes_tensor(counts=None, waiting=None, speed_sum=None, bins=None, edges=None)
+    eng.observe_lanes_tensor(counts=None, waiting=None, speed_sum=None, bins=None, edges=None, front_distance=None,
+                             front_speed=None, front_lane_steps=None, front_waiting_steps=None)
                                                          fills every given tensor with one kernel launch
+    eng.get_lane_front_vehicles_tensor(k, distance=None, speed=None)
+                                                         float64 [L, k] each: the k vehicles nearest every lane's end
+    eng.get_lane_front_vehicles_array(k)                 the front outputs as numpy arrays (waits for the device)
     eng.observe_intersections_tensor(phase=None, phase_remain=None, movement_in=None, movement_in_waiting=None,
                                      movement_out=None, movement_inside=None, phase_pressure=None)
                                                          per-intersection observations, one kernel launch (see its docstring)
@@ -135,15 +139,34 @@ def _check_edges(torch, edges, n_lanes, device):
     return edges.to(torch.float64).contiguous(), n_bins, per_lane
 
 
-def observe_lanes_tensor(self, counts=None, waiting=None, speed_sum=None, bins=None, edges=None):
+MAX_FRONT = 64  # CFX_MAX_LANE_FRONT
+LANE_FRONT_OUTPUTS = ("front_distance", "front_speed", "front_lane_steps", "front_waiting_steps")
+
+
+def observe_lanes_tensor(self, counts=None, waiting=None, speed_sum=None, bins=None, edges=None, front_distance=None,
+                         front_speed=None, front_lane_steps=None, front_waiting_steps=None):
     """Fill every given tensor with one kernel launch on the engine's stream, ordered against the current torch stream:
     counts / waiting (int32 [L], as get_lane_vehicle_count_tensor / get_lane_waiting_vehicle_count_tensor), speed_sum
     (float64 [L], as get_lane_speed_sum_tensor) and bins (int32 [L, B], as get_lane_vehicle_bins_tensor, with `edges`).
+
+    The front outputs hold, per lane, its first K vehicles from the front (nearest the lane's end first, the order of
+    get_lane_vehicles()); K, 1 to 64, is their last dimension and the same for all of them:
+
+        front_distance       float64 [L, K]  distance from the lane's start, as get_vehicle_distance()   padding -1.0
+        front_speed          float64 [L, K]  as get_vehicle_speed()                                       padding 0.0
+        front_lane_steps     int32 [L, K]    steps the vehicle has been on the lane (s - since)           padding 0
+        front_waiting_steps  int32 [L, K]    steps it has waited there (wait)                             padding 0
+
+    Slot k of lane l is a vehicle exactly if k < counts[l] (lane-change shadows count, as in counts); the slots behind hold the
+    padding, -1.0 being a convenience, not the rule.  Every element is written.  The last two read the track_lane_flow tracker
+    (observe_lane_flow_tensor has its rules) as of the last step, changing nothing in it: RuntimeError while tracking is off, so
+    never with laneChange.  With front outputs alone a lane is read only as far as its K-th vehicle.
     VectorEngine: a leading [R] on every output.  At least one output; every argument is checked before anything is enqueued."""
     torch = _torch()
     shape = tuple(self._tensor_shapes()[0])
-    if counts is None and waiting is None and speed_sum is None and bins is None:
-        raise ValueError("observe_lanes_tensor: give at least one of counts, waiting, speed_sum, bins")
+    fronts = dict(zip(LANE_FRONT_OUTPUTS, (front_distance, front_speed, front_lane_steps, front_waiting_steps)))
+    if counts is None and waiting is None and speed_sum is None and bins is None and all(t is None for t in fronts.values()):
+        raise ValueError("observe_lanes_tensor: give at least one of counts, waiting, speed_sum, bins, " + ", ".join(LANE_FRONT_OUTPUTS))
     if bins is not None and edges is None:
         raise ValueError("observe_lanes_tensor: bins requires edges")
     device = _engine_device(torch, self)
@@ -158,6 +181,19 @@ def observe_lanes_tensor(self, counts=None, waiting=None, speed_sum=None, bins=N
         _check_buf(torch, speed_sum, "speed_sum", shape, torch.float64, device)
     if bins is not None:
         _check_buf(torch, bins, "bins", shape + (n_bins,), torch.int32, device)
+    n_front = 0
+    for name, t in fronts.items():
+        if t is None:
+            continue
+        if not isinstance(t, torch.Tensor):
+            raise TypeError("%s must be a torch.Tensor, not %s" % (name, type(t).__name__))
+        if not n_front:
+            n_front = _check_front_k(t.shape[-1] if t.dim() else 0)
+        _check_buf(torch, t, name, shape + (n_front,), torch.float64 if name in LANE_FRONT_OUTPUTS[:2] else torch.int32, device)
+    tracker = front_lane_steps is not None or front_waiting_steps is not None
+    if tracker and not self._lane_flow_tracking():
+        raise RuntimeError("observe_lanes_tensor: front_lane_steps / front_waiting_steps need lane-flow tracking "
+                           "(track_lane_flow(True) turns it on)")
     if not self._device_buffers():  # (the twin: over the array calls)
         if counts is not None:
             counts.copy_(torch.from_numpy(self.get_lane_vehicle_count_array().reshape(shape)))
@@ -167,10 +203,56 @@ def observe_lanes_tensor(self, counts=None, waiting=None, speed_sum=None, bins=N
             speed_sum.copy_(torch.from_numpy(self.get_lane_speed_sum_array()))
         if bins is not None:
             bins.copy_(torch.from_numpy(self.get_lane_vehicle_bins_array(edges.detach().numpy())))
+        if n_front:
+            arrays = _lane_fronts(self, n_front, tracker)
+            for name, t in fronts.items():
+                if t is not None:
+                    t.copy_(torch.from_numpy(arrays[name]))
         return
     ptr = lambda t: 0 if t is None else t.data_ptr()  # noqa: E731
     self._observe_lanes_device(ptr(counts), ptr(waiting), ptr(speed_sum), ptr(bins), ptr(edges) if bins is not None else 0,
-                               n_bins, per_lane, torch.cuda.current_stream(device).cuda_stream)
+                               n_bins, per_lane, ptr(front_distance), ptr(front_speed), ptr(front_lane_steps),
+                               ptr(front_waiting_steps), n_front, torch.cuda.current_stream(device).cuda_stream)
+
+
+def _check_front_k(k):
+    if isinstance(k, bool) or not isinstance(k, int):
+        raise TypeError("k must be an int, not %s" % type(k).__name__)
+    if not 1 <= k <= MAX_FRONT:
+        raise ValueError("the front outputs hold 1 to %d vehicles per lane (their last dimension), not %d" % (MAX_FRONT, k))
+    return k
+
+
+def _lane_fronts(eng, k, tracker):
+    """{front output: numpy array [L, k]} over the array call; the tracker columns only with `tracker`."""
+    shape = tuple(eng._tensor_shapes()[0]) + (k,)
+    names = LANE_FRONT_OUTPUTS if tracker else LANE_FRONT_OUTPUTS[:2]
+    return {name: a.reshape(shape) for name, a in zip(names, eng._lane_fronts(k, tracker))}
+
+
+def get_lane_front_vehicles_tensor(self, k, distance=None, speed=None):
+    """(distance, speed) of the first k vehicles of every lane from the front, float64 [L, k] each on the engine's device, valid
+    on the current torch stream: the front_distance and front_speed outputs of observe_lanes_tensor (its docstring has the
+    order and the padding), 1 <= k <= 64.  `distance` / `speed`: contiguous tensors of that shape, filled in place; what is not
+    given is allocated."""
+    torch = _torch()
+    shape = tuple(self._tensor_shapes()[0]) + (_check_front_k(k),)
+    device = _engine_device(torch, self)
+    if distance is None:
+        distance = torch.empty(shape, dtype=torch.float64, device=device)
+    elif isinstance(distance, torch.Tensor) and tuple(distance.shape) != shape:
+        raise ValueError("distance must have shape %s, not %s" % (shape, tuple(distance.shape)))
+    if speed is None:
+        speed = torch.empty(shape, dtype=torch.float64, device=device)
+    observe_lanes_tensor(self, front_distance=distance, front_speed=speed)
+    return distance, speed
+
+
+def get_lane_front_vehicles_array(self, k):
+    """The front outputs of observe_lanes_tensor as a dict of numpy arrays [L, k] (same names, dtypes and padding):
+    front_distance and front_speed, and front_lane_steps and front_waiting_steps exactly when track_lane_flow is on.  Waits for
+    the device."""
+    return _lane_fronts(self, _check_front_k(k), self._lane_flow_tracking())
 
 
 def _lane_out(eng, dtype_name):
@@ -382,6 +464,8 @@ def install(*classes):
         cls.get_lane_speed_sum_tensor = get_lane_speed_sum_tensor
         cls.get_lane_vehicle_bins_tensor = get_lane_vehicle_bins_tensor
         cls.observe_lanes_tensor = observe_lanes_tensor
+        cls.get_lane_front_vehicles_tensor = get_lane_front_vehicles_tensor
+        cls.get_lane_front_vehicles_array = get_lane_front_vehicles_array
         cls.observe_intersections_tensor = observe_intersections_tensor
         cls.get_tl_phases_tensor = get_tl_phases_tensor
         cls.observe_intersections_array = observe_intersections_array

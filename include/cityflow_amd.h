@@ -543,6 +543,42 @@ typedef int32_t (*cfx_observe_lanes_device_fn)(cfx_engine *e, int32_t *counts, i
 typedef int32_t (*cfx_get_lane_features_fn)(cfx_engine *e, double *speed_sum, int32_t *bins, const double *edges, int32_t n_bins,
                                             int32_t per_lane_edges);
 #define CFX_MAX_LANE_BINS 32
+#define CFX_MAX_LANE_FRONT 64
+
+/* ---- Every per-lane observation through one descriptor, the first vehicles from the front among them (OPTIONAL entry points,
+ * as above).  v(l, k) is lane l's k-th vehicle from the front (the one closest to the lane's end first, the order of
+ * cfx_get_vehicles inside a drivable), n(l) = counts[l]; rows of n_front slots, 1 <= n_front <= 64:
+ *   front_distance[l * n_front + k]       double: dis of v(l, k), a copy                             padding -1.0
+ *   front_speed[...]                      double: speed of v(l, k), a copy                           padding 0.0
+ *   front_lane_steps[...]                 int32: s - since(v(l, k)) of the lane-flow tracker below   padding 0
+ *   front_waiting_steps[...]              int32: wait(v(l, k)) of the tracker                        padding 0
+ * A slot is real exactly if k < n(l); slots k >= n(l) hold the padding (-1.0 is a convenience: counts decides).  Every
+ * element of a given output is written.  The two tracker columns need the tracker on ("cfx_lane_flow_enable"; CFX_ERR_STATE otherwise,
+ * so never with lane change or on a tile) and show the tracker as of its last tick, s = the step counter then; a
+ * vehicle whose record is not {this lane, that tick} reports 0, 0 — what a baseline would give it, so a baseline that is
+ * still due (cfx_reset, cfx_load_state) reads as if taken.  Reading changes nothing in the tracker.
+ * The descriptor: the caller sets struct_size = sizeof(cfx_lane_obs) and zeroes what it does not use; members behind
+ * struct_size read as zero (a library newer than its caller) and a library that knows fewer members than struct_size names
+ * rejects the call.  counts / waiting / speed_sum / bins / edges / n_bins / per_lane_edges are cfx_observe_lanes_device's.
+ *   "cfx_observe_lane_obs_device"  every pointer device memory (edges too), any output NULL (at least one given), written by
+ *                               ONE kernel on the engine's stream, ordered against consumer_stream as cfx_observe_device.  With
+ *                               front outputs alone a lane's walk ends behind its first n_front vehicles.
+ *   "cfx_get_lane_obs"          the same outputs into host memory, edges read from host memory; synchronous (engine-owned
+ *                               device scratch, kept between calls).
+ * "cfx_observe_lanes_device", "cfx_observe_device" and "cfx_get_lane_features" are these two calls with the front outputs NULL. */
+typedef struct cfx_lane_obs {
+    int32_t struct_size;
+    int32_t n_bins, per_lane_edges;
+    int32_t n_front;             /* slots per lane of the four front outputs (0 allowed when none is given) */
+    int32_t *counts, *waiting;
+    double *speed_sum;
+    int32_t *bins;
+    const double *edges;
+    double *front_distance, *front_speed;
+    int32_t *front_lane_steps, *front_waiting_steps;
+} cfx_lane_obs;
+typedef int32_t (*cfx_observe_lane_obs_device_fn)(cfx_engine *e, const cfx_lane_obs *obs, void *consumer_stream);
+typedef int32_t (*cfx_get_lane_obs_fn)(cfx_engine *e, const cfx_lane_obs *obs);
 
 /* ---- Per-intersection movement and phase observations (OPTIONAL entry points, as above).  Intersection i (n_inters of them,
  * virtual ones included) has its roadLinks m < M_i = inter_n_roadlinks[i] ("movements", ll_roadlink) and its phases p < P_i

@@ -16,7 +16,14 @@ max-pressure loop whose reward (vehicles that left each lane, and the steps they
 observe_lane_flow_tensor(left, left_waiting_steps, reset=True), against the same loop with the reward built from
 get_lane_vehicles() + get_vehicle_speed() and a Python diff every step; both rewards are asserted equal first.
 --lane-flow-only trace runs next_step + observe_lanes_tensor(counts, waiting) + observe_lane_flow_tensor(reset=True) alone, so
-that a kernel trace shows kr_lane_features, kr_lane_flow and k_lane_flow_drain side by side."""
+that a kernel trace shows kr_lane_features, kr_lane_flow and k_lane_flow_drain side by side.
+       python tools/rl_device_loop.py --fronts [--runs N] [--fronts-only four|k8|k32|all8|all32|fronts32]
+--fronts: what the front-K outputs of observe_lanes_tensor cost and replace — the launch alone (host clock, 1 launch + events) with
+the four per-lane outputs, with front_distance + front_speed added at K = 8 and K = 32, with all four front outputs added
+(tracking on), alternated --runs times; then the host path on the same state: get_lane_vehicles() + get_vehicle_distance() +
+get_vehicle_speed() and a Python gather of the first K per lane, asserted equal to the tensors first.  --fronts-only runs one
+output set in the observe -> policy -> set -> next_step loop of --features-only, for a kernel trace (`four` runs on any
+version of the package: it is the launch --features-only all measures)."""
 import argparse
 import os
 import sys
@@ -36,6 +43,8 @@ ap.add_argument("--intersections", action="store_true")
 ap.add_argument("--intersections-only", choices=["lanes", "four", "seven", "no_waiting"], default=None)
 ap.add_argument("--lane-flow", action="store_true")
 ap.add_argument("--lane-flow-only", choices=["trace"], default=None)
+ap.add_argument("--fronts", action="store_true")
+ap.add_argument("--fronts-only", choices=["four", "k8", "k32", "all8", "all32", "fronts32"], default=None)
 ap.add_argument("--runs", type=int, default=3)
 args = ap.parse_args()
 sys.argv = [sys.argv[0]]
@@ -331,6 +340,81 @@ def lane_flow(name, eng, n, runs, only):
         print("%-6s median %10.1f us   min %10.1f   max %10.1f" % (k, float(np.median(v)), min(v), max(v)), flush=True)
     print("python loop / tensor loop %8.1fx" % (float(np.median(res["python"])) / float(np.median(res["tensor"]))), flush=True)
 
+
+def fronts(name, eng, n, runs, only):
+    device = torch.device("cuda", eng._stream_handle()[1])
+    n_phases = torch.from_numpy(eng._phase_counts()).to(device).long()
+    npos = torch.clamp(n_phases, min=1)
+    lanes = eng.lane_ids()
+    L = len(lanes)
+    idx = (torch.arange(n_phases.shape[0], device=device) * 7) % L
+    edges = torch.from_numpy(eng.lane_lengths()[:, None] * np.array([0.0, 1.0 / 3.0, 2.0 / 3.0, np.inf])).to(device)
+    four = {"counts": torch.empty(L, dtype=torch.int32, device=device), "waiting": torch.empty(L, dtype=torch.int32, device=device),
+            "speed_sum": torch.empty(L, dtype=torch.float64, device=device), "bins": torch.empty((L, 3), dtype=torch.int32, device=device),
+            "edges": edges}
+
+    def front_outputs(k, tracker):
+        t = {"front_distance": torch.empty((L, k), dtype=torch.float64, device=device),
+             "front_speed": torch.empty((L, k), dtype=torch.float64, device=device)}
+        if tracker:
+            t["front_lane_steps"] = torch.empty((L, k), dtype=torch.int32, device=device)
+            t["front_waiting_steps"] = torch.empty((L, k), dtype=torch.int32, device=device)
+        return t
+
+    sets = {"four": dict(four), "k8": dict(four, **front_outputs(8, False)), "k32": dict(four, **front_outputs(32, False)),
+            "all8": dict(four, **front_outputs(8, True)), "all32": dict(four, **front_outputs(32, True)),
+            "fronts32": front_outputs(32, False)}
+
+    def host_path(k):
+        lv, dist, speed = eng.get_lane_vehicles(), eng.get_vehicle_distance(), eng.get_vehicle_speed()
+        d, v = np.full((L, k), -1.0), np.zeros((L, k))
+        for l, lane in enumerate(lanes):
+            for j, veh in enumerate(lv[lane][:k]):
+                d[l, j], v[l, j] = dist[veh], speed[veh]
+        return d, v
+
+    for _ in range(300):
+        eng.next_step()
+    eng.sync()
+    print("# %s" % name, flush=True)
+    if only:
+        if only.startswith("all"):
+            eng.track_lane_flow(True)
+        out = sets[only]
+        c, w = four["counts"], four["waiting"]
+        if only == "fronts32":
+            c.zero_()
+            w.zero_()
+
+        def body(s):
+            eng.observe_lanes_tensor(**out)
+            eng.set_tl_phases_tensor(torch.where(n_phases >= 0, (c[idx].long() + w[idx].long() + s) % npos, -1))
+            eng.next_step()
+        measure("observe_lanes_tensor loop, outputs: %s" % only, eng, body, n)
+        return
+    eng.track_lane_flow(True)
+    for k in (8, 32):  # the tensors are what the host path gives, before anything is timed
+        eng.observe_lanes_tensor(**sets["k%d" % k])
+        d, v = host_path(k)
+        assert np.array_equal(sets["k%d" % k]["front_distance"].cpu().numpy(), d) and np.array_equal(sets["k%d" % k]["front_speed"].cpu().numpy(), v)
+    print("front_distance / front_speed equal the host path's at K = 8 and 32 (%d vehicles on lanes, fullest lane %d)"
+          % (int(four["counts"].sum()), int(four["counts"].max())), flush=True)
+    res = {k: [] for k in sets}
+    for r in range(runs):
+        for k, out in sets.items():
+            res[k].append(measure("observe_lanes_tensor(%s) alone (1 launch + events) (run %d)" % (k, r), eng,
+                                  lambda s, out=out: eng.observe_lanes_tensor(**out), n))
+    for k, v in res.items():
+        print("%-9s median %8.1f us   min %8.1f   max %8.1f" % (k, float(np.median(v)), min(v), max(v)), flush=True)
+    for k in (8, 32):
+        measure("host path: 3 dict getters + Python gather of the first %d per lane" % k, eng, lambda s, k=k: host_path(k), max(n // 40, 5))
+
+
+if args.fronts or args.fronts_only:
+    e = _cityflow.Engine(cfg, 1)
+    fronts("Engine, 30x30 RL workload (%d signals, %d lanes)" % (len(e.intersection_ids()), len(e.lane_ids())), e, args.iters,
+           args.runs, args.fronts_only)
+    sys.exit(0)
 
 if args.lane_flow or args.lane_flow_only:
     e = _cityflow.Engine(cfg, 1)
