@@ -173,9 +173,10 @@ class Seen:
             assert max(len(s) for s in self.phases) >= 2, "no intersection showed two phases"
 
 
-def run_against_oracle(eng, cfg, steps, every, where, phases_change=True):
+def run_against_oracle(eng, cfg, steps, every, where, phases_change=True, seen=None):
+    """`seen`: a Seen (or a subclass that asks for more) to fill and check instead of a fresh one."""
     tables = Tables(eng, cfg)
-    seen = Seen()
+    seen = Seen() if seen is None else seen
     for s in range(steps):
         eng.next_step()
         if s % every == every - 1:
@@ -330,6 +331,20 @@ def test_outputs_equal_the_oracle_grid_6x6(mod, scen, workdir, layout, net):
     if eng._device_buffers():
         assert eng._layout() == ("ring" if layout == "auto" else "dense")
     run_against_oracle(eng, cfg, 300, 25, "%s %s" % (net, layout))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("layout", ["auto", "dense"])
+def test_outputs_equal_the_oracle_example_1x1(mod, scen, workdir, layout):
+    """Seven-lane roads: three in-lanes per roadLink, 196 laneLinks at the one intersection."""
+    extra = {} if layout == "auto" else {"cfx": {"layout": "dense"}}
+    cfg = scen.materialize("example_1x1", workdir, **extra)
+    eng = mod.Engine(cfg, 1)
+    if eng._device_buffers():
+        assert eng._layout() == ("ring" if layout == "auto" else "dense")
+    tables = Tables(eng, cfg)
+    assert max(len(a) for rl in tables.ins for a in rl) == 3
+    run_against_oracle(eng, cfg, 300, 25, "example_1x1 %s" % layout)
 
 
 @pytest.mark.gpu

@@ -32,6 +32,9 @@ def edge_sets(lengths):
         ("inverted and NaN", np.array([-inf, 0.0, 20.0, 10.0, inf, np.nan, 5.0])),
         ("B = 32 per lane", lengths[:, None] * np.linspace(0.0, 1.0, 33)),
         ("B = 32 shared", np.concatenate([[-inf], np.linspace(0.0, 300.0, 31), [inf]])),
+        # (the shared row is written for 300 m lanes; the same scheme scaled to each lane's own length)
+        ("B = 32 per lane, open ends", np.concatenate([np.full((L, 1), -inf), lengths[:, None] * np.linspace(0.0, 1.0, 31),
+                                                        np.full((L, 1), inf)], axis=1)),
         ("one bin", np.array([0.0, 100.0])),
     ]
 
@@ -49,8 +52,7 @@ def dict_oracle(eng, edges):
         for v in lanes[lid]:
             s += speed[v]
             d = dist[v]
-            for b in range(B):
-                bins[l, b] += rows[l, b] <= d < rows[l, b + 1]
+            bins[l] += (rows[l, :-1] <= d) & (d < rows[l, 1:])  # (every bin at once: lo <= d < hi)
         ssum[l] = s
     return ssum, bins
 
@@ -68,8 +70,7 @@ def view_oracle(eng, edges):
             continue
         counts[d] += 1
         ssum[d] = ssum[d] + v
-        for b in range(B):
-            bins[d, b] += rows[d, b] <= x < rows[d, b + 1]
+        bins[d] += (rows[d, :-1] <= x) & (x < rows[d, 1:])  # (every bin at once: lo <= x < hi)
     return ssum, bins, counts
 
 

@@ -63,9 +63,11 @@ def want_fronts(lanes, k):
 
 
 class Looked:
-    """What the checked states contained, per K."""
+    """What the checked states contained, per K.  `beyond_64`: the three kinds of lane are asked for at K = 64 too (a network
+    whose lanes hold more than 64 vehicles)."""
 
-    def __init__(self):
+    def __init__(self, beyond_64=False):
+        self.beyond_64 = beyond_64
         self.seen = {k: set() for k in KS}
         self.moving = self.steps = self.waits = 0
 
@@ -80,7 +82,7 @@ class Looked:
 
     def enough(self, tracker=False):
         for k in KS:
-            if k <= 33:
+            if k <= 33 or self.beyond_64:
                 need = {"n > K", "n = 0"} | ({"0 < n < K"} if k >= 2 else set())
                 assert need <= self.seen[k], "K = %d: the checked states never had %s" % (k, sorted(need - self.seen[k]))
         assert self.moving > 0, "no vehicle with a speed in the checked states"
@@ -120,15 +122,15 @@ def check_fronts(eng, lanes_per_env, where, tracker, ks=KS):
         assert np.array_equal(one[names[-1]].cpu().numpy(), want[names[-1]]), "%s, K = %d: %s alone" % (where, k, names[-1])
 
 
-def run_against_dict_oracle(eng, steps, every, where, tracker, fused=False):
+def run_against_dict_oracle(eng, steps, every, where, tracker, fused=False, looked=None):
     """`tracker`: tracking on from the start, the tracker columns against Model.  `fused`: at every check one launch that fills all
-    eight lane outputs, against the four getters that were there before."""
+    eight lane outputs, against the four getters that were there before.  `looked`: a Looked to fill and check instead of a fresh one."""
     model = None
     if tracker:
         eng.track_lane_flow(True)
         model = Model(eng.lane_ids())
         model.baseline(eng.get_lane_vehicles(), 0)
-    looked = Looked()
+    looked = Looked() if looked is None else looked
     for s in range(steps):
         eng.next_step()
         if model is not None:
@@ -173,8 +175,8 @@ def test_tracker_columns_equal_the_model_twin(mod, scen, workdir):
     run_against_dict_oracle(twin(mod, scen.materialize("grid_6x6", workdir)), 400, 25, "twin, tracking", tracker=True, fused=True)
 
 
-def vector_body(vec, singles, steps, every):
-    looked = Looked()
+def vector_body(vec, singles, steps, every, looked=None):
+    looked = Looked() if looked is None else looked
     for s in range(steps):
         vec.next_step()
         for e in singles:
@@ -193,8 +195,9 @@ def test_vector_engine_equals_standalone_twins(mod, scen, workdir):
     vector_body(vec, singles, 400, 25)
 
 
-def vector_tracker_body(vec, singles, steps, every):
-    """The tracker columns of a VectorEngine against standalone engines that track too (those against Model: the tests above)."""
+def vector_tracker_body(vec, singles, steps, every, looked=None):
+    """The tracker columns of a VectorEngine against standalone engines that track too (those against Model: the tests above).
+    `looked`: a Looked to fill with what the standalone engines held at every check (the caller asks it what it needs)."""
     vec.track_lane_flow(True)
     for e in singles:
         e.track_lane_flow(True)
@@ -205,6 +208,8 @@ def vector_tracker_body(vec, singles, steps, every):
             e.next_step()
         if s % every != every - 1:
             continue
+        if looked is not None:
+            looked.at([dict_lanes(e) for e in singles])
         for k in (16, 33):
             got, want = vec.get_lane_front_vehicles_array(k), [e.get_lane_front_vehicles_array(k) for e in singles]
             for name in FRONT + TRACKER:
