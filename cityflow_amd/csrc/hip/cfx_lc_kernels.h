@@ -22,7 +22,10 @@
 
 namespace cfxd {
 
-constexpr int kLcRoadInserts = 32;  // shadows one road can get in one step (more: CFX_ERR_CAPACITY)
+#ifndef CFX_LC_ROAD_INSERTS
+#define CFX_LC_ROAD_INSERTS 32
+#endif
+constexpr int kLcRoadInserts = CFX_LC_ROAD_INSERTS;  // shadows one road can get in one step (more: CFX_ERR_CAPACITY)
 
 // LaneChange::planChange lanechange.cpp:23-25
 __device__ __forceinline__ bool lcPlanChange(const LcDev &lc, int vid, int drv) {

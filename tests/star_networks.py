@@ -1,6 +1,6 @@
 """Star junctions: one signalised intersection `C` whose arms differ in lane count and length — networks the grid generator cannot
 make.  A plain helper module (not collected by pytest, no fixtures); tests/test_star_networks.py says which kernel branch each
-of the three networks below exists for.
+of the three star* networks below exists for, tests/test_lane_change_paths.py does so for the lane-change runs.
 
 star(): arm i lies at angle 2 pi i / arms.  Road in_i runs from the arm's outer node to C and out_i back, both with lanes[i]
 lanes of lengths[i] metres.  C has one roadLink per ordered pair of arms (index = the pair's position in `pairs(arms)`), a
@@ -27,6 +27,10 @@ NETWORKS = {
     "star7": dict(arms=7, lanes=[1] * 7, lengths=[300, 150, 60, 800, 300, 25, 300], width=20, mid=True),
     "star5": dict(arms=5, lanes=[1, 2, 3, 5, 2], lengths=[300, 300, 700, 300, 120], width=40, mid=True),
     "star3": dict(arms=3, lanes=[18, 1, 2], lengths=[200, 300, 300], width=80, mid=False),
+    # with lane_change=True (tests/test_lane_change_paths.py): a 9-lane road whose many candidates share few target lanes ...
+    "wide3": dict(arms=3, lanes=[9, 4, 3], lengths=[500, 700, 2000], width=60, mid=False),
+    # ... and 5-lane roads of 1950 m (28 segments) and 940 m that come to hold more than 400 vehicles
+    "long5": dict(arms=5, lanes=[5, 2, 3, 5, 2], lengths=[1900, 300, 700, 900, 120], width=40, mid=True),
 }
 
 
@@ -115,9 +119,10 @@ def star_flows(arms, mid):
     return flows
 
 
-def star(workdir, name, arms, lanes, lengths, width=30, mid=True, seed=0, layout="auto"):
+def star(workdir, name, arms, lanes, lengths, width=30, mid=True, seed=0, layout="auto", lane_change=False):
     """Write roadnet.json, flow.json and a config into workdir/<name>/; returns the config path.  layout="dense" asks for the
-    dense layout (cfx: {"layout": "dense"}); every (seed, layout) has a config file of its own beside the one network."""
+    dense layout (cfx: {"layout": "dense"}), lane_change for "laneChange": true; every (seed, layout, lane_change) has a
+    config file of its own beside the one network."""
     assert len(lanes) == len(lengths) == arms and layout in ("auto", "dense")
     d = os.path.join(workdir, name)
     os.makedirs(d, exist_ok=True)
@@ -126,15 +131,15 @@ def star(workdir, name, arms, lanes, lengths, width=30, mid=True, seed=0, layout
     with open(os.path.join(d, "flow.json"), "w") as f:
         json.dump(star_flows(arms, mid), f)
     cfg = {"interval": 1.0, "seed": seed, "dir": d + "/", "roadnetFile": "roadnet.json", "flowFile": "flow.json",
-           "rlTrafficLight": False, "laneChange": False, "saveReplay": False}
+           "rlTrafficLight": False, "laneChange": bool(lane_change), "saveReplay": False}
     if layout == "dense":
         cfg["cfx"] = {"layout": "dense"}
-    path = os.path.join(d, "config_seed%d_%s.json" % (seed, layout))
+    path = os.path.join(d, "config_seed%d_%s%s.json" % (seed, layout, "_lanechange" if lane_change else ""))
     with open(path, "w") as f:
         json.dump(cfg, f)
     return path
 
 
-def make(workdir, name, seed=0, layout="auto"):
+def make(workdir, name, seed=0, layout="auto", lane_change=False):
     """One of NETWORKS by name."""
-    return star(workdir, name, seed=seed, layout=layout, **NETWORKS[name])
+    return star(workdir, name, seed=seed, layout=layout, lane_change=lane_change, **NETWORKS[name])
