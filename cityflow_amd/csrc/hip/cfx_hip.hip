@@ -158,6 +158,10 @@ struct cfx_engine {
     // ever counts up; `flowBaseline`: a baseline is due before the next step or read (enabling, reset, cfx_load_state)
     bool flowOn = false, flowBaseline = false;
     LaneFlowDev flow{};
+    // cfx_trip_stats_enable: per-environment trip statistics across steps (k_trip_tick, cfx_kernels.h), kept like lane flow:
+    // `trip.seen` grows with the vehicle tables (ensureVidCap), `tripBaseline`: a baseline is due before the next step or read
+    bool tripOn = false, tripBaseline = false;
+    TripDev trip{};
     int cross2 = -1;                // cross phase: 1 = k_cross2 (throughput), 0 = k_cross (latency), -1 = by size
     HostMirror *hMirror = nullptr;  // pinned; valid while the last thing that changed the scalars was a step
     bool mirrorValid = false;
@@ -504,6 +508,10 @@ struct cfx_engine {
             if ((rc = growDeferred(&flow.rec, (size_t) spawned, nc))) return rc;
             HIP_TRY(hipMemsetAsync(flow.rec + spawned, 0xFF, (nc - (size_t) spawned) * sizeof(int4), stream));
         }
+        if (tripOn) {  // (numbers not used yet: never seen)
+            if ((rc = growDeferred(&trip.seen, (size_t) spawned, nc))) return rc;
+            HIP_TRY(hipMemsetAsync(trip.seen + spawned, 0xFF, nc - (size_t) spawned, stream));
+        }
         vidCap = nc;
         return CFX_OK;
     }
@@ -792,6 +800,32 @@ struct cfx_engine {
         flowBaseline = false;
         return flowTick(true);
     }
+    // cfx_trip_stats_enable: one tick (or baseline) over the vehicle numbers, on the committed state, after everything enqueued so far
+    int tripTick(bool baseline) {
+        if (baseline) {
+            HIP_TRY(hipMemsetAsync(trip.seen, 0xFF, std::max<size_t>(vidCap, 1), stream));
+            HIP_TRY(hipMemsetAsync(trip.env, 0, (size_t) trip.nEnvs * sizeof(cfx_trip_stats_env), stream));
+        }
+        if (spawned <= 0) return CFX_OK;
+        trip.state = vt.state;
+        trip.enterTime = vt.enterTime;
+        trip.route = vt.route;
+        trip.routeStart = dRouteStart.p;
+        trip.routeRoads = dRouteRoads.p;
+        trip.interval = cfg.interval;
+        trip.spawned = (int) spawned;
+        trip.vidCap = (int) vidCap;
+        trip.step = (int32_t) step;
+        trip.baseline = baseline ? 1 : 0;
+        hipLaunchKernelGGL(k_trip_tick, dim3(gridFor(((size_t) spawned + 15) / 16)), dim3(kBlock), 0, stream, trip);
+        HIP_TRY(hipGetLastError());
+        return CFX_OK;
+    }
+    int tripSettle() {
+        if (!tripOn || !tripBaseline) return CFX_OK;
+        tripBaseline = false;
+        return tripTick(true);
+    }
     int settle(bool withHistory = true) {
         if (haloImportPending) {
             haloImportPending = false;
@@ -977,6 +1011,7 @@ struct cfx_engine {
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipStreamSynchronize(stream));
         flowBaseline = flowOn;  // (taken on the state the caller sets up, before the next step or read)
+        tripBaseline = tripOn;
         return CFX_OK;
     }
 };
@@ -1354,6 +1389,7 @@ static int32_t stepImpl(cfx_engine *e, const cfx_spawn *recs, int32_t n) {
         if ((rc = e->ringEnsure())) return rc;
     }
     if ((rc = e->flowSettle())) return rc;  // (lane flow: a baseline that is due is taken on the state this step starts from)
+    if ((rc = e->tripSettle())) return rc;  // (trip statistics: likewise)
     if (e->observing && ++e->observeIdle > cfx_engine::kObserveIdle) {  // nobody has read the lane counts for a while
         e->observing = false;
         e->hCntValid = false;
@@ -1601,7 +1637,7 @@ static int32_t stepImpl(cfx_engine *e, const cfx_spawn *recs, int32_t n) {
         const bool useBig = e->cross2 >= 0 ? e->cross2 == 1 : activeEst > 240000;  // which form of the cross phase (§4)
         // This step's commit rides with the next step's admission (one launch less per step) where the step runs kr_cross,
         // which then advances the lights; the previous step's, if it is still pending, goes with this step's admission.
-        const bool deferCommit = e->ringMerge && !dbg && !e->tiled && !e->observing && !e->devObserving && !e->flowOn;  // (a caller that reads the lane counts after every step wants the commit now; so does the lane-flow tick)
+        const bool deferCommit = e->ringMerge && !dbg && !e->tiled && !e->observing && !e->devObserving && !e->flowOn && !e->tripOn;  // (a caller that reads the lane counts after every step wants the commit now; so do the lane-flow and the trip tick)
         // tiling: the previous step's halo import, if cfx_halo_wait left it to this launch
         const RingHaloIn hin = e->haloImportPending ? e->pendingImport : RingHaloIn{};
         e->haloImportPending = false;
@@ -1782,7 +1818,8 @@ static int32_t stepImpl(cfx_engine *e, const cfx_spawn *recs, int32_t n) {
         e->step += 1;
         e->mirrorValid = !e->tiled;
         e->histPending = e->hist.num != 0;  // (this step's Lane::history: with the next action launch, or settle() — on a tile behind the step's halo import)
-        if (e->flowOn) return e->flowTick(false);
+        if (e->flowOn && (rc = e->flowTick(false))) return rc;
+        if (e->tripOn) return e->tripTick(false);
         return CFX_OK;
     }
     const int64_t spare = e->tiled ? e->spareTotal : (int64_t) e->L;
@@ -1929,7 +1966,8 @@ static int32_t stepImpl(cfx_engine *e, const cfx_spawn *recs, int32_t n) {
         hipLaunchKernelGGL(k_lane_history, dim3(gridFor(e->L)), dim3(kBlock), 0, st, e->ctx(), e->hist);
         HIP_TRY(hipGetLastError());
     }
-    if (e->flowOn) return e->flowTick(false);
+    if (e->flowOn && (rc = e->flowTick(false))) return rc;
+    if (e->tripOn) return e->tripTick(false);
     return CFX_OK;
 }
 extern "C" {
@@ -3746,6 +3784,147 @@ int32_t cfx_lane_flow_set_state(cfx_engine *e, const int32_t *records, int32_t n
     HIP_TRY(hipStreamSynchronize(e->stream));
     e->flow.tick = tick;
     e->flowBaseline = false;
+    return CFX_OK;
+}
+
+// ---- per-environment trip statistics across steps (optional entry points of include/cityflow_amd.h, as above)
+int32_t cfx_trip_stats_enable(cfx_engine *e, int32_t on);
+int32_t cfx_observe_trip_stats_device(cfx_engine *e, const cfx_trip_stats_out *out, void *consumerStream);
+int32_t cfx_get_trip_stats(cfx_engine *e, const cfx_trip_stats_out *out);
+int32_t cfx_trip_stats_get_state(cfx_engine *e, cfx_trip_stats_env *envs, int32_t nEnvs);
+int32_t cfx_trip_stats_set_state(cfx_engine *e, const cfx_trip_stats_env *envs, int32_t nEnvs);
+static_assert(std::is_same<decltype(&cfx_trip_stats_enable), cfx_trip_stats_enable_fn>::value, "cfx_trip_stats_enable");
+static_assert(std::is_same<decltype(&cfx_observe_trip_stats_device), cfx_observe_trip_stats_device_fn>::value, "cfx_observe_trip_stats_device");
+static_assert(std::is_same<decltype(&cfx_get_trip_stats), cfx_get_trip_stats_fn>::value, "cfx_get_trip_stats");
+static_assert(std::is_same<decltype(&cfx_trip_stats_get_state), cfx_trip_stats_get_state_fn>::value, "cfx_trip_stats_get_state");
+static_assert(std::is_same<decltype(&cfx_trip_stats_set_state), cfx_trip_stats_set_state_fn>::value, "cfx_trip_stats_set_state");
+static_assert(sizeof(cfx_trip_stats_env) == 56, "cfx_trip_stats_env");
+
+// what every reader does first: the step's commit, the rings, a baseline that is due
+static int tripStatsPrepare(cfx_engine *e, const char *what) {
+    if (!e->tripOn) {
+        e->err = std::string(what) + ": trip tracking is off (cfx_trip_stats_enable)";
+        return CFX_ERR_STATE;
+    }
+    int rc;
+    if ((rc = e->settle(false))) return rc;
+    if (e->ring && (rc = e->ringEnsure())) return rc;
+    return e->tripSettle();
+}
+
+int32_t cfx_trip_stats_enable(cfx_engine *e, int32_t on) {
+    if (!e) return CFX_ERR_INVALID;
+    auto fail = [e](const std::string &m) { return e->fail(m); };
+    HIP_TRY(hipSetDevice(e->device));
+    if (!on) {
+        if (!e->tripOn) return CFX_OK;
+        HIP_TRY(hipStreamSynchronize(e->stream));  // (a tick may still be running; a shadow a growth retired stays with `retired`)
+        e->forget(e->trip.seen);
+        e->forget(e->trip.env);
+        HIP_TRY(hipFree(e->trip.seen));
+        HIP_TRY(hipFree(e->trip.env));
+        e->trip = TripDev{};
+        e->tripOn = e->tripBaseline = false;
+        return CFX_OK;
+    }
+    if (e->lc.on || e->tiled) {
+        e->err = "cfx_trip_stats_enable: not with lane change and not on a tile";
+        return CFX_ERR_STATE;
+    }
+    if (e->tripOn) return CFX_OK;
+    const int nEnvs = e->cfg.n_envs > 1 ? e->cfg.n_envs : 1;
+    if (e->R % nEnvs != 0) {
+        e->err = "cfx_trip_stats_enable: n_envs does not divide the number of roads";
+        return CFX_ERR_STATE;
+    }
+    int rc;
+    if ((rc = e->settle(false))) return rc;
+    if (e->ring && (rc = e->ringEnsure())) return rc;
+    if ((rc = e->allocRaw(&e->trip.seen, e->vidCap))) return rc;
+    if ((rc = e->allocRaw(&e->trip.env, (size_t) nEnvs))) return rc;
+    e->trip.nEnvs = nEnvs;
+    e->trip.roadsPerEnv = std::max(e->R / nEnvs, 1);
+    e->tripOn = e->tripBaseline = true;
+    return e->tripSettle();
+}
+
+static void launchTripDrain(cfx_engine *e, const cfx_trip_stats_out &o) {
+    hipLaunchKernelGGL(k_trip_drain, dim3(gridFor((size_t) e->trip.nEnvs)), dim3(kBlock), 0, e->stream, e->trip.env, e->trip.nEnvs,
+                       (long long) e->step, e->cfg.interval, o);
+}
+
+int32_t cfx_observe_trip_stats_device(cfx_engine *e, const cfx_trip_stats_out *out, void *consumerStream) {
+    if (!e || !out) return CFX_ERR_INVALID;
+    const void *ptrs[9] = {out->entered, out->admitted, out->admitted_buffer_steps, out->finished, out->finished_travel_steps,
+                           out->in_system, out->buffered, out->in_system_travel_steps, out->average_travel_time};
+    static const char *const names[9] = {"entered", "admitted", "admitted_buffer_steps", "finished", "finished_travel_steps",
+                                         "in_system", "buffered", "in_system_travel_steps", "average_travel_time"};
+    bool any = false;
+    for (const void *q : ptrs) any = any || q;
+    if (!any) return CFX_ERR_INVALID;
+    auto fail = [e](const std::string &m) { return e->fail(m); };
+    HIP_TRY(hipSetDevice(e->device));
+    int rc;
+    for (int i = 0; i < 9; ++i)
+        if (ptrs[i] && (rc = checkDevicePointer(e, ptrs[i], (std::string("cfx_observe_trip_stats_device: ") + names[i]).c_str()))) return rc;
+    if ((rc = tripStatsPrepare(e, "cfx_observe_trip_stats_device"))) return rc;
+    if ((rc = e->orderAfterCaller((hipStream_t) consumerStream))) return rc;
+    launchTripDrain(e, *out);
+    HIP_TRY(hipGetLastError());
+    return e->orderCallerAfter((hipStream_t) consumerStream);
+}
+
+// (the records themselves come back, 56 bytes per environment, and the host does the drain's few lines: no device scratch)
+int32_t cfx_get_trip_stats(cfx_engine *e, const cfx_trip_stats_out *out) {
+    if (!e || !out) return CFX_ERR_INVALID;
+    auto fail = [e](const std::string &m) { return e->fail(m); };
+    HIP_TRY(hipSetDevice(e->device));
+    int rc;
+    if ((rc = tripStatsPrepare(e, "cfx_get_trip_stats"))) return rc;
+    std::vector<cfx_trip_stats_env> envs((size_t) e->trip.nEnvs);
+    HIP_TRY(hipMemcpyAsync(envs.data(), e->trip.env, envs.size() * sizeof(cfx_trip_stats_env), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    const cfx_trip_stats_out &o = *out;
+    for (size_t r = 0; r < envs.size(); ++r) {
+        const cfx_trip_stats_env &a = envs[r];
+        const int32_t inSystem = a.base_in_system + a.entered - a.finished;
+        const int64_t inSteps = (int64_t) inSystem * e->step - (a.enter_sum_created - a.enter_sum_finished);
+        const int64_t n = (int64_t) a.finished + inSystem;
+        if (o.entered) o.entered[r] = a.entered;
+        if (o.admitted) o.admitted[r] = a.admitted;
+        if (o.admitted_buffer_steps) o.admitted_buffer_steps[r] = a.admitted_buffer_steps;
+        if (o.finished) o.finished[r] = a.finished;
+        if (o.finished_travel_steps) o.finished_travel_steps[r] = a.finished_travel_steps;
+        if (o.in_system) o.in_system[r] = inSystem;
+        if (o.buffered) o.buffered[r] = a.base_buffered + a.entered - a.admitted;
+        if (o.in_system_travel_steps) o.in_system_travel_steps[r] = inSteps;
+        if (o.average_travel_time)
+            o.average_travel_time[r] = n == 0 ? 0.0 : (double) (a.finished_travel_steps + inSteps) * e->cfg.interval / (double) n;
+    }
+    return CFX_OK;
+}
+
+int32_t cfx_trip_stats_get_state(cfx_engine *e, cfx_trip_stats_env *envs, int32_t nEnvs) {
+    if (!e || !envs) return CFX_ERR_INVALID;
+    auto fail = [e](const std::string &m) { return e->fail(m); };
+    HIP_TRY(hipSetDevice(e->device));
+    int rc;
+    if ((rc = tripStatsPrepare(e, "cfx_trip_stats_get_state"))) return rc;
+    if (nEnvs != e->trip.nEnvs) return e->fail("cfx_trip_stats_get_state: n_envs is not the engine's"), CFX_ERR_INVALID;
+    HIP_TRY(hipMemcpyAsync(envs, e->trip.env, (size_t) nEnvs * sizeof(cfx_trip_stats_env), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    return CFX_OK;
+}
+
+int32_t cfx_trip_stats_set_state(cfx_engine *e, const cfx_trip_stats_env *envs, int32_t nEnvs) {
+    if (!e || !envs) return CFX_ERR_INVALID;
+    auto fail = [e](const std::string &m) { return e->fail(m); };
+    HIP_TRY(hipSetDevice(e->device));
+    int rc;
+    if ((rc = tripStatsPrepare(e, "cfx_trip_stats_set_state"))) return rc;  // (the load's baseline builds the shadow; then the records)
+    if (nEnvs != e->trip.nEnvs) return e->fail("cfx_trip_stats_set_state: n_envs is not the engine's"), CFX_ERR_INVALID;
+    HIP_TRY(hipMemcpyAsync(e->trip.env, envs, (size_t) nEnvs * sizeof(cfx_trip_stats_env), hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
     return CFX_OK;
 }
 

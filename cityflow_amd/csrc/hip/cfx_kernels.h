@@ -2444,6 +2444,203 @@ __global__ void __launch_bounds__(kBlock) k_lane_flow_drain(cfx_lane_flow_lane *
     }
 }
 
+// cfx_trip_stats_enable: per-environment trip statistics across steps (include/cityflow_amd.h has the rules).  One TICK after
+// every step, on the committed state, over the vehicle numbers [0, spawned): a thread compares sixteen status bytes with their
+// shadow `seen` (the status at the previous tick, 0xFF = never seen) — one 16-byte load each — and only looks at a number whose
+// byte differs; in a step few do.  A changed number's enter step and environment come from the tables the device holds; what a
+// thread finds for one environment goes into the block's LDS table (environments below kTripLdsEnvs; beyond that straight to
+// memory) and from there, once per block and environment, into the environment's record with vector atomics.  A block without a
+// change ends behind one barrier.  The present values (in_system, buffered, in_system_travel_steps) are not kept: they follow
+// from the record at read time (k_trip_drain), so nothing ever scans the vehicles alive.
+// A BASELINE is the same launch over a shadow of 0xFF and zeroed records: every number then differs, and the three counts are
+// read as alive / waiting instead of entered / admitted.
+struct TripDev {
+    uint8_t *seen;             // [vidCap]
+    cfx_trip_stats_env *env;   // [nEnvs]
+    const uint8_t *state;      // VidTable::state
+    const double *enterTime;   // VidTable::enterTime
+    const int32_t *route, *routeStart, *routeRoads;
+    double interval;
+    int spawned, vidCap;       // (bytes at and beyond `spawned` are not defined in `state` and stay 0xFF in `seen`)
+    int nEnvs, roadsPerEnv;
+    int32_t step;              // the step counter after the step
+    int baseline;
+};
+constexpr int kTripLdsEnvs = 64;
+constexpr int kTripCountBits = 21;  // three counts of a block (at most 16 kBlock each) in one 64-bit word
+static_assert(16 * kBlock < (1 << kTripCountBits), "kTripCountBits");
+static_assert(kTripLdsEnvs * 4 == kBlock, "k_trip_tick zeroes its LDS table with one store per thread");
+
+// {counts, sum of e over the first-seen, the admitted, the finished} of one environment into its record
+// (`t` by value: taken by reference, the kernel argument is staged in scratch)
+__device__ __forceinline__ void tripCommit(const TripDev t, int env, unsigned long long cnt, long long s1, long long s2, long long s3) {
+    constexpr unsigned long long kMask = (1ULL << kTripCountBits) - 1;
+    const int c0 = (int) (cnt & kMask), c1 = (int) ((cnt >> kTripCountBits) & kMask), c2 = (int) (cnt >> (2 * kTripCountBits));
+    cfx_trip_stats_env *a = t.env + env;
+    auto add64 = [](int64_t *p, long long v) { atomicAdd((unsigned long long *) p, (unsigned long long) v); };
+    if (t.baseline) {
+        if (c0) atomicAdd(&a->base_in_system, c0);
+        if (c1) atomicAdd(&a->base_buffered, c1);
+        if (s1) add64(&a->enter_sum_created, s1);
+        return;
+    }
+    if (c0) atomicAdd(&a->entered, c0);
+    if (s1) add64(&a->enter_sum_created, s1);
+    if (c1) {
+        atomicAdd(&a->admitted, c1);
+        add64(&a->admitted_buffer_steps, (long long) c1 * (t.step - 1) - s2);
+    }
+    if (c2) {
+        atomicAdd(&a->finished, c2);
+        add64(&a->finished_travel_steps, (long long) c2 * (t.step - 1) - s3);
+        if (s3) add64(&a->enter_sum_finished, s3);
+    }
+}
+
+__global__ void __launch_bounds__(kBlock) k_trip_tick(TripDev t) {
+    __shared__ unsigned long long acc[kTripLdsEnvs * 4];
+    acc[threadIdx.x] = 0;
+    __syncthreads();
+    const long long base = ((long long) blockIdx.x * kBlock + threadIdx.x) * 16;
+    const int valid = (int) min(16LL, max(0LL, (long long) t.spawned - base));
+    bool changed = false;
+    if (valid > 0) {
+        unsigned now[4], old[4];
+        const bool whole = base + 16 <= (long long) t.vidCap;  // (the tables' last sixteen may be cut short: byte by byte)
+        if (whole) {
+            const uint4 a = *reinterpret_cast<const uint4 *>(t.state + base);
+            const uint4 b = *reinterpret_cast<const uint4 *>(t.seen + base);
+            now[0] = a.x, now[1] = a.y, now[2] = a.z, now[3] = a.w;
+            old[0] = b.x, old[1] = b.y, old[2] = b.z, old[3] = b.w;
+        } else {
+#pragma unroll
+            for (int w = 0; w < 4; ++w) now[w] = old[w] = 0xFFFFFFFFu;
+#pragma unroll
+            for (int j = 0; j < 16; ++j)
+                if (j < valid) {
+                    const unsigned sh = 8u * (j & 3), keep = ~(0xFFu << sh);
+                    now[j >> 2] = (now[j >> 2] & keep) | ((unsigned) t.state[base + j] << sh);
+                    old[j >> 2] = (old[j >> 2] & keep) | ((unsigned) t.seen[base + j] << sh);
+                }
+        }
+        int curEnv = -1;
+        unsigned long long cnt = 0;
+        long long s1 = 0, s2 = 0, s3 = 0;
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+            const int nv = min(max(valid - 4 * w, 0), 4);  // the tail: a byte that is not a vehicle yet keeps its shadow
+            const unsigned mask = nv == 4 ? 0xFFFFFFFFu : (1u << (8 * nv)) - 1u;
+            now[w] = (now[w] & mask) | (old[w] & ~mask);
+            const unsigned diff = now[w] ^ old[w];
+            if (diff == 0) continue;
+            changed = true;
+            // The enter step and the environment of the word's four numbers, asked for together before any is used: a step's new
+            // vehicles are consecutive numbers, so a thread that has one change has sixteen, and one number after the other
+            // would be sixteen dependent chains enterTime / route -> routeStart -> routeRoads in a row.  (A byte beyond
+            // `spawned` reads the last vehicle's entries and is not used.)
+            long long e4[4];
+            int env4[4] = {0, 0, 0, 0};
+#pragma unroll
+            for (int k = 0; k < 4; ++k) e4[k] = __double2ll_rn(t.enterTime[min(base + 4 * w + k, (long long) t.spawned - 1)] / t.interval);
+            if (t.nEnvs > 1) {
+                int r4[4];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) r4[k] = t.route[min(base + 4 * w + k, (long long) t.spawned - 1)];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) r4[k] = t.routeStart[r4[k]];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) env4[k] = min(max(t.routeRoads[r4[k]] / t.roadsPerEnv, 0), t.nEnvs - 1);
+            }
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                if (((diff >> (8 * k)) & 0xFFu) == 0) continue;
+                const unsigned prev = (old[w] >> (8 * k)) & 0xFFu, cur = (now[w] >> (8 * k)) & 0xFFu;
+                const long long e = e4[k];
+                const int env = env4[k];
+                if (env != curEnv) {
+                    if (cnt) {
+                        if (curEnv < kTripLdsEnvs) {
+                            atomicAdd(&acc[4 * curEnv], cnt);
+                            atomicAdd(&acc[4 * curEnv + 1], (unsigned long long) s1);
+                            atomicAdd(&acc[4 * curEnv + 2], (unsigned long long) s2);
+                            atomicAdd(&acc[4 * curEnv + 3], (unsigned long long) s3);
+                        } else {
+                            tripCommit(t, curEnv, cnt, s1, s2, s3);
+                        }
+                    }
+                    curEnv = env;
+                    cnt = 0;
+                    s1 = s2 = s3 = 0;
+                }
+                if (t.baseline) {
+                    if (cur != 2u) {
+                        cnt += 1ULL;
+                        s1 += e;
+                        if (cur == 0u) cnt += 1ULL << kTripCountBits;
+                    }
+                } else {
+                    if (prev == 0xFFu) {
+                        cnt += 1ULL;
+                        s1 += e;
+                    }
+                    if (cur == 1u && prev != 1u) {
+                        cnt += 1ULL << kTripCountBits;
+                        s2 += e;
+                    }
+                    if (cur == 2u && prev != 2u) {
+                        cnt += 1ULL << (2 * kTripCountBits);
+                        s3 += e;
+                    }
+                }
+            }
+        }
+        if (cnt) {
+            if (curEnv < kTripLdsEnvs) {
+                atomicAdd(&acc[4 * curEnv], cnt);
+                atomicAdd(&acc[4 * curEnv + 1], (unsigned long long) s1);
+                atomicAdd(&acc[4 * curEnv + 2], (unsigned long long) s2);
+                atomicAdd(&acc[4 * curEnv + 3], (unsigned long long) s3);
+            } else {
+                tripCommit(t, curEnv, cnt, s1, s2, s3);
+            }
+        }
+        if (changed) {
+            if (whole) {
+                *reinterpret_cast<uint4 *>(t.seen + base) = make_uint4(now[0], now[1], now[2], now[3]);
+            } else {
+#pragma unroll
+                for (int j = 0; j < 16; ++j)
+                    if (j < valid) t.seen[base + j] = (uint8_t) (now[j >> 2] >> (8 * (j & 3)));
+            }
+        }
+    }
+    if (!__syncthreads_or(changed ? 1 : 0)) return;
+    const int env = threadIdx.x;
+    if (env < kTripLdsEnvs && env < t.nEnvs && acc[4 * env])
+        tripCommit(t, env, acc[4 * env], (long long) acc[4 * env + 1], (long long) acc[4 * env + 2], (long long) acc[4 * env + 3]);
+}
+
+// cfx_observe_trip_stats_device / cfx_get_trip_stats: the nine outputs from the environments' records (any pointer may be null).
+// One thread per environment; `step` is the step counter of the last tick.
+__global__ void __launch_bounds__(kBlock) k_trip_drain(const cfx_trip_stats_env *envs, int nEnvs, long long step, double interval,
+                                                       cfx_trip_stats_out o) {
+    const int r = (int) (blockIdx.x * (size_t) blockDim.x + threadIdx.x);
+    if (r >= nEnvs) return;
+    const cfx_trip_stats_env a = envs[r];
+    const int inSystem = a.base_in_system + a.entered - a.finished;
+    const long long inSteps = (long long) inSystem * step - (a.enter_sum_created - a.enter_sum_finished);
+    const long long n = (long long) a.finished + inSystem;
+    if (o.entered) o.entered[r] = a.entered;
+    if (o.admitted) o.admitted[r] = a.admitted;
+    if (o.admitted_buffer_steps) o.admitted_buffer_steps[r] = a.admitted_buffer_steps;
+    if (o.finished) o.finished[r] = a.finished;
+    if (o.finished_travel_steps) o.finished_travel_steps[r] = a.finished_travel_steps;
+    if (o.in_system) o.in_system[r] = inSystem;
+    if (o.buffered) o.buffered[r] = a.base_buffered + a.entered - a.admitted;
+    if (o.in_system_travel_steps) o.in_system_travel_steps[r] = inSteps;
+    if (o.average_travel_time) o.average_travel_time[r] = n == 0 ? 0.0 : (double) (a.finished_travel_steps + inSteps) * interval / (double) n;
+}
+
 // cfx_observe_intersections_device / cfx_get_intersection_features: what a signal policy observes, per intersection, in one
 // launch (any output may be null; every element of a given output has exactly one writer, padding included, so the caller's
 // buffers need no zeroing and there is no atomic).  One BLOCK owns one intersection; its sixteen groups of kFeatGroup threads

@@ -498,6 +498,9 @@ void EngineHost::compactVehicles() {
         flow = flow_.state(nV);
         flow.renumber(newOfOld, nLive);
     }
+    // trip statistics: the same vehicles are alive before and after, so the environment's record goes round the load as it is
+    std::vector<cfx_trip_stats_env> trips;
+    if (trip_.on()) trips = trip_.state();
     // custom speeds of vehicles that are STILL waiting (cfx_state carries those of running vehicles only)
     std::map<int32_t, double> stillWaiting;
     for (const auto &kv : waitingCustom_)
@@ -505,6 +508,7 @@ void EngineHost::compactVehicles() {
             stillWaiting[newOfOld[(size_t) kv.first]] = kv.second;
     load(a);
     if (flow_.on()) flow_.setState(flow);
+    if (trip_.on()) trip_.setState(trips);
     for (const auto &kv : stillWaiting) check(be_.cfx_set_vehicle_speed(dev_, kv.first, kv.second), "cfx_set_vehicle_speed");
     waitingCustom_.swap(stillWaiting);
     vehicleCompactions_ += 1;
@@ -578,6 +582,9 @@ void EngineHost::load(const Archive &a) {
     }
     step_ = (size_t) d.step;
     flow_.baseline((int64_t) step_);
+    trip_.forget();
+    tripNoteVehicles();
+    trip_.baseline((int64_t) step_);
     waitingCustom_.clear();  // (compactVehicles puts back what it carries over)
     vehicleEpoch_ += 1;  // vehicle numbers of the archive replace the current ones
     // An archive taken earlier holds fewer vehicle numbers than the state it replaces: the next compaction is due that many

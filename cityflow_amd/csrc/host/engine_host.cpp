@@ -102,6 +102,11 @@ void Backend::open(const std::string &libPath) {
     CFX_FN_OPTIONAL(cfx_get_lane_flow)
     CFX_FN_OPTIONAL(cfx_lane_flow_get_state)
     CFX_FN_OPTIONAL(cfx_lane_flow_set_state)
+    CFX_FN_OPTIONAL(cfx_trip_stats_enable)
+    CFX_FN_OPTIONAL(cfx_observe_trip_stats_device)
+    CFX_FN_OPTIONAL(cfx_get_trip_stats)
+    CFX_FN_OPTIONAL(cfx_trip_stats_get_state)
+    CFX_FN_OPTIONAL(cfx_trip_stats_set_state)
 #undef CFX_FN_OPTIONAL
     if (cfx_abi_version() != CFX_ABI_VERSION)
         throw std::runtime_error("cityflow_amd: ABI version mismatch in '" + libPath + "'");
@@ -249,6 +254,7 @@ EngineHost::EngineHost(const std::string &configFile, int threadNum, const std::
     });
     uploadNewTablesIfAny();
     flow_.bind(&be_, dev_, (int) net_->lanes.size());
+    trip_.bind(&be_, dev_, 1, interval_);
 }
 
 EngineHost::~EngineHost() {
@@ -388,6 +394,8 @@ void EngineHost::nextStep() {
     } note{this, lap, step_};
     step_ += 1;
     flow_.afterStep((int64_t) step_);  // (the host tracker's tick; a backend that keeps the tracker has ticked inside cfx_step)
+    tripNoteVehicles();
+    trip_.afterStep((int64_t) step_);  // (likewise)
     // The finished vehicles are forgotten once enough have been created since the last time (archive.cpp compactVehicles): the
     // reference frees a vehicle when it finishes; here host and device remember every vehicle number until then.
     // What it costs is proportional to the vehicles ALIVE (a snapshot and a load: ~0.15-0.3 us per vehicle), so the automatic
@@ -788,6 +796,28 @@ void EngineHost::observeLaneFlowDevice(uintptr_t entered, uintptr_t left, uintpt
     flow_.observeDevice(o, reset, consumerStream);
 }
 
+void EngineHost::trackTrips(bool on) {
+    if (on && laneChange_) throw std::logic_error("track_trips: not with laneChange (a shadow is a vehicle number with its parent's enter time)");
+    if (on == trip_.on()) return;
+    trip_.enable(on);
+    tripNoteVehicles();
+    trip_.baseline((int64_t) step_);
+}
+
+void EngineHost::tripNoteVehicles() {
+    if (!trip_.on() || trip_.onDevice()) return;
+    const size_t n = spawner_.committedVehicleCount();
+    for (size_t v = (size_t) trip_.noted(); v < n; ++v) trip_.note((int32_t) v, spawner_.vehicles[v].enterTime, 0);
+}
+
+// (like the count getters, these leave the step prepared ahead in place)
+void EngineHost::tripFeatures(const cfx_trip_stats_out &out) {
+    trip_.features(out);
+    raiseDeviceError();
+}
+
+void EngineHost::observeTripsDevice(const cfx_trip_stats_out &out, uintptr_t consumerStream) { trip_.observeDevice(out, consumerStream); }
+
 const InterLayout &EngineHost::intersectionLayout() {
     if (!interLayout_) interLayout_.reset(new InterLayout(intersectionLayoutOf(*net_)));
     return *interLayout_;
@@ -872,6 +902,8 @@ void EngineHost::reset(bool resetRnd) {
     step_ = 0;
     vehicleEpoch_ += 1;
     flow_.baseline(0);
+    trip_.forget();
+    trip_.baseline(0);
 }
 
 // ---------------------------------------------------------------- getters

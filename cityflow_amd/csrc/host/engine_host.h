@@ -16,6 +16,7 @@
 #include "cityflow_amd.h"
 #include "flow.h"
 #include "lane_flow.h"
+#include "trip_stats.h"
 #include "replay.h"
 #include "roadnet.h"
 
@@ -98,6 +99,12 @@ struct Backend {
     cfx_get_lane_flow_fn cfx_get_lane_flow = nullptr;
     cfx_lane_flow_get_state_fn cfx_lane_flow_get_state = nullptr;
     cfx_lane_flow_set_state_fn cfx_lane_flow_set_state = nullptr;
+    // optional as a set: per-environment trip statistics kept by the backend (without them the host keeps them: trip_stats.h)
+    cfx_trip_stats_enable_fn cfx_trip_stats_enable = nullptr;
+    cfx_observe_trip_stats_device_fn cfx_observe_trip_stats_device = nullptr;
+    cfx_get_trip_stats_fn cfx_get_trip_stats = nullptr;
+    cfx_trip_stats_get_state_fn cfx_trip_stats_get_state = nullptr;
+    cfx_trip_stats_set_state_fn cfx_trip_stats_set_state = nullptr;
     void open(const std::string &libPath);  // throws std::runtime_error
     ~Backend();
 };
@@ -239,6 +246,12 @@ public:
     void laneFlowFeatures(const LaneFlowOut &out, bool reset);  // any pointer may be null
     void observeLaneFlowDevice(uintptr_t entered, uintptr_t left, uintptr_t leftSteps, uintptr_t leftWaitingSteps,
                                uintptr_t waitingSteps, uintptr_t maxWaitingSteps, bool reset, uintptr_t consumerStream);
+    // ---- trip statistics and the average travel time across steps (trip_stats.h; the torch layer is cityflow_amd/torch_io.py).
+    //      Off by default; a baseline when it is turned on and after reset / load; vehicle compaction carries it along
+    void trackTrips(bool on);
+    bool tripTracking() const { return trip_.on(); }
+    void tripFeatures(const cfx_trip_stats_out &out);  // any pointer may be null; one element each
+    void observeTripsDevice(const cfx_trip_stats_out &out, uintptr_t consumerStream);
     // Lane::history as the device keeps it ("cfx": {"laneHistory": true}; cfx_get_lane_history): lane-major, oldest record first
     void laneHistory(std::vector<int32_t> &len, std::vector<int32_t> &vehicleNum, std::vector<double> &averageSpeed,
                      std::vector<int32_t> &historyVehicleNum, std::vector<double> &historyAverageSpeed);
@@ -346,6 +359,8 @@ private:
     uint64_t vehicleEpoch_ = 0;
     std::unique_ptr<InterLayout> interLayout_;  // built by the first call that needs it
     LaneFlow flow_;
+    TripStats trip_;
+    void tripNoteVehicles();  // (host tracker: the vehicle numbers created since the last call)
 };
 
 struct EngineConfig {  // Engine::loadConfig engine.cpp:37-84

@@ -362,6 +362,43 @@ void observeLanesDevice(E &e, uintptr_t counts, uintptr_t waiting, uintptr_t spe
     e.observeLanesDevice(a, consumerStream);
 }
 
+// ---- trip statistics across steps (Engine and VectorEngine; the public calls are cityflow_amd/torch_io.py)
+inline py::ssize_t tripEnvs(EngineHost &) { return 1; }
+inline py::ssize_t tripEnvs(cfa::VectorEngineHost &e) { return (py::ssize_t) e.numEnvs(); }
+template <typename E> py::tuple tripTuple(E &e) {
+    const py::ssize_t n = tripEnvs(e);
+    py::array_t<int32_t> entered(n), admitted(n), finished(n), inSystem(n), buffered(n);
+    py::array_t<int64_t> bufferSteps(n), travelSteps(n), inSteps(n);
+    py::array_t<double> average(n);
+    cfx_trip_stats_out o{};
+    o.entered = entered.mutable_data();
+    o.admitted = admitted.mutable_data();
+    o.admitted_buffer_steps = bufferSteps.mutable_data();
+    o.finished = finished.mutable_data();
+    o.finished_travel_steps = travelSteps.mutable_data();
+    o.in_system = inSystem.mutable_data();
+    o.buffered = buffered.mutable_data();
+    o.in_system_travel_steps = inSteps.mutable_data();
+    o.average_travel_time = average.mutable_data();
+    e.tripFeatures(o);
+    return py::make_tuple(entered, admitted, bufferSteps, finished, travelSteps, inSystem, buffered, inSteps, average);
+}
+template <typename E>
+void observeTripsDevice(E &e, uintptr_t entered, uintptr_t admitted, uintptr_t bufferSteps, uintptr_t finished, uintptr_t travelSteps,
+                        uintptr_t inSystem, uintptr_t buffered, uintptr_t inSteps, uintptr_t average, uintptr_t consumerStream) {
+    cfx_trip_stats_out o{};
+    o.entered = (int32_t *) entered;
+    o.admitted = (int32_t *) admitted;
+    o.admitted_buffer_steps = (int64_t *) bufferSteps;
+    o.finished = (int32_t *) finished;
+    o.finished_travel_steps = (int64_t *) travelSteps;
+    o.in_system = (int32_t *) inSystem;
+    o.buffered = (int32_t *) buffered;
+    o.in_system_travel_steps = (int64_t *) inSteps;
+    o.average_travel_time = (double *) average;
+    e.observeTripsDevice(o, consumerStream);
+}
+
 // Device buffers: raw pointers and streams under the tensor methods of cityflow_amd/torch_io.py (Engine and VectorEngine alike)
 template <typename E> void defDeviceBuffers(py::class_<E> &c) {
     c.def("_device_buffers", &E::deviceBuffers, "the backend takes observations / signals in device memory")
@@ -395,7 +432,24 @@ template <typename E> void defDeviceBuffers(py::class_<E> &c) {
         .def("_lane_flow_features", [](E &e, bool reset) { return laneFlowTuple(e, reset); }, "reset"_a,
              "(entered, left, left_steps, left_waiting_steps, waiting_steps, max_waiting_steps), flat (env-major)")
         .def("_observe_lane_flow_device", &E::observeLaneFlowDevice, "entered_ptr"_a, "left_ptr"_a, "left_steps_ptr"_a,
-             "left_waiting_steps_ptr"_a, "waiting_steps_ptr"_a, "max_waiting_steps_ptr"_a, "reset"_a, "consumer_stream"_a);
+             "left_waiting_steps_ptr"_a, "waiting_steps_ptr"_a, "max_waiting_steps_ptr"_a, "reset"_a, "consumer_stream"_a)
+        .def("_track_trips",
+             [](E &e, bool on) {
+                 try {
+                     e.trackTrips(on);
+                 } catch (const std::logic_error &x) {  // (lane change: out of scope, not a failure of the call)
+                     PyErr_SetString(PyExc_NotImplementedError, x.what());
+                     throw py::error_already_set();
+                 }
+             },
+             "on"_a)
+        .def("_trip_tracking", &E::tripTracking)
+        .def("_trip_features", [](E &e) { return tripTuple(e); },
+             "(entered, admitted, admitted_buffer_steps, finished, finished_travel_steps, in_system, buffered, "
+             "in_system_travel_steps, average_travel_time), one element per environment")
+        .def("_observe_trips_device", &observeTripsDevice<E>, "entered_ptr"_a, "admitted_ptr"_a, "admitted_buffer_steps_ptr"_a,
+             "finished_ptr"_a, "finished_travel_steps_ptr"_a, "in_system_ptr"_a, "buffered_ptr"_a, "in_system_travel_steps_ptr"_a,
+             "average_travel_time_ptr"_a, "consumer_stream"_a);
 }
 
 // Engine.set_tl_phase(intersection_id, phase_id) (reference src/cityflow.cpp:35, engine.cpp:719-725) as a vectorcall method of its

@@ -1,0 +1,154 @@
+// Trip-statistics tracker: dispatcher over the backend's entry points and the host tracker (trip_stats.h).
+#include "trip_stats.h"
+
+#include <algorithm>
+#include <cmath>
+#include <stdexcept>
+#include <string>
+
+#include "engine_host.h"
+
+namespace cfa {
+
+bool TripStats::onDevice() const {
+    return be_->cfx_trip_stats_enable && be_->cfx_observe_trip_stats_device && be_->cfx_get_trip_stats && be_->cfx_trip_stats_get_state &&
+           be_->cfx_trip_stats_set_state;
+}
+
+void TripStats::fail(const char *what) const {
+    const char *msg = be_->cfx_last_error(dev_);
+    throw std::runtime_error(std::string("cityflow_amd: ") + what + " failed: " + (msg ? msg : ""));
+}
+
+void TripStats::requireOn(const char *what) const {
+    if (!on_) throw std::runtime_error(std::string(what) + ": trip tracking is off (track_trips(True) turns it on)");
+}
+
+void TripStats::enable(bool on) {
+    if (on == on_) return;
+    if (onDevice()) {
+        if (be_->cfx_trip_stats_enable(dev_, on ? 1 : 0) != CFX_OK) fail("cfx_trip_stats_enable");
+        on_ = on;
+        return;
+    }
+    on_ = on;
+    std::vector<cfx_trip_stats_env>().swap(rec_);
+    std::vector<uint8_t>().swap(seen_);
+    std::vector<uint8_t>().swap(status_);
+    forget();
+    if (on) rec_.assign((size_t) nEnvs_, cfx_trip_stats_env{});
+}
+
+void TripStats::note(int32_t vid, double enterTime, int env) {
+    if (!on_ || onDevice() || vid < 0) return;
+    if ((size_t) vid >= enter_.size()) {
+        enter_.resize((size_t) vid + 1, 0);
+        env_.resize((size_t) vid + 1, 0);
+    }
+    enter_[(size_t) vid] = (int32_t) std::llrint(enterTime / interval_);
+    env_[(size_t) vid] = std::min(std::max(env, 0), nEnvs_ - 1);
+}
+
+void TripStats::forget() {
+    std::vector<int32_t>().swap(enter_);
+    std::vector<int32_t>().swap(env_);
+}
+
+void TripStats::afterStep(int64_t step) {
+    if (on_ && !onDevice()) walk(step, false);
+}
+
+void TripStats::baseline(int64_t step) {
+    if (on_ && !onDevice()) walk(step, true);
+}
+
+// one tick (or baseline) of the host tracker: the rules of include/cityflow_amd.h over the status of every vehicle number noted
+void TripStats::walk(int64_t step, bool baseline) {
+    const size_t n = enter_.size();
+    status_.resize(n);
+    if (n && be_->cfx_get_vehicle_status(dev_, 0, (int32_t) n, status_.data()) != CFX_OK) fail("cfx_get_vehicle_status");
+    step_ = step;
+    if (baseline) {
+        rec_.assign((size_t) nEnvs_, cfx_trip_stats_env{});
+        seen_.assign(n, 0xFF);
+    } else {
+        seen_.resize(n, 0xFF);
+    }
+    for (size_t v = 0; v < n; ++v) {
+        const uint8_t prev = seen_[v], cur = status_[v];
+        if (prev == cur) continue;
+        seen_[v] = cur;
+        cfx_trip_stats_env &a = rec_[(size_t) env_[v]];
+        const int64_t e = enter_[v];
+        if (baseline) {
+            if (cur != 2) {
+                a.base_in_system += 1;
+                a.enter_sum_created += e;
+                if (cur == 0) a.base_buffered += 1;
+            }
+            continue;
+        }
+        if (prev == 0xFF) {
+            a.entered += 1;
+            a.enter_sum_created += e;
+        }
+        if (cur == 1 && prev != 1) {
+            a.admitted += 1;
+            a.admitted_buffer_steps += (step - 1) - e;
+        }
+        if (cur == 2 && prev != 2) {
+            a.finished += 1;
+            a.finished_travel_steps += (step - 1) - e;
+            a.enter_sum_finished += e;
+        }
+    }
+}
+
+void TripStats::features(const cfx_trip_stats_out &o) {
+    requireOn("observe_trips");
+    if (onDevice()) {
+        if (be_->cfx_get_trip_stats(dev_, &o) != CFX_OK) fail("cfx_get_trip_stats");
+        return;
+    }
+    for (size_t r = 0; r < rec_.size(); ++r) {  // (the present values follow from the record: k_trip_drain of the HIP library)
+        const cfx_trip_stats_env &a = rec_[r];
+        const int32_t inSystem = a.base_in_system + a.entered - a.finished;
+        const int64_t inSteps = (int64_t) inSystem * step_ - (a.enter_sum_created - a.enter_sum_finished);
+        const int64_t n = (int64_t) a.finished + inSystem;
+        if (o.entered) o.entered[r] = a.entered;
+        if (o.admitted) o.admitted[r] = a.admitted;
+        if (o.admitted_buffer_steps) o.admitted_buffer_steps[r] = a.admitted_buffer_steps;
+        if (o.finished) o.finished[r] = a.finished;
+        if (o.finished_travel_steps) o.finished_travel_steps[r] = a.finished_travel_steps;
+        if (o.in_system) o.in_system[r] = inSystem;
+        if (o.buffered) o.buffered[r] = a.base_buffered + a.entered - a.admitted;
+        if (o.in_system_travel_steps) o.in_system_travel_steps[r] = inSteps;
+        if (o.average_travel_time)
+            o.average_travel_time[r] = n == 0 ? 0.0 : (double) (a.finished_travel_steps + inSteps) * interval_ / (double) n;
+    }
+}
+
+void TripStats::observeDevice(const cfx_trip_stats_out &o, uintptr_t consumerStream) {
+    requireOn("observe_trips_tensor");
+    if (!onDevice()) throw std::runtime_error("cityflow_amd: '" + be_->path + "' has no device-side trip statistics");
+    if (be_->cfx_observe_trip_stats_device(dev_, &o, (void *) consumerStream) != CFX_OK) fail("cfx_observe_trip_stats_device");
+}
+
+std::vector<cfx_trip_stats_env> TripStats::state() {
+    requireOn("trip statistics");
+    if (!onDevice()) return rec_;
+    std::vector<cfx_trip_stats_env> s((size_t) nEnvs_);
+    if (be_->cfx_trip_stats_get_state(dev_, s.data(), nEnvs_) != CFX_OK) fail("cfx_trip_stats_get_state");
+    return s;
+}
+
+void TripStats::setState(const std::vector<cfx_trip_stats_env> &s) {
+    requireOn("trip statistics");
+    if (!onDevice()) {
+        rec_ = s;
+        return;
+    }
+    if (be_->cfx_trip_stats_set_state(dev_, s.data(), (int32_t) s.size()) != CFX_OK) fail("cfx_trip_stats_set_state");
+}
+
+}  // namespace cfa

@@ -180,6 +180,7 @@ VectorEngineHost::VectorEngineHost(const std::string &configFile, int numEnvs, i
               "cfx_add_routes");
     }
     flow_.bind(&be_, dev_, R_ * L_);
+    trip_.bind(&be_, dev_, R_, interval_);
 }
 
 VectorEngineHost::~VectorEngineHost() {
@@ -525,6 +526,11 @@ void VectorEngineHost::nextStep() {
         std::lock_guard<std::mutex> guard(queryMutex_);
         flow_.afterStep((int64_t) step_);
     }
+    if (trip_.on() && !trip_.onDevice()) {  // (the batch just handed over names the new vehicles; the ahead thread works on the next one)
+        for (const cfx_spawn &s : recs_) trip_.note(s.vid, s.enter_time, L_ > 0 ? s.lane / L_ : 0);
+        std::lock_guard<std::mutex> guard(queryMutex_);
+        trip_.afterStep((int64_t) step_);
+    }
 }
 
 void VectorEngineHost::reset(bool resetRnd) {
@@ -545,6 +551,8 @@ void VectorEngineHost::reset(bool resetRnd) {
     {
         std::lock_guard<std::mutex> guard(queryMutex_);
         flow_.baseline(0);
+        trip_.forget();
+        trip_.baseline(0);
     }
     submitted_.store(0, std::memory_order_release);
     hostSpawnSec_ = hostTranslateSec_ = hostSubmitSec_ = 0;
@@ -652,6 +660,33 @@ void VectorEngineHost::trackLaneFlow(bool on) {
     if (on && laneChange_) throw std::logic_error("track_lane_flow: not with laneChange (a shadow changes identity when its change finishes)");
     std::lock_guard<std::mutex> guard(queryMutex_);
     flow_.enable(on, (int64_t) step_);
+}
+
+void VectorEngineHost::trackTrips(bool on) {
+    if (on && laneChange_) throw std::logic_error("track_trips: not with laneChange (a shadow is a vehicle number with its parent's enter time)");
+    if (on == trip_.on()) return;
+    waitAhead();  // (the host tracker reads the numbering below; the batch being prepared appends to it)
+    std::lock_guard<std::mutex> guard(queryMutex_);
+    trip_.enable(on);
+    if (!on || trip_.onDevice()) return;
+    cfx_scalars sc{};
+    check(be_.cfx_get_scalars(dev_, &sc), "cfx_get_scalars");
+    for (int64_t v = 0; v < sc.spawned_vehicle_count && (size_t) v < globalToLocal_.size(); ++v) {
+        const auto gl = globalToLocal_[(size_t) v];
+        trip_.note((int32_t) v, spawners_[(size_t) gl.first]->vehicles[(size_t) gl.second].enterTime, gl.first);
+    }
+    trip_.baseline((int64_t) step_);
+}
+
+void VectorEngineHost::tripFeatures(const cfx_trip_stats_out &out) {
+    std::lock_guard<std::mutex> guard(queryMutex_);  // (the ABI is not re-entrant: the ahead thread may be asking the device)
+    trip_.features(out);
+    raiseDeviceError();
+}
+
+void VectorEngineHost::observeTripsDevice(const cfx_trip_stats_out &out, uintptr_t consumerStream) {
+    std::lock_guard<std::mutex> guard(queryMutex_);
+    trip_.observeDevice(out, consumerStream);
 }
 
 void VectorEngineHost::laneFlowFeatures(const LaneFlowOut &out, bool reset) {

@@ -63,6 +63,11 @@ public:
     void laneFlowFeatures(const LaneFlowOut &out, bool reset);
     void observeLaneFlowDevice(uintptr_t entered, uintptr_t left, uintptr_t leftSteps, uintptr_t leftWaitingSteps,
                                uintptr_t waitingSteps, uintptr_t maxWaitingSteps, bool reset, uintptr_t consumerStream);
+    // trip statistics and the average travel time per environment (EngineHost::trackTrips and its kin): outputs [R]
+    void trackTrips(bool on);
+    bool tripTracking() const { return trip_.on(); }
+    void tripFeatures(const cfx_trip_stats_out &out);
+    void observeTripsDevice(const cfx_trip_stats_out &out, uintptr_t consumerStream);
     std::vector<std::string> laneIds() const;
     std::vector<std::string> intersectionIds() const;
     cfx_scalars scalars();
@@ -83,6 +88,7 @@ private:
     void check(int32_t rc, const char *what);
     std::unique_ptr<InterLayout> interLayout_;  // built by the first call that needs it
     LaneFlow flow_;                      // (every call with queryMutex_ held: it asks the device)
+    TripStats trip_;                     // (likewise)
     bool devicePhaseUnchecked_ = false;  // as EngineHost: read by every call below that has waited for the device
     void raiseDeviceError();             // (the caller holds queryMutex_)
 

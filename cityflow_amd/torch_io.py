@@ -23,6 +23,12 @@
                                  max_waiting_steps=None, reset=False)
                                                          drains them into the given tensors, one kernel launch (see its docstring)
     eng.observe_lane_flow_array(reset=False)             the same six outputs as numpy arrays (waits for the device)
+    eng.track_trips(on=True) / eng.trip_tracking()       trip statistics per environment ACROSS steps (off by default)
+    eng.observe_trips_tensor(entered=None, admitted=None, admitted_buffer_steps=None, finished=None,
+                             finished_travel_steps=None, in_system=None, buffered=None, in_system_travel_steps=None,
+                             average_travel_time=None)   0-dim (VectorEngine: [R]) each, one kernel launch (see its docstring)
+    eng.observe_trips_array()                            the same nine outputs as numpy arrays (waits for the device)
+    eng.get_average_travel_time_tensor(out=None)         float64 0-dim (VectorEngine: [R]): get_average_travel_time() on the device
 
 On the HIP engine the tensors live on the engine's GPU and nothing here waits for the device:
   * a getter's kernel writes the caller's tensor on the engine's stream after everything already enqueued there and on the
@@ -456,6 +462,95 @@ def observe_lane_flow_array(self, reset=False):
     return {name: a.reshape(shape) for name, a in zip(LANE_FLOW_OUTPUTS, self._lane_flow_features(bool(reset)))}
 
 
+TRIP_OUTPUTS = ("entered", "admitted", "admitted_buffer_steps", "finished", "finished_travel_steps", "in_system", "buffered",
+                "in_system_travel_steps", "average_travel_time")
+_TRIP_INT64 = ("admitted_buffer_steps", "finished_travel_steps", "in_system_travel_steps")
+
+
+def _trip_dtype(torch, name):
+    return torch.float64 if name == "average_travel_time" else torch.int64 if name in _TRIP_INT64 else torch.int32
+
+
+def track_trips(self, on=True):
+    """Turn the trip tracker on or off (off by default: nothing is allocated or launched, and it frees its memory when turned
+    off).  While it is on, every next_step() ends with one tracker update (one extra kernel launch on the HIP engine).
+    Turning it on takes a baseline: the five accumulators are zero, and the vehicles alive then are in in_system / buffered /
+    in_system_travel_steps with their true enter times without being counted as entered (they count as admitted or finished
+    when that happens); reset(), load() and load_from_file() take a new baseline and keep it on.  Not with laneChange
+    (NotImplementedError)."""
+    self._track_trips(bool(on))
+
+
+def trip_tracking(self):
+    """Whether track_trips is on."""
+    return self._trip_tracking()
+
+
+def observe_trips_tensor(self, entered=None, admitted=None, admitted_buffer_steps=None, finished=None, finished_travel_steps=None,
+                         in_system=None, buffered=None, in_system_travel_steps=None, average_travel_time=None):
+    """Fill every given tensor with one kernel launch on the engine's stream, ordered against the current torch stream as
+    observe_lanes_tensor (no host wait).  Every output is 0-dim on an Engine and [R], one element per environment, on a
+    VectorEngine.  s = steps taken, e(v) = the step at which vehicle v was created (enter time / interval).  After every step:
+
+        entered                 int32  vehicles seen for the first time (created, whether or not a lane has admitted them)
+        admitted                int32  vehicles that left their first lane's entry buffer and started to run
+        admitted_buffer_steps   int64  sum over those of the steps they sat in the buffer, (s - 1) - e(v)
+        finished                int32  vehicles that reached the end of their route
+        finished_travel_steps   int64  sum over those of (s - 1) - e(v): cumulative travel time / interval
+      all five accumulated since the baseline (track_trips; reset(), load(), load_from_file()) and never reset in between — a
+      window is the difference of two reads — and, as of the last step,
+        in_system               int32  vehicles created and not finished (in an entry buffer or running)
+        buffered                int32  those of them still in an entry buffer: on no lane, invisible to the lane observations
+        in_system_travel_steps  int64  sum over the vehicles in the system of s - e(v)
+        average_travel_time     float64  (finished_travel_steps + in_system_travel_steps) * interval / (finished + in_system),
+                                         0.0 without vehicles
+
+    average_travel_time equals get_average_travel_time() (per environment) only while tracking has been on since the engine
+    was created or last reset(), and only while no push_vehicle() has happened since the last step: the reference counts a
+    pushed vehicle at once, the tracker sees it with the next step.  Seconds = steps * interval.  Every element is written.
+    At least one output; every argument is checked before anything is enqueued; RuntimeError while tracking is off."""
+    torch = _torch()
+    given = dict(zip(TRIP_OUTPUTS, (entered, admitted, admitted_buffer_steps, finished, finished_travel_steps, in_system, buffered,
+                                    in_system_travel_steps, average_travel_time)))
+    if all(t is None for t in given.values()):
+        raise ValueError("observe_trips_tensor: give at least one of " + ", ".join(TRIP_OUTPUTS))
+    shape = tuple(self._tensor_shapes()[0])[:-1]
+    device = _engine_device(torch, self)
+    for name, t in given.items():
+        if t is not None:
+            _check_buf(torch, t, name, shape, _trip_dtype(torch, name), device)
+    if not self._trip_tracking():
+        raise RuntimeError("observe_trips_tensor: trip tracking is off (track_trips(True) turns it on)")
+    if not self._device_buffers():  # (the twin: over the array call)
+        arrays = observe_trips_array(self)
+        for name, t in given.items():
+            if t is not None:
+                t.copy_(torch.from_numpy(arrays[name]))
+        return
+    self._observe_trips_device(*[0 if given[name] is None else given[name].data_ptr() for name in TRIP_OUTPUTS],
+                               torch.cuda.current_stream(device).cuda_stream)
+
+
+def observe_trips_array(self):
+    """The nine outputs of observe_trips_tensor as a dict of numpy arrays (same names, dtypes and shapes); waits for the
+    device.  RuntimeError while tracking is off."""
+    if not self._trip_tracking():
+        raise RuntimeError("observe_trips_array: trip tracking is off (track_trips(True) turns it on)")
+    shape = tuple(self._tensor_shapes()[0])[:-1]
+    return {name: a.reshape(shape) for name, a in zip(TRIP_OUTPUTS, self._trip_features())}
+
+
+def get_average_travel_time_tensor(self, out=None):
+    """The average_travel_time output of observe_trips_tensor alone: float64, 0-dim ([R] on a VectorEngine), into `out` or a
+    new tensor; no host wait on the HIP engine.  It equals get_average_travel_time() only while tracking has been on since the
+    engine's creation or last reset() and no push_vehicle() has happened since the last step (observe_trips_tensor)."""
+    torch = _torch()
+    if out is None:
+        out = torch.empty(tuple(self._tensor_shapes()[0])[:-1], dtype=torch.float64, device=_engine_device(torch, self))
+    observe_trips_tensor(self, average_travel_time=out)
+    return out
+
+
 def install(*classes):
     for cls in classes:
         cls.get_lane_vehicle_count_tensor = get_lane_vehicle_count_tensor
@@ -474,3 +569,8 @@ def install(*classes):
         cls.lane_flow_tracking = lane_flow_tracking
         cls.observe_lane_flow_tensor = observe_lane_flow_tensor
         cls.observe_lane_flow_array = observe_lane_flow_array
+        cls.track_trips = track_trips
+        cls.trip_tracking = trip_tracking
+        cls.observe_trips_tensor = observe_trips_tensor
+        cls.observe_trips_array = observe_trips_array
+        cls.get_average_travel_time_tensor = get_average_travel_time_tensor

@@ -647,6 +647,56 @@ typedef int32_t (*cfx_lane_flow_get_state_fn)(cfx_engine *e, int32_t *records, i
 typedef int32_t (*cfx_lane_flow_set_state_fn)(cfx_engine *e, const int32_t *records, int32_t n_vehicles,
                                               const cfx_lane_flow_lane *lanes, int32_t tick);
 
+/* ---- Per-environment trip statistics and the average travel time accumulated across steps (OPTIONAL entry points, as above;
+ * not with lane change, not on a tile: CFX_ERR_STATE).  Off by default: nothing is allocated or launched.  s = the step counter;
+ * e(v) = llrint(enter_time(v) / interval) = the step at which vehicle v was created; r(v) = its environment (cfx_config::n_envs:
+ * the first road of its route / (n_roads / n_envs); one environment otherwise).  While it is on, every cfx_step ends with one
+ * TICK on the state the step left (s counts that step), over the status of every vehicle number (cfx_get_vehicle_status):
+ *   v seen for the first time:                             entered[r] += 1
+ *   v running now and not at the previous tick:            admitted[r] += 1, admitted_buffer_steps[r] += (s - 1) - e(v)
+ *                                                          (the steps it sat in its lane's entry buffer)
+ *   v finished now and not at the previous tick:           finished[r] += 1, finished_travel_steps[r] += (s - 1) - e(v)
+ *                                                          (what cumulative_travel_time got for it, divided by interval)
+ * and as of the last tick  in_system[r] = vehicles created and not finished,  buffered[r] = those of them still waiting,
+ * in_system_travel_steps[r] = sum of s - e(v) over them,  average_travel_time[r] = (double) (finished_travel_steps +
+ * in_system_travel_steps) * interval / (double) (finished + in_system), 0.0 without vehicles — Engine::getAverageTravelTime
+ * per environment, while tracking has been on since cfx_create / cfx_reset.  The accumulators only ever grow: a window is the
+ * difference of two reads.  A BASELINE (enabling, cfx_reset, cfx_load_state) zeroes the five accumulators and takes the
+ * vehicles alive then into in_system / buffered / in_system_travel_steps with their true e(v), without counting them as
+ * entered; they count as admitted or finished when that happens.
+ * Outputs, [max(n_envs, 1)] each: counts int32, step sums int64, average_travel_time double.
+ *   "cfx_trip_stats_enable"         on != 0: allocate (1 byte per vehicle number the tables hold, 56 per environment) and take a
+ *                                   baseline; 0: free.  While it is on the ring layout launches every step's commit with the step.
+ *   "cfx_observe_trip_stats_device" any of the nine NULL (at least one given), all in device memory, written by ONE kernel on
+ *                                   the engine's stream, ordered against consumer_stream as cfx_observe_device.
+ *   "cfx_get_trip_stats"            the same into host memory; synchronous.
+ *   "cfx_trip_stats_get_state" / "cfx_trip_stats_set_state"  the per-environment records as they stand, for a host that renumbers
+ *                                   the vehicles through cfx_load_state (which takes a baseline) without changing which are alive:
+ *                                   set replaces the records after that load; the per-vehicle part is the one the load's
+ *                                   baseline built.  Synchronous. */
+typedef struct cfx_trip_stats_env {
+    int64_t admitted_buffer_steps, finished_travel_steps;
+    int64_t enter_sum_created;   /* sum of e(v) over the vehicles alive at the baseline and those seen since */
+    int64_t enter_sum_finished;  /* ... over those that finished since the baseline */
+    int32_t entered, admitted, finished;
+    int32_t base_in_system, base_buffered;  /* alive / waiting at the baseline */
+    int32_t reserved;
+} cfx_trip_stats_env;
+typedef struct cfx_trip_stats_out {
+    int32_t *entered, *admitted;
+    int64_t *admitted_buffer_steps;
+    int32_t *finished;
+    int64_t *finished_travel_steps;
+    int32_t *in_system, *buffered;
+    int64_t *in_system_travel_steps;
+    double *average_travel_time;
+} cfx_trip_stats_out;
+typedef int32_t (*cfx_trip_stats_enable_fn)(cfx_engine *e, int32_t on);
+typedef int32_t (*cfx_observe_trip_stats_device_fn)(cfx_engine *e, const cfx_trip_stats_out *out, void *consumer_stream);
+typedef int32_t (*cfx_get_trip_stats_fn)(cfx_engine *e, const cfx_trip_stats_out *out);
+typedef int32_t (*cfx_trip_stats_get_state_fn)(cfx_engine *e, cfx_trip_stats_env *envs, int32_t n_envs);
+typedef int32_t (*cfx_trip_stats_set_state_fn)(cfx_engine *e, const cfx_trip_stats_env *envs, int32_t n_envs);
+
 #ifdef __cplusplus
 }
 #endif

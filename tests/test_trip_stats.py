@@ -1,0 +1,562 @@
+"""Per-environment trip statistics and the average travel time across steps: track_trips / observe_trips_tensor /
+observe_trips_array / get_average_travel_time_tensor on Engine and VectorEngine (cityflow_amd/torch_io.py; k_trip_tick /
+k_trip_drain on the device, the host tracker of csrc/host/trip_stats.cpp on the twin).
+
+After every step, with s = steps taken and e(v) = the step at which vehicle v was created:
+  1. v seen for the first time:                    entered += 1
+  2. v running now and not at the previous tick:   admitted += 1, admitted_buffer_steps += (s - 1) - e(v)
+  3. v finished now and not at the previous tick:  finished += 1, finished_travel_steps += (s - 1) - e(v)
+in_system / buffered / in_system_travel_steps describe the vehicles created and not finished as of the last tick, and
+average_travel_time = (finished_travel_steps + in_system_travel_steps) * interval / (finished + in_system).  A baseline
+(tracking turned on, reset, load) zeroes the five accumulators and keeps the vehicles alive with their true e(v).
+
+The oracle is the small model of these rules below, fed only by getters that existed before the feature — get_vehicles(True)
+and get_vehicles() after every step, ids as strings, e(v) = (tick of first sight) - 1 — never by the feature's own arrays.
+Every integer output is compared with array_equal after EVERY step; the interval of every scenario is 1.0, so the sums behind
+the average are integers in a double and the average is compared for equality too."""
+import copy
+import json
+import os
+
+import numpy as np
+import pytest
+
+from conftest import TWIN_LIB, assert_hip_backend
+
+torch = pytest.importorskip("torch")
+
+from test_device_tensors import tensor_device, twin  # noqa: E402
+
+NAMES = ("entered", "admitted", "admitted_buffer_steps", "finished", "finished_travel_steps", "in_system", "buffered",
+         "in_system_travel_steps", "average_travel_time")
+INT_NAMES = NAMES[:8]
+ACCUMULATED = NAMES[:5]
+DTYPES = {k: np.int32 for k in NAMES}
+DTYPES.update({k: np.int64 for k in ("admitted_buffer_steps", "finished_travel_steps", "in_system_travel_steps")})
+DTYPES["average_travel_time"] = np.float64
+TORCH_DTYPES = {np.int32: torch.int32, np.int64: torch.int64, np.float64: torch.float64}
+
+
+# ------------------------------------------------------------------------------------------------------------------ oracle
+class Model:
+    """The rules over the ids get_vehicles(True) (created and not finished) and get_vehicles() (running) list.  It is ticked
+    from the engine's first step on, so that it knows every vehicle's enter step when a baseline is taken later."""
+
+    def __init__(self, interval=1.0):
+        self.interval = interval
+        self.enter = {}       # id -> e(v), every vehicle ever seen
+        self.alive = set()
+        self.running = set()
+        self.enter_sum = 0    # sum of e(v) over `alive`
+        self.s = 0
+        self.acc = dict.fromkeys(ACCUMULATED, 0)
+        self.first_finish = None
+        self.peak_buffered = 0
+
+    def baseline(self):
+        self.acc = dict.fromkeys(ACCUMULATED, 0)
+
+    def tick(self, eng, s):
+        alive, running = set(eng.get_vehicles(True)), set(eng.get_vehicles())
+        assert running <= alive
+        new = alive - self.enter.keys()
+        for v in new:
+            self.enter[v] = s - 1
+            self.enter_sum += s - 1
+        self.acc["entered"] += len(new)
+        admitted = running - self.running
+        self.acc["admitted"] += len(admitted)
+        self.acc["admitted_buffer_steps"] += sum((s - 1) - self.enter[v] for v in admitted)
+        finished = self.alive - alive
+        self.acc["finished"] += len(finished)
+        self.acc["finished_travel_steps"] += sum((s - 1) - self.enter[v] for v in finished)
+        self.enter_sum -= sum(self.enter[v] for v in finished)
+        if finished and self.first_finish is None:
+            self.first_finish = s
+        self.alive, self.running, self.s = alive, running, s
+        self.peak_buffered = max(self.peak_buffered, len(alive) - len(running))
+
+    def outputs(self):
+        o = dict(self.acc)
+        o["in_system"] = len(self.alive)
+        o["buffered"] = len(self.alive) - len(self.running)
+        o["in_system_travel_steps"] = len(self.alive) * self.s - self.enter_sum
+        n = o["finished"] + o["in_system"]
+        o["average_travel_time"] = float(o["finished_travel_steps"] + o["in_system_travel_steps"]) * self.interval / float(n) if n else 0.0
+        return o
+
+
+def stack(rows):
+    """[R] arrays from R models' (or engines') outputs."""
+    return {k: np.array([r[k] for r in rows], dtype=DTYPES[k]) for k in NAMES}
+
+
+def empty_outputs(eng, shape=()):
+    # (filled with a value no output takes: every element must be written)
+    return {k: torch.full(shape, -7, dtype=TORCH_DTYPES[DTYPES[k]], device=tensor_device(eng)) for k in NAMES}
+
+
+def read(eng, where, shape=()):
+    """The array call and the tensor call (all nine, and the average alone); they must agree.  Returns numpy arrays."""
+    got = eng.observe_trips_array()
+    assert sorted(got) == sorted(NAMES)
+    t = empty_outputs(eng, shape)
+    eng.observe_trips_tensor(**t)
+    avg = eng.get_average_travel_time_tensor()
+    assert avg.dtype == torch.float64 and tuple(avg.shape) == shape and avg.device == tensor_device(eng)
+    for k in NAMES:
+        assert got[k].dtype == DTYPES[k] and got[k].shape == shape, "%s: %s is %s %s" % (where, k, got[k].dtype, got[k].shape)
+        assert np.array_equal(t[k].cpu().numpy(), got[k]), "%s: %s differs between the tensor and the array call" % (where, k)
+    assert np.array_equal(avg.cpu().numpy(), got["average_travel_time"]), where
+    return got
+
+
+def check(got, want, where):
+    for k in NAMES:
+        assert np.array_equal(got[k], np.asarray(want[k], dtype=DTYPES[k])), "%s: %s is %s, the model says %s" % (where, k, got[k], want[k])
+
+
+def check_reference_totals(eng, got, where):
+    """What the engine itself has always reported about finished vehicles, and the call the feature replaces (interval 1.0)."""
+    sc = eng._scalars()
+    assert int(got["finished"]) == sc["finished_vehicle_count"], where
+    assert float(got["finished_travel_steps"]) * 1.0 == sc["cumulative_travel_time"], where
+    assert float(got["average_travel_time"]) == eng.get_average_travel_time(), where
+
+
+def run_engine(eng, steps, where, other=None):
+    """Tracking on since creation; every output against the model after every step (and against `other`, a second engine in
+    lockstep, output by output); the engine's own totals every 10th step.  Returns (model, last outputs)."""
+    eng.track_trips(True)
+    assert eng.trip_tracking()
+    if other is not None:
+        other.track_trips(True)
+    model = Model()
+    check(read(eng, where + ", before the first step"), model.outputs(), where + ", before the first step")
+    for s in range(1, steps + 1):
+        eng.next_step()
+        model.tick(eng, s)
+        at = "%s, step %d" % (where, s)
+        got = read(eng, at)
+        check(got, model.outputs(), at)
+        if other is not None:
+            other.next_step()
+            theirs = other.observe_trips_array()
+            for k in NAMES:
+                assert np.array_equal(got[k], theirs[k]), "%s: %s differs from the twin" % (at, k)
+        if s % 10 == 0:
+            check_reference_totals(eng, got, at)
+    return model, got
+
+
+# ------------------------------------------------------------------------------------------------------------- the bodies
+def example_body(make, scen, workdir, layout, with_twin=None):
+    cfg = scen.materialize("example_1x1", workdir, **({"cfx": {"layout": "dense"}} if layout == "dense" else {}))
+    model, got = run_engine(make(cfg), 200, "example_1x1 " + layout, other=with_twin(cfg) if with_twin else None)
+    assert got["finished"] > 0
+    # what the CPU twin showed for this scenario
+    assert model.first_finish == 41
+    assert (int(got["entered"]), int(got["finished"]), int(got["finished_travel_steps"])) == (480, 292, 17915)
+    assert got["admitted_buffer_steps"] == 0 and got["buffered"] == 0  # (nothing ever waits in a buffer here)
+
+
+def grid_body(make, scen, workdir, with_twin=None):
+    cfg = scen.materialize("grid_6x6", workdir, cfx={"layout": "ring", "ringCapacityPercent": 60})
+    eng = make(cfg)
+    model, got = run_engine(eng, 450, "grid_6x6", other=with_twin(cfg) if with_twin else None)
+    assert got["admitted_buffer_steps"] > 0 and got["buffered"] > 0 and got["finished"] > 0
+    assert got["entered"] > 4096  # (the vehicle tables start at 4096 numbers with the start-small knob, and double)
+    assert model.first_finish == 392
+    assert (int(got["entered"]), int(got["finished"])) == (10800, 120)
+    assert model.peak_buffered == 8988
+    if eng._device_buffers():
+        assert eng._host_stats(False)["table_grows_total"] > 0
+
+
+def vector_body(make_vec, make_single, scen, workdir, name, steps, rl, vec_twin=None):
+    R = 3
+    kw = {"rlTrafficLight": True} if rl else {}
+    vec = make_vec(scen.materialize(name, workdir, **kw), R)
+    other = vec_twin(scen.materialize(name, workdir, **kw), R) if vec_twin else None
+    singles = [make_single(scen.materialize(name, workdir, seed=r, **kw)) for r in range(R)]
+    models = [Model() for _ in range(R)]
+    vec.track_trips(True)
+    if other is not None:
+        other.track_trips(True)
+    inter_ids = vec.intersection_ids()
+    differed = False
+    for s in range(1, steps + 1):
+        if rl and (s - 1) % 10 == 0:  # the per-environment phase plan of tests/test_vector_engine.py::_check
+            ph = np.zeros((R, len(inter_ids)), dtype=np.int32)
+            for r in range(R):
+                ph[r, :] = ((s - 1) // 10 + r) % 8
+                for i, iid in enumerate(inter_ids):
+                    try:
+                        singles[r].set_tl_phase(iid, int(ph[r, i]))
+                    except (IndexError, RuntimeError):
+                        pass  # virtual intersections
+            vec.set_tl_phases(ph)
+            if other is not None:
+                other.set_tl_phases(ph)
+        vec.next_step()
+        for r in range(R):
+            singles[r].next_step()
+            models[r].tick(singles[r], s)
+        at = "%s x%d, step %d" % (name, R, s)
+        got = read(vec, at, shape=(R,))
+        check(got, stack([m.outputs() for m in models]), at)
+        if other is not None:
+            other.next_step()
+            theirs = other.observe_trips_array()
+            for k in NAMES:
+                assert np.array_equal(got[k], theirs[k]), "%s: %s differs from the twin" % (at, k)
+        differed = differed or any(len(set(got[k].tolist())) > 1 for k in INT_NAMES)
+        if s % 10 == 0:
+            sc = vec._scalars()
+            assert int(got["finished"].sum()) == sc["finished_vehicle_count"], at
+            assert float(got["finished_travel_steps"].sum()) == sc["cumulative_travel_time"], at
+            for r in range(R):
+                assert got["average_travel_time"][r] == singles[r].get_average_travel_time(), at
+    assert got["finished"].sum() > 0
+    assert differed, "the rows were equal at every step"
+    return models, got
+
+
+def vector_grid_checks(models, got):
+    # what the CPU twin showed for the per-environment phase plan
+    assert [m.first_finish for m in models] == [465, 455, 444]
+    assert got["finished"].tolist() == [96, 96, 96]
+    assert got["finished_travel_steps"].tolist() == [46536, 45576, 44604]
+
+
+def follow(eng, model, first, steps, where):
+    for s in range(first + 1, first + steps + 1):
+        eng.next_step()
+        model.tick(eng, s)
+        got = read(eng, "%s, step %d" % (where, s))
+        check(got, model.outputs(), "%s, step %d" % (where, s))
+    return got
+
+
+def baselines_body(make, scen, workdir, tmp_path):
+    cfg = scen.materialize("example_1x1", workdir)
+    eng = make(cfg)
+    assert not eng.trip_tracking()
+    model = Model()
+    for s in range(1, 61):
+        eng.next_step()
+        model.tick(eng, s)
+    # turned on at step 60: the vehicles alive are in the system with their true enter steps, and are not counted as entered
+    eng.track_trips(True)
+    model.baseline()
+    got = read(eng, "turned on at step 60")
+    check(got, model.outputs(), "turned on at step 60")
+    assert got["entered"] == 0 and got["in_system"] > 0 and got["in_system_travel_steps"] > got["in_system"]
+    got = follow(eng, model, 60, 40, "after turning on at step 60")
+    assert got["finished"] > 0, "no vehicle that was alive at the baseline has finished"
+    # snapshot / load: tracking stays on, the accumulators restart, on the archive's vehicles
+    archive, kept = eng.snapshot(), copy.deepcopy(model)
+    path = str(tmp_path / "trip_archive.json")
+    archive.dump(path)
+    follow(eng, model, 100, 25, "after the snapshot")
+    for how in ("load", "load_from_file"):
+        if how == "load":
+            eng.load(archive)
+        else:
+            eng.load_from_file(path)
+        assert eng.trip_tracking()
+        model = copy.deepcopy(kept)
+        model.baseline()
+        got = read(eng, how)
+        check(got, model.outputs(), how)
+        assert not any(got[k] for k in ACCUMULATED) and got["in_system"] > 0
+        got = follow(eng, model, 100, 25, "after " + how)
+        assert got["finished"] > 0
+    eng.reset()
+    assert eng.trip_tracking()
+    model = Model()
+    got = read(eng, "reset")
+    check(got, model.outputs(), "reset")
+    assert not any(got[k] for k in INT_NAMES) and got["average_travel_time"] == 0.0
+    got = follow(eng, model, 0, 60, "after reset")
+    assert got["entered"] > 0 and got["finished"] > 0
+    check_reference_totals(eng, got, "after reset")  # (tracking on since the reset: the average is the reference's again)
+    # off: the observe calls raise; on again: a new baseline
+    eng.track_trips(False)
+    assert not eng.trip_tracking()
+    with pytest.raises(RuntimeError):
+        eng.observe_trips_array()
+    with pytest.raises(RuntimeError):
+        eng.observe_trips_tensor(entered=torch.zeros((), dtype=torch.int32, device=tensor_device(eng)))
+    with pytest.raises(RuntimeError):
+        eng.get_average_travel_time_tensor()
+    eng.next_step()
+    model.tick(eng, 61)
+    eng.track_trips(True)
+    model.baseline()
+    check(read(eng, "turned on again"), model.outputs(), "turned on again")
+    follow(eng, model, 61, 20, "after turning on again")
+
+
+def compaction_body(make, scen, workdir):
+    a = make(scen.materialize("example_1x1", workdir, cfx={"compactVehicles": 100}))
+    b = make(scen.materialize("example_1x1", workdir, cfx={"compactVehicles": 0}))
+    a.track_trips(True)
+    b.track_trips(True)
+    for s in range(1, 201):
+        a.next_step()
+        b.next_step()
+        ga, gb = read(a, "compacting, step %d" % s), read(b, "never compacting, step %d" % s)
+        for k in NAMES:
+            assert np.array_equal(ga[k], gb[k]), "step %d: %s differs from the engine that never compacts" % (s, k)
+    assert a._vehicle_table()[1] > 0 and b._vehicle_table()[1] == 0, (a._vehicle_table(), b._vehicle_table())
+    assert gb["finished"] > 0
+
+
+def load_into_new_tables_body(make, scen, workdir):
+    """An archive loaded into an engine that has not stepped yet: its vehicle tables are made for the archive's vehicle numbers
+    plus one, which is no multiple of 16 here — the baseline's last sixteen status bytes are cut short by the tables' end."""
+    cfg = scen.materialize("grid_6x6", workdir, cfx={"layout": "ring", "ringCapacityPercent": 60})
+    a, model = make(cfg), Model()
+    for s in range(1, 202):
+        a.next_step()
+        model.tick(a, s)
+    assert a._vehicle_table() == (4824, 0)  # (more than the 4096 numbers the tables start with; 4825 % 16 == 9)
+    archive = a.snapshot()
+    b = make(cfg)
+    b.track_trips(True)
+    b.load(archive)
+    model.baseline()
+    got = read(b, "loaded into a new engine")
+    check(got, model.outputs(), "loaded into a new engine")
+    assert got["in_system"] == 4824 and got["buffered"] > 0 and got["entered"] == 0
+    got = follow(b, model, 201, 30, "after the load into a new engine")
+    assert got["entered"] > 0 and got["admitted"] > 0
+
+
+def push_vehicle_body(make, scen, workdir):
+    cfg = scen.materialize("example_1x1", workdir)
+    eng = make(cfg)
+    eng.track_trips(True)
+    model = Model()
+    follow(eng, model, 0, 50, "before the push")
+    n = len(eng.get_vehicles(True))
+    with open(os.path.join(os.path.dirname(cfg), "roadnet.json")) as f:
+        road = json.load(f)["roads"][0]["id"]
+    eng.push_vehicle({"length": 5.0, "maxSpeed": 11.0}, [road])
+    assert len(eng.get_vehicles(True)) == n + 1
+    # (the model is fed after every step only: it sees the pushed vehicle at the tick after the next step, as the tracker does)
+    entered = int(eng.observe_trips_array()["entered"])
+    got = follow(eng, model, 50, 60, "after the push")
+    assert got["entered"] > entered and got["finished"] > 0
+    check_reference_totals(eng, got, "60 steps after the push")
+
+
+def argument_errors_body(eng, vec):
+    dev = tensor_device(eng)
+    with pytest.raises(RuntimeError):  # tracking is off
+        eng.observe_trips_tensor(entered=torch.zeros((), dtype=torch.int32, device=dev))
+    with pytest.raises(RuntimeError):
+        eng.observe_trips_array()
+    with pytest.raises(RuntimeError):
+        vec.observe_trips_array()
+    eng.track_trips()
+    vec.track_trips(True)
+    for s in range(5):
+        eng.next_step()
+    with pytest.raises(ValueError):  # no output given
+        eng.observe_trips_tensor()
+    with pytest.raises(TypeError):   # wrong dtypes
+        eng.observe_trips_tensor(entered=torch.zeros((), dtype=torch.int64, device=dev))
+    with pytest.raises(TypeError):
+        eng.observe_trips_tensor(finished_travel_steps=torch.zeros((), dtype=torch.int32, device=dev))
+    with pytest.raises(TypeError):
+        eng.observe_trips_tensor(average_travel_time=torch.zeros((), dtype=torch.float32, device=dev))
+    with pytest.raises(TypeError):
+        eng.get_average_travel_time_tensor(out=torch.zeros((), dtype=torch.int64, device=dev))
+    with pytest.raises(TypeError):
+        eng.observe_trips_tensor(finished=np.zeros((), dtype=np.int32))
+    with pytest.raises(TypeError):   # wrong device
+        eng.observe_trips_tensor(finished=torch.zeros((), dtype=torch.int32, device="meta"))
+    if dev.type == "cuda":
+        with pytest.raises(TypeError):  # (the HIP engine never falls back to a CPU tensor)
+            eng.observe_trips_tensor(finished=torch.zeros((), dtype=torch.int32))
+    elif torch.cuda.is_available():
+        with pytest.raises(TypeError):  # (the twin's tensors live on the CPU)
+            eng.observe_trips_tensor(finished=torch.zeros((), dtype=torch.int32, device="cuda"))
+    with pytest.raises(ValueError):  # wrong shapes
+        eng.observe_trips_tensor(in_system=torch.zeros(1, dtype=torch.int32, device=dev))
+    with pytest.raises(ValueError):
+        vec.observe_trips_tensor(in_system=torch.zeros((), dtype=torch.int32, device=dev))
+    with pytest.raises(ValueError):
+        vec.observe_trips_tensor(in_system=torch.zeros(3, dtype=torch.int32, device=dev))
+    with pytest.raises(ValueError):  # not contiguous
+        vec.observe_trips_tensor(entered=torch.zeros(4, dtype=torch.int32, device=dev)[::2])
+    # nothing is written when a later argument is wrong
+    good = torch.full((), -7, dtype=torch.int32, device=dev)
+    with pytest.raises(ValueError):
+        eng.observe_trips_tensor(entered=good, buffered=torch.zeros(2, dtype=torch.int32, device=dev))
+    assert int(good) == -7
+    eng.observe_trips_tensor(entered=good)
+    assert int(good) == int(eng.observe_trips_array()["entered"]) > 0
+    out = torch.full((2,), -7.0, dtype=torch.float64, device=dev)
+    assert vec.get_average_travel_time_tensor(out=out) is out and bool((out == 0.0).all())
+
+
+# ---------------------------------------------------------------------------------------------------------------- CPU (twin)
+def vec_twin(mod):
+    return lambda cfg, n: mod.VectorEngine._with_backend(cfg, n, 1, TWIN_LIB)
+
+
+@pytest.mark.parametrize("layout", ["auto", "dense"])
+def test_example_equals_the_model(mod, scen, workdir, layout):
+    example_body(lambda cfg: twin(mod, cfg), scen, workdir, layout)
+
+
+def test_grid_equals_the_model(mod, scen, workdir):
+    grid_body(lambda cfg: twin(mod, cfg), scen, workdir)
+
+
+def test_vector_engine_example(mod, scen, workdir):
+    vector_body(vec_twin(mod), lambda cfg: twin(mod, cfg), scen, workdir, "example_1x1", 200, rl=False)
+
+
+def test_vector_engine_grid_with_a_phase_plan(mod, scen, workdir):
+    vector_grid_checks(*vector_body(vec_twin(mod), lambda cfg: twin(mod, cfg), scen, workdir, "grid_6x6", 520, rl=True))
+
+
+def test_baselines(mod, scen, workdir, tmp_path):
+    baselines_body(lambda cfg: twin(mod, cfg), scen, workdir, tmp_path)
+
+
+def test_compaction_is_invisible(mod, scen, workdir):
+    compaction_body(lambda cfg: twin(mod, cfg), scen, workdir)
+
+
+def test_load_into_new_tables(mod, scen, workdir):
+    load_into_new_tables_body(lambda cfg: twin(mod, cfg), scen, workdir)
+
+
+def test_push_vehicle(mod, scen, workdir):
+    push_vehicle_body(lambda cfg: twin(mod, cfg), scen, workdir)
+
+
+def test_argument_errors(mod, scen, workdir):
+    cfg = scen.materialize("example_1x1", workdir)
+    argument_errors_body(twin(mod, cfg), mod.VectorEngine._with_backend(cfg, 2, 1, TWIN_LIB))
+
+
+def test_lane_change_is_not_implemented(mod, scen, workdir):
+    cfg = scen.materialize("grid_6x6", workdir, laneChange=True)
+    eng = twin(mod, cfg)
+    with pytest.raises(NotImplementedError):
+        eng.track_trips(True)
+    assert not eng.trip_tracking()
+    eng.track_trips(False)  # (turning it off is no error)
+    vec = mod.VectorEngine._with_backend(cfg, 2, 1, TWIN_LIB)
+    with pytest.raises(NotImplementedError):
+        vec.track_trips(True)
+
+
+def test_tiled_engine_has_no_trip_tracking(mod):
+    for name in ("track_trips", "trip_tracking", "observe_trips_tensor", "observe_trips_array", "get_average_travel_time_tensor"):
+        assert hasattr(mod.Engine, name) and hasattr(mod.VectorEngine, name), name
+        assert not hasattr(mod.TiledEngine, name), name
+
+
+# ---------------------------------------------------------------------------------------------------------------- GPU
+def hip_engine(mod, cfg):
+    eng = mod.Engine(cfg, 1)
+    assert_hip_backend(eng)
+    return eng
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("layout", ["auto", "dense"])
+def test_example_equals_the_model_and_the_twin_on_the_device(mod, scen, workdir, layout):
+    example_body(lambda cfg: hip_engine(mod, cfg), scen, workdir, layout, with_twin=lambda cfg: twin(mod, cfg))
+
+
+@pytest.mark.gpu
+def test_grid_equals_the_model_and_the_twin_on_the_device(mod, scen, workdir):
+    grid_body(lambda cfg: hip_engine(mod, cfg), scen, workdir, with_twin=lambda cfg: twin(mod, cfg))
+
+
+@pytest.mark.gpu
+def test_vector_engine_example_on_the_device(mod, scen, workdir):
+    vector_body(lambda cfg, n: mod.VectorEngine(cfg, n), lambda cfg: twin(mod, cfg), scen, workdir, "example_1x1", 200, rl=False,
+                vec_twin=vec_twin(mod))
+
+
+@pytest.mark.gpu
+def test_vector_engine_grid_with_a_phase_plan_on_the_device(mod, scen, workdir):
+    vector_grid_checks(*vector_body(lambda cfg, n: mod.VectorEngine(cfg, n), lambda cfg: twin(mod, cfg), scen, workdir, "grid_6x6",
+                                    520, rl=True, vec_twin=vec_twin(mod)))
+
+
+@pytest.mark.gpu
+def test_baselines_on_the_device(mod, scen, workdir, tmp_path):
+    baselines_body(lambda cfg: hip_engine(mod, cfg), scen, workdir, tmp_path)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("layout", ["auto", "dense"])
+def test_compaction_is_invisible_on_the_device(mod, scen, workdir, layout):
+    class S:  # (scen with the layout added to every config)
+        @staticmethod
+        def materialize(name, wd, cfx):
+            if layout == "dense":
+                cfx = dict(cfx, layout="dense")
+            return scen.materialize(name, wd, cfx=cfx)
+    compaction_body(lambda cfg: hip_engine(mod, cfg), S, workdir)
+
+
+@pytest.mark.gpu
+def test_load_into_new_tables_on_the_device(mod, scen, workdir):
+    load_into_new_tables_body(lambda cfg: hip_engine(mod, cfg), scen, workdir)
+
+
+@pytest.mark.gpu
+def test_push_vehicle_on_the_device(mod, scen, workdir):
+    push_vehicle_body(lambda cfg: hip_engine(mod, cfg), scen, workdir)
+
+
+@pytest.mark.gpu
+def test_argument_errors_on_the_device(mod, scen, workdir):
+    cfg = scen.materialize("example_1x1", workdir)
+    argument_errors_body(hip_engine(mod, cfg), mod.VectorEngine(cfg, 2))
+
+
+@pytest.mark.gpu
+def test_lane_change_is_not_implemented_on_the_device(mod, scen, workdir):
+    eng = mod.Engine(scen.materialize("grid_6x6", workdir, laneChange=True), 1)
+    with pytest.raises(NotImplementedError):
+        eng.track_trips(True)
+    assert not eng.trip_tracking()
+
+
+@pytest.mark.gpu
+def test_trips_on_a_side_stream(mod, scen, workdir):
+    eng = hip_engine(mod, scen.materialize("example_1x1", workdir))
+    if not eng._device_buffers():
+        pytest.skip("needs device buffers: torch streams do not exist on the twin")
+    eng.track_trips(True)
+    model = Model()
+    device = tensor_device(eng)
+    side = torch.cuda.Stream(device=device)
+    records = []
+    with torch.cuda.stream(side):
+        for s in range(1, 81):
+            eng.next_step()
+            t = empty_outputs(eng)
+            eng.observe_trips_tensor(**t)
+            records.append({k: v.clone() for k, v in t.items()})  # (consumed on `side`, in its order)
+    side.synchronize()
+    ref = twin(mod, scen.materialize("example_1x1", workdir))
+    for s in range(1, 81):
+        ref.next_step()
+        model.tick(ref, s)
+        want = model.outputs()
+        for k in NAMES:
+            assert np.array_equal(records[s - 1][k].cpu().numpy(), np.asarray(want[k], dtype=DTYPES[k])), "step %d: %s" % (s, k)
+    assert model.acc["finished"] > 0

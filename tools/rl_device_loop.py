@@ -23,7 +23,13 @@ the four per-lane outputs, with front_distance + front_speed added at K = 8 and 
 (tracking on), alternated --runs times; then the host path on the same state: get_lane_vehicles() + get_vehicle_distance() +
 get_vehicle_speed() and a Python gather of the first K per lane, asserted equal to the tensors first.  --fronts-only runs one
 output set in the observe -> policy -> set -> next_step loop of --features-only, for a kernel trace (`four` runs on any
-version of the package: it is the launch --features-only all measures)."""
+version of the package: it is the launch --features-only all measures).
+       python tools/rl_device_loop.py --trips [--runs N] [--envs R] [--skip-vector | --skip-single] [--trips-only trace]
+--trips: what track_trips costs and replaces, on the Engine and on VectorEngine --envs x the same — tracking is on from the first
+step, and get_average_travel_time_tensor() is asserted equal to Engine.get_average_travel_time() after the warm-up steps; then
+next_step alone with tracking off and on, alternated --runs times; then get_average_travel_time_tensor() per call against
+Engine.get_average_travel_time() per call on the same state.  --trips-only trace runs next_step + observe_trips_tensor(all nine)
+alone, so that a kernel trace shows k_trip_tick and k_trip_drain beside the step's kernels."""
 import argparse
 import os
 import sys
@@ -45,6 +51,9 @@ ap.add_argument("--lane-flow", action="store_true")
 ap.add_argument("--lane-flow-only", choices=["trace"], default=None)
 ap.add_argument("--fronts", action="store_true")
 ap.add_argument("--fronts-only", choices=["four", "k8", "k32", "all8", "all32", "fronts32"], default=None)
+ap.add_argument("--trips", action="store_true")
+ap.add_argument("--trips-only", choices=["trace"], default=None)
+ap.add_argument("--skip-single", action="store_true", help="--trips: the VectorEngine alone")
 ap.add_argument("--runs", type=int, default=3)
 args = ap.parse_args()
 sys.argv = [sys.argv[0]]
@@ -409,6 +418,61 @@ def fronts(name, eng, n, runs, only):
     for k in (8, 32):
         measure("host path: 3 dict getters + Python gather of the first %d per lane" % k, eng, lambda s, k=k: host_path(k), max(n // 40, 5))
 
+
+def trips(name, eng, n, runs, only):
+    device = torch.device("cuda", eng._stream_handle()[1])
+    shape = tuple(eng._tensor_shapes()[0])[:-1]
+    int64 = ("admitted_buffer_steps", "finished_travel_steps", "in_system_travel_steps")
+    names = ("entered", "admitted", "admitted_buffer_steps", "finished", "finished_travel_steps", "in_system", "buffered",
+             "in_system_travel_steps")
+    out = {k: torch.empty(shape, dtype=torch.int64 if k in int64 else torch.int32, device=device) for k in names}
+    out["average_travel_time"] = torch.empty(shape, dtype=torch.float64, device=device)
+    avg = out["average_travel_time"]
+    eng.track_trips(True)  # (from the first step on: only then is the average the reference's)
+    for _ in range(300):
+        eng.next_step()
+    eng.sync()
+    print("# %s" % name, flush=True)
+    eng.observe_trips_tensor(**out)
+    torch.cuda.synchronize()
+    print("after 300 steps: entered %d, admitted %d, finished %d, in_system %d, buffered %d" % tuple(
+        int(out[k].sum()) for k in ("entered", "admitted", "finished", "in_system", "buffered")), flush=True)
+    if not shape:
+        want = eng.get_average_travel_time()
+        assert float(avg) == want, "get_average_travel_time_tensor %r is not get_average_travel_time %r" % (float(avg), want)
+        print("get_average_travel_time_tensor() == get_average_travel_time() == %.6f" % want, flush=True)
+    if only:
+        def trace(s):
+            eng.next_step()
+            eng.observe_trips_tensor(**out)
+        measure("next_step + observe_trips_tensor(all nine)", eng, trace, n)
+        return
+    res = {"off": [], "on": []}
+    for r in range(runs):
+        eng.track_trips(False)
+        res["off"].append(measure("next_step alone, tracking off (run %d)" % r, eng, lambda s: eng.next_step(), n))
+        eng.track_trips(True)
+        res["on"].append(measure("next_step alone, tracking on  (run %d)" % r, eng, lambda s: eng.next_step(), n))
+    for k, v in res.items():
+        print("%-4s median %8.1f us   min %8.1f   max %8.1f" % (k, float(np.median(v)), min(v), max(v)), flush=True)
+    print("tracking on - off (medians) %8.1f us per step" % (float(np.median(res["on"])) - float(np.median(res["off"]))), flush=True)
+    measure("get_average_travel_time_tensor(out) alone (1 launch + events)", eng, lambda s: eng.get_average_travel_time_tensor(out=avg), n)
+    measure("observe_trips_tensor(all nine) alone (1 launch + events)", eng, lambda s: eng.observe_trips_tensor(**out), n)
+    if not shape:
+        measure("Engine.get_average_travel_time() alone (status bytes to the host, sort, sum)", eng,
+                lambda s: eng.get_average_travel_time(), max(n // 20, 10))
+
+
+if args.trips or args.trips_only:
+    if not args.skip_single:
+        e = _cityflow.Engine(cfg, 1)
+        trips("Engine, 30x30 RL workload (%d signals, %d lanes)" % (len(e.intersection_ids()), len(e.lane_ids())), e, args.iters,
+              args.runs, args.trips_only)
+        del e
+    if not args.skip_vector:
+        v = _cityflow.VectorEngine(cfg, args.envs, 1)
+        trips("VectorEngine, %d x 30x30 RL workload" % args.envs, v, max(args.iters // 4, 50), args.runs, args.trips_only)
+    sys.exit(0)
 
 if args.fronts or args.fronts_only:
     e = _cityflow.Engine(cfg, 1)
