@@ -852,6 +852,698 @@ struct cfx_engine {
         }
         return CFX_OK;
     }
+
+    // ================================================================================= the parts of cfx_step (stepImpl)
+    // cfx_config::debug_sync (developer aid): wait for what the step has launched so far and name the kernel that faulted
+    int debugCheck(bool ringStep, const char *name) {
+        if (!cfg.debug_sync) return CFX_OK;
+        if (ringStep) fprintf(stderr, "[cfx ring] step %lld: %s\n", (long long) step, name);
+        const hipError_t er = hipStreamSynchronize(stream);
+        if (er != hipSuccess) return fail(std::string(ringStep ? "ring step: " : "lane change: ") + name + ": " + hipGetErrorString(er));
+        return CFX_OK;
+    }
+
+    // What has to hold before a step touches anything: tables uploaded, no overflow pending, the host not too far ahead, rings
+    // built, baselines of the statistics taken, the lane-change protocol kept (`n`: the step's spawn records)
+    int stepPreamble(int32_t n) {
+        HIP_TRY(hipSetDevice(device));
+        int rc;
+        if ((rc = syncTables())) return rc;
+        // Fail at the step that failed (or the one after): every step leaves its scalars in pinned host memory, so an
+        // overflow code raised by a step the device has already finished is seen here without waiting for anything.
+        if (mirrorValid && __atomic_load_n(&hMirror->sc.overflow, __ATOMIC_RELAXED) != 0) {
+            DevScalars s;
+            if ((rc = readScalars(s))) return rc == CFX_ERR_DEVICE ? CFX_ERR_CAPACITY : rc;
+        }
+        // ---- the host's lead over the device is bounded.  A free-running caller submits a 30x30 step in ~20 us and the device takes
+        //      ~40: unbounded, the stream's backlog grows by half a step per step, and the next call that has to wait for the device
+        //      (a getter, the spawner's priority-collision query) pays for all of it — 4.5 ms behind a 200-step window, 2 ms with 48 steps in flight.  The step's
+        //      commit publishes the number of completed steps in pinned host memory: wait (yielding) while more than kMaxLead steps
+        //      are in flight.  The device is never idle for it — kMaxLead steps of work are queued behind the one it is executing —
+        //      and a caller that synchronises every step never waits here.  (Built while looking for the 45-80 ms "stall" of the
+        //      sustained windows of rounds 4-6, which it did NOT cure: that was the container's CPU quota — bench.py's header.)
+        if (mirrorValid && !tiled) {
+            constexpr int64_t kMaxLead = 16;  // (16 steps of a 30x30 network = 0.65 ms of queued work: what the next waiting call pays at most)
+            const auto t0 = std::chrono::steady_clock::now();
+            for (unsigned spins = 0;; ++spins) {
+                const int64_t done = (int64_t) (__atomic_load_n(&hMirror->progress, __ATOMIC_RELAXED) >> 32);
+                if (done <= 0 || done > step || step - done <= kMaxLead) break;
+                if ((spins & 63) == 63 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(200)) break;  // (never hang on it)
+                std::this_thread::yield();
+            }
+        }
+        if (ring) {
+            if (mirrorValid && __atomic_load_n(&hMirror->sc.ringNearFull, __ATOMIC_RELAXED) != 0) ringGrowRequested = true;
+            if ((rc = ringEnsure())) return rc;
+        }
+        if ((rc = flowSettle())) return rc;  // (lane flow: a baseline that is due is taken on the state this step starts from)
+        if ((rc = tripSettle())) return rc;  // (trip statistics: likewise)
+        if (observing && ++observeIdle > kObserveIdle) {  // nobody has read the lane counts for a while
+            observing = false;
+            hCntValid = false;
+        }
+        if (devObserving && ++devObserveIdle > kObserveIdle) devObserving = false;
+
+        if (lc.on) {
+            if (pollPending) return fail("cfx_step: the previous lane-change step was not polled (cfx_lane_change_poll)");
+            if (!hPoll) return fail("cfx_step: cfx_lane_change_supply must be called before a step with lane change");
+            if ((rc = ensureVidCap((size_t) spawned + (size_t) n + (size_t) poolN))) return rc;
+        }
+        return CFX_OK;
+    }
+
+    // ---- phase 0/1 tail: how a step's spawn records reach the device (stageSpawns fills it, the admission launches read it)
+    struct SpawnPlan {
+        SpawnBatchBig batch;    // the records go with the admission kernel's arguments: up to kAdmitRecs, kd_admit / kr_admit up to kAdmitRecsBig
+        SpawnBatchMem mem{};    // ... or, more of them on the ring layout, in pinned memory
+        bool inMem = false;     // (neither: k_spawn_link has linked them, the admission takes an empty batch)
+        int memStageUsed = -1;  // the pinned buffer `mem` points into: free again when the admission launch is through
+        SpawnBatch smallBatch() const {  // (the kernels that take at most kAdmitRecs records)
+            SpawnBatch b;
+            b.n = batch.n;
+            b.firstNewVid = batch.firstNewVid;
+            b.enterTime = batch.enterTime;
+            for (int i = 0; i < batch.n && i < kAdmitRecs; ++i) {
+                b.lane[i] = batch.lane[i];
+                b.prevWait[i] = batch.prevWait[i];
+                b.route[i] = batch.route[i];
+                b.priority[i] = batch.priority[i];
+                b.firstNext[i] = batch.firstNext[i];
+                b.templ[i] = batch.templ[i];
+                b.vidOff[i] = batch.vidOff[i];
+            }
+            return b;
+        }
+    };
+
+    // the records as kernel arguments (kr_admit / kd_admit / k_admit take the batch): sorted by lane; false if they do not qualify
+    bool spawnsInArgs(const cfx_spawn *recs, int32_t n, SpawnBatchBig &batch) const {
+        batch.n = (int) n;
+        batch.firstNewVid = (int) spawned;
+        batch.enterTime = recs[0].enter_time;
+        int order[kAdmitRecsBig];
+        bool seen[kAdmitRecsBig] = {};
+        bool inArgs = true;
+        for (int i = 0; inArgs && i < n; ++i) {
+            const int64_t off = (int64_t) recs[i].vid - spawned;
+            inArgs = off >= 0 && off < n && !seen[off] && recs[i].lane >= -1 && recs[i].enter_time == batch.enterTime &&
+                     recs[i].templ < 32768;
+            if (inArgs) seen[off] = true;
+            order[i] = i;
+        }
+        if (!inArgs) {
+            batch.n = 0;
+            return false;
+        }
+        std::sort(order, order + n, [recs](int x, int y) {
+            return recs[x].lane != recs[y].lane ? recs[x].lane < recs[y].lane : recs[x].vid < recs[y].vid;
+        });
+        for (int j = 0; j < n; ++j) {
+            const cfx_spawn &r = recs[order[j]];
+            batch.lane[j] = r.lane;
+            batch.prevWait[j] = r.prev_wait;
+            batch.route[j] = r.route;
+            batch.priority[j] = r.priority;
+            batch.firstNext[j] = firstNextOf(r.lane, r.route);
+            batch.templ[j] = (int16_t) r.templ;
+            batch.vidOff[j] = (int16_t) (r.vid - spawned);
+        }
+        return true;
+    }
+
+    // ring layout, more records than the arguments hold (batched environments): the columns go into pinned memory, sorted
+    // by lane, with the offsets of every block of lanes — kr_admit reads its own lanes' records from there (SpawnBatchMem).
+    // `p.inMem` says whether they qualified.
+    int spawnsInMem(const cfx_spawn *recs, int32_t n, SpawnPlan &p) {
+        const int nLaneBlocks = (L + kBlock - 1) / kBlock;
+        bool inMem = true;
+        const int64_t base = spawned;
+        const double t0 = recs[0].enter_time;
+        // a counting sort by block of lanes (bucket 0: the records without a lane here), then each block's few records by
+        // lane — the kernel looks a lane's records up by bisection; a lane's own records may come in any order
+        memSeen.assign((size_t) n, 0);
+        memBucket.assign((size_t) nLaneBlocks + 2, 0);
+        for (int i = 0; inMem && i < n; ++i) {
+            const int64_t off = (int64_t) recs[i].vid - base;
+            inMem = off >= 0 && off < n && !memSeen[(size_t) off] && recs[i].lane >= -1 && recs[i].lane < L &&
+                    recs[i].enter_time == t0;
+            if (inMem) {
+                memSeen[(size_t) off] = 1;  // (every vehicle number once)
+                memBucket[(size_t) (recs[i].lane < 0 ? 0 : 1 + recs[i].lane / kBlock) + 1] += 1;
+            }
+        }
+        if (!inMem) return CFX_OK;
+        for (int q = 0; q <= nLaneBlocks; ++q) memBucket[(size_t) q + 1] += memBucket[(size_t) q];  // bucket q starts at [q]
+        memOrder.resize((size_t) n);
+        memCursor.assign(memBucket.begin(), memBucket.end() - 1);
+        for (int i = 0; i < n; ++i) memOrder[(size_t) memCursor[(size_t) (recs[i].lane < 0 ? 0 : 1 + recs[i].lane / kBlock)]++] = i;
+        for (int q = 1; q <= nLaneBlocks; ++q) {
+            int32_t *const o = memOrder.data();
+            const int from = memBucket[(size_t) q], to = memBucket[(size_t) q + 1];
+            if (to - from > 24) {
+                std::stable_sort(o + from, o + to, [recs](int x, int y) { return recs[x].lane < recs[y].lane; });
+            } else {
+                for (int j = from + 1; j < to; ++j) {
+                    const int x = o[j], lx = recs[x].lane;
+                    int i = j;
+                    for (; i > from && recs[o[i - 1]].lane > lx; --i) o[i] = o[i - 1];
+                    o[i] = x;
+                }
+            }
+        }
+        const size_t words = (size_t) 7 * (size_t) n + (size_t) nLaneBlocks + 1;
+        if (words > memStageWords) {
+            stallCause |= CFX_STALL_STAGE_GROW;
+            HIP_TRY(hipStreamSynchronize(stream));
+            const size_t nc = std::max<size_t>(words * 2, 4096);
+            for (int i = 0; i < kStages; ++i) {
+                if (hMemStage[i]) HIP_TRY(hipHostFree(hMemStage[i]));
+                hMemStage[i] = nullptr;
+                HIP_TRY(hipHostMalloc((void **) &hMemStage[i], nc * sizeof(int32_t), hipHostMallocDefault));
+                if (!memStageEvent[i]) HIP_TRY(hipEventCreateWithFlags(&memStageEvent[i], hipEventDisableTiming));
+                memStageBusy[i] = false;
+            }
+            memStageWords = nc;
+        }
+        const int si = memStageIdx;
+        memStageIdx = (si + 1) % kStages;
+        if (memStageBusy[si]) HIP_TRY(hipEventSynchronize(memStageEvent[si]));
+        int32_t *const w = hMemStage[si];
+        int32_t *const cLane = w, *const cPrev = w + n, *const cRoute = w + 2 * (size_t) n, *const cPrio = w + 3 * (size_t) n,
+                       *const cNext = w + 4 * (size_t) n, *const cTempl = w + 5 * (size_t) n, *const cOff = w + 6 * (size_t) n,
+                       *const cBlock = w + 7 * (size_t) n;
+        for (int j = 0; j < n; ++j) {
+            const cfx_spawn &r = recs[memOrder[(size_t) j]];
+            cLane[j] = r.lane;
+            cPrev[j] = r.prev_wait;
+            cRoute[j] = r.route;
+            cPrio[j] = r.priority;
+            cNext[j] = firstNextOf(r.lane, r.route);
+            cTempl[j] = r.templ;
+            cOff[j] = (int32_t) (r.vid - spawned);
+        }
+        for (int q = 0; q <= nLaneBlocks; ++q) cBlock[q] = memBucket[(size_t) q + 1];  // block q's records: bucket q + 1
+        p.mem.n = (int) n;
+        p.mem.firstNewVid = (int) spawned;
+        p.mem.enterTime = recs[0].enter_time;
+        p.mem.lane = cLane;
+        p.mem.prevWait = cPrev;
+        p.mem.route = cRoute;
+        p.mem.priority = cPrio;
+        p.mem.firstNext = cNext;
+        p.mem.templ = cTempl;
+        p.mem.vidOff = cOff;
+        p.mem.blockOff = cBlock;
+        p.mem.nLaneBlocks = nLaneBlocks;
+        p.inMem = true;
+        p.memStageUsed = si;
+        return CFX_OK;
+    }
+
+    // ... and whatever fits neither: a pinned copy of the records and a launch of k_spawn_link, with the custom speeds that
+    // wait for one of these vehicles behind it on the stream
+    int spawnsByKernel(const cfx_spawn *recs, int32_t n, const std::vector<std::pair<int32_t, double>> &customNow) {
+        int rc;
+        if ((rc = settle(false))) return rc;  // (k_spawn_link looks at what the previous step's commit leaves)
+        if ((size_t) n > recCap) {
+            size_t nc = std::max<size_t>((size_t) n * 2, 1024);
+            if ((rc = grow(&dRecs, 0, nc))) return rc;
+            recCap = nc;
+        }
+        if ((size_t) n > stageCap) {
+            stallCause |= CFX_STALL_STAGE_GROW;
+            HIP_TRY(hipStreamSynchronize(stream));
+            size_t nc = std::max<size_t>((size_t) n * 2, 1024);
+            for (int i = 0; i < kStages; ++i) {
+                if (hStage[i]) HIP_TRY(hipHostFree(hStage[i]));
+                HIP_TRY(hipHostMalloc((void **) &hStage[i], nc * sizeof(cfx_spawn), hipHostMallocDefault));
+                if (!stageEvent[i]) HIP_TRY(hipEventCreateWithFlags(&stageEvent[i], hipEventDisableTiming));
+                stageBusy[i] = false;
+            }
+            stageCap = nc;
+        }
+        const int si = stageIdx;
+        stageIdx = (si + 1) % kStages;
+        if (stageBusy[si]) HIP_TRY(hipEventSynchronize(stageEvent[si]));
+        memcpy(hStage[si], recs, (size_t) n * sizeof(cfx_spawn));
+        // the kernel reads the pinned (device-visible) staging buffer itself: no separate copy launch
+        launchNamed(PK_SPAWN, "k_spawn_link", k_spawn_link, dim3(gridFor(n)), dim3(kBlock), (const cfx_spawn *) hStage[si], (int) n,
+                    (int) spawned, vt, waitHead, lc);
+        HIP_TRY(hipEventRecord(stageEvent[si], stream));
+        stageBusy[si] = true;
+        if (!customNow.empty()) {  // Vehicle::setCustomSpeed on a vehicle still in its waiting buffer (cfx_set_vehicle_speed)
+            const uint8_t one = 1;
+            for (const auto &fc : customNow) {
+                HIP_TRY(hipMemcpyAsync(vt.customSpeed + fc.first, &fc.second, sizeof(double), hipMemcpyHostToDevice, stream));
+                HIP_TRY(hipMemcpyAsync(vt.pendingCustom + fc.first, &one, 1, hipMemcpyHostToDevice, stream));
+            }
+            HIP_TRY(hipStreamSynchronize(stream));  // (the sources live on this frame)
+        }
+        return CFX_OK;
+    }
+
+    // Hand the spawn records to the device, by the cheapest route they qualify for
+    int stageSpawns(const cfx_spawn *recs, int32_t n, SpawnPlan &p) {
+        p.batch.n = 0;
+        p.batch.firstNewVid = 0;
+        if (n <= 0) return CFX_OK;
+        int rc;
+        // (the ring layout too: more records than the small batch holds kept the step from riding its commit with the next
+        // admission, and cost a launch of their own; a step with up to kAdmitRecs records runs the small instantiation as before)
+        const int batchRoom = ((useTails() && (denseForm & 4)) || ring) ? kAdmitRecsBig : kAdmitRecs;
+        // the batch carries the next n vehicle numbers, each once, in any order (checked in full by the CPU twin)
+        if (recs[0].vid < spawned || recs[0].vid >= spawned + n)
+            return fail("cfx_step: spawn records must continue the dense vid sequence");
+        if ((rc = ensureVidCap((size_t) spawned + n))) return rc;
+        // a custom speed waiting for one of these vehicles has to be in the vehicle table before the admission looks at it:
+        // the records then take the k_spawn_link path and the speeds follow it on the stream (rare: push_vehicle + set_vehicle_speed)
+        std::vector<std::pair<int32_t, double>> customNow;
+        for (const auto &fc : futureCustom)
+            if (fc.first < spawned + n) customNow.push_back(fc);
+        // ring layout: a step's few records go with kr_admit's arguments (each lane's thread links its own): no launch.  They
+        // fit if they are few, all for lanes of this engine, and all enter at the same time (what a host spawner produces:
+        // Engine::getCurrentTime); record i of the batch is vehicle spawned + i, whatever order they came in
+        const bool inArgs = n <= batchRoom && customNow.empty() && spawnsInArgs(recs, n, p.batch);
+        if (!inArgs && ring && n > batchRoom && customNow.empty() && !cfg.debug_sync && (rc = spawnsInMem(recs, n, p))) return rc;
+        if (!inArgs && !p.inMem && (rc = spawnsByKernel(recs, n, customNow))) return rc;
+        spawned += n;
+        return CFX_OK;
+    }
+
+    // What the step's records mean for the host's bookkeeping: custom speeds that found no vehicle, and the slot capacity.
+    // Two host-side upper bounds of the vehicles that can be running after this step:
+    //   (a) spawned - finished (as of the last read)           — tight while nobody queues for long;
+    //   (b) running (as of the last read) + what can have been admitted since: at most one vehicle per step on every
+    //       lane that has ever had a vehicle queued, plus halo migrants — stays small when entry lanes saturate and the
+    //       waiting queues grow without bound (they hold vehicle-table entries, not slots).
+    // When the smaller of the two outgrows the buffers, the true count is read back and the buffers grow only if needed.
+    void accountSpawns(const cfx_spawn *recs, int32_t n) {
+        for (const auto &fc : futureCustom)  // (what this batch did not create was not a vehicle of this step: counted, not silent)
+            if (fc.first >= spawned) droppedFutureSpeeds += 1;
+        futureCustom.clear();
+        for (int i = 0; i < n; ++i) {
+            if (!dyadic(recs[i].enter_time)) timesDyadic = false;
+            const int lane = recs[i].lane;
+            if (lane >= 0 && !laneQueued[lane]) {
+                laneQueued[lane] = 1;
+                nQueueLanes += 1;
+            }
+            spawnedHere += lane >= 0;
+        }
+        liveUpper += nQueueLanes;
+    }
+
+    // ---- ring layout
+    // kr_admit<COMMIT, N, Batch>: with or without the previous step's commit, for the records as the plan holds them
+    template <bool COMMIT>
+    void launchRingAdmit(const SpawnPlan &p, int blocks, const RingCtx &c, const RingCommit &rk, const RingHaloIn &hin) {
+        if (p.inMem)
+            launchNamed(PK_ADMIT, COMMIT ? "kr_admit<true, kBlock, SpawnBatchMem>" : "kr_admit<false, kBlock, SpawnBatchMem>",
+                        kr_admit<COMMIT, kBlock, SpawnBatchMem>, dim3(blocks), dim3(kBlock), c, admitStep, waitHead, vt, sc, p.mem, rk, hin);
+        else if (p.batch.n > kAdmitRecs)
+            launchNamed(PK_ADMIT, COMMIT ? "kr_admit<true, kAdmitRecsBig>" : "kr_admit<false, kAdmitRecsBig>", kr_admit<COMMIT, kAdmitRecsBig>,
+                        dim3(blocks), dim3(kBlock), c, admitStep, waitHead, vt, sc, p.batch, rk, hin);
+        else
+            launchNamed(PK_ADMIT, COMMIT ? "kr_admit<true>" : "kr_admit<false>", kr_admit<COMMIT>, dim3(blocks), dim3(kBlock), c, admitStep,
+                        waitHead, vt, sc, p.smallBatch(), rk, hin);
+    }
+    // kr_action<B, GHOST>: a tile's ghost lanes take the instantiations that know about frozen proxies
+    template <int B>
+    void launchRingLanes(dim3 grid, const RingCtx &c, const RingOut &ro, const JobQueue &jq, RingJob *jobRecs, int G, int nLaneBlocks,
+                         int nLLBlocks, const RingHist &rh) {
+        static_assert(B == 256 || B == 512, "the block sizes kr_action is launched with");
+        if (tiled)
+            launchNamed(PK_ACTION, B == 256 ? "kr_action<256, true>" : "kr_action<512, true>", kr_action<B, true>, grid, dim3(B), c, ro, jq,
+                        jobRecs, G, nLaneBlocks, nLLBlocks, rh);
+        else
+            launchNamed(PK_ACTION, B == 256 ? "kr_action<256>" : "kr_action<512>", kr_action<B>, grid, dim3(B), c, ro, jq, jobRecs, G,
+                        nLaneBlocks, nLLBlocks, rh);
+    }
+
+    // The action phase's organisation.  Lane walking (kr_action): one workgroup = B threads over G lanes (or B laneLinks).
+    // G is picked so that a block's vehicles fit one pass (B - 1) with room for uneven lanes; small networks take small blocks
+    // (every block resident at once, the step is bound by the slowest block's chain), large ones full blocks (throughput).
+    // The list form (kr_index + kl_action) is the default where the cross phase runs k_cross2, and on large networks: lane
+    // walking costs per lane, the list per vehicle plus 8 to 12 us for the list — 30x30, 10.8 k lanes, 90 k vehicles: 41.0 us
+    // per step lane-walking, 49.0 with the list; 100x100, 120 k lanes, 72 k vehicles: 97.1 and 54.7.
+    // cfx_config::ring_lanes_per_wave = G + 1000 * (B / 256) overrides G and B (developer knob; B = 256 or 512); + 20000
+    // forces lane walking, + 30000 the list (+ 60000: with its tiles handed out by ticket).
+    struct RingShape {
+        int G, B;
+        bool list;
+    };
+    RingShape pickRingShape(size_t activeEst, bool useBig) {
+        int G = ringG, Bsel = 256;
+        const int form = (cfg.ring_lanes_per_wave / 10000) % 10;
+        const int want = cfg.ring_lanes_per_wave % 10000;
+        if (want > 0) {
+            G = std::max(1, want % 1000);
+            Bsel = want >= 2000 ? 512 : 256;
+        } else if (useBig || activeEst > 240000) {
+            G = 28;  // many rounds of blocks anyway: full blocks, a second chunk where the lanes are dense (throughput)
+        } else if (mirrorValid) {
+            // adapt to the traffic: the densest block of a recent step (pinned mirror, possibly a few steps old) should
+            // fit one pass with some room; results do not depend on G
+            const int maxT = __atomic_load_n(&hMirror->sc.actionMaxT, __ATOMIC_RELAXED);
+            if (ringHold > 0) {
+                ringHold -= 1;  // (the mirror lags a few steps behind: let a change show before the next one)
+            } else if (maxT > Bsel - 1) {
+                ringG = std::max(4, ringG - 1);
+                ringCalm = 0;
+                ringHold = 8;
+            } else if (maxT == 0 && ringG < 16) {  // no block above 3/4 of a pass for a while: fuller blocks
+                if (++ringCalm >= 256) {
+                    ringG += 1;
+                    ringCalm = 0;
+                }
+            } else {
+                ringCalm = 0;
+            }
+            G = ringG;
+        }
+        const bool list = form == 3 || form == 6 || (form == 0 && (useBig || activeEst > 240000 || L > 20000));
+        return RingShape{std::min(G, Bsel), Bsel, list};
+    }
+
+    // The list form: a TRUE bound of the vehicles this step can list (the list and the launch are sized by it) — what the
+    // device reported after the last step it has completed (`pr`) plus one admission per queueing lane and step since — and
+    // the list grown to it.  Returns the blocks of kListBlock entries the action launch covers.
+    int ringListEnsure(unsigned long long pr, int *nVehBlocksOut) {
+        const int64_t done = (int64_t) (pr >> 32);
+        // (a tile: plus what the halo can have brought in since — its count is as of the commit, before that step's import)
+        if (done > 0 && done <= step)
+            liveUpper = std::min(liveUpper, (int64_t) (pr & 0xFFFFFFFFu) + nQueueLanes * (step + 1 - done) +
+                                                (tiled ? (int64_t) halo.nImport * CFX_HALO_MAX_MIGRANTS * (step + 2 - done) +
+                                                             2 * (int64_t) halo.nGhost : 0));
+        const size_t listBound = (size_t) std::min<int64_t>(liveUpper, (int64_t) ringSlots);
+        const size_t needList = (listBound + kListBlock - 1) / kListBlock * kListBlock + kListBlock;
+        if (needList > rListCap) {
+            stallCause |= CFX_STALL_LIST_GROW;
+            hostStats.table_grows_total += 1;
+            const size_t nc = std::max(needList + needList / 4, rListCap * 2) / kListBlock * kListBlock;
+            int rc = growDeferred(&rList, 0, nc);  // (rebuilt every step: nothing to keep)
+            if (rc) return rc;
+            rListCap = nc;
+            if (!rListCount) {
+                if ((rc = allocRaw(&rListCount, 2)) || (rc = allocRaw(&rIdxGranules, (size_t) gridFor(D)))) return rc;
+                HIP_TRY(hipMemsetAsync(rIdxGranules, 0, (size_t) gridFor(D) * sizeof(unsigned long long), stream));
+                HIP_TRY(hipMemsetAsync(rListCount, 0, 2 * sizeof(int32_t), stream));
+            }
+        }
+        *nVehBlocksOut = (int) (needList / kListBlock);  // (every entry a block of the launch reads exists)
+        return CFX_OK;
+    }
+
+    // The action phase (+ the laneLinks' notify sources, + the last step's Lane::history) in the form `shape` names
+    int launchRingAction(const RingShape &shape, unsigned long long pr, const RingCtx &c, const RingOut &ro, const JobQueue &jq, RingJob *jobRecs) {
+        int rc;
+        if (shape.list) {
+            int nVehBlocks = 0;
+            if ((rc = ringListEnsure(pr, &nVehBlocks))) return rc;
+            const int nLL = (K + kListBlock - 1) / kListBlock;
+            const int nIdxTiles = (int) ((D + kIndexTile - 1) / kIndexTile);
+            // (1024 threads: two blocks per CU.  Form 6 hands the tiles out by ticket whatever their number: the path of networks
+            //  above half a million drivables, for the tests)
+            const bool ticketForm = (cfg.ring_lanes_per_wave / 10000) % 10 == 6;
+            int32_t *const idxTicket = (nIdxTiles > kScanResidentTiles || ticketForm) ? rListCount + 1 : nullptr;
+            launchNamed(PK_SCAN, "kr_index", kr_index, dim3(nIdxTiles), dim3(kIndexBlock), c, rIdxGranules, idxTicket, (unsigned) (step + 1),
+                        // (the capacity the kernel checks is what THIS step's action launch covers, not the allocation — which has
+                        //  25 % of headroom and never shrinks: entries beyond the launch would never take their step, unflagged)
+                        rList, (int) std::min<size_t>(rListCap, (size_t) nVehBlocks * kListBlock), rListCount, sc);
+            if ((rc = debugCheck(true, "kr_index"))) return rc;
+            const RingHist rh = takeHist(nVehBlocks + nLL);  // (the last step's Lane::history: trailing blocks of this launch)
+            const int nHist = rh.h.num ? (L + kListBlock - 1) / kListBlock : 0;
+            launchNamed(PK_ACTION, tiled ? "kl_action<true>" : "kl_action", tiled ? kl_action<true> : kl_action<false>, dim3(nVehBlocks + nLL + nHist),
+                        dim3(kListBlock), c, ro, jq, jobRecs, (const int4 *) rList, (const int32_t *) rListCount, nVehBlocks, idxTicket, rh);
+            return CFX_OK;
+        }
+        const int G = shape.G, Bsel = shape.B;
+        const int nLaneBlocks = (L + G - 1) / G, nLLBlocks = (K + Bsel - 1) / Bsel;
+        // (as many blocks again at the end of the grid compute the laneLinks' notify sources)
+        const RingHist rh = takeHist(nLaneBlocks + 2 * nLLBlocks);  // (the last step's Lane::history: trailing blocks of this launch)
+        const dim3 grid(nLaneBlocks + 2 * nLLBlocks + (rh.h.num ? (L + Bsel - 1) / Bsel : 0));
+        if (Bsel == 256) launchRingLanes<256>(grid, c, ro, jq, jobRecs, G, nLaneBlocks, nLLBlocks, rh);
+        else launchRingLanes<512>(grid, c, ro, jq, jobRecs, G, nLaneBlocks, nLLBlocks, rh);
+        return CFX_OK;
+    }
+
+    // The cross phase in its form for throughput (k_cross2, from the slots) or for latency (kr_cross, from the job records);
+    // `lightsToo`: the kernel advances the lights, because the step's commit is deferred
+    void launchRingCross(bool useBig, size_t activeEst, const RingCtx &c, const RingOut &ro, const JobQueue &jq, bool lightsToo) {
+        if (useBig) {
+            launchNamed(PK_CROSS, "k_cross2<false, RingCtx, RingOut>", k_cross2<false, RingCtx, RingOut>,
+                        dim3((int) std::min<size_t>(std::max<size_t>(64, (activeEst / 4 + 15) / 16), (size_t) CFX_RING_CROSS2_WAVES * nCU)),  // (5 blocks per CU: 96 registers)
+                        dim3(kCross2Block), c, ro, jq, RingLights{curPhase, remain, lightsToo ? 1 : 0});
+            return;
+        }
+        // one 16-lane group per queued vehicle; sized by the job count of the last step the device has reported (every
+        // block of the grid pays the prologue, and blocks that find no job still take a wavefront slot for it)
+        size_t groups = activeEst / 4;
+        if (mirrorValid) {
+            const int lastJobs = __atomic_load_n(&hMirror->sc.nCrossJobs, __ATOMIC_RELAXED);
+            if (lastJobs > 0) groups = std::min<size_t>(groups, (size_t) lastJobs + (size_t) lastJobs / 4 + 256);
+        }
+        launchNamed(PK_CROSS, "kr_cross", kr_cross, dim3((int) std::min<size_t>(std::max<size_t>(64, (groups * 16 + kCrossBlock - 1) / kCrossBlock), 32768)),
+                    dim3(kCrossBlock), c, ro, jq, (const RingJob *) rJobRecs, RingLights{curPhase, remain, lightsToo ? 1 : 0});
+    }
+
+    // debug_sync: the rings' invariants after the action phase (kr_validate)
+    int ringValidate(const RingCtx &c, const JobQueue &jq) {
+        HIP_TRY(hipMemsetAsync(laneOut, 0, 8 * sizeof(int32_t), stream));
+        hipLaunchKernelGGL(kr_validate, dim3(gridFor(std::max(D, 16))), dim3(kBlock), 0, stream, c, jq, (int) spawned,
+                           (int) hRouteStart.size() - 1, (int) ringSlots, laneOut);
+        int32_t rep[5] = {0, 0, 0, 0, 0};
+        HIP_TRY(hipMemcpyAsync(rep, laneOut, sizeof rep, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        if (rep[0]) {
+            char buf[160];
+            snprintf(buf, sizeof buf, "ring invariant %d violated at step %lld: %d %d %d %d", rep[0], (long long) step, rep[1], rep[2], rep[3], rep[4]);
+            return fail(buf);
+        }
+        return CFX_OK;
+    }
+
+    // ring layout: admit, action (+ notify sources), cross, commit — no scan, no scatter
+    int stepRing(const SpawnPlan &p) {
+        int rc;
+        RingCtx c = rctx(true);
+        const bool dbg = cfg.debug_sync != 0;  // developer aid: name the kernel that faults
+        if ((rc = debugCheck(true, "before the step"))) return rc;
+        const unsigned long long pr = __atomic_load_n(&hMirror->progress, __ATOMIC_RELAXED);
+        // running vehicles as of the last step the device has completed (stale by the few steps the host runs ahead):
+        // only sizes the cross phase's grid and picks its organisation
+        const size_t activeEst = (size_t) (pr & 0xFFFFFFFFu) + (size_t) nQueueLanes * 4;
+        const bool useBig = cross2 >= 0 ? cross2 == 1 : activeEst > 240000;  // which form of the cross phase (§4)
+        // This step's commit rides with the next step's admission (one launch less per step) where the step runs kr_cross,
+        // which then advances the lights; the previous step's, if it is still pending, goes with this step's admission.
+        const bool deferCommit = ringMerge && !dbg && !tiled && !observing && !devObserving && !flowOn && !tripOn;  // (a caller that reads the lane counts after every step wants the commit now; so do the lane-flow and the trip tick)
+        // tiling: the previous step's halo import, if cfx_halo_wait left it to this launch
+        const RingHaloIn hin = haloImportPending ? pendingImport : RingHaloIn{};
+        haloImportPending = false;
+        if (commitPending) {
+            commitPending = false;
+            int nStatPrev = 1;
+            const RingCommit rkPrev = commitArgs(activeEst, true, &nStatPrev);
+            launchRingAdmit<true>(p, gridFor(D) + nStatPrev, rctx(true, step - 1, rcur ^ 1), rkPrev, RingHaloIn{});
+        } else {
+            launchRingAdmit<false>(p, gridFor(D), c, RingCommit{}, hin);
+        }
+        if (p.memStageUsed >= 0) {  // (the kernel reads the pinned buffer itself: free again when this launch is through)
+            HIP_TRY(hipEventRecord(memStageEvent[p.memStageUsed], stream));
+            memStageBusy[p.memStageUsed] = true;
+        }
+        if ((rc = debugCheck(true, "kr_admit"))) return rc;
+        RingJob *const jobRecs = useBig ? nullptr : rJobRecs;  // k_cross2 starts from the slots: no job records then
+        RingOut ro{c.kinN, c.blkW, rScratch, rMovers, sc, rFinKey, rFinVid, rFinCap, finCount};
+        JobQueue jq{jobCount, rJobs, rJobCap, &sc->overflow};
+        if ((rc = launchRingAction(pickRingShape(activeEst, useBig), pr, c, ro, jq, jobRecs))) return rc;
+        if ((rc = debugCheck(true, "kr_action"))) return rc;
+        if (dbg && (rc = ringValidate(c, jq))) return rc;
+        launchRingCross(useBig, activeEst, c, ro, jq, deferCommit && !cfg.rl_traffic_light);
+        if ((rc = debugCheck(true, "k_cross"))) return rc;
+        if (deferCommit) {
+            commitPending = true;  // launched by the next cfx_step (with its admission) or by settle()
+        } else {
+            int nStat = 1;
+            const RingCommit rk = commitArgs(activeEst, false, &nStat);
+            launchNamed(PK_COMMIT, "kr_commit", kr_commit, dim3(gridStride((size_t) std::max(D, std::max(I, nMaskWords))) + nStat), dim3(kBlock), c, rk, vt,
+                        ringHalo());
+            if ((rc = debugCheck(true, "kr_commit"))) return rc;
+        }
+        HIP_TRY(hipGetLastError());
+        rcur ^= 1;
+        step += 1;
+        mirrorValid = !tiled;
+        histPending = hist.num != 0;  // (this step's Lane::history: with the next action launch, or settle() — on a tile behind the step's halo import)
+        if (flowOn && (rc = flowTick(false))) return rc;
+        if (tripOn) return tripTick(false);
+        return CFX_OK;
+    }
+
+    // ---- dense layout (and lane change, which runs on it)
+    // a host-side upper bound of the vehicles that can be running after this step (accountSpawns has the story)
+    int64_t denseBound() const {
+        const int64_t a = spawnedHere - (finishedKnown - finishedOffset);
+        return tiled ? liveUpper : std::min(a, liveUpper);
+    }
+    int64_t shadowRoom() const { return lc.on ? poolN : 0; }  // this step's shadows
+    // ... and the lanes that get them move behind the layout's end (k_lc_insert), each at most once per step, with the shadows
+    // they receive: all running vehicles plus the step's shadows is a true bound of what can move (round 3 reserved a heuristic
+    // quarter of the vehicles, which a dense jam in which every lane gets a shadow could exceed: ADVICE round 3)
+    int64_t moveRoom() const { return lc.on ? denseBound() + shadowRoom() + 64 : (int64_t) 0; }
+
+    // the slots the step can need, with the buffers grown to them
+    int denseEnsureSlots(size_t *needOut) {
+        int rc;
+        const int64_t spare = tiled ? spareTotal : (int64_t) L;
+        size_t need = (size_t) (denseBound() + spare + shadowRoom() + moveRoom()) + 1;
+        if (need > slotCap && !tiled) {
+            // the device's own count as of the last step it has completed, read without waiting for it
+            const unsigned long long pr = __atomic_load_n(&hMirror->progress, __ATOMIC_RELAXED);
+            const int64_t done = (int64_t) (pr >> 32);
+            if (done > 0 && done <= step) {
+                // since then: at most one admission per queueing lane and step, and (lane change) that step's shadows
+                liveUpper = std::min(liveUpper, (int64_t) (pr & 0xFFFFFFFFu) + (nQueueLanes + shadowRoom()) * (step + 1 - done));
+                need = (size_t) (denseBound() + spare + shadowRoom() + moveRoom()) + 1;
+            }
+        }
+        if (need > slotCap) {
+            DevScalars s;
+            if ((rc = readScalars(s))) return rc;  // refreshes finishedKnown too
+            liveUpper = s.active + 2 * (int64_t) halo.nGhost + nQueueLanes;
+            need = (size_t) (denseBound() + spare + shadowRoom() + moveRoom()) + 1;
+            if ((rc = ensureSlotCap(need))) return rc;
+        }
+        *needOut = need;
+        return CFX_OK;
+    }
+
+    // kd_admit<LANES, N> over the lanes only or over every drivable, k_admit with lane change
+    template <bool LANES>
+    void launchDenseAdmit(const SpawnPlan &p, const StepCtx &c) {
+        if (p.batch.n > kAdmitRecs)
+            launchNamed(PK_ADMIT, LANES ? "kd_admit<true, kAdmitRecsBig>" : "kd_admit<false, kAdmitRecsBig>", kd_admit<LANES, kAdmitRecsBig>,
+                        dim3(gridFor(LANES ? L : D)), dim3(kBlock), c, admitStep, waitHead, vt, cs, p.batch, LANES ? gatePhase : (int32_t *) nullptr);
+        else
+            launchNamed(PK_ADMIT, LANES ? "kd_admit<true, kAdmitRecs>" : "kd_admit<false, kAdmitRecs>", kd_admit<LANES, kAdmitRecs>,
+                        dim3(gridFor(LANES ? L : D)), dim3(kBlock), c, admitStep, waitHead, vt, cs, p.smallBatch(), LANES ? gatePhase : (int32_t *) nullptr);
+    }
+
+    // Engine::nextStep engine.cpp:571-575: initSegments, planLaneChange (+ scheduleLaneChange), and the order rebuilt
+    // with the step's shadows in place (cfx_lc_kernels.h)
+    int stepLaneChange(StepCtx &c, size_t slotBound) {
+        int rc;
+        hipLaunchKernelGGL(k_lc_plan, dim3(gridStride(slotBound)), dim3(kBlock), 0, stream, c);
+        if ((rc = debugCheck(false, "k_lc_plan"))) return rc;
+        hipLaunchKernelGGL(k_lc_schedule, dim3(R), dim3(64), 0, stream, c, sc, (const int32_t *) vt.priority);
+        if ((rc = debugCheck(false, "k_lc_schedule"))) return rc;
+        hipLaunchKernelGGL(k_lc_insert, dim3(256), dim3(64), 0, stream, c, vt, sc, hPoll, oldToNew, segStart[cur].p, cnt[cur].p,
+                           (int) slotCap);
+        if ((rc = debugCheck(false, "k_lc_insert"))) return rc;
+        HIP_TRY(hipEventRecord(pollEvent, stream));  // cfx_lane_change_poll waits for this, not for the whole step
+        pollPending = true;
+        HIP_TRY(hipGetLastError());
+        c.admissionsVisible = 1;
+        // the leader / gap pass between planLaneChange and getAction takes a history record too (engine.cpp:571-575, 429-442);
+        // k_lc_insert has moved the lanes that got shadows: the context is taken anew
+        if (hist.num && !tiled) hipLaunchKernelGGL(k_lane_history, dim3(gridFor(L)), dim3(kBlock), 0, stream, ctx(), hist);
+        return CFX_OK;
+    }
+
+    // dense layout: admit, (lane change,) action, cross, (lane change's resolution,) scan, scatter
+    int stepDense(const SpawnPlan &p) {
+        int rc;
+        size_t need = 0;
+        if ((rc = denseEnsureSlots(&need))) return rc;
+        if (lc.on) {  // per-step fields of the lane-change context
+            lc.firstShadowVid = (int) spawned;
+            lc.pool = hPool;  // pinned: k_lc_insert reads the few priorities it hands out straight from the host's buffer
+            lc.insCap = poolN;
+        }
+        const bool tails = useTails();
+        if (tails && !dTailNow) {
+            if ((rc = allocRaw(&dTail[0], (size_t) D))) return rc;
+            if ((rc = allocRaw(&dTail[1], (size_t) D))) return rc;
+            if ((rc = allocRaw(&dTailNow, (size_t) D))) return rc;
+            if ((rc = allocRaw(&dGate4, (size_t) std::max(K, 1)))) return rc;
+        }
+        StepCtx c = ctx();
+        if (tails && !tailsValid) {  // after a reset / cfx_load_state: the records of the generation the step starts from
+            hipLaunchKernelGGL(kd_init_tails, dim3(gridFor(D)), dim3(kBlock), 0, stream, c, dTail[0], dTail[1]);
+            tailsValid = true;
+        }
+        // grids: the slots the layout can hold; with lane change the room reserved for moving lanes lies behind them and is
+        // covered by the kernels' stride loops in the (rare) step that uses much of it
+        const size_t slotBound = std::min(need - (size_t) moveRoom() + (lc.on ? (size_t) 4096 : 0), slotCap);
+        // Two organisations of the cross walk: for latency (fewest dependent rounds per vehicle) and, for large networks, for
+        // throughput (far fewer wave-rounds per vehicle).  They break even at ~220 k slots on the MI355X.
+        const bool useBig = cross2 >= 0 ? cross2 == 1 : slotBound > 240000;
+        if (lc.on && !lcSegValid) {  // after a reset / cfx_load_state
+            hipLaunchKernelGGL(k_lc_naive, dim3(gridStride(slotBound)), dim3(kBlock), 0, stream, c);
+            lcSegValid = true;
+        }
+        if (tails && c.laneAdmit) {
+            if (!gatePhase) {
+                if ((rc = allocRaw(&gatePhase, (size_t) 2 * std::max(I, 1)))) return rc;
+                HIP_TRY(hipMemsetAsync(gatePhase, 0xFF, (size_t) 2 * std::max(I, 1) * sizeof(int32_t), stream));
+            }
+            launchDenseAdmit<true>(p, c);
+        } else if (tails) {
+            launchDenseAdmit<false>(p, c);
+        } else {
+            launchNamed(PK_ADMIT, "k_admit", k_admit, dim3(gridFor(D)), dim3(kBlock), c, admitStep, waitHead, vt, cs, p.smallBatch());
+        }
+        ActionOut ao{ab, cs, vt, sc, finList, (int) slotCap, finCount};
+        if (lc.on && (rc = stepLaneChange(c, slotBound))) return rc;
+        const int nxt = cur ^ 1;
+        JobQueue jq{jobCount, crossJobs, (int) slotCap, &sc->overflow};
+        if (tails) {
+            const int nv = (int) ((slotBound + kDenseActBlock - 1) / kDenseActBlock), nl = (K + kDenseActBlock - 1) / kDenseActBlock;
+            launchNamed(PK_ACTION, "kd_action", kd_action, dim3(nv + nl), dim3(kDenseActBlock), c, ao, jq, nv);
+        } else {  // (lane change)
+            const int nVehBlocks = (int) std::min<size_t>(std::max<size_t>(1, (slotBound + kActBlock - 1) / kActBlock), 8192);
+            const int nLLBlocks = (K + kActBlock - 1) / kActBlock;
+            launchNamed(PK_ACTION, "k_action<true>", k_action, dim3(nVehBlocks + nLLBlocks), dim3(kActBlock), c, ao, jq, nVehBlocks);
+        }
+        if (useBig)
+            // (the blocks the chip holds at once — 7 per CU: the kernel's LDS — or fewer for a short queue: the kernel sizes its batches)
+            launchNamed(PK_CROSS, lc.on ? "k_cross2<true>" : "k_cross2<false>", lc.on ? k_cross2<true> : k_cross2<false>, dim3((int) std::min<size_t>(std::max<size_t>(1, (slotBound + 15) / 16), (size_t) CFX_CROSS2_BLOCKS_PER_CU * nCU)),
+                        dim3(kCross2Block), c, ao, jq, RingLights{nullptr, nullptr, 0});
+        else
+            launchNamed(PK_CROSS, lc.on ? "k_cross<true>" : "k_cross<false>", lc.on ? k_cross<true> : k_cross<false>,
+                        dim3((int) std::min<size_t>(std::max<size_t>(1, (slotBound * 16 + kCrossBlock - 1) / kCrossBlock), 32768)),
+                        dim3(kCrossBlock), c, ao, jq);
+        if (lc.on) {
+            hipLaunchKernelGGL(k_lc_resolve, dim3((int) std::min<size_t>(std::max<size_t>(1, (slotBound / 8 + kBlock - 1) / kBlock), 1024)),
+                               dim3(kBlock), 0, stream, c, ao, oldToNew2);
+            hipLaunchKernelGGL(k_lc_resolve_rest, dim3(1), dim3(kBlock), 0, stream, c, ao, oldToNew2);
+        }
+        int32_t *const ticket = nScanBlocks > kScanResidentTiles ? scanTicket : nullptr;
+        launchNamed(PK_SCAN, "k_scan", k_scan, dim3(nScanBlocks), dim3(kBlock), (int) D, (int) L, (const int32_t *) cnt[cur].p, cs,
+                    scanGranules, ticket, (unsigned) (step + 1), segStart[nxt].p, cnt[nxt].p, gen[nxt].vid,
+                    gen[nxt].drv, sc, net.laneSpare, (const int32_t *) admitStep, (int) step, waitHead, vt,
+                    net.laneGhost, (const int2 *) admitRec, publishTo(), lc.on ? 1 : 0);
+        // finish statistics: one extra block per 64 k slots (a rank sort of the step's finishers, see finishStatistics)
+        const int nStat = (int) std::min<size_t>(std::max<size_t>(1, slotBound >> 16), 64);
+        launchNamed(PK_SCATTER, lc.on ? "k_scatter<true>" : "k_scatter<false>", lc.on ? k_scatter<true> : k_scatter<false>,
+                    dim3(gridStride(std::max<size_t>(slotBound, (size_t) std::max(I, nMaskWords))) + nStat), dim3(kBlock), c, ab,
+                    cs, gen[nxt], (const int32_t *) segStart[nxt].p, oldToNew, curPhase, remain,
+                    (int) cfg.rl_traffic_light, (int) nMaskWords, ticket, vt, sc, (const int32_t *) finList,
+                    finTerm, (int) slotCap, jobCount, tiled ? (HostMirror *) nullptr : hMirror, finTicket, nStat,
+                    exactTimes() ? 1 : 0, (const int32_t *) cnt[nxt].p, finCount);
+        HIP_TRY(hipGetLastError());
+        cur = nxt;
+        step += 1;
+        mirrorValid = !tiled;
+        if (hist.num && !tiled) {  // Lane::updateHistory, on the committed state
+            hipLaunchKernelGGL(k_lane_history, dim3(gridFor(L)), dim3(kBlock), 0, stream, ctx(), hist);
+            HIP_TRY(hipGetLastError());
+        }
+        if (flowOn && (rc = flowTick(false))) return rc;
+        if (tripOn) return tripTick(false);
+        return CFX_OK;
+    }
+
     // (Re)build the rings: first use, a shorter vehicle template than the capacities were computed for, or growth.
     // ---- tiling on the rings: the export is part of the step's commit (RingHalo), the import a kernel of its own
     int32_t *dCutIndex = nullptr;     // [L] -1 / ghost lane i / nGhost + import lane j
@@ -1059,6 +1751,14 @@ void cfx_destroy(cfx_engine *e) {
 
 static int32_t createImpl(cfx_engine *e, const cfx_net *n, const cfx_config *cfg) {
     auto fail = [e](const std::string &m) { return e->fail(m); };
+    {  // the form digit of the developer knob names a form of the step, or nothing (include/cityflow_amd.h)
+        const int form = (cfg->ring_lanes_per_wave / 10000) % 10;
+        if (form == 1 || form == 5 || form == 8 || form == 9) {
+            e->fail("cfx_create: ringLanesPerWave = " + std::to_string(cfg->ring_lanes_per_wave) + " names no form of the step (digit " +
+                    std::to_string(form) + " of cfx_config::ring_lanes_per_wave / 10000; the forms are 0, 2, 3, 4, 6, 7)");
+            return CFX_ERR_INVALID;
+        }
+    }
     int ndev = 0;
     HIP_TRY(hipGetDeviceCount(&ndev));
     if (ndev <= 0) return e->fail("no HIP device visible");
@@ -1315,7 +2015,15 @@ int32_t cfx_add_routes(cfx_engine *e, int32_t nRoutes, const int32_t *routeStart
 }
 
 }  // extern "C"
-static int32_t stepImpl(cfx_engine *e, const cfx_spawn *recs, int32_t n);
+// One step: the parts are members of cfx_engine, in this order
+static int32_t stepImpl(cfx_engine *e, const cfx_spawn *recs, int32_t n) {
+    int rc;
+    if ((rc = e->stepPreamble(n))) return rc;
+    cfx_engine::SpawnPlan plan;
+    if ((rc = e->stageSpawns(recs, n, plan))) return rc;
+    e->accountSpawns(recs, n);
+    return e->ring ? e->stepRing(plan) : e->stepDense(plan);
+}
 extern "C" {
 
 int32_t cfx_step(cfx_engine *e, const cfx_spawn *recs, int32_t n) {
@@ -1353,624 +2061,6 @@ int32_t cfx_get_host_stats(cfx_engine *e, cfx_host_stats *out, int32_t reset) {
 const char *cfx_profile_kernel_symbol(cfx_engine *e, int32_t k) {
     return (e && k >= 0 && k < kNumProfKernels && e->slotSymbol[k]) ? e->slotSymbol[k] : "";
 }
-
-}  // extern "C"
-static int32_t stepImpl(cfx_engine *e, const cfx_spawn *recs, int32_t n) {
-    auto fail = [e](const std::string &m) { return e->fail(m); };
-    HIP_TRY(hipSetDevice(e->device));
-    int rc;
-    if ((rc = e->syncTables())) return rc;
-    hipStream_t st = e->stream;
-    // Fail at the step that failed (or the one after): every step leaves its scalars in pinned host memory, so an
-    // overflow code raised by a step the device has already finished is seen here without waiting for anything.
-    if (e->mirrorValid && __atomic_load_n(&e->hMirror->sc.overflow, __ATOMIC_RELAXED) != 0) {
-        DevScalars s;
-        if ((rc = e->readScalars(s))) return rc == CFX_ERR_DEVICE ? CFX_ERR_CAPACITY : rc;
-    }
-    // ---- the host's lead over the device is bounded.  A free-running caller submits a 30x30 step in ~20 us and the device takes
-    //      ~40: unbounded, the stream's backlog grows by half a step per step, and the next call that has to wait for the device
-    //      (a getter, the spawner's priority-collision query) pays for all of it — 4.5 ms behind a 200-step window, 2 ms with 48 steps in flight.  The step's
-    //      commit publishes the number of completed steps in pinned host memory: wait (yielding) while more than kMaxLead steps
-    //      are in flight.  The device is never idle for it — kMaxLead steps of work are queued behind the one it is executing —
-    //      and a caller that synchronises every step never waits here.  (Built while looking for the 45-80 ms "stall" of the
-    //      sustained windows of rounds 4-6, which it did NOT cure: that was the container's CPU quota — bench.py's header.)
-    if (e->mirrorValid && !e->tiled) {
-        constexpr int64_t kMaxLead = 16;  // (16 steps of a 30x30 network = 0.65 ms of queued work: what the next waiting call pays at most)
-        const auto t0 = std::chrono::steady_clock::now();
-        for (unsigned spins = 0;; ++spins) {
-            const int64_t done = (int64_t) (__atomic_load_n(&e->hMirror->progress, __ATOMIC_RELAXED) >> 32);
-            if (done <= 0 || done > e->step || e->step - done <= kMaxLead) break;
-            if ((spins & 63) == 63 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(200)) break;  // (never hang on it)
-            std::this_thread::yield();
-        }
-    }
-    if (e->ring) {
-        if (e->mirrorValid && __atomic_load_n(&e->hMirror->sc.ringNearFull, __ATOMIC_RELAXED) != 0) e->ringGrowRequested = true;
-        if ((rc = e->ringEnsure())) return rc;
-    }
-    if ((rc = e->flowSettle())) return rc;  // (lane flow: a baseline that is due is taken on the state this step starts from)
-    if ((rc = e->tripSettle())) return rc;  // (trip statistics: likewise)
-    if (e->observing && ++e->observeIdle > cfx_engine::kObserveIdle) {  // nobody has read the lane counts for a while
-        e->observing = false;
-        e->hCntValid = false;
-    }
-    if (e->devObserving && ++e->devObserveIdle > cfx_engine::kObserveIdle) e->devObserving = false;
-
-    if (e->lc.on) {
-        if (e->pollPending) return e->fail("cfx_step: the previous lane-change step was not polled (cfx_lane_change_poll)");
-        if (!e->hPoll) return e->fail("cfx_step: cfx_lane_change_supply must be called before a step with lane change");
-        if ((rc = e->ensureVidCap((size_t) e->spawned + (size_t) n + (size_t) e->poolN))) return rc;
-    }
-    // ---- phase 0/1 tail: hand the spawn records to the device
-    SpawnBatchBig batch;  // (the records go with the admission kernel's arguments: up to kAdmitRecs, kd_admit up to kAdmitRecsBig)
-    batch.n = 0;
-    batch.firstNewVid = 0;
-    SpawnBatchMem memBatch{};  // ... or, more of them on the ring layout, in pinned memory
-    bool inMem = false;
-    int memStageUsed = -1;
-    // (the ring layout too: more records than the small batch holds kept the step from riding its commit with the next
-    // admission, and cost a launch of their own; a step with up to kAdmitRecs records runs the small instantiation as before)
-    const int batchRoom = ((e->useTails() && (e->denseForm & 4)) || e->ring) ? kAdmitRecsBig : kAdmitRecs;
-    auto smallBatch = [&batch]() {  // (the kernels that take at most kAdmitRecs records)
-        SpawnBatch b;
-        b.n = batch.n;
-        b.firstNewVid = batch.firstNewVid;
-        b.enterTime = batch.enterTime;
-        for (int i = 0; i < batch.n && i < kAdmitRecs; ++i) {
-            b.lane[i] = batch.lane[i];
-            b.prevWait[i] = batch.prevWait[i];
-            b.route[i] = batch.route[i];
-            b.priority[i] = batch.priority[i];
-            b.firstNext[i] = batch.firstNext[i];
-            b.templ[i] = batch.templ[i];
-            b.vidOff[i] = batch.vidOff[i];
-        }
-        return b;
-    };
-    if (n > 0) {
-        // the batch carries the next n vehicle numbers, each once, in any order (checked in full by the CPU twin)
-        if (recs[0].vid < e->spawned || recs[0].vid >= e->spawned + n)
-            return e->fail("cfx_step: spawn records must continue the dense vid sequence");
-        if ((rc = e->ensureVidCap((size_t) e->spawned + n))) return rc;
-        // ring layout: a step's few records go with kr_admit's arguments (each lane's thread links its own): no launch.  They
-        // fit if they are few, all for lanes of this engine, and all enter at the same time (what a host spawner produces:
-        // Engine::getCurrentTime); record i of the batch is vehicle spawned + i, whatever order they came in
-        bool inArgs = n <= batchRoom;  // (kr_admit / kd_admit / k_admit take the batch)
-        // a custom speed waiting for one of these vehicles has to be in the vehicle table before the admission looks at it:
-        // the records then take the k_spawn_link path and the speeds follow it on the stream (rare: push_vehicle + set_vehicle_speed)
-        std::vector<std::pair<int32_t, double>> customNow;
-        for (const auto &fc : e->futureCustom)
-            if (fc.first < e->spawned + n) customNow.push_back(fc);
-        if (!customNow.empty()) inArgs = false;
-        if (inArgs) {
-            batch.n = (int) n;
-            batch.firstNewVid = (int) e->spawned;
-            batch.enterTime = recs[0].enter_time;
-            int order[kAdmitRecsBig];
-            bool seen[kAdmitRecsBig] = {};
-            for (int i = 0; inArgs && i < n; ++i) {
-                const int64_t off = (int64_t) recs[i].vid - e->spawned;
-                inArgs = off >= 0 && off < n && !seen[off] && recs[i].lane >= -1 && recs[i].enter_time == batch.enterTime &&
-                         recs[i].templ < 32768;
-                if (inArgs) seen[off] = true;
-                order[i] = i;
-            }
-            if (inArgs) {
-                std::sort(order, order + n, [recs](int x, int y) {
-                    return recs[x].lane != recs[y].lane ? recs[x].lane < recs[y].lane : recs[x].vid < recs[y].vid;
-                });
-                for (int j = 0; j < n; ++j) {
-                    const cfx_spawn &r = recs[order[j]];
-                    batch.lane[j] = r.lane;
-                    batch.prevWait[j] = r.prev_wait;
-                    batch.route[j] = r.route;
-                    batch.priority[j] = r.priority;
-                    batch.firstNext[j] = e->firstNextOf(r.lane, r.route);
-                    batch.templ[j] = (int16_t) r.templ;
-                    batch.vidOff[j] = (int16_t) (r.vid - e->spawned);
-                }
-            } else {
-                batch.n = 0;
-            }
-        }
-        // ring layout, more records than the arguments hold (batched environments): the columns go into pinned memory, sorted
-        // by lane, with the offsets of every block of lanes — kr_admit reads its own lanes' records from there (SpawnBatchMem)
-        const int nLaneBlocks = (e->L + kBlock - 1) / kBlock;
-        if (!inArgs && e->ring && n > batchRoom && customNow.empty() && !e->cfg.debug_sync) {
-            inMem = true;
-            const int64_t base = e->spawned;
-            const double t0 = recs[0].enter_time;
-            // a counting sort by block of lanes (bucket 0: the records without a lane here), then each block's few records by
-            // lane — the kernel looks a lane's records up by bisection; a lane's own records may come in any order
-            e->memSeen.assign((size_t) n, 0);
-            e->memBucket.assign((size_t) nLaneBlocks + 2, 0);
-            for (int i = 0; inMem && i < n; ++i) {
-                const int64_t off = (int64_t) recs[i].vid - base;
-                inMem = off >= 0 && off < n && !e->memSeen[(size_t) off] && recs[i].lane >= -1 && recs[i].lane < e->L &&
-                        recs[i].enter_time == t0;
-                if (inMem) {
-                    e->memSeen[(size_t) off] = 1;  // (every vehicle number once)
-                    e->memBucket[(size_t) (recs[i].lane < 0 ? 0 : 1 + recs[i].lane / kBlock) + 1] += 1;
-                }
-            }
-        }
-        if (inMem) {
-            for (int q = 0; q <= nLaneBlocks; ++q) e->memBucket[(size_t) q + 1] += e->memBucket[(size_t) q];  // bucket q starts at [q]
-            e->memOrder.resize((size_t) n);
-            e->memCursor.assign(e->memBucket.begin(), e->memBucket.end() - 1);
-            for (int i = 0; i < n; ++i) e->memOrder[(size_t) e->memCursor[(size_t) (recs[i].lane < 0 ? 0 : 1 + recs[i].lane / kBlock)]++] = i;
-            for (int q = 1; q <= nLaneBlocks; ++q) {
-                int32_t *const o = e->memOrder.data();
-                const int from = e->memBucket[(size_t) q], to = e->memBucket[(size_t) q + 1];
-                if (to - from > 24) {
-                    std::stable_sort(o + from, o + to, [recs](int x, int y) { return recs[x].lane < recs[y].lane; });
-                } else {
-                    for (int j = from + 1; j < to; ++j) {
-                        const int x = o[j], lx = recs[x].lane;
-                        int i = j;
-                        for (; i > from && recs[o[i - 1]].lane > lx; --i) o[i] = o[i - 1];
-                        o[i] = x;
-                    }
-                }
-            }
-            const size_t words = (size_t) 7 * (size_t) n + (size_t) nLaneBlocks + 1;
-            if (words > e->memStageWords) {
-                e->stallCause |= CFX_STALL_STAGE_GROW;
-                HIP_TRY(hipStreamSynchronize(st));
-                const size_t nc = std::max<size_t>(words * 2, 4096);
-                for (int i = 0; i < cfx_engine::kStages; ++i) {
-                    if (e->hMemStage[i]) HIP_TRY(hipHostFree(e->hMemStage[i]));
-                    e->hMemStage[i] = nullptr;
-                    HIP_TRY(hipHostMalloc((void **) &e->hMemStage[i], nc * sizeof(int32_t), hipHostMallocDefault));
-                    if (!e->memStageEvent[i]) HIP_TRY(hipEventCreateWithFlags(&e->memStageEvent[i], hipEventDisableTiming));
-                    e->memStageBusy[i] = false;
-                }
-                e->memStageWords = nc;
-            }
-            const int si = e->memStageIdx;
-            e->memStageIdx = (si + 1) % cfx_engine::kStages;
-            if (e->memStageBusy[si]) HIP_TRY(hipEventSynchronize(e->memStageEvent[si]));
-            int32_t *const w = e->hMemStage[si];
-            int32_t *const cLane = w, *const cPrev = w + n, *const cRoute = w + 2 * (size_t) n, *const cPrio = w + 3 * (size_t) n,
-                           *const cNext = w + 4 * (size_t) n, *const cTempl = w + 5 * (size_t) n, *const cOff = w + 6 * (size_t) n,
-                           *const cBlock = w + 7 * (size_t) n;
-            for (int j = 0; j < n; ++j) {
-                const cfx_spawn &r = recs[e->memOrder[(size_t) j]];
-                cLane[j] = r.lane;
-                cPrev[j] = r.prev_wait;
-                cRoute[j] = r.route;
-                cPrio[j] = r.priority;
-                cNext[j] = e->firstNextOf(r.lane, r.route);
-                cTempl[j] = r.templ;
-                cOff[j] = (int32_t) (r.vid - e->spawned);
-            }
-            for (int q = 0; q <= nLaneBlocks; ++q) cBlock[q] = e->memBucket[(size_t) q + 1];  // block q's records: bucket q + 1
-            memBatch.n = (int) n;
-            memBatch.firstNewVid = (int) e->spawned;
-            memBatch.enterTime = recs[0].enter_time;
-            memBatch.lane = cLane;
-            memBatch.prevWait = cPrev;
-            memBatch.route = cRoute;
-            memBatch.priority = cPrio;
-            memBatch.firstNext = cNext;
-            memBatch.templ = cTempl;
-            memBatch.vidOff = cOff;
-            memBatch.blockOff = cBlock;
-            memBatch.nLaneBlocks = nLaneBlocks;
-            memStageUsed = si;
-        } else if (inArgs) {
-            // (nothing to launch)
-        } else {
-            if ((rc = e->settle(false))) return rc;  // (k_spawn_link looks at what the previous step's commit leaves)
-            if ((size_t) n > e->recCap) {
-                size_t nc = std::max<size_t>((size_t) n * 2, 1024);
-                if ((rc = e->grow(&e->dRecs, 0, nc))) return rc;
-                e->recCap = nc;
-            }
-            if ((size_t) n > e->stageCap) {
-                e->stallCause |= CFX_STALL_STAGE_GROW;
-                HIP_TRY(hipStreamSynchronize(st));
-                size_t nc = std::max<size_t>((size_t) n * 2, 1024);
-                for (int i = 0; i < cfx_engine::kStages; ++i) {
-                    if (e->hStage[i]) HIP_TRY(hipHostFree(e->hStage[i]));
-                    HIP_TRY(hipHostMalloc((void **) &e->hStage[i], nc * sizeof(cfx_spawn), hipHostMallocDefault));
-                    if (!e->stageEvent[i]) HIP_TRY(hipEventCreateWithFlags(&e->stageEvent[i], hipEventDisableTiming));
-                    e->stageBusy[i] = false;
-                }
-                e->stageCap = nc;
-            }
-            const int si = e->stageIdx;
-            e->stageIdx = (si + 1) % cfx_engine::kStages;
-            if (e->stageBusy[si]) HIP_TRY(hipEventSynchronize(e->stageEvent[si]));
-            memcpy(e->hStage[si], recs, (size_t) n * sizeof(cfx_spawn));
-            // the kernel reads the pinned (device-visible) staging buffer itself: no separate copy launch
-            e->launchNamed(PK_SPAWN, "k_spawn_link", k_spawn_link, dim3(gridFor(n)), dim3(kBlock), (const cfx_spawn *) e->hStage[si], (int) n,
-                      (int) e->spawned, e->vt, e->waitHead, e->lc);
-            HIP_TRY(hipEventRecord(e->stageEvent[si], st));
-            e->stageBusy[si] = true;
-            if (!customNow.empty()) {  // Vehicle::setCustomSpeed on a vehicle still in its waiting buffer (cfx_set_vehicle_speed)
-                const uint8_t one = 1;
-                for (const auto &fc : customNow) {
-                    HIP_TRY(hipMemcpyAsync(e->vt.customSpeed + fc.first, &fc.second, sizeof(double), hipMemcpyHostToDevice, st));
-                    HIP_TRY(hipMemcpyAsync(e->vt.pendingCustom + fc.first, &one, 1, hipMemcpyHostToDevice, st));
-                }
-                HIP_TRY(hipStreamSynchronize(st));  // (the sources live on this frame)
-            }
-        }
-        e->spawned += n;
-    }
-    for (const auto &fc : e->futureCustom)  // (what this batch did not create was not a vehicle of this step: counted, not silent)
-        if (fc.first >= e->spawned) e->droppedFutureSpeeds += 1;
-    e->futureCustom.clear();
-    // ---- slot capacity.  Two host-side upper bounds of the vehicles that can be running after this step:
-    //   (a) spawned - finished (as of the last read)           — tight while nobody queues for long;
-    //   (b) running (as of the last read) + what can have been admitted since: at most one vehicle per step on every
-    //       lane that has ever had a vehicle queued, plus halo migrants — stays small when entry lanes saturate and the
-    //       waiting queues grow without bound (they hold vehicle-table entries, not slots).
-    // When the smaller of the two outgrows the buffers, the true count is read back and the buffers grow only if needed.
-    for (int i = 0; i < n; ++i) {
-        if (!cfx_engine::dyadic(recs[i].enter_time)) e->timesDyadic = false;
-        const int lane = recs[i].lane;
-        if (lane >= 0 && !e->laneQueued[lane]) {
-            e->laneQueued[lane] = 1;
-            e->nQueueLanes += 1;
-        }
-        e->spawnedHere += lane >= 0;
-    }
-    e->liveUpper += e->nQueueLanes;
-
-    if (e->ring) {
-        // ---- ring layout: admit, action (+ notify sources), cross, commit — no scan, no scatter
-        RingCtx c = e->rctx(true);
-        const bool dbg = e->cfg.debug_sync != 0;  // developer aid: name the kernel that faults
-#define RING_CHECK(name)                                                                                          \
-    if (dbg) {                                                                                                    \
-        fprintf(stderr, "[cfx ring] step %lld: %s\n", (long long) e->step, name);                                 \
-        hipError_t er = hipStreamSynchronize(st);                                                                 \
-        if (er != hipSuccess) return e->fail(std::string("ring step: ") + name + ": " + hipGetErrorString(er));   \
-    }
-        RING_CHECK("before the step")
-        const unsigned long long pr = __atomic_load_n(&e->hMirror->progress, __ATOMIC_RELAXED);
-        // running vehicles as of the last step the device has completed (stale by the few steps the host runs ahead):
-        // only sizes the cross phase's grid and picks its organisation
-        const size_t activeEst = (size_t) (pr & 0xFFFFFFFFu) + (size_t) e->nQueueLanes * 4;
-        const bool useBig = e->cross2 >= 0 ? e->cross2 == 1 : activeEst > 240000;  // which form of the cross phase (§4)
-        // This step's commit rides with the next step's admission (one launch less per step) where the step runs kr_cross,
-        // which then advances the lights; the previous step's, if it is still pending, goes with this step's admission.
-        const bool deferCommit = e->ringMerge && !dbg && !e->tiled && !e->observing && !e->devObserving && !e->flowOn && !e->tripOn;  // (a caller that reads the lane counts after every step wants the commit now; so do the lane-flow and the trip tick)
-        // tiling: the previous step's halo import, if cfx_halo_wait left it to this launch
-        const RingHaloIn hin = e->haloImportPending ? e->pendingImport : RingHaloIn{};
-        e->haloImportPending = false;
-        if (e->commitPending) {
-            e->commitPending = false;
-            int nStatPrev = 1;
-            const RingCommit rkPrev = e->commitArgs(activeEst, true, &nStatPrev);
-            if (inMem)
-                e->launchNamed(PK_ADMIT, "kr_admit<true, kBlock, SpawnBatchMem>", kr_admit<true, kBlock, SpawnBatchMem>, dim3(gridFor(e->D) + nStatPrev), dim3(kBlock), e->rctx(true, e->step - 1, e->rcur ^ 1),
-                          e->admitStep, e->waitHead, e->vt, e->sc, memBatch, rkPrev, RingHaloIn{});
-            else if (batch.n > kAdmitRecs)
-                e->launchNamed(PK_ADMIT, "kr_admit<true, kAdmitRecsBig>", kr_admit<true, kAdmitRecsBig>, dim3(gridFor(e->D) + nStatPrev), dim3(kBlock), e->rctx(true, e->step - 1, e->rcur ^ 1),
-                          e->admitStep, e->waitHead, e->vt, e->sc, batch, rkPrev, RingHaloIn{});
-            else
-                e->launchNamed(PK_ADMIT, "kr_admit<true>", kr_admit<true>, dim3(gridFor(e->D) + nStatPrev), dim3(kBlock), e->rctx(true, e->step - 1, e->rcur ^ 1),
-                          e->admitStep, e->waitHead, e->vt, e->sc, smallBatch(), rkPrev, RingHaloIn{});
-        } else {
-            if (inMem)
-                e->launchNamed(PK_ADMIT, "kr_admit<false, kBlock, SpawnBatchMem>", kr_admit<false, kBlock, SpawnBatchMem>, dim3(gridFor(e->D)), dim3(kBlock), c, e->admitStep, e->waitHead, e->vt, e->sc, memBatch, RingCommit{}, hin);
-            else if (batch.n > kAdmitRecs)
-                e->launchNamed(PK_ADMIT, "kr_admit<false, kAdmitRecsBig>", kr_admit<false, kAdmitRecsBig>, dim3(gridFor(e->D)), dim3(kBlock), c, e->admitStep, e->waitHead, e->vt, e->sc, batch, RingCommit{}, hin);
-            else
-                e->launchNamed(PK_ADMIT, "kr_admit<false>", kr_admit<false>, dim3(gridFor(e->D)), dim3(kBlock), c, e->admitStep, e->waitHead, e->vt, e->sc, smallBatch(), RingCommit{}, hin);
-        }
-        if (memStageUsed >= 0) {  // (the kernel reads the pinned buffer itself: free again when this launch is through)
-            HIP_TRY(hipEventRecord(e->memStageEvent[memStageUsed], st));
-            e->memStageBusy[memStageUsed] = true;
-        }
-        RING_CHECK("kr_admit")
-        RingJob *const jobRecs = useBig ? nullptr : e->rJobRecs;  // k_cross2 starts from the slots: no job records then
-        RingOut ro{c.kinN, c.blkW, e->rScratch, e->rMovers, e->sc, e->rFinKey, e->rFinVid, e->rFinCap, e->finCount};
-        JobQueue jq{e->jobCount, e->rJobs, e->rJobCap, &e->sc->overflow};
-        {
-            // One workgroup = B threads over G lanes (or B laneLinks).  G is picked so that a block's vehicles fit one pass
-            // (B - 1) with room for uneven lanes; small networks take small blocks (every block resident at once, the step
-            // is bound by the slowest block's chain), large ones full blocks (throughput).
-            // cfx_config::ring_lanes_per_wave = G + 1000 * (B / 256) overrides both (developer knob; B = 256 or 512);
-            // + 10000 forces the wave form of the action kernel (kw_action; the default above 240 k vehicles), + 20000 the
-            // block form (kr_action; the default below).
-            int G = e->ringG, Bsel = 256;
-            const int form = (e->cfg.ring_lanes_per_wave / 10000) % 10;
-            const bool blockForm = form == 2 || (form == 0 && !(useBig || activeEst > 240000));
-            const int want = e->cfg.ring_lanes_per_wave % 10000;
-            if (want > 0) {
-                G = std::max(1, want % 1000);
-                Bsel = want >= 2000 ? 512 : 256;
-            } else if (useBig || activeEst > 240000) {
-                G = 28;  // many rounds of blocks anyway: full blocks, a second chunk where the lanes are dense (throughput)
-            } else if (e->mirrorValid) {
-                // adapt to the traffic: the densest block of a recent step (pinned mirror, possibly a few steps old) should
-                // fit one pass with some room; results do not depend on G
-                const int maxT = __atomic_load_n(&e->hMirror->sc.actionMaxT, __ATOMIC_RELAXED);
-                if (e->ringHold > 0) {
-                    e->ringHold -= 1;  // (the mirror lags a few steps behind: let a change show before the next one)
-                } else if (maxT > Bsel - 1) {
-                    e->ringG = std::max(4, e->ringG - 1);
-                    e->ringCalm = 0;
-                    e->ringHold = 8;
-                } else if (maxT == 0 && e->ringG < 16) {  // no block above 3/4 of a pass for a while: fuller blocks
-                    if (++e->ringCalm >= 256) {
-                        e->ringG += 1;
-                        e->ringCalm = 0;
-                    }
-                } else {
-                    e->ringCalm = 0;
-                }
-                G = e->ringG;
-            }
-            // + 30000: the list form (kr_index + kl_action; the default where the cross phase runs k_cross2)
-            // (the lane-walking forms cost per lane, the list per vehicle plus 8 to 12 us for the list: 30x30, 10.8 k lanes, 90 k
-            //  vehicles: 41.0 us per step in block form, 49.0 with the list; 100x100, 120 k lanes, 72 k vehicles: 97.1 and 54.7)
-            const bool listForm = form == 3 || form == 6 || (form == 0 && (useBig || activeEst > 240000 || e->L > 20000));
-            if (listForm) {
-                // a TRUE bound of the vehicles this step can list (the list and the launch are sized by it): what the device
-                // reported after the last step it has completed plus one admission per queueing lane and step since
-                const int64_t done = (int64_t) (pr >> 32);
-                // (a tile: plus what the halo can have brought in since — its count is as of the commit, before that step's import)
-                if (done > 0 && done <= e->step)
-                    e->liveUpper = std::min(e->liveUpper, (int64_t) (pr & 0xFFFFFFFFu) + e->nQueueLanes * (e->step + 1 - done) +
-                                                              (e->tiled ? (int64_t) e->halo.nImport * CFX_HALO_MAX_MIGRANTS * (e->step + 2 - done) +
-                                                                              2 * (int64_t) e->halo.nGhost : 0));
-                const size_t listBound = (size_t) std::min<int64_t>(e->liveUpper, (int64_t) e->ringSlots);
-                const size_t needList = (listBound + kListBlock - 1) / kListBlock * kListBlock + kListBlock;
-                if (needList > e->rListCap) {
-                    e->stallCause |= CFX_STALL_LIST_GROW;
-                    e->hostStats.table_grows_total += 1;
-                    const size_t nc = std::max(needList + needList / 4, e->rListCap * 2) / kListBlock * kListBlock;
-                    int rc = e->growDeferred(&e->rList, 0, nc);  // (rebuilt every step: nothing to keep)
-                    if (rc) return rc;
-                    e->rListCap = nc;
-                    if (!e->rListCount) {
-                        if ((rc = e->allocRaw(&e->rListCount, 2)) || (rc = e->allocRaw(&e->rIdxGranules, (size_t) gridFor(e->D)))) return rc;
-                        HIP_TRY(hipMemsetAsync(e->rIdxGranules, 0, (size_t) gridFor(e->D) * sizeof(unsigned long long), st));
-                        HIP_TRY(hipMemsetAsync(e->rListCount, 0, 2 * sizeof(int32_t), st));
-                    }
-                }
-                const int nVehBlocks = (int) (needList / kListBlock);  // (every entry a block of the launch reads exists)
-                const int nLL = (e->K + kListBlock - 1) / kListBlock;
-                const int nIdxTiles = (int) ((e->D + kIndexTile - 1) / kIndexTile);
-                // (1024 threads: two blocks per CU.  Form 6 hands the tiles out by ticket whatever their number: the path of networks
-                //  above half a million drivables, for the tests)
-                int32_t *const idxTicket = (nIdxTiles > kScanResidentTiles || form == 6) ? e->rListCount + 1 : nullptr;
-                e->launchNamed(PK_SCAN, "kr_index", kr_index, dim3(nIdxTiles), dim3(kIndexBlock), c, e->rIdxGranules, idxTicket, (unsigned) (e->step + 1),
-                          // (the capacity the kernel checks is what THIS step's action launch covers, not the allocation — which has
-                          //  25 % of headroom and never shrinks: entries beyond the launch would never take their step, unflagged)
-                          e->rList, (int) std::min<size_t>(e->rListCap, (size_t) nVehBlocks * kListBlock), e->rListCount, e->sc);
-                RING_CHECK("kr_index")
-                const RingHist rh = e->takeHist(nVehBlocks + nLL);  // (the last step's Lane::history: trailing blocks of this launch)
-                const int nHist = rh.h.num ? (e->L + kListBlock - 1) / kListBlock : 0;
-                e->launchNamed(PK_ACTION, e->tiled ? "kl_action<true>" : "kl_action", e->tiled ? kl_action<true> : kl_action<false>, dim3(nVehBlocks + nLL + nHist), dim3(kListBlock), c, ro, jq, jobRecs, (const int4 *) e->rList,
-                          (const int32_t *) e->rListCount, nVehBlocks, idxTicket, rh);
-            } else {
-            G = std::min(G, Bsel);
-            const int nLaneBlocks = (e->L + G - 1) / G, nLLBlocks = (e->K + Bsel - 1) / Bsel;
-            // (first form: as many blocks again at the end of the grid compute the laneLinks' notify sources)
-            const RingHist rh = e->takeHist(nLaneBlocks + 2 * nLLBlocks);  // (the last step's Lane::history: trailing blocks of this launch)
-            const dim3 grid(nLaneBlocks + 2 * nLLBlocks + (rh.h.num ? (e->L + Bsel - 1) / Bsel : 0)), block(Bsel);
-            if (blockForm) {
-                if (e->tiled) {  // (ghost lanes: the instantiations that know about frozen proxies)
-                    if (Bsel == 256) e->launchNamed(PK_ACTION, "kr_action<256, true>", kr_action<256, true>, grid, block, c, ro, jq, jobRecs, G, nLaneBlocks, nLLBlocks, rh);
-                    else e->launchNamed(PK_ACTION, "kr_action<512, true>", kr_action<512, true>, grid, block, c, ro, jq, jobRecs, G, nLaneBlocks, nLLBlocks, rh);
-                } else if (Bsel == 256) e->launchNamed(PK_ACTION, "kr_action<256>", kr_action<256>, grid, block, c, ro, jq, jobRecs, G, nLaneBlocks, nLLBlocks, rh);
-                else e->launchNamed(PK_ACTION, "kr_action<512>", kr_action<512>, grid, block, c, ro, jq, jobRecs, G, nLaneBlocks, nLLBlocks, rh);
-            } else {
-                if (e->tiled) {
-                    if (Bsel == 256) e->launchNamed(PK_ACTION, "kw_action<256, true>", kw_action<256, true>, grid, block, c, ro, jq, jobRecs, G, nLaneBlocks, nLLBlocks, rh);
-                    else e->launchNamed(PK_ACTION, "kw_action<512, true>", kw_action<512, true>, grid, block, c, ro, jq, jobRecs, G, nLaneBlocks, nLLBlocks, rh);
-                } else if (Bsel == 256) e->launchNamed(PK_ACTION, "kw_action<256>", kw_action<256>, grid, block, c, ro, jq, jobRecs, G, nLaneBlocks, nLLBlocks, rh);
-                else e->launchNamed(PK_ACTION, "kw_action<512>", kw_action<512>, grid, block, c, ro, jq, jobRecs, G, nLaneBlocks, nLLBlocks, rh);
-            }
-            }
-        }
-        RING_CHECK("kr_action")
-        if (dbg) {
-            HIP_TRY(hipMemsetAsync(e->laneOut, 0, 8 * sizeof(int32_t), st));
-            hipLaunchKernelGGL(kr_validate, dim3(gridFor(std::max(e->D, 16))), dim3(kBlock), 0, st, c, jq, (int) e->spawned,
-                               (int) e->hRouteStart.size() - 1, (int) e->ringSlots, e->laneOut);
-            int32_t rep[5] = {0, 0, 0, 0, 0};
-            HIP_TRY(hipMemcpyAsync(rep, e->laneOut, sizeof rep, hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipStreamSynchronize(st));
-            if (rep[0]) {
-                char buf[160];
-                snprintf(buf, sizeof buf, "ring invariant %d violated at step %lld: %d %d %d %d", rep[0], (long long) e->step, rep[1], rep[2], rep[3], rep[4]);
-                return e->fail(buf);
-            }
-        }
-        if (useBig)
-            e->launchNamed(PK_CROSS, "k_cross2<false, RingCtx, RingOut>", k_cross2<false, RingCtx, RingOut>,
-                      dim3((int) std::min<size_t>(std::max<size_t>(64, (activeEst / 4 + 15) / 16), (size_t) CFX_RING_CROSS2_WAVES * e->nCU)),  // (5 blocks per CU: 96 registers)
-                      dim3(kCross2Block), c, ro, jq, RingLights{e->curPhase, e->remain, (deferCommit && !e->cfg.rl_traffic_light) ? 1 : 0});
-        else
-        {
-            // one 16-lane group per queued vehicle; sized by the job count of the last step the device has reported (every
-            // block of the grid pays the prologue, and blocks that find no job still take a wavefront slot for it)
-            size_t groups = activeEst / 4;
-            if (e->mirrorValid) {
-                const int lastJobs = __atomic_load_n(&e->hMirror->sc.nCrossJobs, __ATOMIC_RELAXED);
-                if (lastJobs > 0) groups = std::min<size_t>(groups, (size_t) lastJobs + (size_t) lastJobs / 4 + 256);
-            }
-            e->launchNamed(PK_CROSS, "kr_cross", kr_cross,
-                      dim3((int) std::min<size_t>(std::max<size_t>(64, (groups * 16 + kCrossBlock - 1) / kCrossBlock), 32768)),
-                      dim3(kCrossBlock), c, ro, jq, (const RingJob *) e->rJobRecs,
-                      RingLights{e->curPhase, e->remain, (deferCommit && !e->cfg.rl_traffic_light) ? 1 : 0});
-        }
-        RING_CHECK("k_cross")
-        if (deferCommit) {
-            e->commitPending = true;  // launched by the next cfx_step (with its admission) or by settle()
-        } else {
-            int nStat = 1;
-            const RingCommit rk = e->commitArgs(activeEst, false, &nStat);
-            e->launchNamed(PK_COMMIT, "kr_commit", kr_commit, dim3(gridStride((size_t) std::max(e->D, std::max(e->I, e->nMaskWords))) + nStat), dim3(kBlock), c, rk, e->vt,
-                           e->ringHalo());
-            RING_CHECK("kr_commit")
-        }
-#undef RING_CHECK
-        HIP_TRY(hipGetLastError());
-        e->rcur ^= 1;
-        e->step += 1;
-        e->mirrorValid = !e->tiled;
-        e->histPending = e->hist.num != 0;  // (this step's Lane::history: with the next action launch, or settle() — on a tile behind the step's halo import)
-        if (e->flowOn && (rc = e->flowTick(false))) return rc;
-        if (e->tripOn) return e->tripTick(false);
-        return CFX_OK;
-    }
-    const int64_t spare = e->tiled ? e->spareTotal : (int64_t) e->L;
-    auto bound = [e]() {
-        const int64_t a = e->spawnedHere - (e->finishedKnown - e->finishedOffset);
-        return e->tiled ? e->liveUpper : std::min(a, e->liveUpper);
-    };
-    const int64_t shadowRoom = e->lc.on ? e->poolN : 0;  // this step's shadows
-    // ... and the lanes that get them move behind the layout's end (k_lc_insert), each at most once per step, with the shadows
-    // they receive: all running vehicles plus the step's shadows is a true bound of what can move (round 3 reserved a heuristic
-    // quarter of the vehicles, which a dense jam in which every lane gets a shadow could exceed: ADVICE round 3)
-    auto moveRoom = [e, &bound, shadowRoom]() { return e->lc.on ? bound() + shadowRoom + 64 : (int64_t) 0; };
-    size_t need = (size_t) (bound() + spare + shadowRoom + moveRoom()) + 1;
-    if (need > e->slotCap && !e->tiled) {
-        // the device's own count as of the last step it has completed, read without waiting for it
-        const unsigned long long pr = __atomic_load_n(&e->hMirror->progress, __ATOMIC_RELAXED);
-        const int64_t done = (int64_t) (pr >> 32);
-        if (done > 0 && done <= e->step) {
-            // since then: at most one admission per queueing lane and step, and (lane change) that step's shadows
-            e->liveUpper = std::min(e->liveUpper, (int64_t) (pr & 0xFFFFFFFFu) + (e->nQueueLanes + shadowRoom) * (e->step + 1 - done));
-            need = (size_t) (bound() + spare + shadowRoom + moveRoom()) + 1;
-        }
-    }
-    if (need > e->slotCap) {
-        DevScalars s;
-        if ((rc = e->readScalars(s))) return rc;  // refreshes finishedKnown too
-        e->liveUpper = s.active + 2 * (int64_t) e->halo.nGhost + e->nQueueLanes;
-        need = (size_t) (bound() + spare + shadowRoom + moveRoom()) + 1;
-        if ((rc = e->ensureSlotCap(need))) return rc;
-    }
-
-    if (e->lc.on) {  // per-step fields of the lane-change context
-        e->lc.firstShadowVid = (int) e->spawned;
-        e->lc.pool = e->hPool;  // pinned: k_lc_insert reads the few priorities it hands out straight from the host's buffer
-        e->lc.insCap = e->poolN;
-    }
-    const bool tails = e->useTails();
-    if (tails && !e->dTailNow) {
-        if ((rc = e->allocRaw(&e->dTail[0], (size_t) e->D))) return rc;
-        if ((rc = e->allocRaw(&e->dTail[1], (size_t) e->D))) return rc;
-        if ((rc = e->allocRaw(&e->dTailNow, (size_t) e->D))) return rc;
-        if ((rc = e->allocRaw(&e->dGate4, (size_t) std::max(e->K, 1)))) return rc;
-    }
-    StepCtx c = e->ctx();
-    if (tails && !e->tailsValid) {  // after a reset / cfx_load_state: the records of the generation the step starts from
-        hipLaunchKernelGGL(kd_init_tails, dim3(gridFor(e->D)), dim3(kBlock), 0, st, c, e->dTail[0], e->dTail[1]);
-        e->tailsValid = true;
-    }
-    // grids: the slots the layout can hold; with lane change the room reserved for moving lanes lies behind them and is
-    // covered by the kernels' stride loops in the (rare) step that uses much of it
-    const size_t slotBound = std::min(need - (size_t) moveRoom() + (e->lc.on ? (size_t) 4096 : 0), e->slotCap);
-    // Two organisations of the cross walk: for latency (fewest dependent rounds per vehicle) and, for large networks, for
-    // throughput (far fewer wave-rounds per vehicle).  They break even at ~220 k slots on the MI355X.
-    const bool useBig = e->cross2 >= 0 ? e->cross2 == 1 : slotBound > 240000;
-    if (e->lc.on && !e->lcSegValid) {  // after a reset / cfx_load_state
-        hipLaunchKernelGGL(k_lc_naive, dim3(gridStride(slotBound)), dim3(kBlock), 0, st, c);
-        e->lcSegValid = true;
-    }
-    if (tails && c.laneAdmit) {
-        if (!e->gatePhase) {
-            if ((rc = e->allocRaw(&e->gatePhase, (size_t) 2 * std::max(e->I, 1)))) return rc;
-            HIP_TRY(hipMemsetAsync(e->gatePhase, 0xFF, (size_t) 2 * std::max(e->I, 1) * sizeof(int32_t), st));
-        }
-        if (batch.n > kAdmitRecs)
-            e->launchNamed(PK_ADMIT, "kd_admit<true, kAdmitRecsBig>", kd_admit<true, kAdmitRecsBig>, dim3(gridFor(e->L)), dim3(kBlock), c, e->admitStep, e->waitHead, e->vt, e->cs, batch, e->gatePhase);
-        else
-            e->launchNamed(PK_ADMIT, "kd_admit<true, kAdmitRecs>", kd_admit<true, kAdmitRecs>, dim3(gridFor(e->L)), dim3(kBlock), c, e->admitStep, e->waitHead, e->vt, e->cs, smallBatch(), e->gatePhase);
-    } else if (tails) {
-        if (batch.n > kAdmitRecs)
-            e->launchNamed(PK_ADMIT, "kd_admit<false, kAdmitRecsBig>", kd_admit<false, kAdmitRecsBig>, dim3(gridFor(e->D)), dim3(kBlock), c, e->admitStep, e->waitHead, e->vt, e->cs, batch, (int32_t *) nullptr);
-        else
-            e->launchNamed(PK_ADMIT, "kd_admit<false, kAdmitRecs>", kd_admit<false, kAdmitRecs>, dim3(gridFor(e->D)), dim3(kBlock), c, e->admitStep, e->waitHead, e->vt, e->cs, smallBatch(), (int32_t *) nullptr);
-    } else e->launchNamed(PK_ADMIT, "k_admit", k_admit, dim3(gridFor(e->D)), dim3(kBlock), c, e->admitStep, e->waitHead, e->vt, e->cs, smallBatch());
-    ActionOut ao{e->ab, e->cs, e->vt, e->sc, e->finList, (int) e->slotCap, e->finCount};
-    if (e->lc.on) {
-        // Engine::nextStep engine.cpp:571-575: initSegments, planLaneChange (+ scheduleLaneChange), and the order rebuilt
-        // with the step's shadows in place (cfx_lc_kernels.h)
-        const bool dbgSync = e->cfg.debug_sync != 0;  // developer aid: name the kernel that faults
-#define LC_CHECK(name)                                                                                     \
-    if (dbgSync) {                                                                                         \
-        hipError_t er = hipStreamSynchronize(st);                                                          \
-        if (er != hipSuccess) return e->fail(std::string("lane change: ") + name + ": " + hipGetErrorString(er)); \
-    }
-        hipLaunchKernelGGL(k_lc_plan, dim3(gridStride(slotBound)), dim3(kBlock), 0, st, c);
-        LC_CHECK("k_lc_plan")
-        hipLaunchKernelGGL(k_lc_schedule, dim3(e->R), dim3(64), 0, st, c, e->sc, (const int32_t *) e->vt.priority);
-        LC_CHECK("k_lc_schedule")
-        hipLaunchKernelGGL(k_lc_insert, dim3(256), dim3(64), 0, st, c, e->vt, e->sc, e->hPoll, e->oldToNew, e->segStart[e->cur].p,
-                           e->cnt[e->cur].p, (int) e->slotCap);
-        LC_CHECK("k_lc_insert")
-        HIP_TRY(hipEventRecord(e->pollEvent, st));  // cfx_lane_change_poll waits for this, not for the whole step
-        e->pollPending = true;
-        HIP_TRY(hipGetLastError());
-        c.admissionsVisible = 1;
-        // the leader / gap pass between planLaneChange and getAction takes a history record too (engine.cpp:571-575, 429-442);
-        // k_lc_insert has moved the lanes that got shadows: the context is taken anew
-        if (e->hist.num && !e->tiled) hipLaunchKernelGGL(k_lane_history, dim3(gridFor(e->L)), dim3(kBlock), 0, st, e->ctx(), e->hist);
-    }
-    const int nxt = e->cur ^ 1;
-    // Two organisations of the cross walk: for latency (fewest dependent rounds per vehicle) and, for large networks, for
-    // throughput (far fewer wave-rounds per vehicle).  They break even at ~220 k slots on the MI355X.
-    JobQueue jq{e->jobCount, e->crossJobs, (int) e->slotCap, &e->sc->overflow};
-    {
-        const int nVehBlocks = (int) std::min<size_t>(std::max<size_t>(1, (slotBound + kActBlock - 1) / kActBlock), 8192);
-        const int nLLBlocks = (e->K + kActBlock - 1) / kActBlock;
-        if (tails) {
-            const int nv = (int) ((slotBound + kDenseActBlock - 1) / kDenseActBlock), nl = (e->K + kDenseActBlock - 1) / kDenseActBlock;
-            e->launchNamed(PK_ACTION, "kd_action", kd_action, dim3(nv + nl), dim3(kDenseActBlock), c, ao, jq, nv);
-        }
-        else e->launchNamed(PK_ACTION, e->lc.on ? "k_action<true>" : "k_action<false>", e->lc.on ? k_action<true> : k_action<false>, dim3(nVehBlocks + nLLBlocks), dim3(kActBlock), c, ao, jq,
-                       nVehBlocks);
-    }
-    if (useBig)
-        // (the blocks the chip holds at once — 7 per CU: the kernel's LDS — or fewer for a short queue: the kernel sizes its batches)
-        e->launchNamed(PK_CROSS, e->lc.on ? "k_cross2<true>" : "k_cross2<false>", e->lc.on ? k_cross2<true> : k_cross2<false>, dim3((int) std::min<size_t>(std::max<size_t>(1, (slotBound + 15) / 16), (size_t) CFX_CROSS2_BLOCKS_PER_CU * e->nCU)),
-                  dim3(kCross2Block), c, ao, jq, RingLights{nullptr, nullptr, 0});
-    else
-        e->launchNamed(PK_CROSS, e->lc.on ? "k_cross<true>" : "k_cross<false>", e->lc.on ? k_cross<true> : k_cross<false>,
-                  dim3((int) std::min<size_t>(std::max<size_t>(1, (slotBound * 16 + kCrossBlock - 1) / kCrossBlock), 32768)),
-                  dim3(kCrossBlock), c, ao, jq);
-    if (e->lc.on) {
-        hipLaunchKernelGGL(k_lc_resolve, dim3((int) std::min<size_t>(std::max<size_t>(1, (slotBound / 8 + kBlock - 1) / kBlock), 1024)),
-                           dim3(kBlock), 0, st, c, ao, e->oldToNew2);
-        hipLaunchKernelGGL(k_lc_resolve_rest, dim3(1), dim3(kBlock), 0, st, c, ao, e->oldToNew2);
-    }
-    int32_t *const scanTicket = e->nScanBlocks > kScanResidentTiles ? e->scanTicket : nullptr;
-    e->launchNamed(PK_SCAN, "k_scan", k_scan, dim3(e->nScanBlocks), dim3(kBlock), (int) e->D, (int) e->L, (const int32_t *) e->cnt[e->cur].p, e->cs,
-              e->scanGranules, scanTicket, (unsigned) (e->step + 1), e->segStart[nxt].p, e->cnt[nxt].p, e->gen[nxt].vid,
-              e->gen[nxt].drv, e->sc, e->net.laneSpare, (const int32_t *) e->admitStep, (int) e->step, e->waitHead, e->vt,
-              e->net.laneGhost, (const int2 *) e->admitRec, e->publishTo(), e->lc.on ? 1 : 0);
-    // finish statistics: one extra block per 64 k slots (a rank sort of the step's finishers, see finishStatistics)
-    const int nStat = (int) std::min<size_t>(std::max<size_t>(1, slotBound >> 16), 64);
-    e->launchNamed(PK_SCATTER, e->lc.on ? "k_scatter<true>" : "k_scatter<false>", e->lc.on ? k_scatter<true> : k_scatter<false>,
-              dim3(gridStride(std::max<size_t>(slotBound, (size_t) std::max(e->I, e->nMaskWords))) + nStat), dim3(kBlock), c, e->ab,
-              e->cs, e->gen[nxt], (const int32_t *) e->segStart[nxt].p, e->oldToNew, e->curPhase, e->remain,
-              (int) e->cfg.rl_traffic_light, (int) e->nMaskWords, scanTicket, e->vt, e->sc, (const int32_t *) e->finList,
-              e->finTerm, (int) e->slotCap, e->jobCount, e->tiled ? (HostMirror *) nullptr : e->hMirror, e->finTicket, nStat,
-              e->exactTimes() ? 1 : 0, (const int32_t *) e->cnt[nxt].p, e->finCount);
-    HIP_TRY(hipGetLastError());
-    e->cur = nxt;
-    e->step += 1;
-    e->mirrorValid = !e->tiled;
-    if (e->hist.num && !e->tiled) {  // Lane::updateHistory, on the committed state
-        hipLaunchKernelGGL(k_lane_history, dim3(gridFor(e->L)), dim3(kBlock), 0, st, e->ctx(), e->hist);
-        HIP_TRY(hipGetLastError());
-    }
-    if (e->flowOn && (rc = e->flowTick(false))) return rc;
-    if (e->tripOn) return e->tripTick(false);
-    return CFX_OK;
-}
-extern "C" {
 
 // Lane::history as the ABI shows it: lane-major, oldest record first (the device keeps a ring per lane, record-major)
 int32_t cfx_get_lane_history(cfx_engine *e, cfx_lane_history *out) {

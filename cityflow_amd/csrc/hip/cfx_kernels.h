@@ -966,7 +966,7 @@ struct PushJob {
     }
 };
 
-template <bool LC>
+// (the dense layout without lane change runs kd_action: this kernel is the lane-change step's, and is reported as k_action<true>)
 __global__ __launch_bounds__(kActBlock) void k_action(StepCtx c, ActionOut o, JobQueue q, int nVehicleBlocks) {
     // The trailing blocks of the launch do the (independent) per-laneLink notify sources for k_cross.
     if ((int) blockIdx.x >= nVehicleBlocks) {
@@ -989,7 +989,7 @@ __global__ __launch_bounds__(kActBlock) void k_action(StepCtx c, ActionOut o, Jo
     for (int s = blockIdx.x * blockDim.x + threadIdx.x; s < S; s += stride) {
         SlotIn in = loadSlot(c, s);
         if (in.vid >= 0 && in.head && in.d < c.n.L && in.nd0 >= c.n.L) in.hop = c.n.laneLL4[in.d];  // (findHeadLeader's first hop)
-        actionOne<LC>(c, o, tv, s, in, push);
+        actionOne<true>(c, o, tv, s, in, push);
     }
 }
 

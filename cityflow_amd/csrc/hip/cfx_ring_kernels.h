@@ -1540,7 +1540,7 @@ __global__ CFX_KR_ACTION_BOUNDS(B) void kr_action(RingCtx c, RingOut o, JobQueue
             in.lm = sLM[i];
             in.hop = (in.nd0 >= c.n.L) ? sHop[i] : make_int4(-2, -2, -2, -2);
             in.laneAdmitted = sAdm[i] != 0;
-            in.endLane = -1;  // (the end lanes from the lane's static tables, as kw_action has them: measured in round 4, 12.0 us either way)
+            in.endLane = -1;  // (the end lanes from the lane's static tables instead: measured in round 4, 12.0 us either way)
             actionOneRounds<GHOST>(c, o, tv, slot, in, push);
         }
         __syncthreads();
@@ -1552,150 +1552,7 @@ __global__ CFX_KR_ACTION_BOUNDS(B) void kr_action(RingCtx c, RingOut o, JobQueue
 #endif
 }
 
-// The same phase with WAVE-granular passes (the default).  The preamble is kr_action's — the block's first threads read the
-// rings and lane tables of G lanes (or B laneLinks), one block-wide prefix sum, ONE barrier — but the block's vehicle list is
-// then dealt out in chunks of 64 to the block's wavefronts, each of which runs on its own: a vehicle takes its leader's
-// {dis, speed, template} from the lane below it in the wavefront (`__shfl_up`; lane 0 of a chunk loads the vehicle ahead of
-// the chunk together with its own), so there is no LDS window and no barrier in the loop.  A block of 190 vehicles keeps
-// three wavefronts busy and lets the fourth go at once (the block form keeps 256 threads through two barriers per pass);
-// large networks take more lanes per block and every wavefront walks several chunks.  The end lanes of the laneLinks that
-// leave a lane come with the lane's static tables, so the tail records behind the next laneLink are requested in round A.
-template <int B, bool GHOST = false>
-__global__ __launch_bounds__(B) void kw_action(RingCtx c, RingOut o, JobQueue q, RingJob *jobRecs, int G, int nLaneBlocks, int nLLBlocks,
-                                                             const RingHist rh) {
-    const int w = (int) blockIdx.x, t = (int) threadIdx.x;
-    if (w >= nLaneBlocks + nLLBlocks) {  // trailing blocks: the per-laneLink notify sources for the cross phase, then Lane::history
-        if (w >= rh.firstBlock) ringLaneHistory(c, rh.h, (w - rh.firstBlock) * B + t);
-        else llstateRing(c, (w - nLaneBlocks - nLLBlocks) * B + t);
-        return;
-    }
-    __shared__ cfx_vehicle_template sT[kLdsTempl];
-    __shared__ int sPre[B + 1];
-    __shared__ int2 sGeo[B];
-    __shared__ int sHead[B];
-    __shared__ double2 sLM[B];
-    __shared__ int4 sHop[B];
-    __shared__ int4 sEnd[B];
-    __shared__ unsigned char sAdm[B];
-    __shared__ int sWave[B / 64];
-    const cfx_vehicle_template *tv = c.t.templ;
-    const bool laneBlock = w < nLaneBlocks;
-    const int g = laneBlock ? G : B;
-    const int d0 = laneBlock ? w * G : c.n.L + (w - nLaneBlocks) * B;
-    const int dEnd = laneBlock ? c.n.L : c.n.L + c.n.K;
-    const int dMine = d0 + t;
-    int n = 0;
-    if (t < g && dMine < dEnd) {
-        const int2 geo = c.ringGeo[dMine];
-        const int head = c.head[dMine];
-        n = c.cnt[dMine];
-        const bool admitted = laneBlock && c.admitStep[dMine] == c.step;
-        if (admitted) n += 1;
-        sAdm[t] = admitted ? 1 : 0;
-        sLM[t] = c.n.drvLM[dMine];
-        sHop[t] = laneBlock ? c.n.laneLL4[dMine] : make_int4(-2, -2, -2, -2);
-        sEnd[t] = laneBlock ? c.n.laneEnd4[dMine] : make_int4(-1, -1, -1, -1);
-        sGeo[t] = geo;
-        sHead[t] = head;
-    }
-    if (c.t.nTempl <= kLdsTempl) {
-        const int nd = c.t.nTempl * (int) (sizeof(cfx_vehicle_template) / sizeof(double));
-        const double *src = (const double *) c.t.templ;
-        double *dst = (double *) sT;
-        for (int i = t; i < nd; i += B) dst[i] = src[i];
-        tv = sT;
-    }
-    int incl = n;
-    for (int off = 1; off < 64; off <<= 1) {
-        const int up = __shfl_up(incl, off, 64);
-        if ((t & 63) >= off) incl += up;
-    }
-    if constexpr (B > 64) {
-        if ((t & 63) == 63) sWave[t >> 6] = incl;
-        __syncthreads();
-        for (int i = 0; i < (t >> 6); ++i) incl += sWave[i];
-    }
-    sPre[t + 1] = incl;
-    if (t == 0) sPre[0] = 0;
-    __syncthreads();
-    const int T = sPre[B];
-    // feedback for the host's choice of lanes per block (small networks: every wavefront should need one chunk only)
-    if (t == 0 && T > B * 3 / 4) atomicMax(&o.sc->actionMaxT, T);
-    const RingPush push{q, jobRecs, c.n.L};
-    const int lane = t & 63;
-    for (int q0 = (t >> 6) * 64; q0 < T; q0 += B) {  // chunk q0 / 64 belongs to wavefront (q0 / 64) mod (B / 64)
-        const int qv = q0 + lane;
-        const bool valid = qv < T;
-        int i = 0, idx = 0, slot = 0;
-        int2 geo = make_int2(0, 0);
-        int head = 0;
-        SlotIn in;
-        in.vid = 0;  // (the vehicle number is loaded where it is needed: custom speed, leaving the drivable)
-        in.dis = 0.0;
-        in.speed = 0.0;
-        in.templIdx = 0;
-        in.nd0 = -1;
-        in.flags = 0;
-        double2 kp = make_double2(0.0, 0.0);
-        int tp = 0;
-        if (valid) {
-            int lo = 0, hi = g;  // the drivable this list position belongs to: the last i with sPre[i] <= qv
-            while (hi - lo > 1) {
-                const int mid = (lo + hi) >> 1;
-                if (sPre[mid] <= qv) lo = mid;
-                else hi = mid;
-            }
-            i = lo;
-            idx = qv - sPre[i];
-            geo = sGeo[i];
-            head = sHead[i];
-            slot = ringSlot(geo, head, idx);
-            const double2 kv = c.kin[slot];  // the two records of the slot: 2 x 16 B, adjacent lanes adjacent in memory
-            const int4 mv = c.meta[slot];
-            if (lane == 0 && idx > 0) {  // the vehicle ahead of the chunk: this lane's leader
-                const int ls = ringSlot(geo, head, idx - 1);
-                kp = c.kin[ls];
-                tp = c.meta[ls].x;
-            }
-            in.dis = kv.x;
-            in.speed = kv.y;
-            in.templIdx = mv.x;
-            in.nd0 = mv.y;
-            in.flags = mv.z;
-            in.lastRoadFlags = mv.z;
-        }
-        // the leader inside the drivable is the lane below (all lanes take part in the exchange)
-        const double disUp = __shfl_up(in.dis, 1, 64), speedUp = __shfl_up(in.speed, 1, 64);
-        const int templUp = __shfl_up(in.templIdx, 1, 64);
-        if (!valid) continue;  // (a chunk's invalid lanes are its last ones: nobody reads them)
-        in.d = d0 + i;
-        in.head = idx == 0;
-        in.idx = idx;
-        in.nNow = sPre[i + 1] - sPre[i];
-        in.leaderSlot = 0;
-        in.disPrev = lane == 0 ? kp.x : disUp;
-        in.speedPrev = lane == 0 ? kp.y : speedUp;
-        in.templPrev = lane == 0 ? tp : templUp;
-        if (idx > 0) in.leaderSlot = ringSlot(geo, head, idx - 1);
-        if (in.flags & (kFlagCustom | kFlagStateGap)) {
-            in.vid = c.s.vid[slot];
-            c.meta[slot].z = in.flags & ~(kFlagCustom | kFlagStateGap);  // Vehicle::update clears isCustomSpeedSet (vehicle.cpp:120-122)
-        }
-        in.lm = sLM[i];
-        in.hop = make_int4(-2, -2, -2, -2);
-        in.endLane = -1;
-        if (in.nd0 >= c.n.L) {
-            in.hop = sHop[i];
-            const int4 en = sEnd[i];
-            const int ll = in.nd0 - c.n.L;
-            in.endLane = in.hop.x == ll ? en.x : (in.hop.y == ll ? en.y : (in.hop.z == ll ? en.z : (in.hop.w == ll ? en.w : -1)));
-        }
-        in.laneAdmitted = sAdm[i] != 0;
-        actionOneRounds<GHOST>(c, o, tv, slot, in, push);
-    }
-}
-
-// The LIST form of the phase (large networks).  kw_action pays a block-wide preamble — ring geometry, prefix sum, a binary
+// The LIST form of the phase (large networks; the default there).  kr_action pays a block-wide preamble — ring geometry, prefix sum, a binary
 // search per vehicle — before its first slot load, and a block's vehicles rarely fill its chunks (28 lanes x 4.3 vehicles =
 // 120 of 256 threads at 1 M vehicles).  Here the step first writes the list of its vehicles, {slot, drivable, list index,
 // vehicles on the drivable | admitted << 31} in drivable order (kr_index: an exclusive scan over the drivables' counts with

@@ -136,9 +136,9 @@ def test_lane_history_with_lane_change_hip_equals_twin(mod, scen, workdir):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("form", [0, 10000, 20000, 30000])
+@pytest.mark.parametrize("form", [0, 20000, 30000])
 def test_lane_history_rides_with_the_next_action_launch(mod, scen, workdir, form):
-    """Ring layout, round 6: a step's record is taken by trailing blocks of the NEXT step's action launch (block form, wave form,
+    """Ring layout, round 6: a step's record is taken by trailing blocks of the NEXT step's action launch (lane-walking form,
     list form) or, when somebody asks first, by a launch of its own.  An agent's loop (signals set, lane counts read every step:
     the commit is a launch of its own, the getters do not ask for the history), free-running stretches (the commit rides with
     the next admission), resets and loads in between — the record of the last step before each must not get lost

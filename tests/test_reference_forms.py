@@ -1,6 +1,6 @@
 """GPU (-m gpu): EVERY organisation of the HIP engine's step against records the unmodified REFERENCE produced — not only
 against the CPU twin.  The forms `auto` would not pick on a small network are forced through the config's "cfx" object
-(which never changes results): ring layout in block form, wave form, list form (kr_index + kl_action) and its ticketed
+(which never changes results): ring layout in lane-walking (block) form, list form (kr_index + kl_action) and its ticketed
 variant, with the cross phase in both organisations; dense layout in its round-2 form and with every `denseForm` bit.
 
   * the reference's golden checkpoints of the stock grids (tests/golden/reference_checkpoints.json, make_goldens.py):
@@ -22,7 +22,6 @@ from test_irregular import irregular
 FORMS = {
     "auto": {},
     "ring-block-latency": {"layout": "ring", "ringLanesPerWave": 20000, "crossMode": "latency"},
-    "ring-wave-throughput": {"layout": "ring", "ringLanesPerWave": 10000, "crossMode": "throughput"},
     "ring-list-throughput": {"layout": "ring", "ringLanesPerWave": 30000, "crossMode": "throughput"},
     "ring-list-latency": {"layout": "ring", "ringLanesPerWave": 30000, "crossMode": "latency"},
     "ring-list-ticket": {"layout": "ring", "ringLanesPerWave": 60000, "crossMode": "throughput"},

@@ -40,6 +40,7 @@ for i, spec in enumerate(args):
     json.dump(c, open(path, "w"))
     engines.append((spec, _cityflow.Engine._with_backend(path, 1, lib) if lib else _cityflow.Engine(path, 1), {}, []))
 steps_timed = int(os.environ.get("CFX_AB_STEPS", 200))
+host = {}  # id(engine) -> mean us per cfx_step call of each timed run
 for r in range(rounds):
     for spec, eng, res, wall in engines:
         eng.load(arch)
@@ -59,11 +60,13 @@ for r in range(rounds):
         for _ in range(12):
             eng.next_step()
         eng.sync()
+        eng._host_stats(True)
         t0 = time.perf_counter()
         for _ in range(steps_timed):
             eng.next_step()
         eng.sync()
         wall.append((time.perf_counter() - t0) / steps_timed * 1e6)
+        host.setdefault(id(eng), []).append(eng._host_stats(True)["step_call_us_mean"])  # (the host's own time inside cfx_step)
 print("scenario", scenario, "running", running, "rounds", rounds)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 try:
@@ -77,4 +80,6 @@ for spec, eng, res, wall in engines:
     sc = eng._scalars()
     print("   diag", spec, {k: v for k, v in sc.items() if k.startswith("diag_")}, "running", sc["active_vehicle_count"])
     med = {k: round(statistics.median(v), 2) for k, v in res.items()}
-    print("%-46s %s sum %.1f | wall us/step median %.1f min %.1f" % (spec, med, sum(med.values()), statistics.median(wall), min(wall)), flush=True)
+    print("%-46s %s sum %.1f | wall us/step median %.1f min %.1f max %.1f | host us/cfx_step mean %.2f min %.2f max %.2f" % (
+        spec, med, sum(med.values()), statistics.median(wall), min(wall), max(wall), statistics.mean(host[id(eng)]), min(host[id(eng)]),
+        max(host[id(eng)])), flush=True)
