@@ -162,6 +162,13 @@ struct cfx_engine {
     // `trip.seen` grows with the vehicle tables (ensureVidCap), `tripBaseline`: a baseline is due before the next step or read
     bool tripOn = false, tripBaseline = false;
     TripDev trip{};
+    // cfx_movement_flow_enable: per-movement flow statistics across steps (moveFlowTick, cfx_kernels.h), kept like lane flow:
+    // `move.rec` grows with the vehicle tables (ensureVidCap), `moveBaseline`: a baseline is due before the next step or read;
+    // the host getter's device scratch (in `owned`, freed with the tracker)
+    bool moveOn = false, moveBaseline = false;
+    MoveFlowDev move{};
+    int32_t *moveOutI = nullptr;    // [3 I M] entered, left, max_waiting_steps
+    int64_t *moveOutL = nullptr;    // [5 I M] the five sums
     int cross2 = -1;                // cross phase: 1 = k_cross2 (throughput), 0 = k_cross (latency), -1 = by size
     HostMirror *hMirror = nullptr;  // pinned; valid while the last thing that changed the scalars was a step
     bool mirrorValid = false;
@@ -508,6 +515,10 @@ struct cfx_engine {
             if ((rc = growDeferred(&flow.rec, (size_t) spawned, nc))) return rc;
             HIP_TRY(hipMemsetAsync(flow.rec + spawned, 0xFF, (nc - (size_t) spawned) * sizeof(int4), stream));
         }
+        if (moveOn) {  // (records of numbers not used yet name drivable -1 at tick -1: they match nothing)
+            if ((rc = growDeferred(&move.rec, (size_t) spawned, nc))) return rc;
+            HIP_TRY(hipMemsetAsync(move.rec + spawned, 0xFF, (nc - (size_t) spawned) * sizeof(int4), stream));
+        }
         if (tripOn) {  // (numbers not used yet: never seen)
             if ((rc = growDeferred(&trip.seen, (size_t) spawned, nc))) return rc;
             HIP_TRY(hipMemsetAsync(trip.seen + spawned, 0xFF, nc - (size_t) spawned, stream));
@@ -800,6 +811,28 @@ struct cfx_engine {
         flowBaseline = false;
         return flowTick(true);
     }
+    // cfx_movement_flow_enable: one tick (or baseline) over every drivable, on the committed state, after everything enqueued so far
+    int moveTick(bool baseline) {
+        move.tick += 1;
+        move.step = (int32_t) step;
+        move.baseline = baseline ? 1 : 0;
+        move.vidCap = (int) vidCap;
+        if (baseline && K > 0) {
+            HIP_TRY(hipMemsetAsync(move.link, 0, (size_t) K * sizeof(cfx_movement_flow_link), stream));
+            HIP_TRY(hipMemsetAsync(move.skip, 0, (size_t) K * 3 * sizeof(unsigned long long), stream));
+        }
+        if (D <= 0) return CFX_OK;
+        const size_t threads = (size_t) D * kFeatGroup;
+        if (ring) hipLaunchKernelGGL(kr_movement_flow, dim3(gridFor(threads)), dim3(kBlock), 0, stream, rctx(), move);
+        else hipLaunchKernelGGL(kd_movement_flow, dim3(gridFor(threads)), dim3(kBlock), 0, stream, ctx(), move);
+        HIP_TRY(hipGetLastError());
+        return CFX_OK;
+    }
+    int moveSettle() {
+        if (!moveOn || !moveBaseline) return CFX_OK;
+        moveBaseline = false;
+        return moveTick(true);
+    }
     // cfx_trip_stats_enable: one tick (or baseline) over the vehicle numbers, on the committed state, after everything enqueued so far
     int tripTick(bool baseline) {
         if (baseline) {
@@ -897,6 +930,7 @@ struct cfx_engine {
             if ((rc = ringEnsure())) return rc;
         }
         if ((rc = flowSettle())) return rc;  // (lane flow: a baseline that is due is taken on the state this step starts from)
+        if ((rc = moveSettle())) return rc;  // (movement flow: likewise)
         if ((rc = tripSettle())) return rc;  // (trip statistics: likewise)
         if (observing && ++observeIdle > kObserveIdle) {  // nobody has read the lane counts for a while
             observing = false;
@@ -1336,7 +1370,7 @@ struct cfx_engine {
         const bool useBig = cross2 >= 0 ? cross2 == 1 : activeEst > 240000;  // which form of the cross phase (§4)
         // This step's commit rides with the next step's admission (one launch less per step) where the step runs kr_cross,
         // which then advances the lights; the previous step's, if it is still pending, goes with this step's admission.
-        const bool deferCommit = ringMerge && !dbg && !tiled && !observing && !devObserving && !flowOn && !tripOn;  // (a caller that reads the lane counts after every step wants the commit now; so do the lane-flow and the trip tick)
+        const bool deferCommit = ringMerge && !dbg && !tiled && !observing && !devObserving && !flowOn && !tripOn && !moveOn;  // (a caller that reads the lane counts after every step wants the commit now; so do the lane-flow, the movement-flow and the trip tick)
         // tiling: the previous step's halo import, if cfx_halo_wait left it to this launch
         const RingHaloIn hin = haloImportPending ? pendingImport : RingHaloIn{};
         haloImportPending = false;
@@ -1376,6 +1410,7 @@ struct cfx_engine {
         mirrorValid = !tiled;
         histPending = hist.num != 0;  // (this step's Lane::history: with the next action launch, or settle() — on a tile behind the step's halo import)
         if (flowOn && (rc = flowTick(false))) return rc;
+        if (moveOn && (rc = moveTick(false))) return rc;
         if (tripOn) return tripTick(false);
         return CFX_OK;
     }
@@ -1540,6 +1575,7 @@ struct cfx_engine {
             HIP_TRY(hipGetLastError());
         }
         if (flowOn && (rc = flowTick(false))) return rc;
+        if (moveOn && (rc = moveTick(false))) return rc;
         if (tripOn) return tripTick(false);
         return CFX_OK;
     }
@@ -1704,6 +1740,7 @@ struct cfx_engine {
         HIP_TRY(hipStreamSynchronize(stream));
         flowBaseline = flowOn;  // (taken on the state the caller sets up, before the next step or read)
         tripBaseline = tripOn;
+        moveBaseline = moveOn;
         return CFX_OK;
     }
 };
@@ -4015,6 +4052,202 @@ int32_t cfx_trip_stats_set_state(cfx_engine *e, const cfx_trip_stats_env *envs, 
     if (nEnvs != e->trip.nEnvs) return e->fail("cfx_trip_stats_set_state: n_envs is not the engine's"), CFX_ERR_INVALID;
     HIP_TRY(hipMemcpyAsync(e->trip.env, envs, (size_t) nEnvs * sizeof(cfx_trip_stats_env), hipMemcpyHostToDevice, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
+    return CFX_OK;
+}
+
+// ---- per-movement flow and delay statistics across steps (optional entry points of include/cityflow_amd.h, as above)
+int32_t cfx_movement_flow_enable(cfx_engine *e, int32_t on);
+int32_t cfx_observe_movement_flow_device(cfx_engine *e, const cfx_movement_flow_out *out, void *consumerStream);
+int32_t cfx_get_movement_flow(cfx_engine *e, const cfx_movement_flow_out *out);
+int32_t cfx_movement_flow_get_state(cfx_engine *e, int32_t *records, int32_t nVehicles, cfx_movement_flow_link *links, int32_t *tick);
+int32_t cfx_movement_flow_set_state(cfx_engine *e, const int32_t *records, int32_t nVehicles, const cfx_movement_flow_link *links,
+                                    int32_t tick);
+static_assert(std::is_same<decltype(&cfx_movement_flow_enable), cfx_movement_flow_enable_fn>::value, "cfx_movement_flow_enable");
+static_assert(std::is_same<decltype(&cfx_observe_movement_flow_device), cfx_observe_movement_flow_device_fn>::value,
+              "cfx_observe_movement_flow_device");
+static_assert(std::is_same<decltype(&cfx_get_movement_flow), cfx_get_movement_flow_fn>::value, "cfx_get_movement_flow");
+static_assert(std::is_same<decltype(&cfx_movement_flow_get_state), cfx_movement_flow_get_state_fn>::value, "cfx_movement_flow_get_state");
+static_assert(std::is_same<decltype(&cfx_movement_flow_set_state), cfx_movement_flow_set_state_fn>::value, "cfx_movement_flow_set_state");
+static_assert(sizeof(cfx_movement_flow_link) == 64, "cfx_movement_flow_link");
+
+// what every reader does first: the step's commit, the rings, a baseline that is due
+static int moveFlowPrepare(cfx_engine *e, const char *what) {
+    if (!e->moveOn) {
+        e->err = std::string(what) + ": movement-flow tracking is off (cfx_movement_flow_enable)";
+        return CFX_ERR_STATE;
+    }
+    int rc;
+    if ((rc = e->settle(false))) return rc;
+    if (e->ring && (rc = e->ringEnsure())) return rc;
+    return e->moveSettle();
+}
+
+int32_t cfx_movement_flow_enable(cfx_engine *e, int32_t on) {
+    if (!e) return CFX_ERR_INVALID;
+    auto fail = [e](const std::string &m) { return e->fail(m); };
+    HIP_TRY(hipSetDevice(e->device));
+    if (!on) {
+        if (!e->moveOn) return CFX_OK;
+        HIP_TRY(hipStreamSynchronize(e->stream));  // (a tick may still be running; a record array a growth retired stays with `retired`)
+        int rc = e->freeRaw(&e->move.rec) | e->freeRaw(&e->move.link) | e->freeRaw(&e->move.skip) | e->freeRaw(&e->moveOutI) |
+                 e->freeRaw(&e->moveOutL);
+        e->move = MoveFlowDev{};
+        e->moveOn = e->moveBaseline = false;
+        return rc ? CFX_ERR_DEVICE : CFX_OK;
+    }
+    if (e->lc.on || e->tiled) {
+        e->err = "cfx_movement_flow_enable: not with lane change and not on a tile";
+        return CFX_ERR_STATE;
+    }
+    if (e->moveOn) return CFX_OK;
+    int rc;
+    if ((rc = e->settle(false))) return rc;
+    if (e->ring && (rc = e->ringEnsure())) return rc;
+    if ((rc = e->allocRaw(&e->move.rec, e->vidCap))) return rc;
+    if ((rc = e->allocRaw(&e->move.link, (size_t) e->K))) return rc;
+    if ((rc = e->allocRaw(&e->move.skip, (size_t) e->K * 3))) return rc;
+    HIP_TRY(hipMemsetAsync(e->move.rec, 0xFF, std::max<size_t>(e->vidCap, 1) * sizeof(int4), e->stream));
+    e->move.tick = 0;
+    e->moveOn = e->moveBaseline = true;
+    return e->moveSettle();  // (the baseline zeroes link and skip)
+}
+
+// the descriptor as this library knows it; CFX_ERR_INVALID with a message otherwise
+static int moveFlowArgs(cfx_engine *e, const cfx_movement_flow_out *out, cfx_movement_flow_out *a, const char *what) {
+    if (!e || !out || out->struct_size < (int32_t) sizeof(int32_t)) return CFX_ERR_INVALID;
+    if ((size_t) out->struct_size > sizeof(cfx_movement_flow_out)) {
+        e->err = std::string(what) + ": struct_size names members this library does not know";
+        return CFX_ERR_INVALID;
+    }
+    *a = cfx_movement_flow_out{};
+    memcpy(a, out, (size_t) out->struct_size);
+    if (!a->entered && !a->entered_lane_steps && !a->entered_lane_waiting_steps && !a->left && !a->left_steps && !a->left_waiting_steps &&
+        !a->waiting_steps && !a->max_waiting_steps && !a->reset)
+        return CFX_ERR_INVALID;
+    return CFX_OK;
+}
+
+// ... the roadLink index and the caller's row length
+static int moveFlowRows(cfx_engine *e, const cfx_movement_flow_out &a, const char *what) {
+    int rc;
+    if ((rc = interTables(e))) return rc;
+    if (a.max_roadlinks != e->interTab.M) {
+        e->err = std::string(what) + ": max_roadlinks must be the network's " + std::to_string(e->interTab.M) + ", not " +
+                 std::to_string(a.max_roadlinks);
+        return CFX_ERR_INVALID;
+    }
+    return CFX_OK;
+}
+
+// a group per roadLink row (k_movement_flow_drain, cfx_kernels.h)
+static void launchMoveFlowDrain(cfx_engine *e, const MoveFlowOut &o, int32_t reset) {
+    const size_t rows = (size_t) e->I * e->interTab.M;
+    if (rows == 0) return;
+    hipLaunchKernelGGL(k_movement_flow_drain, dim3(gridFor(rows * kFeatGroup)), dim3(kBlock), 0, e->stream, e->move.link, e->move.skip,
+                       e->interTab.rlOff, e->interTab.rlLinks, e->net.interVirtual, (int) rows, e->interTab.M, o, reset ? 1 : 0);
+}
+
+int32_t cfx_observe_movement_flow_device(cfx_engine *e, const cfx_movement_flow_out *out, void *consumerStream) {
+    cfx_movement_flow_out a{};
+    int rc;
+    if ((rc = moveFlowArgs(e, out, &a, "cfx_observe_movement_flow_device"))) return rc;
+    auto fail = [e](const std::string &m) { return e->fail(m); };
+    HIP_TRY(hipSetDevice(e->device));
+    const std::pair<const void *, const char *> bufs[] = {
+        {a.entered, "cfx_observe_movement_flow_device: entered"},
+        {a.entered_lane_steps, "cfx_observe_movement_flow_device: entered_lane_steps"},
+        {a.entered_lane_waiting_steps, "cfx_observe_movement_flow_device: entered_lane_waiting_steps"},
+        {a.left, "cfx_observe_movement_flow_device: left"},
+        {a.left_steps, "cfx_observe_movement_flow_device: left_steps"},
+        {a.left_waiting_steps, "cfx_observe_movement_flow_device: left_waiting_steps"},
+        {a.waiting_steps, "cfx_observe_movement_flow_device: waiting_steps"},
+        {a.max_waiting_steps, "cfx_observe_movement_flow_device: max_waiting_steps"}};
+    for (const auto &b : bufs)
+        if (b.first && (rc = checkDevicePointer(e, b.first, b.second))) return rc;
+    if ((rc = moveFlowPrepare(e, "cfx_observe_movement_flow_device"))) return rc;
+    if ((rc = moveFlowRows(e, a, "cfx_observe_movement_flow_device"))) return rc;
+    if ((rc = e->orderAfterCaller((hipStream_t) consumerStream))) return rc;
+    launchMoveFlowDrain(e, MoveFlowOut{a.entered, a.entered_lane_steps, a.entered_lane_waiting_steps, a.left, a.left_steps,
+                                       a.left_waiting_steps, a.waiting_steps, a.max_waiting_steps}, a.reset);
+    HIP_TRY(hipGetLastError());
+    return e->orderCallerAfter((hipStream_t) consumerStream);
+}
+
+int32_t cfx_get_movement_flow(cfx_engine *e, const cfx_movement_flow_out *out) {
+    cfx_movement_flow_out a{};
+    int rc;
+    if ((rc = moveFlowArgs(e, out, &a, "cfx_get_movement_flow"))) return rc;
+    auto fail = [e](const std::string &m) { return e->fail(m); };
+    HIP_TRY(hipSetDevice(e->device));
+    if ((rc = moveFlowPrepare(e, "cfx_get_movement_flow"))) return rc;
+    if ((rc = moveFlowRows(e, a, "cfx_get_movement_flow"))) return rc;
+    const size_t rows = (size_t) e->I * e->interTab.M;
+    if (!e->moveOutI && (rc = e->allocRaw(&e->moveOutI, 3 * rows))) return rc;
+    if (!e->moveOutL && (rc = e->allocRaw(&e->moveOutL, 5 * rows))) return rc;
+    int32_t *dEntered = e->moveOutI, *dLeft = dEntered + rows, *dMax = dLeft + rows;
+    int64_t *dELS = e->moveOutL, *dELW = dELS + rows, *dLS = dELW + rows, *dLW = dLS + rows, *dW = dLW + rows;
+    launchMoveFlowDrain(e, MoveFlowOut{a.entered ? dEntered : nullptr, a.entered_lane_steps ? dELS : nullptr,
+                                       a.entered_lane_waiting_steps ? dELW : nullptr, a.left ? dLeft : nullptr,
+                                       a.left_steps ? dLS : nullptr, a.left_waiting_steps ? dLW : nullptr,
+                                       a.waiting_steps ? dW : nullptr, a.max_waiting_steps ? dMax : nullptr}, a.reset);
+    HIP_TRY(hipGetLastError());
+    auto back = [&](void *dst, const void *src, size_t bytes) {
+        return (dst && bytes) ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, e->stream) : hipSuccess;
+    };
+    HIP_TRY(back(a.entered, dEntered, rows * sizeof(int32_t)));
+    HIP_TRY(back(a.entered_lane_steps, dELS, rows * sizeof(int64_t)));
+    HIP_TRY(back(a.entered_lane_waiting_steps, dELW, rows * sizeof(int64_t)));
+    HIP_TRY(back(a.left, dLeft, rows * sizeof(int32_t)));
+    HIP_TRY(back(a.left_steps, dLS, rows * sizeof(int64_t)));
+    HIP_TRY(back(a.left_waiting_steps, dLW, rows * sizeof(int64_t)));
+    HIP_TRY(back(a.waiting_steps, dW, rows * sizeof(int64_t)));
+    HIP_TRY(back(a.max_waiting_steps, dMax, rows * sizeof(int32_t)));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    return CFX_OK;
+}
+
+int32_t cfx_movement_flow_get_state(cfx_engine *e, int32_t *records, int32_t nVehicles, cfx_movement_flow_link *links, int32_t *tick) {
+    if (!e || !tick || nVehicles < 0 || (nVehicles > 0 && !records) || (e->K > 0 && !links)) return CFX_ERR_INVALID;
+    auto fail = [e](const std::string &m) { return e->fail(m); };
+    HIP_TRY(hipSetDevice(e->device));
+    int rc;
+    if ((rc = moveFlowPrepare(e, "cfx_movement_flow_get_state"))) return rc;
+    if ((size_t) nVehicles > e->vidCap) return e->fail("cfx_movement_flow_get_state: n_vehicles beyond the vehicle tables"), CFX_ERR_INVALID;
+    std::vector<unsigned long long> skip((size_t) e->K * 3);
+    if (nVehicles) HIP_TRY(hipMemcpyAsync(records, e->move.rec, (size_t) nVehicles * sizeof(int4), hipMemcpyDeviceToHost, e->stream));
+    if (e->K > 0) {
+        HIP_TRY(hipMemcpyAsync(links, e->move.link, (size_t) e->K * sizeof(cfx_movement_flow_link), hipMemcpyDeviceToHost, e->stream));
+        HIP_TRY(hipMemcpyAsync(skip.data(), e->move.skip, skip.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, e->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    for (size_t k = 0; k < (size_t) e->K; ++k) {  // (what crossings of whole laneLinks added, folded in as the drain does)
+        links[k].entered += (int32_t) skip[3 * k];
+        links[k].left += (int32_t) skip[3 * k];
+        links[k].entered_lane_steps += (int64_t) skip[3 * k + 1];
+        links[k].entered_lane_waiting_steps += (int64_t) skip[3 * k + 2];
+    }
+    *tick = e->move.tick;
+    return CFX_OK;
+}
+
+int32_t cfx_movement_flow_set_state(cfx_engine *e, const int32_t *records, int32_t nVehicles, const cfx_movement_flow_link *links,
+                                    int32_t tick) {
+    if (!e || nVehicles < 0 || (nVehicles > 0 && !records) || (e->K > 0 && !links)) return CFX_ERR_INVALID;
+    auto fail = [e](const std::string &m) { return e->fail(m); };
+    HIP_TRY(hipSetDevice(e->device));
+    if (!e->moveOn) return e->fail("cfx_movement_flow_set_state: movement-flow tracking is off (cfx_movement_flow_enable)"), CFX_ERR_STATE;
+    if ((size_t) nVehicles > e->vidCap) return e->fail("cfx_movement_flow_set_state: n_vehicles beyond the vehicle tables"), CFX_ERR_INVALID;
+    int rc;
+    if ((rc = e->settle(false))) return rc;
+    HIP_TRY(hipMemsetAsync(e->move.rec, 0xFF, std::max<size_t>(e->vidCap, 1) * sizeof(int4), e->stream));
+    if (nVehicles) HIP_TRY(hipMemcpyAsync(e->move.rec, records, (size_t) nVehicles * sizeof(int4), hipMemcpyHostToDevice, e->stream));
+    if (e->K > 0) {
+        HIP_TRY(hipMemcpyAsync(e->move.link, links, (size_t) e->K * sizeof(cfx_movement_flow_link), hipMemcpyHostToDevice, e->stream));
+        HIP_TRY(hipMemsetAsync(e->move.skip, 0, (size_t) e->K * 3 * sizeof(unsigned long long), e->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    e->move.tick = tick;
+    e->moveBaseline = false;
     return CFX_OK;
 }
 

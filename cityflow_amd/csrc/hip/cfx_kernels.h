@@ -2444,6 +2444,178 @@ __global__ void __launch_bounds__(kBlock) k_lane_flow_drain(cfx_lane_flow_lane *
     }
 }
 
+// cfx_movement_flow_enable: per-movement flow and delay statistics across steps (include/cityflow_amd.h has the rules).  One TICK
+// after every step, on the committed state, over ALL drivables: a group of kFeatGroup threads walks drivable d (a lane, or laneLink
+// d - L) as laneFlowTick does, and each thread does the read-modify-write of its vehicle's record rec[vid] = {drivable, tick
+// last seen, since, wait}.  A vehicle is on one drivable, so its record has one writer; where it was at the previous tick (r.x
+// while r.y == this tick - 1, otherwise nothing) is read off the old record before it is overwritten.  Lanes have no record of
+// their own: they are walked for the per-vehicle records.  A laneLink keeps the difference form of cfx_lane_flow_lane (who left
+// is the difference of its sums) plus the two lane sums of its entrants, one writer (the group's first thread).  A vehicle that
+// crossed a whole laneLink inside the step is found by the END LANE's group: its additions go to `skip` with vector atomics,
+// never into the record another group rewrites whole, and the drain folds them in.
+struct MoveFlowDev {
+    int4 *rec;                     // [vidCap]
+    cfx_movement_flow_link *link;  // [K]
+    unsigned long long *skip;      // [3 K] {crossings, their lane steps, their lane waiting steps} of whole-laneLink crossings
+    int vidCap;
+    int32_t tick, step;
+    int baseline;                  // every vehicle: since = step, wait = 0, not entered (the host has zeroed link and skip)
+};
+struct MoveFlowNet {  // lane -> laneLink list -> end lane
+    int L;
+    const int32_t *laneLLStart, *laneLL, *llEndLane;
+};
+__device__ __forceinline__ MoveFlowNet moveFlowNet(const DevNet &n) { return MoveFlowNet{n.L, n.laneLLStart, n.laneLL, n.llEndLane}; }
+
+// (`f` and `net` by value, as laneFlowTick takes its argument struct)
+template <typename Rec, typename Vid>
+__device__ __forceinline__ void moveFlowTick(const MoveFlowDev f, const MoveFlowNet net, int d, int n, int sub, Rec rec, Vid vidOf) {
+    const bool isLink = d >= net.L;  // (the same in every thread of the group)
+    cfx_movement_flow_link a{};
+    if (isLink && sub == 0) a = f.link[d - net.L];  // (requested before the walk, used behind it)
+    int entered = 0, inc = 0, mx = 0;
+    long long S = 0, W = 0, ES = 0, EW = 0;
+    for (int i = sub; i < n; i += kFeatGroup) {
+        const int v = vidOf(i);
+        if ((unsigned) v >= (unsigned) f.vidCap) continue;  // (never: every running vehicle has a number the tables hold)
+        const bool waiting = rec(i).y < 0.1;
+        const int4 r = f.rec[v];
+        int since = r.z, wait = r.w;
+        if (f.baseline) {
+            since = f.step;
+            wait = 0;
+        } else if (r.y != f.tick - 1 || r.x != d) {  // new on d
+            const int p = r.y == f.tick - 1 ? r.x : -1;
+            const bool fromLane = p >= 0 && p < net.L;
+            if (isLink) {
+                entered += 1;
+                if (fromLane) {
+                    ES += f.step - r.z;
+                    EW += r.w;
+                }
+            } else if (fromLane) {  // lane -> lane: the first laneLink of p that ends on d
+                const int end = net.laneLLStart[p + 1];
+                for (int q = net.laneLLStart[p]; q < end; ++q) {
+                    const int k = net.laneLL[q];
+                    if (net.llEndLane[k] != d) continue;
+                    atomicAdd(&f.skip[3 * (size_t) k], 1ull);
+                    atomicAdd(&f.skip[3 * (size_t) k + 1], (unsigned long long) (f.step - r.z));
+                    atomicAdd(&f.skip[3 * (size_t) k + 2], (unsigned long long) r.w);
+                    break;
+                }
+            }
+            since = f.step;
+            wait = 0;
+        }
+        if (waiting && !f.baseline) {
+            wait += 1;
+            inc += 1;
+        }
+        f.rec[v] = make_int4(d, f.tick, since, wait);
+        S += since;
+        W += wait;
+        mx = max(mx, wait);
+    }
+    if (!isLink) return;
+    for (int off = kFeatGroup / 2; off > 0; off >>= 1) {
+        entered += __shfl_xor(entered, off, kFeatGroup);
+        inc += __shfl_xor(inc, off, kFeatGroup);
+        mx = max(mx, __shfl_xor(mx, off, kFeatGroup));
+        S += featShflXor64(S, off);
+        W += featShflXor64(W, off);
+        ES += featShflXor64(ES, off);
+        EW += featShflXor64(EW, off);
+    }
+    if (sub != 0) return;
+    if (!f.baseline) {  // (a baseline: the accumulators are zero already)
+        const int left = a.count + entered - n;
+        a.entered += entered;
+        a.entered_lane_steps += ES;
+        a.entered_lane_waiting_steps += EW;
+        a.left += left;
+        a.left_steps += (long long) f.step * left - (a.since_sum + (long long) f.step * entered - S);
+        a.left_waiting_steps += a.waiting_steps - (W - inc);
+    }
+    a.since_sum = S;
+    a.waiting_steps = W;
+    a.count = n;
+    a.max_waiting_steps = mx;
+    f.link[d - net.L] = a;
+}
+
+__global__ void __launch_bounds__(kBlock) kd_movement_flow(StepCtx c, MoveFlowDev f) {
+    const int d = (int) ((blockIdx.x * (size_t) blockDim.x + threadIdx.x) / kFeatGroup);
+    if (d >= c.n.L + c.n.K) return;  // (whole groups)
+    moveFlowTick(f, moveFlowNet(c.n), d, c.cnt[d], threadIdx.x % kFeatGroup, laneRec(c, d), laneVid(c, d));
+}
+
+// cfx_observe_movement_flow_device / cfx_get_movement_flow: a group of kFeatGroup threads per roadLink row (i, m) adds up the records
+// of the row's laneLinks (rlOff / rlLinks of InterFeatOut; a roadLink may have more laneLinks than the group has threads) and
+// what `skip` holds for them, and writes the outputs asked for (any pointer may be null), the padding rows included; rows of a
+// virtual intersection read 0.  With `reset` it zeroes the six accumulators of its laneLinks and their skip entries: a laneLink
+// belongs to one roadLink, so each has one writer here.
+struct MoveFlowOut {
+    int32_t *entered;
+    int64_t *enteredLaneSteps, *enteredLaneWaitingSteps;
+    int32_t *left;
+    int64_t *leftSteps, *leftWaitingSteps, *waitingSteps;
+    int32_t *maxWaitingSteps;
+};
+__global__ void __launch_bounds__(kBlock) k_movement_flow_drain(cfx_movement_flow_link *link, unsigned long long *skip, const int4 *rlOff,
+                                                                const int32_t *rlLinks, const int32_t *interVirtual, int rows, int M,
+                                                                MoveFlowOut o, int reset) {
+    const int row = (int) ((blockIdx.x * (size_t) blockDim.x + threadIdx.x) / kFeatGroup);
+    if (row >= rows) return;  // (whole groups)
+    const int sub = threadIdx.x % kFeatGroup;
+    const int first = rlOff[row].z, end = rlOff[row + 1].z;
+    int entered = 0, left = 0, mx = 0;
+    long long ES = 0, EW = 0, LS = 0, LW = 0, W = 0;
+    for (int j = first + sub; j < end; j += kFeatGroup) {
+        const int k = rlLinks[j];
+        const cfx_movement_flow_link a = link[k];
+        const unsigned long long s0 = skip[3 * (size_t) k], s1 = skip[3 * (size_t) k + 1], s2 = skip[3 * (size_t) k + 2];
+        entered += a.entered + (int) s0;
+        left += a.left + (int) s0;
+        ES += a.entered_lane_steps + (long long) s1;
+        EW += a.entered_lane_waiting_steps + (long long) s2;
+        LS += a.left_steps;
+        LW += a.left_waiting_steps;
+        W += a.waiting_steps;
+        mx = max(mx, a.max_waiting_steps);
+        if (reset) {
+            link[k].left_steps = 0;
+            link[k].left_waiting_steps = 0;
+            link[k].entered_lane_steps = 0;
+            link[k].entered_lane_waiting_steps = 0;
+            link[k].entered = 0;
+            link[k].left = 0;
+            skip[3 * (size_t) k] = 0;
+            skip[3 * (size_t) k + 1] = 0;
+            skip[3 * (size_t) k + 2] = 0;
+        }
+    }
+    for (int off = kFeatGroup / 2; off > 0; off >>= 1) {
+        entered += __shfl_xor(entered, off, kFeatGroup);
+        left += __shfl_xor(left, off, kFeatGroup);
+        mx = max(mx, __shfl_xor(mx, off, kFeatGroup));
+        ES += featShflXor64(ES, off);
+        EW += featShflXor64(EW, off);
+        LS += featShflXor64(LS, off);
+        LW += featShflXor64(LW, off);
+        W += featShflXor64(W, off);
+    }
+    if (sub != 0) return;
+    if (interVirtual[row / M]) entered = left = mx = 0, ES = EW = LS = LW = W = 0;
+    if (o.entered) o.entered[row] = entered;
+    if (o.enteredLaneSteps) o.enteredLaneSteps[row] = ES;
+    if (o.enteredLaneWaitingSteps) o.enteredLaneWaitingSteps[row] = EW;
+    if (o.left) o.left[row] = left;
+    if (o.leftSteps) o.leftSteps[row] = LS;
+    if (o.leftWaitingSteps) o.leftWaitingSteps[row] = LW;
+    if (o.waitingSteps) o.waitingSteps[row] = W;
+    if (o.maxWaitingSteps) o.maxWaitingSteps[row] = mx;
+}
+
 // cfx_trip_stats_enable: per-environment trip statistics across steps (include/cityflow_amd.h has the rules).  One TICK after
 // every step, on the committed state, over the vehicle numbers [0, spawned): a thread compares sixteen status bytes with their
 // shadow `seen` (the status at the previous tick, 0xFF = never seen) — one 16-byte load each — and only looks at a number whose

@@ -2229,6 +2229,14 @@ __global__ void __launch_bounds__(kBlock) kr_lane_flow(RingCtx c, LaneFlowDev f)
     laneFlowTick(f, lane, c.cnt[lane], threadIdx.x % kFeatGroup, laneRec(c, lane), laneVid(c, lane));
 }
 
+// cfx_movement_flow_enable, ring layout: moveFlowTick (cfx_kernels.h) over the ring of every drivable, laneLinks included
+// (ringGeo, head and cnt hold all D = L + K drivables)
+__global__ void __launch_bounds__(kBlock) kr_movement_flow(RingCtx c, MoveFlowDev f) {
+    const int d = (int) ((blockIdx.x * (size_t) blockDim.x + threadIdx.x) / kFeatGroup);
+    if (d >= c.n.L + c.n.K) return;  // (whole groups)
+    moveFlowTick(f, moveFlowNet(c.n), d, c.cnt[d], threadIdx.x % kFeatGroup, laneRec(c, d), laneVid(c, d));
+}
+
 // cfx_observe_intersections_device / cfx_get_intersection_features, ring layout: interFeatures (cfx_kernels.h) over the rings
 __global__ void __launch_bounds__(kBlock) kr_intersection_features(RingCtx c, InterFeatOut o) {
     extern __shared__ int32_t interDiff[];

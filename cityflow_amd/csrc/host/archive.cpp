@@ -498,6 +498,11 @@ void EngineHost::compactVehicles() {
         flow = flow_.state(nV);
         flow.renumber(newOfOld, nLive);
     }
+    MoveFlowState moveFlow;  // movement-flow statistics: likewise
+    if (move_.on()) {
+        moveFlow = move_.state(nV);
+        moveFlow.renumber(newOfOld, nLive);
+    }
     // trip statistics: the same vehicles are alive before and after, so the environment's record goes round the load as it is
     std::vector<cfx_trip_stats_env> trips;
     if (trip_.on()) trips = trip_.state();
@@ -508,6 +513,7 @@ void EngineHost::compactVehicles() {
             stillWaiting[newOfOld[(size_t) kv.first]] = kv.second;
     load(a);
     if (flow_.on()) flow_.setState(flow);
+    if (move_.on()) move_.setState(moveFlow);
     if (trip_.on()) trip_.setState(trips);
     for (const auto &kv : stillWaiting) check(be_.cfx_set_vehicle_speed(dev_, kv.first, kv.second), "cfx_set_vehicle_speed");
     waitingCustom_.swap(stillWaiting);
@@ -582,6 +588,7 @@ void EngineHost::load(const Archive &a) {
     }
     step_ = (size_t) d.step;
     flow_.baseline((int64_t) step_);
+    move_.baseline((int64_t) step_);
     trip_.forget();
     tripNoteVehicles();
     trip_.baseline((int64_t) step_);

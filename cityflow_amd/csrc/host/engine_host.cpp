@@ -107,6 +107,11 @@ void Backend::open(const std::string &libPath) {
     CFX_FN_OPTIONAL(cfx_get_trip_stats)
     CFX_FN_OPTIONAL(cfx_trip_stats_get_state)
     CFX_FN_OPTIONAL(cfx_trip_stats_set_state)
+    CFX_FN_OPTIONAL(cfx_movement_flow_enable)
+    CFX_FN_OPTIONAL(cfx_observe_movement_flow_device)
+    CFX_FN_OPTIONAL(cfx_get_movement_flow)
+    CFX_FN_OPTIONAL(cfx_movement_flow_get_state)
+    CFX_FN_OPTIONAL(cfx_movement_flow_set_state)
 #undef CFX_FN_OPTIONAL
     if (cfx_abi_version() != CFX_ABI_VERSION)
         throw std::runtime_error("cityflow_amd: ABI version mismatch in '" + libPath + "'");
@@ -254,6 +259,7 @@ EngineHost::EngineHost(const std::string &configFile, int threadNum, const std::
     });
     uploadNewTablesIfAny();
     flow_.bind(&be_, dev_, (int) net_->lanes.size());
+    move_.bind(&be_, dev_, &net_->flat(), 1);
     trip_.bind(&be_, dev_, 1, interval_);
 }
 
@@ -394,6 +400,7 @@ void EngineHost::nextStep() {
     } note{this, lap, step_};
     step_ += 1;
     flow_.afterStep((int64_t) step_);  // (the host tracker's tick; a backend that keeps the tracker has ticked inside cfx_step)
+    move_.afterStep((int64_t) step_);
     tripNoteVehicles();
     trip_.afterStep((int64_t) step_);  // (likewise)
     // The finished vehicles are forgotten once enough have been created since the last time (archive.cpp compactVehicles): the
@@ -796,6 +803,21 @@ void EngineHost::observeLaneFlowDevice(uintptr_t entered, uintptr_t left, uintpt
     flow_.observeDevice(o, reset, consumerStream);
 }
 
+void EngineHost::trackMovementFlow(bool on) {
+    if (on && laneChange_) throw std::logic_error("track_movement_flow: not with laneChange (a shadow changes identity when its change finishes)");
+    move_.enable(on, (int64_t) step_);
+}
+
+// (like the count getters, these leave the step prepared ahead in place)
+void EngineHost::movementFlowFeatures(const MoveFlowOut &out, bool reset) {
+    move_.features(out, reset);
+    raiseDeviceError();
+}
+
+void EngineHost::observeMovementFlowDevice(const MoveFlowOut &out, bool reset, uintptr_t consumerStream) {
+    move_.observeDevice(out, reset, consumerStream);
+}
+
 void EngineHost::trackTrips(bool on) {
     if (on && laneChange_) throw std::logic_error("track_trips: not with laneChange (a shadow is a vehicle number with its parent's enter time)");
     if (on == trip_.on()) return;
@@ -902,6 +924,7 @@ void EngineHost::reset(bool resetRnd) {
     step_ = 0;
     vehicleEpoch_ += 1;
     flow_.baseline(0);
+    move_.baseline(0);
     trip_.forget();
     trip_.baseline(0);
 }

@@ -16,6 +16,7 @@
 #include "cityflow_amd.h"
 #include "flow.h"
 #include "lane_flow.h"
+#include "movement_flow.h"
 #include "trip_stats.h"
 #include "replay.h"
 #include "roadnet.h"
@@ -105,6 +106,12 @@ struct Backend {
     cfx_get_trip_stats_fn cfx_get_trip_stats = nullptr;
     cfx_trip_stats_get_state_fn cfx_trip_stats_get_state = nullptr;
     cfx_trip_stats_set_state_fn cfx_trip_stats_set_state = nullptr;
+    // optional as a set: per-movement flow statistics kept by the backend (without them the host keeps them: movement_flow.h)
+    cfx_movement_flow_enable_fn cfx_movement_flow_enable = nullptr;
+    cfx_observe_movement_flow_device_fn cfx_observe_movement_flow_device = nullptr;
+    cfx_get_movement_flow_fn cfx_get_movement_flow = nullptr;
+    cfx_movement_flow_get_state_fn cfx_movement_flow_get_state = nullptr;
+    cfx_movement_flow_set_state_fn cfx_movement_flow_set_state = nullptr;
     void open(const std::string &libPath);  // throws std::runtime_error
     ~Backend();
 };
@@ -241,6 +248,13 @@ public:
                                     uintptr_t inside, uintptr_t pressure, int maxRoadLinks, int maxPhases, uintptr_t consumerStream);
     // ---- per-lane flow and waiting-time statistics across steps (lane_flow.h; the torch layer is cityflow_amd/torch_io.py).
     //      Off by default; a baseline when it is turned on and after reset / load; vehicle compaction carries it along
+    // ---- per-movement flow and delay statistics across steps (movement_flow.h; the torch layer is cityflow_amd/torch_io.py):
+    //      outputs [I * M], any pointer may be null
+    void trackMovementFlow(bool on);
+    bool movementFlowTracking() const { return move_.on(); }
+    int movementFlowRows() const { return (int) move_.rows(); }
+    void movementFlowFeatures(const MoveFlowOut &out, bool reset);
+    void observeMovementFlowDevice(const MoveFlowOut &out, bool reset, uintptr_t consumerStream);
     void trackLaneFlow(bool on);
     bool laneFlowTracking() const { return flow_.on(); }
     void laneFlowFeatures(const LaneFlowOut &out, bool reset);  // any pointer may be null
@@ -359,6 +373,7 @@ private:
     uint64_t vehicleEpoch_ = 0;
     std::unique_ptr<InterLayout> interLayout_;  // built by the first call that needs it
     LaneFlow flow_;
+    MoveFlow move_;
     TripStats trip_;
     void tripNoteVehicles();  // (host tracker: the vehicle numbers created since the last call)
 };

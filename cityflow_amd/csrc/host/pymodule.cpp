@@ -323,6 +323,38 @@ template <typename E> py::tuple laneFlowTuple(E &e, bool reset) {
     return py::make_tuple(entered, left, leftSteps, leftWait, waitNow, maxWait);
 }
 
+// ---- per-movement flow statistics across steps (Engine and VectorEngine; the public calls are cityflow_amd/torch_io.py)
+template <typename E> py::tuple movementFlowTuple(E &e, bool reset) {
+    const py::ssize_t n = (py::ssize_t) e.movementFlowRows();
+    py::array_t<int32_t> entered(n), left(n), maxWait(n);
+    py::array_t<int64_t> laneSteps(n), laneWait(n), leftSteps(n), leftWait(n), waitNow(n);
+    cfa::MoveFlowOut o;
+    o.entered = entered.mutable_data();
+    o.enteredLaneSteps = laneSteps.mutable_data();
+    o.enteredLaneWaitingSteps = laneWait.mutable_data();
+    o.left = left.mutable_data();
+    o.leftSteps = leftSteps.mutable_data();
+    o.leftWaitingSteps = leftWait.mutable_data();
+    o.waitingSteps = waitNow.mutable_data();
+    o.maxWaitingSteps = maxWait.mutable_data();
+    e.movementFlowFeatures(o, reset);
+    return py::make_tuple(entered, laneSteps, laneWait, left, leftSteps, leftWait, waitNow, maxWait);
+}
+template <typename E>
+void observeMovementFlowDevice(E &e, uintptr_t entered, uintptr_t laneSteps, uintptr_t laneWait, uintptr_t left, uintptr_t leftSteps,
+                               uintptr_t leftWait, uintptr_t waitNow, uintptr_t maxWait, bool reset, uintptr_t consumerStream) {
+    cfa::MoveFlowOut o;
+    o.entered = (int32_t *) entered;
+    o.enteredLaneSteps = (int64_t *) laneSteps;
+    o.enteredLaneWaitingSteps = (int64_t *) laneWait;
+    o.left = (int32_t *) left;
+    o.leftSteps = (int64_t *) leftSteps;
+    o.leftWaitingSteps = (int64_t *) leftWait;
+    o.waitingSteps = (int64_t *) waitNow;
+    o.maxWaitingSteps = (int32_t *) maxWait;
+    e.observeMovementFlowDevice(o, reset, consumerStream);
+}
+
 // ---- the first k vehicles of every lane from the front (Engine and VectorEngine; the public calls are cityflow_amd/torch_io.py)
 template <typename E> py::tuple laneFrontsTuple(E &e, int k, bool tracker) {
     if (k < 1 || k > CFX_MAX_LANE_FRONT)
@@ -433,6 +465,23 @@ template <typename E> void defDeviceBuffers(py::class_<E> &c) {
              "(entered, left, left_steps, left_waiting_steps, waiting_steps, max_waiting_steps), flat (env-major)")
         .def("_observe_lane_flow_device", &E::observeLaneFlowDevice, "entered_ptr"_a, "left_ptr"_a, "left_steps_ptr"_a,
              "left_waiting_steps_ptr"_a, "waiting_steps_ptr"_a, "max_waiting_steps_ptr"_a, "reset"_a, "consumer_stream"_a)
+        .def("_track_movement_flow",
+             [](E &e, bool on) {
+                 try {
+                     e.trackMovementFlow(on);
+                 } catch (const std::logic_error &x) {  // (lane change: out of scope, not a failure of the call)
+                     PyErr_SetString(PyExc_NotImplementedError, x.what());
+                     throw py::error_already_set();
+                 }
+             },
+             "on"_a)
+        .def("_movement_flow_tracking", &E::movementFlowTracking)
+        .def("_movement_flow_features", [](E &e, bool reset) { return movementFlowTuple(e, reset); }, "reset"_a,
+             "(entered, entered_lane_steps, entered_lane_waiting_steps, left, left_steps, left_waiting_steps, waiting_steps, "
+             "max_waiting_steps), flat (env-major, then intersection, then roadLink)")
+        .def("_observe_movement_flow_device", &observeMovementFlowDevice<E>, "entered_ptr"_a, "entered_lane_steps_ptr"_a,
+             "entered_lane_waiting_steps_ptr"_a, "left_ptr"_a, "left_steps_ptr"_a, "left_waiting_steps_ptr"_a, "waiting_steps_ptr"_a,
+             "max_waiting_steps_ptr"_a, "reset"_a, "consumer_stream"_a)
         .def("_track_trips",
              [](E &e, bool on) {
                  try {

@@ -180,6 +180,7 @@ VectorEngineHost::VectorEngineHost(const std::string &configFile, int numEnvs, i
               "cfx_add_routes");
     }
     flow_.bind(&be_, dev_, R_ * L_);
+    move_.bind(&be_, dev_, &net_->flat(), R_);
     trip_.bind(&be_, dev_, R_, interval_);
 }
 
@@ -526,6 +527,10 @@ void VectorEngineHost::nextStep() {
         std::lock_guard<std::mutex> guard(queryMutex_);
         flow_.afterStep((int64_t) step_);
     }
+    if (move_.on() && !move_.onDevice()) {
+        std::lock_guard<std::mutex> guard(queryMutex_);
+        move_.afterStep((int64_t) step_);
+    }
     if (trip_.on() && !trip_.onDevice()) {  // (the batch just handed over names the new vehicles; the ahead thread works on the next one)
         for (const cfx_spawn &s : recs_) trip_.note(s.vid, s.enter_time, L_ > 0 ? s.lane / L_ : 0);
         std::lock_guard<std::mutex> guard(queryMutex_);
@@ -551,6 +556,7 @@ void VectorEngineHost::reset(bool resetRnd) {
     {
         std::lock_guard<std::mutex> guard(queryMutex_);
         flow_.baseline(0);
+        move_.baseline(0);
         trip_.forget();
         trip_.baseline(0);
     }
@@ -660,6 +666,23 @@ void VectorEngineHost::trackLaneFlow(bool on) {
     if (on && laneChange_) throw std::logic_error("track_lane_flow: not with laneChange (a shadow changes identity when its change finishes)");
     std::lock_guard<std::mutex> guard(queryMutex_);
     flow_.enable(on, (int64_t) step_);
+}
+
+void VectorEngineHost::trackMovementFlow(bool on) {
+    if (on && laneChange_) throw std::logic_error("track_movement_flow: not with laneChange (a shadow changes identity when its change finishes)");
+    std::lock_guard<std::mutex> guard(queryMutex_);
+    move_.enable(on, (int64_t) step_);
+}
+
+void VectorEngineHost::movementFlowFeatures(const MoveFlowOut &out, bool reset) {
+    std::lock_guard<std::mutex> guard(queryMutex_);  // (the ABI is not re-entrant: the ahead thread may be asking the device)
+    move_.features(out, reset);
+    raiseDeviceError();
+}
+
+void VectorEngineHost::observeMovementFlowDevice(const MoveFlowOut &out, bool reset, uintptr_t consumerStream) {
+    std::lock_guard<std::mutex> guard(queryMutex_);
+    move_.observeDevice(out, reset, consumerStream);
 }
 
 void VectorEngineHost::trackTrips(bool on) {

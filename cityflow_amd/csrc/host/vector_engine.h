@@ -58,6 +58,13 @@ public:
     void observeIntersectionsDevice(uintptr_t phase, uintptr_t remain, uintptr_t in, uintptr_t inWaiting, uintptr_t out,
                                     uintptr_t inside, uintptr_t pressure, int maxRoadLinks, int maxPhases, uintptr_t consumerStream);
     // per-lane flow statistics across steps over every environment (EngineHost::trackLaneFlow and its kin): outputs [R * L]
+    // ---- per-movement flow and delay statistics across steps over every environment (EngineHost::trackMovementFlow and its
+    //      kin): outputs [R * I * M], any pointer may be null
+    void trackMovementFlow(bool on);
+    bool movementFlowTracking() const { return move_.on(); }
+    int movementFlowRows() const { return (int) move_.rows(); }
+    void movementFlowFeatures(const MoveFlowOut &out, bool reset);
+    void observeMovementFlowDevice(const MoveFlowOut &out, bool reset, uintptr_t consumerStream);
     void trackLaneFlow(bool on);
     bool laneFlowTracking() const { return flow_.on(); }
     void laneFlowFeatures(const LaneFlowOut &out, bool reset);
@@ -88,6 +95,7 @@ private:
     void check(int32_t rc, const char *what);
     std::unique_ptr<InterLayout> interLayout_;  // built by the first call that needs it
     LaneFlow flow_;                      // (every call with queryMutex_ held: it asks the device)
+    MoveFlow move_;                      // (likewise)
     TripStats trip_;                     // (likewise)
     bool devicePhaseUnchecked_ = false;  // as EngineHost: read by every call below that has waited for the device
     void raiseDeviceError();             // (the caller holds queryMutex_)

@@ -23,6 +23,12 @@
                                  max_waiting_steps=None, reset=False)
                                                          drains them into the given tensors, one kernel launch (see its docstring)
     eng.observe_lane_flow_array(reset=False)             the same six outputs as numpy arrays (waits for the device)
+    eng.track_movement_flow(on=True) / eng.movement_flow_tracking()
+                                                         per-movement throughput and delay statistics ACROSS steps (off by default)
+    eng.observe_movement_flow_tensor(entered=None, entered_lane_steps=None, entered_lane_waiting_steps=None, left=None,
+                                     left_steps=None, left_waiting_steps=None, waiting_steps=None, max_waiting_steps=None,
+                                     reset=False)        drains them into the given [I, M] tensors, one kernel launch
+    eng.observe_movement_flow_array(reset=False)         the same eight outputs as numpy arrays (waits for the device)
     eng.track_trips(on=True) / eng.trip_tracking()       trip statistics per environment ACROSS steps (off by default)
     eng.observe_trips_tensor(entered=None, admitted=None, admitted_buffer_steps=None, finished=None,
                              finished_travel_steps=None, in_system=None, buffered=None, in_system_travel_steps=None,
@@ -462,6 +468,85 @@ def observe_lane_flow_array(self, reset=False):
     return {name: a.reshape(shape) for name, a in zip(LANE_FLOW_OUTPUTS, self._lane_flow_features(bool(reset)))}
 
 
+MOVEMENT_FLOW_OUTPUTS = ("entered", "entered_lane_steps", "entered_lane_waiting_steps", "left", "left_steps", "left_waiting_steps",
+                         "waiting_steps", "max_waiting_steps")
+_MOVEMENT_FLOW_INT32 = ("entered", "left", "max_waiting_steps")
+
+
+def track_movement_flow(self, on=True):
+    """Turn the per-movement flow tracker on or off (off by default: nothing is allocated or launched, and it frees its memory
+    when turned off).  While it is on, every next_step() ends with one tracker update (one extra kernel launch on the HIP
+    engine; independent of track_lane_flow: both on means two updates).  Turning it on takes a baseline: every vehicle then on
+    a lane or inside an intersection starts with no waiting time and is not counted as entered, all accumulators are zero;
+    reset(), load() and load_from_file() take a new baseline and keep it on.  Not with laneChange (NotImplementedError)."""
+    self._track_movement_flow(bool(on))
+
+
+def movement_flow_tracking(self):
+    """Whether track_movement_flow is on."""
+    return self._movement_flow_tracking()
+
+
+def _movement_flow_shape(eng):
+    return tuple(eng._tensor_shapes()[1]) + (eng._intersection_dims()[0],)
+
+
+def observe_movement_flow_tensor(self, entered=None, entered_lane_steps=None, entered_lane_waiting_steps=None, left=None,
+                                 left_steps=None, left_waiting_steps=None, waiting_steps=None, max_waiting_steps=None, reset=False):
+    """Fill every given tensor with one kernel launch on the engine's stream, ordered against the current torch stream as
+    observe_lane_flow_tensor (no host wait).  Per roadLink ("movement") (i, m), in the indexing of observe_intersections_tensor:
+    the sum (max_waiting_steps: the maximum) over the roadLink's laneLinks.  s = steps taken; a vehicle is on a lane or on a
+    laneLink (inside the intersection), the `drivable` of get_vehicle_info; it keeps since (the step it came onto its drivable)
+    and wait (the steps it has stood there with speed < 0.1, the criterion of get_lane_waiting_vehicle_count).  After every step:
+    a vehicle new on a laneLink counts as entered, with — if it came off a lane — the steps it spent on that lane and the
+    steps it waited there; a vehicle no longer on a laneLink counts as left, with the steps it spent and waited inside.  A
+    vehicle that went from a lane to the next lane in one step counts as entered and left on the first laneLink joining the two
+    (in the lane's laneLink order), with its lane steps and nothing inside.
+
+        entered                     int32 [I, M]  vehicles that crossed the stop line             \\
+        entered_lane_steps          int64 [I, M]  sum of the steps they spent on the approach lane  | accumulated since the
+        entered_lane_waiting_steps  int64 [I, M]  sum of the steps they waited there                | last call with
+        left                        int32 [I, M]  vehicles that left the intersection               | reset=True, or since
+        left_steps                  int64 [I, M]  sum of the steps they spent inside                | the baseline
+        left_waiting_steps          int64 [I, M]  sum of the steps they waited inside              /
+        waiting_steps               int64 [I, M]  now: sum of wait over the vehicles inside
+        max_waiting_steps           int32 [I, M]  now: the largest wait inside (0 if there is none)
+
+    Seconds = steps * interval.  Rows m >= M_i and every row of a virtual intersection are 0; every element is written.
+    reset=True zeroes the six accumulators in the same launch, after they were read — all six, whether or not they were asked
+    for.  VectorEngine: a leading [R] on every output.  At least one output; every argument is checked before anything is
+    enqueued; RuntimeError while tracking is off."""
+    torch = _torch()
+    given = dict(zip(MOVEMENT_FLOW_OUTPUTS, (entered, entered_lane_steps, entered_lane_waiting_steps, left, left_steps,
+                                             left_waiting_steps, waiting_steps, max_waiting_steps)))
+    if all(t is None for t in given.values()):
+        raise ValueError("observe_movement_flow_tensor: give at least one of " + ", ".join(MOVEMENT_FLOW_OUTPUTS))
+    shape = _movement_flow_shape(self)
+    device = _engine_device(torch, self)
+    for name, t in given.items():
+        if t is not None:
+            _check_buf(torch, t, name, shape, torch.int32 if name in _MOVEMENT_FLOW_INT32 else torch.int64, device)
+    if not self._movement_flow_tracking():
+        raise RuntimeError("observe_movement_flow_tensor: movement-flow tracking is off (track_movement_flow(True) turns it on)")
+    if not self._device_buffers():  # (the twin: over the array call)
+        arrays = observe_movement_flow_array(self, reset=reset)
+        for name, t in given.items():
+            if t is not None:
+                t.copy_(torch.from_numpy(arrays[name]))
+        return
+    self._observe_movement_flow_device(*[0 if given[name] is None else given[name].data_ptr() for name in MOVEMENT_FLOW_OUTPUTS],
+                                       bool(reset), torch.cuda.current_stream(device).cuda_stream)
+
+
+def observe_movement_flow_array(self, reset=False):
+    """The eight outputs of observe_movement_flow_tensor as a dict of numpy arrays (same names, dtypes and shapes); waits for
+    the device.  RuntimeError while tracking is off."""
+    if not self._movement_flow_tracking():
+        raise RuntimeError("observe_movement_flow_array: movement-flow tracking is off (track_movement_flow(True) turns it on)")
+    shape = _movement_flow_shape(self)
+    return {name: a.reshape(shape) for name, a in zip(MOVEMENT_FLOW_OUTPUTS, self._movement_flow_features(bool(reset)))}
+
+
 TRIP_OUTPUTS = ("entered", "admitted", "admitted_buffer_steps", "finished", "finished_travel_steps", "in_system", "buffered",
                 "in_system_travel_steps", "average_travel_time")
 _TRIP_INT64 = ("admitted_buffer_steps", "finished_travel_steps", "in_system_travel_steps")
@@ -569,6 +654,10 @@ def install(*classes):
         cls.lane_flow_tracking = lane_flow_tracking
         cls.observe_lane_flow_tensor = observe_lane_flow_tensor
         cls.observe_lane_flow_array = observe_lane_flow_array
+        cls.track_movement_flow = track_movement_flow
+        cls.movement_flow_tracking = movement_flow_tracking
+        cls.observe_movement_flow_tensor = observe_movement_flow_tensor
+        cls.observe_movement_flow_array = observe_movement_flow_array
         cls.track_trips = track_trips
         cls.trip_tracking = trip_tracking
         cls.observe_trips_tensor = observe_trips_tensor

@@ -698,6 +698,69 @@ typedef int32_t (*cfx_get_trip_stats_fn)(cfx_engine *e, const cfx_trip_stats_out
 typedef int32_t (*cfx_trip_stats_get_state_fn)(cfx_engine *e, cfx_trip_stats_env *envs, int32_t n_envs);
 typedef int32_t (*cfx_trip_stats_set_state_fn)(cfx_engine *e, const cfx_trip_stats_env *envs, int32_t n_envs);
 
+/* ---- Per-movement (roadLink) throughput and delay statistics accumulated across steps (OPTIONAL entry points, as above; not with
+ * lane change, not on a tile: CFX_ERR_STATE).  Off by default: nothing is allocated or launched.  Independent of the lane-flow
+ * tracker: both on means two ticks and two records per vehicle.  s = the step counter after a step; D(v) = the drivable
+ * vehicle v is on then (a lane l < n_lanes or laneLink k as n_lanes + k, the `drivable` column of cfx_get_vehicles; a vehicle
+ * in an entry buffer is on nothing), D'(v) = the same at the previous tick or the baseline.  Every vehicle has one record
+ * {drivable, tick last seen, since, wait}.  While it is on, every cfx_step ends with one TICK on the state the step left:
+ *   1. D(v) = d != D'(v) = p.  Read off the record before it is overwritten with since(v) = s, wait(v) = 0:
+ *        d laneLink k, p a lane:      entered[k] += 1, entered_lane_steps[k] += s - since_p(v),
+ *                                     entered_lane_waiting_steps[k] += wait_p(v)
+ *        d laneLink k, p not a lane:  entered[k] += 1 (p nothing or another laneLink: a lane shorter than one step's travel)
+ *        d a lane, p another lane:    the vehicle crossed a whole laneLink inside the step.  k = the first laneLink of p's
+ *                                     laneLink list (lane_ll order) whose end lane is d: the three additions of the first case
+ *                                     and left[k] += 1 (nothing to left_steps / left_waiting_steps); without such a k, nothing
+ *   2. v no longer on laneLink k:     left[k] += 1, left_steps[k] += s - since(v), left_waiting_steps[k] += wait(v)
+ *   3. v on any drivable with speed < 0.1 (the criterion of cfx_get_lane_waiting_counts): wait(v) += 1, after rule 1
+ * and as of the last tick waiting_steps[k] = sum of wait(v) over the vehicles on laneLink k, max_waiting_steps[k] = their
+ * maximum (0 on an empty laneLink).  A BASELINE (enabling, cfx_reset, cfx_load_state) gives every vehicle then on a drivable
+ * since = s, wait = 0 without counting it as entered, and zeroes the accumulators.
+ * Outputs are per roadLink (i, m), rows of max_roadlinks as in cfx_observe_intersections_device, [n_inters * max_roadlinks]
+ * each: the sum (max_waiting_steps: the maximum) over the roadLink's laneLinks; 0 for m >= M_i and in every row of a virtual
+ * intersection.  Every element of a given output is written.  The descriptor follows the struct_size rules of cfx_lane_obs.
+ *   "cfx_movement_flow_enable"         on != 0: allocate (16 bytes per vehicle number the tables hold, 88 per laneLink) and
+ *                                      take a baseline; 0: free.  While it is on the ring layout launches every step's commit
+ *                                      with the step.
+ *   "cfx_observe_movement_flow_device" any of the eight NULL (at least one given unless reset), all in device memory, written by
+ *                                      ONE kernel on the engine's stream, ordered against consumer_stream as
+ *                                      cfx_observe_device; reset != 0 zeroes the six accumulators in that launch, after they
+ *                                      were read.  The first call builds the roadLink index of cfx_observe_intersections_device.
+ *   "cfx_get_movement_flow"            the same into host memory; synchronous.
+ *   "cfx_movement_flow_get_state" / "cfx_movement_flow_set_state"  the tracker as it stands, for a host that renumbers the
+ *                                      vehicles through cfx_load_state (which takes a baseline): records[4 v ..] of vehicle
+ *                                      number v < n_vehicles, links[n_lanelinks] (what crossings of whole laneLinks added
+ *                                      folded in), and the tick counter.  set replaces all three and cancels a pending
+ *                                      baseline.  Synchronous. */
+typedef struct cfx_movement_flow_link {
+    int64_t since_sum;           /* sum of since(v) over the laneLink's vehicles at the last tick */
+    int64_t waiting_steps;       /* sum of wait(v) over them */
+    int64_t left_steps, left_waiting_steps;
+    int64_t entered_lane_steps, entered_lane_waiting_steps;
+    int32_t count;               /* vehicles on the laneLink at the last tick */
+    int32_t entered, left;
+    int32_t max_waiting_steps;
+} cfx_movement_flow_link;
+typedef struct cfx_movement_flow_out {
+    int32_t struct_size;
+    int32_t max_roadlinks;       /* the network's largest roadLink count (CFX_ERR_INVALID otherwise) */
+    int32_t reset;
+    int32_t reserved;
+    int32_t *entered;
+    int64_t *entered_lane_steps, *entered_lane_waiting_steps;
+    int32_t *left;
+    int64_t *left_steps, *left_waiting_steps;
+    int64_t *waiting_steps;
+    int32_t *max_waiting_steps;
+} cfx_movement_flow_out;
+typedef int32_t (*cfx_movement_flow_enable_fn)(cfx_engine *e, int32_t on);
+typedef int32_t (*cfx_observe_movement_flow_device_fn)(cfx_engine *e, const cfx_movement_flow_out *out, void *consumer_stream);
+typedef int32_t (*cfx_get_movement_flow_fn)(cfx_engine *e, const cfx_movement_flow_out *out);
+typedef int32_t (*cfx_movement_flow_get_state_fn)(cfx_engine *e, int32_t *records, int32_t n_vehicles, cfx_movement_flow_link *links,
+                                                  int32_t *tick);
+typedef int32_t (*cfx_movement_flow_set_state_fn)(cfx_engine *e, const int32_t *records, int32_t n_vehicles,
+                                                  const cfx_movement_flow_link *links, int32_t tick);
+
 #ifdef __cplusplus
 }
 #endif

@@ -29,7 +29,14 @@ version of the package: it is the launch --features-only all measures).
 step, and get_average_travel_time_tensor() is asserted equal to Engine.get_average_travel_time() after the warm-up steps; then
 next_step alone with tracking off and on, alternated --runs times; then get_average_travel_time_tensor() per call against
 Engine.get_average_travel_time() per call on the same state.  --trips-only trace runs next_step + observe_trips_tensor(all nine)
-alone, so that a kernel trace shows k_trip_tick and k_trip_drain beside the step's kernels."""
+alone, so that a kernel trace shows k_trip_tick and k_trip_drain beside the step's kernels.
+       python tools/rl_device_loop.py --movement-flow [--runs N] [--movement-flow-only trace]
+--movement-flow: what track_movement_flow costs and saves — next_step alone with tracking off and on, alternated --runs times;
+then a max-pressure loop whose reward (vehicles that crossed a stop line, and the steps they waited on their approach lane)
+comes from observe_movement_flow_tensor(entered, entered_lane_waiting_steps, reset=True), against the same loop with the reward
+built from _vehicle_state() and a numpy diff every step; both rewards are asserted equal over 12 steps first.
+--movement-flow-only trace runs next_step + observe_lane_flow_tensor(reset=True) + observe_movement_flow_tensor(reset=True) alone,
+so that a kernel trace shows kr_lane_flow, k_lane_flow_drain, kr_movement_flow and k_movement_flow_drain side by side."""
 import argparse
 import os
 import sys
@@ -53,6 +60,8 @@ ap.add_argument("--fronts", action="store_true")
 ap.add_argument("--fronts-only", choices=["four", "k8", "k32", "all8", "all32", "fronts32"], default=None)
 ap.add_argument("--trips", action="store_true")
 ap.add_argument("--trips-only", choices=["trace"], default=None)
+ap.add_argument("--movement-flow", action="store_true")
+ap.add_argument("--movement-flow-only", choices=["trace"], default=None)
 ap.add_argument("--skip-single", action="store_true", help="--trips: the VectorEngine alone")
 ap.add_argument("--runs", type=int, default=3)
 args = ap.parse_args()
@@ -462,6 +471,111 @@ def trips(name, eng, n, runs, only):
         measure("Engine.get_average_travel_time() alone (status bytes to the host, sort, sum)", eng,
                 lambda s: eng.get_average_travel_time(), max(n // 20, 10))
 
+
+def movement_flow(name, eng, n, runs, only):
+    device = torch.device("cuda", eng._stream_handle()[1])
+    lay = eng.intersection_layout()
+    L = len(eng.lane_ids())
+    I, P, M = lay["phase_avail"].shape
+    pp = torch.empty((I, P), dtype=torch.int32, device=device)
+    entered = torch.empty((I, M), dtype=torch.int32, device=device)
+    lane_wait = torch.empty((I, M), dtype=torch.int64, device=device)
+    left = torch.empty(L, dtype=torch.int32, device=device)
+    reward = {}
+
+    def control():
+        eng.observe_intersections_tensor(phase_pressure=pp)
+        eng.set_tl_phases_tensor(pp.argmax(-1))
+        eng.next_step()
+
+    def tensor_loop(s):
+        control()
+        eng.observe_movement_flow_tensor(entered=entered, entered_lane_waiting_steps=lane_wait, reset=True)
+        reward["tensor"] = torch.stack((entered.sum(), lane_wait.sum()))  # (stays on the device)
+
+    # the same reward by vehicle number over _vehicle_state(): the drivable and the steps waited on it at the last step
+    host = {"drv": np.full(0, -1, dtype=np.int64), "wait": np.zeros(0, dtype=np.int64)}
+
+    def numpy_reward(baseline=False):
+        st = eng._vehicle_state()
+        vid, drv = st["vid"].astype(np.int64), st["drivable"].astype(np.int64)
+        size = max(int(vid.max()) + 1 if vid.size else 0, host["drv"].size)
+        grow = size - host["drv"].size
+        prev = np.concatenate([host["drv"], np.full(grow, -1, dtype=np.int64)])
+        wait = np.concatenate([host["wait"], np.zeros(grow, dtype=np.int64)])
+        now = np.full(size, -1, dtype=np.int64)
+        now[vid] = drv
+        slow = np.zeros(size, dtype=bool)
+        slow[vid] = st["speed"] < 0.1
+        new = (now != prev) & (now >= 0)
+        # (lane -> lane inside one step: the vehicle crossed the whole laneLink that joins the two, and a route has one)
+        crossed = new & ((now >= L) | ((prev >= 0) & (prev < L)))
+        from_lane = crossed & (prev >= 0) & (prev < L)
+        result = (int(crossed.sum()), int(wait[from_lane].sum()))
+        wait[new | baseline] = 0
+        wait[slow & (now >= 0) & (not baseline)] += 1
+        host["drv"], host["wait"] = now, wait
+        return result
+
+    def numpy_loop(s):
+        control()
+        reward["numpy"] = numpy_reward()
+
+    lf_left = torch.empty(L, dtype=torch.int32, device=device)
+
+    def trace(s):
+        eng.next_step()
+        eng.observe_lane_flow_tensor(left=lf_left, reset=True)
+        eng.observe_movement_flow_tensor(entered=entered, entered_lane_waiting_steps=lane_wait, reset=True)
+
+    for _ in range(300):
+        eng.next_step()
+    eng.sync()
+    print("# %s" % name, flush=True)
+    if only:
+        eng.track_lane_flow(True)
+        eng.track_movement_flow(True)
+        measure("next_step + observe_lane_flow_tensor(1, reset) + observe_movement_flow_tensor(2, reset)", eng, trace, n)
+        return
+    res = {"off": [], "on": []}
+    for r in range(runs):
+        eng.track_movement_flow(False)
+        res["off"].append(measure("next_step alone, tracking off (run %d)" % r, eng, lambda s: eng.next_step(), n))
+        eng.track_movement_flow(True)
+        res["on"].append(measure("next_step alone, tracking on  (run %d)" % r, eng, lambda s: eng.next_step(), n))
+    for k, v in res.items():
+        print("%-4s median %8.1f us   min %8.1f   max %8.1f" % (k, float(np.median(v)), min(v), max(v)), flush=True)
+    print("tracking on - off (medians) %8.1f us per step" % (float(np.median(res["on"])) - float(np.median(res["off"]))), flush=True)
+    measure("observe_movement_flow_tensor(entered, entered_lane_waiting_steps, reset) alone (1 launch + events)", eng,
+            lambda s: eng.observe_movement_flow_tensor(entered=entered, entered_lane_waiting_steps=lane_wait, reset=True), n)
+    # both rewards from one engine, step by step, before anything is timed
+    eng.track_movement_flow(False)
+    eng.track_movement_flow(True)  # (a baseline for both)
+    numpy_reward(baseline=True)
+    total = 0
+    for s in range(12):
+        control()
+        eng.observe_movement_flow_tensor(entered=entered, entered_lane_waiting_steps=lane_wait, reset=True)
+        got, want = (int(entered.sum()), int(lane_wait.sum())), numpy_reward()
+        assert got == want, "step %d: the tensor reward %s is not the numpy diff's %s" % (s, got, want)
+        total += want[0]
+    assert total > 0
+    print("the two rewards are equal over 12 steps (%d vehicles crossed a stop line)" % total, flush=True)
+    n_np = max(n // 10, 10)
+    res = {"tensor": [], "numpy": []}
+    for r in range(runs):
+        res["tensor"].append(measure("observe_intersections -> argmax -> set -> next_step -> observe_movement_flow_tensor (run %d)" % r, eng, tensor_loop, n))
+        res["numpy"].append(measure("... -> next_step -> _vehicle_state() + numpy diff (run %d)" % r, eng, numpy_loop, n_np))
+    for k, v in res.items():
+        print("%-6s median %10.1f us   min %10.1f   max %10.1f" % (k, float(np.median(v)), min(v), max(v)), flush=True)
+    print("numpy loop / tensor loop %8.1fx" % (float(np.median(res["numpy"])) / float(np.median(res["tensor"]))), flush=True)
+
+
+if args.movement_flow or args.movement_flow_only:
+    e = _cityflow.Engine(cfg, 1)
+    movement_flow("Engine, 30x30 RL workload (%d signals, %d lanes)" % (len(e.intersection_ids()), len(e.lane_ids())), e, args.iters,
+                  args.runs, args.movement_flow_only)
+    sys.exit(0)
 
 if args.trips or args.trips_only:
     if not args.skip_single:
