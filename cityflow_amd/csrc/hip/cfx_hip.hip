@@ -140,6 +140,15 @@ struct cfx_engine {
     bool devObserving = false;
     int devObserveIdle = 0;
     int32_t *hPhaseErr = nullptr;  // pinned, host-mapped: {intersection, phase} of the first rejected device-side entry, {-1, 0}
+    // cfx_set_tl_plan_device and its kin: the durations in force are net.phaseTime itself, held here non-const (every kernel that
+    // reads a phase's time indexes that array on every use); the file's, for cfx_restore_tl_plan; the largest phase count of a
+    // signalised intersection (the row length of the padded arrays); the record of a rejected call; the host calls' scratch
+    double *phaseTime = nullptr, *phaseTimeFile = nullptr;
+    int nPhaseTimes = 0, planMaxPhases = 0;
+    TlPlanErr *hPlanErr = nullptr;  // pinned, host-mapped; inter = -1: none
+    int32_t planCalls = 0;          // set calls enqueued so far (TlPlanErr::done: the last one the device has decided)
+    double *planD = nullptr;        // [I * planMaxPhases + I] durations, then remain
+    int32_t *planI = nullptr;       // [I] phase
     // cfx_get_lane_obs / cfx_get_lane_features: device scratch kept between calls (grown to the largest request seen; in `owned`)
     double *featSum = nullptr, *featEdges = nullptr;
     int32_t *featBins = nullptr;
@@ -1782,6 +1791,7 @@ void cfx_destroy(cfx_engine *e) {
     if (e->devInEvent) (void) hipEventDestroy(e->devInEvent);
     if (e->devOutEvent) (void) hipEventDestroy(e->devOutEvent);
     if (e->hPhaseErr) (void) hipHostFree(e->hPhaseErr);
+    if (e->hPlanErr) (void) hipHostFree(e->hPlanErr);
     if (e->stream) (void) hipStreamDestroy(e->stream);
     delete e;
 }
@@ -1856,7 +1866,12 @@ static int32_t createImpl(cfx_engine *e, const cfx_net *n, const cfx_config *cfg
     UP(interNRL, n->inter_n_roadlinks, e->I)
     UP(interPhaseStart, n->inter_phase_start, e->I + 1)
     UP(interAvailStart, n->inter_avail_start, e->I)
-    UP(phaseTime, n->phase_time, n->n_phases)
+    if ((rc = e->upload(&e->phaseTime, n->phase_time, (size_t) n->n_phases))) return rc;  // (written by cfx_set_tl_plan*)
+    d.phaseTime = e->phaseTime;
+    if ((rc = e->upload(&e->phaseTimeFile, n->phase_time, (size_t) n->n_phases))) return rc;
+    e->nPhaseTimes = n->n_phases;
+    for (int i = 0; i < e->I; ++i)
+        if (!n->inter_virtual[i]) e->planMaxPhases = std::max(e->planMaxPhases, n->inter_phase_start[i + 1] - n->inter_phase_start[i]);
     UP(phaseAvail, n->phase_avail, n->n_avail)
 #undef UP
     const size_t dPad = e->dPadded();
@@ -1880,6 +1895,8 @@ static int32_t createImpl(cfx_engine *e, const cfx_net *n, const cfx_config *cfg
     HIP_TRY(hipHostMalloc((void **) &e->hPhaseErr, 2 * sizeof(int32_t), hipHostMallocDefault));
     e->hPhaseErr[0] = -1;
     e->hPhaseErr[1] = 0;
+    HIP_TRY(hipHostMalloc((void **) &e->hPlanErr, sizeof(TlPlanErr), hipHostMallocDefault));
+    *e->hPlanErr = TlPlanErr{-1, 0, -1, 0, 0.0};
     HIP_TRY(hipEventCreateWithFlags(&e->devInEvent, hipEventDisableTiming));
     HIP_TRY(hipEventCreateWithFlags(&e->devOutEvent, hipEventDisableTiming));
     if ((rc = e->allocRaw(&e->finTicket, 4))) return rc;  // [0] ticket, [2..3] 64-bit total of exactFinishStatistics
@@ -3420,6 +3437,142 @@ int32_t cfx_device_error(cfx_engine *e, int32_t *inter, int32_t *phase) {
     if (inter) *inter = i;
     if (phase) *phase = rec[1];
     rec[0] = -1;
+    return 1;
+}
+
+// ---- the fixed-time signal plan as engine state (optional entry points of include/cityflow_amd.h, as above)
+int32_t cfx_set_tl_plan_device(cfx_engine *e, const double *durations, const int32_t *phase, const double *remain, int32_t n,
+                               int32_t maxPhases, void *producerStream);
+int32_t cfx_set_tl_plan(cfx_engine *e, const double *durations, const int32_t *phase, const double *remain, int32_t n, int32_t maxPhases);
+int32_t cfx_get_tl_phase_durations_device(cfx_engine *e, double *out, int32_t maxPhases, void *consumerStream);
+int32_t cfx_get_tl_phase_durations(cfx_engine *e, double *out, int32_t maxPhases);
+int32_t cfx_restore_tl_plan(cfx_engine *e);
+int32_t cfx_tl_plan_error(cfx_engine *e, int32_t *what, int32_t *inter, int32_t *phase, double *value);
+static_assert(std::is_same<decltype(&cfx_set_tl_plan_device), cfx_set_tl_plan_device_fn>::value, "cfx_set_tl_plan_device");
+static_assert(std::is_same<decltype(&cfx_set_tl_plan), cfx_set_tl_plan_fn>::value, "cfx_set_tl_plan");
+static_assert(std::is_same<decltype(&cfx_get_tl_phase_durations_device), cfx_get_tl_phase_durations_device_fn>::value,
+              "cfx_get_tl_phase_durations_device");
+static_assert(std::is_same<decltype(&cfx_get_tl_phase_durations), cfx_get_tl_phase_durations_fn>::value, "cfx_get_tl_phase_durations");
+static_assert(std::is_same<decltype(&cfx_restore_tl_plan), cfx_restore_tl_plan_fn>::value, "cfx_restore_tl_plan");
+static_assert(std::is_same<decltype(&cfx_tl_plan_error), cfx_tl_plan_error_fn>::value, "cfx_tl_plan_error");
+
+// what every plan call checks first: not on a tile (its lights are another tile's too), the caller's row length
+static int tlPlanArgs(cfx_engine *e, int32_t maxPhases, const char *what) {
+    if (e->tiled) {
+        e->err = std::string(what) + ": not on a tile";
+        return CFX_ERR_STATE;
+    }
+    if (maxPhases != e->planMaxPhases) {
+        e->err = std::string(what) + ": max_phases must be the network's " + std::to_string(e->planMaxPhases) + ", not " +
+                 std::to_string(maxPhases);
+        return CFX_ERR_INVALID;
+    }
+    return CFX_OK;
+}
+
+static void launchSetTlPlan(cfx_engine *e, const double *durations, const int32_t *phase, const double *remain) {
+    const TlPlanIn in{durations, phase, remain, e->I, e->planMaxPhases, e->cfg.interval, ++e->planCalls};
+    hipLaunchKernelGGL(k_set_tl_plan, dim3(1), dim3(1024), 0, e->stream, in, e->net.interPhaseStart, e->net.interVirtual, e->phaseTime,
+                       e->curPhase, e->remain, e->hPlanErr);
+}
+
+int32_t cfx_set_tl_plan_device(cfx_engine *e, const double *durations, const int32_t *phase, const double *remain, int32_t n,
+                               int32_t maxPhases, void *producerStream) {
+    if (!e || (!durations && !phase && !remain) || n != e->I) return CFX_ERR_INVALID;
+    auto fail = [e](const std::string &m) { return e->fail(m); };
+    HIP_TRY(hipSetDevice(e->device));
+    int rc;
+    if ((rc = tlPlanArgs(e, maxPhases, "cfx_set_tl_plan_device"))) return rc;
+    if (durations && (rc = checkDevicePointer(e, durations, "cfx_set_tl_plan_device: durations"))) return rc;
+    if (phase && (rc = checkDevicePointer(e, phase, "cfx_set_tl_plan_device: phase"))) return rc;
+    if (remain && (rc = checkDevicePointer(e, remain, "cfx_set_tl_plan_device: remain"))) return rc;
+    if ((rc = e->settle(false))) return rc;  // (as cfx_set_tl_phases_device: the deferred commit advances the lights of the last step first)
+    if ((rc = e->orderAfterCaller((hipStream_t) producerStream))) return rc;
+    launchSetTlPlan(e, durations, phase, remain);
+    HIP_TRY(hipGetLastError());
+    return e->orderCallerAfter((hipStream_t) producerStream);
+}
+
+int32_t cfx_set_tl_plan(cfx_engine *e, const double *durations, const int32_t *phase, const double *remain, int32_t n, int32_t maxPhases) {
+    if (!e || (!durations && !phase && !remain) || n != e->I) return CFX_ERR_INVALID;
+    auto fail = [e](const std::string &m) { return e->fail(m); };
+    HIP_TRY(hipSetDevice(e->device));
+    int rc;
+    if ((rc = tlPlanArgs(e, maxPhases, "cfx_set_tl_plan"))) return rc;
+    if ((rc = e->settle(false))) return rc;
+    const size_t nI = (size_t) e->I, nD = nI * (size_t) e->planMaxPhases;
+    if (!e->planD && (rc = e->allocRaw(&e->planD, nD + nI))) return rc;
+    if (!e->planI && (rc = e->allocRaw(&e->planI, nI))) return rc;
+    if (durations && nD) HIP_TRY(hipMemcpyAsync(e->planD, durations, nD * sizeof(double), hipMemcpyHostToDevice, e->stream));
+    if (phase && nI) HIP_TRY(hipMemcpyAsync(e->planI, phase, nI * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
+    if (remain && nI) HIP_TRY(hipMemcpyAsync(e->planD + nD, remain, nI * sizeof(double), hipMemcpyHostToDevice, e->stream));
+    launchSetTlPlan(e, durations ? e->planD : nullptr, phase ? e->planI : nullptr, remain ? e->planD + nD : nullptr);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    return CFX_OK;
+}
+
+static void launchGetPhaseDurations(cfx_engine *e, double *out) {
+    const size_t total = (size_t) e->I * (size_t) e->planMaxPhases;
+    if (!total) return;
+    hipLaunchKernelGGL(k_get_phase_durations, dim3(gridFor((int) std::min<size_t>(total, 1u << 20))), dim3(kBlock), 0, e->stream, e->I,
+                       e->planMaxPhases, e->net.interPhaseStart, e->net.interVirtual, e->phaseTime, out);
+}
+
+// (no settle: the durations are written by the calls above and by nothing a step launches)
+int32_t cfx_get_tl_phase_durations_device(cfx_engine *e, double *out, int32_t maxPhases, void *consumerStream) {
+    if (!e || !out) return CFX_ERR_INVALID;
+    auto fail = [e](const std::string &m) { return e->fail(m); };
+    HIP_TRY(hipSetDevice(e->device));
+    int rc;
+    if ((rc = tlPlanArgs(e, maxPhases, "cfx_get_tl_phase_durations_device"))) return rc;
+    if ((rc = checkDevicePointer(e, out, "cfx_get_tl_phase_durations_device: out"))) return rc;
+    if ((rc = e->orderAfterCaller((hipStream_t) consumerStream))) return rc;
+    launchGetPhaseDurations(e, out);
+    HIP_TRY(hipGetLastError());
+    return e->orderCallerAfter((hipStream_t) consumerStream);
+}
+
+int32_t cfx_get_tl_phase_durations(cfx_engine *e, double *out, int32_t maxPhases) {
+    if (!e || !out) return CFX_ERR_INVALID;
+    auto fail = [e](const std::string &m) { return e->fail(m); };
+    HIP_TRY(hipSetDevice(e->device));
+    int rc;
+    if ((rc = tlPlanArgs(e, maxPhases, "cfx_get_tl_phase_durations"))) return rc;
+    const size_t nI = (size_t) e->I, nD = nI * (size_t) e->planMaxPhases;
+    if (!e->planD && (rc = e->allocRaw(&e->planD, nD + nI))) return rc;
+    launchGetPhaseDurations(e, e->planD);
+    HIP_TRY(hipGetLastError());
+    if (nD) HIP_TRY(hipMemcpyAsync(out, e->planD, nD * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    return CFX_OK;
+}
+
+int32_t cfx_restore_tl_plan(cfx_engine *e) {
+    if (!e) return CFX_ERR_INVALID;
+    auto fail = [e](const std::string &m) { return e->fail(m); };
+    HIP_TRY(hipSetDevice(e->device));
+    int rc;
+    if ((rc = tlPlanArgs(e, e->planMaxPhases, "cfx_restore_tl_plan"))) return rc;
+    if ((rc = e->settle(false))) return rc;  // (the last step's lights advance on the durations that were in force for it)
+    if (e->nPhaseTimes)
+        HIP_TRY(hipMemcpyAsync(e->phaseTime, e->phaseTimeFile, (size_t) e->nPhaseTimes * sizeof(double), hipMemcpyDeviceToDevice, e->stream));
+    return CFX_OK;
+}
+
+int32_t cfx_tl_plan_error(cfx_engine *e, int32_t *what, int32_t *inter, int32_t *phase, double *value) {
+    if (!e) return CFX_ERR_INVALID;
+    volatile TlPlanErr *rec = e->hPlanErr;
+    const bool decided = rec->done - e->planCalls >= 0;  // (every set call enqueued so far has validated)
+    std::atomic_thread_fence(std::memory_order_acquire);
+    const int32_t i = rec->inter;
+    if (i < 0) return decided ? 0 : 2;
+    std::atomic_thread_fence(std::memory_order_acquire);
+    if (what) *what = rec->what;
+    if (inter) *inter = i;
+    if (phase) *phase = rec->phase;
+    if (value) *value = rec->value;
+    rec->inter = -1;
     return 1;
 }
 

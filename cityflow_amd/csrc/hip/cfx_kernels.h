@@ -1890,6 +1890,121 @@ __global__ void __launch_bounds__(1024) k_set_phases_dense(const int32_t *phases
     }
 }
 
+// cfx_set_tl_plan_device / cfx_set_tl_plan (include/cityflow_amd.h): the durations in force (n.phaseTime itself — every reader
+// indexes it anew each step), the current phase and its remaining time, from [I, P]-padded / [I] arrays; any of the three
+// null.  k_set_phases_dense's pattern: ONE workgroup, a thread per intersection validates all of it (its row's sum in p order,
+// so the number is the same whichever thread takes the row), the block agrees on the lowest failing check, and only then
+// does the same thread apply its rows — or thread 0 records the offender and nothing is written.  Checks are ordered by
+// key = intersection * (P + 3) + {p | P: the sum | P + 1: phase | P + 2: remain}.
+struct TlPlanIn {
+    const double *durations;
+    const int32_t *phase;
+    const double *remain;
+    int n, maxPhases;
+    double interval;
+    int32_t seq;  // the number of this call: left in TlPlanErr::done when the kernel has decided
+};
+struct TlPlanErr {  // pinned, host-mapped; inter < 0: no record (written behind the record's other fields, before `done`)
+    int32_t inter, what, phase;
+    int32_t done;  // the last call that has validated (and recorded its offender, if any): what the host compares with the calls it made
+    double value;
+};
+__device__ inline bool tlPlanSeconds(double x) { return x >= 0.0 && x < __builtin_huge_val(); }  // finite, not negative, not NaN
+__device__ inline double tlPlanSum(const TlPlanIn &a, const double *phaseTime, int i, int ps, int np) {
+    double sum = 0.0;
+    for (int p = 0; p < np; ++p) {
+        const double d = a.durations[(size_t) i * a.maxPhases + p];
+        sum += d != d ? phaseTime[ps + p] : d;
+    }
+    return sum;
+}
+__global__ void __launch_bounds__(1024) k_set_tl_plan(TlPlanIn a, const int32_t *interPhaseStart, const int32_t *interVirtual,
+                                                      double *phaseTime, int32_t *curPhase, double *remain, TlPlanErr *err) {
+    constexpr unsigned long long kNone = ~0ull;
+    __shared__ unsigned long long firstBad;
+    if (threadIdx.x == 0) firstBad = kNone;
+    __syncthreads();
+    const unsigned long long slots = (unsigned long long) a.maxPhases + 3;
+    for (int i = threadIdx.x; i < a.n; i += blockDim.x) {
+        if (interVirtual[i]) continue;
+        const int ps = interPhaseStart[i], np = interPhaseStart[i + 1] - ps;
+        unsigned long long bad = kNone;
+        if (a.remain) {
+            const double r = a.remain[i];
+            if (r == r && !tlPlanSeconds(r)) bad = (unsigned long long) a.maxPhases + 2;
+        }
+        if (a.phase) {
+            const int p = a.phase[i];
+            if (p < -1 || p >= np) bad = (unsigned long long) a.maxPhases + 1;
+        }
+        if (a.durations) {
+            if (!(tlPlanSum(a, phaseTime, i, ps, np) >= a.interval)) bad = (unsigned long long) a.maxPhases;
+            for (int p = np - 1; p >= 0; --p) {
+                const double d = a.durations[(size_t) i * a.maxPhases + p];
+                if (d == d && !tlPlanSeconds(d)) bad = (unsigned long long) p;
+            }
+        }
+        if (bad != kNone) atomicMin(&firstBad, (unsigned long long) i * slots + bad);
+    }
+    __syncthreads();
+    const unsigned long long bad = firstBad;
+    if (bad == kNone) {
+        for (int i = threadIdx.x; i < a.n; i += blockDim.x) {
+            if (interVirtual[i]) continue;
+            const int ps = interPhaseStart[i], np = interPhaseStart[i + 1] - ps;
+            if (a.durations)
+                for (int p = 0; p < np; ++p) {
+                    const double d = a.durations[(size_t) i * a.maxPhases + p];
+                    if (d == d) phaseTime[ps + p] = d;
+                }
+            if (a.phase && a.phase[i] >= 0) curPhase[i] = a.phase[i];
+            if (a.remain) {
+                const double r = a.remain[i];
+                if (r == r) remain[i] = r;
+            }
+        }
+        if (threadIdx.x == 0) {
+            volatile TlPlanErr *rec = err;
+            rec->done = a.seq;
+            __threadfence_system();
+        }
+    } else if (threadIdx.x == 0) {
+        volatile TlPlanErr *rec = err;
+        if (rec->inter < 0) {
+            const int i = (int) (bad / slots), slot = (int) (bad % slots);
+            const int ps = interPhaseStart[i], np = interPhaseStart[i + 1] - ps;
+            if (slot < a.maxPhases) {
+                rec->what = CFX_TL_PLAN_DURATION;
+                rec->phase = slot;
+                rec->value = a.durations[(size_t) i * a.maxPhases + slot];
+            } else {
+                rec->what = CFX_TL_PLAN_SUM + (slot - a.maxPhases);  // (CFX_TL_PLAN_SUM, _PHASE, _REMAIN follow each other)
+                rec->phase = -1;
+                rec->value = slot == a.maxPhases       ? tlPlanSum(a, phaseTime, i, ps, np)
+                             : slot == a.maxPhases + 1 ? (double) a.phase[i]
+                                                       : a.remain[i];
+            }
+            __threadfence_system();
+            rec->inter = i;
+        }
+        __threadfence_system();
+        rec->done = a.seq;
+        __threadfence_system();
+    }
+}
+
+// cfx_get_tl_phase_durations_device / cfx_get_tl_phase_durations: the durations in force as [I, P] rows, 0.0 in the padding and at
+// virtual intersections (whose one phase of the file is no signal plan); every element is written
+__global__ void k_get_phase_durations(int nInters, int maxPhases, const int32_t *interPhaseStart, const int32_t *interVirtual,
+                                      const double *phaseTime, double *out) {
+    const size_t total = (size_t) nInters * maxPhases, stride = (size_t) gridDim.x * blockDim.x;
+    for (size_t x = (size_t) blockIdx.x * blockDim.x + threadIdx.x; x < total; x += stride) {
+        const int i = (int) (x / maxPhases), p = (int) (x % maxPhases);
+        const int ps = interPhaseStart[i];
+        out[x] = (!interVirtual[i] && p < interPhaseStart[i + 1] - ps) ? phaseTime[ps + p] : 0.0;
+    }
+}
+
 __global__ void k_refresh_next(StepCtx c) {  // after cfx_load_state: Router::getNextDrivable(0) of every vehicle
     const int S = c.segStart[c.n.L + c.n.K];
     const int stride = gridDim.x * blockDim.x;

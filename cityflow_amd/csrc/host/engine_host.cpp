@@ -112,6 +112,12 @@ void Backend::open(const std::string &libPath) {
     CFX_FN_OPTIONAL(cfx_get_movement_flow)
     CFX_FN_OPTIONAL(cfx_movement_flow_get_state)
     CFX_FN_OPTIONAL(cfx_movement_flow_set_state)
+    CFX_FN_OPTIONAL(cfx_set_tl_plan_device)
+    CFX_FN_OPTIONAL(cfx_set_tl_plan)
+    CFX_FN_OPTIONAL(cfx_get_tl_phase_durations_device)
+    CFX_FN_OPTIONAL(cfx_get_tl_phase_durations)
+    CFX_FN_OPTIONAL(cfx_restore_tl_plan)
+    CFX_FN_OPTIONAL(cfx_tl_plan_error)
 #undef CFX_FN_OPTIONAL
     if (cfx_abi_version() != CFX_ABI_VERSION)
         throw std::runtime_error("cityflow_amd: ABI version mismatch in '" + libPath + "'");
@@ -261,6 +267,7 @@ EngineHost::EngineHost(const std::string &configFile, int threadNum, const std::
     flow_.bind(&be_, dev_, (int) net_->lanes.size());
     move_.bind(&be_, dev_, &net_->flat(), 1);
     trip_.bind(&be_, dev_, 1, interval_);
+    plan_.bind(&be_, dev_, net_.get(), 1, false);
 }
 
 EngineHost::~EngineHost() {
@@ -464,13 +471,122 @@ void EngineHost::sync() {
 }
 
 void EngineHost::raiseDeviceError() {
-    if (!devicePhaseUnchecked_) return;
-    devicePhaseUnchecked_ = false;
-    int32_t inter = -1, phase = 0;
-    if (be_.cfx_device_error(dev_, &inter, &phase) != 1) return;
-    const std::string id = inter >= 0 && inter < (int) net_->inters.size() ? net_->inters[(size_t) inter].id : std::to_string(inter);
-    throw std::out_of_range("set_tl_phases_tensor: phase " + std::to_string(phase) + " out of range for intersection '" + id +
-                            "' (the call was not applied)");
+    if (devicePhaseUnchecked_) {
+        devicePhaseUnchecked_ = false;
+        int32_t inter = -1, phase = 0;
+        if (be_.cfx_device_error(dev_, &inter, &phase) == 1) {
+            const std::string id = inter >= 0 && inter < (int) net_->inters.size() ? net_->inters[(size_t) inter].id : std::to_string(inter);
+            throw std::out_of_range("set_tl_phases_tensor: phase " + std::to_string(phase) + " out of range for intersection '" + id +
+                                    "' (the call was not applied)");
+        }
+    }
+    plan_.raise();
+}
+
+// ---------------------------------------------------------------- the signal plan as engine state
+void TlPlan::bind(const Backend *be, cfx_engine *dev, const HostRoadNet *net, int nEnvs, bool namesEnv) {
+    be_ = be;
+    dev_ = dev;
+    net_ = net;
+    nEnvs_ = nEnvs;
+    namesEnv_ = namesEnv;
+    I_ = (int) net->inters.size();
+    P_ = 0;
+    for (const HostInter &in : net->inters)
+        if (!in.isVirtual) P_ = std::max(P_, (int) in.phases.size());
+}
+
+void TlPlan::need(const char *what) const {
+    if (!available())
+        throw std::logic_error(std::string(what) + ": the backend '" + (be_ ? be_->path : std::string()) +
+                               "' does not keep the signal plan as engine state");
+}
+
+void TlPlan::check(int32_t rc, const char *what) const {
+    if (rc == CFX_OK) return;
+    const char *msg = be_->cfx_last_error(dev_);
+    throw std::runtime_error(std::string("cityflow_amd: ") + what + " failed (" + std::to_string(rc) + "): " + (msg ? msg : ""));
+}
+
+void TlPlan::setDevice(uintptr_t durations, uintptr_t phase, uintptr_t remain, uintptr_t producerStream) {
+    need("set_tl_plan_tensor");
+    check(be_->cfx_set_tl_plan_device(dev_, (const double *) durations, (const int32_t *) phase, (const double *) remain,
+                                      (int32_t) (nEnvs_ * I_), P_, (void *) producerStream),
+          "cfx_set_tl_plan_device");
+    unchecked_ = true;
+}
+
+void TlPlan::durationsDevice(uintptr_t out, uintptr_t consumerStream) {
+    need("get_tl_phase_durations_tensor");
+    check(be_->cfx_get_tl_phase_durations_device(dev_, (double *) out, P_, (void *) consumerStream), "cfx_get_tl_phase_durations_device");
+}
+
+void TlPlan::set(const double *durations, const int32_t *phase, const double *remain) {
+    need("set_tl_plan");
+    check(be_->cfx_set_tl_plan(dev_, durations, phase, remain, (int32_t) (nEnvs_ * I_), P_), "cfx_set_tl_plan");
+    unchecked_ = true;
+}
+
+void TlPlan::durations(double *out) {
+    need("get_tl_phase_durations_array");
+    check(be_->cfx_get_tl_phase_durations(dev_, out, P_), "cfx_get_tl_phase_durations");
+}
+
+void TlPlan::restore() {
+    need("restore_tl_plan");
+    check(be_->cfx_restore_tl_plan(dev_), "cfx_restore_tl_plan");
+}
+
+void TlPlan::raise() {
+    if (!unchecked_) return;
+    int32_t what = 0, inter = -1, phase = -1;
+    double value = 0.0;
+    const int32_t found = be_->cfx_tl_plan_error(dev_, &what, &inter, &phase, &value);
+    if (found == 2) return;  // (this call did not wait for the set call after all — a getter before the first step: the next one asks again)
+    unchecked_ = found == 1;  // (a record may stand for an earlier call than the last: the next waiting call asks once more)
+    if (found != 1) return;
+    const int env = I_ > 0 ? inter / I_ : 0, local = I_ > 0 ? inter % I_ : inter;
+    std::string where = "intersection '" + (local >= 0 && local < I_ ? net_->inters[(size_t) local].id : std::to_string(local)) + "'";
+    if (namesEnv_) where += " of env " + std::to_string(env);
+    char num[64];
+    snprintf(num, sizeof num, "%.17g", value);
+    std::string m = "set_tl_plan: ";
+    switch (what) {
+    case CFX_TL_PLAN_DURATION:
+        m += "durations: " + std::string(num) + " for phase " + std::to_string(phase) + " of " + where + " is negative or not finite";
+        break;
+    case CFX_TL_PLAN_SUM:
+        m += "durations: the phases of " + where + " would sum to " + num + " s, less than the step interval";
+        break;
+    case CFX_TL_PLAN_PHASE:
+        m += "phase: " + std::to_string((long long) value) + " out of range for " + where;
+        break;
+    default:
+        m += "phase_remain: " + std::string(num) + " for " + where + " is negative or not finite";
+    }
+    throw std::invalid_argument(m + " (the call was not applied)");
+}
+
+void EngineHost::setTlPlanDevice(uintptr_t durations, uintptr_t phase, uintptr_t remain, uintptr_t producerStream) {
+    if (phase) {
+        flushPhases();  // (single sets made before this call land first, as they were made)
+        forgetPhases();
+    }
+    plan_.setDevice(durations, phase, remain, producerStream);
+}
+
+void EngineHost::setTlPlan(const double *durations, const int32_t *phase, const double *remain) {
+    if (phase) {
+        flushPhases();
+        forgetPhases();
+    }
+    plan_.set(durations, phase, remain);
+    raiseDeviceError();
+}
+
+void EngineHost::tlPhaseDurations(double *out) {
+    plan_.durations(out);
+    raiseDeviceError();
 }
 
 std::pair<uintptr_t, int> EngineHost::streamHandle() {
@@ -913,7 +1029,7 @@ void EngineHost::reset(bool resetRnd) {
     pendingPhaseInter_.clear();  // TrafficLight::reset puts every light back to phase 0 anyway
     pendingPhaseValue_.clear();
     forgetPhases();
-    if (devicePhaseUnchecked_) {  // (a rejected device-side signal set is reported before the reset, not lost in it)
+    if (devicePhaseUnchecked_ || plan_.unchecked()) {  // (a rejected device-side signal set is reported before the reset, not lost in it)
         check(be_.cfx_sync(dev_), "cfx_sync");
         raiseDeviceError();
     }

@@ -112,6 +112,17 @@ struct Backend {
     cfx_get_movement_flow_fn cfx_get_movement_flow = nullptr;
     cfx_movement_flow_get_state_fn cfx_movement_flow_get_state = nullptr;
     cfx_movement_flow_set_state_fn cfx_movement_flow_set_state = nullptr;
+    // optional as a set: the fixed-time signal plan as engine state (without them there is no such call: TlPlan below)
+    cfx_set_tl_plan_device_fn cfx_set_tl_plan_device = nullptr;
+    cfx_set_tl_plan_fn cfx_set_tl_plan = nullptr;
+    cfx_get_tl_phase_durations_device_fn cfx_get_tl_phase_durations_device = nullptr;
+    cfx_get_tl_phase_durations_fn cfx_get_tl_phase_durations = nullptr;
+    cfx_restore_tl_plan_fn cfx_restore_tl_plan = nullptr;
+    cfx_tl_plan_error_fn cfx_tl_plan_error = nullptr;
+    bool hasTlPlan() const {
+        return hasDeviceBuffers() && cfx_set_tl_plan_device && cfx_set_tl_plan && cfx_get_tl_phase_durations_device &&
+               cfx_get_tl_phase_durations && cfx_restore_tl_plan && cfx_tl_plan_error;
+    }
     void open(const std::string &libPath);  // throws std::runtime_error
     ~Backend();
 };
@@ -156,6 +167,36 @@ struct InterFeatures {
 // backend's message).  `lay`: one environment's layout, `nLanes` / `nLaneLinks`: of one environment
 void intersectionFeaturesOf(const Backend &be, cfx_engine *dev, const InterLayout &lay, int nEnvs, int nLanes, int nLaneLinks,
                             const InterFeatures &out);
+
+// The fixed-time signal plan as engine state (cfx_set_tl_plan_device and its kin; the public calls are cityflow_amd/torch_io.py):
+// what EngineHost and VectorEngineHost share.  Arrays cover every environment, env-major: durations [nEnvs * I * P] (P = the
+// largest phase count of a signalised intersection), phase / remain [nEnvs * I]; any of the three may be null.  The caller
+// holds whatever lock its ABI calls need.  A backend without the entry points: std::logic_error from every call.
+class TlPlan {
+public:
+    void bind(const Backend *be, cfx_engine *dev, const HostRoadNet *net, int nEnvs, bool namesEnv);
+    bool available() const { return be_ && be_->hasTlPlan(); }
+    int maxPhases() const { return P_; }
+    // device addresses, ordered against the caller's stream; a rejected call shows in raise() once the device has run it
+    void setDevice(uintptr_t durations, uintptr_t phase, uintptr_t remain, uintptr_t producerStream);
+    void durationsDevice(uintptr_t out, uintptr_t consumerStream);
+    // host memory, synchronous: set() throws at once what raise() would
+    void set(const double *durations, const int32_t *phase, const double *remain);
+    void durations(double *out);
+    void restore();
+    bool unchecked() const { return unchecked_; }
+    // after a call that has waited for the device: std::invalid_argument naming the entry that rejected a set call
+    void raise();
+
+private:
+    void need(const char *what) const;
+    void check(int32_t rc, const char *what) const;
+    const Backend *be_ = nullptr;
+    cfx_engine *dev_ = nullptr;
+    const HostRoadNet *net_ = nullptr;
+    int nEnvs_ = 1, I_ = 0, P_ = 0;
+    bool namesEnv_ = false, unchecked_ = false;
+};
 
 // the four front-vehicle outputs in host memory ([n_lanes * k] each, of every environment; any may be null)
 struct LaneFronts {
@@ -231,6 +272,13 @@ public:
     void setTrafficLightPhasesDevice(uintptr_t phases, size_t n, uintptr_t producerStream);
     bool rlTrafficLight() const { return rlTrafficLight_; }
     std::vector<int32_t> phaseCounts() const;  // [n_intersections] phases per intersection, -1 for virtual ones
+    // ---- the fixed-time signal plan as engine state (TlPlan above): durations [I * P], phase / remain [I], any null
+    bool tlPlanCalls() const { return plan_.available(); }
+    void setTlPlanDevice(uintptr_t durations, uintptr_t phase, uintptr_t remain, uintptr_t producerStream);
+    void setTlPlan(const double *durations, const int32_t *phase, const double *remain);
+    void tlPhaseDurationsDevice(uintptr_t out, uintptr_t consumerStream) { plan_.durationsDevice(out, consumerStream); }
+    void tlPhaseDurations(double *out);
+    void restoreTlPlan() { plan_.restore(); }
     // ---- per-lane speed and position features (cfx_observe_lanes_device / cfx_get_lane_features; the twin: from the vehicles)
     std::vector<double> laneLengths() const;  // [n_lanes] Lane::getLength
     // speedSum [n_lanes], bins [n_lanes * nBins] (either may be null), edges: [n_lanes][nBins + 1] or [nBins + 1]
@@ -328,7 +376,8 @@ private:
     // a device-side signal set was enqueued whose offender record has not been read since: every call below that has waited
     // for the device reads it (raiseDeviceError), and throws std::out_of_range naming the intersection it rejected
     bool devicePhaseUnchecked_ = false;
-    void raiseDeviceError();
+    void raiseDeviceError();  // (then a rejected plan: TlPlan::raise, std::invalid_argument)
+    TlPlan plan_;
 
     std::shared_ptr<HostRoadNet> net_ = std::make_shared<HostRoadNet>();
     Spawner spawner_;

@@ -8,6 +8,7 @@
 
 #include <chrono>
 #include <iostream>
+#include <optional>
 
 #include "archive.h"
 #include "engine_host.h"
@@ -431,9 +432,49 @@ void observeTripsDevice(E &e, uintptr_t entered, uintptr_t admitted, uintptr_t b
     e.observeTripsDevice(o, consumerStream);
 }
 
+// VectorEngine(seeds=...): None -> empty (seed + env index); anything else must hold one seed per environment
+std::vector<int> envSeeds(int envs, const std::optional<std::vector<int>> &seeds) {
+    if (!seeds) return {};
+    if (envs < 1 || seeds->size() != (size_t) envs)
+        throw std::invalid_argument("VectorEngine: seeds must hold num_envs = " + std::to_string(envs) + " seeds, not " +
+                                    std::to_string(seeds->size()));
+    return *seeds;
+}
+
+// ---- the fixed-time signal plan as engine state (Engine and VectorEngine; the public calls are cityflow_amd/torch_io.py)
+inline py::ssize_t planRows(EngineHost &e) { return (py::ssize_t) e.net().inters.size(); }
+inline py::ssize_t planRows(cfa::VectorEngineHost &e) { return (py::ssize_t) e.numEnvs() * e.numIntersections(); }
+
+template <typename E> void setTlPlanArrays(E &e, const py::object &durations, const py::object &phase, const py::object &remain) {
+    using DArr = py::array_t<double, py::array::c_style | py::array::forcecast>;
+    using IArr = py::array_t<int32_t, py::array::c_style | py::array::forcecast>;
+    const py::ssize_t rows = planRows(e), P = e.intersectionLayout().P;
+    DArr d, r;
+    IArr p;
+    if (!durations.is_none()) d = durations.cast<DArr>();
+    if (!phase.is_none()) p = phase.cast<IArr>();
+    if (!remain.is_none()) r = remain.cast<DArr>();
+    if ((!durations.is_none() && d.size() != rows * P) || (!phase.is_none() && p.size() != rows) || (!remain.is_none() && r.size() != rows))
+        throw std::invalid_argument("set_tl_plan: an array of the wrong size");
+    e.setTlPlan(durations.is_none() ? nullptr : d.data(), phase.is_none() ? nullptr : p.data(), remain.is_none() ? nullptr : r.data());
+}
+
+template <typename E> py::array_t<double> tlPhaseDurationsArray(E &e) {
+    py::array_t<double> out(planRows(e) * (py::ssize_t) e.intersectionLayout().P);
+    e.tlPhaseDurations(out.mutable_data());
+    return out;
+}
+
 // Device buffers: raw pointers and streams under the tensor methods of cityflow_amd/torch_io.py (Engine and VectorEngine alike)
 template <typename E> void defDeviceBuffers(py::class_<E> &c) {
     c.def("_device_buffers", &E::deviceBuffers, "the backend takes observations / signals in device memory")
+        .def("_tl_plan_calls", &E::tlPlanCalls, "the backend keeps the signal plan as engine state (set_tl_plan_tensor and its kin)")
+        .def("_set_tl_plan_device", &E::setTlPlanDevice, "durations_ptr"_a, "phase_ptr"_a, "phase_remain_ptr"_a, "producer_stream"_a)
+        .def("_set_tl_plan", &setTlPlanArrays<E>, "durations"_a, "phase"_a, "phase_remain"_a,
+             "float64 [.., I, P] / int32 [.., I] / float64 [.., I] or None each; waits for the device")
+        .def("_tl_phase_durations_device", &E::tlPhaseDurationsDevice, "out_ptr"_a, "consumer_stream"_a)
+        .def("_tl_phase_durations", &tlPhaseDurationsArray<E>, "float64, flat (env-major, then intersection, then phase)")
+        .def("_restore_tl_plan", &E::restoreTlPlan)
         .def("_stream_handle", &E::streamHandle, "(engine's hipStream_t as an int, HIP device ordinal)")
         .def("_set_tl_phases_device", &E::setTrafficLightPhasesDevice, "phases_ptr"_a, "n"_a, "producer_stream"_a)
         .def("_rl_traffic_light", &E::rlTrafficLight)
@@ -870,17 +911,22 @@ PYBIND11_MODULE(_cityflow, m) {
 
     using cfa::VectorEngineHost;
     py::class_<VectorEngineHost> vectorClass(m, "VectorEngine",
-                                             "num_envs independent copies of one scenario (env e uses seed + e) advanced in "
+                                             "num_envs independent copies of one scenario (env e uses seed + e, or seeds[e]) advanced in "
                                              "lock-step by one device engine; observations and actions are arrays of shape "
                                              "[num_envs, ...].");
     vectorClass
-        .def(py::init<const std::string &, int, int>(), "config_file"_a, "num_envs"_a, "thread_num"_a = 1)
+        .def(py::init([](const std::string &cfg, int envs, int threads, const std::optional<std::vector<int>> &seeds) {
+                 return std::unique_ptr<VectorEngineHost>(new VectorEngineHost(cfg, envs, threads, "", envSeeds(envs, seeds)));
+             }),
+             "config_file"_a, "num_envs"_a, "thread_num"_a = 1, "seeds"_a = py::none(),
+             "seeds: num_envs ints, one per environment, instead of seed + env index (also on reset(seed=True)); equal seeds give "
+             "every environment the same demand")
         .def_static(
             "_with_backend",
-            [](const std::string &cfg, int envs, int threads, const std::string &lib) {
-                return std::unique_ptr<VectorEngineHost>(new VectorEngineHost(cfg, envs, threads, lib));
+            [](const std::string &cfg, int envs, int threads, const std::string &lib, const std::optional<std::vector<int>> &seeds) {
+                return std::unique_ptr<VectorEngineHost>(new VectorEngineHost(cfg, envs, threads, lib, envSeeds(envs, seeds)));
             },
-            "config_file"_a, "num_envs"_a, "thread_num"_a, "backend_library"_a)
+            "config_file"_a, "num_envs"_a, "thread_num"_a, "backend_library"_a, "seeds"_a = py::none())
         .def_property_readonly("num_envs", &VectorEngineHost::numEnvs)
         .def("_host_seconds", &VectorEngineHost::hostSeconds,
              "[spawners, record translation, cfx_step] cumulative host wall seconds since the last reset")

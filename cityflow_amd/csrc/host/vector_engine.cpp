@@ -117,9 +117,13 @@ struct ReplicatedNet {
 
 }  // namespace
 
-VectorEngineHost::VectorEngineHost(const std::string &configFile, int numEnvs, int threadNum, const std::string &backendLib)
+VectorEngineHost::VectorEngineHost(const std::string &configFile, int numEnvs, int threadNum, const std::string &backendLib,
+                                   const std::vector<int> &seeds)
     : R_(numEnvs) {
     if (numEnvs < 1) throw std::runtime_error("VectorEngine: num_envs must be >= 1");
+    if (!seeds.empty() && seeds.size() != (size_t) numEnvs)
+        throw std::invalid_argument("VectorEngine: seeds must hold num_envs = " + std::to_string(numEnvs) + " seeds, not " +
+                                    std::to_string(seeds.size()));
     EngineConfig cfg = readEngineConfig(configFile);
     laneChange_ = cfg.laneChange;
     interval_ = cfg.interval;
@@ -130,7 +134,7 @@ VectorEngineHost::VectorEngineHost(const std::string &configFile, int numEnvs, i
         net_->load(cfg.dir + cfg.roadnetFile);
         for (int r = 0; r < R_; ++r) {
             spawners_.emplace_back(new Spawner());
-            spawners_.back()->init(net_.get(), interval_, threadNum, cfg.seed + r);
+            spawners_.back()->init(net_.get(), interval_, threadNum, seeds.empty() ? cfg.seed + r : seeds[(size_t) r]);
             spawners_.back()->exactPeekOnly = cfg.exactShadowPeek;
             spawners_.back()->loadFlows(cfg.dir + cfg.flowFile);
         }
@@ -182,6 +186,7 @@ VectorEngineHost::VectorEngineHost(const std::string &configFile, int numEnvs, i
     flow_.bind(&be_, dev_, R_ * L_);
     move_.bind(&be_, dev_, &net_->flat(), R_);
     trip_.bind(&be_, dev_, R_, interval_);
+    plan_.bind(&be_, dev_, net_.get(), R_, true);
 }
 
 VectorEngineHost::~VectorEngineHost() {
@@ -543,7 +548,7 @@ void VectorEngineHost::reset(bool resetRnd) {
     settleLaneChange();  // (without a reseed the generators go on from behind the last step's shadow draws)
     {
         std::lock_guard<std::mutex> guard(queryMutex_);
-        if (devicePhaseUnchecked_) {  // (a rejected device-side signal set is reported before the reset, not lost in it)
+        if (devicePhaseUnchecked_ || plan_.unchecked()) {  // (a rejected device-side signal set is reported before the reset, not lost in it)
             check(be_.cfx_sync(dev_), "cfx_sync");
             raiseDeviceError();
         }
@@ -598,14 +603,44 @@ void VectorEngineHost::sync() {
 }
 
 void VectorEngineHost::raiseDeviceError() {
-    if (!devicePhaseUnchecked_) return;
-    devicePhaseUnchecked_ = false;
-    int32_t inter = -1, phase = 0;
-    if (be_.cfx_device_error(dev_, &inter, &phase) != 1) return;
-    const int env = I_ > 0 ? inter / I_ : 0, local = I_ > 0 ? inter % I_ : inter;
-    const std::string id = local >= 0 && local < I_ ? net_->inters[(size_t) local].id : std::to_string(local);
-    throw std::out_of_range("set_tl_phases_tensor: phase " + std::to_string(phase) + " out of range for intersection '" + id +
-                            "' of env " + std::to_string(env) + " (the call was not applied)");
+    if (devicePhaseUnchecked_) {
+        devicePhaseUnchecked_ = false;
+        int32_t inter = -1, phase = 0;
+        if (be_.cfx_device_error(dev_, &inter, &phase) == 1) {
+            const int env = I_ > 0 ? inter / I_ : 0, local = I_ > 0 ? inter % I_ : inter;
+            const std::string id = local >= 0 && local < I_ ? net_->inters[(size_t) local].id : std::to_string(local);
+            throw std::out_of_range("set_tl_phases_tensor: phase " + std::to_string(phase) + " out of range for intersection '" + id +
+                                    "' of env " + std::to_string(env) + " (the call was not applied)");
+        }
+    }
+    plan_.raise();
+}
+
+void VectorEngineHost::setTlPlanDevice(uintptr_t durations, uintptr_t phase, uintptr_t remain, uintptr_t producerStream) {
+    std::lock_guard<std::mutex> guard(queryMutex_);
+    plan_.setDevice(durations, phase, remain, producerStream);
+}
+
+void VectorEngineHost::setTlPlan(const double *durations, const int32_t *phase, const double *remain) {
+    std::lock_guard<std::mutex> guard(queryMutex_);
+    plan_.set(durations, phase, remain);
+    raiseDeviceError();
+}
+
+void VectorEngineHost::tlPhaseDurationsDevice(uintptr_t out, uintptr_t consumerStream) {
+    std::lock_guard<std::mutex> guard(queryMutex_);
+    plan_.durationsDevice(out, consumerStream);
+}
+
+void VectorEngineHost::tlPhaseDurations(double *out) {
+    std::lock_guard<std::mutex> guard(queryMutex_);
+    plan_.durations(out);
+    raiseDeviceError();
+}
+
+void VectorEngineHost::restoreTlPlan() {
+    std::lock_guard<std::mutex> guard(queryMutex_);
+    plan_.restore();
 }
 
 void VectorEngineHost::trafficLightState(std::vector<int32_t> &phase, std::vector<double> &remain) {

@@ -2,7 +2,7 @@
 // engine.  The device sees a single road network made of R disjoint replicas (lane r*L+l, laneLink r*K+k, ...),
 // so every kernel launch of a step covers all environments: launch latency is paid once per step instead of
 // once per environment, and the car-following kernel finally gets enough vehicles per launch to approach the
-// HBM roofline.  Each environment has its own flows and its own std::mt19937 (seed + env index)
+// HBM roofline.  Each environment has its own flows and its own std::mt19937 (seed + env index, or seeds[env])
 // and evolves exactly like a standalone Engine built from the same config with that seed
 // (tests/test_vector_engine.py) — with laneChange: true as well: the device takes each environment's lane-change
 // schedule walk and priority stream separately (cfx_config::n_envs).
@@ -22,7 +22,10 @@ namespace cfa {
 
 class VectorEngineHost {
 public:
-    VectorEngineHost(const std::string &configFile, int numEnvs, int threadNum, const std::string &backendLib = "");
+    // seeds: empty = env r is seeded seed + r; otherwise numEnvs seeds, one per environment (std::invalid_argument for another
+    // length) — equal ones give every environment the same demand (common random numbers)
+    VectorEngineHost(const std::string &configFile, int numEnvs, int threadNum, const std::string &backendLib = "",
+                     const std::vector<int> &seeds = {});
     ~VectorEngineHost();
     VectorEngineHost(const VectorEngineHost &) = delete;
     VectorEngineHost &operator=(const VectorEngineHost &) = delete;
@@ -45,6 +48,14 @@ public:
     void setTrafficLightPhasesDevice(uintptr_t phases, size_t n, uintptr_t producerStream);
     bool rlTrafficLight() const { return rlTrafficLight_; }
     std::vector<int32_t> phaseCounts() const;  // [I] phases per intersection of one environment, -1 for virtual ones
+    // the fixed-time signal plan of every environment (EngineHost::setTlPlanDevice and its kin): durations [R * I * P], phase /
+    // remain [R * I]
+    bool tlPlanCalls() const { return plan_.available(); }
+    void setTlPlanDevice(uintptr_t durations, uintptr_t phase, uintptr_t remain, uintptr_t producerStream);
+    void setTlPlan(const double *durations, const int32_t *phase, const double *remain);
+    void tlPhaseDurationsDevice(uintptr_t out, uintptr_t consumerStream);
+    void tlPhaseDurations(double *out);
+    void restoreTlPlan();
     // per-lane speed and position features over every environment (EngineHost::laneFeatures and its kin): outputs [R * L] /
     // [R * L * nBins], edges [L][nBins + 1] or [nBins + 1], shared by the environments
     std::vector<double> laneLengths() const;  // [L] of one environment
@@ -99,6 +110,7 @@ private:
     TripStats trip_;                     // (likewise)
     bool devicePhaseUnchecked_ = false;  // as EngineHost: read by every call below that has waited for the device
     void raiseDeviceError();             // (the caller holds queryMutex_)
+    TlPlan plan_;                        // (every call with queryMutex_ held)
 
     std::shared_ptr<HostRoadNet> net_ = std::make_shared<HostRoadNet>();
     std::vector<std::unique_ptr<Spawner>> spawners_;

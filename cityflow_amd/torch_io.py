@@ -35,6 +35,15 @@
                              average_travel_time=None)   0-dim (VectorEngine: [R]) each, one kernel launch (see its docstring)
     eng.observe_trips_array()                            the same nine outputs as numpy arrays (waits for the device)
     eng.get_average_travel_time_tensor(out=None)         float64 0-dim (VectorEngine: [R]): get_average_travel_time() on the device
+    eng.set_tl_plan_tensor(durations=None, phase=None, phase_remain=None)
+                                                         the fixed-time signal plan as engine state: float64 [I, P] phase durations,
+                                                         integer [I] current phase, float64 [I] its remaining time (VectorEngine:
+                                                         [R, ...], one plan per environment); validated on the device, whole call or
+                                                         nothing, one kernel launch (see its docstring)
+    eng.get_tl_phase_durations_tensor(out=None)          float64 [I, P]: the durations in force
+    eng.set_tl_plan(...) / eng.get_tl_phase_durations_array()
+                                                         the same over numpy arrays (wait for the device)
+    eng.restore_tl_plan()                                the roadnet file's durations are in force again
 
 On the HIP engine the tensors live on the engine's GPU and nothing here waits for the device:
   * a getter's kernel writes the caller's tensor on the engine's stream after everything already enqueued there and on the
@@ -636,8 +645,133 @@ def get_average_travel_time_tensor(self, out=None):
     return out
 
 
+def _plan_shapes(eng):
+    """(shape of durations [.., I, P], shape of phase / phase_remain [.., I])."""
+    lead = tuple(eng._tensor_shapes()[1])
+    return lead + (eng._intersection_dims()[1],), lead
+
+
+def _need_plan_calls(eng, what):
+    if not eng._tl_plan_calls():
+        raise NotImplementedError("%s: the backend %r does not keep the signal plan as engine state" % (what, eng.backend_name()))
+
+
+def set_tl_plan_tensor(self, durations=None, phase=None, phase_remain=None):
+    """Set the fixed-time signal plan — each phase's green time, and where every intersection stands in its cycle — from tensors
+    on the engine's device, with one kernel launch on the engine's stream, read after everything enqueued on the current torch
+    stream (no host wait).  I, P and P_i as in observe_intersections_tensor / intersection_layout().  At least one of:
+
+        durations     float64 [I, P]  seconds of phase p of intersection i; NaN keeps the entry.  Entries p >= P_i and every row
+                                      of a virtual intersection are ignored.  A new duration takes effect the next time the phase
+                                      is entered: the running phase keeps its remaining time unless phase_remain says otherwise
+                                      — what the reference would do if LightPhase::time were changed between two steps
+        phase         integer [I]     the current phase; -1 keeps it.  Allowed whatever rlTrafficLight is; the remaining time is
+                                      not touched
+        phase_remain  float64 [I]     seconds the current phase still has; NaN keeps the value
+
+    The whole call is validated on the device before anything is applied.  At every intersection that is not virtual: every
+    given duration is finite and >= 0; the durations that would be in force after the call sum to at least the step interval
+    over p < P_i (a cycle of no length would never let the lights' advance end); phase is in [-1, P_i); phase_remain is finite
+    and >= 0.  One invalid entry rejects the WHOLE call — nothing is applied, valid rows and the other arguments included — and
+    the next call that waits for the device (sync(), a getter that reads to the host, snapshot, reset) raises ValueError naming
+    the argument, the intersection (the phase index, the env) and saying that the call was not applied.
+
+    The durations in force belong to the engine, like the roadnet: reset() keeps them (its lights go to phase 0 with the
+    remaining time durations[i, 0] in force), snapshot / load / load_from_file and vehicle compaction neither save nor change
+    them (an Archive carries the phase and the remaining time only); restore_tl_plan() brings the roadnet file's back.  With
+    rlTrafficLight the lights do not advance, so durations matter to reset() alone.  VectorEngine: a leading [R] on every
+    argument — one plan per environment.  Every argument is checked before anything is enqueued; NotImplementedError on a
+    backend without the call (the CPU twin)."""
+    torch = _torch()
+    if durations is None and phase is None and phase_remain is None:
+        raise ValueError("set_tl_plan_tensor: give at least one of durations, phase, phase_remain")
+    d_shape, i_shape = _plan_shapes(self)
+    device = _engine_device(torch, self)
+    if durations is not None:
+        _check_buf(torch, durations, "durations", d_shape, torch.float64, device)
+    if phase is not None:
+        _check_phases(torch, phase, i_shape, device)
+        if not phase.is_contiguous():
+            raise ValueError("phase must be contiguous")
+    if phase_remain is not None:
+        _check_buf(torch, phase_remain, "phase_remain", i_shape, torch.float64, device)
+    _need_plan_calls(self, "set_tl_plan_tensor")
+    p = phase
+    if p is not None and p.dtype != torch.int32:  # (values beyond int32 stay invalid instead of wrapping into range)
+        p = p.to(torch.int64).clamp(-2, 2 ** 31 - 1).to(torch.int32)
+    ptr = lambda t: 0 if t is None else t.data_ptr()  # noqa: E731
+    self._set_tl_plan_device(ptr(durations), ptr(p), ptr(phase_remain), torch.cuda.current_stream(device).cuda_stream)
+
+
+def get_tl_phase_durations_tensor(self, out=None):
+    """The phase durations in force as a float64 tensor [I, P] ([R, I, P] on a VectorEngine) on the engine's device, valid on the
+    current torch stream (no host wait): the reading side of set_tl_plan_tensor's `durations`.  0.0 for p >= P_i and in every row
+    of a virtual intersection; every element is written.  `out`: a contiguous float64 tensor of that shape, filled in place.
+    (The current phase and its remaining time are observe_intersections_tensor's phase / phase_remain.)"""
+    torch = _torch()
+    shape = _plan_shapes(self)[0]
+    device = _engine_device(torch, self)
+    if out is not None:
+        _check_buf(torch, out, "out", shape, torch.float64, device)
+    _need_plan_calls(self, "get_tl_phase_durations_tensor")
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float64, device=device)
+    self._tl_phase_durations_device(out.data_ptr(), torch.cuda.current_stream(device).cuda_stream)
+    return out
+
+
+def _plan_array(a, name, shape, dtype):
+    import numpy as np
+
+    if a is None:
+        return None
+    a = np.asarray(a)
+    if dtype == np.int32:
+        if a.dtype == np.bool_ or not np.issubdtype(a.dtype, np.integer):
+            raise TypeError("%s must be an integer array, not %s" % (name, a.dtype))
+        a = np.clip(a.astype(np.int64), -2, 2 ** 31 - 1)
+    elif not np.issubdtype(a.dtype, np.floating):
+        raise TypeError("%s must be a floating array, not %s" % (name, a.dtype))
+    if tuple(a.shape) != shape:
+        raise ValueError("%s must have shape %s, not %s" % (name, shape, tuple(a.shape)))
+    return np.ascontiguousarray(a, dtype=dtype)
+
+
+def set_tl_plan(self, durations=None, phase=None, phase_remain=None):
+    """set_tl_plan_tensor from numpy arrays (same shapes, rules and validation).  Waits for the device: an invalid entry raises
+    ValueError at once, and nothing was applied."""
+    import numpy as np
+
+    if durations is None and phase is None and phase_remain is None:
+        raise ValueError("set_tl_plan: give at least one of durations, phase, phase_remain")
+    d_shape, i_shape = _plan_shapes(self)
+    durations = _plan_array(durations, "durations", d_shape, np.float64)
+    phase = _plan_array(phase, "phase", i_shape, np.int32)
+    phase_remain = _plan_array(phase_remain, "phase_remain", i_shape, np.float64)
+    _need_plan_calls(self, "set_tl_plan")
+    self._set_tl_plan(durations, phase, phase_remain)
+
+
+def get_tl_phase_durations_array(self):
+    """get_tl_phase_durations_tensor as a numpy array; waits for the device."""
+    _need_plan_calls(self, "get_tl_phase_durations_array")
+    return self._tl_phase_durations().reshape(_plan_shapes(self)[0])
+
+
+def restore_tl_plan(self):
+    """Put the roadnet file's phase durations back in force, for every environment; the current phases and remaining times
+    stay as they are.  Ordered on the engine's stream, no host wait."""
+    _need_plan_calls(self, "restore_tl_plan")
+    self._restore_tl_plan()
+
+
 def install(*classes):
     for cls in classes:
+        cls.set_tl_plan_tensor = set_tl_plan_tensor
+        cls.get_tl_phase_durations_tensor = get_tl_phase_durations_tensor
+        cls.set_tl_plan = set_tl_plan
+        cls.get_tl_phase_durations_array = get_tl_phase_durations_array
+        cls.restore_tl_plan = restore_tl_plan
         cls.get_lane_vehicle_count_tensor = get_lane_vehicle_count_tensor
         cls.get_lane_waiting_vehicle_count_tensor = get_lane_waiting_vehicle_count_tensor
         cls.set_tl_phases_tensor = set_tl_phases_tensor

@@ -761,6 +761,48 @@ typedef int32_t (*cfx_movement_flow_get_state_fn)(cfx_engine *e, int32_t *record
 typedef int32_t (*cfx_movement_flow_set_state_fn)(cfx_engine *e, const int32_t *records, int32_t n_vehicles,
                                                   const cfx_movement_flow_link *links, int32_t tick);
 
+/* ---- The fixed-time signal plan as engine state in device memory (OPTIONAL entry points, as above; not on a tile:
+ * CFX_ERR_STATE).  The engine keeps two copies of cfx_net::phase_time: the durations IN FORCE, which TrafficLight::passTime of
+ * every step and cfx_reset read, and the FILE's, as cfx_create got them.  Rows are padded to max_phases = max P_i as in
+ * cfx_observe_intersections_device, and CFX_ERR_INVALID is returned when it is not the network's; n must be n_inters.
+ *   durations[i * max_phases + p]  double: seconds of phase p of intersection i; NaN keeps the entry; entries p >= P_i and
+ *                                  every row of a virtual intersection are ignored.  A new duration is read the next time the
+ *                                  phase is entered (or by cfx_reset); the running phase keeps its remaining time
+ *   phase[i]                       int32: -1 keeps, otherwise the current phase (as cfx_set_tl_phases, whatever rl_traffic_light
+ *                                  is); the remaining time is not touched
+ *   remain[i]                      double: seconds the current phase still has; NaN keeps
+ * Any of the three may be NULL (at least one given).  The call is valid if, at every intersection that is not virtual: every
+ * given duration is finite and >= 0; the sum over p < P_i of the durations in force AFTER the call is >= cfx_config::interval
+ * (what bounds passTime's loop: a cycle of zero length would never leave it); phase is in [-1, P_i); remain is finite and >= 0.
+ * One invalid entry rejects the WHOLE call: nothing is applied, and the first offender — lowest intersection; there durations
+ * by p, then the sum, then phase, then remain — is recorded for "cfx_tl_plan_error".  cfx_load_state and cfx_reset leave
+ * the durations in force alone (cfx_reset's remain is that of phase 0 in force).
+ *   "cfx_set_tl_plan_device"             the three in device memory, validated and applied by ONE kernel on the engine's
+ *                                        stream, read after everything enqueued on producer_stream (as cfx_set_tl_phases_device)
+ *   "cfx_set_tl_plan"                    the same from host memory; synchronous, so cfx_tl_plan_error is current on return
+ *   "cfx_get_tl_phase_durations_device"  out[n_inters * max_phases]: the durations in force, 0.0 for p >= P_i and at virtual
+ *                                        intersections, every element written, ordered against consumer_stream
+ *   "cfx_get_tl_phase_durations"         the same into host memory; synchronous
+ *   "cfx_restore_tl_plan"                the file's durations are in force again (a copy on the engine's stream); phases and
+ *                                        remaining times stay
+ *   "cfx_tl_plan_error"                  non-blocking read of the record, as cfx_device_error: 1 and *what (CFX_TL_PLAN_*),
+ *                                        *inter, *phase (the index p for CFX_TL_PLAN_DURATION, else -1) and *value (the offending
+ *                                        number; the sum for CFX_TL_PLAN_SUM) — the record is then cleared; 0: no record, and
+ *                                        every set call made so far has been validated on the device; 2: no record YET — a set
+ *                                        call is still ahead of the device (the caller did not wait for it): ask again later */
+#define CFX_TL_PLAN_DURATION 1 /* a duration that is negative or not finite */
+#define CFX_TL_PLAN_SUM 2      /* the durations in force after the call would sum to less than the interval */
+#define CFX_TL_PLAN_PHASE 3    /* phase outside [-1, P_i) */
+#define CFX_TL_PLAN_REMAIN 4   /* a remaining time that is negative or not finite */
+typedef int32_t (*cfx_set_tl_plan_device_fn)(cfx_engine *e, const double *durations, const int32_t *phase, const double *remain,
+                                             int32_t n, int32_t max_phases, void *producer_stream);
+typedef int32_t (*cfx_set_tl_plan_fn)(cfx_engine *e, const double *durations, const int32_t *phase, const double *remain, int32_t n,
+                                      int32_t max_phases);
+typedef int32_t (*cfx_get_tl_phase_durations_device_fn)(cfx_engine *e, double *out, int32_t max_phases, void *consumer_stream);
+typedef int32_t (*cfx_get_tl_phase_durations_fn)(cfx_engine *e, double *out, int32_t max_phases);
+typedef int32_t (*cfx_restore_tl_plan_fn)(cfx_engine *e);
+typedef int32_t (*cfx_tl_plan_error_fn)(cfx_engine *e, int32_t *what, int32_t *inter, int32_t *phase, double *value);
+
 #ifdef __cplusplus
 }
 #endif
