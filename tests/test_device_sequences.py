@@ -19,7 +19,11 @@ What the HIP engine is held against — never against itself:
                     TrafficLight::passTime (test_tl_plan.pass_time) on the durations the test has set so far: the lights against
                     that model at every read, the vehicles against the driven twin at every round's end
                     (test_the_plan_comparators_premise: such a twin equals a fixed-time twin bit for bit)
-Each sequence ends by asserting that it was not a quiet one (`Tally.enough`)."""
+Each sequence ends by asserting that it was not a quiet one (`Tally.enough`).
+
+The two VectorEngine drivers (run_vector_sequence, and run_vector_plan_sequence with one plan, one pass_time model and one
+driven twin per environment) take the network and the number of environments from their caller: grid_6x6 x 3 here,
+example_1x1 x 67 in tests/test_vector_many_envs.py."""
 import collections
 import os
 import time
@@ -683,18 +687,26 @@ VECTOR_OPS = (("steps", 8.0), ("count_array", 1.0), ("count_tensor", 1.0), ("pha
               ("speeds", 1.0), ("track", 2.5), ("all_off", 0.6), ("drain", 3.0), ("observe_lanes", 1.2), ("observe_intersections", 1.0))
 
 
+HIGH_ENV = 64  # k_trip_tick's kTripLdsEnvs: environments from here on take its road straight to memory
+
+
 def run_vector_sequence(vec, singles, seed, rounds, where):
-    """`singles`: standalone twins seeded like the environments; every [R, ...] output row by row."""
+    """`singles`: standalone twins seeded like the environments; every [R, ...] output row by row.  With environments beyond
+    HIGH_ENV the sequence must also have had all three trackers on, read the trip tracker while one of those environments had a
+    finished vehicle, observed the lanes with per-lane edges and reset while a tracker was on."""
     rng = np.random.default_rng(seed)
     t = Tally()
     R = len(singles)
+    t.resets_tracked = t.trips_read_high = t.edges_observed = 0
     lanes = list(singles[0].lane_ids())
     assert list(vec.lane_ids()) == lanes and vec.num_envs == R
     L, n_inter = len(lanes), len(singles[0].intersection_ids())
     phase_counts = singles[0]._phase_counts()
-    edges = singles[0].lane_lengths()[:, None] * np.array([0.0, 1.0 / 3.0, 2.0 / 3.0, np.inf])
+    # (a row of edges per lane, and neighbouring lanes' rows differ: a kernel that took another lane's row would show)
+    edges = singles[0].lane_lengths()[:, None] * np.array([0.0, 1.0 / 3.0, 2.0 / 3.0, np.inf]) * (0.7 + 0.1 * (np.arange(L) % 4))[:, None]
+    assert len({tuple(row) for row in edges[:4].tolist()}) == 4
     on = dict.fromkeys(TRACKERS, False)
-    track = {"lane": "track_lane_flow", "move": "track_movement_flow", "trip": "track_trips"}
+    track ={"lane": "track_lane_flow", "move": "track_movement_flow", "trip": "track_trips"}
     kinds = [k for k, _ in VECTOR_OPS]
 
     def at():
@@ -748,6 +760,7 @@ def run_vector_sequence(vec, singles, seed, rounds, where):
                 for e in singles:
                     e.reset(False)
                 t.steps, t.resets = 0, t.resets + 1
+                t.resets_tracked += any(on.values())
             elif op == "speeds":
                 for r, e in enumerate(singles):
                     assert vec.get_vehicle_speed(r) == e.get_vehicle_speed(), "%s: env %d" % (at(), r)
@@ -777,6 +790,7 @@ def run_vector_sequence(vec, singles, seed, rounds, where):
                     out = {k: filled(vec, (R,), trip_stats.DTYPES[k]) for k in trip_stats.NAMES}
                     vec.observe_trips_tensor(**out)
                     names = trip_stats.NAMES
+                    t.trips_read_high += any(p["finished"] > 0 for p in per_env[HIGH_ENV:])
                 elif which == "lane":
                     per_env = [e.observe_lane_flow_array(reset=reset) for e in singles]
                     out = lane_flow.empty_outputs(vec, lead=(R,))
@@ -803,6 +817,7 @@ def run_vector_sequence(vec, singles, seed, rounds, where):
                                 bins=e.get_lane_vehicle_bins_array(edges)) for e in singles]
                 for k in out:
                     same(out[k], np.stack([p[k] for p in per_env]), "%s: observe_lanes_tensor %s" % (at(), k))
+                t.edges_observed += 1
             elif op == "observe_intersections":
                 per_env = [e.observe_intersections_array() for e in singles]
                 want = {k: np.stack([p[k] for p in per_env]) for k in per_env[0]}
@@ -825,15 +840,24 @@ def run_vector_sequence(vec, singles, seed, rounds, where):
             assert sc[k] == sum(x[k] for x in each), "%s: scalar %s" % (where_, k)
     t.enough(kinds, where, reroutes=False, loads=False, merged=False)
     assert vec.get_vehicle_count() > 0
+    if R > HIGH_ENV:
+        assert t.ever_on == set(TRACKERS), "%s: trackers that were never on: %s" % (where, sorted(set(TRACKERS) - t.ever_on))
+        assert t.trips_read_high >= 1, "%s: the trip tracker was never read while an environment from %d on had a finished vehicle" % (where, HIGH_ENV)
+        assert t.edges_observed >= 1, where + ": no observe_lanes call with per-lane edges"
+        assert t.resets_tracked >= 1, where + ": no reset while a tracker was on"
     return t
 
 
-VECTOR_SEED, VECTOR_ROUNDS = 31, 70
+# (net, R) -> seed, chosen like SEEDS: twin against twins until Tally.enough and, at 67 environments, the conditions above hold
+# (tests/test_vector_many_envs.py runs the 67 case)
+VECTOR_ROUNDS = 70
+VECTOR_SEEDS = {("grid_6x6", 3): 31, ("example_1x1", 67): 30}
+VECTOR_SEED = VECTOR_SEEDS["grid_6x6", 3]
 
 
-def vector_engines(scen, workdir, make_vec):
-    cfg = scen.materialize("grid_6x6", workdir, rlTrafficLight=True)
-    return make_vec(cfg, 3), [scen.materialize("grid_6x6", workdir, rlTrafficLight=True, seed=r) for r in range(3)]
+def vector_engines(scen, workdir, make_vec, net="grid_6x6", R=3):
+    cfg = scen.materialize(net, workdir, rlTrafficLight=True)
+    return make_vec(cfg, R), [scen.materialize(net, workdir, rlTrafficLight=True, seed=r) for r in range(R)]
 
 
 def test_vector_sequence_twin_against_twins(mod, scen, workdir):
@@ -847,3 +871,159 @@ def test_vector_sequence_equals_standalone_twins(mod, scen, workdir):
     t0 = time.perf_counter()
     run_vector_sequence(vec, [twin(mod, c) for c in cfgs], VECTOR_SEED, VECTOR_ROUNDS, "vector")
     print("vector grid_6x6 x3: %.1f s" % (time.perf_counter() - t0))
+
+
+# ------------------------------------------------------------------------------------------- VectorEngine: one plan per environment
+VECTOR_PLAN_OPS = (("steps", 8.0), ("reset", 0.6), ("durations", 1.0), ("durations_sparse", 1.0), ("phase", 1.0), ("phase_remain", 1.0),
+                   ("restore", 0.8), ("get_durations", 1.0), ("lights", 1.5), ("observe_intersections", 1.0), ("count_array", 1.0))
+
+
+def run_vector_plan_sequence(vec, singles, cfg, seed, rounds, interval, where):
+    """run_plan_sequence for batched environments.  `vec`: a fixed-time VectorEngine on the device; `singles`: one twin per
+    environment in rlTrafficLight mode, seeded like the environment, each driven before every step from ITS pass_time model
+    (phase[r], remain[r], T[r]).  `vec` None: the operation stream, the models and the driven twins alone.  `cfg`: a config of
+    the network (for the roadnet file's plan)."""
+    rng = np.random.default_rng(seed)
+    t = Tally()
+    R = len(singles)
+    plan = Plan(singles[0], cfg)
+    real, count, I = plan.real, plan.count, plan.I
+    T = np.stack([plan.file()] * R)
+    phase, remain = np.zeros((R, I), dtype=np.int64), np.array(T[:, :, 0])
+    kinds = [k for k, _ in VECTOR_PLAN_OPS]
+    high_differed = 0  # reads at which two environments from HIGH_ENV on showed lights unlike each other's and environment 0's
+    durations_differed = 0  # reads of the durations in force at which no two environments had the same
+    if vec is not None:
+        assert vec.num_envs == R and vec.intersection_ids() == singles[0].intersection_ids()
+
+    def at():
+        return "%s seed %d, step %d (call %d)" % (where, seed, t.steps, sum(t.ops.values()))
+
+    def rows(call):
+        return np.stack([call(e) for e in singles])
+
+    def lights():
+        nonlocal high_differed
+        if vec is not None:
+            got_phase, got_remain = (np.asarray(a) for a in vec._tl_state())
+            assert got_phase.shape == (R, I) and got_remain.shape == (R, I), at()
+            assert np.array_equal(got_phase[:, real], phase[:, real]), at() + ": phases differ from pass_time's"
+            assert np.array_equal(got_remain[:, real], remain[:, real]), at() + ": remaining times differ from pass_time's"
+        light = [(phase[r, real].tolist(), remain[r, real].tolist()) for r in range(R)]
+        unlike = [r for r in range(HIGH_ENV, R) if light[r] != light[0]]
+        high_differed += any(light[a] != light[b] for a in unlike for b in unlike)
+
+    def some_envs():
+        return [r for r in range(R) if rng.random() < 0.35]
+
+    def some():
+        return [i for i in real if rng.random() < 0.5]
+
+    for round_ in range(rounds):
+        for _ in range(int(rng.integers(1, 9))):
+            op = draw(rng, VECTOR_PLAN_OPS)
+            if op == "steps":
+                for _ in range(int(rng.integers(1, 15))):
+                    for r, e in enumerate(singles):
+                        e.set_tl_phases(phase[r].astype(np.int32))
+                        e.next_step()
+                        pass_time(phase[r], remain[r], T[r], count, interval)
+                    if vec is not None:
+                        vec.next_step()
+                    t.steps, t.clock, t.run = t.steps + 1, t.clock + 1, t.run + 1
+                    t.merged += t.run >= 10
+                t.ops[op] += 1
+                continue
+            if op in ("get_durations", "lights", "observe_intersections", "count_array"):
+                t.read()
+            t.run = 0
+            if op == "reset":  # keeps the durations, restarts phase and remaining time from them
+                if vec is not None:
+                    vec.reset(False)
+                for e in singles:
+                    e.reset(False)
+                phase[:], remain[:] = 0, T[:, :, 0]
+                t.steps, t.resets = 0, t.resets + 1
+            elif op == "durations":  # every entry of every environment; some phases of no length, the last one of a second at least
+                new = np.zeros_like(T)
+                for r in range(R):
+                    for i in real:
+                        new[r, i, :count[i]] = quarter(rng, 0.0, 8.0, count[i]) * (rng.random(count[i]) < 0.8)
+                        new[r, i, count[i] - 1] = quarter(rng, 1.0, 8.0)
+                T = new
+                if vec is not None:
+                    vec.set_tl_plan_tensor(durations=dev(vec, np.stack([plan.dirty(T[r]) for r in range(R)])))
+            elif op == "durations_sparse":  # NaN keeps an entry; only some environments change
+                change = np.full_like(T, NAN)
+                for r in some_envs():
+                    for i in some():
+                        p = int(rng.integers(0, count[i]))
+                        change[r, i, p] = T[r, i, p] = quarter(rng, 1.0, 8.0)
+                if vec is not None:
+                    vec.set_tl_plan_tensor(durations=dev(vec, change))
+            elif op == "phase":  # -1 keeps it; the remaining time is not touched
+                only = np.full((R, I), -1, dtype=np.int32)
+                for r in some_envs():
+                    for i in some():
+                        only[r, i] = phase[r, i] = int(rng.integers(0, count[i]))
+                if vec is not None:
+                    vec.set_tl_plan_tensor(phase=dev(vec, only))
+            elif op == "phase_remain":
+                only = np.full((R, I), NAN)
+                for r in some_envs():
+                    for i in some():
+                        only[r, i] = remain[r, i] = quarter(rng, 0.0, 10.0)
+                if vec is not None:
+                    vec.set_tl_plan_tensor(phase_remain=dev(vec, only))
+            elif op == "restore":
+                T = np.stack([plan.file()] * R)
+                if vec is not None:
+                    vec.restore_tl_plan()
+            elif op == "get_durations":
+                if vec is not None:
+                    same(vec.get_tl_phase_durations_tensor(out=filled(vec, T.shape, np.float64)), T, at() + ": durations in force")
+                durations_differed += len({T[r].tobytes() for r in range(R)}) == R
+            elif op == "lights":
+                lights()
+            elif op == "observe_intersections":
+                if vec is not None:
+                    per_env =[e.observe_intersections_array() for e in singles]
+                    want = {k: np.stack([p[k] for p in per_env]) for k in per_env[0]}
+                    out = {k: filled(vec, a.shape, a.dtype) for k, a in want.items()}
+                    vec.observe_intersections_tensor(**out)
+                    for k in out:
+                        if k == "phase":  # (a driven twin holds the phase its last step began with)
+                            assert np.array_equal(out[k].cpu().numpy()[:, real], phase[:, real]), at() + ": phase tensor"
+                        elif k == "phase_remain":
+                            assert np.array_equal(out[k].cpu().numpy()[:, real], remain[:, real]), at() + ": phase_remain tensor"
+                        else:
+                            same(out[k], want[k], "%s: observe_intersections_tensor %s" % (at(), k))
+            elif op == "count_array":
+                if vec is not None:
+                    same(vec.get_lane_vehicle_count_array(), rows(lambda e: e.get_lane_vehicle_count_array()), at() + ": lane counts")
+            t.ops[op] += 1
+        t.read()
+        lights()
+        if vec is not None:
+            where_ = "%s, round %d" % (at(), round_)
+            same(vec.get_lane_vehicle_count_array(), rows(lambda e: e.get_lane_vehicle_count_array()), where_ + ": lane counts")
+            for r, e in enumerate(singles):
+                assert vec.get_vehicle_speed(r) == e.get_vehicle_speed(), "%s: env %d vehicle speeds" % (where_, r)
+    t.enough(kinds, where, reroutes=False, loads=False)
+    assert sum(e.get_vehicle_count() for e in singles) > 0
+    assert durations_differed >= 1, where + ": the durations in force were never read while every environment had a plan of its own"
+    if R > HIGH_ENV:
+        assert high_differed >= 1, "%s: at no read did two environments from %d on differ from each other and from environment 0" % (where, HIGH_ENV)
+    return t
+
+
+# (net, R, interval) -> seed, chosen on the driven twins alone (tests/test_vector_many_envs.py runs them)
+VECTOR_PLAN_ROUNDS = 80
+VECTOR_PLAN_SEEDS = {("example_1x1", 67, 1.0): 21, ("grid_6x6", 3, 0.5): 20}
+
+
+def vector_plan_engines(mod, scen, workdir, net, R, interval, make_vec):
+    """(the fixed-time batched engine or None, the driven twins, a config for Plan)"""
+    vec = make_vec(scen.materialize(net, workdir, interval=interval), R) if make_vec else None
+    cfgs = [scen.materialize(net, workdir, interval=interval, rlTrafficLight=True, seed=r) for r in range(R)]
+    return vec, [twin(mod, c) for c in cfgs], cfgs[0]

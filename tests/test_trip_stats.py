@@ -173,19 +173,15 @@ def grid_body(make, scen, workdir, with_twin=None):
         assert eng._host_stats(False)["table_grows_total"] > 0
 
 
-def vector_body(make_vec, make_single, scen, workdir, name, steps, rl, vec_twin=None):
-    R = 3
-    kw = {"rlTrafficLight": True} if rl else {}
-    vec = make_vec(scen.materialize(name, workdir, **kw), R)
-    other = vec_twin(scen.materialize(name, workdir, **kw), R) if vec_twin else None
-    singles = [make_single(scen.materialize(name, workdir, seed=r, **kw)) for r in range(R)]
-    models = [Model() for _ in range(R)]
-    vec.track_trips(True)
-    if other is not None:
-        other.track_trips(True)
+def vector_follow(vec, other, singles, models, first, steps, where, rl=False, exact=True):
+    """`steps` steps from step `first` on: every output of `vec` after every step against the models, which the standalone
+    engines `singles` feed, and against `other`, a second batched engine in lockstep.  `exact`: tracking has been on since
+    the engines were made or reset, so every 10th step the totals are the engines' own and the average is each standalone
+    engine's get_average_travel_time().  Returns (last outputs, whether two rows ever differed)."""
+    R = len(singles)
     inter_ids = vec.intersection_ids()
-    differed = False
-    for s in range(1, steps + 1):
+    differed, got = False, None
+    for s in range(first + 1, first + steps + 1):
         if rl and (s - 1) % 10 == 0:  # the per-environment phase plan of tests/test_vector_engine.py::_check
             ph = np.zeros((R, len(inter_ids)), dtype=np.int32)
             for r in range(R):
@@ -202,7 +198,7 @@ def vector_body(make_vec, make_single, scen, workdir, name, steps, rl, vec_twin=
         for r in range(R):
             singles[r].next_step()
             models[r].tick(singles[r], s)
-        at = "%s x%d, step %d" % (name, R, s)
+        at = "%s, step %d" % (where, s)
         got = read(vec, at, shape=(R,))
         check(got, stack([m.outputs() for m in models]), at)
         if other is not None:
@@ -211,14 +207,30 @@ def vector_body(make_vec, make_single, scen, workdir, name, steps, rl, vec_twin=
             for k in NAMES:
                 assert np.array_equal(got[k], theirs[k]), "%s: %s differs from the twin" % (at, k)
         differed = differed or any(len(set(got[k].tolist())) > 1 for k in INT_NAMES)
-        if s % 10 == 0:
+        if exact and s % 10 == 0:
             sc = vec._scalars()
             assert int(got["finished"].sum()) == sc["finished_vehicle_count"], at
             assert float(got["finished_travel_steps"].sum()) == sc["cumulative_travel_time"], at
             for r in range(R):
                 assert got["average_travel_time"][r] == singles[r].get_average_travel_time(), at
+    return got, differed
+
+
+def vector_body(make_vec, make_single, scen, workdir, name, steps, rl, vec_twin=None, R=3, engines=None):
+    """`engines`: a list that receives (vec, other, singles), for a caller that goes on with them."""
+    kw = {"rlTrafficLight": True} if rl else {}
+    vec = make_vec(scen.materialize(name, workdir, **kw), R)
+    other = vec_twin(scen.materialize(name, workdir, **kw), R) if vec_twin else None
+    singles = [make_single(scen.materialize(name, workdir, seed=r, **kw)) for r in range(R)]
+    models = [Model() for _ in range(R)]
+    vec.track_trips(True)
+    if other is not None:
+        other.track_trips(True)
+    got, differed = vector_follow(vec, other, singles, models, 0, steps, "%s x%d" % (name, R), rl=rl)
     assert got["finished"].sum() > 0
     assert differed, "the rows were equal at every step"
+    if engines is not None:
+        engines.append((vec, other, singles))
     return models, got
 
 

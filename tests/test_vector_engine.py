@@ -117,19 +117,29 @@ def test_vector_engine_lane_change_threaded_spawners_twin(mod, scen, workdir):
     assert vec.get_vehicle_count() > sum(len(vec.get_vehicle_speed(e)) for e in range(6))  # shadows alive
 
 
-@pytest.mark.parametrize("seed", [1, 2])
-def test_vector_engine_lane_change_random_control_twin(mod, scen, workdir, seed):
+def shadow_ids(eng):
+    """The lane-change shadows on a standalone engine's lanes: get_lane_vehicles() lists them as `<vehicle>_shadow`
+    (get_vehicles() leaves them out, as the reference's does)."""
+    return {v for ids in eng.get_lane_vehicles().values() for v in ids if v.endswith("_shadow")}
+
+
+def lane_change_random_control(mod, scen, workdir, make_vec, seed, envs=3, steps=260):
     """Batched environments with lane change under random control — every signal set per environment, resets with and without
-    a new seed in the middle of lane changes: every environment still equals its standalone engine after every step."""
+    a new seed in the middle of lane changes: every environment still equals its standalone twin after every step (lane
+    counts; vehicle speeds every 7th).  Returns what the run held, counted in the standalone twins: `resets_with_shadows`
+    (resets at which a shadow was alive), `most_inserted` (the most shadows one step created, all environments together) and
+    `inserting_envs` (per step, the environments in which it created one)."""
     rng = np.random.default_rng(seed)
-    envs = 3
     cfg = scen.materialize("example_1x1", workdir, laneChange=True, rlTrafficLight=True)
-    vec = mod.VectorEngine._with_backend(cfg, envs, 1, TWIN_LIB)
+    vec = make_vec(cfg, envs)
     singles = [mod.Engine._with_backend(scen.materialize("example_1x1", workdir, laneChange=True, rlTrafficLight=True, seed=e), 1, TWIN_LIB)
                for e in range(envs)]
     inter_ids = vec.intersection_ids()
     shadows = 0
-    for s in range(260):
+    alive = [set() for _ in range(envs)]
+    seen = [set() for _ in range(envs)]  # since the last reset: an id counts as created once (never too many)
+    held = {"resets_with_shadows": 0, "most_inserted": 0, "inserting_envs": []}
+    for s in range(steps):
         r = rng.random()
         if r < 0.15:
             ph = rng.integers(0, 8, size=(envs, len(inter_ids))).astype(np.int32)
@@ -142,12 +152,21 @@ def test_vector_engine_lane_change_random_control_twin(mod, scen, workdir, seed)
             vec.set_tl_phases(ph)
         elif r < 0.17 and s > 30:
             reseed = bool(rng.integers(0, 2))
+            held["resets_with_shadows"] += any(alive)
             vec.reset(reseed)
             for e in singles:
                 e.reset(reseed)
+            alive, seen = [set() for _ in range(envs)], [set() for _ in range(envs)]
         vec.next_step()
         for e in singles:
             e.next_step()
+        now = [shadow_ids(e) for e in singles]
+        created = [len(now[e] - seen[e]) for e in range(envs)]
+        alive = now
+        for e in range(envs):
+            seen[e] |= now[e]
+        held["most_inserted"] = max(held["most_inserted"], sum(created))
+        held["inserting_envs"].append([e for e in range(envs) if created[e]])
         counts = vec.get_lane_vehicle_count_array()
         for e in range(envs):
             assert np.array_equal(counts[e], singles[e].get_lane_vehicle_count_array()), (s, e)
@@ -156,6 +175,13 @@ def test_vector_engine_lane_change_random_control_twin(mod, scen, workdir, seed)
                 assert vec.get_vehicle_speed(e) == singles[e].get_vehicle_speed(), (s, e)
             shadows = max(shadows, vec.get_vehicle_count() - sum(len(vec.get_vehicle_speed(e)) for e in range(envs)))
     assert shadows > 0
+    assert held["resets_with_shadows"] > 0, "no reset fell into the middle of a lane change"
+    return held
+
+
+@pytest.mark.parametrize("seed", [1, 2])
+def test_vector_engine_lane_change_random_control_twin(mod, scen, workdir, seed):
+    lane_change_random_control(mod, scen, workdir, lambda c, n: mod.VectorEngine._with_backend(c, n, 1, TWIN_LIB), seed)
 
 
 def test_vector_engine_lane_change_reset_twin(mod, scen, workdir):
