@@ -18,6 +18,7 @@
 
 
 #include "cfx_kernels.h"
+#include "cfx_launch_policy.h"
 #include "cfx_lc_kernels.h"
 #include "cfx_ring_kernels.h"
 #include "cfx_dense_kernels.h"
@@ -769,6 +770,10 @@ struct cfx_engine {
     //      then it is pending; anything else that looks at the state launches it on its own first.
     bool ringMerge = true;       // cfx_config::ring_lanes_per_wave / 10000 == 4 turns the deferral off (developer knob)
     bool commitPending = false;  // the commit of step - 1 has not been launched yet (its lights were advanced by kr_cross)
+    // kr_cross's grid: the peak of the reported job counts (cfx_launch_policy.h); cfx_config::ring_lanes_per_wave / 100000 > 0
+    // forces its blocks instead (developer knob, for the tests: results never depend on the grid); the blocks of the last launch
+    cfx_policy::CrossGridPolicy crossPolicy;
+    int crossForceBlocks = 0, lastCrossBlocks = 0;
     size_t activeEstimate() const {
         const unsigned long long pr = __atomic_load_n(&hMirror->progress, __ATOMIC_RELAXED);
         return (size_t) (pr & 0xFFFFFFFFu) + (size_t) nQueueLanes * 4;
@@ -1339,15 +1344,26 @@ struct cfx_engine {
                         dim3(kCross2Block), c, ro, jq, RingLights{curPhase, remain, lightsToo ? 1 : 0});
             return;
         }
-        // one 16-lane group per queued vehicle; sized by the job count of the last step the device has reported (every
-        // block of the grid pays the prologue, and blocks that find no job still take a wavefront slot for it)
-        size_t groups = activeEst / 4;
+        // one 16-lane group per queued vehicle; sized by the decayed peak of the job counts the device has reported (every
+        // block of the grid pays the prologue, so not simply by the running vehicles; the last report alone is about
+        // kMaxLead + 2 steps old and follows the queue down into every all-red phase: cfx_launch_policy.h)
+        static_assert(cfx_policy::kCrossLanes == kCrossGroup && cfx_policy::kCrossThreads == kCrossBlock && cfx_policy::kCrossShards == kJobShards,
+                      "cfx_launch_policy.h counts in kr_cross's groups, blocks and shards");
         if (mirrorValid) {
-            const int lastJobs = __atomic_load_n(&hMirror->sc.nCrossJobs, __ATOMIC_RELAXED);
-            if (lastJobs > 0) groups = std::min<size_t>(groups, (size_t) lastJobs + (size_t) lastJobs / 4 + 256);
+            const int jobs = __atomic_load_n(&hMirror->sc.nCrossJobs, __ATOMIC_RELAXED);
+            const int at = __atomic_load_n(&hMirror->sc.crossJobsStep, __ATOMIC_RELAXED);
+            if (jobs > 0 || crossPolicy.lastStep >= 0) crossPolicy.report(at, jobs);
+        } else {
+            crossPolicy.reset();
         }
-        launchNamed(PK_CROSS, "kr_cross", kr_cross, dim3((int) std::min<size_t>(std::max<size_t>(64, (groups * 16 + kCrossBlock - 1) / kCrossBlock), 32768)),
-                    dim3(kCrossBlock), c, ro, jq, (const RingJob *) rJobRecs, RingLights{curPhase, remain, lightsToo ? 1 : 0});
+#ifdef CFX_CROSS_GRID_LAST_REPORT  // (measurement aid: the sizing this policy replaced, from the last report alone)
+        const size_t groups = cfx_policy::crossGroups(activeEst, crossPolicy.lastStep >= 0 ? (size_t) std::max(0, __atomic_load_n(&hMirror->sc.nCrossJobs, __ATOMIC_RELAXED)) : 0);
+#else
+        const size_t groups = crossPolicy.groups(activeEst);
+#endif
+        lastCrossBlocks = cfx_policy::crossBlocks(groups, crossForceBlocks);
+        launchNamed(PK_CROSS, "kr_cross", kr_cross, dim3(lastCrossBlocks), dim3(kCrossBlock), c, ro, jq, (const RingJob *) rJobRecs,
+                    RingLights{curPhase, remain, lightsToo ? 1 : 0});
     }
 
     // debug_sync: the rings' invariants after the action phase (kr_validate)
@@ -1827,6 +1843,7 @@ static int32_t createImpl(cfx_engine *e, const cfx_net *n, const cfx_config *cfg
     // 72 k / 277 k / 970 k running vehicles 54.7 / 86 / 141 us per step against 69.4 / 100 / 157.6 on the dense layout.
     e->ring = cfg->layout == CFX_LAYOUT_RING || (cfg->layout == CFX_LAYOUT_AUTO && !cfg->lane_change);
     e->ringMerge = (cfg->ring_lanes_per_wave / 10000) % 10 != 4;
+    e->crossForceBlocks = std::max(0, cfg->ring_lanes_per_wave / 100000);
     e->denseForm = cfg->dense_form ? (cfg->dense_form & 255) : CFX_DENSE_FORM_DEFAULT;
     e->hDrvLength.assign(n->drv_length, n->drv_length + n->n_lanes + n->n_lanelinks);
     e->hLaneRoad.assign(n->lane_road, n->lane_road + n->n_lanes);
@@ -2108,6 +2125,32 @@ int32_t cfx_get_host_stats(cfx_engine *e, cfx_host_stats *out, int32_t reset) {
         e->hostStats = cfx_host_stats{};
         e->hostStats.ring_regrows_total = rr;
         e->hostStats.table_grows_total = tg;
+    }
+    return CFX_OK;
+}
+
+// what kr_cross's grids did (optional entry point of include/cityflow_amd.h)
+int32_t cfx_get_cross_stats(cfx_engine *e, cfx_cross_stats *out, int32_t reset);
+static_assert(std::is_same<decltype(&cfx_get_cross_stats), cfx_get_cross_stats_fn>::value, "cfx_get_cross_stats");
+int32_t cfx_get_cross_stats(cfx_engine *e, cfx_cross_stats *out, int32_t reset) {
+    if (!e || !out) return CFX_ERR_INVALID;
+    auto fail = [e](const std::string &m) { return e->fail(m); };
+    HIP_TRY(hipSetDevice(e->device));
+    if (int rcSettle = e->settle(false)) return rcSettle;
+    DevScalars s;
+    if (int rc = e->readScalars(s)) return rc;
+    out->multi_pass_launches = s.crossMultiPass;
+    out->max_passes = s.crossMaxPasses;
+    out->last_jobs = s.nCrossJobs;
+    out->last_grid_blocks = e->lastCrossBlocks;
+    out->held_jobs = (int32_t) std::min<int64_t>(e->crossPolicy.held, INT32_MAX);
+    out->action_multi_pass_blocks = s.actionMultiPass;
+    out->action_lanes_per_block = e->ringG;
+    if (reset) {  // (the stream is idle: the three counters sit side by side, here and in the pinned copy)
+        static_assert(offsetof(DevScalars, actionMultiPass) == offsetof(DevScalars, crossMultiPass) + 2 * sizeof(int), "cleared together");
+        HIP_TRY(hipMemsetAsync(&e->sc->crossMultiPass, 0, 3 * sizeof(int), e->stream));
+        HIP_TRY(hipStreamSynchronize(e->stream));
+        if (e->hMirror) e->hMirror->sc.crossMultiPass = e->hMirror->sc.crossMaxPasses = e->hMirror->sc.actionMultiPass = 0;
     }
     return CFX_OK;
 }

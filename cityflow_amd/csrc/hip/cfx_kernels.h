@@ -102,6 +102,12 @@ struct DevScalars {
     // ring layout: vehicles admitted by the step of that parity, folded into `active` by that step's commit (the admission of
     // step t + 1 may run in the same launch as the commit of step t, which reads and rewrites `active`)
     long long admitPending[2];
+    // kr_cross: the step nCrossJobs belongs to (the host sizes the coming grids from the pair: cfx_launch_policy.h), and what its
+    // grids did to the groups (cfx_get_cross_stats): launches in which some group took more than one job, the most jobs a group took
+    int crossJobsStep;
+    int crossMultiPass;
+    int crossMaxPasses;
+    int actionMultiPass;  // kr_action: blocks that held more vehicles than one pass takes (T > B - 1), since the last clearing
 };
 
 struct HostMirror {  // pinned host copy of the end-of-step scalars (written by k_scatter's statistics block)

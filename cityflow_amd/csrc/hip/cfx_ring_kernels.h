@@ -1093,6 +1093,11 @@ __global__ __launch_bounds__(kCrossBlock, CFX_KR_CROSS_WAVES) void kr_cross(Ring
     const RingJob *const shardRecs = recs + (size_t) shard * q.capacity;
     RingJob jr = shardRecs[jFirst < q.capacity ? jFirst : q.capacity - 1];
     const int nShard = min(q.count[shard * kJobShardStride], q.capacity);
+    // (A block none of whose groups has a job — the host sizes the grid for the peak of the recent queues, cfx_launch_policy.h,
+    // so a quarter of the blocks and more are of this kind — still stages the table and meets at the barrier.  Letting it
+    // leave as soon as the count is there, the table's words requested before and stored behind that test, was measured:
+    // kr_cross 16.5 against 16.1 us over 200 traced launches, the step 41.0 against 40.7 us in six alternated runs each,
+    // profiles/cross_grid.txt — not kept.)
     if (c.t.nTempl <= kLdsTempl) {
         const int nd = c.t.nTempl * (int) (sizeof(cfx_vehicle_template) / sizeof(double));
         const double *src = (const double *) c.t.templ;
@@ -1100,10 +1105,20 @@ __global__ __launch_bounds__(kCrossBlock, CFX_KR_CROSS_WAVES) void kr_cross(Ring
         for (int i = threadIdx.x; i < nd; i += blockDim.x) dst[i] = src[i];
         tv = sT;
     }
-    if (blockIdx.x == 0 && threadIdx.x == 0) {  // (sizes the next steps' grids, through the host mirror)
-        int nJ = 0;
-        for (int i = 0; i < kJobShards; ++i) nJ += min(q.count[i * kJobShardStride], q.capacity);
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        // (sizes the next steps' grids, through the host mirror; and what this grid does to its groups: shard i has the
+        //  blocks i, i + 16, ... of the grid, and a group takes every (its blocks * 16)th job of the shard)
+        int nJ = 0, passes = 0;
+        for (int i = 0; i < kJobShards; ++i) {
+            const int n = min(q.count[i * kJobShardStride], q.capacity);
+            const int groupsOfShard = (((int) gridDim.x - i + kJobShards - 1) / kJobShards) * groupsPerBlock;
+            nJ += n;
+            if (groupsOfShard > 0) passes = max(passes, (n + groupsOfShard - 1) / groupsOfShard);
+        }
         o.sc->nCrossJobs = nJ;
+        o.sc->crossJobsStep = c.step;
+        if (passes > 1) atomicAdd(&o.sc->crossMultiPass, 1);  // (atomics whose result nobody reads: nothing waits for them)
+        atomicMax(&o.sc->crossMaxPasses, passes);
     }
     __syncthreads();
     XSTAMP(1);
@@ -1484,7 +1499,10 @@ __global__ CFX_KR_ACTION_BOUNDS(B) void kr_action(RingCtx c, RingOut o, JobQueue
     __syncthreads();
     const int T = sPre[B];
     // feedback for the host's choice of lanes per block (a block that needs a second pass is the step's slowest)
-    if (t == 0 && T > (B - 1) * 3 / 4) atomicMax(&o.sc->actionMaxT, T);
+    if (t == 0 && T > (B - 1) * 3 / 4) {
+        atomicMax(&o.sc->actionMaxT, T);
+        if (T > B - 1) atomicAdd(&o.sc->actionMultiPass, 1);  // (cfx_get_cross_stats)
+    }
     // (letting the laneLink blocks compute their own laneLinks' notify sources instead of the trailing blocks was measured in
     // round 3: 12.4 -> 14.9 us at 30x30 — the laneLink blocks then become the longest ones)
     TRACE_STAMP(1);

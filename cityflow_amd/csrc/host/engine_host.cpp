@@ -118,6 +118,7 @@ void Backend::open(const std::string &libPath) {
     CFX_FN_OPTIONAL(cfx_get_tl_phase_durations)
     CFX_FN_OPTIONAL(cfx_restore_tl_plan)
     CFX_FN_OPTIONAL(cfx_tl_plan_error)
+    CFX_FN_OPTIONAL(cfx_get_cross_stats)
 #undef CFX_FN_OPTIONAL
     if (cfx_abi_version() != CFX_ABI_VERSION)
         throw std::runtime_error("cityflow_amd: ABI version mismatch in '" + libPath + "'");
@@ -1012,6 +1013,13 @@ cfx_host_stats EngineHost::hostStats(bool reset) {
     cfx_host_stats s{};
     check(be_.cfx_get_host_stats(dev_, &s, reset ? 1 : 0), "cfx_get_host_stats");
     return s;
+}
+
+bool EngineHost::crossStats(bool reset, cfx_cross_stats *out) {
+    *out = cfx_cross_stats{};
+    if (!be_.cfx_get_cross_stats) return false;
+    check(be_.cfx_get_cross_stats(dev_, out, reset ? 1 : 0), "cfx_get_cross_stats");
+    return true;
 }
 
 cfx_scalars EngineHost::scalars() {

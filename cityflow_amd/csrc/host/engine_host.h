@@ -119,6 +119,7 @@ struct Backend {
     cfx_get_tl_phase_durations_fn cfx_get_tl_phase_durations = nullptr;
     cfx_restore_tl_plan_fn cfx_restore_tl_plan = nullptr;
     cfx_tl_plan_error_fn cfx_tl_plan_error = nullptr;
+    cfx_get_cross_stats_fn cfx_get_cross_stats = nullptr;  // (a library without it: crossStats() reports nothing)
     bool hasTlPlan() const {
         return hasDeviceBuffers() && cfx_set_tl_plan_device && cfx_set_tl_plan && cfx_get_tl_phase_durations_device &&
                cfx_get_tl_phase_durations && cfx_restore_tl_plan && cfx_tl_plan_error;
@@ -333,6 +334,7 @@ public:
     std::map<std::string, std::pair<double, int64_t>> profileRead();  // kernel -> (total ms, launches)
     std::map<std::string, std::string> profileSymbols();  // timing slot -> symbol of the kernel launched last in it
     cfx_host_stats hostStats(bool reset);
+    bool crossStats(bool reset, cfx_cross_stats *out);  // kr_cross's grids (false: the library has no such entry point)
     // the slowest nextStep() since the last clearing read: total us, the step, and its parts {phases + lane-change settle, this
     // step's spawn records (taken or made), table upload + lane-change supply, cfx_step, replay log, the spawner of the step ahead}
     struct SlowestStep {

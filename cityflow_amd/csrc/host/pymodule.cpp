@@ -880,6 +880,16 @@ PYBIND11_MODULE(_cityflow, m) {
             d["status_queries"] = s.status_queries;
             d["worst_status_query_us"] = py::make_tuple(s.worst_status_query_us, s.worst_status_query_settle_us,
                                                          s.worst_status_query_copy_us, s.worst_status_query_wait_us);
+            cfx_cross_stats x;
+            if (e.crossStats(reset, &x)) {  // (kr_cross's grids: waits for the stream)
+                d["cross_multi_pass_launches"] = x.multi_pass_launches;
+                d["cross_max_passes"] = x.max_passes;
+                d["cross_last_jobs"] = x.last_jobs;
+                d["cross_last_grid_blocks"] = x.last_grid_blocks;
+                d["cross_held_jobs"] = x.held_jobs;
+                d["action_multi_pass_blocks"] = x.action_multi_pass_blocks;
+                d["action_lanes_per_block"] = x.action_lanes_per_block;
+            }
             return d;
         }, "reset"_a = false, "host time inside cfx_step (cfx_get_host_stats)")
         .def("_vehicle_id", [](EngineHost &e, int vid) { return e.vehicleId(vid); }, "vid"_a)

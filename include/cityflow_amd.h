@@ -803,6 +803,25 @@ typedef int32_t (*cfx_get_tl_phase_durations_fn)(cfx_engine *e, double *out, int
 typedef int32_t (*cfx_restore_tl_plan_fn)(cfx_engine *e);
 typedef int32_t (*cfx_tl_plan_error_fn)(cfx_engine *e, int32_t *what, int32_t *inter, int32_t *phase, double *value);
 
+/* ---- What the grids of the ring layout's latency cross kernel (kr_cross) did (OPTIONAL entry point, as above; a diagnostic:
+ * results never depend on a grid).  A launch gives every queued vehicle a 16-lane group; the host sizes it from job counts the
+ * device reported some steps ago, and a group of a grid that is too small takes a second vehicle when the first is through.
+ *   "cfx_get_cross_stats"  waits for the stream (a deferred commit is launched first) and fills *out; reset != 0 then clears
+ *                          the device counters.  cfx_reset and cfx_load_state clear them too.
+ * cfx_config::ring_lanes_per_wave / 100000 (the digits above the form digit), where > 0, is the number of blocks every such
+ * launch gets instead (at least 16, one per shard of the queue; developer knob for the tests). */
+typedef struct cfx_cross_stats {
+    int64_t multi_pass_launches; /* launches in which some group took more than one job */
+    int32_t max_passes;          /* the most jobs one group took in a launch (0: no launch) */
+    int32_t last_jobs;           /* jobs of the last launch */
+    int32_t last_grid_blocks;    /* blocks of the last launch (256 threads, 16 groups each) */
+    int32_t held_jobs;           /* the job count the next grid would be sized from (the decayed peak of the reports) */
+    int32_t action_multi_pass_blocks; /* blocks of the lane-walking action kernel (kr_action) that held more vehicles than one
+                                       * pass of theirs takes, over all launches (cleared with the two counters above) */
+    int32_t action_lanes_per_block;   /* lanes the host currently gives a block of that kernel (it follows the fullest block) */
+} cfx_cross_stats;
+typedef int32_t (*cfx_get_cross_stats_fn)(cfx_engine *e, cfx_cross_stats *out, int32_t reset);
+
 #ifdef __cplusplus
 }
 #endif

@@ -4,7 +4,8 @@ RL network (bench.py's 30x30 workload, rlTrafficLight) and on VectorEngine 16 x 
 usage: python tools/rl_device_loop.py [--iters N] [--envs R]      (the probe tools/rl_probe.py is the numpy side's own story)
        python tools/rl_device_loop.py --features [--features-only all|counts_waiting]
 --features: observe_lanes_tensor (one launch of kr_lane_features) against the two count getters, on the Engine only;
---features-only runs just that observe_lanes_tensor loop (with all four outputs, B = 3, or counts + waiting), for a kernel trace.
+--features-only runs just that observe_lanes_tensor loop (with all four outputs, B = 3, or counts + waiting), for a kernel trace;
+--lib PATH runs either on another build of the device library.
        python tools/rl_device_loop.py --intersections [--runs N] [--intersections-only lanes|four|seven|no_waiting]
 --intersections: a max-pressure loop built two ways, alternated --runs times — A: observe_lanes_tensor(counts, waiting) and torch
 ops over index tensors made once (movement_in, movement_in_waiting, movement_out, phase_pressure); B: observe_intersections_tensor
@@ -64,6 +65,7 @@ ap.add_argument("--movement-flow", action="store_true")
 ap.add_argument("--movement-flow-only", choices=["trace"], default=None)
 ap.add_argument("--skip-single", action="store_true", help="--trips: the VectorEngine alone")
 ap.add_argument("--runs", type=int, default=3)
+ap.add_argument("--lib", default="", help="--features: a differently built device library (an A/B against another build)")
 args = ap.parse_args()
 sys.argv = [sys.argv[0]]
 import bench  # noqa: E402
@@ -607,7 +609,7 @@ if args.intersections or args.intersections_only:
     sys.exit(0)
 
 if args.features or args.features_only:
-    e = _cityflow.Engine(cfg, 1)
+    e = _cityflow.Engine._with_backend(cfg, 1, os.path.abspath(args.lib)) if args.lib else _cityflow.Engine(cfg, 1)
     features("Engine, 30x30 RL workload (%d signals, %d lanes)" % (len(e.intersection_ids()), len(e.lane_ids())), e, args.iters,
              args.features_only)
     sys.exit(0)
