@@ -65,6 +65,33 @@ inline int gridStride(size_t n) { return (int) std::min<size_t>(std::max<size_t>
 
 }  // namespace
 
+// A checkpoint in device memory (cfx_checkpoint_save / _restore, include/cityflow_amd.h): ONE allocation that holds the running
+// vehicles in the dense form of the getters (RingDense, with leader and gap) plus everything else cfx_load_state writes, as the
+// arrays stand; and on the host what cfx_load_state recomputes from an archive's columns.
+struct cfx_checkpoint {
+    cfx_engine *owner = nullptr;  // null once the engine is gone
+    char *arena = nullptr;
+    size_t arenaCap = 0;
+    bool saved = false;
+    int32_t nR = 0, nV = 0;
+    // ---- views into the arena
+    RingDense rd{};
+    int32_t *off = nullptr;  // [D + 1]
+    int32_t *priority = nullptr, *templ = nullptr, *route = nullptr, *nextWait = nullptr;  // [nV] VidTable
+    double *enterTime = nullptr, *customSpeed = nullptr;
+    uint8_t *state = nullptr, *pendingCustom = nullptr;
+    int32_t *waitHead = nullptr, *curPhase = nullptr;  // [L], [I]
+    double *remain = nullptr;                          // [I]
+    LaneHistDev hist{};                                // (null where the engine keeps no Lane::history)
+    // ---- host part
+    DevScalars sc{};
+    std::vector<int32_t> cnt;  // [D] vehicles per drivable (ring capacities are checked against it)
+    int64_t step = -1, finishedOffset = 0, nQueueLanes = 0;
+    std::vector<uint8_t> laneQueued;
+    std::map<int32_t, double> futureCustom;
+    bool timesDyadic = true;
+};
+
 struct cfx_engine {
     int device = 0;
     int nCU = 256;  // compute units of the device (hipDeviceProp_t::multiProcessorCount)
@@ -748,17 +775,54 @@ struct cfx_engine {
     }
     // ring order -> dense staging arrays (Drivable::vehicles order); returns the number of running vehicles
     int ringGather(bool wantLeader, int32_t *totalOut) {
+        int rc = ringOffsets(totalOut);
+        if (rc || (rc = ensureDense((size_t) *totalOut))) return rc;
+        return ringGatherInto(rd, *totalOut, wantLeader);
+    }
+    // ... its two halves, for a caller that brings the arrays (cfx_checkpoint_save): the offsets into rOff and the number of
+    // running vehicles (waits for the stream), then the gather
+    int ringOffsets(int32_t *totalOut) {
         hipLaunchKernelGGL(kr_offsets, dim3(1), dim3(kOffBlock), 0, stream, (const int32_t *) rCnt, rOff, D + 1);
         int32_t total = 0;
         HIP_TRY(hipMemcpyAsync(&total, rOff + D, sizeof(int32_t), hipMemcpyDeviceToHost, stream));
         HIP_TRY(hipStreamSynchronize(stream));
-        int rc = ensureDense((size_t) total);
-        if (rc) return rc;
-        if (total) hipLaunchKernelGGL(kr_gather, dim3(gridFor(D)), dim3(kBlock), 0, stream, rctx(), (const int32_t *) rOff, rd, wantLeader ? 1 : 0);
-        HIP_TRY(hipGetLastError());
         *totalOut = total;
         return CFX_OK;
     }
+    int ringGatherInto(const RingDense &out, int32_t total, bool wantLeader) {
+        if (total) hipLaunchKernelGGL(kr_gather, dim3(gridFor(D)), dim3(kBlock), 0, stream, rctx(), (const int32_t *) rOff, out, wantLeader ? 1 : 0);
+        HIP_TRY(hipGetLastError());
+        return CFX_OK;
+    }
+    // cfx_load_state and cfx_checkpoint_restore, after the reset: rings that are too small for the state's vehicles (`cnt`: per
+    // drivable) — capacities from a fraction of the bound, or a state denser than this engine has seen — double every capacity
+    // until it fits: the growth path of a running engine.  `what` names the caller in the error.
+    int ringFit(const int32_t *cnt, const char *what) {
+        for (;;) {
+            bool fits = true;
+            for (int d = 0; d < D && fits; ++d) fits = cnt[d] + std::min(8, (hRingGeo[d].y + 1) / 2) <= hRingGeo[d].y;
+            if (fits) break;
+            if (ringScale >= 4096) return fail(std::string(what) + ": more vehicles on one drivable than its ring can hold");
+            ringGrowRequested = true;
+            const int rc = ringEnsure();
+            if (rc) return rc;
+        }
+        for (int d = 0; d < D; ++d)
+            if (cnt[d] > hRingGeo[d].y) return fail(std::string(what) + ": more vehicles on one drivable than its ring holds");
+        return CFX_OK;
+    }
+    // ... at their end: the dense arrays (rd, rOff) onto the rings, once the vehicle table and the step counter are in place
+    // (the blockers' validity tag is "set in the previous step")
+    int ringFromDense() {
+        if (spawned) HIP_TRY(hipMemsetAsync(slotOf, 0xFF, (size_t) spawned * sizeof(int32_t), stream));
+        const int rc = ringClearStepTags();
+        if (rc) return rc;
+        hipLaunchKernelGGL(kr_scatter_in, dim3(gridFor(D)), dim3(kBlock), 0, stream, rctx(), (const int32_t *) rOff, rd, vt);
+        HIP_TRY(hipGetLastError());
+        return CFX_OK;
+    }
+    // Device checkpoints of this engine that are still alive (cfx_checkpoint_create / _destroy): cfx_destroy takes their memory
+    std::vector<cfx_checkpoint *> checkpoints;
     // Records that are valid "for the step in their tag" must not survive a change of the step counter (reset, load) or of
     // the slots they name (rebuilt rings); the occupancy bits are rebuilt by kr_scatter_in.
     int ringClearStepTags() {
@@ -1781,6 +1845,13 @@ void cfx_destroy(cfx_engine *e) {
     if (!e) return;
     (void) hipSetDevice(e->device);
     if (e->stream) (void) hipStreamSynchronize(e->stream);
+    for (cfx_checkpoint *ck : e->checkpoints) {  // (they outlive the engine as empty shells: cfx_checkpoint_destroy)
+        if (ck->arena) (void) hipFree(ck->arena);
+        ck->arena = nullptr;
+        ck->arenaCap = 0;
+        ck->saved = false;
+        ck->owner = nullptr;
+    }
     for (void *p : e->owned) (void) hipFree(p);
     for (hipEvent_t ev : e->evPool) (void) hipEventDestroy(ev);
     for (int i = 0; i < cfx_engine::kStages; ++i) {
@@ -2857,20 +2928,9 @@ int32_t cfx_load_state(cfx_engine *e, const cfx_state *s) {
     if (e->ring) {
         // the caller's arrays ARE the dense staging view (Drivable::vehicles order); kr_scatter_in (below, once the vehicle
         // table is on the device) puts them on the rings
-        // rings that are too small for the archive (capacities from a fraction of the bound, or an archive from a denser
-        // state than this engine has seen): double every capacity until it fits — the growth path of a running engine
-        for (;;) {
-            bool fits = true;
-            for (int d = 0; d < D && fits; ++d) fits = cnt[d] + std::min(8, (e->hRingGeo[d].y + 1) / 2) <= e->hRingGeo[d].y;
-            if (fits) break;
-            if (e->ringScale >= 4096) return e->fail("cfx_load_state: more vehicles on one drivable than its ring can hold");
-            e->ringGrowRequested = true;
-            if ((rc = e->ringEnsure())) return rc;
-        }
-        for (int d = 0; d < D; ++d) {
-            segStart[d + 1] = segStart[d] + cnt[d];
-            if (cnt[d] > e->hRingGeo[d].y) return e->fail("cfx_load_state: more vehicles on one drivable than its ring holds");
-        }
+        // (rings that are too small for the archive grow first)
+        if ((rc = e->ringFit(cnt.data(), "cfx_load_state"))) return rc;
+        for (int d = 0; d < D; ++d) segStart[d + 1] = segStart[d] + cnt[d];
         if ((rc = e->ensureDense((size_t) nR))) return rc;
         std::vector<int32_t> blk((size_t) std::max(nR, 1), -1);
         std::vector<uint8_t> flags((size_t) std::max(nR, 1), 0);
@@ -3051,16 +3111,227 @@ int32_t cfx_load_state(cfx_engine *e, const cfx_state *s) {
         HIP_TRY(up(lc.followerGap, zero.data(), nv * 8));
         HIP_TRY(hipStreamSynchronize(e->stream));  // the staging vectors die with this scope
     }
-    if (e->ring) {  // (needs the vehicle table and e->step: the blockers' validity tag is "set in the previous step")
-        if (e->spawned) HIP_TRY(hipMemsetAsync(e->slotOf, 0xFF, (size_t) e->spawned * sizeof(int32_t), e->stream));
-        if ((rc = e->ringClearStepTags())) return rc;
-        hipLaunchKernelGGL(kr_scatter_in, dim3(gridFor(D)), dim3(kBlock), 0, e->stream, e->rctx(), (const int32_t *) e->rOff, e->rd, e->vt);
+    if (e->ring) {
+        if ((rc = e->ringFromDense())) return rc;
     } else
     // cached next drivable of every slot (uses the device copies of the route tables)
     hipLaunchKernelGGL(k_refresh_next, dim3(gridStride(std::max(S, 1))), dim3(kBlock), 0, e->stream, e->ctx());
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(e->stream));
     return CFX_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- device checkpoints
+// (optional entry points of include/cityflow_amd.h)
+int32_t cfx_checkpoint_create(cfx_engine *e, cfx_checkpoint **out);
+int32_t cfx_checkpoint_save(cfx_engine *e, cfx_checkpoint *ck);
+int32_t cfx_checkpoint_restore(cfx_engine *e, cfx_checkpoint *ck);
+int32_t cfx_checkpoint_info(const cfx_checkpoint *ck, cfx_checkpoint_desc *out);
+void cfx_checkpoint_destroy(cfx_checkpoint *ck);
+static_assert(std::is_same<decltype(&cfx_checkpoint_create), cfx_checkpoint_create_fn>::value, "cfx_checkpoint_create");
+static_assert(std::is_same<decltype(&cfx_checkpoint_save), cfx_checkpoint_save_fn>::value, "cfx_checkpoint_save");
+static_assert(std::is_same<decltype(&cfx_checkpoint_restore), cfx_checkpoint_restore_fn>::value, "cfx_checkpoint_restore");
+static_assert(std::is_same<decltype(&cfx_checkpoint_info), cfx_checkpoint_info_fn>::value, "cfx_checkpoint_info");
+static_assert(std::is_same<decltype(&cfx_checkpoint_destroy), cfx_checkpoint_destroy_fn>::value, "cfx_checkpoint_destroy");
+
+// Where a checkpoint of nR running vehicles and nV vehicle numbers keeps its arrays: one after the other from `base`, each on
+// a 256-byte boundary (so that the pack kernel moves 16 bytes per lane).  Returns the bytes needed; base may be null (sizing).
+static size_t checkpointLayout(cfx_checkpoint *ck, char *base, const cfx_engine *e, size_t nR, size_t nV) {
+    size_t at = 0;
+    auto take = [&](auto *&ptr, size_t n) {
+        using T = typename std::remove_reference<decltype(*ptr)>::type;
+        ptr = base ? reinterpret_cast<T *>(base + at) : nullptr;
+        at += (std::max<size_t>(n, 1) * sizeof(T) + 255) & ~(size_t) 255;
+    };
+    take(ck->rd.vid, nR); take(ck->rd.drv, nR); take(ck->rd.prevDrv, nR); take(ck->rd.blockerVid, nR); take(ck->rd.enterLLT, nR);
+    take(ck->rd.routePos, nR); take(ck->rd.leaderVid, nR); take(ck->rd.flags, nR); take(ck->rd.dis, nR); take(ck->rd.speed, nR);
+    take(ck->rd.gap, nR);
+    take(ck->off, (size_t) e->D + 1);
+    take(ck->priority, nV); take(ck->templ, nV); take(ck->route, nV); take(ck->nextWait, nV); take(ck->enterTime, nV);
+    take(ck->customSpeed, nV); take(ck->state, nV); take(ck->pendingCustom, nV);
+    take(ck->waitHead, (size_t) e->L); take(ck->curPhase, (size_t) e->I); take(ck->remain, (size_t) e->I);
+    ck->hist = LaneHistDev{};
+    if (e->hist.num) {
+        const size_t L = (size_t) e->L, M = (size_t) kLaneHistoryMax;
+        take(ck->hist.num, M * L); take(ck->hist.avg, M * L); take(ck->hist.head, L); take(ck->hist.len, L); take(ck->hist.hNum, L);
+        take(ck->hist.hAvg, L);
+        ck->hist.L = e->hist.L;
+    }
+    return at;
+}
+
+// The segments of a save (toCheckpoint) or a restore: every array that is kept as it stands; a restore also brings the dense
+// form back into the engine's staging arrays, from where the rings are rebuilt
+static int checkpointPack(cfx_engine *e, cfx_checkpoint *ck, bool toCheckpoint) {
+    PackTable t{};
+    unsigned chunks = 0;
+    bool full = false;
+    auto seg = [&](auto *engineSide, auto *checkpointSide, size_t n) {
+        const unsigned long long bytes = (unsigned long long) n * sizeof(*engineSide);
+        static_assert(sizeof(*engineSide) == sizeof(*checkpointSide), "one element type on both sides");
+        if (!bytes) return;
+        if (t.n >= kPackSegs) {
+            full = true;
+            return;
+        }
+        t.src[t.n] = toCheckpoint ? (const char *) engineSide : (const char *) checkpointSide;
+        t.dst[t.n] = toCheckpoint ? (char *) checkpointSide : (char *) engineSide;
+        t.bytes[t.n] = bytes;
+        chunks += (unsigned) ((bytes + kPackChunk - 1) / kPackChunk);
+        t.chunkEnd[t.n] = chunks;
+        t.n += 1;
+    };
+    const size_t nR = (size_t) ck->nR, nV = (size_t) ck->nV, L = (size_t) e->L, I = (size_t) e->I;
+    if (!toCheckpoint) {  // (a save's dense form is written by the gather itself)
+        seg(e->rd.vid, ck->rd.vid, nR); seg(e->rd.prevDrv, ck->rd.prevDrv, nR); seg(e->rd.blockerVid, ck->rd.blockerVid, nR);
+        seg(e->rd.enterLLT, ck->rd.enterLLT, nR); seg(e->rd.routePos, ck->rd.routePos, nR); seg(e->rd.flags, ck->rd.flags, nR);
+        seg(e->rd.dis, ck->rd.dis, nR); seg(e->rd.speed, ck->rd.speed, nR); seg(e->rd.gap, ck->rd.gap, nR);
+    }
+    seg(e->rOff, ck->off, (size_t) e->D + 1);
+    seg(e->vt.priority, ck->priority, nV); seg(e->vt.templ, ck->templ, nV); seg(e->vt.route, ck->route, nV);
+    seg(e->vt.nextWait, ck->nextWait, nV); seg(e->vt.enterTime, ck->enterTime, nV); seg(e->vt.customSpeed, ck->customSpeed, nV);
+    seg(e->vt.state, ck->state, nV); seg(e->vt.pendingCustom, ck->pendingCustom, nV);
+    seg(e->waitHead, ck->waitHead, L); seg(e->curPhase, ck->curPhase, I); seg(e->remain, ck->remain, I);
+    if (e->hist.num && ck->hist.num) {
+        const size_t M = (size_t) kLaneHistoryMax;
+        seg(e->hist.num, ck->hist.num, M * L); seg(e->hist.avg, ck->hist.avg, M * L); seg(e->hist.head, ck->hist.head, L);
+        seg(e->hist.len, ck->hist.len, L); seg(e->hist.hNum, ck->hist.hNum, L); seg(e->hist.hAvg, ck->hist.hAvg, L);
+    }
+    if (full) return e->fail("device checkpoint: more segments than the pack kernel's table holds (internal error)");
+    if (!chunks) return CFX_OK;
+    t.chunks = chunks;
+    hipLaunchKernelGGL(k_pack_segments, dim3(std::min(chunks, 2048u)), dim3(kPackBlock), 0, e->stream, t);
+    if (hipGetLastError() != hipSuccess) return e->fail("device checkpoint: the pack launch failed");
+    return CFX_OK;
+}
+
+int32_t cfx_checkpoint_create(cfx_engine *e, cfx_checkpoint **out) {
+    if (!e || !out) return CFX_ERR_INVALID;
+    *out = nullptr;
+    if (!e->ring || e->lc.on || e->tiled) {
+        e->err = std::string("cfx_checkpoint_create: device checkpoints exist on the ring layout only; this engine ") +
+                 (e->lc.on ? "runs with lane_change" : (e->tiled ? "is a tile" : "uses the dense layout"));
+        return CFX_ERR_STATE;
+    }
+    cfx_checkpoint *ck = new cfx_checkpoint();
+    ck->owner = e;
+    e->checkpoints.push_back(ck);
+    *out = ck;
+    return CFX_OK;
+}
+
+int32_t cfx_checkpoint_save(cfx_engine *e, cfx_checkpoint *ck) {
+    if (!e || !ck) return CFX_ERR_INVALID;
+    auto fail = [e](const std::string &m) { return e->fail(m); };
+    if (ck->owner != e) {
+        e->err = "cfx_checkpoint_save: the checkpoint belongs to another engine";
+        return CFX_ERR_INVALID;
+    }
+    if (!e->ring || e->lc.on || e->tiled) return e->fail("cfx_checkpoint_save: the engine has left the ring layout"), CFX_ERR_STATE;
+    HIP_TRY(hipSetDevice(e->device));
+    int rc;
+    if ((rc = e->settle())) return rc;  // (a deferred commit, the last step's Lane::history record)
+    if ((rc = e->syncTables()) || (rc = e->ringEnsure())) return rc;
+    ck->saved = false;
+    // the scalars and the per-drivable counts ride with the wait for the number of running vehicles
+    ck->cnt.assign((size_t) e->D, 0);
+    HIP_TRY(hipMemcpyAsync(&ck->sc, e->sc, sizeof(DevScalars), hipMemcpyDeviceToHost, e->stream));
+    if (e->D) HIP_TRY(hipMemcpyAsync(ck->cnt.data(), e->rCnt, (size_t) e->D * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
+    int32_t total = 0;
+    if ((rc = e->ringOffsets(&total))) return rc;
+    e->finishedKnown = ck->sc.finishedCnt;
+    if (ck->sc.overflow) {
+        DevScalars s;
+        return (rc = e->readScalars(s)) ? rc : e->fail("cfx_checkpoint_save: the device reported a capacity overflow");
+    }
+    const size_t need = checkpointLayout(ck, nullptr, e, (size_t) total, (size_t) e->spawned);
+    if (need > ck->arenaCap) {
+        if (ck->arena) HIP_TRY(hipFree(ck->arena));  // (waits for the device: nothing reads it any more)
+        ck->arena = nullptr;
+        ck->arenaCap = 0;
+        const size_t cap = need + need / 8;  // (a checkpoint that is overwritten as the traffic grows does not reallocate every time)
+        void *p = nullptr;
+        HIP_TRY(hipMalloc(&p, cap));
+        ck->arena = (char *) p;
+        ck->arenaCap = cap;
+    }
+    checkpointLayout(ck, ck->arena, e, (size_t) total, (size_t) e->spawned);
+    ck->nR = total;
+    ck->nV = (int32_t) e->spawned;
+    if ((rc = e->ringGatherInto(ck->rd, total, true))) return rc;
+    if ((rc = checkpointPack(e, ck, true))) return rc;
+    ck->step = e->step;
+    ck->finishedOffset = e->finishedOffset;
+    ck->laneQueued = e->laneQueued;
+    ck->nQueueLanes = e->nQueueLanes;
+    ck->futureCustom = e->futureCustom;
+    ck->timesDyadic = e->timesDyadic;
+    ck->saved = true;
+    return CFX_OK;
+}
+
+// cfx_load_state's ring branch with the checkpoint's arrays as the sources
+int32_t cfx_checkpoint_restore(cfx_engine *e, cfx_checkpoint *ck) {
+    if (!e || !ck) return CFX_ERR_INVALID;
+    auto fail = [e](const std::string &m) { return e->fail(m); };
+    if (ck->owner != e || !ck->saved) {
+        e->err = ck->owner != e ? "cfx_checkpoint_restore: the checkpoint belongs to another engine" : "cfx_checkpoint_restore: nothing was saved into the checkpoint";
+        return CFX_ERR_INVALID;
+    }
+    if (!e->ring || e->lc.on || e->tiled) return e->fail("cfx_checkpoint_restore: the engine has left the ring layout"), CFX_ERR_STATE;
+    HIP_TRY(hipSetDevice(e->device));
+    int rc;
+    if ((rc = e->syncTables())) return rc;
+    if ((rc = e->resetState())) return rc;
+    const int nV = ck->nV, nR = ck->nR;
+    if ((rc = e->ensureVidCap((size_t) nV + 1))) return rc;
+    if ((rc = e->ringEnsure())) return rc;
+    if ((rc = e->ringFit(ck->cnt.data(), "cfx_checkpoint_restore"))) return rc;
+    if ((rc = e->ensureDense((size_t) nR))) return rc;
+    if ((rc = checkpointPack(e, ck, false))) return rc;
+    if (nR) hipLaunchKernelGGL(k_checkpoint_state_gap, dim3(gridFor((size_t) nR)), dim3(kBlock), 0, e->stream, nR, (const int32_t *) e->rd.vid,
+                               (const double *) e->rd.gap, e->rd.flags, e->vt.gapState, nV);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemsetD32Async((hipDeviceptr_t) e->vt.firstNext, kFirstNextUnknown, (size_t) std::max(nV, 1), e->stream));  // (waiting vehicles: the walk)
+    DevScalars sc{};
+    sc.active = nR;
+    sc.finishedCnt = ck->sc.finishedCnt;
+    sc.cumulativeTravelTime = ck->sc.cumulativeTravelTime;
+    sc.vehicleSteps = ck->sc.vehicleSteps;
+    HIP_TRY(hipMemcpyAsync(e->sc, &sc, sizeof sc, hipMemcpyHostToDevice, e->stream));
+    e->cumLoaded = sc.cumulativeTravelTime;
+    e->timesDyadic = ck->timesDyadic;
+    e->step = ck->step;
+    e->spawned = nV;
+    e->spawnedHere = nV;
+    e->liveUpper = nR;
+    e->laneQueued = ck->laneQueued;
+    e->nQueueLanes = ck->nQueueLanes;
+    e->futureCustom = ck->futureCustom;
+    e->finishedKnown = sc.finishedCnt;
+    e->finishedOffset = ck->finishedOffset;
+    if ((rc = e->ringFromDense())) return rc;
+    HIP_TRY(hipStreamSynchronize(e->stream));  // (`sc` lives on this frame)
+    return CFX_OK;
+}
+
+int32_t cfx_checkpoint_info(const cfx_checkpoint *ck, cfx_checkpoint_desc *out) {
+    if (!ck || !out) return CFX_ERR_INVALID;
+    out->step = ck->saved ? ck->step : -1;
+    out->device_bytes = (int64_t) ck->arenaCap;
+    out->n_running = ck->saved ? ck->nR : 0;
+    out->n_vehicles = ck->saved ? ck->nV : 0;
+    return CFX_OK;
+}
+
+void cfx_checkpoint_destroy(cfx_checkpoint *ck) {
+    if (!ck) return;
+    if (cfx_engine *e = ck->owner) {
+        (void) hipSetDevice(e->device);
+        if (ck->arena) (void) hipFree(ck->arena);  // (waits for the device: a pack launch may still be reading it)
+        e->checkpoints.erase(std::remove(e->checkpoints.begin(), e->checkpoints.end(), ck), e->checkpoints.end());
+    }
+    delete ck;
 }
 
 // ---------------------------------------------------------------------------------------------- tiling

@@ -2203,6 +2203,66 @@ __global__ __launch_bounds__(kOffBlock) void kr_offsets(const int32_t *in, int32
     }
 }
 
+// Device checkpoints (cfx_checkpoint_save / _restore): every array that is kept as it stands — the vehicle table's columns, the
+// waiting queues' heads, the lights, Lane::history, the gather's offsets — in ONE launch over a table of (source, destination,
+// bytes) segments that arrives with the kernel's arguments.  A segment is cut into chunks of kPackChunk bytes; a block takes
+// chunks grid-stride and finds a chunk's segment by walking the table (uniform across the block: scalar loads of the argument
+// segment).  16 bytes per lane where both ends of the segment are 16-byte aligned (what every allocation and the checkpoint's own
+// layout give), the last bytes of a segment one at a time; a segment that is not aligned goes byte by byte.
+constexpr int kPackSegs = 32;
+constexpr int kPackBlock = 256;
+constexpr unsigned kPackChunk = kPackBlock * 16 * 4;  // four 16-byte accesses per thread and chunk
+struct PackTable {
+    const char *src[kPackSegs];
+    char *dst[kPackSegs];
+    unsigned long long bytes[kPackSegs];
+    unsigned chunkEnd[kPackSegs];  // running total of the segments' chunk counts
+    unsigned chunks;               // ... of all of them
+    int n;
+};
+__global__ __launch_bounds__(kPackBlock) void k_pack_segments(PackTable t) {
+    const unsigned total = t.chunks;
+    for (unsigned chunk = blockIdx.x; chunk < total; chunk += gridDim.x) {
+        int s = 0;
+        while (s + 1 < t.n && chunk >= t.chunkEnd[s]) ++s;
+        const unsigned first = s ? t.chunkEnd[s - 1] : 0;
+        const unsigned long long bytes = t.bytes[s], lo = (unsigned long long) (chunk - first) * kPackChunk;
+        const unsigned long long hi = lo + kPackChunk < bytes ? lo + kPackChunk : bytes;
+        const char *src = t.src[s];
+        char *dst = t.dst[s];
+        if ((((unsigned long long) src | (unsigned long long) dst) & 15ULL) == 0) {
+            const unsigned long long hiVec = hi & ~15ULL;  // (lo is a multiple of the chunk, so of 16)
+            // the four loads first, then the four stores (named registers: an array that is written under a condition goes to LDS)
+            const unsigned long long o0 = lo + (unsigned long long) threadIdx.x * 16, o1 = o0 + kPackBlock * 16,
+                                     o2 = o1 + kPackBlock * 16, o3 = o2 + kPackBlock * 16;
+            uint4 v0 = make_uint4(0, 0, 0, 0), v1 = v0, v2 = v0, v3 = v0;
+            if (o0 < hiVec) v0 = *reinterpret_cast<const uint4 *>(src + o0);
+            if (o1 < hiVec) v1 = *reinterpret_cast<const uint4 *>(src + o1);
+            if (o2 < hiVec) v2 = *reinterpret_cast<const uint4 *>(src + o2);
+            if (o3 < hiVec) v3 = *reinterpret_cast<const uint4 *>(src + o3);
+            if (o0 < hiVec) *reinterpret_cast<uint4 *>(dst + o0) = v0;
+            if (o1 < hiVec) *reinterpret_cast<uint4 *>(dst + o1) = v1;
+            if (o2 < hiVec) *reinterpret_cast<uint4 *>(dst + o2) = v2;
+            if (o3 < hiVec) *reinterpret_cast<uint4 *>(dst + o3) = v3;
+            const unsigned long long o = hiVec + threadIdx.x;
+            if (o < hi) dst[o] = src[o];  // (fewer than 16 bytes)
+        } else {
+            for (unsigned long long o = lo + threadIdx.x; o < hi; o += kPackBlock) dst[o] = src[o];
+        }
+    }
+}
+
+// cfx_checkpoint_restore: what cfx_load_state does to the dense arrays on the host — every running vehicle takes its first
+// step's gap from the state (kFlagStateGap; ControllerInfo::gap is stored state), the custom-speed bit stays
+__global__ void k_checkpoint_state_gap(int n, const int32_t *vid, const double *gap, uint8_t *flags, double *gapState, int nV) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int v = vid[i];
+    if (v < 0 || v >= nV) return;
+    gapState[v] = gap[i];
+    flags[i] = (uint8_t) ((flags[i] & kFlagCustom) | kFlagStateGap);
+}
+
 __global__ void kr_reset(int D, int32_t *head, int32_t *cnt, int4 *scratch) {
     const int d = blockIdx.x * blockDim.x + threadIdx.x;
     if (d >= D) return;

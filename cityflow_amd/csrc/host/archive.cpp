@@ -600,6 +600,91 @@ void EngineHost::load(const Archive &a) {
     nextCompactAt_ = std::min(nextCompactAt_, compactAuto_ ? std::max(compactAt_, 32 * held) : held + compactAt_);
 }
 
+// ------------------------------------------------------------------------------------------ checkpoints in device memory
+void DeviceCheckpoint::release() {
+    if (ck && be && be->cfx_checkpoint_destroy) be->cfx_checkpoint_destroy(ck);
+    ck = nullptr;
+    host.clear();
+    waitingCustom.clear();
+    localToGlobal.clear();
+    globalToLocal.clear();
+}
+
+cfx_checkpoint_desc DeviceCheckpoint::desc() const {
+    cfx_checkpoint_desc d{};
+    if (ck && be && be->cfx_checkpoint_info) be->cfx_checkpoint_info(ck, &d);
+    return d;
+}
+
+void DeviceCheckpoint::checkUsable(const DeviceCheckpoint *ck, const void *owner, const char *what) {
+    if (!ck) throw std::invalid_argument(std::string(what) + ": no checkpoint given");
+    if (ck->released()) throw std::invalid_argument(std::string(what) + ": the checkpoint has been released");
+    if (ck->owner != owner) throw std::invalid_argument(std::string(what) + ": the checkpoint belongs to another engine");
+}
+
+std::string EngineHost::checkpointUnsupported() {
+    if (!be_.hasCheckpoints()) return "the backend '" + backendName() + "' has no checkpoints in device memory";
+    if (laneChange_) return "checkpoints in device memory exist on the ring layout only: not with laneChange";
+    if (layoutName() != "ring") return "checkpoints in device memory exist on the ring layout only: this engine uses the " + layoutName() + " layout";
+    return "";
+}
+
+std::shared_ptr<DeviceCheckpoint> EngineHost::checkpoint(std::shared_ptr<DeviceCheckpoint> into) {
+    const std::string why = checkpointUnsupported();
+    if (!why.empty()) throw std::logic_error("checkpoint: " + why);
+    if (into) DeviceCheckpoint::checkUsable(into.get(), this, "checkpoint(into=)");
+    dropAhead();
+    settleLaneChange();
+    flushPhases();  // (set_tl_phase calls made so far are part of the state, as they are of a snapshot)
+    if (devicePhaseUnchecked_ || plan_.unchecked()) {  // (a rejected device-side signal set is reported before the checkpoint is taken)
+        check(be_.cfx_sync(dev_), "cfx_sync");
+        raiseDeviceError();
+    }
+    std::shared_ptr<DeviceCheckpoint> ck = into;
+    if (!ck) {
+        ck = std::make_shared<DeviceCheckpoint>();
+        ck->be = &be_;
+        ck->owner = this;
+        check(be_.cfx_checkpoint_create(dev_, &ck->ck), "cfx_checkpoint_create");
+    }
+    check(be_.cfx_checkpoint_save(dev_, ck->ck), "cfx_checkpoint_save");
+    ck->host.resize(1);
+    ck->host[0] = spawner_.saveState();
+    ck->step = step_;
+    ck->waitingCustom = waitingCustom_;
+    return ck;
+}
+
+// EngineHost::load with the checkpoint in the archive's place
+void EngineHost::rollback(DeviceCheckpoint &ck) {
+    const std::string why = checkpointUnsupported();
+    if (!why.empty()) throw std::logic_error("rollback: " + why);
+    DeviceCheckpoint::checkUsable(&ck, this, "rollback");
+    if (ck.host.size() != 1) throw std::invalid_argument("rollback: nothing was saved into the checkpoint");
+    dropAhead();
+    settleLaneChange();
+    if (devicePhaseUnchecked_ || plan_.unchecked()) {  // (... and not lost in a rollback)
+        check(be_.cfx_sync(dev_), "cfx_sync");
+        raiseDeviceError();
+    }
+    pendingPhaseInter_.clear();
+    pendingPhaseValue_.clear();
+    spawner_.loadState(ck.host[0]);
+    uploadNewTablesIfAny();
+    check(be_.cfx_checkpoint_restore(dev_, ck.ck), "cfx_checkpoint_restore");
+    forgetPhases();  // (the lights now show the checkpoint's phases)
+    step_ = ck.step;
+    flow_.baseline((int64_t) step_);
+    move_.baseline((int64_t) step_);
+    trip_.forget();
+    tripNoteVehicles();
+    trip_.baseline((int64_t) step_);
+    waitingCustom_ = ck.waitingCustom;
+    vehicleEpoch_ += 1;  // vehicle numbers of the checkpoint replace the current ones (a compaction may lie in between)
+    const size_t held = spawner_.vehicles.size();
+    nextCompactAt_ = std::min(nextCompactAt_, compactAuto_ ? std::max(compactAt_, 32 * held) : held + compactAt_);
+}
+
 // Archive(Engine&, filename) archive.cpp:345-550: rebuild an Archive from the reference's JSON format.
 void EngineHost::loadFromFile(const std::string &path) {
     dropAhead();

@@ -119,6 +119,11 @@ void Backend::open(const std::string &libPath) {
     CFX_FN_OPTIONAL(cfx_restore_tl_plan)
     CFX_FN_OPTIONAL(cfx_tl_plan_error)
     CFX_FN_OPTIONAL(cfx_get_cross_stats)
+    CFX_FN_OPTIONAL(cfx_checkpoint_create)
+    CFX_FN_OPTIONAL(cfx_checkpoint_save)
+    CFX_FN_OPTIONAL(cfx_checkpoint_restore)
+    CFX_FN_OPTIONAL(cfx_checkpoint_info)
+    CFX_FN_OPTIONAL(cfx_checkpoint_destroy)
 #undef CFX_FN_OPTIONAL
     if (cfx_abi_version() != CFX_ABI_VERSION)
         throw std::runtime_error("cityflow_amd: ABI version mismatch in '" + libPath + "'");

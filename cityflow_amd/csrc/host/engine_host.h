@@ -120,6 +120,15 @@ struct Backend {
     cfx_restore_tl_plan_fn cfx_restore_tl_plan = nullptr;
     cfx_tl_plan_error_fn cfx_tl_plan_error = nullptr;
     cfx_get_cross_stats_fn cfx_get_cross_stats = nullptr;  // (a library without it: crossStats() reports nothing)
+    // optional as a set: checkpoints in device memory (without them there is no such call: DeviceCheckpoint below)
+    cfx_checkpoint_create_fn cfx_checkpoint_create = nullptr;
+    cfx_checkpoint_save_fn cfx_checkpoint_save = nullptr;
+    cfx_checkpoint_restore_fn cfx_checkpoint_restore = nullptr;
+    cfx_checkpoint_info_fn cfx_checkpoint_info = nullptr;
+    cfx_checkpoint_destroy_fn cfx_checkpoint_destroy = nullptr;
+    bool hasCheckpoints() const {
+        return cfx_checkpoint_create && cfx_checkpoint_save && cfx_checkpoint_restore && cfx_checkpoint_info && cfx_checkpoint_destroy;
+    }
     bool hasTlPlan() const {
         return hasDeviceBuffers() && cfx_set_tl_plan_device && cfx_set_tl_plan && cfx_get_tl_phase_durations_device &&
                cfx_get_tl_phase_durations && cfx_restore_tl_plan && cfx_tl_plan_error;
@@ -213,6 +222,30 @@ struct VehicleColumns {
 };
 VehicleColumns vehicleColumnsOf(const Backend &be, cfx_engine *dev, bool vid, bool dis, bool speed);  // (drivable always)
 
+// A checkpoint in device memory (cfx_checkpoint_* of include/cityflow_amd.h; the public calls are checkpoint() / rollback() of
+// cityflow_amd/torch_io.py), of an EngineHost or a VectorEngineHost: the backend's part, and what Engine.load() takes from an
+// Archive on the host — the spawners' states (one per environment) and the step — plus what an Archive does not carry.  It
+// belongs to the engine that took it and must not outlive it (the binding keeps the engine alive).
+struct DeviceCheckpoint {
+    const Backend *be = nullptr;
+    cfx_checkpoint *ck = nullptr;  // null once released
+    const void *owner = nullptr;   // the EngineHost / VectorEngineHost
+    std::vector<Spawner::State> host;
+    size_t step = 0;
+    std::map<int32_t, double> waitingCustom;                  // EngineHost::waitingCustom_
+    std::vector<std::vector<int32_t>> localToGlobal;          // VectorEngineHost's numbering
+    std::vector<std::pair<int32_t, int32_t>> globalToLocal;
+    DeviceCheckpoint() = default;
+    DeviceCheckpoint(const DeviceCheckpoint &) = delete;
+    DeviceCheckpoint &operator=(const DeviceCheckpoint &) = delete;
+    ~DeviceCheckpoint() { release(); }
+    bool released() const { return ck == nullptr; }
+    void release();                     // frees the device memory; the checkpoint can no longer be rolled back to
+    cfx_checkpoint_desc desc() const;   // (all zero once released)
+    // what the two hosts share: argument checks (std::invalid_argument), then the backend's calls
+    static void checkUsable(const DeviceCheckpoint *ck, const void *owner, const char *what);
+};
+
 class EngineHost {
 public:
     EngineHost(const std::string &configFile, int threadNum, const std::string &backendLib = "");
@@ -253,6 +286,12 @@ public:
     int64_t vehicleCompactions() const { return vehicleCompactions_; }
     void load(const Archive &archive);         // engine.h:176
     void loadFromFile(const std::string &path);  // engine.cpp:822-825
+    // ---- checkpoints in device memory (DeviceCheckpoint above; archive.cpp): as load(snapshot()), except that the vehicles
+    //      keep their place in their routes and nothing per vehicle crosses the link
+    bool checkpointCalls() const { return be_.hasCheckpoints(); }
+    std::string checkpointUnsupported();  // why this engine has no device checkpoints ("" = it has)
+    std::shared_ptr<DeviceCheckpoint> checkpoint(std::shared_ptr<DeviceCheckpoint> into);  // into: overwritten in place (may be null)
+    void rollback(DeviceCheckpoint &ck);
     void setReplayLogFile(const std::string &logFile);  // engine.cpp:727-734
     void setSaveReplay(bool open);                       // engine.cpp:736-742
 

@@ -475,6 +475,11 @@ template <typename E> void defDeviceBuffers(py::class_<E> &c) {
         .def("_tl_phase_durations_device", &E::tlPhaseDurationsDevice, "out_ptr"_a, "consumer_stream"_a)
         .def("_tl_phase_durations", &tlPhaseDurationsArray<E>, "float64, flat (env-major, then intersection, then phase)")
         .def("_restore_tl_plan", &E::restoreTlPlan)
+        .def("_checkpoint_calls", &E::checkpointCalls, "the backend has checkpoints in device memory (checkpoint() / rollback())")
+        .def("_checkpoint_unsupported", &E::checkpointUnsupported, "why this engine has no checkpoints in device memory ('' = it has)")
+        .def("_checkpoint", &E::checkpoint, "into"_a = py::none(), py::keep_alive<0, 1>(),
+             "DeviceCheckpoint of the state as of now (into: overwritten in place); it keeps the engine alive")
+        .def("_rollback", &E::rollback, "checkpoint"_a)
         .def("_stream_handle", &E::streamHandle, "(engine's hipStream_t as an int, HIP device ordinal)")
         .def("_set_tl_phases_device", &E::setTrafficLightPhasesDevice, "phases_ptr"_a, "n"_a, "producer_stream"_a)
         .def("_rl_traffic_light", &E::rlTrafficLight)
@@ -701,6 +706,20 @@ double spawnBenchmark(const std::string &roadnetFile, const std::string &flowFil
 
 PYBIND11_MODULE(_cityflow, m) {
     m.doc() = "MI355X-native CityFlow step engine (drop-in for the reference `cityflow` module)";
+
+    using cfa::DeviceCheckpoint;
+    py::class_<DeviceCheckpoint, std::shared_ptr<DeviceCheckpoint>>(
+        m, "DeviceCheckpoint",
+        "The whole simulation state of an Engine or VectorEngine in device memory (checkpoint() / rollback()); not consumed by a "
+        "rollback, freed by release() or with the object")
+        .def_property_readonly("step", [](const DeviceCheckpoint &c) { return c.released() ? (int64_t) -1 : c.desc().step; })
+        .def_property_readonly("num_running", [](const DeviceCheckpoint &c) { return c.desc().n_running; }, "running vehicles")
+        .def_property_readonly("num_vehicle_numbers", [](const DeviceCheckpoint &c) { return c.desc().n_vehicles; },
+                               "vehicle numbers handed out (rows of the device's vehicle table)")
+        .def_property_readonly("device_bytes", [](const DeviceCheckpoint &c) { return c.desc().device_bytes; },
+                               "device memory held (0 once released)")
+        .def_property_readonly("released", &DeviceCheckpoint::released)
+        .def("release", &DeviceCheckpoint::release, "free the device memory now; rollback() to it is a ValueError from here on");
 
     py::class_<EngineHost> engineClass(m, "Engine");
     engineClass

@@ -570,6 +570,78 @@ void VectorEngineHost::reset(bool resetRnd) {
     hostAheadSec_.store(0.0, std::memory_order_relaxed);
 }
 
+// ---- checkpoints in device memory: the one device engine's, and per environment what EngineHost keeps for its one
+std::string VectorEngineHost::checkpointUnsupported() {
+    if (!be_.hasCheckpoints()) return "the backend '" + backendName() + "' has no checkpoints in device memory";
+    if (laneChange_) return "checkpoints in device memory exist on the ring layout only: not with laneChange";
+    std::lock_guard<std::mutex> guard(queryMutex_);
+    if (be_.cfx_get_layout(dev_) != CFX_LAYOUT_RING) return "checkpoints in device memory exist on the ring layout only: this engine uses the dense layout";
+    return "";
+}
+
+std::shared_ptr<DeviceCheckpoint> VectorEngineHost::checkpoint(std::shared_ptr<DeviceCheckpoint> into) {
+    const std::string why = checkpointUnsupported();
+    if (!why.empty()) throw std::logic_error("checkpoint: " + why);
+    if (into) DeviceCheckpoint::checkUsable(into.get(), this, "checkpoint(into=)");
+    dropAhead();  // (the ahead thread and its pool are idle from here on; the spawners stand where the last step left them)
+    settleLaneChange();
+    std::shared_ptr<DeviceCheckpoint> ck = into;
+    {
+        std::lock_guard<std::mutex> guard(queryMutex_);
+        if (devicePhaseUnchecked_ || plan_.unchecked()) {  // (a rejected device-side signal set is reported before the checkpoint is taken)
+            check(be_.cfx_sync(dev_), "cfx_sync");
+            raiseDeviceError();
+        }
+        if (!ck) {
+            ck = std::make_shared<DeviceCheckpoint>();
+            ck->be = &be_;
+            ck->owner = this;
+            check(be_.cfx_checkpoint_create(dev_, &ck->ck), "cfx_checkpoint_create");
+        }
+        check(be_.cfx_checkpoint_save(dev_, ck->ck), "cfx_checkpoint_save");
+    }
+    ck->host.resize((size_t) R_);
+    for (int r = 0; r < R_; ++r) ck->host[(size_t) r] = spawners_[(size_t) r]->saveState();
+    ck->localToGlobal = localToGlobal_;
+    ck->globalToLocal = globalToLocal_;
+    ck->step = step_;
+    return ck;
+}
+
+void VectorEngineHost::rollback(DeviceCheckpoint &ck) {
+    const std::string why = checkpointUnsupported();
+    if (!why.empty()) throw std::logic_error("rollback: " + why);
+    DeviceCheckpoint::checkUsable(&ck, this, "rollback");
+    if (ck.host.size() != (size_t) R_) throw std::invalid_argument("rollback: nothing was saved into the checkpoint");
+    dropAhead();
+    settleLaneChange();
+    {
+        std::lock_guard<std::mutex> guard(queryMutex_);
+        if (devicePhaseUnchecked_ || plan_.unchecked()) {  // (... and not lost in a rollback)
+            check(be_.cfx_sync(dev_), "cfx_sync");
+            raiseDeviceError();
+        }
+        check(be_.cfx_checkpoint_restore(dev_, ck.ck), "cfx_checkpoint_restore");
+    }
+    for (int r = 0; r < R_; ++r) spawners_[(size_t) r]->loadState(ck.host[(size_t) r]);
+    localToGlobal_ = ck.localToGlobal;
+    globalToLocal_ = ck.globalToLocal;
+    step_ = ck.step;
+    {
+        std::lock_guard<std::mutex> guard(queryMutex_);
+        flow_.baseline((int64_t) step_);
+        move_.baseline((int64_t) step_);
+        trip_.forget();
+        if (trip_.on() && !trip_.onDevice())  // (host tracker: the vehicles of the checkpoint, by their global numbers)
+            for (size_t g = 0; g < globalToLocal_.size(); ++g) {
+                const auto &el = globalToLocal_[g];
+                trip_.note((int32_t) g, spawners_[(size_t) el.first]->vehicles[(size_t) el.second].enterTime, el.first);
+            }
+        trip_.baseline((int64_t) step_);
+    }
+    submitted_.store((uint64_t) step_, std::memory_order_release);
+}
+
 std::vector<int32_t> VectorEngineHost::laneVehicleCounts() {
     std::lock_guard<std::mutex> guard(queryMutex_);  // (the ABI is not re-entrant: the ahead thread may be asking the device)
     std::vector<int32_t> out((size_t) R_ * L_);

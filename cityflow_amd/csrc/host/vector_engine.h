@@ -35,6 +35,11 @@ public:
     int numIntersections() const { return I_; }
     void nextStep();
     void reset(bool resetRnd);
+    // checkpoints in device memory of every environment at once (EngineHost::checkpoint and its kin)
+    bool checkpointCalls() const { return be_.hasCheckpoints(); }
+    std::string checkpointUnsupported();
+    std::shared_ptr<DeviceCheckpoint> checkpoint(std::shared_ptr<DeviceCheckpoint> into);
+    void rollback(DeviceCheckpoint &ck);
     double getCurrentTime() const { return step_ * interval_; }
     std::vector<int32_t> laneVehicleCounts();         // [R * L], env-major
     std::vector<int32_t> laneWaitingVehicleCounts();  // [R * L]

@@ -765,8 +765,38 @@ def restore_tl_plan(self):
     self._restore_tl_plan()
 
 
+def _need_checkpoint_calls(eng, what):
+    why = eng._checkpoint_unsupported()
+    if why:
+        raise NotImplementedError("%s: %s" % (what, why))
+
+
+def checkpoint(self, into=None):
+    """The whole simulation state as a DeviceCheckpoint held in device memory: every running and waiting vehicle, the lights'
+    phases and remaining times, the counters, Lane::history where it is kept, and the spawners' state on the host — what
+    `snapshot()` puts into an Archive, without any of it crossing the link.  `into`: a checkpoint of this engine that has not
+    been released, overwritten in place (its memory is reused while it is large enough).  Ordered on the engine's stream; waits
+    for the device once.  Needs neither torch nor numpy.  The durations set by set_tl_plan_tensor are the engine's, not the
+    checkpoint's.  The ring layout only — NotImplementedError with laneChange, on the dense layout and on a backend without
+    the call (the CPU twin); ValueError for a checkpoint of another engine or a released one."""
+    _need_checkpoint_calls(self, "checkpoint")
+    return self._checkpoint(into)
+
+
+def rollback(self, checkpoint):
+    """Return to the state `checkpoint` holds, as `load(snapshot())` would — except that the vehicles keep their place in their
+    routes (get_vehicle_info's route), so the run continues bit for bit as if it had never left that state.  The checkpoint is
+    not consumed: roll back to it as often as needed ("roll back, try the next plan").  It stays valid across ring and table
+    growth, vehicle compaction and reset().  Trackers (track_lane_flow, track_movement_flow, track_trips) take a new baseline
+    and stay on, as after load().  ValueError for a checkpoint of another engine or a released one."""
+    _need_checkpoint_calls(self, "rollback")
+    self._rollback(checkpoint)
+
+
 def install(*classes):
     for cls in classes:
+        cls.checkpoint = checkpoint
+        cls.rollback = rollback
         cls.set_tl_plan_tensor = set_tl_plan_tensor
         cls.get_tl_phase_durations_tensor = get_tl_phase_durations_tensor
         cls.set_tl_plan = set_tl_plan

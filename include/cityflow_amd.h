@@ -822,6 +822,36 @@ typedef struct cfx_cross_stats {
 } cfx_cross_stats;
 typedef int32_t (*cfx_get_cross_stats_fn)(cfx_engine *e, cfx_cross_stats *out, int32_t reset);
 
+/* ---- Checkpoints in device memory (OPTIONAL entry points, as above; all five or none).  A checkpoint holds what cfx_load_state
+ * replaces — the running vehicles in cfx_state's order with leader and gap, the vehicle table up to the numbers handed out, the
+ * waiting queues, the lights' phases and remaining times, the scalars, Lane::history where the engine keeps it — in memory of
+ * the engine's device; nothing per vehicle crosses the link in either direction.  The ring layout only (engines without
+ * lane_change and tiles, not created with CFX_LAYOUT_DENSE): otherwise cfx_checkpoint_create returns CFX_ERR_STATE and
+ * cfx_last_error says why.  A checkpoint belongs to the engine that created it and is independent of the rings' and the vehicle
+ * table's capacities, so it stays valid across their growth, cfx_load_state and cfx_reset.  The durations set by
+ * cfx_set_tl_plan are not part of it (as for cfx_load_state).
+ *   "cfx_checkpoint_create"   a new, empty checkpoint of e in *out
+ *   "cfx_checkpoint_save"     overwrite ck with the state as of now (a deferred commit and Lane::history record are launched first);
+ *                             waits for the device once, for the number of running vehicles, which sizes ck's memory
+ *   "cfx_checkpoint_restore"  cfx_load_state from ck: the same reset, capacity checks, ring growth and rebuild, with device-to-device
+ *                             sources; every running vehicle keeps its route position (cfx_state::r_route_pos as cfx_get_vehicles
+ *                             reports it).  ck is not consumed.  Statistics kept by the backend take a new baseline, as after a load.
+ *                             CFX_ERR_INVALID for a checkpoint of another engine or one never saved
+ *   "cfx_checkpoint_info"     what ck holds
+ *   "cfx_checkpoint_destroy"  frees ck; checkpoints still alive at cfx_destroy lose their device memory there and can only be destroyed */
+typedef struct cfx_checkpoint cfx_checkpoint;
+typedef struct cfx_checkpoint_desc {
+    int64_t step;         /* cfx_state::step of the saved state (-1: never saved) */
+    int64_t device_bytes; /* device memory held (0 after cfx_destroy of the engine) */
+    int32_t n_running;    /* running vehicles */
+    int32_t n_vehicles;   /* vehicle numbers handed out (rows of the vehicle table) */
+} cfx_checkpoint_desc;
+typedef int32_t (*cfx_checkpoint_create_fn)(cfx_engine *e, cfx_checkpoint **out);
+typedef int32_t (*cfx_checkpoint_save_fn)(cfx_engine *e, cfx_checkpoint *ck);
+typedef int32_t (*cfx_checkpoint_restore_fn)(cfx_engine *e, cfx_checkpoint *ck);
+typedef int32_t (*cfx_checkpoint_info_fn)(const cfx_checkpoint *ck, cfx_checkpoint_desc *out);
+typedef void (*cfx_checkpoint_destroy_fn)(cfx_checkpoint *ck);
+
 #ifdef __cplusplus
 }
 #endif
