@@ -92,6 +92,11 @@ struct cfx_checkpoint {
     bool timesDyadic = true;
 };
 
+// the trackers (cfx_engine::tracker), in the order of their lifecycle, and their names in messages
+enum Tracker { kLaneFlow, kMoveFlow, kTrips, kTrackers };
+static const char *const kTrackerName[kTrackers] = {"lane-flow", "movement-flow", "trip"};
+static const char *const kTrackerEnable[kTrackers] = {"cfx_lane_flow_enable", "cfx_movement_flow_enable", "cfx_trip_stats_enable"};
+
 struct cfx_engine {
     int device = 0;
     int nCU = 256;  // compute units of the device (hipDeviceProp_t::multiProcessorCount)
@@ -190,20 +195,17 @@ struct cfx_engine {
     InterFeatOut interTab{};        // the table pointers and M / P; the output pointers stay null here
     int32_t *interOutI = nullptr;   // [I * (1 + 4 M + P)] phase, in, in_waiting, out, inside, phase_pressure
     double *interOutD = nullptr;    // [I]
-    // cfx_lane_flow_enable: per-lane flow statistics across steps (laneFlowTick, cfx_kernels.h).  Nothing is allocated or launched
-    // while it is off.  `flow.rec` grows with the vehicle tables (ensureVidCap); `flow.tick` is the last tick taken and only
-    // ever counts up; `flowBaseline`: a baseline is due before the next step or read (enabling, reset, cfx_load_state)
-    bool flowOn = false, flowBaseline = false;
-    LaneFlowDev flow{};
-    // cfx_trip_stats_enable: per-environment trip statistics across steps (k_trip_tick, cfx_kernels.h), kept like lane flow:
-    // `trip.seen` grows with the vehicle tables (ensureVidCap), `tripBaseline`: a baseline is due before the next step or read
-    bool tripOn = false, tripBaseline = false;
-    TripDev trip{};
-    // cfx_movement_flow_enable: per-movement flow statistics across steps (moveFlowTick, cfx_kernels.h), kept like lane flow:
-    // `move.rec` grows with the vehicle tables (ensureVidCap), `moveBaseline`: a baseline is due before the next step or read;
-    // the host getter's device scratch (in `owned`, freed with the tracker)
-    bool moveOn = false, moveBaseline = false;
-    MoveFlowDev move{};
+    // The trackers: statistics kept across steps (cfx_lane_flow_enable, cfx_movement_flow_enable, cfx_trip_stats_enable; DESIGN.md
+    // "One scaffold for the trackers").  One lifecycle, always in this order.  Nothing is allocated or launched for a tracker
+    // that is off.  `baselineDue`: enabling, a reset or cfx_load_state left a baseline to the next step or read (trackersSettle).
+    // Each keeps a per-vehicle shadow that grows with the vehicle tables (ensureVidCap) and a tick that only ever counts up.
+    struct TrackerSlot {
+        bool on = false, baselineDue = false;
+    } tracker[kTrackers];
+    LaneFlowDev flow{};             // laneFlowTick (cfx_kernels.h)
+    MoveFlowDev move{};             // moveFlowTick
+    TripDev trip{};                 // k_trip_tick
+    // cfx_get_movement_flow: the host getter's device scratch (freed with the tracker)
     int32_t *moveOutI = nullptr;    // [3 I M] entered, left, max_waiting_steps
     int64_t *moveOutL = nullptr;    // [5 I M] the five sums
     int cross2 = -1;                // cross phase: 1 = k_cross2 (throughput), 0 = k_cross (latency), -1 = by size
@@ -548,19 +550,18 @@ struct cfx_engine {
         // nextWait of not-yet-used vids must read -1 (k_spawn_link relies on it)
         HIP_TRY(hipMemsetAsync(vt.nextWait + spawned, 0xFF, (nc - (size_t) spawned) * sizeof(int32_t), stream));
         if (ring) HIP_TRY(hipMemsetAsync(slotOf + spawned, 0xFF, (nc - (size_t) spawned) * sizeof(int32_t), stream));
-        if (flowOn) {  // (records of numbers not used yet name lane -1: they match no lane)
-            if ((rc = growDeferred(&flow.rec, (size_t) spawned, nc))) return rc;
-            HIP_TRY(hipMemsetAsync(flow.rec + spawned, 0xFF, (nc - (size_t) spawned) * sizeof(int4), stream));
-        }
-        if (moveOn) {  // (records of numbers not used yet name drivable -1 at tick -1: they match nothing)
-            if ((rc = growDeferred(&move.rec, (size_t) spawned, nc))) return rc;
-            HIP_TRY(hipMemsetAsync(move.rec + spawned, 0xFF, (nc - (size_t) spawned) * sizeof(int4), stream));
-        }
-        if (tripOn) {  // (numbers not used yet: never seen)
-            if ((rc = growDeferred(&trip.seen, (size_t) spawned, nc))) return rc;
-            HIP_TRY(hipMemsetAsync(trip.seen + spawned, 0xFF, nc - (size_t) spawned, stream));
-        }
+        // (numbers not used yet: a record names drivable -1 at tick -1 and matches nothing; a status reads never seen)
+        if (tracker[kLaneFlow].on && (rc = growShadow(&flow.rec, nc))) return rc;
+        if (tracker[kMoveFlow].on && (rc = growShadow(&move.rec, nc))) return rc;
+        if (tracker[kTrips].on && (rc = growShadow(&trip.seen, nc))) return rc;
         vidCap = nc;
+        return CFX_OK;
+    }
+    // a tracker's per-vehicle shadow follows the vehicle tables: the numbers in use kept, the new tail all 0xFF
+    template <typename T> int growShadow(T **p, size_t nc) {
+        int rc;
+        if ((rc = growDeferred(p, (size_t) spawned, nc))) return rc;
+        HIP_TRY(hipMemsetAsync(*p + spawned, 0xFF, (nc - (size_t) spawned) * sizeof(T), stream));
         return CFX_OK;
     }
 
@@ -883,12 +884,6 @@ struct cfx_engine {
         HIP_TRY(hipGetLastError());
         return CFX_OK;
     }
-    // ... the baseline that enabling, a reset or a load left to the next step or read (the caller has settled the step and the rings)
-    int flowSettle() {
-        if (!flowOn || !flowBaseline) return CFX_OK;
-        flowBaseline = false;
-        return flowTick(true);
-    }
     // cfx_movement_flow_enable: one tick (or baseline) over every drivable, on the committed state, after everything enqueued so far
     int moveTick(bool baseline) {
         move.tick += 1;
@@ -905,11 +900,6 @@ struct cfx_engine {
         else hipLaunchKernelGGL(kd_movement_flow, dim3(gridFor(threads)), dim3(kBlock), 0, stream, ctx(), move);
         HIP_TRY(hipGetLastError());
         return CFX_OK;
-    }
-    int moveSettle() {
-        if (!moveOn || !moveBaseline) return CFX_OK;
-        moveBaseline = false;
-        return moveTick(true);
     }
     // cfx_trip_stats_enable: one tick (or baseline) over the vehicle numbers, on the committed state, after everything enqueued so far
     int tripTick(bool baseline) {
@@ -932,10 +922,89 @@ struct cfx_engine {
         HIP_TRY(hipGetLastError());
         return CFX_OK;
     }
-    int tripSettle() {
-        if (!tripOn || !tripBaseline) return CFX_OK;
-        tripBaseline = false;
-        return tripTick(true);
+    // what enabling a tracker allocates (a shadow starts all 0xFF; what the first baseline fills is left to it) ...
+    int trackerAlloc(int which) {
+        int rc;
+        if (which == kLaneFlow) {
+            if ((rc = allocRaw(&flow.rec, vidCap)) || (rc = allocRaw(&flow.lane, (size_t) L))) return rc;
+            HIP_TRY(hipMemsetAsync(flow.rec, 0xFF, std::max<size_t>(vidCap, 1) * sizeof(int4), stream));
+            HIP_TRY(hipMemsetAsync(flow.lane, 0, std::max<size_t>((size_t) L, 1) * sizeof(cfx_lane_flow_lane), stream));
+        } else if (which == kMoveFlow) {
+            if ((rc = allocRaw(&move.rec, vidCap)) || (rc = allocRaw(&move.link, (size_t) K)) || (rc = allocRaw(&move.skip, (size_t) K * 3))) return rc;
+            HIP_TRY(hipMemsetAsync(move.rec, 0xFF, std::max<size_t>(vidCap, 1) * sizeof(int4), stream));
+        } else {
+            const int nEnvs = cfg.n_envs > 1 ? cfg.n_envs : 1;
+            if (R % nEnvs != 0) {
+                err = "cfx_trip_stats_enable: n_envs does not divide the number of roads";
+                return CFX_ERR_STATE;
+            }
+            if ((rc = allocRaw(&trip.seen, vidCap)) || (rc = allocRaw(&trip.env, (size_t) nEnvs))) return rc;
+            trip.nEnvs = nEnvs;
+            trip.roadsPerEnv = std::max(R / nEnvs, 1);
+        }
+        return CFX_OK;
+    }
+    // ... and disabling frees, the getters' scratch too
+    int trackerFree(int which) {
+        int rc;
+        if (which == kLaneFlow) {
+            rc = freeRaw(&flow.rec) | freeRaw(&flow.lane);
+            flow = LaneFlowDev{};
+        } else if (which == kMoveFlow) {
+            rc = freeRaw(&move.rec) | freeRaw(&move.link) | freeRaw(&move.skip) | freeRaw(&moveOutI) | freeRaw(&moveOutL);
+            move = MoveFlowDev{};
+        } else {
+            rc = freeRaw(&trip.seen) | freeRaw(&trip.env);
+            trip = TripDev{};
+        }
+        return rc ? CFX_ERR_DEVICE : CFX_OK;
+    }
+    // ---- the trackers' lifecycle, always lane, movement, trips
+    int trackerTick(int which, bool baseline) {
+        return which == kLaneFlow ? flowTick(baseline) : which == kMoveFlow ? moveTick(baseline) : tripTick(baseline);
+    }
+    bool anyTracker() const { return tracker[kLaneFlow].on || tracker[kMoveFlow].on || tracker[kTrips].on; }
+    // the baseline that enabling, a reset or a load left to the next step or read (the caller has settled the step and the rings)
+    int trackerSettle(int which) {
+        if (!tracker[which].on || !tracker[which].baselineDue) return CFX_OK;
+        tracker[which].baselineDue = false;
+        return trackerTick(which, true);
+    }
+    int trackersSettle() {
+        int rc = CFX_OK;
+        for (int t = 0; t < kTrackers && !rc; ++t) rc = trackerSettle(t);
+        return rc;
+    }
+    int trackersTick() {  // after a step, on the committed state
+        int rc = CFX_OK;
+        for (int t = 0; t < kTrackers && !rc; ++t)
+            if (tracker[t].on) rc = trackerTick(t, false);
+        return rc;
+    }
+    void trackersRebaseline() {  // a reset or a load: taken on the state the caller sets up, before the next step or read
+        for (TrackerSlot &t : tracker) t.baselineDue = t.on;
+    }
+    // cfx_*_enable: on takes the first baseline at once
+    int trackerEnable(int which, int32_t on) {
+        HIP_TRY(hipSetDevice(device));
+        TrackerSlot &t = tracker[which];
+        if (!on) {
+            if (!t.on) return CFX_OK;
+            HIP_TRY(hipStreamSynchronize(stream));  // (a tick may still be running; a shadow a growth retired stays with `retired`)
+            t = TrackerSlot{};
+            return trackerFree(which);
+        }
+        if (lc.on || tiled) {
+            err = std::string(kTrackerEnable[which]) + ": not with lane change and not on a tile";
+            return CFX_ERR_STATE;
+        }
+        if (t.on) return CFX_OK;
+        int rc;
+        if ((rc = settle(false))) return rc;
+        if (ring && (rc = ringEnsure())) return rc;
+        if ((rc = trackerAlloc(which))) return rc;
+        t.on = t.baselineDue = true;
+        return trackerSettle(which);
     }
     int settle(bool withHistory = true) {
         if (haloImportPending) {
@@ -1007,9 +1076,7 @@ struct cfx_engine {
             if (mirrorValid && __atomic_load_n(&hMirror->sc.ringNearFull, __ATOMIC_RELAXED) != 0) ringGrowRequested = true;
             if ((rc = ringEnsure())) return rc;
         }
-        if ((rc = flowSettle())) return rc;  // (lane flow: a baseline that is due is taken on the state this step starts from)
-        if ((rc = moveSettle())) return rc;  // (movement flow: likewise)
-        if ((rc = tripSettle())) return rc;  // (trip statistics: likewise)
+        if ((rc = trackersSettle())) return rc;  // (a baseline that is due is taken on the state this step starts from)
         if (observing && ++observeIdle > kObserveIdle) {  // nobody has read the lane counts for a while
             observing = false;
             hCntValid = false;
@@ -1459,7 +1526,7 @@ struct cfx_engine {
         const bool useBig = cross2 >= 0 ? cross2 == 1 : activeEst > 240000;  // which form of the cross phase (§4)
         // This step's commit rides with the next step's admission (one launch less per step) where the step runs kr_cross,
         // which then advances the lights; the previous step's, if it is still pending, goes with this step's admission.
-        const bool deferCommit = ringMerge && !dbg && !tiled && !observing && !devObserving && !flowOn && !tripOn && !moveOn;  // (a caller that reads the lane counts after every step wants the commit now; so do the lane-flow, the movement-flow and the trip tick)
+        const bool deferCommit = ringMerge && !dbg && !tiled && !observing && !devObserving && !anyTracker();  // (a caller that reads the lane counts after every step wants the commit now; so do the trackers' ticks)
         // tiling: the previous step's halo import, if cfx_halo_wait left it to this launch
         const RingHaloIn hin = haloImportPending ? pendingImport : RingHaloIn{};
         haloImportPending = false;
@@ -1498,10 +1565,7 @@ struct cfx_engine {
         step += 1;
         mirrorValid = !tiled;
         histPending = hist.num != 0;  // (this step's Lane::history: with the next action launch, or settle() — on a tile behind the step's halo import)
-        if (flowOn && (rc = flowTick(false))) return rc;
-        if (moveOn && (rc = moveTick(false))) return rc;
-        if (tripOn) return tripTick(false);
-        return CFX_OK;
+        return trackersTick();
     }
 
     // ---- dense layout (and lane change, which runs on it)
@@ -1663,10 +1727,7 @@ struct cfx_engine {
             hipLaunchKernelGGL(k_lane_history, dim3(gridFor(L)), dim3(kBlock), 0, stream, ctx(), hist);
             HIP_TRY(hipGetLastError());
         }
-        if (flowOn && (rc = flowTick(false))) return rc;
-        if (moveOn && (rc = moveTick(false))) return rc;
-        if (tripOn) return tripTick(false);
-        return CFX_OK;
+        return trackersTick();
     }
 
     // (Re)build the rings: first use, a shorter vehicle template than the capacities were computed for, or growth.
@@ -1827,9 +1888,7 @@ struct cfx_engine {
         if (vidCap) HIP_TRY(hipMemsetAsync(vt.nextWait, 0xFF, vidCap * sizeof(int32_t), stream));
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipStreamSynchronize(stream));
-        flowBaseline = flowOn;  // (taken on the state the caller sets up, before the next step or read)
-        tripBaseline = tripOn;
-        moveBaseline = moveOn;
+        trackersRebaseline();
         return CFX_OK;
     }
 };
@@ -3721,6 +3780,14 @@ static int checkDevicePointer(cfx_engine *e, const void *p, const char *what) {
     return CFX_OK;
 }
 
+// ... each buffer of a list that is given (`what`: "<entry point>", the message names "<entry point>: <name>")
+static int checkDevicePointers(cfx_engine *e, const char *what, std::initializer_list<std::pair<const void *, const char *>> bufs) {
+    int rc;
+    for (const auto &b : bufs)
+        if (b.first && (rc = checkDevicePointer(e, b.first, (std::string(what) + ": " + b.second).c_str()))) return rc;
+    return CFX_OK;
+}
+
 int32_t cfx_stream_handle(cfx_engine *e, void **stream, int32_t *device) {
     if (!e) return CFX_ERR_INVALID;
     if (stream) *stream = (void *) e->stream;
@@ -3943,14 +4010,13 @@ static int laneObs(cfx_engine *e, const cfx_lane_obs *obs, bool toHost, void *co
     HIP_TRY(hipSetDevice(e->device));
     int rc;
     if (!toHost) {
-        const std::pair<const void *, const char *> bufs[] = {
-            {a.counts, "counts"}, {a.waiting, "waiting"}, {a.speed_sum, "speed_sum"}, {a.bins, "bins"}, {a.bins ? a.edges : nullptr, "edges"},
-            {a.front_distance, "front_distance"}, {a.front_speed, "front_speed"}, {a.front_lane_steps, "front_lane_steps"},
-            {a.front_waiting_steps, "front_waiting_steps"}};
-        for (const auto &b : bufs)
-            if (b.first && (rc = checkDevicePointer(e, b.first, (std::string(what) + ": " + b.second).c_str()))) return rc;
+        if ((rc = checkDevicePointers(e, what, {{a.counts, "counts"}, {a.waiting, "waiting"}, {a.speed_sum, "speed_sum"}, {a.bins, "bins"},
+                                                {a.bins ? a.edges : nullptr, "edges"}, {a.front_distance, "front_distance"},
+                                                {a.front_speed, "front_speed"}, {a.front_lane_steps, "front_lane_steps"},
+                                                {a.front_waiting_steps, "front_waiting_steps"}})))
+            return rc;
     }
-    if (tracker && !e->flowOn) {
+    if (tracker && !e->tracker[kLaneFlow].on) {
         e->err = std::string(what) + ": front_lane_steps / front_waiting_steps need lane-flow tracking (cfx_lane_flow_enable)";
         return CFX_ERR_STATE;
     }
@@ -3968,7 +4034,7 @@ static int laneObs(cfx_engine *e, const cfx_lane_obs *obs, bool toHost, void *co
     if (tracker) {
         o.flowRec = e->flow.rec;
         o.flowVidCap = (int) e->vidCap;
-        o.flowTick = e->flow.tick + (e->flowBaseline ? 1 : 0);  // (a baseline that is due: no record carries the tick it will take)
+        o.flowTick = e->flow.tick + (e->tracker[kLaneFlow].baselineDue ? 1 : 0);  // (a baseline that is due: no record carries the tick it will take)
         o.flowStep = e->flow.step;
     }
     if (!toHost) {
@@ -4256,49 +4322,41 @@ static_assert(std::is_same<decltype(&cfx_lane_flow_get_state), cfx_lane_flow_get
 static_assert(std::is_same<decltype(&cfx_lane_flow_set_state), cfx_lane_flow_set_state_fn>::value, "cfx_lane_flow_set_state");
 static_assert(sizeof(cfx_lane_flow_lane) == 48, "cfx_lane_flow_lane");
 
-// what every reader does first: the step's commit, the rings, a baseline that is due
-static int laneFlowPrepare(cfx_engine *e, const char *what) {
-    if (!e->flowOn) {
-        e->err = std::string(what) + ": lane-flow tracking is off (cfx_lane_flow_enable)";
-        return CFX_ERR_STATE;
-    }
-    int rc;
-    if ((rc = e->settle(false))) return rc;
-    if (e->ring && (rc = e->ringEnsure())) return rc;
-    return e->flowSettle();
+// ---- what the entry points of the three trackers share
+static int trackerRequire(cfx_engine *e, int which, const char *what) {
+    if (e->tracker[which].on) return CFX_OK;
+    e->err = std::string(what) + ": " + kTrackerName[which] + " tracking is off (" + kTrackerEnable[which] + ")";
+    return CFX_ERR_STATE;
 }
 
-int32_t cfx_lane_flow_enable(cfx_engine *e, int32_t on) {
-    if (!e) return CFX_ERR_INVALID;
-    auto fail = [e](const std::string &m) { return e->fail(m); };
-    HIP_TRY(hipSetDevice(e->device));
-    if (!on) {
-        if (!e->flowOn) return CFX_OK;
-        HIP_TRY(hipStreamSynchronize(e->stream));  // (a tick may still be running; a record array a growth retired stays with `retired`)
-        e->forget(e->flow.rec);
-        e->forget(e->flow.lane);
-        HIP_TRY(hipFree(e->flow.rec));
-        HIP_TRY(hipFree(e->flow.lane));
-        e->flow = LaneFlowDev{};
-        e->flowOn = e->flowBaseline = false;
-        return CFX_OK;
-    }
-    if (e->lc.on || e->tiled) {
-        e->err = "cfx_lane_flow_enable: not with lane change and not on a tile";
-        return CFX_ERR_STATE;
-    }
-    if (e->flowOn) return CFX_OK;
+// what every reader does first: the step's commit, the rings, a baseline that is due
+static int trackerPrepare(cfx_engine *e, int which, const char *what) {
     int rc;
+    if ((rc = trackerRequire(e, which, what))) return rc;
     if ((rc = e->settle(false))) return rc;
     if (e->ring && (rc = e->ringEnsure())) return rc;
-    if ((rc = e->allocRaw(&e->flow.rec, e->vidCap))) return rc;
-    if ((rc = e->allocRaw(&e->flow.lane, (size_t) e->L))) return rc;
-    HIP_TRY(hipMemsetAsync(e->flow.rec, 0xFF, std::max<size_t>(e->vidCap, 1) * sizeof(int4), e->stream));
-    HIP_TRY(hipMemsetAsync(e->flow.lane, 0, std::max<size_t>((size_t) e->L, 1) * sizeof(cfx_lane_flow_lane), e->stream));
-    e->flow.tick = 0;
-    e->flowOn = e->flowBaseline = true;
-    return e->flowSettle();
+    return e->trackerSettle(which);
 }
+
+// the per-vehicle records of a flow tracker (`rec`: LaneFlowDev::rec, MoveFlowDev::rec), copied out for cfx_*_get_state ...
+static int recordsOut(cfx_engine *e, const char *what, const int4 *rec, int32_t *records, int32_t nVehicles) {
+    auto fail = [e](const std::string &m) { return e->fail(m); };
+    if ((size_t) nVehicles > e->vidCap) return e->fail(std::string(what) + ": n_vehicles beyond the vehicle tables"), CFX_ERR_INVALID;
+    if (nVehicles) HIP_TRY(hipMemcpyAsync(records, rec, (size_t) nVehicles * sizeof(int4), hipMemcpyDeviceToHost, e->stream));
+    return CFX_OK;
+}
+// ... and in for cfx_*_set_state, behind the step's commit: the numbers past `nVehicles` read unused (0xFF) again
+static int recordsIn(cfx_engine *e, const char *what, int4 *rec, const int32_t *records, int32_t nVehicles) {
+    auto fail = [e](const std::string &m) { return e->fail(m); };
+    if ((size_t) nVehicles > e->vidCap) return e->fail(std::string(what) + ": n_vehicles beyond the vehicle tables"), CFX_ERR_INVALID;
+    int rc;
+    if ((rc = e->settle(false))) return rc;
+    HIP_TRY(hipMemsetAsync(rec, 0xFF, std::max<size_t>(e->vidCap, 1) * sizeof(int4), e->stream));
+    if (nVehicles) HIP_TRY(hipMemcpyAsync(rec, records, (size_t) nVehicles * sizeof(int4), hipMemcpyHostToDevice, e->stream));
+    return CFX_OK;
+}
+
+int32_t cfx_lane_flow_enable(cfx_engine *e, int32_t on) { return e ? e->trackerEnable(kLaneFlow, on) : CFX_ERR_INVALID; }
 
 static void launchLaneFlowDrain(cfx_engine *e, const LaneFlowOut &o, int32_t reset) {
     if (e->L <= 0) return;
@@ -4311,13 +4369,11 @@ int32_t cfx_observe_lane_flow_device(cfx_engine *e, int32_t *entered, int32_t *l
     auto fail = [e](const std::string &m) { return e->fail(m); };
     HIP_TRY(hipSetDevice(e->device));
     int rc;
-    if (entered && (rc = checkDevicePointer(e, entered, "cfx_observe_lane_flow_device: entered"))) return rc;
-    if (left && (rc = checkDevicePointer(e, left, "cfx_observe_lane_flow_device: left"))) return rc;
-    if (leftSteps && (rc = checkDevicePointer(e, leftSteps, "cfx_observe_lane_flow_device: left_steps"))) return rc;
-    if (leftWaitingSteps && (rc = checkDevicePointer(e, leftWaitingSteps, "cfx_observe_lane_flow_device: left_waiting_steps"))) return rc;
-    if (waitingSteps && (rc = checkDevicePointer(e, waitingSteps, "cfx_observe_lane_flow_device: waiting_steps"))) return rc;
-    if (maxWaitingSteps && (rc = checkDevicePointer(e, maxWaitingSteps, "cfx_observe_lane_flow_device: max_waiting_steps"))) return rc;
-    if ((rc = laneFlowPrepare(e, "cfx_observe_lane_flow_device"))) return rc;
+    if ((rc = checkDevicePointers(e, "cfx_observe_lane_flow_device",
+                                  {{entered, "entered"}, {left, "left"}, {leftSteps, "left_steps"}, {leftWaitingSteps, "left_waiting_steps"},
+                                   {waitingSteps, "waiting_steps"}, {maxWaitingSteps, "max_waiting_steps"}})))
+        return rc;
+    if ((rc = trackerPrepare(e, kLaneFlow, "cfx_observe_lane_flow_device"))) return rc;
     if ((rc = e->orderAfterCaller((hipStream_t) consumerStream))) return rc;
     launchLaneFlowDrain(e, LaneFlowOut{entered, left, leftSteps, leftWaitingSteps, waitingSteps, maxWaitingSteps}, reset);
     HIP_TRY(hipGetLastError());
@@ -4330,7 +4386,7 @@ int32_t cfx_get_lane_flow(cfx_engine *e, int32_t *entered, int32_t *left, int64_
     auto fail = [e](const std::string &m) { return e->fail(m); };
     HIP_TRY(hipSetDevice(e->device));
     int rc;
-    if ((rc = laneFlowPrepare(e, "cfx_get_lane_flow"))) return rc;
+    if ((rc = trackerPrepare(e, kLaneFlow, "cfx_get_lane_flow"))) return rc;
     // (the records themselves come back, 48 bytes per lane: no device scratch, and the kernel only has to zero)
     std::vector<cfx_lane_flow_lane> lanes((size_t) e->L);
     if (e->L > 0) HIP_TRY(hipMemcpyAsync(lanes.data(), e->flow.lane, lanes.size() * sizeof(cfx_lane_flow_lane), hipMemcpyDeviceToHost, e->stream));
@@ -4355,9 +4411,8 @@ int32_t cfx_lane_flow_get_state(cfx_engine *e, int32_t *records, int32_t nVehicl
     auto fail = [e](const std::string &m) { return e->fail(m); };
     HIP_TRY(hipSetDevice(e->device));
     int rc;
-    if ((rc = laneFlowPrepare(e, "cfx_lane_flow_get_state"))) return rc;
-    if ((size_t) nVehicles > e->vidCap) return e->fail("cfx_lane_flow_get_state: n_vehicles beyond the vehicle tables"), CFX_ERR_INVALID;
-    if (nVehicles) HIP_TRY(hipMemcpyAsync(records, e->flow.rec, (size_t) nVehicles * sizeof(int4), hipMemcpyDeviceToHost, e->stream));
+    if ((rc = trackerPrepare(e, kLaneFlow, "cfx_lane_flow_get_state"))) return rc;
+    if ((rc = recordsOut(e, "cfx_lane_flow_get_state", e->flow.rec, records, nVehicles))) return rc;
     if (e->L > 0) HIP_TRY(hipMemcpyAsync(lanes, e->flow.lane, (size_t) e->L * sizeof(cfx_lane_flow_lane), hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
     *tick = e->flow.tick;
@@ -4368,16 +4423,13 @@ int32_t cfx_lane_flow_set_state(cfx_engine *e, const int32_t *records, int32_t n
     if (!e || !lanes || nVehicles < 0 || (nVehicles > 0 && !records)) return CFX_ERR_INVALID;
     auto fail = [e](const std::string &m) { return e->fail(m); };
     HIP_TRY(hipSetDevice(e->device));
-    if (!e->flowOn) return e->fail("cfx_lane_flow_set_state: lane-flow tracking is off (cfx_lane_flow_enable)"), CFX_ERR_STATE;
-    if ((size_t) nVehicles > e->vidCap) return e->fail("cfx_lane_flow_set_state: n_vehicles beyond the vehicle tables"), CFX_ERR_INVALID;
     int rc;
-    if ((rc = e->settle(false))) return rc;
-    HIP_TRY(hipMemsetAsync(e->flow.rec, 0xFF, std::max<size_t>(e->vidCap, 1) * sizeof(int4), e->stream));
-    if (nVehicles) HIP_TRY(hipMemcpyAsync(e->flow.rec, records, (size_t) nVehicles * sizeof(int4), hipMemcpyHostToDevice, e->stream));
+    if ((rc = trackerRequire(e, kLaneFlow, "cfx_lane_flow_set_state"))) return rc;
+    if ((rc = recordsIn(e, "cfx_lane_flow_set_state", e->flow.rec, records, nVehicles))) return rc;
     if (e->L > 0) HIP_TRY(hipMemcpyAsync(e->flow.lane, lanes, (size_t) e->L * sizeof(cfx_lane_flow_lane), hipMemcpyHostToDevice, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
     e->flow.tick = tick;
-    e->flowBaseline = false;
+    e->tracker[kLaneFlow].baselineDue = false;
     return CFX_OK;
 }
 
@@ -4394,53 +4446,7 @@ static_assert(std::is_same<decltype(&cfx_trip_stats_get_state), cfx_trip_stats_g
 static_assert(std::is_same<decltype(&cfx_trip_stats_set_state), cfx_trip_stats_set_state_fn>::value, "cfx_trip_stats_set_state");
 static_assert(sizeof(cfx_trip_stats_env) == 56, "cfx_trip_stats_env");
 
-// what every reader does first: the step's commit, the rings, a baseline that is due
-static int tripStatsPrepare(cfx_engine *e, const char *what) {
-    if (!e->tripOn) {
-        e->err = std::string(what) + ": trip tracking is off (cfx_trip_stats_enable)";
-        return CFX_ERR_STATE;
-    }
-    int rc;
-    if ((rc = e->settle(false))) return rc;
-    if (e->ring && (rc = e->ringEnsure())) return rc;
-    return e->tripSettle();
-}
-
-int32_t cfx_trip_stats_enable(cfx_engine *e, int32_t on) {
-    if (!e) return CFX_ERR_INVALID;
-    auto fail = [e](const std::string &m) { return e->fail(m); };
-    HIP_TRY(hipSetDevice(e->device));
-    if (!on) {
-        if (!e->tripOn) return CFX_OK;
-        HIP_TRY(hipStreamSynchronize(e->stream));  // (a tick may still be running; a shadow a growth retired stays with `retired`)
-        e->forget(e->trip.seen);
-        e->forget(e->trip.env);
-        HIP_TRY(hipFree(e->trip.seen));
-        HIP_TRY(hipFree(e->trip.env));
-        e->trip = TripDev{};
-        e->tripOn = e->tripBaseline = false;
-        return CFX_OK;
-    }
-    if (e->lc.on || e->tiled) {
-        e->err = "cfx_trip_stats_enable: not with lane change and not on a tile";
-        return CFX_ERR_STATE;
-    }
-    if (e->tripOn) return CFX_OK;
-    const int nEnvs = e->cfg.n_envs > 1 ? e->cfg.n_envs : 1;
-    if (e->R % nEnvs != 0) {
-        e->err = "cfx_trip_stats_enable: n_envs does not divide the number of roads";
-        return CFX_ERR_STATE;
-    }
-    int rc;
-    if ((rc = e->settle(false))) return rc;
-    if (e->ring && (rc = e->ringEnsure())) return rc;
-    if ((rc = e->allocRaw(&e->trip.seen, e->vidCap))) return rc;
-    if ((rc = e->allocRaw(&e->trip.env, (size_t) nEnvs))) return rc;
-    e->trip.nEnvs = nEnvs;
-    e->trip.roadsPerEnv = std::max(e->R / nEnvs, 1);
-    e->tripOn = e->tripBaseline = true;
-    return e->tripSettle();
-}
+int32_t cfx_trip_stats_enable(cfx_engine *e, int32_t on) { return e ? e->trackerEnable(kTrips, on) : CFX_ERR_INVALID; }
 
 static void launchTripDrain(cfx_engine *e, const cfx_trip_stats_out &o) {
     hipLaunchKernelGGL(k_trip_drain, dim3(gridFor((size_t) e->trip.nEnvs)), dim3(kBlock), 0, e->stream, e->trip.env, e->trip.nEnvs,
@@ -4449,21 +4455,22 @@ static void launchTripDrain(cfx_engine *e, const cfx_trip_stats_out &o) {
 
 int32_t cfx_observe_trip_stats_device(cfx_engine *e, const cfx_trip_stats_out *out, void *consumerStream) {
     if (!e || !out) return CFX_ERR_INVALID;
-    const void *ptrs[9] = {out->entered, out->admitted, out->admitted_buffer_steps, out->finished, out->finished_travel_steps,
-                           out->in_system, out->buffered, out->in_system_travel_steps, out->average_travel_time};
-    static const char *const names[9] = {"entered", "admitted", "admitted_buffer_steps", "finished", "finished_travel_steps",
-                                         "in_system", "buffered", "in_system_travel_steps", "average_travel_time"};
-    bool any = false;
-    for (const void *q : ptrs) any = any || q;
-    if (!any) return CFX_ERR_INVALID;
+    const cfx_trip_stats_out &o = *out;
+    if (!o.entered && !o.admitted && !o.admitted_buffer_steps && !o.finished && !o.finished_travel_steps && !o.in_system && !o.buffered &&
+        !o.in_system_travel_steps && !o.average_travel_time)
+        return CFX_ERR_INVALID;
     auto fail = [e](const std::string &m) { return e->fail(m); };
     HIP_TRY(hipSetDevice(e->device));
     int rc;
-    for (int i = 0; i < 9; ++i)
-        if (ptrs[i] && (rc = checkDevicePointer(e, ptrs[i], (std::string("cfx_observe_trip_stats_device: ") + names[i]).c_str()))) return rc;
-    if ((rc = tripStatsPrepare(e, "cfx_observe_trip_stats_device"))) return rc;
+    if ((rc = checkDevicePointers(e, "cfx_observe_trip_stats_device",
+                                  {{o.entered, "entered"}, {o.admitted, "admitted"}, {o.admitted_buffer_steps, "admitted_buffer_steps"},
+                                   {o.finished, "finished"}, {o.finished_travel_steps, "finished_travel_steps"}, {o.in_system, "in_system"},
+                                   {o.buffered, "buffered"}, {o.in_system_travel_steps, "in_system_travel_steps"},
+                                   {o.average_travel_time, "average_travel_time"}})))
+        return rc;
+    if ((rc = trackerPrepare(e, kTrips, "cfx_observe_trip_stats_device"))) return rc;
     if ((rc = e->orderAfterCaller((hipStream_t) consumerStream))) return rc;
-    launchTripDrain(e, *out);
+    launchTripDrain(e, o);
     HIP_TRY(hipGetLastError());
     return e->orderCallerAfter((hipStream_t) consumerStream);
 }
@@ -4474,7 +4481,7 @@ int32_t cfx_get_trip_stats(cfx_engine *e, const cfx_trip_stats_out *out) {
     auto fail = [e](const std::string &m) { return e->fail(m); };
     HIP_TRY(hipSetDevice(e->device));
     int rc;
-    if ((rc = tripStatsPrepare(e, "cfx_get_trip_stats"))) return rc;
+    if ((rc = trackerPrepare(e, kTrips, "cfx_get_trip_stats"))) return rc;
     std::vector<cfx_trip_stats_env> envs((size_t) e->trip.nEnvs);
     HIP_TRY(hipMemcpyAsync(envs.data(), e->trip.env, envs.size() * sizeof(cfx_trip_stats_env), hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
@@ -4503,7 +4510,7 @@ int32_t cfx_trip_stats_get_state(cfx_engine *e, cfx_trip_stats_env *envs, int32_
     auto fail = [e](const std::string &m) { return e->fail(m); };
     HIP_TRY(hipSetDevice(e->device));
     int rc;
-    if ((rc = tripStatsPrepare(e, "cfx_trip_stats_get_state"))) return rc;
+    if ((rc = trackerPrepare(e, kTrips, "cfx_trip_stats_get_state"))) return rc;
     if (nEnvs != e->trip.nEnvs) return e->fail("cfx_trip_stats_get_state: n_envs is not the engine's"), CFX_ERR_INVALID;
     HIP_TRY(hipMemcpyAsync(envs, e->trip.env, (size_t) nEnvs * sizeof(cfx_trip_stats_env), hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
@@ -4515,7 +4522,7 @@ int32_t cfx_trip_stats_set_state(cfx_engine *e, const cfx_trip_stats_env *envs, 
     auto fail = [e](const std::string &m) { return e->fail(m); };
     HIP_TRY(hipSetDevice(e->device));
     int rc;
-    if ((rc = tripStatsPrepare(e, "cfx_trip_stats_set_state"))) return rc;  // (the load's baseline builds the shadow; then the records)
+    if ((rc = trackerPrepare(e, kTrips, "cfx_trip_stats_set_state"))) return rc;  // (the load's baseline builds the shadow; then the records)
     if (nEnvs != e->trip.nEnvs) return e->fail("cfx_trip_stats_set_state: n_envs is not the engine's"), CFX_ERR_INVALID;
     HIP_TRY(hipMemcpyAsync(e->trip.env, envs, (size_t) nEnvs * sizeof(cfx_trip_stats_env), hipMemcpyHostToDevice, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
@@ -4537,47 +4544,7 @@ static_assert(std::is_same<decltype(&cfx_movement_flow_get_state), cfx_movement_
 static_assert(std::is_same<decltype(&cfx_movement_flow_set_state), cfx_movement_flow_set_state_fn>::value, "cfx_movement_flow_set_state");
 static_assert(sizeof(cfx_movement_flow_link) == 64, "cfx_movement_flow_link");
 
-// what every reader does first: the step's commit, the rings, a baseline that is due
-static int moveFlowPrepare(cfx_engine *e, const char *what) {
-    if (!e->moveOn) {
-        e->err = std::string(what) + ": movement-flow tracking is off (cfx_movement_flow_enable)";
-        return CFX_ERR_STATE;
-    }
-    int rc;
-    if ((rc = e->settle(false))) return rc;
-    if (e->ring && (rc = e->ringEnsure())) return rc;
-    return e->moveSettle();
-}
-
-int32_t cfx_movement_flow_enable(cfx_engine *e, int32_t on) {
-    if (!e) return CFX_ERR_INVALID;
-    auto fail = [e](const std::string &m) { return e->fail(m); };
-    HIP_TRY(hipSetDevice(e->device));
-    if (!on) {
-        if (!e->moveOn) return CFX_OK;
-        HIP_TRY(hipStreamSynchronize(e->stream));  // (a tick may still be running; a record array a growth retired stays with `retired`)
-        int rc = e->freeRaw(&e->move.rec) | e->freeRaw(&e->move.link) | e->freeRaw(&e->move.skip) | e->freeRaw(&e->moveOutI) |
-                 e->freeRaw(&e->moveOutL);
-        e->move = MoveFlowDev{};
-        e->moveOn = e->moveBaseline = false;
-        return rc ? CFX_ERR_DEVICE : CFX_OK;
-    }
-    if (e->lc.on || e->tiled) {
-        e->err = "cfx_movement_flow_enable: not with lane change and not on a tile";
-        return CFX_ERR_STATE;
-    }
-    if (e->moveOn) return CFX_OK;
-    int rc;
-    if ((rc = e->settle(false))) return rc;
-    if (e->ring && (rc = e->ringEnsure())) return rc;
-    if ((rc = e->allocRaw(&e->move.rec, e->vidCap))) return rc;
-    if ((rc = e->allocRaw(&e->move.link, (size_t) e->K))) return rc;
-    if ((rc = e->allocRaw(&e->move.skip, (size_t) e->K * 3))) return rc;
-    HIP_TRY(hipMemsetAsync(e->move.rec, 0xFF, std::max<size_t>(e->vidCap, 1) * sizeof(int4), e->stream));
-    e->move.tick = 0;
-    e->moveOn = e->moveBaseline = true;
-    return e->moveSettle();  // (the baseline zeroes link and skip)
-}
+int32_t cfx_movement_flow_enable(cfx_engine *e, int32_t on) { return e ? e->trackerEnable(kMoveFlow, on) : CFX_ERR_INVALID; }
 
 // the descriptor as this library knows it; CFX_ERR_INVALID with a message otherwise
 static int moveFlowArgs(cfx_engine *e, const cfx_movement_flow_out *out, cfx_movement_flow_out *a, const char *what) {
@@ -4620,18 +4587,13 @@ int32_t cfx_observe_movement_flow_device(cfx_engine *e, const cfx_movement_flow_
     if ((rc = moveFlowArgs(e, out, &a, "cfx_observe_movement_flow_device"))) return rc;
     auto fail = [e](const std::string &m) { return e->fail(m); };
     HIP_TRY(hipSetDevice(e->device));
-    const std::pair<const void *, const char *> bufs[] = {
-        {a.entered, "cfx_observe_movement_flow_device: entered"},
-        {a.entered_lane_steps, "cfx_observe_movement_flow_device: entered_lane_steps"},
-        {a.entered_lane_waiting_steps, "cfx_observe_movement_flow_device: entered_lane_waiting_steps"},
-        {a.left, "cfx_observe_movement_flow_device: left"},
-        {a.left_steps, "cfx_observe_movement_flow_device: left_steps"},
-        {a.left_waiting_steps, "cfx_observe_movement_flow_device: left_waiting_steps"},
-        {a.waiting_steps, "cfx_observe_movement_flow_device: waiting_steps"},
-        {a.max_waiting_steps, "cfx_observe_movement_flow_device: max_waiting_steps"}};
-    for (const auto &b : bufs)
-        if (b.first && (rc = checkDevicePointer(e, b.first, b.second))) return rc;
-    if ((rc = moveFlowPrepare(e, "cfx_observe_movement_flow_device"))) return rc;
+    if ((rc = checkDevicePointers(e, "cfx_observe_movement_flow_device",
+                                  {{a.entered, "entered"}, {a.entered_lane_steps, "entered_lane_steps"},
+                                   {a.entered_lane_waiting_steps, "entered_lane_waiting_steps"}, {a.left, "left"}, {a.left_steps, "left_steps"},
+                                   {a.left_waiting_steps, "left_waiting_steps"}, {a.waiting_steps, "waiting_steps"},
+                                   {a.max_waiting_steps, "max_waiting_steps"}})))
+        return rc;
+    if ((rc = trackerPrepare(e, kMoveFlow, "cfx_observe_movement_flow_device"))) return rc;
     if ((rc = moveFlowRows(e, a, "cfx_observe_movement_flow_device"))) return rc;
     if ((rc = e->orderAfterCaller((hipStream_t) consumerStream))) return rc;
     launchMoveFlowDrain(e, MoveFlowOut{a.entered, a.entered_lane_steps, a.entered_lane_waiting_steps, a.left, a.left_steps,
@@ -4646,7 +4608,7 @@ int32_t cfx_get_movement_flow(cfx_engine *e, const cfx_movement_flow_out *out) {
     if ((rc = moveFlowArgs(e, out, &a, "cfx_get_movement_flow"))) return rc;
     auto fail = [e](const std::string &m) { return e->fail(m); };
     HIP_TRY(hipSetDevice(e->device));
-    if ((rc = moveFlowPrepare(e, "cfx_get_movement_flow"))) return rc;
+    if ((rc = trackerPrepare(e, kMoveFlow, "cfx_get_movement_flow"))) return rc;
     if ((rc = moveFlowRows(e, a, "cfx_get_movement_flow"))) return rc;
     const size_t rows = (size_t) e->I * e->interTab.M;
     if (!e->moveOutI && (rc = e->allocRaw(&e->moveOutI, 3 * rows))) return rc;
@@ -4678,10 +4640,9 @@ int32_t cfx_movement_flow_get_state(cfx_engine *e, int32_t *records, int32_t nVe
     auto fail = [e](const std::string &m) { return e->fail(m); };
     HIP_TRY(hipSetDevice(e->device));
     int rc;
-    if ((rc = moveFlowPrepare(e, "cfx_movement_flow_get_state"))) return rc;
-    if ((size_t) nVehicles > e->vidCap) return e->fail("cfx_movement_flow_get_state: n_vehicles beyond the vehicle tables"), CFX_ERR_INVALID;
+    if ((rc = trackerPrepare(e, kMoveFlow, "cfx_movement_flow_get_state"))) return rc;
+    if ((rc = recordsOut(e, "cfx_movement_flow_get_state", e->move.rec, records, nVehicles))) return rc;
     std::vector<unsigned long long> skip((size_t) e->K * 3);
-    if (nVehicles) HIP_TRY(hipMemcpyAsync(records, e->move.rec, (size_t) nVehicles * sizeof(int4), hipMemcpyDeviceToHost, e->stream));
     if (e->K > 0) {
         HIP_TRY(hipMemcpyAsync(links, e->move.link, (size_t) e->K * sizeof(cfx_movement_flow_link), hipMemcpyDeviceToHost, e->stream));
         HIP_TRY(hipMemcpyAsync(skip.data(), e->move.skip, skip.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, e->stream));
@@ -4702,19 +4663,16 @@ int32_t cfx_movement_flow_set_state(cfx_engine *e, const int32_t *records, int32
     if (!e || nVehicles < 0 || (nVehicles > 0 && !records) || (e->K > 0 && !links)) return CFX_ERR_INVALID;
     auto fail = [e](const std::string &m) { return e->fail(m); };
     HIP_TRY(hipSetDevice(e->device));
-    if (!e->moveOn) return e->fail("cfx_movement_flow_set_state: movement-flow tracking is off (cfx_movement_flow_enable)"), CFX_ERR_STATE;
-    if ((size_t) nVehicles > e->vidCap) return e->fail("cfx_movement_flow_set_state: n_vehicles beyond the vehicle tables"), CFX_ERR_INVALID;
     int rc;
-    if ((rc = e->settle(false))) return rc;
-    HIP_TRY(hipMemsetAsync(e->move.rec, 0xFF, std::max<size_t>(e->vidCap, 1) * sizeof(int4), e->stream));
-    if (nVehicles) HIP_TRY(hipMemcpyAsync(e->move.rec, records, (size_t) nVehicles * sizeof(int4), hipMemcpyHostToDevice, e->stream));
+    if ((rc = trackerRequire(e, kMoveFlow, "cfx_movement_flow_set_state"))) return rc;
+    if ((rc = recordsIn(e, "cfx_movement_flow_set_state", e->move.rec, records, nVehicles))) return rc;
     if (e->K > 0) {
         HIP_TRY(hipMemcpyAsync(e->move.link, links, (size_t) e->K * sizeof(cfx_movement_flow_link), hipMemcpyHostToDevice, e->stream));
         HIP_TRY(hipMemsetAsync(e->move.skip, 0, (size_t) e->K * 3 * sizeof(unsigned long long), e->stream));
     }
     HIP_TRY(hipStreamSynchronize(e->stream));
     e->move.tick = tick;
-    e->moveBaseline = false;
+    e->tracker[kMoveFlow].baselineDue = false;
     return CFX_OK;
 }
 

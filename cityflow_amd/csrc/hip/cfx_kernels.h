@@ -2482,6 +2482,44 @@ __device__ __forceinline__ long long featShflXor64(long long v, int off) {
     return (long long) (((unsigned long long) hi << 32) | lo);
 }
 
+// What a group's threads add up over their vehicles of one drivable, and the group's totals of it (in every thread of the
+// group).  `kEntrants`: the two lane sums of a laneLink's entrants too.  By value, as everything here (below).
+struct FlowSums {
+    int entered, inc, mx;
+    long long S, W, ES, EW;
+};
+template <bool kEntrants> __device__ __forceinline__ FlowSums flowGroupSums(FlowSums s) {
+    for (int off = kFeatGroup / 2; off > 0; off >>= 1) {
+        s.entered += __shfl_xor(s.entered, off, kFeatGroup);
+        s.inc += __shfl_xor(s.inc, off, kFeatGroup);
+        s.mx = max(s.mx, __shfl_xor(s.mx, off, kFeatGroup));
+        s.S += featShflXor64(s.S, off);
+        s.W += featShflXor64(s.W, off);
+        if (kEntrants) {
+            s.ES += featShflXor64(s.ES, off);
+            s.EW += featShflXor64(s.EW, off);
+        }
+    }
+    return s;
+}
+
+// The closing update of a lane's or a laneLink's record `a` (cfx_lane_flow_lane, cfx_movement_flow_link) from the totals of the
+// `n` vehicles on it now: who left is the difference of the sums (above); a baseline only takes the sums
+template <typename A> __device__ __forceinline__ A flowClose(A a, const FlowSums s, int n, int step, int baseline) {
+    if (!baseline) {
+        const int left = a.count + s.entered - n;
+        a.entered += s.entered;
+        a.left += left;
+        a.left_steps += (long long) step * left - (a.since_sum + (long long) step * s.entered - s.S);
+        a.left_waiting_steps += a.waiting_steps - (s.W - s.inc);
+    }
+    a.since_sum = s.S;
+    a.waiting_steps = s.W;
+    a.count = n;
+    a.max_waiting_steps = s.mx;
+    return a;
+}
+
 // (`f` by value: taken by reference, the kernel argument is staged in scratch)
 template <typename Rec, typename Vid>
 __device__ __forceinline__ void laneFlowTick(const LaneFlowDev f, int lane, int n, int sub, Rec rec, Vid vidOf) {
@@ -2509,29 +2547,13 @@ __device__ __forceinline__ void laneFlowTick(const LaneFlowDev f, int lane, int 
         W += wait;
         mx = max(mx, wait);
     }
-    for (int off = kFeatGroup / 2; off > 0; off >>= 1) {
-        entered += __shfl_xor(entered, off, kFeatGroup);
-        inc += __shfl_xor(inc, off, kFeatGroup);
-        mx = max(mx, __shfl_xor(mx, off, kFeatGroup));
-        S += featShflXor64(S, off);
-        W += featShflXor64(W, off);
-    }
+    const FlowSums t = flowGroupSums<false>(FlowSums{entered, inc, mx, S, W, 0, 0});
     if (sub != 0) return;
     if (f.baseline) {
         a.left_steps = a.left_waiting_steps = 0;
         a.entered = a.left = 0;
-    } else {
-        const int left = a.count + entered - n;
-        a.entered += entered;
-        a.left += left;
-        a.left_steps += (long long) f.step * left - (a.since_sum + (long long) f.step * entered - S);
-        a.left_waiting_steps += a.waiting_steps - (W - inc);
     }
-    a.since_sum = S;
-    a.waiting_steps = W;
-    a.count = n;
-    a.max_waiting_steps = mx;
-    f.lane[lane] = a;
+    f.lane[lane] = flowClose(a, t, n, f.step, f.baseline);
 }
 
 __global__ void __launch_bounds__(kBlock) kd_lane_flow(StepCtx c, LaneFlowDev f) {
@@ -2638,30 +2660,13 @@ __device__ __forceinline__ void moveFlowTick(const MoveFlowDev f, const MoveFlow
         mx = max(mx, wait);
     }
     if (!isLink) return;
-    for (int off = kFeatGroup / 2; off > 0; off >>= 1) {
-        entered += __shfl_xor(entered, off, kFeatGroup);
-        inc += __shfl_xor(inc, off, kFeatGroup);
-        mx = max(mx, __shfl_xor(mx, off, kFeatGroup));
-        S += featShflXor64(S, off);
-        W += featShflXor64(W, off);
-        ES += featShflXor64(ES, off);
-        EW += featShflXor64(EW, off);
-    }
+    const FlowSums t = flowGroupSums<true>(FlowSums{entered, inc, mx, S, W, ES, EW});
     if (sub != 0) return;
     if (!f.baseline) {  // (a baseline: the accumulators are zero already)
-        const int left = a.count + entered - n;
-        a.entered += entered;
-        a.entered_lane_steps += ES;
-        a.entered_lane_waiting_steps += EW;
-        a.left += left;
-        a.left_steps += (long long) f.step * left - (a.since_sum + (long long) f.step * entered - S);
-        a.left_waiting_steps += a.waiting_steps - (W - inc);
+        a.entered_lane_steps += t.ES;
+        a.entered_lane_waiting_steps += t.EW;
     }
-    a.since_sum = S;
-    a.waiting_steps = W;
-    a.count = n;
-    a.max_waiting_steps = mx;
-    f.link[d - net.L] = a;
+    f.link[d - net.L] = flowClose(a, t, n, f.step, f.baseline);
 }
 
 __global__ void __launch_bounds__(kBlock) kd_movement_flow(StepCtx c, MoveFlowDev f) {

@@ -492,29 +492,14 @@ void EngineHost::compactVehicles() {
         if (newOfOld[(size_t) v] >= 0) state[(size_t) newOfOld[(size_t) v]] = d.vState[(size_t) v];
     d.vState.swap(state);
     a.host = spawner_.compactedState(newOfOld, nLive);
-    // lane-flow statistics: a load takes a baseline, a compaction must not show — the tracker as it stands goes round the load
-    LaneFlowState flow;
-    if (flow_.on()) {
-        flow = flow_.state(nV);
-        flow.renumber(newOfOld, nLive);
-    }
-    MoveFlowState moveFlow;  // movement-flow statistics: likewise
-    if (move_.on()) {
-        moveFlow = move_.state(nV);
-        moveFlow.renumber(newOfOld, nLive);
-    }
-    // trip statistics: the same vehicles are alive before and after, so the environment's record goes round the load as it is
-    std::vector<cfx_trip_stats_env> trips;
-    if (trip_.on()) trips = trip_.state();
+    const Trackers::Carry tracked = trackers_.take(nV, newOfOld, nLive);  // (the load's baseline must not show)
     // custom speeds of vehicles that are STILL waiting (cfx_state carries those of running vehicles only)
     std::map<int32_t, double> stillWaiting;
     for (const auto &kv : waitingCustom_)
         if (kv.first >= 0 && kv.first < nV && newOfOld[(size_t) kv.first] >= 0 && d.vState[(size_t) newOfOld[(size_t) kv.first]] == 0)
             stillWaiting[newOfOld[(size_t) kv.first]] = kv.second;
     load(a);
-    if (flow_.on()) flow_.setState(flow);
-    if (move_.on()) move_.setState(moveFlow);
-    if (trip_.on()) trip_.setState(trips);
+    trackers_.put(tracked);
     for (const auto &kv : stillWaiting) check(be_.cfx_set_vehicle_speed(dev_, kv.first, kv.second), "cfx_set_vehicle_speed");
     waitingCustom_.swap(stillWaiting);
     vehicleCompactions_ += 1;
@@ -587,11 +572,7 @@ void EngineHost::load(const Archive &a) {
         check(be_.cfx_set_lane_history(dev_, &h), "cfx_set_lane_history");
     }
     step_ = (size_t) d.step;
-    flow_.baseline((int64_t) step_);
-    move_.baseline((int64_t) step_);
-    trip_.forget();
-    tripNoteVehicles();
-    trip_.baseline((int64_t) step_);
+    trackers_.rebaseline((int64_t) step_, [this] { tripNoteVehicles(); });
     waitingCustom_.clear();  // (compactVehicles puts back what it carries over)
     vehicleEpoch_ += 1;  // vehicle numbers of the archive replace the current ones
     // An archive taken earlier holds fewer vehicle numbers than the state it replaces: the next compaction is due that many
@@ -674,11 +655,7 @@ void EngineHost::rollback(DeviceCheckpoint &ck) {
     check(be_.cfx_checkpoint_restore(dev_, ck.ck), "cfx_checkpoint_restore");
     forgetPhases();  // (the lights now show the checkpoint's phases)
     step_ = ck.step;
-    flow_.baseline((int64_t) step_);
-    move_.baseline((int64_t) step_);
-    trip_.forget();
-    tripNoteVehicles();
-    trip_.baseline((int64_t) step_);
+    trackers_.rebaseline((int64_t) step_, [this] { tripNoteVehicles(); });
     waitingCustom_ = ck.waitingCustom;
     vehicleEpoch_ += 1;  // vehicle numbers of the checkpoint replace the current ones (a compaction may lie in between)
     const size_t held = spawner_.vehicles.size();

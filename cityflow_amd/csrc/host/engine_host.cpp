@@ -270,9 +270,7 @@ EngineHost::EngineHost(const std::string &configFile, int threadNum, const std::
         return st == 2;
     });
     uploadNewTablesIfAny();
-    flow_.bind(&be_, dev_, (int) net_->lanes.size());
-    move_.bind(&be_, dev_, &net_->flat(), 1);
-    trip_.bind(&be_, dev_, 1, interval_);
+    trackers_.bind(&be_, dev_, &net_->flat(), 1, interval_);
     plan_.bind(&be_, dev_, net_.get(), 1, false);
 }
 
@@ -412,10 +410,8 @@ void EngineHost::nextStep() {
         }
     } note{this, lap, step_};
     step_ += 1;
-    flow_.afterStep((int64_t) step_);  // (the host tracker's tick; a backend that keeps the tracker has ticked inside cfx_step)
-    move_.afterStep((int64_t) step_);
     tripNoteVehicles();
-    trip_.afterStep((int64_t) step_);  // (likewise)
+    trackers_.afterStep((int64_t) step_);
     // The finished vehicles are forgotten once enough have been created since the last time (archive.cpp compactVehicles): the
     // reference frees a vehicle when it finishes; here host and device remember every vehicle number until then.
     // What it costs is proportional to the vehicles ALIVE (a snapshot and a load: ~0.15-0.3 us per vehicle), so the automatic
@@ -634,10 +630,10 @@ void EngineHost::observeLanesDevice(const cfx_lane_obs &obs, uintptr_t consumerS
 }
 
 void EngineHost::laneFronts(int k, const LaneFronts &out) {
-    if ((out.laneSteps || out.waitingSteps) && !flow_.on())
+    if ((out.laneSteps || out.waitingSteps) && !trackers_.flow.on())
         throw std::runtime_error("lane fronts: lane_steps / waiting_steps need lane-flow tracking (track_lane_flow(True) turns it on)");
     if (out.distance || out.speed) laneFrontsOf(be_, dev_, (int) net_->lanes.size(), k, out.distance, out.speed);
-    if (out.laneSteps || out.waitingSteps) flow_.fronts(k, out.laneSteps, out.waitingSteps);
+    if (out.laneSteps || out.waitingSteps) trackers_.flow.fronts(k, out.laneSteps, out.waitingSteps);
     raiseDeviceError();
 }
 
@@ -904,63 +900,55 @@ void intersectionFeaturesOf(const Backend &be, cfx_engine *dev, const InterLayou
 
 void EngineHost::trackLaneFlow(bool on) {
     if (on && laneChange_) throw std::logic_error("track_lane_flow: not with laneChange (a shadow changes identity when its change finishes)");
-    flow_.enable(on, (int64_t) step_);
+    trackers_.flow.enable(on, (int64_t) step_);
 }
 
 // (like the count getters, these leave the step prepared ahead in place)
 void EngineHost::laneFlowFeatures(const LaneFlowOut &out, bool reset) {
-    flow_.features(out, reset);
+    trackers_.flow.features(out, reset);
     raiseDeviceError();
 }
 
-void EngineHost::observeLaneFlowDevice(uintptr_t entered, uintptr_t left, uintptr_t leftSteps, uintptr_t leftWaitingSteps,
-                                       uintptr_t waitingSteps, uintptr_t maxWaitingSteps, bool reset, uintptr_t consumerStream) {
-    LaneFlowOut o;
-    o.entered = (int32_t *) entered;
-    o.left = (int32_t *) left;
-    o.leftSteps = (int64_t *) leftSteps;
-    o.leftWaitingSteps = (int64_t *) leftWaitingSteps;
-    o.waitingSteps = (int64_t *) waitingSteps;
-    o.maxWaitingSteps = (int32_t *) maxWaitingSteps;
-    flow_.observeDevice(o, reset, consumerStream);
+void EngineHost::observeLaneFlowDevice(const LaneFlowOut &out, bool reset, uintptr_t consumerStream) {
+    trackers_.flow.observeDevice(out, reset, consumerStream);
 }
 
 void EngineHost::trackMovementFlow(bool on) {
     if (on && laneChange_) throw std::logic_error("track_movement_flow: not with laneChange (a shadow changes identity when its change finishes)");
-    move_.enable(on, (int64_t) step_);
+    trackers_.move.enable(on, (int64_t) step_);
 }
 
 // (like the count getters, these leave the step prepared ahead in place)
 void EngineHost::movementFlowFeatures(const MoveFlowOut &out, bool reset) {
-    move_.features(out, reset);
+    trackers_.move.features(out, reset);
     raiseDeviceError();
 }
 
 void EngineHost::observeMovementFlowDevice(const MoveFlowOut &out, bool reset, uintptr_t consumerStream) {
-    move_.observeDevice(out, reset, consumerStream);
+    trackers_.move.observeDevice(out, reset, consumerStream);
 }
 
 void EngineHost::trackTrips(bool on) {
     if (on && laneChange_) throw std::logic_error("track_trips: not with laneChange (a shadow is a vehicle number with its parent's enter time)");
-    if (on == trip_.on()) return;
-    trip_.enable(on);
+    if (on == trackers_.trip.on()) return;
+    trackers_.trip.enable(on);
     tripNoteVehicles();
-    trip_.baseline((int64_t) step_);
+    trackers_.trip.baseline((int64_t) step_);
 }
 
 void EngineHost::tripNoteVehicles() {
-    if (!trip_.on() || trip_.onDevice()) return;
+    if (!trackers_.trip.onHost()) return;
     const size_t n = spawner_.committedVehicleCount();
-    for (size_t v = (size_t) trip_.noted(); v < n; ++v) trip_.note((int32_t) v, spawner_.vehicles[v].enterTime, 0);
+    for (size_t v = (size_t) trackers_.trip.noted(); v < n; ++v) trackers_.trip.note((int32_t) v, spawner_.vehicles[v].enterTime, 0);
 }
 
 // (like the count getters, these leave the step prepared ahead in place)
 void EngineHost::tripFeatures(const cfx_trip_stats_out &out) {
-    trip_.features(out);
+    trackers_.trip.features(out);
     raiseDeviceError();
 }
 
-void EngineHost::observeTripsDevice(const cfx_trip_stats_out &out, uintptr_t consumerStream) { trip_.observeDevice(out, consumerStream); }
+void EngineHost::observeTripsDevice(const cfx_trip_stats_out &out, uintptr_t consumerStream) { trackers_.trip.observeDevice(out, consumerStream); }
 
 const InterLayout &EngineHost::intersectionLayout() {
     if (!interLayout_) interLayout_.reset(new InterLayout(intersectionLayoutOf(*net_)));
@@ -1052,10 +1040,7 @@ void EngineHost::reset(bool resetRnd) {
     nextCompactAt_ = compactAt_;
     step_ = 0;
     vehicleEpoch_ += 1;
-    flow_.baseline(0);
-    move_.baseline(0);
-    trip_.forget();
-    trip_.baseline(0);
+    trackers_.rebaseline(0, [] {});
 }
 
 // ---------------------------------------------------------------- getters

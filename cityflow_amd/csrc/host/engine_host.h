@@ -15,9 +15,7 @@
 #include "archive.h"
 #include "cityflow_amd.h"
 #include "flow.h"
-#include "lane_flow.h"
-#include "movement_flow.h"
-#include "trip_stats.h"
+#include "trackers.h"
 #include "replay.h"
 #include "roadnet.h"
 
@@ -339,19 +337,18 @@ public:
     // ---- per-movement flow and delay statistics across steps (movement_flow.h; the torch layer is cityflow_amd/torch_io.py):
     //      outputs [I * M], any pointer may be null
     void trackMovementFlow(bool on);
-    bool movementFlowTracking() const { return move_.on(); }
-    int movementFlowRows() const { return (int) move_.rows(); }
+    bool movementFlowTracking() const { return trackers_.move.on(); }
+    int movementFlowRows() const { return (int) trackers_.move.rows(); }
     void movementFlowFeatures(const MoveFlowOut &out, bool reset);
     void observeMovementFlowDevice(const MoveFlowOut &out, bool reset, uintptr_t consumerStream);
     void trackLaneFlow(bool on);
-    bool laneFlowTracking() const { return flow_.on(); }
+    bool laneFlowTracking() const { return trackers_.flow.on(); }
     void laneFlowFeatures(const LaneFlowOut &out, bool reset);  // any pointer may be null
-    void observeLaneFlowDevice(uintptr_t entered, uintptr_t left, uintptr_t leftSteps, uintptr_t leftWaitingSteps,
-                               uintptr_t waitingSteps, uintptr_t maxWaitingSteps, bool reset, uintptr_t consumerStream);
+    void observeLaneFlowDevice(const LaneFlowOut &out, bool reset, uintptr_t consumerStream);
     // ---- trip statistics and the average travel time across steps (trip_stats.h; the torch layer is cityflow_amd/torch_io.py).
     //      Off by default; a baseline when it is turned on and after reset / load; vehicle compaction carries it along
     void trackTrips(bool on);
-    bool tripTracking() const { return trip_.on(); }
+    bool tripTracking() const { return trackers_.trip.on(); }
     void tripFeatures(const cfx_trip_stats_out &out);  // any pointer may be null; one element each
     void observeTripsDevice(const cfx_trip_stats_out &out, uintptr_t consumerStream);
     // Lane::history as the device keeps it ("cfx": {"laneHistory": true}; cfx_get_lane_history): lane-major, oldest record first
@@ -462,9 +459,7 @@ private:
     std::vector<int32_t> laneIdOrder_;
     uint64_t vehicleEpoch_ = 0;
     std::unique_ptr<InterLayout> interLayout_;  // built by the first call that needs it
-    LaneFlow flow_;
-    MoveFlow move_;
-    TripStats trip_;
+    Trackers trackers_;
     void tripNoteVehicles();  // (host tracker: the vehicle numbers created since the last call)
 };
 

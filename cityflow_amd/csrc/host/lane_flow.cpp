@@ -9,39 +9,17 @@
 
 namespace cfa {
 
-void LaneFlowState::renumber(const std::vector<int32_t> &newOfOld, int nLive) {
-    std::vector<int32_t> moved((size_t) nLive * 4, -1);
-    for (size_t v = 0; v < newOfOld.size() && 4 * v + 3 < records.size(); ++v)
-        if (newOfOld[v] >= 0 && newOfOld[v] < nLive) std::copy(records.begin() + 4 * v, records.begin() + 4 * v + 4, moved.begin() + 4 * (size_t) newOfOld[v]);
-    records.swap(moved);
-}
-
-bool LaneFlow::onDevice() const {
-    return be_->cfx_lane_flow_enable && be_->cfx_observe_lane_flow_device && be_->cfx_get_lane_flow && be_->cfx_lane_flow_get_state &&
-           be_->cfx_lane_flow_set_state;
-}
-
-void LaneFlow::fail(const char *what) const {
-    const char *msg = be_->cfx_last_error(dev_);
-    throw std::runtime_error(std::string("cityflow_amd: ") + what + " failed: " + (msg ? msg : ""));
-}
-
-void LaneFlow::requireOn(const char *what) const {
-    if (!on_) throw std::runtime_error(std::string(what) + ": lane-flow tracking is off (track_lane_flow(True) turns it on)");
+void LaneFlow::bind(const Backend *be, cfx_engine *dev, int nLanes) {
+    bindBackend(be, dev, "cfx_lane_flow_enable", be->cfx_lane_flow_enable, be->cfx_observe_lane_flow_device, be->cfx_get_lane_flow,
+                be->cfx_lane_flow_get_state, be->cfx_lane_flow_set_state);
+    nLanes_ = nLanes;
 }
 
 void LaneFlow::enable(bool on, int64_t step) {
-    if (on == on_) return;
-    if (onDevice()) {
-        if (be_->cfx_lane_flow_enable(dev_, on ? 1 : 0) != CFX_OK) fail("cfx_lane_flow_enable");
-        on_ = on;
-        return;
-    }
-    on_ = on;
+    if (!switchTo(on)) return;
     host_ = LaneFlowState{};
     if (!on) {
-        for (std::vector<int32_t> *v : {&vid_, &drv_, &n_, &entered_, &inc_, &max_}) std::vector<int32_t>().swap(*v);
-        std::vector<double>().swap(speed_);
+        for (std::vector<int32_t> *v : {&n_, &entered_, &inc_, &max_}) std::vector<int32_t>().swap(*v);
         std::vector<int64_t>().swap(since_);
         std::vector<int64_t>().swap(wait_);
         return;
@@ -50,36 +28,9 @@ void LaneFlow::enable(bool on, int64_t step) {
     walk(step, true);
 }
 
-void LaneFlow::afterStep(int64_t step) {
-    if (on_ && !onDevice()) walk(step, false);
-}
-
-void LaneFlow::baseline(int64_t step) {
-    if (on_ && !onDevice()) walk(step, true);
-}
-
 // one tick (or baseline) of the host tracker: the rules of include/cityflow_amd.h over the running vehicles as the backend lists them
 void LaneFlow::walk(int64_t step, bool baseline) {
-    cfx_scalars sc{};
-    if (be_->cfx_get_scalars(dev_, &sc) != CFX_OK) fail("cfx_get_scalars");
-    cfx_vehicle_view v{};
-    for (int cap = (int) sc.active_vehicle_count + 16;;) {
-        vid_.resize((size_t) cap);
-        drv_.resize((size_t) cap);
-        speed_.resize((size_t) cap);
-        v = cfx_vehicle_view{};
-        v.capacity = cap;
-        v.vid = vid_.data();
-        v.drivable = drv_.data();
-        v.speed = speed_.data();
-        const int32_t rc = be_->cfx_get_vehicles(dev_, &v);
-        if (rc == CFX_ERR_CAPACITY && v.count > cap) {
-            cap = v.count + 16;
-            continue;
-        }
-        if (rc != CFX_OK) fail("cfx_get_vehicles");
-        break;
-    }
+    const VehicleColumns v = vehicleColumnsOf(*be_, dev_, true, false, true);
     const size_t L = (size_t) nLanes_;
     n_.assign(L, 0);
     entered_.assign(L, 0);
@@ -90,10 +41,9 @@ void LaneFlow::walk(int64_t step, bool baseline) {
     const int32_t tick = ++host_.tick, s = (int32_t) step;
     hostStep_ = s;
     for (int i = 0; i < v.count; ++i) {
-        const int32_t l = drv_[(size_t) i], id = vid_[(size_t) i];
+        const int32_t l = v.drivable[(size_t) i], id = v.vid[(size_t) i];
         if (l < 0 || l >= nLanes_ || id < 0) continue;  // (on a laneLink: on no lane)
-        if (4 * (size_t) id + 3 >= host_.records.size()) host_.records.resize(std::max(4 * (size_t) id + 4, 2 * host_.records.size()), -1);
-        int32_t *r = &host_.records[4 * (size_t) id];
+        int32_t *r = host_.of(id);
         if (baseline || r[0] != l || r[1] != tick - 1) {
             r[2] = s;
             r[3] = 0;
@@ -101,7 +51,7 @@ void LaneFlow::walk(int64_t step, bool baseline) {
         }
         r[0] = l;
         r[1] = tick;
-        if (!baseline && speed_[(size_t) i] < 0.1) {
+        if (!baseline && v.speed[(size_t) i] < 0.1) {
             r[3] += 1;
             inc_[(size_t) l] += 1;
         }
@@ -115,17 +65,8 @@ void LaneFlow::walk(int64_t step, bool baseline) {
         if (baseline) {
             a.left_steps = a.left_waiting_steps = 0;
             a.entered = a.left = 0;
-        } else {  // who left is the difference of the lane's sums (include/cityflow_amd.h; laneFlowTick of the HIP library)
-            const int32_t left = a.count + entered_[l] - n_[l];
-            a.entered += entered_[l];
-            a.left += left;
-            a.left_steps += (int64_t) s * left - (a.since_sum + (int64_t) s * entered_[l] - since_[l]);
-            a.left_waiting_steps += a.waiting_steps - (wait_[l] - inc_[l]);
         }
-        a.since_sum = since_[l];
-        a.waiting_steps = wait_[l];
-        a.count = n_[l];
-        a.max_waiting_steps = max_[l];
+        closeFlowRecord(a, baseline, s, n_[l], entered_[l], inc_[l], since_[l], wait_[l], max_[l]);
     }
 }
 
@@ -154,7 +95,7 @@ void LaneFlow::features(const LaneFlowOut &o, bool reset) {
 
 void LaneFlow::observeDevice(const LaneFlowOut &o, bool reset, uintptr_t consumerStream) {
     requireOn("observe_lane_flow_tensor");
-    if (!onDevice()) throw std::runtime_error("cityflow_amd: '" + be_->path + "' has no device-side lane-flow statistics");
+    requireDevice("lane-flow statistics");
     if (be_->cfx_observe_lane_flow_device(dev_, o.entered, o.left, o.leftSteps, o.leftWaitingSteps, o.waitingSteps, o.maxWaitingSteps,
                                           reset ? 1 : 0, (void *) consumerStream) != CFX_OK)
         fail("cfx_observe_lane_flow_device");

@@ -9,16 +9,9 @@
 
 namespace cfa {
 
-void MoveFlowState::renumber(const std::vector<int32_t> &newOfOld, int nLive) {
-    std::vector<int32_t> moved((size_t) nLive * 4, -1);
-    for (size_t v = 0; v < newOfOld.size() && 4 * v + 3 < records.size(); ++v)
-        if (newOfOld[v] >= 0 && newOfOld[v] < nLive) std::copy(records.begin() + 4 * v, records.begin() + 4 * v + 4, moved.begin() + 4 * (size_t) newOfOld[v]);
-    records.swap(moved);
-}
-
 void MoveFlow::bind(const Backend *be, cfx_engine *dev, const cfx_net *net, int nEnvs) {
-    be_ = be;
-    dev_ = dev;
+    bindBackend(be, dev, "cfx_movement_flow_enable", be->cfx_movement_flow_enable, be->cfx_observe_movement_flow_device,
+                be->cfx_get_movement_flow, be->cfx_movement_flow_get_state, be->cfx_movement_flow_set_state);
     net_ = net;
     R_ = nEnvs;
     L_ = net->n_lanes;
@@ -28,28 +21,8 @@ void MoveFlow::bind(const Backend *be, cfx_engine *dev, const cfx_net *net, int 
     for (int i = 0; i < I_; ++i) M_ = std::max(M_, (int) net->inter_n_roadlinks[i]);
 }
 
-bool MoveFlow::onDevice() const {
-    return be_->cfx_movement_flow_enable && be_->cfx_observe_movement_flow_device && be_->cfx_get_movement_flow &&
-           be_->cfx_movement_flow_get_state && be_->cfx_movement_flow_set_state;
-}
-
-void MoveFlow::fail(const char *what) const {
-    const char *msg = be_->cfx_last_error(dev_);
-    throw std::runtime_error(std::string("cityflow_amd: ") + what + " failed: " + (msg ? msg : ""));
-}
-
-void MoveFlow::requireOn(const char *what) const {
-    if (!on_) throw std::runtime_error(std::string(what) + ": movement-flow tracking is off (track_movement_flow(True) turns it on)");
-}
-
 void MoveFlow::enable(bool on, int64_t step) {
-    if (on == on_) return;
-    if (onDevice()) {
-        if (be_->cfx_movement_flow_enable(dev_, on ? 1 : 0) != CFX_OK) fail("cfx_movement_flow_enable");
-        on_ = on;
-        return;
-    }
-    on_ = on;
+    if (!switchTo(on)) return;
     host_ = MoveFlowState{};
     if (!on) {
         for (std::vector<int32_t> *v : {&n_, &entered_, &inc_, &max_}) std::vector<int32_t>().swap(*v);
@@ -61,16 +34,8 @@ void MoveFlow::enable(bool on, int64_t step) {
     walk(step, true);
 }
 
-void MoveFlow::afterStep(int64_t step) {
-    if (on_ && !onDevice()) walk(step, false);
-}
-
-void MoveFlow::baseline(int64_t step) {
-    if (on_ && !onDevice()) walk(step, true);
-}
-
 // one tick (or baseline) of the host tracker: the rules of include/cityflow_amd.h over the running vehicles as the backend lists
-// them; the laneLink records in the difference form of moveFlowTick of the HIP library
+// them; the laneLink records in the difference form
 void MoveFlow::walk(int64_t step, bool baseline) {
     const VehicleColumns v = vehicleColumnsOf(*be_, dev_, true, false, true);
     const int Lt = R_ * L_, Kt = R_ * K_;
@@ -86,8 +51,7 @@ void MoveFlow::walk(int64_t step, bool baseline) {
     for (int i = 0; i < v.count; ++i) {
         const int32_t d = v.drivable[(size_t) i], id = v.vid[(size_t) i];
         if (d < 0 || d >= Lt + Kt || id < 0) continue;
-        if (4 * (size_t) id + 3 >= host_.records.size()) host_.records.resize(std::max(4 * (size_t) id + 4, 2 * host_.records.size()), -1);
-        int32_t *r = &host_.records[4 * (size_t) id];
+        int32_t *r = host_.of(id);
         if (baseline) {
             r[2] = s;
             r[3] = 0;
@@ -129,20 +93,7 @@ void MoveFlow::walk(int64_t step, bool baseline) {
         wait_[k] += r[3];
         max_[k] = std::max(max_[k], r[3]);
     }
-    for (size_t k = 0; k < nK; ++k) {
-        cfx_movement_flow_link &a = host_.links[k];
-        if (!baseline) {  // who left is the difference of the laneLink's sums
-            const int32_t left = a.count + entered_[k] - n_[k];
-            a.entered += entered_[k];
-            a.left += left;
-            a.left_steps += (int64_t) s * left - (a.since_sum + (int64_t) s * entered_[k] - since_[k]);
-            a.left_waiting_steps += a.waiting_steps - (wait_[k] - inc_[k]);
-        }
-        a.since_sum = since_[k];
-        a.waiting_steps = wait_[k];
-        a.count = n_[k];
-        a.max_waiting_steps = max_[k];
-    }
+    for (size_t k = 0; k < nK; ++k) closeFlowRecord(host_.links[k], baseline, s, n_[k], entered_[k], inc_[k], since_[k], wait_[k], max_[k]);
 }
 
 cfx_movement_flow_out MoveFlow::descriptor(const MoveFlowOut &o, bool reset) const {
@@ -204,7 +155,7 @@ void MoveFlow::features(const MoveFlowOut &o, bool reset) {
 
 void MoveFlow::observeDevice(const MoveFlowOut &o, bool reset, uintptr_t consumerStream) {
     requireOn("observe_movement_flow_tensor");
-    if (!onDevice()) throw std::runtime_error("cityflow_amd: '" + be_->path + "' has no device-side movement-flow statistics");
+    requireDevice("movement-flow statistics");
     const cfx_movement_flow_out a = descriptor(o, reset);
     if (be_->cfx_observe_movement_flow_device(dev_, &a, (void *) consumerStream) != CFX_OK) fail("cfx_observe_movement_flow_device");
 }

@@ -309,37 +309,42 @@ template <typename E> py::dict intersectionLayoutDict(E &e) {
 // ---- per-lane flow statistics across steps (Engine and VectorEngine; the public calls are cityflow_amd/torch_io.py)
 inline py::ssize_t laneFlowLanes(EngineHost &e) { return (py::ssize_t) e.net().lanes.size(); }
 inline py::ssize_t laneFlowLanes(cfa::VectorEngineHost &e) { return (py::ssize_t) e.numEnvs() * e.numLanes(); }
+// one output of a tracker's array call: a fresh array of n elements, and the descriptor's pointer to its data
+template <typename T> py::array_t<T> column(T *&slot, py::ssize_t n) {
+    py::array_t<T> a(n);
+    slot = a.mutable_data();
+    return a;
+}
 template <typename E> py::tuple laneFlowTuple(E &e, bool reset) {
     const py::ssize_t n = laneFlowLanes(e);
-    py::array_t<int32_t> entered(n), left(n), maxWait(n);
-    py::array_t<int64_t> leftSteps(n), leftWait(n), waitNow(n);
     cfa::LaneFlowOut o;
-    o.entered = entered.mutable_data();
-    o.left = left.mutable_data();
-    o.leftSteps = leftSteps.mutable_data();
-    o.leftWaitingSteps = leftWait.mutable_data();
-    o.waitingSteps = waitNow.mutable_data();
-    o.maxWaitingSteps = maxWait.mutable_data();
+    py::tuple t = py::make_tuple(column(o.entered, n), column(o.left, n), column(o.leftSteps, n), column(o.leftWaitingSteps, n),
+                                 column(o.waitingSteps, n), column(o.maxWaitingSteps, n));
     e.laneFlowFeatures(o, reset);
-    return py::make_tuple(entered, left, leftSteps, leftWait, waitNow, maxWait);
+    return t;
+}
+template <typename E>
+void observeLaneFlowDevice(E &e, uintptr_t entered, uintptr_t left, uintptr_t leftSteps, uintptr_t leftWait, uintptr_t waitNow,
+                           uintptr_t maxWait, bool reset, uintptr_t consumerStream) {
+    cfa::LaneFlowOut o;
+    o.entered = (int32_t *) entered;
+    o.left = (int32_t *) left;
+    o.leftSteps = (int64_t *) leftSteps;
+    o.leftWaitingSteps = (int64_t *) leftWait;
+    o.waitingSteps = (int64_t *) waitNow;
+    o.maxWaitingSteps = (int32_t *) maxWait;
+    e.observeLaneFlowDevice(o, reset, consumerStream);
 }
 
 // ---- per-movement flow statistics across steps (Engine and VectorEngine; the public calls are cityflow_amd/torch_io.py)
 template <typename E> py::tuple movementFlowTuple(E &e, bool reset) {
     const py::ssize_t n = (py::ssize_t) e.movementFlowRows();
-    py::array_t<int32_t> entered(n), left(n), maxWait(n);
-    py::array_t<int64_t> laneSteps(n), laneWait(n), leftSteps(n), leftWait(n), waitNow(n);
     cfa::MoveFlowOut o;
-    o.entered = entered.mutable_data();
-    o.enteredLaneSteps = laneSteps.mutable_data();
-    o.enteredLaneWaitingSteps = laneWait.mutable_data();
-    o.left = left.mutable_data();
-    o.leftSteps = leftSteps.mutable_data();
-    o.leftWaitingSteps = leftWait.mutable_data();
-    o.waitingSteps = waitNow.mutable_data();
-    o.maxWaitingSteps = maxWait.mutable_data();
+    py::tuple t = py::make_tuple(column(o.entered, n), column(o.enteredLaneSteps, n), column(o.enteredLaneWaitingSteps, n), column(o.left, n),
+                                 column(o.leftSteps, n), column(o.leftWaitingSteps, n), column(o.waitingSteps, n),
+                                 column(o.maxWaitingSteps, n));
     e.movementFlowFeatures(o, reset);
-    return py::make_tuple(entered, laneSteps, laneWait, left, leftSteps, leftWait, waitNow, maxWait);
+    return t;
 }
 template <typename E>
 void observeMovementFlowDevice(E &e, uintptr_t entered, uintptr_t laneSteps, uintptr_t laneWait, uintptr_t left, uintptr_t leftSteps,
@@ -400,21 +405,12 @@ inline py::ssize_t tripEnvs(EngineHost &) { return 1; }
 inline py::ssize_t tripEnvs(cfa::VectorEngineHost &e) { return (py::ssize_t) e.numEnvs(); }
 template <typename E> py::tuple tripTuple(E &e) {
     const py::ssize_t n = tripEnvs(e);
-    py::array_t<int32_t> entered(n), admitted(n), finished(n), inSystem(n), buffered(n);
-    py::array_t<int64_t> bufferSteps(n), travelSteps(n), inSteps(n);
-    py::array_t<double> average(n);
     cfx_trip_stats_out o{};
-    o.entered = entered.mutable_data();
-    o.admitted = admitted.mutable_data();
-    o.admitted_buffer_steps = bufferSteps.mutable_data();
-    o.finished = finished.mutable_data();
-    o.finished_travel_steps = travelSteps.mutable_data();
-    o.in_system = inSystem.mutable_data();
-    o.buffered = buffered.mutable_data();
-    o.in_system_travel_steps = inSteps.mutable_data();
-    o.average_travel_time = average.mutable_data();
+    py::tuple t = py::make_tuple(column(o.entered, n), column(o.admitted, n), column(o.admitted_buffer_steps, n), column(o.finished, n),
+                                 column(o.finished_travel_steps, n), column(o.in_system, n), column(o.buffered, n),
+                                 column(o.in_system_travel_steps, n), column(o.average_travel_time, n));
     e.tripFeatures(o);
-    return py::make_tuple(entered, admitted, bufferSteps, finished, travelSteps, inSystem, buffered, inSteps, average);
+    return t;
 }
 template <typename E>
 void observeTripsDevice(E &e, uintptr_t entered, uintptr_t admitted, uintptr_t bufferSteps, uintptr_t finished, uintptr_t travelSteps,
@@ -465,6 +461,16 @@ template <typename E> py::array_t<double> tlPhaseDurationsArray(E &e) {
     return out;
 }
 
+// track_lane_flow / track_movement_flow / track_trips: lane change is out of scope (logic_error), not a failure of the call
+template <typename E, void (E::*Track)(bool)> void trackOrNotImplemented(E &e, bool on) {
+    try {
+        (e.*Track)(on);
+    } catch (const std::logic_error &x) {
+        PyErr_SetString(PyExc_NotImplementedError, x.what());
+        throw py::error_already_set();
+    }
+}
+
 // Device buffers: raw pointers and streams under the tensor methods of cityflow_amd/torch_io.py (Engine and VectorEngine alike)
 template <typename E> void defDeviceBuffers(py::class_<E> &c) {
     c.def("_device_buffers", &E::deviceBuffers, "the backend takes observations / signals in device memory")
@@ -496,31 +502,13 @@ template <typename E> void defDeviceBuffers(py::class_<E> &c) {
         .def("_intersection_layout", [](E &e) { return intersectionLayoutDict(e); })
         .def("_observe_intersections_device", &E::observeIntersectionsDevice, "phase_ptr"_a, "remain_ptr"_a, "in_ptr"_a,
              "in_waiting_ptr"_a, "out_ptr"_a, "inside_ptr"_a, "pressure_ptr"_a, "max_roadlinks"_a, "max_phases"_a, "consumer_stream"_a)
-        .def("_track_lane_flow",
-             [](E &e, bool on) {
-                 try {
-                     e.trackLaneFlow(on);
-                 } catch (const std::logic_error &x) {  // (lane change: out of scope, not a failure of the call)
-                     PyErr_SetString(PyExc_NotImplementedError, x.what());
-                     throw py::error_already_set();
-                 }
-             },
-             "on"_a)
+        .def("_track_lane_flow", &trackOrNotImplemented<E, &E::trackLaneFlow>, "on"_a)
         .def("_lane_flow_tracking", &E::laneFlowTracking)
         .def("_lane_flow_features", [](E &e, bool reset) { return laneFlowTuple(e, reset); }, "reset"_a,
              "(entered, left, left_steps, left_waiting_steps, waiting_steps, max_waiting_steps), flat (env-major)")
-        .def("_observe_lane_flow_device", &E::observeLaneFlowDevice, "entered_ptr"_a, "left_ptr"_a, "left_steps_ptr"_a,
+        .def("_observe_lane_flow_device", &observeLaneFlowDevice<E>, "entered_ptr"_a, "left_ptr"_a, "left_steps_ptr"_a,
              "left_waiting_steps_ptr"_a, "waiting_steps_ptr"_a, "max_waiting_steps_ptr"_a, "reset"_a, "consumer_stream"_a)
-        .def("_track_movement_flow",
-             [](E &e, bool on) {
-                 try {
-                     e.trackMovementFlow(on);
-                 } catch (const std::logic_error &x) {  // (lane change: out of scope, not a failure of the call)
-                     PyErr_SetString(PyExc_NotImplementedError, x.what());
-                     throw py::error_already_set();
-                 }
-             },
-             "on"_a)
+        .def("_track_movement_flow", &trackOrNotImplemented<E, &E::trackMovementFlow>, "on"_a)
         .def("_movement_flow_tracking", &E::movementFlowTracking)
         .def("_movement_flow_features", [](E &e, bool reset) { return movementFlowTuple(e, reset); }, "reset"_a,
              "(entered, entered_lane_steps, entered_lane_waiting_steps, left, left_steps, left_waiting_steps, waiting_steps, "
@@ -528,16 +516,7 @@ template <typename E> void defDeviceBuffers(py::class_<E> &c) {
         .def("_observe_movement_flow_device", &observeMovementFlowDevice<E>, "entered_ptr"_a, "entered_lane_steps_ptr"_a,
              "entered_lane_waiting_steps_ptr"_a, "left_ptr"_a, "left_steps_ptr"_a, "left_waiting_steps_ptr"_a, "waiting_steps_ptr"_a,
              "max_waiting_steps_ptr"_a, "reset"_a, "consumer_stream"_a)
-        .def("_track_trips",
-             [](E &e, bool on) {
-                 try {
-                     e.trackTrips(on);
-                 } catch (const std::logic_error &x) {  // (lane change: out of scope, not a failure of the call)
-                     PyErr_SetString(PyExc_NotImplementedError, x.what());
-                     throw py::error_already_set();
-                 }
-             },
-             "on"_a)
+        .def("_track_trips", &trackOrNotImplemented<E, &E::trackTrips>, "on"_a)
         .def("_trip_tracking", &E::tripTracking)
         .def("_trip_features", [](E &e) { return tripTuple(e); },
              "(entered, admitted, admitted_buffer_steps, finished, finished_travel_steps, in_system, buffered, "

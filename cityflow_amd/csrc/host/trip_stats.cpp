@@ -10,28 +10,15 @@
 
 namespace cfa {
 
-bool TripStats::onDevice() const {
-    return be_->cfx_trip_stats_enable && be_->cfx_observe_trip_stats_device && be_->cfx_get_trip_stats && be_->cfx_trip_stats_get_state &&
-           be_->cfx_trip_stats_set_state;
-}
-
-void TripStats::fail(const char *what) const {
-    const char *msg = be_->cfx_last_error(dev_);
-    throw std::runtime_error(std::string("cityflow_amd: ") + what + " failed: " + (msg ? msg : ""));
-}
-
-void TripStats::requireOn(const char *what) const {
-    if (!on_) throw std::runtime_error(std::string(what) + ": trip tracking is off (track_trips(True) turns it on)");
+void TripStats::bind(const Backend *be, cfx_engine *dev, int nEnvs, double interval) {
+    bindBackend(be, dev, "cfx_trip_stats_enable", be->cfx_trip_stats_enable, be->cfx_observe_trip_stats_device, be->cfx_get_trip_stats,
+                be->cfx_trip_stats_get_state, be->cfx_trip_stats_set_state);
+    nEnvs_ = nEnvs;
+    interval_ = interval;
 }
 
 void TripStats::enable(bool on) {
-    if (on == on_) return;
-    if (onDevice()) {
-        if (be_->cfx_trip_stats_enable(dev_, on ? 1 : 0) != CFX_OK) fail("cfx_trip_stats_enable");
-        on_ = on;
-        return;
-    }
-    on_ = on;
+    if (!switchTo(on)) return;
     std::vector<cfx_trip_stats_env>().swap(rec_);
     std::vector<uint8_t>().swap(seen_);
     std::vector<uint8_t>().swap(status_);
@@ -52,14 +39,6 @@ void TripStats::note(int32_t vid, double enterTime, int env) {
 void TripStats::forget() {
     std::vector<int32_t>().swap(enter_);
     std::vector<int32_t>().swap(env_);
-}
-
-void TripStats::afterStep(int64_t step) {
-    if (on_ && !onDevice()) walk(step, false);
-}
-
-void TripStats::baseline(int64_t step) {
-    if (on_ && !onDevice()) walk(step, true);
 }
 
 // one tick (or baseline) of the host tracker: the rules of include/cityflow_amd.h over the status of every vehicle number noted
@@ -130,7 +109,7 @@ void TripStats::features(const cfx_trip_stats_out &o) {
 
 void TripStats::observeDevice(const cfx_trip_stats_out &o, uintptr_t consumerStream) {
     requireOn("observe_trips_tensor");
-    if (!onDevice()) throw std::runtime_error("cityflow_amd: '" + be_->path + "' has no device-side trip statistics");
+    requireDevice("trip statistics");
     if (be_->cfx_observe_trip_stats_device(dev_, &o, (void *) consumerStream) != CFX_OK) fail("cfx_observe_trip_stats_device");
 }
 

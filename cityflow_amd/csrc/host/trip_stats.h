@@ -1,38 +1,25 @@
 // Per-environment trip statistics and the average travel time across steps (include/cityflow_amd.h "cfx_trip_stats_enable" has
-// the rules), as Engine and VectorEngine hold them.  On a backend that exports the five optional entry points the device keeps
-// the tracker and this is a thin dispatcher.  A backend without them (the CPU twin) gets the HOST tracker below: the same rules
-// in C++ over cfx_get_vehicle_status, ticked by the owner after every step.  The owner tells it every vehicle number's enter
-// time and environment (note) before the tick that first sees the number.  Both keep a status byte per vehicle number (the
-// status at the previous tick, 0xFF = never seen) and a cfx_trip_stats_env per environment.
+// the rules), as Engine and VectorEngine hold them (tracker_base.h has the lifecycle).  The host tracker walks
+// cfx_get_vehicle_status; the owner tells it every vehicle number's enter time and environment (note) before the tick that
+// first sees the number.  Device and host keep a status byte per vehicle number (the status at the previous tick, 0xFF = never
+// seen) and a cfx_trip_stats_env per environment.
 #pragma once
 
-#include <cstdint>
-#include <vector>
-
-#include "cityflow_amd.h"
+#include "tracker_base.h"
 
 namespace cfa {
 
-struct Backend;
-
-class TripStats {
+class TripStats : public TrackerBase {
 public:
-    void bind(const Backend *be, cfx_engine *dev, int nEnvs, double interval) {
-        be_ = be;
-        dev_ = dev;
-        nEnvs_ = nEnvs;
-        interval_ = interval;
-    }
-    bool on() const { return on_; }
-    bool onDevice() const;             // the backend keeps the tracker (all five entry points)
+    TripStats() : TrackerBase("trip", "track_trips") {}
+    void bind(const Backend *be, cfx_engine *dev, int nEnvs, double interval);
     // on: the device takes its baseline; the owner of a HOST tracker notes the vehicles alive and calls baseline().  off: freed
     void enable(bool on);
     // ---- host tracker (no-ops while the device keeps it)
     int32_t noted() const { return (int32_t) enter_.size(); }
     void note(int32_t vid, double enterTime, int env);
     void forget();                     // the vehicle numbers are about to mean something else (reset, load)
-    void baseline(int64_t step);       // on the statuses as they stand: nothing is counted as entered
-    void afterStep(int64_t step);      // the tick
+    // (baseline(): on the statuses as they stand, nothing is counted as entered)
     // ----
     void features(const cfx_trip_stats_out &out);  // any pointer may be null; host memory
     void observeDevice(const cfx_trip_stats_out &out, uintptr_t consumerStream);
@@ -40,14 +27,9 @@ public:
     void setState(const std::vector<cfx_trip_stats_env> &s);
 
 private:
-    void requireOn(const char *what) const;
-    void fail(const char *what) const;
-    void walk(int64_t step, bool baseline);
-    const Backend *be_ = nullptr;
-    cfx_engine *dev_ = nullptr;
+    void walk(int64_t step, bool baseline) override;
     int nEnvs_ = 1;
     double interval_ = 1.0;
-    bool on_ = false;
     // the host tracker
     std::vector<cfx_trip_stats_env> rec_;
     std::vector<uint8_t> seen_, status_;

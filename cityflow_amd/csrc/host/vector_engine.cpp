@@ -183,9 +183,7 @@ VectorEngineHost::VectorEngineHost(const std::string &configFile, int numEnvs, i
         check(be_.cfx_add_routes(dev_, routesPerEnv_, rt.routeStart.data(), roads.data(), rt.nextStart.data(), nextLL.data()),
               "cfx_add_routes");
     }
-    flow_.bind(&be_, dev_, R_ * L_);
-    move_.bind(&be_, dev_, &net_->flat(), R_);
-    trip_.bind(&be_, dev_, R_, interval_);
+    trackers_.bind(&be_, dev_, &net_->flat(), R_, interval_);
     plan_.bind(&be_, dev_, net_.get(), R_, true);
 }
 
@@ -528,18 +526,11 @@ void VectorEngineHost::nextStep() {
     hostTranslateSec_ += translateSec;
     hostSubmitSec_ += std::chrono::duration<double>(t3 - t2).count();
     step_ += 1;
-    if (flow_.on() && !flow_.onDevice()) {  // (the host tracker's tick; a backend that keeps the tracker has ticked inside cfx_step)
+    if (trackers_.onHost()) {
+        // (the batch just handed over names the new vehicles; the ahead thread works on the next one)
+        for (const cfx_spawn &s : recs_) trackers_.trip.note(s.vid, s.enter_time, L_ > 0 ? s.lane / L_ : 0);
         std::lock_guard<std::mutex> guard(queryMutex_);
-        flow_.afterStep((int64_t) step_);
-    }
-    if (move_.on() && !move_.onDevice()) {
-        std::lock_guard<std::mutex> guard(queryMutex_);
-        move_.afterStep((int64_t) step_);
-    }
-    if (trip_.on() && !trip_.onDevice()) {  // (the batch just handed over names the new vehicles; the ahead thread works on the next one)
-        for (const cfx_spawn &s : recs_) trip_.note(s.vid, s.enter_time, L_ > 0 ? s.lane / L_ : 0);
-        std::lock_guard<std::mutex> guard(queryMutex_);
-        trip_.afterStep((int64_t) step_);
+        trackers_.afterStep((int64_t) step_);
     }
 }
 
@@ -560,10 +551,7 @@ void VectorEngineHost::reset(bool resetRnd) {
     step_ = 0;
     {
         std::lock_guard<std::mutex> guard(queryMutex_);
-        flow_.baseline(0);
-        move_.baseline(0);
-        trip_.forget();
-        trip_.baseline(0);
+        trackers_.rebaseline(0, [] {});
     }
     submitted_.store(0, std::memory_order_release);
     hostSpawnSec_ = hostTranslateSec_ = hostSubmitSec_ = 0;
@@ -629,15 +617,13 @@ void VectorEngineHost::rollback(DeviceCheckpoint &ck) {
     step_ = ck.step;
     {
         std::lock_guard<std::mutex> guard(queryMutex_);
-        flow_.baseline((int64_t) step_);
-        move_.baseline((int64_t) step_);
-        trip_.forget();
-        if (trip_.on() && !trip_.onDevice())  // (host tracker: the vehicles of the checkpoint, by their global numbers)
+        trackers_.rebaseline((int64_t) step_, [this] {  // (host tracker: the vehicles of the checkpoint, by their global numbers)
+            if (!trackers_.trip.onHost()) return;
             for (size_t g = 0; g < globalToLocal_.size(); ++g) {
                 const auto &el = globalToLocal_[g];
-                trip_.note((int32_t) g, spawners_[(size_t) el.first]->vehicles[(size_t) el.second].enterTime, el.first);
+                trackers_.trip.note((int32_t) g, spawners_[(size_t) el.first]->vehicles[(size_t) el.second].enterTime, el.first);
             }
-        trip_.baseline((int64_t) step_);
+        });
     }
     submitted_.store((uint64_t) step_, std::memory_order_release);
 }
@@ -762,80 +748,72 @@ void VectorEngineHost::observeLanesDevice(const cfx_lane_obs &obs, uintptr_t con
 
 void VectorEngineHost::laneFronts(int k, const LaneFronts &out) {
     std::lock_guard<std::mutex> guard(queryMutex_);  // (the ABI is not re-entrant: the ahead thread may be asking the device)
-    if ((out.laneSteps || out.waitingSteps) && !flow_.on())
+    if ((out.laneSteps || out.waitingSteps) && !trackers_.flow.on())
         throw std::runtime_error("lane fronts: lane_steps / waiting_steps need lane-flow tracking (track_lane_flow(True) turns it on)");
     if (out.distance || out.speed) laneFrontsOf(be_, dev_, R_ * L_, k, out.distance, out.speed);
-    if (out.laneSteps || out.waitingSteps) flow_.fronts(k, out.laneSteps, out.waitingSteps);
+    if (out.laneSteps || out.waitingSteps) trackers_.flow.fronts(k, out.laneSteps, out.waitingSteps);
     raiseDeviceError();
 }
 
 void VectorEngineHost::trackLaneFlow(bool on) {
     if (on && laneChange_) throw std::logic_error("track_lane_flow: not with laneChange (a shadow changes identity when its change finishes)");
     std::lock_guard<std::mutex> guard(queryMutex_);
-    flow_.enable(on, (int64_t) step_);
+    trackers_.flow.enable(on, (int64_t) step_);
 }
 
 void VectorEngineHost::trackMovementFlow(bool on) {
     if (on && laneChange_) throw std::logic_error("track_movement_flow: not with laneChange (a shadow changes identity when its change finishes)");
     std::lock_guard<std::mutex> guard(queryMutex_);
-    move_.enable(on, (int64_t) step_);
+    trackers_.move.enable(on, (int64_t) step_);
 }
 
 void VectorEngineHost::movementFlowFeatures(const MoveFlowOut &out, bool reset) {
     std::lock_guard<std::mutex> guard(queryMutex_);  // (the ABI is not re-entrant: the ahead thread may be asking the device)
-    move_.features(out, reset);
+    trackers_.move.features(out, reset);
     raiseDeviceError();
 }
 
 void VectorEngineHost::observeMovementFlowDevice(const MoveFlowOut &out, bool reset, uintptr_t consumerStream) {
     std::lock_guard<std::mutex> guard(queryMutex_);
-    move_.observeDevice(out, reset, consumerStream);
+    trackers_.move.observeDevice(out, reset, consumerStream);
 }
 
 void VectorEngineHost::trackTrips(bool on) {
     if (on && laneChange_) throw std::logic_error("track_trips: not with laneChange (a shadow is a vehicle number with its parent's enter time)");
-    if (on == trip_.on()) return;
+    if (on == trackers_.trip.on()) return;
     waitAhead();  // (the host tracker reads the numbering below; the batch being prepared appends to it)
     std::lock_guard<std::mutex> guard(queryMutex_);
-    trip_.enable(on);
-    if (!on || trip_.onDevice()) return;
+    trackers_.trip.enable(on);
+    if (!on || trackers_.trip.onDevice()) return;
     cfx_scalars sc{};
     check(be_.cfx_get_scalars(dev_, &sc), "cfx_get_scalars");
     for (int64_t v = 0; v < sc.spawned_vehicle_count && (size_t) v < globalToLocal_.size(); ++v) {
         const auto gl = globalToLocal_[(size_t) v];
-        trip_.note((int32_t) v, spawners_[(size_t) gl.first]->vehicles[(size_t) gl.second].enterTime, gl.first);
+        trackers_.trip.note((int32_t) v, spawners_[(size_t) gl.first]->vehicles[(size_t) gl.second].enterTime, gl.first);
     }
-    trip_.baseline((int64_t) step_);
+    trackers_.trip.baseline((int64_t) step_);
 }
 
 void VectorEngineHost::tripFeatures(const cfx_trip_stats_out &out) {
     std::lock_guard<std::mutex> guard(queryMutex_);  // (the ABI is not re-entrant: the ahead thread may be asking the device)
-    trip_.features(out);
+    trackers_.trip.features(out);
     raiseDeviceError();
 }
 
 void VectorEngineHost::observeTripsDevice(const cfx_trip_stats_out &out, uintptr_t consumerStream) {
     std::lock_guard<std::mutex> guard(queryMutex_);
-    trip_.observeDevice(out, consumerStream);
+    trackers_.trip.observeDevice(out, consumerStream);
 }
 
 void VectorEngineHost::laneFlowFeatures(const LaneFlowOut &out, bool reset) {
     std::lock_guard<std::mutex> guard(queryMutex_);  // (the ABI is not re-entrant: the ahead thread may be asking the device)
-    flow_.features(out, reset);
+    trackers_.flow.features(out, reset);
     raiseDeviceError();
 }
 
-void VectorEngineHost::observeLaneFlowDevice(uintptr_t entered, uintptr_t left, uintptr_t leftSteps, uintptr_t leftWaitingSteps,
-                                             uintptr_t waitingSteps, uintptr_t maxWaitingSteps, bool reset, uintptr_t consumerStream) {
-    LaneFlowOut o;
-    o.entered = (int32_t *) entered;
-    o.left = (int32_t *) left;
-    o.leftSteps = (int64_t *) leftSteps;
-    o.leftWaitingSteps = (int64_t *) leftWaitingSteps;
-    o.waitingSteps = (int64_t *) waitingSteps;
-    o.maxWaitingSteps = (int32_t *) maxWaitingSteps;
+void VectorEngineHost::observeLaneFlowDevice(const LaneFlowOut &out, bool reset, uintptr_t consumerStream) {
     std::lock_guard<std::mutex> guard(queryMutex_);
-    flow_.observeDevice(o, reset, consumerStream);
+    trackers_.flow.observeDevice(out, reset, consumerStream);
 }
 
 const InterLayout &VectorEngineHost::intersectionLayout() {

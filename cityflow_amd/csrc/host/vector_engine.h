@@ -77,18 +77,17 @@ public:
     // ---- per-movement flow and delay statistics across steps over every environment (EngineHost::trackMovementFlow and its
     //      kin): outputs [R * I * M], any pointer may be null
     void trackMovementFlow(bool on);
-    bool movementFlowTracking() const { return move_.on(); }
-    int movementFlowRows() const { return (int) move_.rows(); }
+    bool movementFlowTracking() const { return trackers_.move.on(); }
+    int movementFlowRows() const { return (int) trackers_.move.rows(); }
     void movementFlowFeatures(const MoveFlowOut &out, bool reset);
     void observeMovementFlowDevice(const MoveFlowOut &out, bool reset, uintptr_t consumerStream);
     void trackLaneFlow(bool on);
-    bool laneFlowTracking() const { return flow_.on(); }
+    bool laneFlowTracking() const { return trackers_.flow.on(); }
     void laneFlowFeatures(const LaneFlowOut &out, bool reset);
-    void observeLaneFlowDevice(uintptr_t entered, uintptr_t left, uintptr_t leftSteps, uintptr_t leftWaitingSteps,
-                               uintptr_t waitingSteps, uintptr_t maxWaitingSteps, bool reset, uintptr_t consumerStream);
+    void observeLaneFlowDevice(const LaneFlowOut &out, bool reset, uintptr_t consumerStream);
     // trip statistics and the average travel time per environment (EngineHost::trackTrips and its kin): outputs [R]
     void trackTrips(bool on);
-    bool tripTracking() const { return trip_.on(); }
+    bool tripTracking() const { return trackers_.trip.on(); }
     void tripFeatures(const cfx_trip_stats_out &out);
     void observeTripsDevice(const cfx_trip_stats_out &out, uintptr_t consumerStream);
     std::vector<std::string> laneIds() const;
@@ -110,9 +109,7 @@ public:
 private:
     void check(int32_t rc, const char *what);
     std::unique_ptr<InterLayout> interLayout_;  // built by the first call that needs it
-    LaneFlow flow_;                      // (every call with queryMutex_ held: it asks the device)
-    MoveFlow move_;                      // (likewise)
-    TripStats trip_;                     // (likewise)
+    Trackers trackers_;                  // (every call with queryMutex_ held: it asks the device)
     bool devicePhaseUnchecked_ = false;  // as EngineHost: read by every call below that has waited for the device
     void raiseDeviceError();             // (the caller holds queryMutex_)
     TlPlan plan_;                        // (every call with queryMutex_ held)

@@ -410,6 +410,32 @@ def intersection_layout(self):
     return d
 
 
+def _observe_tracker_tensor(eng, what, names, tensors, dtype_of, shape, tracking, off, arrays, device_call, extra=()):
+    """What observe_lane_flow_tensor, observe_movement_flow_tensor and observe_trips_tensor do.  `tensors`: the outputs in the
+    order of `names` (None: not asked for), each of `shape()` and `dtype_of(torch, name)`; `tracking()`, and the message `off`
+    while it is not on; `arrays()`: the array call, for an engine without device buffers (the twin); `device_call(*pointers,
+    *extra, stream)`, 0 for an output not asked for.  In this order: at least one output, every buffer, tracking on — and
+    nothing is enqueued before all of that."""
+    torch = _torch()
+    given = dict(zip(names, tensors))
+    if all(t is None for t in given.values()):
+        raise ValueError(what + ": give at least one of " + ", ".join(names))
+    shape = shape()
+    device = _engine_device(torch, eng)
+    for name, t in given.items():
+        if t is not None:
+            _check_buf(torch, t, name, shape, dtype_of(torch, name), device)
+    if not tracking():
+        raise RuntimeError(what + ": " + off)
+    if not eng._device_buffers():  # (the twin: over the array call)
+        for name, a in arrays().items():
+            if given[name] is not None:
+                given[name].copy_(torch.from_numpy(a))
+        return
+    device_call(*[0 if given[name] is None else given[name].data_ptr() for name in names], *extra,
+                torch.cuda.current_stream(device).cuda_stream)
+
+
 LANE_FLOW_OUTPUTS = ("entered", "left", "left_steps", "left_waiting_steps", "waiting_steps", "max_waiting_steps")
 _LANE_FLOW_INT64 = ("left_steps", "left_waiting_steps", "waiting_steps")
 
@@ -447,25 +473,12 @@ def observe_lane_flow_tensor(self, entered=None, left=None, left_steps=None, lef
     Seconds = steps * interval.  reset=True zeroes the four accumulators in the same launch, after they were read — all four,
     whether or not they were asked for.  Every element is written.  VectorEngine: a leading [R] on every output.  At least one
     output; every argument is checked before anything is enqueued; RuntimeError while tracking is off."""
-    torch = _torch()
-    given = dict(zip(LANE_FLOW_OUTPUTS, (entered, left, left_steps, left_waiting_steps, waiting_steps, max_waiting_steps)))
-    if all(t is None for t in given.values()):
-        raise ValueError("observe_lane_flow_tensor: give at least one of " + ", ".join(LANE_FLOW_OUTPUTS))
-    shape = tuple(self._tensor_shapes()[0])
-    device = _engine_device(torch, self)
-    for name, t in given.items():
-        if t is not None:
-            _check_buf(torch, t, name, shape, torch.int64 if name in _LANE_FLOW_INT64 else torch.int32, device)
-    if not self._lane_flow_tracking():
-        raise RuntimeError("observe_lane_flow_tensor: lane-flow tracking is off (track_lane_flow(True) turns it on)")
-    if not self._device_buffers():  # (the twin: over the array call)
-        arrays = observe_lane_flow_array(self, reset=reset)
-        for name, t in given.items():
-            if t is not None:
-                t.copy_(torch.from_numpy(arrays[name]))
-        return
-    self._observe_lane_flow_device(*[0 if given[name] is None else given[name].data_ptr() for name in LANE_FLOW_OUTPUTS],
-                                   bool(reset), torch.cuda.current_stream(device).cuda_stream)
+    _observe_tracker_tensor(
+        self, "observe_lane_flow_tensor", LANE_FLOW_OUTPUTS,
+        (entered, left, left_steps, left_waiting_steps, waiting_steps, max_waiting_steps),
+        lambda torch, name: torch.int64 if name in _LANE_FLOW_INT64 else torch.int32, lambda: tuple(self._tensor_shapes()[0]),
+        self._lane_flow_tracking, "lane-flow tracking is off (track_lane_flow(True) turns it on)",
+        lambda: observe_lane_flow_array(self, reset=reset), self._observe_lane_flow_device, (bool(reset),))
 
 
 def observe_lane_flow_array(self, reset=False):
@@ -525,26 +538,12 @@ def observe_movement_flow_tensor(self, entered=None, entered_lane_steps=None, en
     reset=True zeroes the six accumulators in the same launch, after they were read — all six, whether or not they were asked
     for.  VectorEngine: a leading [R] on every output.  At least one output; every argument is checked before anything is
     enqueued; RuntimeError while tracking is off."""
-    torch = _torch()
-    given = dict(zip(MOVEMENT_FLOW_OUTPUTS, (entered, entered_lane_steps, entered_lane_waiting_steps, left, left_steps,
-                                             left_waiting_steps, waiting_steps, max_waiting_steps)))
-    if all(t is None for t in given.values()):
-        raise ValueError("observe_movement_flow_tensor: give at least one of " + ", ".join(MOVEMENT_FLOW_OUTPUTS))
-    shape = _movement_flow_shape(self)
-    device = _engine_device(torch, self)
-    for name, t in given.items():
-        if t is not None:
-            _check_buf(torch, t, name, shape, torch.int32 if name in _MOVEMENT_FLOW_INT32 else torch.int64, device)
-    if not self._movement_flow_tracking():
-        raise RuntimeError("observe_movement_flow_tensor: movement-flow tracking is off (track_movement_flow(True) turns it on)")
-    if not self._device_buffers():  # (the twin: over the array call)
-        arrays = observe_movement_flow_array(self, reset=reset)
-        for name, t in given.items():
-            if t is not None:
-                t.copy_(torch.from_numpy(arrays[name]))
-        return
-    self._observe_movement_flow_device(*[0 if given[name] is None else given[name].data_ptr() for name in MOVEMENT_FLOW_OUTPUTS],
-                                       bool(reset), torch.cuda.current_stream(device).cuda_stream)
+    _observe_tracker_tensor(
+        self, "observe_movement_flow_tensor", MOVEMENT_FLOW_OUTPUTS,
+        (entered, entered_lane_steps, entered_lane_waiting_steps, left, left_steps, left_waiting_steps, waiting_steps, max_waiting_steps),
+        lambda torch, name: torch.int32 if name in _MOVEMENT_FLOW_INT32 else torch.int64, lambda: _movement_flow_shape(self),
+        self._movement_flow_tracking, "movement-flow tracking is off (track_movement_flow(True) turns it on)",
+        lambda: observe_movement_flow_array(self, reset=reset), self._observe_movement_flow_device, (bool(reset),))
 
 
 def observe_movement_flow_array(self, reset=False):
@@ -603,26 +602,12 @@ def observe_trips_tensor(self, entered=None, admitted=None, admitted_buffer_step
     was created or last reset(), and only while no push_vehicle() has happened since the last step: the reference counts a
     pushed vehicle at once, the tracker sees it with the next step.  Seconds = steps * interval.  Every element is written.
     At least one output; every argument is checked before anything is enqueued; RuntimeError while tracking is off."""
-    torch = _torch()
-    given = dict(zip(TRIP_OUTPUTS, (entered, admitted, admitted_buffer_steps, finished, finished_travel_steps, in_system, buffered,
-                                    in_system_travel_steps, average_travel_time)))
-    if all(t is None for t in given.values()):
-        raise ValueError("observe_trips_tensor: give at least one of " + ", ".join(TRIP_OUTPUTS))
-    shape = tuple(self._tensor_shapes()[0])[:-1]
-    device = _engine_device(torch, self)
-    for name, t in given.items():
-        if t is not None:
-            _check_buf(torch, t, name, shape, _trip_dtype(torch, name), device)
-    if not self._trip_tracking():
-        raise RuntimeError("observe_trips_tensor: trip tracking is off (track_trips(True) turns it on)")
-    if not self._device_buffers():  # (the twin: over the array call)
-        arrays = observe_trips_array(self)
-        for name, t in given.items():
-            if t is not None:
-                t.copy_(torch.from_numpy(arrays[name]))
-        return
-    self._observe_trips_device(*[0 if given[name] is None else given[name].data_ptr() for name in TRIP_OUTPUTS],
-                               torch.cuda.current_stream(device).cuda_stream)
+    _observe_tracker_tensor(
+        self, "observe_trips_tensor", TRIP_OUTPUTS,
+        (entered, admitted, admitted_buffer_steps, finished, finished_travel_steps, in_system, buffered, in_system_travel_steps,
+         average_travel_time),
+        _trip_dtype, lambda: tuple(self._tensor_shapes()[0])[:-1], self._trip_tracking,
+        "trip tracking is off (track_trips(True) turns it on)", lambda: observe_trips_array(self), self._observe_trips_device)
 
 
 def observe_trips_array(self):
