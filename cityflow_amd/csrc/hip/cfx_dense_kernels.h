@@ -72,21 +72,14 @@ __device__ inline void finishAction(const StepCtx &c, const ActionOut &o, const 
 // changed the light: the commit's TrafficLight::passTime, cfx_set_tl_phase(s), a load, a reset, which sets gatePhase to
 // -1), their tails "as of this step" are the committed records (linkTailNow), and the compaction scratch of all drivables
 // is cleared by the lanes' threads in strides (16 B per drivable, written, nothing read).
-template <bool LANES, int NB>
+template <bool LANES, int NB, bool GT = false>
 __global__ __launch_bounds__(kBlock) void kd_admit(StepCtx c, int32_t *admitStep, int32_t *waitHead, VidTable vt, CompactScratch cs,
                                                    const SpawnBatchT<NB> batch, int32_t *gatePhase) {
     __shared__ cfx_vehicle_template sT[kLdsTempl];
     __shared__ int sLane[NB];
     const int nRecs = batch.n, firstNewVid = batch.firstNewVid;
     for (int i = threadIdx.x; i < nRecs; i += blockDim.x) sLane[i] = batch.lane[i];
-    const cfx_vehicle_template *tv = c.t.templ;
-    if (c.t.nTempl <= kLdsTempl) {
-        const int nd = c.t.nTempl * (int) (sizeof(cfx_vehicle_template) / sizeof(double));
-        const double *src = (const double *) c.t.templ;
-        double *dst = (double *) sT;
-        for (int i = threadIdx.x; i < nd; i += blockDim.x) dst[i] = src[i];
-        tv = sT;
-    }
+    const cfx_vehicle_template *const tv = templatesOf<GT>(c.t, sT);
     const int d = blockIdx.x * blockDim.x + threadIdx.x;
     const bool isLane = d < c.n.L, inRange = LANES ? isLane : d < c.n.L + c.n.K;
     TailRec committed{};
@@ -269,6 +262,7 @@ constexpr int kDenseActBlock = CFX_KD_ACT_BLOCK;
 #ifndef CFX_KD_ACTION_WAVES
 #define CFX_KD_ACTION_WAVES 5
 #endif
+template <bool GT = false>
 __global__ __launch_bounds__(kDenseActBlock, CFX_KD_ACTION_WAVES) void kd_action(StepCtx c, ActionOut o, JobQueue q, int nVehicleBlocks) {
     KSTAMP(6, 0);
     if ((int) blockIdx.x >= nVehicleBlocks) {  // trailing blocks: the per-laneLink notify sources for the cross phase
@@ -282,15 +276,8 @@ __global__ __launch_bounds__(kDenseActBlock, CFX_KD_ACTION_WAVES) void kd_action
     const int S = c.segStart[c.n.L + c.n.K];
     if ((int) (blockIdx.x * blockDim.x) >= S) return;
     __shared__ cfx_vehicle_template sT[kLdsTempl];
-    const cfx_vehicle_template *tv = c.t.templ;
-    if (c.t.nTempl <= kLdsTempl) {
-        const int nd = c.t.nTempl * (int) (sizeof(cfx_vehicle_template) / sizeof(double));
-        const double *src = (const double *) c.t.templ;
-        double *dst = (double *) sT;
-        for (int i = threadIdx.x; i < nd; i += blockDim.x) dst[i] = src[i];
-        __syncthreads();
-        tv = sT;
-    }
+    const cfx_vehicle_template *const tv = templatesOf<GT>(c.t, sT);
+    if (!GT) __syncthreads();
     KSTAMP(6, 1);
     // (requesting the slot's columns in front of this barrier — so that they travel with the template table and the slot
     // count — was measured in round 4: 9.5 -> 9.3 us at 30x30, 46.8 -> 48.5 us at 1 M vehicles; not kept)

@@ -366,6 +366,10 @@ struct cfx_engine {
     // Launch `kernel`; while profiling, with the dispatch's own start / stop timestamps (hipExtLaunchKernel records the
     // events at the kernel's begin and end, the same clock readings a rocprofv3 kernel trace reports — a pair of
     // hipEventRecord calls around the launch would add the marker packets' latency, ~3 us, to every kernel).
+    // The instantiation of a step kernel by where it reads the vehicle templates: the block's LDS copy up to kLdsTempl of them,
+    // global memory beyond (templatesOf, cfx_kernels.h).  `...`: the kernel's other template arguments, every one of them.
+    bool manyTempl() const { return hTempl.size() > (size_t) kLdsTempl; }
+#define CFX_BY_TEMPL(K, ...) (manyTempl() ? K<__VA_ARGS__, true> : K<__VA_ARGS__, false>)
     template <typename K, typename... A>
     void launchNamed(int kernelId, const char *symbol, K kernel, dim3 grid, dim3 block, A... args) {
         slotSymbol[kernelId] = symbol;
@@ -1338,12 +1342,12 @@ struct cfx_engine {
     void launchRingAdmit(const SpawnPlan &p, int blocks, const RingCtx &c, const RingCommit &rk, const RingHaloIn &hin) {
         if (p.inMem)
             launchNamed(PK_ADMIT, COMMIT ? "kr_admit<true, kBlock, SpawnBatchMem>" : "kr_admit<false, kBlock, SpawnBatchMem>",
-                        kr_admit<COMMIT, kBlock, SpawnBatchMem>, dim3(blocks), dim3(kBlock), c, admitStep, waitHead, vt, sc, p.mem, rk, hin);
+                        CFX_BY_TEMPL(kr_admit, COMMIT, kBlock, SpawnBatchMem), dim3(blocks), dim3(kBlock), c, admitStep, waitHead, vt, sc, p.mem, rk, hin);
         else if (p.batch.n > kAdmitRecs)
-            launchNamed(PK_ADMIT, COMMIT ? "kr_admit<true, kAdmitRecsBig>" : "kr_admit<false, kAdmitRecsBig>", kr_admit<COMMIT, kAdmitRecsBig>,
+            launchNamed(PK_ADMIT, COMMIT ? "kr_admit<true, kAdmitRecsBig>" : "kr_admit<false, kAdmitRecsBig>", CFX_BY_TEMPL(kr_admit, COMMIT, kAdmitRecsBig, SpawnBatchT<kAdmitRecsBig>),
                         dim3(blocks), dim3(kBlock), c, admitStep, waitHead, vt, sc, p.batch, rk, hin);
         else
-            launchNamed(PK_ADMIT, COMMIT ? "kr_admit<true>" : "kr_admit<false>", kr_admit<COMMIT>, dim3(blocks), dim3(kBlock), c, admitStep,
+            launchNamed(PK_ADMIT, COMMIT ? "kr_admit<true>" : "kr_admit<false>", CFX_BY_TEMPL(kr_admit, COMMIT, kAdmitRecs, SpawnBatchT<kAdmitRecs>), dim3(blocks), dim3(kBlock), c, admitStep,
                         waitHead, vt, sc, p.smallBatch(), rk, hin);
     }
     // kr_action<B, GHOST>: a tile's ghost lanes take the instantiations that know about frozen proxies
@@ -1352,10 +1356,10 @@ struct cfx_engine {
                          int nLLBlocks, const RingHist &rh) {
         static_assert(B == 256 || B == 512, "the block sizes kr_action is launched with");
         if (tiled)
-            launchNamed(PK_ACTION, B == 256 ? "kr_action<256, true>" : "kr_action<512, true>", kr_action<B, true>, grid, dim3(B), c, ro, jq,
+            launchNamed(PK_ACTION, B == 256 ? "kr_action<256, true>" : "kr_action<512, true>", CFX_BY_TEMPL(kr_action, B, true), grid, dim3(B), c, ro, jq,
                         jobRecs, G, nLaneBlocks, nLLBlocks, rh);
         else
-            launchNamed(PK_ACTION, B == 256 ? "kr_action<256>" : "kr_action<512>", kr_action<B>, grid, dim3(B), c, ro, jq, jobRecs, G,
+            launchNamed(PK_ACTION, B == 256 ? "kr_action<256>" : "kr_action<512>", CFX_BY_TEMPL(kr_action, B, false), grid, dim3(B), c, ro, jq, jobRecs, G,
                         nLaneBlocks, nLLBlocks, rh);
     }
 
@@ -1452,7 +1456,7 @@ struct cfx_engine {
             if ((rc = debugCheck(true, "kr_index"))) return rc;
             const RingHist rh = takeHist(nVehBlocks + nLL);  // (the last step's Lane::history: trailing blocks of this launch)
             const int nHist = rh.h.num ? (L + kListBlock - 1) / kListBlock : 0;
-            launchNamed(PK_ACTION, tiled ? "kl_action<true>" : "kl_action", tiled ? kl_action<true> : kl_action<false>, dim3(nVehBlocks + nLL + nHist),
+            launchNamed(PK_ACTION, tiled ? "kl_action<true>" : "kl_action", tiled ? CFX_BY_TEMPL(kl_action, true) : CFX_BY_TEMPL(kl_action, false), dim3(nVehBlocks + nLL + nHist),
                         dim3(kListBlock), c, ro, jq, jobRecs, (const int4 *) rList, (const int32_t *) rListCount, nVehBlocks, idxTicket, rh);
             return CFX_OK;
         }
@@ -1470,7 +1474,7 @@ struct cfx_engine {
     // `lightsToo`: the kernel advances the lights, because the step's commit is deferred
     void launchRingCross(bool useBig, size_t activeEst, const RingCtx &c, const RingOut &ro, const JobQueue &jq, bool lightsToo) {
         if (useBig) {
-            launchNamed(PK_CROSS, "k_cross2<false, RingCtx, RingOut>", k_cross2<false, RingCtx, RingOut>,
+            launchNamed(PK_CROSS, "k_cross2<false, RingCtx, RingOut>", CFX_BY_TEMPL(k_cross2, false, RingCtx, RingOut),
                         dim3((int) std::min<size_t>(std::max<size_t>(64, (activeEst / 4 + 15) / 16), (size_t) CFX_RING_CROSS2_WAVES * nCU)),  // (5 blocks per CU: 96 registers)
                         dim3(kCross2Block), c, ro, jq, RingLights{curPhase, remain, lightsToo ? 1 : 0});
             return;
@@ -1493,7 +1497,7 @@ struct cfx_engine {
         const size_t groups = crossPolicy.groups(activeEst);
 #endif
         lastCrossBlocks = cfx_policy::crossBlocks(groups, crossForceBlocks);
-        launchNamed(PK_CROSS, "kr_cross", kr_cross, dim3(lastCrossBlocks), dim3(kCrossBlock), c, ro, jq, (const RingJob *) rJobRecs,
+        launchNamed(PK_CROSS, "kr_cross", manyTempl() ? kr_cross<true> : kr_cross<false>, dim3(lastCrossBlocks), dim3(kCrossBlock), c, ro, jq, (const RingJob *) rJobRecs,
                     RingLights{curPhase, remain, lightsToo ? 1 : 0});
     }
 
@@ -1610,10 +1614,10 @@ struct cfx_engine {
     template <bool LANES>
     void launchDenseAdmit(const SpawnPlan &p, const StepCtx &c) {
         if (p.batch.n > kAdmitRecs)
-            launchNamed(PK_ADMIT, LANES ? "kd_admit<true, kAdmitRecsBig>" : "kd_admit<false, kAdmitRecsBig>", kd_admit<LANES, kAdmitRecsBig>,
+            launchNamed(PK_ADMIT, LANES ? "kd_admit<true, kAdmitRecsBig>" : "kd_admit<false, kAdmitRecsBig>", CFX_BY_TEMPL(kd_admit, LANES, kAdmitRecsBig),
                         dim3(gridFor(LANES ? L : D)), dim3(kBlock), c, admitStep, waitHead, vt, cs, p.batch, LANES ? gatePhase : (int32_t *) nullptr);
         else
-            launchNamed(PK_ADMIT, LANES ? "kd_admit<true, kAdmitRecs>" : "kd_admit<false, kAdmitRecs>", kd_admit<LANES, kAdmitRecs>,
+            launchNamed(PK_ADMIT, LANES ? "kd_admit<true, kAdmitRecs>" : "kd_admit<false, kAdmitRecs>", CFX_BY_TEMPL(kd_admit, LANES, kAdmitRecs),
                         dim3(gridFor(LANES ? L : D)), dim3(kBlock), c, admitStep, waitHead, vt, cs, p.smallBatch(), LANES ? gatePhase : (int32_t *) nullptr);
     }
 
@@ -1687,18 +1691,18 @@ struct cfx_engine {
         JobQueue jq{jobCount, crossJobs, (int) slotCap, &sc->overflow};
         if (tails) {
             const int nv = (int) ((slotBound + kDenseActBlock - 1) / kDenseActBlock), nl = (K + kDenseActBlock - 1) / kDenseActBlock;
-            launchNamed(PK_ACTION, "kd_action", kd_action, dim3(nv + nl), dim3(kDenseActBlock), c, ao, jq, nv);
+            launchNamed(PK_ACTION, "kd_action", manyTempl() ? kd_action<true> : kd_action<false>, dim3(nv + nl), dim3(kDenseActBlock), c, ao, jq, nv);
         } else {  // (lane change)
             const int nVehBlocks = (int) std::min<size_t>(std::max<size_t>(1, (slotBound + kActBlock - 1) / kActBlock), 8192);
             const int nLLBlocks = (K + kActBlock - 1) / kActBlock;
-            launchNamed(PK_ACTION, "k_action<true>", k_action, dim3(nVehBlocks + nLLBlocks), dim3(kActBlock), c, ao, jq, nVehBlocks);
+            launchNamed(PK_ACTION, "k_action<true>", manyTempl() ? k_action<true> : k_action<false>, dim3(nVehBlocks + nLLBlocks), dim3(kActBlock), c, ao, jq, nVehBlocks);
         }
         if (useBig)
             // (the blocks the chip holds at once — 7 per CU: the kernel's LDS — or fewer for a short queue: the kernel sizes its batches)
-            launchNamed(PK_CROSS, lc.on ? "k_cross2<true>" : "k_cross2<false>", lc.on ? k_cross2<true> : k_cross2<false>, dim3((int) std::min<size_t>(std::max<size_t>(1, (slotBound + 15) / 16), (size_t) CFX_CROSS2_BLOCKS_PER_CU * nCU)),
+            launchNamed(PK_CROSS, lc.on ? "k_cross2<true>" : "k_cross2<false>", lc.on ? CFX_BY_TEMPL(k_cross2, true, StepCtx, ActionOut) : CFX_BY_TEMPL(k_cross2, false, StepCtx, ActionOut), dim3((int) std::min<size_t>(std::max<size_t>(1, (slotBound + 15) / 16), (size_t) CFX_CROSS2_BLOCKS_PER_CU * nCU)),
                         dim3(kCross2Block), c, ao, jq, RingLights{nullptr, nullptr, 0});
         else
-            launchNamed(PK_CROSS, lc.on ? "k_cross<true>" : "k_cross<false>", lc.on ? k_cross<true> : k_cross<false>,
+            launchNamed(PK_CROSS, lc.on ? "k_cross<true>" : "k_cross<false>", lc.on ? CFX_BY_TEMPL(k_cross, true, StepCtx, ActionOut) : CFX_BY_TEMPL(k_cross, false, StepCtx, ActionOut),
                         dim3((int) std::min<size_t>(std::max<size_t>(1, (slotBound * 16 + kCrossBlock - 1) / kCrossBlock), 32768)),
                         dim3(kCrossBlock), c, ao, jq);
         if (lc.on) {

@@ -32,6 +32,26 @@ constexpr int kCrossBlock = CFX_CROSS_BLOCK;  // k_cross workgroup (16-lane grou
 #define CFX_LDS_TEMPL 32
 #endif
 constexpr int kLdsTempl = CFX_LDS_TEMPL;   // vehicle templates staged in LDS by k_action (104 B each)
+// Where a kernel reads the vehicle templates.  GT = false: from the block's LDS copy, which this fills (the caller's barrier
+// follows); GT = true: from the table in global memory, for more than kLdsTempl templates.  The host picks the instantiation
+// (Impl::manyTempl).  One kernel that takes either pointer at run time holds a generic one: every field is then a flat load,
+// and the wait for a flat load is vmcnt(0) and lgkmcnt(0) at once — it drains every global load in flight, those a kernel
+// requested for much later included.
+// A read of LDS where the other arm of a `?:` reads global memory: written plainly the compiler selects between the two
+// ADDRESSES and reads through a generic pointer — a flat load again.  Reads of different address spaces are not merged.
+template <class T> __device__ __forceinline__ T ldsRead(const T *p) { return *(const __attribute__((address_space(3))) T *) p; }
+template <bool GT>
+__device__ __forceinline__ const cfx_vehicle_template *templatesOf(const DevTables &t, cfx_vehicle_template *sT) {
+    if constexpr (GT) {
+        return t.templ;
+    } else {
+        const int nd = t.nTempl * (int) (sizeof(cfx_vehicle_template) / sizeof(double));
+        const double *src = (const double *) t.templ;
+        double *dst = (double *) sT;
+        for (int i = threadIdx.x; i < nd; i += blockDim.x) dst[i] = src[i];
+        return sT;
+    }
+}
 // Wavefronts per SIMD the register allocation of a kernel is asked to leave room for (second argument of __launch_bounds__;
 // 0 = whatever the compiler arrives at).  Build-time knobs for A/B runs (tools/exp_bench.py with differently built
 // libraries); the defaults are what was measured best.
@@ -873,7 +893,8 @@ __device__ __forceinline__ void actionOne(const C &c, const Out &o, const cfx_ve
     }
 
     // --- Vehicle::getNextSpeed vehicle.cpp:308-335
-    double v = t.max_speed;
+    const double maxSpeed = t.max_speed;  // (read once: `custom ? c.vCustomSpeed[..] : t.max_speed` becomes one flat load of a selected address)
+    double v = maxSpeed;
     v = min2(v, speed + t.max_pos_acc * interval);
     v = min2(v, lm.y);
 
@@ -881,7 +902,7 @@ __device__ __forceinline__ void actionOne(const C &c, const Out &o, const cfx_ve
     double cf;
     const bool custom = (flags & 1) != 0;  // Vehicle::hasSetCustomSpeed
     if (ls < 0) {
-        cf = custom ? c.vCustomSpeed[vid] : t.max_speed;
+        cf = custom ? c.vCustomSpeed[vid] : maxSpeed;
     } else if (custom) {
         const cfx_vehicle_template &tl = tv[leaderTempl];
         cf = min2(c.vCustomSpeed[vid], noCollisionSpeed(leaderSpeed, tl.max_neg_acc, speed, t.max_neg_acc, gap, interval, 0));
@@ -973,6 +994,7 @@ struct PushJob {
 };
 
 // (the dense layout without lane change runs kd_action: this kernel is the lane-change step's, and is reported as k_action<true>)
+template <bool GT = false>
 __global__ __launch_bounds__(kActBlock) void k_action(StepCtx c, ActionOut o, JobQueue q, int nVehicleBlocks) {
     // The trailing blocks of the launch do the (independent) per-laneLink notify sources for k_cross.
     if ((int) blockIdx.x >= nVehicleBlocks) {
@@ -980,15 +1002,8 @@ __global__ __launch_bounds__(kActBlock) void k_action(StepCtx c, ActionOut o, Jo
         return;
     }
     __shared__ cfx_vehicle_template sT[kLdsTempl];
-    const cfx_vehicle_template *tv = c.t.templ;
-    if (c.t.nTempl <= kLdsTempl) {
-        const int nd = c.t.nTempl * (int) (sizeof(cfx_vehicle_template) / sizeof(double));
-        const double *src = (const double *) c.t.templ;
-        double *dst = (double *) sT;
-        for (int i = threadIdx.x; i < nd; i += blockDim.x) dst[i] = src[i];
-        __syncthreads();
-        tv = sT;
-    }
+    const cfx_vehicle_template *const tv = templatesOf<GT>(c.t, sT);
+    if (!GT) __syncthreads();
     const int S = c.segStart[c.n.L + c.n.K];
     const int stride = nVehicleBlocks * blockDim.x;
     const PushJob push{q};
@@ -1015,10 +1030,9 @@ __device__ __forceinline__ int keepBlocker(const StepCtx &c, int blockerSlot) {
     return blockerSlot;
 }
 
-template <bool LC, class C = StepCtx, class Out = ActionOut>
+template <bool LC, class C = StepCtx, class Out = ActionOut, bool GT = false>
 __global__ __launch_bounds__(kCrossBlock) void k_cross(C c, Out o, JobQueue q) {
     __shared__ cfx_vehicle_template sT[kLdsTempl];
-    const cfx_vehicle_template *tv = c.t.templ;
     // A block works on ONE shard of the queue (the one its index names), so it needs that shard's count only — no prefix over
     // the shards, no second barrier — and every group's first queue entry is requested together with the count and the
     // template table (its place follows from the block and group index; an entry beyond the count is read and dropped).
@@ -1031,14 +1045,8 @@ __global__ __launch_bounds__(kCrossBlock) void k_cross(C c, Out o, JobQueue q) {
     const int32_t *const shardJobs = q.jobs + (size_t) shard * q.capacity;
     const int sFirstJob = shardJobs[jFirst < q.capacity ? jFirst : q.capacity - 1];
     const int nShard = min(q.count[shard * kJobShardStride], q.capacity);
-    if (c.t.nTempl <= kLdsTempl) {
-        const int nd = c.t.nTempl * (int) (sizeof(cfx_vehicle_template) / sizeof(double));
-        const double *src = (const double *) c.t.templ;
-        double *dst = (double *) sT;
-        for (int i = threadIdx.x; i < nd; i += blockDim.x) dst[i] = src[i];
-        __syncthreads();
-        tv = sT;
-    }
+    const cfx_vehicle_template *const tv = templatesOf<GT>(c.t, sT);
+    if (!GT) __syncthreads();
     for (int j = jFirst; j < nShard; j += blocksOfShard * groupsPerBlock) {
         const int s = j == jFirst ? sFirstJob : shardJobs[j];
         const int d = c.s.drv[s];
@@ -1145,7 +1153,7 @@ __device__ inline void passTimeAll(const DevNet &n, int32_t *curPhase, double *r
     }
 }
 
-template <bool LC, class C = StepCtx, class Out = ActionOut>
+template <bool LC, class C = StepCtx, class Out = ActionOut, bool GT = false>
 __global__ __launch_bounds__(kCross2Block, C::kCross2Waves) void k_cross2(C c, Out o, JobQueue q, RingLights lights = RingLights{nullptr, nullptr, 0}) {
     // (nothing in this kernel reads the lights: the approaching vehicles' light test is folded into llDyn by the action kernel)
     KSTAMP(8, 0);
@@ -1161,14 +1169,7 @@ __global__ __launch_bounds__(kCross2Block, C::kCross2Waves) void k_cross2(C c, O
     __shared__ double sD0[kCross2JobsMax], sSpeed[kCross2JobsMax];
     __shared__ int sWorkJob[kCross2Work], sWorkE[kCross2Work];
     __shared__ int sNWork;
-    const cfx_vehicle_template *tv = c.t.templ;
-    if (c.t.nTempl <= kLdsTempl) {
-        const int nd = c.t.nTempl * (int) (sizeof(cfx_vehicle_template) / sizeof(double));
-        const double *src = (const double *) c.t.templ;
-        double *dst = (double *) sT;
-        for (int i = threadIdx.x; i < nd; i += blockDim.x) dst[i] = src[i];
-        tv = sT;
-    }
+    const cfx_vehicle_template *const tv = templatesOf<GT>(c.t, sT);
     if (threadIdx.x == 0) {
         int run = 0;
         for (int i = 0; i < kJobShards; ++i) {
@@ -1277,7 +1278,7 @@ __global__ __launch_bounds__(kCross2Block, C::kCross2Waves) void k_cross2(C c, O
                 const VehRef self{speed, &tv[templ]};
                 if (!canYield(self, dOn4[u] - d0)) continue;
                 const int bit = bit4[u];
-                const unsigned long long word = (bit >> 6) == 0 ? sMask0[jl] : c.interMask[sMb[jl] + (bit >> 6)];
+                const unsigned long long word = (bit >> 6) == 0 ? ldsRead(&sMask0[jl]) : c.interMask[sMb[jl] + (bit >> 6)];
                 if (!((word >> (bit & 63)) & 1ULL)) continue;  // nobody to yield to there
                 const int w = atomicAdd(&sNWork, 1);
                 if (w < kCross2Work) {

@@ -559,7 +559,7 @@ __global__ void kr_halo_import(RingCtx c, HaloDev h, HaloIO io, VidTable vt, Dev
 // its tail, its count, its queue — except the lights, which the cross kernel of the committed step has already advanced.
 // NB: spawn records the arguments hold (kAdmitRecsBig on large networks, as kd_admit) — or, with Batch = SpawnBatchMem (any
 // number of records, in pinned host memory), the records of ONE block's lanes that are staged in LDS
-template <bool COMMIT, int NB = kAdmitRecs, class Batch = SpawnBatchT<NB>>
+template <bool COMMIT, int NB = kAdmitRecs, class Batch = SpawnBatchT<NB>, bool GT = false>
 __global__ __launch_bounds__(kBlock) void kr_admit(RingCtx cIn, int32_t *admitStep, int32_t *waitHead, VidTable vt, DevScalars *sc,
                                                    const Batch batch, const RingCommit k, const RingHaloIn hin) {
     constexpr bool kMem = std::is_same<Batch, SpawnBatchMem>::value;
@@ -647,7 +647,6 @@ __global__ __launch_bounds__(kBlock) void kr_admit(RingCtx cIn, int32_t *admitSt
     __shared__ int sAdmitted;
     __shared__ cfx_vehicle_template sT[kLdsTempl];
     __shared__ int sLane[NB];
-    const cfx_vehicle_template *tv = c.t.templ;
     const int nRecs = batch.n, firstNewVid = batch.firstNewVid;
     if (threadIdx.x == 0) sAdmitted = 0;
     if constexpr (kMem) {
@@ -657,17 +656,11 @@ __global__ __launch_bounds__(kBlock) void kr_admit(RingCtx cIn, int32_t *admitSt
     }
     // the lane of record j / the records this thread's lane can be found among
     auto laneOfRec = [&](int j) {
-        if constexpr (kMem) return j - b0 < NB ? sLane[j - b0] : batch.lane[j];
+        if constexpr (kMem) return j - b0 < NB ? ldsRead(&sLane[j - b0]) : batch.lane[j];
         else return sLane[j];
     };
     const int recLo = kMem ? b0 : 0, recHi = kMem ? b1 : nRecs;
-    if (c.t.nTempl <= kLdsTempl) {
-        const int nd = c.t.nTempl * (int) (sizeof(cfx_vehicle_template) / sizeof(double));
-        const double *src = (const double *) c.t.templ;
-        double *dst = (double *) sT;
-        for (int i = threadIdx.x; i < nd; i += blockDim.x) dst[i] = src[i];
-        tv = sT;
-    }
+    const cfx_vehicle_template *const tv = templatesOf<GT>(c.t, sT);
     if constexpr (!COMMIT) {
         // ---- round 1: everything that hangs on the drivable alone (a lane's ring position is requested whether or not it
         //      will admit: the kernel is bound by its longest chain of dependent loads, not by bytes)
@@ -929,6 +922,11 @@ __device__ inline Notified notifiedEagerFrom(const RingCtx &c, const cfx_vehicle
         b0 = c.blkR[w0];
         v0 = c.s.vid[w0];
     }
+    // WHO is notified is settled first, without a request of its own; then ONE request of the extras, for every lane whose
+    // vehicle is not the one whose extras came with the round above.  (Requested where each candidate is found — four places
+    // in divergent branches — a wavefront whose lanes sit on different crosses walked them one after the other, each with
+    // its own wait.)
+    bool found = false, extras = false;
     if (haveU) {
         const double vehDistance = a.uDis - tv[a.uTempl].len;
         const double crossDistance = a.llLen - x;
@@ -937,12 +935,11 @@ __device__ inline Notified notifiedEagerFrom(const RingCtx &c, const cfx_vehicle
             nf.templ = a.uTempl;
             nf.speed = a.uSpeed;
             nf.dist = -(a.uDis + crossDistance);
-            notifiedExtras(c, nf);
-            return nf;
+            found = extras = true;
         }
     }
-    if (haveOn) {
-        for (int q = 0; q < 2 && q < dyn.w; ++q) {  // the first two came with the round above
+    if (!found && haveOn) {
+        for (int q = 0; q < 2 && q < dyn.w && !found; ++q) {  // the first two came with the round above
             const double2 kw = q ? k1 : k0;
             const int4 mw = q ? m1 : m0;
             const double vehDistance = kw.x;
@@ -951,22 +948,22 @@ __device__ inline Notified notifiedEagerFrom(const RingCtx &c, const cfx_vehicle
                 nf.templ = mw.x;
                 nf.speed = kw.y;
                 nf.dist = x - vehDistance;
+                found = true;
                 if (q == 0) {
                     nf.enterLLT = mw.w;
                     nf.blk = b0;
                     nf.vid = v0;
                     nf.pre = true;
                 } else {
-                    notifiedExtras(c, nf);
+                    extras = true;
                 }
-                return nf;
             }
         }
-        for (int i = 2; i < dyn.w; i += 2) {  // two vehicles per round of loads (the walk stops at the first that matches)
+        for (int i = 2; i < dyn.w && !found; i += 2) {  // two vehicles per round of loads (the walk stops at the first that matches)
             const int x0 = walk.at(i), x1 = walk.at(i + 1 < dyn.w ? i + 1 : i);
             const double2 q0 = c.kin[x0], q1 = c.kin[x1];
             const int t0 = c.meta[x0].x, t1 = c.meta[x1].x;
-            for (int q = 0; q < 2 && i + q < dyn.w; ++q) {
+            for (int q = 0; q < 2 && i + q < dyn.w && !found; ++q) {
                 const int w = q ? x1 : x0;
                 const double2 kw = q ? q1 : q0;
                 const double vehDistance = kw.x;
@@ -976,19 +973,19 @@ __device__ inline Notified notifiedEagerFrom(const RingCtx &c, const cfx_vehicle
                     nf.templ = wt;
                     nf.speed = kw.y;
                     nf.dist = x - vehDistance;
-                    notifiedExtras(c, nf);
-                    return nf;
+                    found = extras = true;
                 }
             }
         }
     }
-    if (dyn.y >= 0) {
+    if (!found && dyn.y >= 0) {
         nf.slot = dyn.y;
         nf.templ = a.fTempl;
         nf.speed = a.fSpeed;
         nf.dist = (a.startLen - a.fDis) + x;
-        notifiedExtras(c, nf);
+        extras = true;
     }
+    if (extras) notifiedExtras(c, nf);
     return nf;
 }
 
@@ -1062,6 +1059,7 @@ struct RingPush {
 #else
 #define CFX_KR_ACTION_BOUNDS(B) __launch_bounds__(B)
 #endif
+template <bool GT = false>
 __global__ __launch_bounds__(kCrossBlock, CFX_KR_CROSS_WAVES) void kr_cross(RingCtx c, RingOut o, JobQueue q, const RingJob *recs, RingLights lights) {
     // (nothing in this kernel reads the lights: the approaching vehicles' light test is folded into llDyn by the action kernel.
     // They are advanced by the LAST blocks of the grid — the host sizes it with room to spare, so those have the fewest jobs)
@@ -1069,7 +1067,6 @@ __global__ __launch_bounds__(kCrossBlock, CFX_KR_CROSS_WAVES) void kr_cross(Ring
         passTimeAll(c.n, lights.curPhase, lights.remain, c.interval, ((int) gridDim.x - 1 - (int) blockIdx.x) * (int) blockDim.x + (int) threadIdx.x,
                     gridDim.x * blockDim.x);
     __shared__ cfx_vehicle_template sT[kLdsTempl];
-    const cfx_vehicle_template *tv = c.t.templ;
 #ifdef CFX_TRACE
     const int traceRow = 4096 + (int) blockIdx.x;
 #define XSTAMP(k) if (threadIdx.x == 0) g_trace[(size_t) traceRow * 8 + (k)] = (long long) wall_clock64()
@@ -1098,27 +1095,30 @@ __global__ __launch_bounds__(kCrossBlock, CFX_KR_CROSS_WAVES) void kr_cross(Ring
     // leave as soon as the count is there, the table's words requested before and stored behind that test, was measured:
     // kr_cross 16.5 against 16.1 us over 200 traced launches, the step 41.0 against 40.7 us in six alternated runs each,
     // profiles/cross_grid.txt — not kept.)
-    if (c.t.nTempl <= kLdsTempl) {
-        const int nd = c.t.nTempl * (int) (sizeof(cfx_vehicle_template) / sizeof(double));
-        const double *src = (const double *) c.t.templ;
-        double *dst = (double *) sT;
-        for (int i = threadIdx.x; i < nd; i += blockDim.x) dst[i] = src[i];
-        tv = sT;
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
+    const cfx_vehicle_template *const tv = templatesOf<GT>(c.t, sT);
+    if (blockIdx.x == 0 && threadIdx.x < 64) {
         // (sizes the next steps' grids, through the host mirror; and what this grid does to its groups: shard i has the
-        //  blocks i, i + 16, ... of the grid, and a group takes every (its blocks * 16)th job of the shard)
+        //  blocks i, i + 16, ... of the grid, and a group takes every (its blocks * 16)th job of the shard.
+        //  A lane per shard and a reduction over the lanes: one thread's loop over the shards was emitted as sixteen loads
+        //  each waited for by itself, with a division behind each, in front of the barrier of a block whose groups have jobs.)
+        static_assert(kJobShards <= 64 && (kJobShards & (kJobShards - 1)) == 0, "a lane of the first wavefront per shard");
+        const int i = (int) threadIdx.x;
         int nJ = 0, passes = 0;
-        for (int i = 0; i < kJobShards; ++i) {
-            const int n = min(q.count[i * kJobShardStride], q.capacity);
+        if (i < kJobShards) {
+            nJ = min(q.count[i * kJobShardStride], q.capacity);
             const int groupsOfShard = (((int) gridDim.x - i + kJobShards - 1) / kJobShards) * groupsPerBlock;
-            nJ += n;
-            if (groupsOfShard > 0) passes = max(passes, (n + groupsOfShard - 1) / groupsOfShard);
+            if (groupsOfShard > 0) passes = (nJ + groupsOfShard - 1) / groupsOfShard;
         }
-        o.sc->nCrossJobs = nJ;
-        o.sc->crossJobsStep = c.step;
-        if (passes > 1) atomicAdd(&o.sc->crossMultiPass, 1);  // (atomics whose result nobody reads: nothing waits for them)
-        atomicMax(&o.sc->crossMaxPasses, passes);
+        for (int off = kJobShards / 2; off > 0; off >>= 1) {
+            nJ += __shfl_xor(nJ, off, 64);
+            passes = max(passes, __shfl_xor(passes, off, 64));
+        }
+        if (i == 0) {
+            o.sc->nCrossJobs = nJ;
+            o.sc->crossJobsStep = c.step;
+            if (passes > 1) atomicAdd(&o.sc->crossMultiPass, 1);  // (atomics whose result nobody reads: nothing waits for them)
+            atomicMax(&o.sc->crossMaxPasses, passes);
+        }
     }
     __syncthreads();
     XSTAMP(1);
@@ -1154,8 +1154,12 @@ __global__ __launch_bounds__(kCrossBlock, CFX_KR_CROSS_WAVES) void kr_cross(Ring
             int foe = -1, foeVid = -2;
             double dOn = 0.0;
             if (e < jr.xe) {
-                const double2 dd = c.n.xDD[e];  // {distance on this laneLink, distance on the peer laneLink}
+                // ONE round for the cross's two records: the younger request is the one tested first, so its wait covers both,
+                // and no load moves across the fence behind them (left alone the compiler requests xPack only behind the
+                // `dOn < d0` test, under a wait of its own)
                 const int4 xp = c.n.xPack[e];   // {peer laneLink, peer bit, peer roadLink type, -}
+                const double2 dd = c.n.xDD[e];  // {distance on this laneLink, distance on the peer laneLink}
+                asm volatile("" ::: "memory");
                 dOn = dd.x;
                 // (a vehicle that can no longer yield passes whoever comes, Cross::canPass roadnet.cpp:617-618: tested in front
                 // of the notified vehicle's gathers)
@@ -1435,7 +1439,7 @@ __device__ inline void ringLaneHistory(const RingCtx &c, const LaneHistDev &h, i
     laneHistoryStep(h, lane, c.cnt[lane], [&](int i) { return c.kin[ringSlot(geo, head, i)].y; });
 }
 
-template <int B, bool GHOST = false>
+template <int B, bool GHOST = false, bool GT = false>
 __global__ CFX_KR_ACTION_BOUNDS(B) void kr_action(RingCtx c, RingOut o, JobQueue q, RingJob *jobRecs, int G, int nLaneBlocks, int nLLBlocks,
                                                              const RingHist rh) {
     const int w = (int) blockIdx.x, t = (int) threadIdx.x;
@@ -1456,7 +1460,6 @@ __global__ CFX_KR_ACTION_BOUNDS(B) void kr_action(RingCtx c, RingOut o, JobQueue
     __shared__ double sDis[B], sSpeed[B];
     __shared__ int sTempl[B];
     __shared__ int sWave[B / 64];
-    const cfx_vehicle_template *tv = c.t.templ;
     // ---- the block's drivables: G lanes, or B laneLinks
     const bool laneBlock = w < nLaneBlocks;
     const int g = laneBlock ? G : B;
@@ -1476,13 +1479,7 @@ __global__ CFX_KR_ACTION_BOUNDS(B) void kr_action(RingCtx c, RingOut o, JobQueue
         sGeo[t] = geo;
         sHead[t] = head;
     }
-    if (c.t.nTempl <= kLdsTempl) {
-        const int nd = c.t.nTempl * (int) (sizeof(cfx_vehicle_template) / sizeof(double));
-        const double *src = (const double *) c.t.templ;
-        double *dst = (double *) sT;
-        for (int i = t; i < nd; i += B) dst[i] = src[i];
-        tv = sT;
-    }
+    const cfx_vehicle_template *const tv = templatesOf<GT>(c.t, sT);
     // block-wide inclusive prefix sum of the counts
     int incl = n;
     for (int off = 1; off < 64; off <<= 1) {
@@ -1717,7 +1714,7 @@ __global__ __launch_bounds__(kIndexBlock) void kr_index(RingCtx c, unsigned long
 #endif
 constexpr int kListBlock = CFX_KL_BLOCK;
 #define CFX_KL_BOUNDS __launch_bounds__(kListBlock, CFX_KL_WAVES)  // (second argument: wavefronts per SIMD)
-template <bool GHOST = false>
+template <bool GHOST = false, bool GT = false>
 __global__ CFX_KL_BOUNDS void kl_action(RingCtx c, RingOut o, JobQueue q, RingJob *jobRecs, const int4 *list,
                                                     const int32_t *listCount, int nVehBlocks, int32_t *ticket, const RingHist rh) {
     const int w = (int) blockIdx.x, t = (int) threadIdx.x;
@@ -1735,15 +1732,8 @@ __global__ CFX_KL_BOUNDS void kl_action(RingCtx c, RingOut o, JobQueue q, RingJo
     int ls = 0;
     if ((t & 63) == 0 && qv > 0) ls = list[qv - 1].x;  // the vehicle ahead of the wavefront's first one, if it has a leader
     if (w * kListBlock >= total) return;
-    const cfx_vehicle_template *tv = c.t.templ;
-    if (c.t.nTempl <= kLdsTempl) {
-        const int nd = c.t.nTempl * (int) (sizeof(cfx_vehicle_template) / sizeof(double));
-        const double *src = (const double *) c.t.templ;
-        double *dst = (double *) sT;
-        for (int i = t; i < nd; i += kListBlock) dst[i] = src[i];
-        tv = sT;
-        __syncthreads();
-    }
+    const cfx_vehicle_template *const tv = templatesOf<GT>(c.t, sT);
+    if (!GT) __syncthreads();
     const bool valid = qv < total;
     const int lane = t & 63;
     const int slot = valid ? e.x : 0, d = e.y, idx = valid ? e.z : 0;
