@@ -828,6 +828,7 @@ struct cfx_engine {
     }
     // Device checkpoints of this engine that are still alive (cfx_checkpoint_create / _destroy): cfx_destroy takes their memory
     std::vector<cfx_checkpoint *> checkpoints;
+    DBuf<int32_t> envGather;  // cfx_checkpoint_restore_envs: the tables of the last call (kept: a search loop calls it every round)
     // Records that are valid "for the step in their tag" must not survive a change of the step counter (reset, load) or of
     // the slots they name (rebuilt rings); the occupancy bits are rebuilt by kr_scatter_in.
     int ringClearStepTags() {
@@ -3191,6 +3192,8 @@ int32_t cfx_checkpoint_save(cfx_engine *e, cfx_checkpoint *ck);
 int32_t cfx_checkpoint_restore(cfx_engine *e, cfx_checkpoint *ck);
 int32_t cfx_checkpoint_info(const cfx_checkpoint *ck, cfx_checkpoint_desc *out);
 void cfx_checkpoint_destroy(cfx_checkpoint *ck);
+int32_t cfx_checkpoint_restore_envs(cfx_engine *e, cfx_checkpoint *ck, const cfx_env_gather *g);
+static_assert(std::is_same<decltype(&cfx_checkpoint_restore_envs), cfx_checkpoint_restore_envs_fn>::value, "cfx_checkpoint_restore_envs");
 static_assert(std::is_same<decltype(&cfx_checkpoint_create), cfx_checkpoint_create_fn>::value, "cfx_checkpoint_create");
 static_assert(std::is_same<decltype(&cfx_checkpoint_save), cfx_checkpoint_save_fn>::value, "cfx_checkpoint_save");
 static_assert(std::is_same<decltype(&cfx_checkpoint_restore), cfx_checkpoint_restore_fn>::value, "cfx_checkpoint_restore");
@@ -3373,6 +3376,142 @@ int32_t cfx_checkpoint_restore(cfx_engine *e, cfx_checkpoint *ck) {
     e->futureCustom = ck->futureCustom;
     e->finishedKnown = sc.finishedCnt;
     e->finishedOffset = ck->finishedOffset;
+    if ((rc = e->ringFromDense())) return rc;
+    HIP_TRY(hipStreamSynchronize(e->stream));  // (`sc` lives on this frame)
+    return CFX_OK;
+}
+
+// cfx_checkpoint_restore with every environment taking another's state: the same reset, capacity checks, ring growth and
+// rebuild; the checkpoint's arrays come through the three k_env_gather_* kernels instead of the pack, and what the restore
+// takes from the checkpoint's host part is put together from the environments taken
+int32_t cfx_checkpoint_restore_envs(cfx_engine *e, cfx_checkpoint *ck, const cfx_env_gather *g) {
+    if (!e || !ck || !g) return CFX_ERR_INVALID;
+    auto fail = [e](const std::string &m) { return e->fail(m); };
+    if (ck->owner != e || !ck->saved) {
+        e->err = ck->owner != e ? "cfx_checkpoint_restore_envs: the checkpoint belongs to another engine" : "cfx_checkpoint_restore_envs: nothing was saved into the checkpoint";
+        return CFX_ERR_INVALID;
+    }
+    if (!e->ring || e->lc.on || e->tiled) return e->fail("cfx_checkpoint_restore_envs: the engine has left the ring layout"), CFX_ERR_STATE;
+    auto invalid = [e](const std::string &m) {
+        e->err = "cfx_checkpoint_restore_envs: " + m;
+        return CFX_ERR_INVALID;
+    };
+    // ---- the tables: nothing that is not checked here indexes device memory below
+    const int nE = e->cfg.n_envs > 1 ? e->cfg.n_envs : 1, nOld = ck->nV, nNew = g->n_new;
+    const int nRoutes = (int) e->hRouteStart.size() - 1;
+    if (g->n_envs != nE) return invalid("n_envs is not the engine's");
+    if (e->L % nE || e->K % nE || e->I % nE || nRoutes % nE) return invalid("the environments do not divide the network or the routes evenly");
+    if (g->n_old != nOld) return invalid("n_old is not the checkpoint's number of vehicle numbers");
+    if (nNew < 0 || !g->src_env || !g->env_first || (nOld && (!g->old_env || !g->old_local)) || (nNew && !g->new_src)) return invalid("a table is missing");
+    if (ck->finishedOffset != 0) {
+        e->err = "cfx_checkpoint_restore_envs: the checkpoint counts finished vehicles that are not in its vehicle table (a state loaded from an archive)";
+        return CFX_ERR_STATE;
+    }
+    const int Lpe = e->L / nE, Kpe = e->K / nE, Ipe = e->I / nE, L = e->L, D = e->D;
+    std::vector<int32_t> perEnv((size_t) nE, 0);
+    for (int o = 0; o < nOld; ++o) {
+        if (g->old_env[o] < 0 || g->old_env[o] >= nE || g->old_local[o] < 0) return invalid("old_env / old_local: entry out of range");
+        perEnv[(size_t) g->old_env[o]] += 1;
+    }
+    if (g->env_first[0] != 0 || g->env_first[nE] != nNew) return invalid("env_first does not span the new numbers");
+    for (int r = 0; r < nE; ++r) {
+        const int s = g->src_env[r];
+        if (s < 0 || s >= nE) return invalid("src_env: entry out of range");
+        if (g->env_first[r + 1] - g->env_first[r] != perEnv[(size_t) s]) return invalid("env_first: an environment's numbers are not its source's");
+        for (int v = g->env_first[r]; v < g->env_first[r + 1]; ++v) {
+            const int o = g->new_src[v];
+            if (o < 0 || o >= nOld || g->old_env[o] != s || g->old_local[o] != v - g->env_first[r]) return invalid("new_src does not match old_env / old_local");
+        }
+    }
+    // ---- per drivable: the vehicles after the call, where they start, and the two runs of every environment
+    auto srcDrv = [&](int d) { return d < L ? d + (g->src_env[d / Lpe] - d / Lpe) * Lpe : d + (g->src_env[(d - L) / Kpe] - (d - L) / Kpe) * Kpe; };
+    std::vector<int32_t> srcOff((size_t) D + 1, 0), cnt((size_t) D, 0), off((size_t) D + 1, 0);
+    for (int d = 0; d < D; ++d) srcOff[(size_t) d + 1] = srcOff[(size_t) d] + ck->cnt[(size_t) d];
+    if (srcOff[(size_t) D] != ck->nR) return e->fail("cfx_checkpoint_restore_envs: the checkpoint's counts do not add up (internal error)");
+    for (int d = 0; d < D; ++d) {
+        cnt[(size_t) d] = ck->cnt[(size_t) srcDrv(d)];
+        if ((int64_t) off[(size_t) d] + cnt[(size_t) d] > INT32_MAX) return e->fail("cfx_checkpoint_restore_envs: more than 2^31 running vehicles");
+        off[(size_t) d + 1] = off[(size_t) d] + cnt[(size_t) d];
+    }
+    const int nR = off[(size_t) D];
+    // one upload: srcEnv, envFirst, runDst, runSrc, oldLocal, newSrc, newEnv, then the counter of finished vehicles (8 bytes, aligned)
+    const size_t aSrcEnv = 0, aEnvFirst = aSrcEnv + nE, aRunDst = aEnvFirst + nE, aRunSrc = aRunDst + 2 * (size_t) nE + 1,
+                 aOldLocal = aRunSrc + 2 * (size_t) nE, aNewSrc = aOldLocal + (size_t) nOld, aNewEnv = aNewSrc + (size_t) nNew,
+                 aFinished = (aNewEnv + (size_t) nNew + 1) & ~(size_t) 1, nWords = aFinished + 2;
+    std::vector<int32_t> h(nWords, 0);
+    for (int r = 0; r < nE; ++r) {
+        const int s = g->src_env[r];
+        h[aSrcEnv + r] = s;
+        h[aEnvFirst + r] = g->env_first[r];
+        h[aRunDst + r] = off[(size_t) r * Lpe];
+        h[aRunDst + nE + r] = off[(size_t) L + (size_t) r * Kpe];
+        h[aRunSrc + r] = srcOff[(size_t) s * Lpe];
+        h[aRunSrc + nE + r] = srcOff[(size_t) L + (size_t) s * Kpe];
+        std::fill(h.begin() + aNewEnv + g->env_first[r], h.begin() + aNewEnv + g->env_first[r + 1], r);
+    }
+    h[aRunDst + 2 * (size_t) nE] = nR;
+    if (nOld) std::copy(g->old_local, g->old_local + nOld, h.begin() + aOldLocal);
+    if (nNew) std::copy(g->new_src, g->new_src + nNew, h.begin() + aNewSrc);
+
+    HIP_TRY(hipSetDevice(e->device));
+    int rc;
+    if ((rc = e->syncTables())) return rc;
+    if ((rc = e->resetState())) return rc;
+    if ((rc = e->ensureVidCap((size_t) nNew + 1))) return rc;
+    if ((rc = e->ringEnsure())) return rc;
+    if ((rc = e->ringFit(cnt.data(), "cfx_checkpoint_restore_envs"))) return rc;
+    if ((rc = e->ensureDense((size_t) nR))) return rc;
+    if (nWords > e->envGather.cap) {
+        const size_t nc = nWords + nWords / 4;
+        if ((rc = e->freeRaw(&e->envGather.p)) || (rc = e->allocRaw(&e->envGather.p, nc))) return rc;
+        e->envGather.cap = nc;
+    }
+    int32_t *t = e->envGather.p;
+    HIP_TRY(hipMemcpyAsync(t, h.data(), nWords * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipMemcpyAsync(e->rOff, off.data(), ((size_t) D + 1) * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
+    EnvGather eg{};
+    eg.nEnvs = nE, eg.lanesPerEnv = Lpe, eg.linksPerEnv = Kpe, eg.intersPerEnv = Ipe, eg.routesPerEnv = nRoutes / nE;
+    eg.nOld = nOld, eg.nNew = nNew;
+    eg.srcEnv = t + aSrcEnv, eg.envFirst = t + aEnvFirst, eg.oldLocal = t + aOldLocal, eg.newSrc = t + aNewSrc, eg.newEnv = t + aNewEnv;
+    eg.runDst = t + aRunDst, eg.runSrc = t + aRunSrc;
+    unsigned long long *dFinished = reinterpret_cast<unsigned long long *>(t + aFinished);
+    if (nR) hipLaunchKernelGGL(k_env_gather_running, dim3(gridFor((size_t) nR)), dim3(kBlock), 0, e->stream, eg, nR, ck->rd, e->rd, e->vt.gapState);
+    if (nNew) {
+        const EnvGatherTable src{ck->priority, ck->templ, ck->route, ck->nextWait, ck->enterTime, ck->customSpeed, ck->state, ck->pendingCustom};
+        hipLaunchKernelGGL(k_env_gather_table, dim3(gridFor((size_t) nNew)), dim3(kBlock), 0, e->stream, eg, src, e->vt, dFinished);
+    }
+    {
+        EnvGatherNet src{ck->waitHead, ck->curPhase, ck->remain, ck->hist};
+        LaneHistDev hist = e->hist;
+        if (!ck->hist.num) hist.num = nullptr;
+        hipLaunchKernelGGL(k_env_gather_net, dim3(gridFor((size_t) std::max(e->L, e->I))), dim3(kBlock), 0, e->stream, eg, src, e->waitHead, e->curPhase,
+                           e->remain, hist);
+    }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemsetD32Async((hipDeviceptr_t) e->vt.firstNext, kFirstNextUnknown, (size_t) std::max(nNew, 1), e->stream));  // (waiting vehicles: the walk)
+    unsigned long long finished = 0;
+    HIP_TRY(hipMemcpyAsync(&finished, dFinished, sizeof finished, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));  // (`h`, `off` and `finished` live on this frame)
+    DevScalars sc{};
+    sc.active = nR;
+    sc.finishedCnt = (long long) finished;
+    // (the travel-time sum and the vehicle steps are kept per engine, not per environment: the checkpoint's totals stand)
+    sc.cumulativeTravelTime = ck->sc.cumulativeTravelTime;
+    sc.vehicleSteps = ck->sc.vehicleSteps;
+    HIP_TRY(hipMemcpyAsync(e->sc, &sc, sizeof sc, hipMemcpyHostToDevice, e->stream));
+    e->cumLoaded = sc.cumulativeTravelTime;
+    e->timesDyadic = ck->timesDyadic;
+    e->step = ck->step;
+    e->spawned = nNew;
+    e->spawnedHere = nNew;
+    e->liveUpper = nR;
+    e->nQueueLanes = 0;
+    for (int l = 0; l < L; ++l) {
+        e->laneQueued[(size_t) l] = ck->laneQueued[(size_t) srcDrv(l)];
+        e->nQueueLanes += e->laneQueued[(size_t) l] ? 1 : 0;
+    }
+    e->finishedKnown = sc.finishedCnt;
+    e->finishedOffset = 0;
     if ((rc = e->ringFromDense())) return rc;
     HIP_TRY(hipStreamSynchronize(e->stream));  // (`sc` lives on this frame)
     return CFX_OK;

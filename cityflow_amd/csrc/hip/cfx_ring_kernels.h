@@ -2253,6 +2253,124 @@ __global__ void k_checkpoint_state_gap(int n, const int32_t *vid, const double *
     flags[i] = (uint8_t) ((flags[i] & kFlagCustom) | kFlagStateGap);
 }
 
+// cfx_checkpoint_restore_envs: environment r of a batched engine (cfx_config::n_envs) takes the state that environment
+// srcEnv[r] has in the checkpoint.  The environments are disjoint copies of one network, so everything an environment owns is a
+// range of every index space — lanes [r * lanesPerEnv ...), laneLinks, intersections, routes — and a value that names one moves
+// by (r - srcEnv[r]) times the range's length.  Vehicle numbers do not form ranges (a step's batch numbers the environments'
+// newcomers one after the other), and a state that is taken twice needs two sets of them: the host numbers the vehicles anew,
+// destination by destination, and brings per new number the checkpoint's number it copies (newSrc) and its environment (newEnv),
+// per checkpoint number its number within its environment (oldLocal) and per environment its first new number (envFirst); a
+// number v of the source environment is envFirst[r] + oldLocal[v] in destination r.
+struct EnvGather {
+    int nEnvs, lanesPerEnv, linksPerEnv, intersPerEnv, routesPerEnv;
+    int nOld, nNew;           // vehicle numbers of the checkpoint / after the call
+    const int32_t *srcEnv;    // [nEnvs]
+    const int32_t *envFirst;  // [nEnvs]
+    const int32_t *oldLocal;  // [nOld]
+    const int32_t *newSrc;    // [nNew]
+    const int32_t *newEnv;    // [nNew]
+    // the running vehicles lie by drivable — every environment's lanes, then every environment's laneLinks — so an environment
+    // owns two runs of them: run c < nEnvs the lanes of environment c, run nEnvs + c its laneLinks
+    const int32_t *runDst;    // [2 nEnvs + 1] where the runs start after the call (the last: the number of running vehicles)
+    const int32_t *runSrc;    // [2 nEnvs] where run c's source starts in the checkpoint
+};
+__device__ __forceinline__ int envGatherVid(const EnvGather &g, int v, int env) {
+    return (unsigned) v < (unsigned) g.nOld ? g.envFirst[env] + g.oldLocal[v] : -1;
+}
+
+// ... the running vehicles, one thread each: the record's loads together, then the two number lookups together.  Takes
+// k_checkpoint_state_gap's part along (the first step's gap is the state's; the custom-speed bit stays).
+__global__ void __launch_bounds__(kBlock) k_env_gather_running(EnvGather g, int n, RingDense src, RingDense dst, double *gapState) {
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n) return;
+    int lo = 0, hi = 2 * g.nEnvs;  // runDst[lo] <= j < runDst[hi]; an empty run is never the last one that starts at or before j
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (g.runDst[mid] <= j) lo = mid;
+        else hi = mid;
+    }
+    const int env = lo < g.nEnvs ? lo : lo - g.nEnvs, delta = env - g.srcEnv[env];
+    const int i = g.runSrc[lo] + (j - g.runDst[lo]);
+    const int vid = src.vid[i], prevDrv = src.prevDrv[i], blocker = src.blockerVid[i], enterLLT = src.enterLLT[i], routePos = src.routePos[i];
+    const uint8_t flags = src.flags[i];
+    const double dis = src.dis[i], speed = src.speed[i], gap = src.gap[i];
+    const int newVid = envGatherVid(g, vid, env), newBlocker = envGatherVid(g, blocker, env);
+    const int nLanes = g.nEnvs * g.lanesPerEnv;
+    dst.vid[j] = newVid;
+    dst.prevDrv[j] = prevDrv < 0 ? prevDrv : prevDrv + delta * (prevDrv < nLanes ? g.lanesPerEnv : g.linksPerEnv);
+    dst.blockerVid[j] = newBlocker;
+    dst.enterLLT[j] = enterLLT;
+    dst.routePos[j] = routePos;
+    dst.flags[j] = (uint8_t) ((flags & kFlagCustom) | kFlagStateGap);
+    dst.dis[j] = dis;
+    dst.speed[j] = speed;
+    dst.gap[j] = gap;
+    if ((unsigned) newVid < (unsigned) g.nNew) gapState[newVid] = gap;
+}
+
+// ... the vehicle table, one thread per new number; the finished vehicles are counted on the way (the engine-wide count is the
+// sum over the environments taken, not the checkpoint's): one atomic per wavefront
+struct EnvGatherTable {
+    const int32_t *priority, *templ, *route, *nextWait;
+    const double *enterTime, *customSpeed;
+    const uint8_t *state, *pendingCustom;
+};
+__global__ void __launch_bounds__(kBlock) k_env_gather_table(EnvGather g, EnvGatherTable src, VidTable dst, unsigned long long *finished) {
+    const int v = blockIdx.x * blockDim.x + threadIdx.x;
+    bool fin = false;
+    if (v < g.nNew) {
+        const int o = g.newSrc[v], env = g.newEnv[v];
+        if ((unsigned) o < (unsigned) g.nOld && (unsigned) env < (unsigned) g.nEnvs) {
+            const int delta = env - g.srcEnv[env];
+            const int priority = src.priority[o], templ = src.templ[o], route = src.route[o], nextWait = src.nextWait[o];
+            const double enterTime = src.enterTime[o], customSpeed = src.customSpeed[o];
+            const uint8_t state = src.state[o], pendingCustom = src.pendingCustom[o];
+            dst.priority[v] = priority;
+            dst.templ[v] = templ;
+            dst.route[v] = route < 0 ? route : route + delta * g.routesPerEnv;
+            dst.nextWait[v] = envGatherVid(g, nextWait, env);
+            dst.enterTime[v] = enterTime;
+            dst.customSpeed[v] = customSpeed;
+            dst.state[v] = state;
+            dst.pendingCustom[v] = pendingCustom;
+            fin = state == 2;
+        }
+    }
+    const unsigned long long m = __ballot(fin);
+    if (m && (threadIdx.x & 63) == 0) atomicAdd(finished, (unsigned long long) __popcll(m));
+}
+
+// ... what the network carries, one thread per lane and per intersection: the entry buffers' heads (vehicle numbers), the
+// lights' phases and remaining times, and Lane::history where the engine keeps it (record-major: a record's lanes are adjacent)
+struct EnvGatherNet {
+    const int32_t *waitHead, *curPhase;
+    const double *remain;
+    LaneHistDev hist;  // (num == nullptr: not kept)
+};
+__global__ void __launch_bounds__(kBlock) k_env_gather_net(EnvGather g, EnvGatherNet src, int32_t *waitHead, int32_t *curPhase, double *remain,
+                                                           LaneHistDev hist) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    const int nLanes = g.nEnvs * g.lanesPerEnv, nInters = g.nEnvs * g.intersPerEnv;
+    if (t < nInters) {
+        const int env = t / g.intersPerEnv, s = t + (g.srcEnv[env] - env) * g.intersPerEnv;
+        curPhase[t] = src.curPhase[s];
+        remain[t] = src.remain[s];
+    }
+    if (t >= nLanes) return;
+    const int env = t / g.lanesPerEnv, s = t + (g.srcEnv[env] - env) * g.lanesPerEnv;
+    waitHead[t] = envGatherVid(g, src.waitHead[s], env);
+    if (!hist.num || !src.hist.num) return;
+    hist.head[t] = src.hist.head[s];
+    hist.len[t] = src.hist.len[s];
+    hist.hNum[t] = src.hist.hNum[s];
+    hist.hAvg[t] = src.hist.hAvg[s];
+#pragma unroll 8
+    for (int m = 0; m < kLaneHistoryMax; ++m) {
+        hist.num[(size_t) m * nLanes + t] = src.hist.num[(size_t) m * nLanes + s];
+        hist.avg[(size_t) m * nLanes + t] = src.hist.avg[(size_t) m * nLanes + s];
+    }
+}
+
 __global__ void kr_reset(int D, int32_t *head, int32_t *cnt, int4 *scratch) {
     const int d = blockIdx.x * blockDim.x + threadIdx.x;
     if (d >= D) return;

@@ -124,6 +124,7 @@ void Backend::open(const std::string &libPath) {
     CFX_FN_OPTIONAL(cfx_checkpoint_restore)
     CFX_FN_OPTIONAL(cfx_checkpoint_info)
     CFX_FN_OPTIONAL(cfx_checkpoint_destroy)
+    CFX_FN_OPTIONAL(cfx_checkpoint_restore_envs)
 #undef CFX_FN_OPTIONAL
     if (cfx_abi_version() != CFX_ABI_VERSION)
         throw std::runtime_error("cityflow_amd: ABI version mismatch in '" + libPath + "'");

@@ -124,6 +124,7 @@ struct Backend {
     cfx_checkpoint_restore_fn cfx_checkpoint_restore = nullptr;
     cfx_checkpoint_info_fn cfx_checkpoint_info = nullptr;
     cfx_checkpoint_destroy_fn cfx_checkpoint_destroy = nullptr;
+    cfx_checkpoint_restore_envs_fn cfx_checkpoint_restore_envs = nullptr;  // (optional beside them: VectorEngine::rollback(ck, envs))
     bool hasCheckpoints() const {
         return cfx_checkpoint_create && cfx_checkpoint_save && cfx_checkpoint_restore && cfx_checkpoint_info && cfx_checkpoint_destroy;
     }

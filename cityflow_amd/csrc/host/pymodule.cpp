@@ -1004,6 +1004,25 @@ PYBIND11_MODULE(_cityflow, m) {
             return d;
         });
     defDeviceBuffers(vectorClass);
+    vectorClass
+        .def("_rollback_envs", &VectorEngineHost::rollbackEnvs, "checkpoint"_a, "envs"_a,
+             "_rollback with environment r taking the state of environment envs[r] (num_envs ints in [0, num_envs))")
+        .def("_keeps_lane_history", &VectorEngineHost::keepsLaneHistory)
+        .def("_ring_info", &VectorEngineHost::ringInfo, "(total ring slots, capacity scale) of the ring layout")
+        .def("_lane_history",
+             [](VectorEngineHost &e, int env) {  // test hook: cfx_get_lane_history, one environment's lanes; as Engine._lane_history
+                 std::vector<int32_t> len, num, hn;
+                 std::vector<double> avg, ha;
+                 e.laneHistory(env, len, num, avg, hn, ha);
+                 py::dict d;
+                 d["len"] = toArray(len);
+                 d["vehicle_num"] = toArray(num);
+                 d["average_speed"] = toArray(avg);
+                 d["history_vehicle_num"] = toArray(hn);
+                 d["history_average_speed"] = toArray(ha);
+                 return d;
+             },
+             "env"_a);
     vectorClass.def("_intersection_features", [](VectorEngineHost &e) { return intersectionFeaturesTuple(e, e.numEnvs()); },
                     "(phase, remain, in, in_waiting, out, inside, phase_pressure), flat, env-major");
 

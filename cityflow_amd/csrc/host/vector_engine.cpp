@@ -152,6 +152,7 @@ VectorEngineHost::VectorEngineHost(const std::string &configFile, int numEnvs, i
     cfx_config cc{};
     cfg.apply(cc);
     cc.n_envs = R_;  // (lane change: every environment has its own schedule walk and priority stream)
+    laneHistory_ = cc.lane_history != 0;
     int32_t rc = be_.cfx_create(&rn.flat, &cc, &dev_);
     if (rc != CFX_OK || !dev_) {
         const char *msg = be_.cfx_last_error(nullptr);
@@ -596,24 +597,77 @@ std::shared_ptr<DeviceCheckpoint> VectorEngineHost::checkpoint(std::shared_ptr<D
     return ck;
 }
 
-void VectorEngineHost::rollback(DeviceCheckpoint &ck) {
+void VectorEngineHost::rollbackTo(DeviceCheckpoint &ck, const std::vector<int32_t> *envs) {
     const std::string why = checkpointUnsupported();
     if (!why.empty()) throw std::logic_error("rollback: " + why);
+    if (envs && !be_.cfx_checkpoint_restore_envs)
+        throw std::logic_error("rollback: the backend '" + backendName() + "' cannot roll back with an environment map (envs=)");
     DeviceCheckpoint::checkUsable(&ck, this, "rollback");
     if (ck.host.size() != (size_t) R_) throw std::invalid_argument("rollback: nothing was saved into the checkpoint");
+    if (envs) {
+        if (envs->size() != (size_t) R_) throw std::invalid_argument("rollback: envs must hold num_envs = " + std::to_string(R_) + " entries");
+        for (size_t r = 0; r < envs->size(); ++r)
+            if ((*envs)[r] < 0 || (*envs)[r] >= R_)
+                throw std::invalid_argument("rollback: envs[" + std::to_string(r) + "] = " + std::to_string((*envs)[r]) + " is not an environment");
+    }
     dropAhead();
     settleLaneChange();
+    // the new numbering of a gathered rollback: environment by environment, each environment's vehicles in its source's order
+    std::vector<int32_t> envFirst, oldEnv, oldLocal, newSrc;
+    if (envs) {
+        const size_t nOld = ck.globalToLocal.size();
+        oldEnv.resize(nOld);
+        oldLocal.resize(nOld);
+        for (size_t g = 0; g < nOld; ++g) {
+            oldEnv[g] = ck.globalToLocal[g].first;
+            oldLocal[g] = ck.globalToLocal[g].second;
+        }
+        envFirst.assign((size_t) R_ + 1, 0);
+        for (int r = 0; r < R_; ++r) {
+            const std::vector<int32_t> &src = ck.localToGlobal[(size_t) (*envs)[(size_t) r]];
+            if ((size_t) envFirst[(size_t) r] + src.size() > (size_t) INT32_MAX) throw std::runtime_error("rollback: more than 2^31 vehicle numbers");
+            envFirst[(size_t) r + 1] = envFirst[(size_t) r] + (int32_t) src.size();
+            newSrc.insert(newSrc.end(), src.begin(), src.end());
+        }
+    }
     {
         std::lock_guard<std::mutex> guard(queryMutex_);
         if (devicePhaseUnchecked_ || plan_.unchecked()) {  // (... and not lost in a rollback)
             check(be_.cfx_sync(dev_), "cfx_sync");
             raiseDeviceError();
         }
-        check(be_.cfx_checkpoint_restore(dev_, ck.ck), "cfx_checkpoint_restore");
+        if (!envs) {
+            check(be_.cfx_checkpoint_restore(dev_, ck.ck), "cfx_checkpoint_restore");
+        } else {
+            cfx_env_gather g{};
+            g.n_envs = R_;
+            g.src_env = envs->data();
+            g.env_first = envFirst.data();
+            g.n_old = (int32_t) oldEnv.size();
+            g.old_env = oldEnv.data();
+            g.old_local = oldLocal.data();
+            g.n_new = envFirst[(size_t) R_];
+            g.new_src = newSrc.data();
+            check(be_.cfx_checkpoint_restore_envs(dev_, ck.ck, &g), "cfx_checkpoint_restore_envs");
+        }
     }
-    for (int r = 0; r < R_; ++r) spawners_[(size_t) r]->loadState(ck.host[(size_t) r]);
-    localToGlobal_ = ck.localToGlobal;
-    globalToLocal_ = ck.globalToLocal;
+    if (!envs) {
+        for (int r = 0; r < R_; ++r) spawners_[(size_t) r]->loadState(ck.host[(size_t) r]);
+        localToGlobal_ = ck.localToGlobal;
+        globalToLocal_ = ck.globalToLocal;
+    } else {
+        globalToLocal_.resize((size_t) envFirst[(size_t) R_]);
+        for (int r = 0; r < R_; ++r) {
+            spawners_[(size_t) r]->loadState(ck.host[(size_t) (*envs)[(size_t) r]]);
+            const int32_t first = envFirst[(size_t) r], n = envFirst[(size_t) r + 1] - first;
+            std::vector<int32_t> &l2g = localToGlobal_[(size_t) r];
+            l2g.resize((size_t) n);
+            for (int32_t k = 0; k < n; ++k) {
+                l2g[(size_t) k] = first + k;
+                globalToLocal_[(size_t) (first + k)] = std::make_pair((int32_t) r, k);
+            }
+        }
+    }
     step_ = ck.step;
     {
         std::lock_guard<std::mutex> guard(queryMutex_);
@@ -626,6 +680,25 @@ void VectorEngineHost::rollback(DeviceCheckpoint &ck) {
         });
     }
     submitted_.store((uint64_t) step_, std::memory_order_release);
+}
+
+void VectorEngineHost::laneHistory(int env, std::vector<int32_t> &len, std::vector<int32_t> &vehicleNum, std::vector<double> &averageSpeed,
+                                   std::vector<int32_t> &historyVehicleNum, std::vector<double> &historyAverageSpeed) {
+    if (env < 0 || env >= R_) throw std::out_of_range("env index out of range");
+    const size_t nL = (size_t) R_ * L_, M = CFX_LANE_HISTORY_MAX;
+    std::vector<int32_t> allLen(nL, 0), allNum(nL * M, 0), allHn(nL, 0);
+    std::vector<double> allAvg(nL * M, 0.0), allHa(nL, 0.0);
+    cfx_lane_history h{(int32_t) nL, allLen.data(), allNum.data(), allAvg.data(), allHn.data(), allHa.data()};
+    {
+        std::lock_guard<std::mutex> guard(queryMutex_);
+        check(be_.cfx_get_lane_history(dev_, &h), "cfx_get_lane_history");
+    }
+    const size_t lo = (size_t) env * L_, hi = lo + (size_t) L_;
+    len.assign(allLen.begin() + lo, allLen.begin() + hi);
+    vehicleNum.assign(allNum.begin() + lo * M, allNum.begin() + hi * M);
+    averageSpeed.assign(allAvg.begin() + lo * M, allAvg.begin() + hi * M);
+    historyVehicleNum.assign(allHn.begin() + lo, allHn.begin() + hi);
+    historyAverageSpeed.assign(allHa.begin() + lo, allHa.begin() + hi);
 }
 
 std::vector<int32_t> VectorEngineHost::laneVehicleCounts() {

@@ -39,7 +39,22 @@ public:
     bool checkpointCalls() const { return be_.hasCheckpoints(); }
     std::string checkpointUnsupported();
     std::shared_ptr<DeviceCheckpoint> checkpoint(std::shared_ptr<DeviceCheckpoint> into);
-    void rollback(DeviceCheckpoint &ck);
+    void rollback(DeviceCheckpoint &ck) { rollbackTo(ck, nullptr); }
+    // ... with environment r taking the state that environment envs[r] has in the checkpoint (repeats allowed; an environment
+    // named nowhere is dropped): its vehicles, entry buffers, lights, Lane::history and its spawner's state, generator included.
+    // The vehicles are numbered anew, environment by environment.
+    void rollbackEnvs(DeviceCheckpoint &ck, const std::vector<int32_t> &envs) { rollbackTo(ck, &envs); }
+    // Lane::history of one environment as the device keeps it ("cfx": {"laneHistory": true}; EngineHost::laneHistory)
+    bool keepsLaneHistory() const { return laneHistory_; }
+    std::pair<int64_t, int> ringInfo() {  // (total ring slots, capacity scale) of the ring layout, as EngineHost::ringInfo
+        std::lock_guard<std::mutex> guard(queryMutex_);
+        int64_t slots = 0;
+        int32_t scale = 1;
+        be_.cfx_get_ring_info(dev_, &slots, &scale);
+        return {slots, scale};
+    }
+    void laneHistory(int env, std::vector<int32_t> &len, std::vector<int32_t> &vehicleNum, std::vector<double> &averageSpeed,
+                     std::vector<int32_t> &historyVehicleNum, std::vector<double> &historyAverageSpeed);
     double getCurrentTime() const { return step_ * interval_; }
     std::vector<int32_t> laneVehicleCounts();         // [R * L], env-major
     std::vector<int32_t> laneWaitingVehicleCounts();  // [R * L]
@@ -108,6 +123,8 @@ public:
 
 private:
     void check(int32_t rc, const char *what);
+    void rollbackTo(DeviceCheckpoint &ck, const std::vector<int32_t> *envs);  // (envs null: every environment its own state)
+    bool laneHistory_ = false;
     std::unique_ptr<InterLayout> interLayout_;  // built by the first call that needs it
     Trackers trackers_;                  // (every call with queryMutex_ held: it asks the device)
     bool devicePhaseUnchecked_ = false;  // as EngineHost: read by every call below that has waited for the device

@@ -778,10 +778,64 @@ def rollback(self, checkpoint):
     self._rollback(checkpoint)
 
 
+def _env_map(envs, num_envs):
+    """`envs` of VectorEngine.rollback as a list of ints: the type of every entry first, then the length, then the range."""
+    import numbers
+
+    device = getattr(envs, "device", None)
+    if device is not None and getattr(device, "type", "cpu") != "cpu":
+        raise TypeError("rollback: envs is a host argument (the spawners' states are copied by it) and a tensor on %s would be "
+                        "read with a silent wait for the device: pass envs.tolist()" % (device,))
+    if hasattr(envs, "tolist"):  # (numpy array, CPU tensor: Python scalars from here on)
+        envs = envs.tolist()
+    if isinstance(envs, (str, bytes)) or not hasattr(envs, "__len__") or not hasattr(envs, "__iter__"):
+        raise TypeError("rollback: envs must be a sequence of num_envs ints, not %s" % type(envs).__name__)
+    envs = list(envs)
+    for r, s in enumerate(envs):
+        if isinstance(s, bool) or type(s).__name__ == "bool_" or not isinstance(s, numbers.Integral):
+            raise TypeError("rollback: envs[%d] = %r is not an integer" % (r, s))
+    if len(envs) != num_envs:
+        raise ValueError("rollback: envs must hold num_envs = %d entries, not %d" % (num_envs, len(envs)))
+    for r, s in enumerate(envs):
+        if not 0 <= s < num_envs:
+            raise ValueError("rollback: envs[%d] = %d is not an environment (position %d; valid: 0 .. %d)" % (r, s, r, num_envs - 1))
+    return [int(s) for s in envs]
+
+
+def rollback_envs(self, checkpoint, envs=None):
+    """rollback(checkpoint) of a VectorEngine, with `envs` a gathered one: afterwards environment r is in the state that
+    environment envs[r] had when `checkpoint` was saved.  `envs`: a sequence or integer numpy array (or CPU tensor) of num_envs
+    values in [0, num_envs); repeats are allowed, an environment named nowhere is dropped — "keep the best k, continue all R from
+    them".  envs=None is the plain rollback, on its own code path.
+
+    Environment r takes from envs[r]: its running vehicles (position, speed, place in the route, the leader and gap of the first
+    step, a custom speed and its pending flag), its entry buffers in queue order, every intersection's phase and remaining time,
+    Lane::history where the engine keeps it, and its spawner's state with the mt19937 — so r continues bit for bit as envs[r]
+    would have, with per-environment seeds as with equal ones.  The durations set by set_tl_plan_tensor stay slot r's own, as in
+    a plain rollback: replicate the survivors' states, then give every slot its next candidate plan.  As in a plain rollback the
+    trackers take a new baseline and stay on, pending set_tl_phases calls are dropped and the step becomes the checkpoint's.  The
+    engine-wide counts of running and finished vehicles are those of the environments taken; _scalars()'s cumulative_travel_time
+    and vehicle_steps, which nothing splits by environment, stay the checkpoint's totals (per-environment travel times are
+    track_trips').  Vehicle ids stay the source's (two slots that took one state hold vehicles of the same ids).
+
+    The checkpoint is neither consumed nor modified: any number of maps, and envs=None afterwards.  `envs` is a host argument
+    (the spawners' states are copied on the host): a tensor on a device is a TypeError that says to pass .tolist(); nothing here
+    waits for the device unseen.  Checked first, in this order: an entry that is not an integer (bools included) TypeError, a
+    wrong length ValueError, an entry out of range ValueError naming the position; then rollback's own checks."""
+    if envs is None:
+        return rollback(self, checkpoint)
+    envs = _env_map(envs, self.num_envs)
+    _need_checkpoint_calls(self, "rollback")
+    self._rollback_envs(checkpoint, envs)
+
+
+rollback_envs.__name__ = rollback_envs.__qualname__ = "rollback"  # (VectorEngine.rollback)
+
+
 def install(*classes):
     for cls in classes:
         cls.checkpoint = checkpoint
-        cls.rollback = rollback
+        cls.rollback = rollback_envs if hasattr(cls, "_rollback_envs") else rollback
         cls.set_tl_plan_tensor = set_tl_plan_tensor
         cls.get_tl_phase_durations_tensor = get_tl_phase_durations_tensor
         cls.set_tl_plan = set_tl_plan

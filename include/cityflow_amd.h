@@ -852,6 +852,33 @@ typedef int32_t (*cfx_checkpoint_restore_fn)(cfx_engine *e, cfx_checkpoint *ck);
 typedef int32_t (*cfx_checkpoint_info_fn)(const cfx_checkpoint *ck, cfx_checkpoint_desc *out);
 typedef void (*cfx_checkpoint_destroy_fn)(cfx_checkpoint *ck);
 
+/* ---- "cfx_checkpoint_restore_envs" (OPTIONAL, and only beside the five above): cfx_checkpoint_restore on an engine of
+ * cfx_config::n_envs environments, with environment r taking the state that environment src_env[r] has in ck.  Repeats are
+ * allowed; an environment named nowhere is dropped.  Everything an environment owns moves with it: its running vehicles, entry
+ * buffers, lights (phase and remaining time) and Lane::history; lane, laneLink, intersection and route indices are shifted by
+ * (r - src_env[r]) times the per-environment counts.  Vehicle numbers are the caller's to hand out, because a state taken twice
+ * needs two sets of them: after the call environment r owns the numbers env_first[r] .. env_first[r + 1] - 1, and number
+ * env_first[r] + k is the vehicle that ck knows as the k-th of environment src_env[r]:
+ *   old_env[o], old_local[o]   for every vehicle number o of ck: its environment, and its rank k among that environment's numbers
+ *   new_src[v]                 for every number v after the call: the number of ck that it copies
+ * The tables are checked against each other (CFX_ERR_INVALID; nothing has happened then).  The engine-wide counts of running and
+ * finished vehicles, the per-drivable counts the rings are fitted to and the lanes that may admit are those of the environments
+ * taken; cfx_scalars::cumulative_travel_time and ::vehicle_steps, which no record splits by environment, stay the totals of ck.
+ * Speeds set for vehicles that do not exist yet (cfx_set_vehicle_speed) are dropped.  ck is not consumed and not modified.
+ * Returns CFX_ERR_STATE / CFX_ERR_INVALID where cfx_checkpoint_restore does, CFX_ERR_STATE also for a ck that counts finished
+ * vehicles outside its vehicle table (a state that came from cfx_load_state with such a count). */
+typedef struct cfx_env_gather {
+    int32_t n_envs;           /* cfx_config::n_envs of the engine */
+    const int32_t *src_env;   /* [n_envs] */
+    const int32_t *env_first; /* [n_envs + 1], env_first[0] = 0, env_first[n_envs] = n_new */
+    int32_t n_old;            /* cfx_checkpoint_desc::n_vehicles of ck */
+    const int32_t *old_env;   /* [n_old] */
+    const int32_t *old_local; /* [n_old] */
+    int32_t n_new;
+    const int32_t *new_src;   /* [n_new] */
+} cfx_env_gather;
+typedef int32_t (*cfx_checkpoint_restore_envs_fn)(cfx_engine *e, cfx_checkpoint *ck, const cfx_env_gather *g);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,18 +1,27 @@
 """What checkpoint() / rollback() cost beside snapshot() / load(), and what they buy a rollout loop.
 
-  python tools/checkpoint_loop.py [--which bench|6x6|vector|all] [--repeats 5] [--rollout-steps 300] [--candidates 3]
+  python tools/checkpoint_loop.py [--which bench|6x6|vector|vector16|all] [--repeats 5] [--rollout-steps 300] [--candidates 3]
       bench   the benchmark workload (bench.build_workload: 30x30, ~96 k running vehicles after bench.BUILD_UP_STEPS steps,
               Lane::history on)
       6x6     the stock grid_6x6 after 300 steps
       vector  a 64-environment grid_6x6 VectorEngine after 300 steps (no snapshot / load there: absolute times only)
+      vector16  the same with 16 environments
       Per workload: checkpoint() + rollback() + sync() and snapshot() + load() + sync() timed as pairs, alternating in the same
       process after a warm-up of each, `repeats` times, median / min / max printed with device_bytes; then a rollout of
       `rollout-steps` steps per candidate in the form "checkpoint once, roll back per candidate" against rebuilding the state
       from step 0 (reset(True) and the steps up to it) for every candidate.  The two forms must end in the same state.
+      A VectorEngine also gets rollback(ck), rollback(ck, envs=identity) and rollback(ck, envs=the 8 environments with the
+      fewest vehicles, tiled over the slots), each ending in sync(), timed in turn in every repeat after a warm-up of each;
+      then "continue every slot from the 8 survivors": the gathered rollback and `rollout-steps` steps, beside the rollout
+      rebuilt from step 0 above.
 
   python tools/checkpoint_loop.py --trace [--iters 20]
       the workload for a `rocprofv3 --kernel-trace --stats` run of its own: `iters` checkpoint(into=) + rollback() pairs on the
-      benchmark workload (k_pack_segments, kr_gather, kr_offsets, kr_scatter_in, k_checkpoint_state_gap)."""
+      benchmark workload (k_pack_segments, kr_gather, kr_offsets, kr_scatter_in, k_checkpoint_state_gap).
+
+  python tools/checkpoint_loop.py --trace-envs [--iters 20] [--envs 64]
+      the same for rollback(ck, envs=the 8 survivors tiled) on the 64-environment VectorEngine (k_env_gather_running,
+      k_env_gather_table, k_env_gather_net, kr_scatter_in)."""
 import argparse
 import os
 import statistics
@@ -99,6 +108,46 @@ def rollouts(eng, ck, steps_before, rollout_steps, candidates):
     spread("... rebuilt from step 0 (%d + %d steps)" % (steps_before, rollout_steps), from_zero)
 
 
+def survivors(eng, k=8):
+    """envs of "keep the k environments with the fewest vehicles, continue every slot from them": the k tiled over the slots."""
+    import numpy as np
+    per_env = eng.get_lane_vehicle_count_array().sum(axis=1)
+    best = np.argsort(per_env, kind="stable")[:k]
+    return [int(best[r % len(best)]) for r in range(eng.num_envs)]
+
+
+def gathered(eng, ck, repeats, rollout_steps):
+    import inspect
+    R = eng.num_envs
+    eng.rollback(ck)
+    identity, top = list(range(R)), survivors(eng)
+    forms = (("rollback(ck) + sync()", None), ("rollback(ck, envs=identity) + sync()", identity),
+             ("rollback(ck, envs=8 survivors tiled) + sync()", top))
+    if "envs" not in inspect.signature(type(eng).rollback).parameters:  # (this tool beside an older build, for the A/B of the plain call)
+        forms = forms[:1]
+    times = {name: [] for name, _ in forms}
+    for warm in (True, False):
+        for _ in range(1 if warm else repeats):
+            for name, envs in forms:
+                t = timed(lambda: (eng.rollback(ck) if envs is None else eng.rollback(ck, envs=envs), eng.sync()))
+                if not warm:
+                    times[name].append(t)
+    for name, _ in forms:
+        spread(name, times[name])
+    cont = []
+    for _ in range(max(repeats // 2, 2) if len(forms) > 1 else 0):
+        def a():
+            eng.rollback(ck, envs=top)
+            for _ in range(rollout_steps):
+                eng.next_step()
+            eng.sync()
+        cont.append(timed(a))
+    if cont:
+        spread("every slot continued from the 8 survivors, %d steps" % rollout_steps, cont)
+    eng.rollback(ck)
+    eng.sync()
+
+
 def workload(which, work):
     if which == "bench":
         eng = cityflow_amd.Engine(bench.build_workload(work, 0, scenario="grid_30x30"), 1)
@@ -106,12 +155,12 @@ def workload(which, work):
     cfg = scenarios.materialize("grid_6x6", work)
     if which == "6x6":
         return cityflow_amd.Engine(cfg, 1), 300, True
-    return cityflow_amd.VectorEngine(cfg, 64, 1), 300, False
+    return cityflow_amd.VectorEngine(cfg, 16 if which == "vector16" else 64, 1), 300, False
 
 
 def measure(args):
     work = tempfile.mkdtemp(prefix="checkpoint_loop_")
-    for which in (("bench", "6x6", "vector") if args.which == "all" else (args.which,)):
+    for which in (("bench", "6x6", "vector", "vector16") if args.which == "all" else (args.which,)):
         eng, before, with_archive = workload(which, work)
         eng.reset(True)  # (the same seeding as the rebuilt runs below)
         for _ in range(before):
@@ -121,6 +170,8 @@ def measure(args):
             which, type(eng).__name__, before, eng.get_vehicle_count(),
             ", Lane::history %s" % ("on" if eng._keeps_lane_history() else "off") if with_archive else ""), flush=True)
         ck = pairs(eng, args.repeats, with_archive)
+        if which.startswith("vector"):
+            gathered(eng, ck, args.repeats, args.rollout_steps)
         rollouts(eng, ck, before, args.rollout_steps, args.candidates)
         ck.release()
         del eng
@@ -141,13 +192,33 @@ def trace(args):
         args.iters, ck.num_running, (time.perf_counter() - t0) / args.iters * 1e3, ck.device_bytes), flush=True)
 
 
+def trace_envs(args):
+    work = tempfile.mkdtemp(prefix="checkpoint_trace_envs_")
+    eng = cityflow_amd.VectorEngine(scenarios.materialize("grid_6x6", work), args.envs, 1)
+    for _ in range(300):
+        eng.next_step()
+    ck = eng.checkpoint()
+    top = survivors(eng)
+    eng.rollback(ck, envs=top)
+    eng.sync()
+    t0 = time.perf_counter()
+    for _ in range(args.iters):
+        eng.rollback(ck, envs=top)
+    eng.sync()
+    print("%d rollback(ck, envs=8 survivors tiled) at %d environments, %d running vehicles in the checkpoint, %d after: %.3f ms each on "
+          "the host's clock" % (args.iters, args.envs, ck.num_running, eng.get_vehicle_count(), (time.perf_counter() - t0) / args.iters * 1e3),
+          flush=True)
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
-    ap.add_argument("--which", choices=("bench", "6x6", "vector", "all"), default="all")
+    ap.add_argument("--which", choices=("bench", "6x6", "vector", "vector16", "all"), default="all")
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--rollout-steps", type=int, default=300)
     ap.add_argument("--candidates", type=int, default=3)
     ap.add_argument("--trace", action="store_true")
+    ap.add_argument("--trace-envs", action="store_true")
+    ap.add_argument("--envs", type=int, default=64)
     ap.add_argument("--iters", type=int, default=20)
     a = ap.parse_args()
-    trace(a) if a.trace else measure(a)
+    trace_envs(a) if a.trace_envs else trace(a) if a.trace else measure(a)

@@ -8,6 +8,14 @@
       Both times are printed (engine construction and file writing counted apart), and leg A's travel times must equal leg B's
       per environment, exactly.
 
+  python tools/plan_search_loop.py --rounds 2 [--keep 8] [--envs 64] [--steps 300] [--seed 3] [--runs 3]
+      the search loop that rollback(ck, envs=) closes: per round R candidate plans run `steps` steps side by side, the `keep`
+      environments with the lowest average travel time of the round survive, and EVERY slot goes on from a survivor's state
+      (checkpoint(into=) + rollback(ck, envs=the survivors tiled)) under a new candidate: the survivor's plan, with some phases
+      redrawn in all but the survivor's first slot.  Timed beside the only route without the call: every round starts with
+      reset(True) and the earlier rounds again from step 0, each slot under the plans its state came from (round n costs n
+      rounds of steps).  Both must end in the same lane counts.
+
   python tools/plan_search_loop.py --trace [--iters 220] [--which engine|vector]
       the workload for a `rocprofv3 --kernel-trace --stats` run of its own: set_tl_plan_tensor(durations, phase, phase_remain),
       get_tl_phase_durations_tensor and set_tl_phases_tensor, `iters` times each, on an Engine(grid_30x30) and on a
@@ -115,6 +123,73 @@ def search(args):
     print("ratio of the medians %.1fx" % (statistics.median(b_times) / statistics.median(a_times)))
 
 
+def search_rounds(args):
+    work = tempfile.mkdtemp(prefix="plan_rounds_")
+    cfg = scenarios.materialize("grid_6x6", work, seed=args.seed)
+    R, k = args.envs, min(args.keep, args.envs)
+    vec = cityflow_amd.VectorEngine(cfg, R, 1, seeds=[args.seed] * R)
+    device = torch.device("cuda", vec._stream_handle()[1])
+    n_phases = vec._phase_counts()
+    P = vec._intersection_dims()[1]
+    vec.track_trips(True)
+
+    def run_round(plans):
+        vec.set_tl_plan_tensor(durations=torch.from_numpy(plans).to(device))
+        for s in range(args.steps):
+            vec.next_step()
+        return vec.get_average_travel_time_tensor().cpu().numpy()  # (of the round: the trackers took a baseline at its start)
+
+    search_ms, gather_ms, rebuilt_ms = [], [], []
+    ck = None
+    for run in range(args.runs + 1):  # (run 0 warms up)
+        rng = np.random.default_rng(args.seed + run)
+        vec.restore_tl_plan()  # (a reset restarts the lights from the durations in force: both legs start from the file's)
+        vec.reset(True)
+        vec.sync()
+        t0 = time.perf_counter()
+        plans = random_plans(rng, n_phases, P, R)
+        history, histories, t_gather = [], [], 0.0  # per round: the plans whose states the slots go on from
+        for rnd in range(args.rounds):
+            att = run_round(plans)
+            history.append(plans)
+            histories.append(list(history))
+            if rnd + 1 == args.rounds:
+                break
+            best = np.argsort(att, kind="stable")[:k]
+            envs = [int(best[r % k]) for r in range(R)]
+            t1 = time.perf_counter()
+            ck = vec.checkpoint(into=ck)
+            vec.rollback(ck, envs=envs)
+            t_gather += time.perf_counter() - t1
+            history = [h[envs] for h in history]
+            plans = plans[envs].copy()
+            fresh = random_plans(rng, n_phases, P, R)
+            redraw = rng.random(plans.shape) < 0.25
+            redraw[:k] = False  # (the survivors themselves go on unchanged in the first k slots)
+            plans = np.where(redraw & (plans > 0), fresh, plans)
+        vec.sync()
+        t_search = time.perf_counter() - t0
+        lanes = vec.get_lane_vehicle_count_array()
+        winner = int(att.argmin())
+        # the same rounds without the call: each from step 0 again, every slot under the plans its state came from
+        t0 = time.perf_counter()
+        for upto in histories:
+            vec.restore_tl_plan()
+            vec.reset(True)
+            for h in upto:
+                run_round(h)
+        vec.sync()
+        t_rebuilt = time.perf_counter() - t0
+        assert np.array_equal(vec.get_lane_vehicle_count_array(), lanes), "the searched and the rebuilt run end in different lane counts"
+        if run:
+            search_ms.append(t_search * 1e3), gather_ms.append(t_gather * 1e3), rebuilt_ms.append(t_rebuilt * 1e3)
+            print("run %d: %d rounds of %d plans x %d steps, keep %d: %8.1f ms, of which checkpoint + gathered rollback %6.1f ms; "
+                  "rebuilt from step 0 %8.1f ms; best of the last round: slot %d, %.3f s; end states equal"
+                  % (run, args.rounds, R, args.steps, k, search_ms[-1], gather_ms[-1], rebuilt_ms[-1], winner, att[winner]), flush=True)
+    for name, ts in (("search loop", search_ms), ("  checkpoint(into=) + rollback(ck, envs=)", gather_ms), ("rebuilt from step 0", rebuilt_ms)):
+        print("%-44s median %8.1f ms  min %8.1f  max %8.1f" % (name, statistics.median(ts), min(ts), max(ts)))
+
+
 def trace(args):
     work = tempfile.mkdtemp(prefix="plan_trace_")
     engines = [("Engine 30x30", cityflow_amd.Engine(scenarios.materialize("grid_30x30", work, rlTrafficLight=True), 1)),
@@ -148,8 +223,10 @@ if __name__ == "__main__":
     ap.add_argument("--steps", type=int, default=300)
     ap.add_argument("--seed", type=int, default=3)
     ap.add_argument("--runs", type=int, default=3)
+    ap.add_argument("--rounds", type=int, default=0, help="the keep-the-best search loop with this many rounds (0: the plan evaluation)")
+    ap.add_argument("--keep", type=int, default=8)
     ap.add_argument("--trace", action="store_true")
     ap.add_argument("--iters", type=int, default=220)
     ap.add_argument("--which", choices=("both", "engine", "vector"), default="both", help="--trace: one engine alone (a trace per size)")
     a = ap.parse_args()
-    trace(a) if a.trace else search(a)
+    trace(a) if a.trace else search_rounds(a) if a.rounds else search(a)
