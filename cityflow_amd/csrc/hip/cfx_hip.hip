@@ -93,9 +93,10 @@ struct cfx_checkpoint {
 };
 
 // the trackers (cfx_engine::tracker), in the order of their lifecycle, and their names in messages
-enum Tracker { kLaneFlow, kMoveFlow, kTrips, kTrackers };
-static const char *const kTrackerName[kTrackers] = {"lane-flow", "movement-flow", "trip"};
-static const char *const kTrackerEnable[kTrackers] = {"cfx_lane_flow_enable", "cfx_movement_flow_enable", "cfx_trip_stats_enable"};
+enum Tracker { kLaneFlow, kMoveFlow, kTrips, kDetectors, kTrackers };
+static const char *const kTrackerName[kTrackers] = {"lane-flow", "movement-flow", "trip", "detector"};
+static const char *const kTrackerEnable[kTrackers] = {"cfx_lane_flow_enable", "cfx_movement_flow_enable", "cfx_trip_stats_enable",
+                                                      "cfx_detectors_enable"};
 
 struct cfx_engine {
     int device = 0;
@@ -195,9 +196,9 @@ struct cfx_engine {
     InterFeatOut interTab{};        // the table pointers and M / P; the output pointers stay null here
     int32_t *interOutI = nullptr;   // [I * (1 + 4 M + P)] phase, in, in_waiting, out, inside, phase_pressure
     double *interOutD = nullptr;    // [I]
-    // The trackers: statistics kept across steps (cfx_lane_flow_enable, cfx_movement_flow_enable, cfx_trip_stats_enable; DESIGN.md
-    // "One scaffold for the trackers").  One lifecycle, always in this order.  Nothing is allocated or launched for a tracker
-    // that is off.  `baselineDue`: enabling, a reset or cfx_load_state left a baseline to the next step or read (trackersSettle).
+    // The trackers: statistics kept across steps (cfx_lane_flow_enable, cfx_movement_flow_enable, cfx_trip_stats_enable,
+    // cfx_detectors_enable; DESIGN.md "One scaffold for the trackers").  One lifecycle, always in this order.  Nothing is
+    // allocated or launched for a tracker that is off.  `baselineDue`: enabling, a reset or cfx_load_state left a baseline to the next step or read (trackersSettle).
     // Each keeps a per-vehicle shadow that grows with the vehicle tables (ensureVidCap) and a tick that only ever counts up.
     struct TrackerSlot {
         bool on = false, baselineDue = false;
@@ -205,6 +206,12 @@ struct cfx_engine {
     LaneFlowDev flow{};             // laneFlowTick (cfx_kernels.h)
     MoveFlowDev move{};             // moveFlowTick
     TripDev trip{};                 // k_trip_tick
+    DetectorDev det{};              // detectorTick
+    // cfx_detectors_define: ONE environment's set as the caller gave it (kept while the tracker is off too), and the tables
+    // trackerAlloc builds from it for every environment (DetectorDev's lanes / first / order point at them)
+    std::vector<int32_t> detLane;
+    std::vector<double> detStart, detEnd;
+    int32_t *detLanes = nullptr, *detFirst = nullptr, *detOrder = nullptr;
     // cfx_get_movement_flow: the host getter's device scratch (freed with the tracker)
     int32_t *moveOutI = nullptr;    // [3 I M] entered, left, max_waiting_steps
     int64_t *moveOutL = nullptr;    // [5 I M] the five sums
@@ -558,6 +565,7 @@ struct cfx_engine {
         if (tracker[kLaneFlow].on && (rc = growShadow(&flow.rec, nc))) return rc;
         if (tracker[kMoveFlow].on && (rc = growShadow(&move.rec, nc))) return rc;
         if (tracker[kTrips].on && (rc = growShadow(&trip.seen, nc))) return rc;
+        if (tracker[kDetectors].on && (rc = growShadow(&det.rec, nc))) return rc;
         vidCap = nc;
         return CFX_OK;
     }
@@ -927,6 +935,64 @@ struct cfx_engine {
         HIP_TRY(hipGetLastError());
         return CFX_OK;
     }
+    // cfx_detectors_enable: one tick (or baseline) over the lanes that have a detector, on the committed state, after everything
+    // enqueued so far
+    int detectorTick(bool baseline) {
+        det.tick += 1;
+        det.baseline = baseline ? 1 : 0;
+        det.vidCap = (int) vidCap;
+        if (det.nLanes <= 0) return CFX_OK;
+        const size_t threads = (size_t) det.nLanes * kFeatGroup;
+        if (ring) hipLaunchKernelGGL(kr_detectors, dim3(gridFor(threads)), dim3(kBlock), 0, stream, rctx(), det);
+        else hipLaunchKernelGGL(kd_detectors, dim3(gridFor(threads)), dim3(kBlock), 0, stream, ctx(), det);
+        HIP_TRY(hipGetLastError());
+        return CFX_OK;
+    }
+    // the detector records of every environment from the set cfx_detectors_define keeps, and the index of the lanes that have
+    // one: lanes[g], and order[first[g] .. first[g + 1]) = the records on that lane in the caller's order
+    int detectorTables() {
+        const int nEnvs = cfg.n_envs > 1 ? cfg.n_envs : 1, lanesPerEnv = L / nEnvs, n = (int) detLane.size();
+        std::vector<cfx_detector> recs((size_t) nEnvs * n);
+        std::vector<int32_t> perLane((size_t) L + 1, 0), lanes, first{0}, order((size_t) nEnvs * n);
+        for (int r = 0; r < nEnvs; ++r)
+            for (int i = 0; i < n; ++i) {
+                cfx_detector &a = recs[(size_t) r * n + i];
+                a = cfx_detector{};
+                a.start = detStart[(size_t) i];
+                a.end = detEnd[(size_t) i];
+                a.lane = r * lanesPerEnv + detLane[(size_t) i];
+                perLane[(size_t) a.lane + 1] += 1;
+            }
+        for (int l = 0; l < L; ++l) {
+            if (perLane[(size_t) l + 1]) {
+                lanes.push_back(l);
+                first.push_back(first.back() + perLane[(size_t) l + 1]);
+            }
+            perLane[(size_t) l + 1] += perLane[(size_t) l];  // (now: where lane l + 1's run starts)
+        }
+        for (size_t d = 0; d < recs.size(); ++d) order[(size_t) perLane[(size_t) recs[d].lane]++] = (int32_t) d;
+        int rc;
+        if ((rc = allocRaw(&det.det, recs.size())) || (rc = allocRaw(&detLanes, lanes.size())) ||
+            (rc = allocRaw(&detFirst, first.size())) || (rc = allocRaw(&detOrder, order.size())))
+            return rc;
+        HIP_TRY(hipMemcpyAsync(det.det, recs.data(), recs.size() * sizeof(cfx_detector), hipMemcpyHostToDevice, stream));
+        HIP_TRY(hipMemcpyAsync(detLanes, lanes.data(), lanes.size() * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+        HIP_TRY(hipMemcpyAsync(detFirst, first.data(), first.size() * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+        HIP_TRY(hipMemcpyAsync(detOrder, order.data(), order.size() * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+        HIP_TRY(hipStreamSynchronize(stream));  // (the vectors live on this frame)
+        det.lanes = detLanes;
+        det.first = detFirst;
+        det.order = detOrder;
+        det.nLanes = (int) lanes.size();
+        det.nDet = (int) recs.size();
+        return CFX_OK;
+    }
+    int detectorTablesFree() {
+        const int rc = freeRaw(&det.det) | freeRaw(&detLanes) | freeRaw(&detFirst) | freeRaw(&detOrder);
+        det.lanes = det.first = det.order = nullptr;
+        det.nLanes = det.nDet = 0;
+        return rc;
+    }
     // what enabling a tracker allocates (a shadow starts all 0xFF; what the first baseline fills is left to it) ...
     int trackerAlloc(int which) {
         int rc;
@@ -937,6 +1003,14 @@ struct cfx_engine {
         } else if (which == kMoveFlow) {
             if ((rc = allocRaw(&move.rec, vidCap)) || (rc = allocRaw(&move.link, (size_t) K)) || (rc = allocRaw(&move.skip, (size_t) K * 3))) return rc;
             HIP_TRY(hipMemsetAsync(move.rec, 0xFF, std::max<size_t>(vidCap, 1) * sizeof(int4), stream));
+        } else if (which == kDetectors) {
+            if (detLane.empty()) {
+                err = "cfx_detectors_enable: no detectors are defined (cfx_detectors_define)";
+                return CFX_ERR_STATE;
+            }
+            if ((rc = allocRaw(&det.rec, vidCap))) return rc;
+            HIP_TRY(hipMemsetAsync(det.rec, 0xFF, std::max<size_t>(vidCap, 1) * sizeof(int4), stream));
+            if ((rc = detectorTables())) return rc;
         } else {
             const int nEnvs = cfg.n_envs > 1 ? cfg.n_envs : 1;
             if (R % nEnvs != 0) {
@@ -958,17 +1032,23 @@ struct cfx_engine {
         } else if (which == kMoveFlow) {
             rc = freeRaw(&move.rec) | freeRaw(&move.link) | freeRaw(&move.skip) | freeRaw(&moveOutI) | freeRaw(&moveOutL);
             move = MoveFlowDev{};
+        } else if (which == kDetectors) {
+            rc = freeRaw(&det.rec) | detectorTablesFree();
+            det = DetectorDev{};
+            detLane.clear();
+            detStart.clear();
+            detEnd.clear();
         } else {
             rc = freeRaw(&trip.seen) | freeRaw(&trip.env);
             trip = TripDev{};
         }
         return rc ? CFX_ERR_DEVICE : CFX_OK;
     }
-    // ---- the trackers' lifecycle, always lane, movement, trips
+    // ---- the trackers' lifecycle, always lane, movement, trips, detectors
     int trackerTick(int which, bool baseline) {
-        return which == kLaneFlow ? flowTick(baseline) : which == kMoveFlow ? moveTick(baseline) : tripTick(baseline);
+        return which == kLaneFlow ? flowTick(baseline) : which == kMoveFlow ? moveTick(baseline) : which == kTrips ? tripTick(baseline) : detectorTick(baseline);
     }
-    bool anyTracker() const { return tracker[kLaneFlow].on || tracker[kMoveFlow].on || tracker[kTrips].on; }
+    bool anyTracker() const { return tracker[kLaneFlow].on || tracker[kMoveFlow].on || tracker[kTrips].on || tracker[kDetectors].on; }
     // the baseline that enabling, a reset or a load left to the next step or read (the caller has settled the step and the rings)
     int trackerSettle(int which) {
         if (!tracker[which].on || !tracker[which].baselineDue) return CFX_OK;
@@ -4573,6 +4653,133 @@ int32_t cfx_lane_flow_set_state(cfx_engine *e, const int32_t *records, int32_t n
     HIP_TRY(hipStreamSynchronize(e->stream));
     e->flow.tick = tick;
     e->tracker[kLaneFlow].baselineDue = false;
+    return CFX_OK;
+}
+
+// ---- virtual loop detectors (optional entry points of include/cityflow_amd.h, as above)
+int32_t cfx_detectors_define(cfx_engine *e, const int32_t *lane, const double *start, const double *end, int32_t n);
+int32_t cfx_detectors_enable(cfx_engine *e, int32_t on);
+int32_t cfx_observe_detectors_device(cfx_engine *e, const cfx_detectors_out *out, int32_t reset, void *consumerStream);
+int32_t cfx_get_detectors(cfx_engine *e, const cfx_detectors_out *out, int32_t reset);
+int32_t cfx_detectors_get_state(cfx_engine *e, int32_t *records, int32_t nVehicles, cfx_detector *detectors, int32_t nDetectors, int32_t *tick);
+int32_t cfx_detectors_set_state(cfx_engine *e, const int32_t *records, int32_t nVehicles, const cfx_detector *detectors, int32_t nDetectors,
+                                int32_t tick);
+static_assert(std::is_same<decltype(&cfx_detectors_define), cfx_detectors_define_fn>::value, "cfx_detectors_define");
+static_assert(std::is_same<decltype(&cfx_detectors_enable), cfx_detectors_enable_fn>::value, "cfx_detectors_enable");
+static_assert(std::is_same<decltype(&cfx_observe_detectors_device), cfx_observe_detectors_device_fn>::value, "cfx_observe_detectors_device");
+static_assert(std::is_same<decltype(&cfx_get_detectors), cfx_get_detectors_fn>::value, "cfx_get_detectors");
+static_assert(std::is_same<decltype(&cfx_detectors_get_state), cfx_detectors_get_state_fn>::value, "cfx_detectors_get_state");
+static_assert(std::is_same<decltype(&cfx_detectors_set_state), cfx_detectors_set_state_fn>::value, "cfx_detectors_set_state");
+static_assert(sizeof(cfx_detector) == 64, "cfx_detector");
+
+int32_t cfx_detectors_define(cfx_engine *e, const int32_t *lane, const double *start, const double *end, int32_t n) {
+    if (!e) return CFX_ERR_INVALID;
+    auto fail = [e](const std::string &m) { return e->fail(m); };
+    if (!lane || !start || !end || n < 1) return e->fail("cfx_detectors_define: lane, start and end of n >= 1 detectors"), CFX_ERR_INVALID;
+    if (e->lc.on || e->tiled) {
+        e->err = "cfx_detectors_define: not with lane change and not on a tile";
+        return CFX_ERR_STATE;
+    }
+    const int lanesPerEnv = e->L / (e->cfg.n_envs > 1 ? e->cfg.n_envs : 1);
+    for (int32_t i = 0; i < n; ++i) {  // (every entry before anything changes)
+        const char *bad = (lane[i] < 0 || lane[i] >= lanesPerEnv) ? "lane is not a lane of one environment"
+                          : !(std::isfinite(start[i]) && start[i] >= 0.0) ? "start is not finite and >= 0"
+                          : !(end[i] > start[i]) ? "end is not beyond start" : nullptr;
+        if (bad) return e->fail("cfx_detectors_define: position " + std::to_string(i) + ": " + bad), CFX_ERR_INVALID;
+    }
+    e->detLane.assign(lane, lane + n);
+    e->detStart.assign(start, start + n);
+    e->detEnd.assign(end, end + n);
+    if (!e->tracker[kDetectors].on) return CFX_OK;
+    // the set in force is replaced: new records and lane index (the vehicle records stay: a baseline overwrites what it uses)
+    HIP_TRY(hipSetDevice(e->device));
+    int rc;
+    if ((rc = e->settle(false))) return rc;
+    if (e->ring && (rc = e->ringEnsure())) return rc;
+    HIP_TRY(hipStreamSynchronize(e->stream));  // (a tick may still be reading the tables)
+    if (e->detectorTablesFree()) return CFX_ERR_DEVICE;
+    if ((rc = e->detectorTables())) return rc;
+    e->tracker[kDetectors].baselineDue = true;
+    return e->trackerSettle(kDetectors);
+}
+
+int32_t cfx_detectors_enable(cfx_engine *e, int32_t on) { return e ? e->trackerEnable(kDetectors, on) : CFX_ERR_INVALID; }
+
+static void launchDetectorsDrain(cfx_engine *e, const cfx_detectors_out &o, int32_t reset) {
+    if (e->det.nDet <= 0) return;
+    hipLaunchKernelGGL(k_detectors_drain, dim3(gridFor((size_t) e->det.nDet)), dim3(kBlock), 0, e->stream, e->det.det, e->det.nDet, o, reset ? 1 : 0);
+}
+
+int32_t cfx_observe_detectors_device(cfx_engine *e, const cfx_detectors_out *out, int32_t reset, void *consumerStream) {
+    if (!e || !out) return CFX_ERR_INVALID;
+    const cfx_detectors_out o = *out;
+    if (!o.passed && !o.occupied_steps && !o.vehicle_steps && !o.waiting_vehicle_steps && !o.speed_sum && !o.count && !reset) return CFX_ERR_INVALID;
+    auto fail = [e](const std::string &m) { return e->fail(m); };
+    HIP_TRY(hipSetDevice(e->device));
+    int rc;
+    if ((rc = checkDevicePointers(e, "cfx_observe_detectors_device",
+                                  {{o.passed, "passed"}, {o.occupied_steps, "occupied_steps"}, {o.vehicle_steps, "vehicle_steps"},
+                                   {o.waiting_vehicle_steps, "waiting_vehicle_steps"}, {o.speed_sum, "speed_sum"}, {o.count, "count"}})))
+        return rc;
+    if ((rc = trackerPrepare(e, kDetectors, "cfx_observe_detectors_device"))) return rc;
+    if ((rc = e->orderAfterCaller((hipStream_t) consumerStream))) return rc;
+    launchDetectorsDrain(e, o, reset);
+    HIP_TRY(hipGetLastError());
+    return e->orderCallerAfter((hipStream_t) consumerStream);
+}
+
+int32_t cfx_get_detectors(cfx_engine *e, const cfx_detectors_out *out, int32_t reset) {
+    if (!e || !out) return CFX_ERR_INVALID;
+    auto fail = [e](const std::string &m) { return e->fail(m); };
+    HIP_TRY(hipSetDevice(e->device));
+    int rc;
+    if ((rc = trackerPrepare(e, kDetectors, "cfx_get_detectors"))) return rc;
+    // (the records themselves come back, 64 bytes per detector: no device scratch, and the kernel only has to zero)
+    std::vector<cfx_detector> recs((size_t) e->det.nDet);
+    if (!recs.empty()) HIP_TRY(hipMemcpyAsync(recs.data(), e->det.det, recs.size() * sizeof(cfx_detector), hipMemcpyDeviceToHost, e->stream));
+    if (reset) {
+        launchDetectorsDrain(e, cfx_detectors_out{}, 1);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    for (size_t d = 0; d < recs.size(); ++d) {
+        if (out->passed) out->passed[d] = recs[d].passed;
+        if (out->occupied_steps) out->occupied_steps[d] = recs[d].occupied_steps;
+        if (out->vehicle_steps) out->vehicle_steps[d] = recs[d].vehicle_steps;
+        if (out->waiting_vehicle_steps) out->waiting_vehicle_steps[d] = recs[d].waiting_vehicle_steps;
+        if (out->speed_sum) out->speed_sum[d] = recs[d].speed_sum;
+        if (out->count) out->count[d] = recs[d].count;
+    }
+    return CFX_OK;
+}
+
+int32_t cfx_detectors_get_state(cfx_engine *e, int32_t *records, int32_t nVehicles, cfx_detector *detectors, int32_t nDetectors, int32_t *tick) {
+    if (!e || !detectors || !tick || nVehicles < 0 || (nVehicles > 0 && !records)) return CFX_ERR_INVALID;
+    auto fail = [e](const std::string &m) { return e->fail(m); };
+    HIP_TRY(hipSetDevice(e->device));
+    int rc;
+    if ((rc = trackerPrepare(e, kDetectors, "cfx_detectors_get_state"))) return rc;
+    if (nDetectors != e->det.nDet) return e->fail("cfx_detectors_get_state: n_detectors is not the number of detectors"), CFX_ERR_INVALID;
+    if ((rc = recordsOut(e, "cfx_detectors_get_state", e->det.rec, records, nVehicles))) return rc;
+    HIP_TRY(hipMemcpyAsync(detectors, e->det.det, (size_t) nDetectors * sizeof(cfx_detector), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    *tick = e->det.tick;
+    return CFX_OK;
+}
+
+int32_t cfx_detectors_set_state(cfx_engine *e, const int32_t *records, int32_t nVehicles, const cfx_detector *detectors, int32_t nDetectors,
+                                int32_t tick) {
+    if (!e || !detectors || nVehicles < 0 || (nVehicles > 0 && !records)) return CFX_ERR_INVALID;
+    auto fail = [e](const std::string &m) { return e->fail(m); };
+    HIP_TRY(hipSetDevice(e->device));
+    int rc;
+    if ((rc = trackerRequire(e, kDetectors, "cfx_detectors_set_state"))) return rc;
+    if (nDetectors != e->det.nDet) return e->fail("cfx_detectors_set_state: n_detectors is not the number of detectors"), CFX_ERR_INVALID;
+    if ((rc = recordsIn(e, "cfx_detectors_set_state", e->det.rec, records, nVehicles))) return rc;
+    HIP_TRY(hipMemcpyAsync(e->det.det, detectors, (size_t) nDetectors * sizeof(cfx_detector), hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    e->det.tick = tick;
+    e->tracker[kDetectors].baselineDue = false;
     return CFX_OK;
 }
 

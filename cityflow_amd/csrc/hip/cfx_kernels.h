@@ -2588,6 +2588,116 @@ __global__ void __launch_bounds__(kBlock) k_lane_flow_drain(cfx_lane_flow_lane *
     }
 }
 
+// cfx_detectors_enable: virtual loop detectors, zones [start, end) of lanes (include/cityflow_amd.h has the rules).  One TICK after
+// every step, on the committed state, over the lanes that HAVE a detector: a group of kFeatGroup threads walks lane lanes[g].
+// First pass, as laneFlowTick: each thread does the read-modify-write of its vehicles' records rec[vid] = {lane, tick last seen
+// on it, 0, 0} (the form of the flow trackers' records; a vehicle is on one lane, so one writer) and the group adds up who is
+// new on the lane.  Second pass, as laneFeatures: every chunk of sixteen {dis, speed} records is staged in LDS, thread j owns
+// the lane's j-th detector (order[first[g] + j]; a lane with more than sixteen takes another round over the lane) and walks the
+// staged chunk serially, front to back — so the zone's speed sum is one chain of adds in the defined order, without shuffles
+// and without atomics, and each detector record has one writer.  The vehicles that left are not looked for: with U = the
+// vehicles upstream of `start`, passed += U' - U + entered, exact in integers because a vehicle on a lane never moves backwards
+// and a lane is left at its front only (it covers the vehicle that went over the rest of the lane in one step).
+struct DetectorDev {
+    int4 *rec;             // [vidCap]
+    cfx_detector *det;     // [nDet], every environment's, in the caller's order
+    const int32_t *lanes;  // [nLanes] the lanes that have a detector
+    const int32_t *first;  // [nLanes + 1] into order
+    const int32_t *order;  // [nDet] the records grouped by lane
+    int nLanes, nDet, vidCap;
+    int32_t tick;
+    int baseline;          // nothing counted, accumulators zero, U and count as of now
+};
+
+// (`f` by value, as laneFlowTick takes its argument struct)
+template <typename Rec, typename Vid>
+__device__ __forceinline__ void detectorTick(const DetectorDev f, int g, int lane, int n, int sub, double2 *stage, Rec rec, Vid vidOf) {
+    int entered = 0;
+    for (int i = sub; i < n; i += kFeatGroup) {
+        const int v = vidOf(i);
+        if ((unsigned) v >= (unsigned) f.vidCap) continue;  // (never: every vehicle on a lane has a number the tables hold)
+        const int4 r = f.rec[v];
+        entered += r.x != lane || r.y != f.tick - 1;
+        f.rec[v] = make_int4(lane, f.tick, 0, 0);
+    }
+    for (int off = kFeatGroup / 2; off > 0; off >>= 1) entered += __shfl_xor(entered, off, kFeatGroup);
+    const int d0 = f.first[g], nd = f.first[g + 1] - d0;
+    for (int j0 = 0; j0 < nd; j0 += kFeatGroup) {  // (the trip counts are the group's: nd and n are the same in all its threads)
+        const bool own = j0 + sub < nd;
+        int di = 0;
+        cfx_detector a{};
+        double lo = 1.0, hi = 0.0;  // (an empty zone: what a thread without a detector adds up goes nowhere)
+        if (own) {
+            di = f.order[d0 + j0 + sub];
+            a = f.det[di];
+            lo = a.start;
+            hi = a.end;
+        }
+        int c = 0, w = 0, u = 0;
+        double t = 0.0;
+        for (int head = 0; head < n; head += kFeatGroup) {
+            double2 r = make_double2(0.0, 0.0);
+            if (head + sub < n) r = rec(head + sub);
+            stage[sub] = r;
+            waveLdsOrder();
+            const int m = min(n - head, kFeatGroup);
+            for (int k = 0; k < m; ++k) {
+                const double2 v = stage[k];  // (the same address in every thread of the group: a broadcast)
+                const bool in = lo <= v.x && v.x < hi;
+                u += v.x < lo;
+                c += in;
+                w += in && v.y < 0.1;
+                if (in) t += v.y;
+            }
+            waveLdsOrder();  // (the next chunk overwrites the stage)
+        }
+        if (!own) continue;
+        if (f.baseline) {
+            a.passed = a.occupied_steps = 0;
+            a.vehicle_steps = a.waiting_vehicle_steps = 0;
+            a.speed_sum = 0.0;
+        } else {
+            a.passed += a.upstream - u + entered;
+            a.occupied_steps += c > 0;
+            a.vehicle_steps += c;
+            a.waiting_vehicle_steps += w;
+            a.speed_sum = a.speed_sum + t;
+        }
+        a.upstream = u;
+        a.count = c;
+        f.det[di] = a;
+    }
+}
+
+__global__ void __launch_bounds__(kBlock) kd_detectors(StepCtx c, DetectorDev f) {
+    __shared__ double2 stage[kBlock];
+    const int g = (int) ((blockIdx.x * (size_t) blockDim.x + threadIdx.x) / kFeatGroup);
+    if (g >= f.nLanes) return;  // (whole groups)
+    const int lane = f.lanes[g], sub = threadIdx.x % kFeatGroup;
+    detectorTick(f, g, lane, c.cnt[lane], sub, stage + (threadIdx.x - sub), laneRec(c, lane), laneVid(c, lane));
+}
+
+// cfx_observe_detectors_device / cfx_get_detectors: the tick left every output in the detector's record; this copies (any pointer
+// may be null) and, with `reset`, zeroes the five accumulators it has just read.  One thread per detector.
+__global__ void __launch_bounds__(kBlock) k_detectors_drain(cfx_detector *det, int n, cfx_detectors_out o, int reset) {
+    const int d = (int) (blockIdx.x * (size_t) blockDim.x + threadIdx.x);
+    if (d >= n) return;
+    const cfx_detector a = det[d];
+    if (o.passed) o.passed[d] = a.passed;
+    if (o.occupied_steps) o.occupied_steps[d] = a.occupied_steps;
+    if (o.vehicle_steps) o.vehicle_steps[d] = a.vehicle_steps;
+    if (o.waiting_vehicle_steps) o.waiting_vehicle_steps[d] = a.waiting_vehicle_steps;
+    if (o.speed_sum) o.speed_sum[d] = a.speed_sum;
+    if (o.count) o.count[d] = a.count;
+    if (reset) {
+        det[d].passed = 0;
+        det[d].occupied_steps = 0;
+        det[d].vehicle_steps = 0;
+        det[d].waiting_vehicle_steps = 0;
+        det[d].speed_sum = 0.0;
+    }
+}
+
 // cfx_movement_flow_enable: per-movement flow and delay statistics across steps (include/cityflow_amd.h has the rules).  One TICK
 // after every step, on the committed state, over ALL drivables: a group of kFeatGroup threads walks drivable d (a lane, or laneLink
 // d - L) as laneFlowTick does, and each thread does the read-modify-write of its vehicle's record rec[vid] = {drivable, tick

@@ -2423,6 +2423,15 @@ __global__ void __launch_bounds__(kBlock) kr_movement_flow(RingCtx c, MoveFlowDe
     moveFlowTick(f, moveFlowNet(c.n), d, c.cnt[d], threadIdx.x % kFeatGroup, laneRec(c, d), laneVid(c, d));
 }
 
+// cfx_detectors_enable, ring layout: detectorTick (cfx_kernels.h) over the rings of the lanes that have a detector
+__global__ void __launch_bounds__(kBlock) kr_detectors(RingCtx c, DetectorDev f) {
+    __shared__ double2 stage[kBlock];
+    const int g = (int) ((blockIdx.x * (size_t) blockDim.x + threadIdx.x) / kFeatGroup);
+    if (g >= f.nLanes) return;  // (whole groups)
+    const int lane = f.lanes[g], sub = threadIdx.x % kFeatGroup;
+    detectorTick(f, g, lane, c.cnt[lane], sub, stage + (threadIdx.x - sub), laneRec(c, lane), laneVid(c, lane));
+}
+
 // cfx_observe_intersections_device / cfx_get_intersection_features, ring layout: interFeatures (cfx_kernels.h) over the rings
 __global__ void __launch_bounds__(kBlock) kr_intersection_features(RingCtx c, InterFeatOut o) {
     extern __shared__ int32_t interDiff[];

@@ -102,6 +102,12 @@ void Backend::open(const std::string &libPath) {
     CFX_FN_OPTIONAL(cfx_get_lane_flow)
     CFX_FN_OPTIONAL(cfx_lane_flow_get_state)
     CFX_FN_OPTIONAL(cfx_lane_flow_set_state)
+    CFX_FN_OPTIONAL(cfx_detectors_define)
+    CFX_FN_OPTIONAL(cfx_detectors_enable)
+    CFX_FN_OPTIONAL(cfx_observe_detectors_device)
+    CFX_FN_OPTIONAL(cfx_get_detectors)
+    CFX_FN_OPTIONAL(cfx_detectors_get_state)
+    CFX_FN_OPTIONAL(cfx_detectors_set_state)
     CFX_FN_OPTIONAL(cfx_trip_stats_enable)
     CFX_FN_OPTIONAL(cfx_observe_trip_stats_device)
     CFX_FN_OPTIONAL(cfx_get_trip_stats)
@@ -950,6 +956,23 @@ void EngineHost::tripFeatures(const cfx_trip_stats_out &out) {
 }
 
 void EngineHost::observeTripsDevice(const cfx_trip_stats_out &out, uintptr_t consumerStream) { trackers_.trip.observeDevice(out, consumerStream); }
+
+void EngineHost::defineDetectors(const int32_t *lane, const double *start, const double *end, int n) {
+    if (laneChange_) throw std::logic_error("track_detectors: not with laneChange (a shadow changes identity when its change finishes)");
+    trackers_.det.define(lane, start, end, n, (int64_t) step_);
+}
+
+void EngineHost::dropDetectors() { trackers_.det.disable(); }
+
+// (like the count getters, these leave the step prepared ahead in place)
+void EngineHost::detectorFeatures(const cfx_detectors_out &out, bool reset) {
+    trackers_.det.features(out, reset);
+    raiseDeviceError();
+}
+
+void EngineHost::observeDetectorsDevice(const cfx_detectors_out &out, bool reset, uintptr_t consumerStream) {
+    trackers_.det.observeDevice(out, reset, consumerStream);
+}
 
 const InterLayout &EngineHost::intersectionLayout() {
     if (!interLayout_) interLayout_.reset(new InterLayout(intersectionLayoutOf(*net_)));

@@ -110,6 +110,13 @@ struct Backend {
     cfx_get_movement_flow_fn cfx_get_movement_flow = nullptr;
     cfx_movement_flow_get_state_fn cfx_movement_flow_get_state = nullptr;
     cfx_movement_flow_set_state_fn cfx_movement_flow_set_state = nullptr;
+    // optional as a set: virtual loop detectors kept by the backend (without them the host keeps them: detectors.h)
+    cfx_detectors_define_fn cfx_detectors_define = nullptr;
+    cfx_detectors_enable_fn cfx_detectors_enable = nullptr;
+    cfx_observe_detectors_device_fn cfx_observe_detectors_device = nullptr;
+    cfx_get_detectors_fn cfx_get_detectors = nullptr;
+    cfx_detectors_get_state_fn cfx_detectors_get_state = nullptr;
+    cfx_detectors_set_state_fn cfx_detectors_set_state = nullptr;
     // optional as a set: the fixed-time signal plan as engine state (without them there is no such call: TlPlan below)
     cfx_set_tl_plan_device_fn cfx_set_tl_plan_device = nullptr;
     cfx_set_tl_plan_fn cfx_set_tl_plan = nullptr;
@@ -352,6 +359,13 @@ public:
     bool tripTracking() const { return trackers_.trip.on(); }
     void tripFeatures(const cfx_trip_stats_out &out);  // any pointer may be null; one element each
     void observeTripsDevice(const cfx_trip_stats_out &out, uintptr_t consumerStream);
+    // ---- virtual loop detectors across steps (detectors.h; the torch layer is cityflow_amd/torch_io.py): `n` zones of lanes;
+    //      outputs [n], any pointer may be null.  Defining turns the tracker on and takes a baseline
+    void defineDetectors(const int32_t *lane, const double *start, const double *end, int n);
+    void dropDetectors();
+    const Detectors &detectors() const { return trackers_.det; }
+    void detectorFeatures(const cfx_detectors_out &out, bool reset);
+    void observeDetectorsDevice(const cfx_detectors_out &out, bool reset, uintptr_t consumerStream);
     // Lane::history as the device keeps it ("cfx": {"laneHistory": true}; cfx_get_lane_history): lane-major, oldest record first
     void laneHistory(std::vector<int32_t> &len, std::vector<int32_t> &vehicleNum, std::vector<double> &averageSpeed,
                      std::vector<int32_t> &historyVehicleNum, std::vector<double> &historyAverageSpeed);

@@ -428,6 +428,47 @@ void observeTripsDevice(E &e, uintptr_t entered, uintptr_t admitted, uintptr_t b
     e.observeTripsDevice(o, consumerStream);
 }
 
+// ---- virtual loop detectors across steps (Engine and VectorEngine; the public calls, and the checks of the arguments' types and
+//      lengths, are cityflow_amd/torch_io.py)
+template <typename E>
+void defineDetectors(E &e, py::array_t<int32_t, py::array::c_style> lane, py::array_t<double, py::array::c_style> start,
+                     py::array_t<double, py::array::c_style> end) {
+    if (lane.ndim() != 1 || start.ndim() != 1 || end.ndim() != 1 || start.size() != lane.size() || end.size() != lane.size())
+        throw py::value_error("track_detectors: lane, start and end must be one-dimensional and of equal length");
+    try {
+        e.defineDetectors(lane.data(), start.data(), end.data(), (int) lane.size());
+    } catch (const std::invalid_argument &) {
+        throw;  // (a ValueError; it is a logic_error too)
+    } catch (const std::logic_error &x) {  // lane change is out of scope, not a failure of the call
+        PyErr_SetString(PyExc_NotImplementedError, x.what());
+        throw py::error_already_set();
+    }
+}
+template <typename E> py::tuple detectorLayoutTuple(E &e) {
+    const cfa::Detectors &d = e.detectors();
+    return py::make_tuple(toArray(d.lanes()), toArray(d.starts()), toArray(d.ends()));
+}
+template <typename E> py::tuple detectorTuple(E &e, bool reset) {
+    const py::ssize_t n = tripEnvs(e) * (py::ssize_t) e.detectors().count();
+    cfx_detectors_out o{};
+    py::tuple t = py::make_tuple(column(o.passed, n), column(o.occupied_steps, n), column(o.vehicle_steps, n),
+                                 column(o.waiting_vehicle_steps, n), column(o.speed_sum, n), column(o.count, n));
+    e.detectorFeatures(o, reset);
+    return t;
+}
+template <typename E>
+void observeDetectorsDevice(E &e, uintptr_t passed, uintptr_t occupied, uintptr_t vehicleSteps, uintptr_t waitingSteps, uintptr_t speedSum,
+                            uintptr_t count, bool reset, uintptr_t consumerStream) {
+    cfx_detectors_out o{};
+    o.passed = (int32_t *) passed;
+    o.occupied_steps = (int32_t *) occupied;
+    o.vehicle_steps = (int64_t *) vehicleSteps;
+    o.waiting_vehicle_steps = (int64_t *) waitingSteps;
+    o.speed_sum = (double *) speedSum;
+    o.count = (int32_t *) count;
+    e.observeDetectorsDevice(o, reset, consumerStream);
+}
+
 // VectorEngine(seeds=...): None -> empty (seed + env index); anything else must hold one seed per environment
 std::vector<int> envSeeds(int envs, const std::optional<std::vector<int>> &seeds) {
     if (!seeds) return {};
@@ -523,7 +564,17 @@ template <typename E> void defDeviceBuffers(py::class_<E> &c) {
              "in_system_travel_steps, average_travel_time), one element per environment")
         .def("_observe_trips_device", &observeTripsDevice<E>, "entered_ptr"_a, "admitted_ptr"_a, "admitted_buffer_steps_ptr"_a,
              "finished_ptr"_a, "finished_travel_steps_ptr"_a, "in_system_ptr"_a, "buffered_ptr"_a, "in_system_travel_steps_ptr"_a,
-             "average_travel_time_ptr"_a, "consumer_stream"_a);
+             "average_travel_time_ptr"_a, "consumer_stream"_a)
+        .def("_define_detectors", &defineDetectors<E>, "lane"_a, "start"_a, "end"_a,
+             "int32 / float64 / float64 [N], of one environment; turns the tracker on and takes a baseline")
+        .def("_drop_detectors", &E::dropDetectors)
+        .def("_detector_tracking", [](E &e) { return e.detectors().on(); })
+        .def("_detector_count", [](E &e) { return e.detectors().count(); }, "detectors of one environment")
+        .def("_detector_layout", [](E &e) { return detectorLayoutTuple(e); }, "(lane, start, end) as they were defined")
+        .def("_detector_features", [](E &e, bool reset) { return detectorTuple(e, reset); }, "reset"_a,
+             "(passed, occupied_steps, vehicle_steps, waiting_vehicle_steps, speed_sum, count), flat (env-major)")
+        .def("_observe_detectors_device", &observeDetectorsDevice<E>, "passed_ptr"_a, "occupied_steps_ptr"_a, "vehicle_steps_ptr"_a,
+             "waiting_vehicle_steps_ptr"_a, "speed_sum_ptr"_a, "count_ptr"_a, "reset"_a, "consumer_stream"_a);
 }
 
 // Engine.set_tl_phase(intersection_id, phase_id) (reference src/cityflow.cpp:35, engine.cpp:719-725) as a vectorcall method of its

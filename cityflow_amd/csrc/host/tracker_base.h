@@ -1,7 +1,7 @@
-// What the three trackers of statistics kept across steps share on the host (lane_flow.h, movement_flow.h, trip_stats.h;
-// DESIGN.md "One scaffold for the trackers").  On a backend that exports a tracker's five optional entry points the device keeps
-// it and the class is a thin dispatcher.  A backend without them (the CPU twin) gets the HOST tracker: the same rules in C++ over
-// the backend's getters, ticked by the owner after every step and given a baseline after a reset or a load.
+// What the four trackers of statistics kept across steps share on the host (lane_flow.h, movement_flow.h, trip_stats.h,
+// detectors.h; DESIGN.md "One scaffold for the trackers").  On a backend that exports a tracker's optional entry points the device
+// keeps it and the class is a thin dispatcher.  A backend without them (the CPU twin) gets the HOST tracker: the same rules in
+// C++ over the backend's getters, ticked by the owner after every step and given a baseline after a reset or a load.
 #pragma once
 
 #include <algorithm>
@@ -18,7 +18,7 @@ class TrackerBase {
 public:
     virtual ~TrackerBase() = default;
     bool on() const { return on_; }
-    bool onDevice() const { return onDevice_; }  // the backend keeps the tracker (all five entry points)
+    bool onDevice() const { return onDevice_; }  // the backend keeps the tracker (all its entry points)
     bool onHost() const { return on_ && !onDevice_; }
     // ---- host tracker (no-ops while the device keeps it, which ticks inside cfx_step and takes its own baselines)
     void afterStep(int64_t step) {

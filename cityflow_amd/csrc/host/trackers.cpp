@@ -1,4 +1,4 @@
-// What the trackers share on the host (tracker_base.h) and the owners' aggregate of the three (trackers.h).
+// What the trackers share on the host (tracker_base.h) and the owners' aggregate of the four (trackers.h).
 #include "trackers.h"
 
 #include <stdexcept>
@@ -46,6 +46,10 @@ Trackers::Carry Trackers::take(int nVehicles, const std::vector<int32_t> &newOfO
         c.move.renumber(newOfOld, nLive);
     }
     if (trip.on()) c.trips = trip.state();
+    if (det.on()) {
+        c.det = det.state(nVehicles);
+        c.det.renumber(newOfOld, nLive);
+    }
     return c;
 }
 
@@ -53,6 +57,7 @@ void Trackers::put(const Carry &c) {
     if (flow.on()) flow.setState(c.flow);
     if (move.on()) move.setState(c.move);
     if (trip.on()) trip.setState(c.trips);
+    if (det.on()) det.setState(c.det);
 }
 
 }  // namespace cfa

@@ -889,6 +889,28 @@ void VectorEngineHost::observeLaneFlowDevice(const LaneFlowOut &out, bool reset,
     trackers_.flow.observeDevice(out, reset, consumerStream);
 }
 
+void VectorEngineHost::defineDetectors(const int32_t *lane, const double *start, const double *end, int n) {
+    if (laneChange_) throw std::logic_error("track_detectors: not with laneChange (a shadow changes identity when its change finishes)");
+    std::lock_guard<std::mutex> guard(queryMutex_);
+    trackers_.det.define(lane, start, end, n, (int64_t) step_);
+}
+
+void VectorEngineHost::dropDetectors() {
+    std::lock_guard<std::mutex> guard(queryMutex_);
+    trackers_.det.disable();
+}
+
+void VectorEngineHost::detectorFeatures(const cfx_detectors_out &out, bool reset) {
+    std::lock_guard<std::mutex> guard(queryMutex_);  // (the ABI is not re-entrant: the ahead thread may be asking the device)
+    trackers_.det.features(out, reset);
+    raiseDeviceError();
+}
+
+void VectorEngineHost::observeDetectorsDevice(const cfx_detectors_out &out, bool reset, uintptr_t consumerStream) {
+    std::lock_guard<std::mutex> guard(queryMutex_);
+    trackers_.det.observeDevice(out, reset, consumerStream);
+}
+
 const InterLayout &VectorEngineHost::intersectionLayout() {
     if (!interLayout_) interLayout_.reset(new InterLayout(intersectionLayoutOf(*net_)));
     return *interLayout_;

@@ -105,6 +105,13 @@ public:
     bool tripTracking() const { return trackers_.trip.on(); }
     void tripFeatures(const cfx_trip_stats_out &out);
     void observeTripsDevice(const cfx_trip_stats_out &out, uintptr_t consumerStream);
+    // virtual loop detectors (EngineHost::defineDetectors and its kin): ONE environment's set, which every environment gets;
+    // outputs [R * n]
+    void defineDetectors(const int32_t *lane, const double *start, const double *end, int n);
+    void dropDetectors();
+    const Detectors &detectors() const { return trackers_.det; }
+    void detectorFeatures(const cfx_detectors_out &out, bool reset);
+    void observeDetectorsDevice(const cfx_detectors_out &out, bool reset, uintptr_t consumerStream);
     std::vector<std::string> laneIds() const;
     std::vector<std::string> intersectionIds() const;
     cfx_scalars scalars();

@@ -35,6 +35,14 @@
                              average_travel_time=None)   0-dim (VectorEngine: [R]) each, one kernel launch (see its docstring)
     eng.observe_trips_array()                            the same nine outputs as numpy arrays (waits for the device)
     eng.get_average_travel_time_tensor(out=None)         float64 0-dim (VectorEngine: [R]): get_average_travel_time() on the device
+    eng.track_detectors(lane=None, start=None, end=None, on=True) / eng.detector_tracking() / eng.detector_layout()
+                                                         N virtual loop detectors, zones [start, end) of lanes: what passed them,
+                                                         how long they were occupied and how fast the traffic over them was,
+                                                         ACROSS steps (off by default)
+    eng.observe_detectors_tensor(passed=None, occupied_steps=None, vehicle_steps=None, waiting_vehicle_steps=None,
+                                 speed_sum=None, count=None, reset=False)
+                                                         drains them into the given [N] tensors, one kernel launch (see its docstring)
+    eng.observe_detectors_array(reset=False)             the same six outputs as numpy arrays (waits for the device)
     eng.set_tl_plan_tensor(durations=None, phase=None, phase_remain=None)
                                                          the fixed-time signal plan as engine state: float64 [I, P] phase durations,
                                                          integer [I] current phase, float64 [I] its remaining time (VectorEngine:
@@ -630,6 +638,162 @@ def get_average_travel_time_tensor(self, out=None):
     return out
 
 
+DETECTOR_OUTPUTS = ("passed", "occupied_steps", "vehicle_steps", "waiting_vehicle_steps", "speed_sum", "count")
+_DETECTOR_INT64 = ("vehicle_steps", "waiting_vehicle_steps")
+
+
+def _detector_dtype(torch, name):
+    return torch.float64 if name == "speed_sum" else torch.int64 if name in _DETECTOR_INT64 else torch.int32
+
+
+def _detector_lanes(lane):
+    """`lane` of track_detectors as a list of ints: TypeError for anything that is not a sequence or array of integers (a bool
+    and a float are not)."""
+    import numbers
+
+    dtype = getattr(lane, "dtype", None)
+    if dtype is not None:  # (numpy array, CPU tensor: judged by its dtype, an empty one too)
+        kind = getattr(dtype, "kind", None)
+        if kind is None:  # a torch dtype
+            if dtype.is_floating_point or dtype.is_complex or str(dtype) == "torch.bool":
+                raise TypeError("track_detectors: lane must hold integers, not %s" % (dtype,))
+        elif kind not in "iu":
+            raise TypeError("track_detectors: lane must hold integers, not %s" % (dtype,))
+    if hasattr(lane, "tolist"):
+        lane = lane.tolist()
+    if isinstance(lane, (str, bytes)) or not hasattr(lane, "__len__") or not hasattr(lane, "__iter__"):
+        raise TypeError("track_detectors: lane must be a sequence of integers, not %s" % type(lane).__name__)
+    lane = list(lane)
+    for i, l in enumerate(lane):
+        if isinstance(l, bool) or type(l).__name__ == "bool_" or not isinstance(l, numbers.Integral):
+            raise TypeError("track_detectors: lane[%d] = %r is not an integer" % (i, l))
+    return [int(l) for l in lane]
+
+
+def _detector_edges(a, name):
+    """`start` / `end` of track_detectors as a list of floats: TypeError for anything that is not a sequence or array of real
+    numbers."""
+    import numbers
+
+    if hasattr(a, "tolist"):
+        a = a.tolist()
+    if isinstance(a, (str, bytes)) or not hasattr(a, "__len__") or not hasattr(a, "__iter__"):
+        raise TypeError("track_detectors: %s must be a sequence of floats, not %s" % (name, type(a).__name__))
+    a = list(a)
+    for i, x in enumerate(a):
+        if isinstance(x, bool) or type(x).__name__ == "bool_" or not isinstance(x, numbers.Real):
+            raise TypeError("track_detectors: %s[%d] = %r is not a number" % (name, i, x))
+    return [float(x) for x in a]
+
+
+def track_detectors(self, lane=None, start=None, end=None, on=True):
+    """Define N virtual loop detectors and turn the detector tracker on (off by default: nothing is allocated or launched), or,
+    with on=False, turn it off and free everything.  Detector d is the zone start[d] <= distance < end[d] of lane lane[d]:
+
+        lane   integer sequence or array [N]  indices into lane_ids()
+        start  floating [N]                   metres from the lane's start, on the scale of get_vehicle_distance()
+        end    floating [N]                   likewise; +inf, or anything beyond the lane's length: the zone reaches to the lane's end
+
+    A detector sees a vehicle's FRONT position only — the project's `distance`; vehicle length is ignored.  Any number of
+    detectors per lane, and they may overlap; lanes without one cost nothing.  VectorEngine: the set is one environment's (lane <
+    L) and every environment gets it.  While the tracker is on, every next_step() ends with one tracker update (one extra
+    kernel launch on the HIP engine, over the lanes that have a detector).  Defining takes a baseline — nothing is counted,
+    the accumulators are zero, `count` is as of now, and every vehicle then on a lane counts as having been there, at its
+    current distance, at the previous update; so do reset(), load(), load_from_file() and rollback(), which keep the tracker
+    on.  Calling it again while it is on replaces the set and takes a new baseline.  Vehicle compaction does not show.
+
+    Every argument is checked before anything changes, in this order: a bool or a float in `lane` (TypeError); unequal lengths
+    or N = 0 (ValueError); then lane in [0, L), start finite and >= 0, end > start, no NaN (ValueError naming the position).
+    Not with laneChange (NotImplementedError)."""
+    if not on:
+        self._drop_detectors()
+        return
+    if lane is None and start is None and end is None:
+        if self._detector_tracking():
+            return
+        raise ValueError("track_detectors: give lane, start and end (the tracker is off and has no detectors)")
+    if lane is None or start is None or end is None:
+        raise ValueError("track_detectors: lane, start and end come together")
+    import math
+
+    import numpy as np
+
+    lane = _detector_lanes(lane)
+    start = _detector_edges(start, "start")
+    end = _detector_edges(end, "end")
+    if not len(lane) == len(start) == len(end):
+        raise ValueError("track_detectors: lane, start and end must have one length, not %d, %d and %d" % (len(lane), len(start), len(end)))
+    if not lane:
+        raise ValueError("track_detectors: at least one detector")
+    n_lanes = tuple(self._tensor_shapes()[0])[-1]
+    for i, (l, a, b) in enumerate(zip(lane, start, end)):
+        if not 0 <= l < n_lanes:
+            raise ValueError("track_detectors: lane[%d] = %d is not an index into lane_ids() (position %d; valid: 0 .. %d)" % (i, l, i, n_lanes - 1))
+        if not (math.isfinite(a) and a >= 0.0):
+            raise ValueError("track_detectors: start[%d] = %r is not finite and >= 0 (position %d)" % (i, a, i))
+        if not b > a:
+            raise ValueError("track_detectors: end[%d] = %r is not beyond start[%d] = %r (position %d)" % (i, b, i, a, i))
+    self._define_detectors(np.asarray(lane, dtype=np.int32), np.asarray(start, dtype=np.float64), np.asarray(end, dtype=np.float64))
+
+
+def detector_tracking(self):
+    """Whether track_detectors is on."""
+    return self._detector_tracking()
+
+
+def detector_layout(self):
+    """The detectors in force as they were defined, of ONE environment, as numpy arrays (host only): {"lane": int32 [N],
+    "start": float64 [N], "end": float64 [N]}.  RuntimeError while tracking is off."""
+    if not self._detector_tracking():
+        raise RuntimeError("detector_layout: detector tracking is off (track_detectors(lane, start, end) turns it on)")
+    return dict(zip(("lane", "start", "end"), self._detector_layout()))
+
+
+def _detector_shape(eng, what):
+    """[N] ([R, N] on a VectorEngine).  (While tracking is off there is no N to check a buffer against: RuntimeError here.)"""
+    if not eng._detector_tracking():
+        raise RuntimeError(what + ": detector tracking is off (track_detectors(lane, start, end) turns it on)")
+    return tuple(eng._tensor_shapes()[0])[:-1] + (eng._detector_count(),)
+
+
+def observe_detectors_tensor(self, passed=None, occupied_steps=None, vehicle_steps=None, waiting_vehicle_steps=None, speed_sum=None,
+                             count=None, reset=False):
+    """Fill every given tensor with one kernel launch on the engine's stream, ordered against the current torch stream as
+    observe_lanes_tensor (no host wait).  Detectors in the order of track_detectors (detector_layout()); a detector sees a
+    vehicle's front position only (vehicle length is ignored).  For detector d = (l, start, end): on(l) = the vehicles
+    get_lane_vehicles() lists on lane l, front to back; dis(v), speed(v) as get_vehicle_distance() / get_vehicle_speed();
+    dis'(v) = dis(v) after the previous step if v was on l then; "in the zone" = start <= dis(v) < end.  After every step:
+
+        passed                 int32 [N]    +1 for every v on l with dis(v) >= start that was not on l before or had       \\
+                                            dis'(v) < start; +1 for every v that was on l with dis'(v) < start and has left   |
+                                            l (it went over the rest of the lane in one step)                                 | accumulated
+        occupied_steps         int32 [N]    +1 if at least one vehicle is in the zone                                       | since the last
+        vehicle_steps          int64 [N]    + the vehicles in the zone                                                      | call with
+        waiting_vehicle_steps  int64 [N]    + those of them with speed < 0.1 (as get_lane_waiting_vehicle_count)            | reset=True, or
+        speed_sum              float64 [N]  + t, the zone's speeds added front to back in one running float64 — as            | the baseline
+                                            get_lane_speed_sum_tensor sums a lane; the order is part of the definition      /
+        count                  int32 [N]    now: the vehicles in the zone
+
+    Derived: occupancy = occupied_steps / steps since the reset; space-mean speed = speed_sum / vehicle_steps; a detector
+    (l, 0, inf) gives passed = `entered` of track_lane_flow and count = the lane's vehicle count.  reset=True zeroes the five
+    accumulators in the same launch, after they were read — all five, whether or not they were asked for.  Every element is
+    written.  VectorEngine: a leading [R] on every output.  At least one output; every argument is checked before anything is
+    enqueued; RuntimeError while tracking is off."""
+    _observe_tracker_tensor(
+        self, "observe_detectors_tensor", DETECTOR_OUTPUTS,
+        (passed, occupied_steps, vehicle_steps, waiting_vehicle_steps, speed_sum, count), _detector_dtype,
+        lambda: _detector_shape(self, "observe_detectors_tensor"), self._detector_tracking,
+        "detector tracking is off (track_detectors(lane, start, end) turns it on)",
+        lambda: observe_detectors_array(self, reset=reset), self._observe_detectors_device, (bool(reset),))
+
+
+def observe_detectors_array(self, reset=False):
+    """The six outputs of observe_detectors_tensor as a dict of numpy arrays (same names, dtypes and shapes); waits for the
+    device.  RuntimeError while tracking is off."""
+    shape = _detector_shape(self, "observe_detectors_array")
+    return {name: a.reshape(shape) for name, a in zip(DETECTOR_OUTPUTS, self._detector_features(bool(reset)))}
+
+
 def _plan_shapes(eng):
     """(shape of durations [.., I, P], shape of phase / phase_remain [.., I])."""
     lead = tuple(eng._tensor_shapes()[1])
@@ -866,3 +1030,8 @@ def install(*classes):
         cls.observe_trips_tensor = observe_trips_tensor
         cls.observe_trips_array = observe_trips_array
         cls.get_average_travel_time_tensor = get_average_travel_time_tensor
+        cls.track_detectors = track_detectors
+        cls.detector_tracking = detector_tracking
+        cls.detector_layout = detector_layout
+        cls.observe_detectors_tensor = observe_detectors_tensor
+        cls.observe_detectors_array = observe_detectors_array

@@ -761,6 +761,69 @@ typedef int32_t (*cfx_movement_flow_get_state_fn)(cfx_engine *e, int32_t *record
 typedef int32_t (*cfx_movement_flow_set_state_fn)(cfx_engine *e, const int32_t *records, int32_t n_vehicles,
                                                   const cfx_movement_flow_link *links, int32_t tick);
 
+/* ---- Virtual loop detectors: passage counts, occupancy and speed over zones of lanes, accumulated across steps (OPTIONAL entry
+ * points, as above; not with lane change, not on a tile: CFX_ERR_STATE).  Off by default: nothing is allocated or launched.  A
+ * detector d = (l, start, end) is a zone of lane l in metres from the lane's start, on the scale of the `dis` column of
+ * cfx_get_vehicles; it sees a vehicle's FRONT position only (vehicle length is ignored).  "In the zone": start <= dis(v) < end;
+ * end may be +inf or beyond the lane's length (the zone then reaches to the lane's end).  Any number of detectors per lane, and
+ * they may overlap; a lane without one costs nothing.  With cfx_config::n_envs > 1 the set is ONE environment's (l < n_lanes /
+ * n_envs) and every environment gets it: n_envs * n records and outputs, environment-major.
+ * While it is on, every cfx_step ends with one TICK on the state the step left.  on(l) = the vehicles on lane l, front to back
+ * (the order of cfx_get_vehicles); dis'(v) = dis(v) at the previous tick if v was on l then.  Per detector:
+ *   passed                 int32   += 1 for every v on l with dis(v) >= start that was not on l at the previous tick or had
+ *                                  dis'(v) < start; += 1 for every v that was on l with dis'(v) < start and is on l no longer (it
+ *                                  went over the rest of the lane in one step).  Kept as a difference: with U = the vehicles on l
+ *                                  upstream of start (dis < start), passed += U' - U + entered(l), exact in integers because a
+ *                                  vehicle on a lane never moves backwards and a lane is left at its front only
+ *   occupied_steps         int32   += 1 if a vehicle is in the zone
+ *   vehicle_steps          int64   += the vehicles in the zone
+ *   waiting_vehicle_steps  int64   += those of them with speed < 0.1 (the criterion of cfx_get_lane_waiting_counts)
+ *   speed_sum              double  acc = acc + t, t = the speeds of the zone's vehicles added front to back in one running
+ *                                  double that starts at 0.0 (as the speed_sum of cfx_get_lane_obs adds a lane's)
+ *   count                  int32   not accumulated: the vehicles in the zone as of the last tick
+ * The first five accumulate since the baseline or the last read with reset != 0.  A BASELINE (enabling, defining again,
+ * cfx_reset, cfx_load_state, cfx_checkpoint_restore) counts nothing, zeroes the accumulators and takes count and U as of now:
+ * every vehicle then on a lane was "on it at the previous tick" with its current distance.
+ *   "cfx_detectors_define"         lane[n], start[n], end[n], n >= 1.  Every entry is checked before anything changes: lane in
+ *                                  [0, n_lanes / n_envs), start finite and >= 0, end > start, no NaN — CFX_ERR_INVALID otherwise,
+ *                                  with the position in cfx_last_error.  While the tracker is off the set is only kept; while it
+ *                                  is on the set replaces the one in force and a baseline is taken.
+ *   "cfx_detectors_enable"         on != 0: allocate (16 bytes per vehicle number the tables hold, 64 per detector) and take a
+ *                                  baseline (CFX_ERR_STATE before any cfx_detectors_define); 0: free, the set is forgotten.  While
+ *                                  it is on the ring layout launches every step's commit with the step.
+ *   "cfx_observe_detectors_device" any of the six NULL (at least one given unless reset), all in device memory, copied by ONE
+ *                                  kernel on the engine's stream, ordered against consumer_stream as cfx_observe_device; reset
+ *                                  != 0 zeroes the five accumulators in that launch, after they were read.
+ *   "cfx_get_detectors"            the same into host memory; synchronous.
+ *   "cfx_detectors_get_state" / "cfx_detectors_set_state"  the tracker as it stands, for a host that renumbers the vehicles through
+ *                                  cfx_load_state (which takes a baseline): records[4 v ..] = {lane, tick last seen on it, 0, 0}
+ *                                  of vehicle number v < n_vehicles, detectors[n_detectors] (all environments'), and the tick
+ *                                  counter.  set replaces all three and cancels a pending baseline.  Synchronous. */
+typedef struct cfx_detector {
+    double start, end;           /* the zone */
+    double speed_sum;
+    int64_t vehicle_steps, waiting_vehicle_steps;
+    int32_t lane;                /* of the engine: environment * (n_lanes / n_envs) + l */
+    int32_t upstream;            /* U: vehicles on the lane with dis < start at the last tick */
+    int32_t passed, occupied_steps;
+    int32_t count;               /* vehicles in the zone at the last tick */
+    int32_t reserved;
+} cfx_detector;
+typedef struct cfx_detectors_out {
+    int32_t *passed, *occupied_steps;
+    int64_t *vehicle_steps, *waiting_vehicle_steps;
+    double *speed_sum;
+    int32_t *count;
+} cfx_detectors_out;
+typedef int32_t (*cfx_detectors_define_fn)(cfx_engine *e, const int32_t *lane, const double *start, const double *end, int32_t n);
+typedef int32_t (*cfx_detectors_enable_fn)(cfx_engine *e, int32_t on);
+typedef int32_t (*cfx_observe_detectors_device_fn)(cfx_engine *e, const cfx_detectors_out *out, int32_t reset, void *consumer_stream);
+typedef int32_t (*cfx_get_detectors_fn)(cfx_engine *e, const cfx_detectors_out *out, int32_t reset);
+typedef int32_t (*cfx_detectors_get_state_fn)(cfx_engine *e, int32_t *records, int32_t n_vehicles, cfx_detector *detectors,
+                                              int32_t n_detectors, int32_t *tick);
+typedef int32_t (*cfx_detectors_set_state_fn)(cfx_engine *e, const int32_t *records, int32_t n_vehicles,
+                                              const cfx_detector *detectors, int32_t n_detectors, int32_t tick);
+
 /* ---- The fixed-time signal plan as engine state in device memory (OPTIONAL entry points, as above; not on a tile:
  * CFX_ERR_STATE).  The engine keeps two copies of cfx_net::phase_time: the durations IN FORCE, which TrafficLight::passTime of
  * every step and cfx_reset read, and the FILE's, as cfx_create got them.  Rows are padded to max_phases = max P_i as in

@@ -37,7 +37,15 @@ then a max-pressure loop whose reward (vehicles that crossed a stop line, and th
 comes from observe_movement_flow_tensor(entered, entered_lane_waiting_steps, reset=True), against the same loop with the reward
 built from _vehicle_state() and a numpy diff every step; both rewards are asserted equal over 12 steps first.
 --movement-flow-only trace runs next_step + observe_lane_flow_tensor(reset=True) + observe_movement_flow_tensor(reset=True) alone,
-so that a kernel trace shows kr_lane_flow, k_lane_flow_drain, kr_movement_flow and k_movement_flow_drain side by side."""
+so that a kernel trace shows kr_lane_flow, k_lane_flow_drain, kr_movement_flow and k_movement_flow_drain side by side.
+       python tools/rl_device_loop.py --detectors [--runs N] [--lib PATH] [--detectors-only trace]
+--detectors: what track_detectors costs and saves, with two detectors on every lane, (len - 10, inf) and (len - 100, len - 90) —
+next_step alone with tracking off and on (and, with --lib, tracking off on that other build of the device library), alternated
+--runs times; observe_detectors_tensor(all six, reset=True) alone; then a decision loop that drains every 10 steps against
+get_lane_vehicles() + get_vehicle_distance() + get_vehicle_speed() after every step and the same numbers computed in Python;
+both loops set the lights by max pressure at every drain, and the two are asserted equal over four decisions first.
+--detectors-only trace runs next_step + observe_detectors_tensor alone, so that a kernel trace shows kr_detectors and
+k_detectors_drain beside the step's kernels."""
 import argparse
 import os
 import sys
@@ -63,6 +71,8 @@ ap.add_argument("--trips", action="store_true")
 ap.add_argument("--trips-only", choices=["trace"], default=None)
 ap.add_argument("--movement-flow", action="store_true")
 ap.add_argument("--movement-flow-only", choices=["trace"], default=None)
+ap.add_argument("--detectors", action="store_true")
+ap.add_argument("--detectors-only", choices=["trace"], default=None)
 ap.add_argument("--skip-single", action="store_true", help="--trips: the VectorEngine alone")
 ap.add_argument("--runs", type=int, default=3)
 ap.add_argument("--lib", default="", help="--features: a differently built device library (an A/B against another build)")
@@ -361,6 +371,119 @@ def lane_flow(name, eng, n, runs, only):
     print("python loop / tensor loop %8.1fx" % (float(np.median(res["python"])) / float(np.median(res["tensor"]))), flush=True)
 
 
+def detectors(name, eng, parent, n, runs, only):
+    """`parent`: an engine on another build of the device library (--lib), never tracked, or None."""
+    device = torch.device("cuda", eng._stream_handle()[1])
+    lanes, length = eng.lane_ids(), eng.lane_lengths()
+    L = len(lanes)
+    # two detectors on every lane: a stop-bar zone and an advance detector
+    lane = np.repeat(np.arange(L, dtype=np.int32), 2)
+    start = np.stack((np.maximum(length - 10.0, 0.0), np.maximum(length - 100.0, 0.0)), axis=1).reshape(-1)
+    end = np.stack((np.full(L, np.inf), np.maximum(length - 90.0, 1.0)), axis=1).reshape(-1)
+    N = len(lane)
+    dtypes = {"passed": torch.int32, "occupied_steps": torch.int32, "vehicle_steps": torch.int64, "waiting_vehicle_steps": torch.int64,
+              "speed_sum": torch.float64, "count": torch.int32}
+    out = {k: torch.empty(N, dtype=t, device=device) for k, t in dtypes.items()}
+    every = 10
+
+    lay = eng.intersection_layout()
+    pp = torch.empty(lay["phase_avail"].shape[:2], dtype=torch.int32, device=device)
+
+    def decide():  # (max pressure, so that the traffic keeps moving)
+        eng.observe_intersections_tensor(phase_pressure=pp)
+        eng.set_tl_phases_tensor(pp.argmax(-1))
+
+    def tensor_loop(s):
+        eng.next_step()
+        if s % every == every - 1:
+            eng.observe_detectors_tensor(reset=True, **out)
+            decide()
+
+    prev = {}  # lane -> {vehicle: distance}
+    acc = {k: np.zeros(N, dtype=np.float64 if k == "speed_sum" else np.int64) for k in list(dtypes)[:5]}
+
+    def python_tick():
+        lv, dis, speed = eng.get_lane_vehicles(), eng.get_vehicle_distance(), eng.get_vehicle_speed()
+        for i in range(N):
+            lid, a, b = lanes[lane[i]], start[i], end[i]
+            was, now = prev.get(lid, {}), lv[lid]
+            here = set(now)
+            passed = sum(1 for v in now if dis[v] >= a and (v not in was or was[v] < a)) + sum(1 for v, d in was.items() if v not in here and d < a)
+            zone = [speed[v] for v in now if a <= dis[v] < b]
+            t = 0.0
+            for x in zone:
+                t = t + x
+            acc["passed"][i] += passed
+            acc["occupied_steps"][i] += 1 if zone else 0
+            acc["vehicle_steps"][i] += len(zone)
+            acc["waiting_vehicle_steps"][i] += sum(1 for x in zone if x < 0.1)
+            acc["speed_sum"][i] = acc["speed_sum"][i] + t
+        prev.clear()
+        prev.update({lid: {v: dis[v] for v in vs} for lid, vs in lv.items()})
+
+    def python_loop(s):
+        eng.next_step()
+        python_tick()
+        if s % every == every - 1:
+            for a in acc.values():
+                a[:] = 0
+            decide()
+
+    for _ in range(300):
+        eng.next_step()
+        if parent is not None:
+            parent.next_step()
+    eng.sync()
+    print("# %s, %d detectors" % (name, N), flush=True)
+    if only:
+        eng.track_detectors(lane, start, end)
+        measure("next_step + observe_detectors_tensor(6, reset) every step", eng,
+                lambda s: (eng.next_step(), eng.observe_detectors_tensor(reset=True, **out)), n)
+        return
+    res = {"off": [], "on": [], "parent": []}
+    for r in range(runs):
+        if parent is not None:
+            res["parent"].append(measure("next_step alone, the other library, tracking off (run %d)" % r, parent, lambda s: parent.next_step(), n))
+        eng.track_detectors(on=False)
+        res["off"].append(measure("next_step alone, tracking off (run %d)" % r, eng, lambda s: eng.next_step(), n))
+        eng.track_detectors(lane, start, end)
+        res["on"].append(measure("next_step alone, tracking on  (run %d)" % r, eng, lambda s: eng.next_step(), n))
+    for k, v in res.items():
+        if v:
+            print("%-6s median %8.1f us   min %8.1f   max %8.1f" % (k, float(np.median(v)), min(v), max(v)), flush=True)
+    print("tracking on - off (medians) %8.1f us per step" % (float(np.median(res["on"])) - float(np.median(res["off"]))), flush=True)
+    drain = [measure("observe_detectors_tensor(6 outputs, reset) alone (1 launch + events) (run %d)" % r, eng,
+                     lambda s: eng.observe_detectors_tensor(reset=True, **out), n) for r in range(runs)]
+    print("drain  median %8.1f us   min %8.1f   max %8.1f" % (float(np.median(drain)), min(drain), max(drain)), flush=True)
+    # both sets of numbers from one engine over four decisions, before anything is timed
+    for s in range(4 * every):  # (the lights have stood still so far)
+        tensor_loop(s)
+    eng.track_detectors(lane, start, end)  # (a baseline for both)
+    lv, dis = eng.get_lane_vehicles(), eng.get_vehicle_distance()
+    prev.update({lid: {v: dis[v] for v in vs} for lid, vs in lv.items()})
+    total = 0
+    for s in range(4 * every):
+        eng.next_step()
+        python_tick()
+        if s % every == every - 1:
+            eng.observe_detectors_tensor(reset=True, **out)
+            decide()
+            for k, a in acc.items():
+                assert np.array_equal(out[k].cpu().numpy(), a.astype(out[k].cpu().numpy().dtype)), "decision %d: %s differs" % (s // every, k)
+                total += int(a.sum()) if k == "passed" else 0
+                a[:] = 0
+    assert total > 0
+    print("the detector outputs equal the Python loop's over four decisions (%d passages)" % total, flush=True)
+    n_py = max(n // 20, 2 * every)
+    res = {"tensor": [], "python": []}
+    for r in range(runs):
+        res["tensor"].append(measure("next_step x 10 + observe_detectors_tensor(6, reset), per step (run %d)" % r, eng, tensor_loop, n))
+        res["python"].append(measure("next_step + 3 getters + the same numbers in Python, per step (run %d)" % r, eng, python_loop, n_py))
+    for k, v in res.items():
+        print("%-6s median %10.1f us   min %10.1f   max %10.1f" % (k, float(np.median(v)), min(v), max(v)), flush=True)
+    print("python loop / tensor loop %8.1fx" % (float(np.median(res["python"])) / float(np.median(res["tensor"]))), flush=True)
+
+
 def fronts(name, eng, n, runs, only):
     device = torch.device("cuda", eng._stream_handle()[1])
     n_phases = torch.from_numpy(eng._phase_counts()).to(device).long()
@@ -572,6 +695,13 @@ def movement_flow(name, eng, n, runs, only):
         print("%-6s median %10.1f us   min %10.1f   max %10.1f" % (k, float(np.median(v)), min(v), max(v)), flush=True)
     print("numpy loop / tensor loop %8.1fx" % (float(np.median(res["numpy"])) / float(np.median(res["tensor"]))), flush=True)
 
+
+if args.detectors or args.detectors_only:
+    e = _cityflow.Engine(cfg, 1)
+    p = _cityflow.Engine._with_backend(cfg, 1, os.path.abspath(args.lib)) if args.lib else None
+    detectors("Engine, 30x30 RL workload (%d signals, %d lanes)" % (len(e.intersection_ids()), len(e.lane_ids())), e, p, args.iters,
+              args.runs, args.detectors_only)
+    sys.exit(0)
 
 if args.movement_flow or args.movement_flow_only:
     e = _cityflow.Engine(cfg, 1)
