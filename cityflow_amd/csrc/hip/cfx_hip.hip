@@ -190,6 +190,7 @@ struct cfx_engine {
     int32_t *obsI = nullptr;  // cfx_get_lane_obs: counts, waiting [L each], then front_lane_steps, front_waiting_steps [L * n_front each]
     double *obsD = nullptr;   // ... front_distance, front_speed [L * n_front each]
     size_t obsICap = 0, obsDCap = 0;
+    int32_t *rowTileSum = nullptr;  // cfx_observe_vehicles_device: the scan's tile totals [ceil(D / kRowTile)] (in `owned`)
     // cfx_observe_intersections_device / cfx_get_intersection_features: the intersection -> roadLink -> {start lanes, end lanes,
     // laneLinks} index, built and uploaded by the first call (interTables), and the host getter's device scratch; in `owned`
     bool interBuilt = false;
@@ -4345,6 +4346,69 @@ int32_t cfx_get_lane_features(cfx_engine *e, double *speedSum, int32_t *bins, co
                               int32_t perLaneEdges) {
     const cfx_lane_obs a = laneObsOf(nullptr, nullptr, speedSum, bins, edges, nBins, perLaneEdges);
     return laneObs(e, &a, true, nullptr, "cfx_get_lane_features");
+}
+
+// ---- per-vehicle observations (an optional entry point of include/cityflow_amd.h, as above): k_vehicle_tile_sums, then
+// kr_vehicle_rows / kd_vehicle_rows (cfx_kernels.h has the scheme)
+int32_t cfx_observe_vehicles_device(cfx_engine *e, const cfx_vehicle_rows *rows, void *consumerStream);
+static_assert(std::is_same<decltype(&cfx_observe_vehicles_device), cfx_observe_vehicles_device_fn>::value, "cfx_observe_vehicles_device");
+
+int32_t cfx_observe_vehicles_device(cfx_engine *e, const cfx_vehicle_rows *rows, void *consumerStream) {
+    const char *what = "cfx_observe_vehicles_device";
+    if (!e || !rows || rows->struct_size < (int32_t) sizeof(int32_t)) return CFX_ERR_INVALID;
+    if ((size_t) rows->struct_size > sizeof(cfx_vehicle_rows)) {
+        e->err = std::string(what) + ": struct_size names members this library does not know";
+        return CFX_ERR_INVALID;
+    }
+    cfx_vehicle_rows a{};
+    memcpy(&a, rows, (size_t) rows->struct_size);
+    if (a.n_rows < 0) {
+        e->err = std::string(what) + ": n_rows must not be negative";
+        return CFX_ERR_INVALID;
+    }
+    if (a.n_rows == 0) a.vehicle = a.drivable = a.env = a.leader = nullptr, a.distance = a.speed = a.gap = nullptr;
+    const bool anyRow = a.vehicle || a.drivable || a.env || a.distance || a.speed || a.leader || a.gap;
+    if (!a.start && !a.count && !anyRow) return CFX_ERR_INVALID;
+    if (e->lc.on || e->tiled) {
+        e->err = std::string(what) + ": not with lane change (shadows) and not on a tile";
+        return CFX_ERR_STATE;
+    }
+    auto fail = [e](const std::string &m) { return e->fail(m); };
+    HIP_TRY(hipSetDevice(e->device));
+    int rc;
+    if ((rc = checkDevicePointers(e, what, {{a.start, "start"}, {a.count, "count"}, {a.vehicle, "vehicle"}, {a.drivable, "drivable"},
+                                            {a.env, "env"}, {a.distance, "distance"}, {a.speed, "speed"}, {a.leader, "leader"},
+                                            {a.gap, "gap"}})))
+        return rc;
+    if ((rc = e->settle(false))) return rc;  // (ring layout: a commit deferred to the next step's admission)
+    if ((rc = e->syncTables())) return rc;
+    if (e->ring && (rc = e->ringEnsure())) return rc;
+    const int nEnvs = e->cfg.n_envs > 1 ? e->cfg.n_envs : 1;
+    VehRowsOut o{};
+    o.start = a.start, o.count = a.count;
+    o.vehicle = a.vehicle, o.drivable = a.drivable, o.env = a.env, o.leader = a.leader;
+    o.distance = a.distance, o.speed = a.speed, o.gap = a.gap;
+    o.nRows = a.n_rows;
+    o.nEnvs = nEnvs, o.lanesPerEnv = e->L / nEnvs, o.linksPerEnv = e->K / nEnvs;
+    o.nTiles = (int) std::max<size_t>(1, ((size_t) e->D + kRowTile - 1) / kRowTile);
+    if (!e->rowTileSum && (rc = e->allocRaw(&e->rowTileSum, (size_t) o.nTiles))) return rc;
+    o.tileSum = e->rowTileSum;
+    const int padBlocks = anyRow ? (int) (((size_t) a.n_rows + kRowPadRows - 1) / kRowPadRows) : 0;
+    if ((rc = e->orderAfterCaller((hipStream_t) consumerStream))) return rc;
+    if (e->ring) {
+        const RingCtx c = e->rctx();
+        hipLaunchKernelGGL(k_vehicle_tile_sums, dim3(o.nTiles), dim3(kBlock), 0, e->stream, (const int32_t *) c.cnt, c.n.L, o);
+        hipLaunchKernelGGL(kr_vehicle_rows, dim3(o.nTiles + padBlocks), dim3(kBlock), 0, e->stream, c, o);
+    } else {
+        const StepCtx c = e->ctx();
+        hipLaunchKernelGGL(k_vehicle_tile_sums, dim3(o.nTiles), dim3(kBlock), 0, e->stream, (const int32_t *) c.cnt, c.n.L, o);
+        hipLaunchKernelGGL(kd_vehicle_rows, dim3(o.nTiles + padBlocks), dim3(kBlock), 0, e->stream, c, o);
+    }
+    HIP_TRY(hipGetLastError());
+    if ((rc = e->orderCallerAfter((hipStream_t) consumerStream))) return rc;
+    e->devObserving = true;
+    e->devObserveIdle = 0;
+    return CFX_OK;
 }
 
 // ---- per-intersection movement and phase observations (optional entry points of include/cityflow_amd.h, as above)

@@ -2459,6 +2459,197 @@ __global__ void __launch_bounds__(kBlock) kd_lane_features(StepCtx c, LaneFeatOu
     laneFeatures(o, lane, c.cnt[lane], sub, stage + (threadIdx.x - sub), laneRec(c, lane), laneVid(c, lane));
 }
 
+// cfx_observe_vehicles_device: every running vehicle as a row, rows in CSR order (include/cityflow_amd.h has the outputs).
+// POSITION p = env * D + d numbers the drivables in the order of the rows (environment-major, an environment's lanes before
+// its laneLinks); the device keeps the lanes of all environments before all laneLinks, so `cnt` is read through rowsDrivable.
+// Two launches, no block waits for another:
+//   1. k_vehicle_tile_sums: one block per tile of kRowTile positions adds up the tile's counts -> tileSum[tile]
+//   2. kr_/kd_vehicle_rows: block b < nTiles adds the tile totals before its own (170 values at 30x30, 2.7 k for sixteen
+//      of them: one wavefront reduction of independent loads), scans its tile's counts in LDS and writes `start`; then its groups of kFeatGroup threads take one drivable
+//      each and copy the drivable's records, sixteen neighbouring vehicles at a time, to rows start + i.  The blocks behind
+//      the tiles write the padding: block nTiles + j owns rows [j, j + 1) * kRowPadRows and writes those from `count` on.
+// A thread scans kRowPer neighbouring positions; every store of a row is bounded by nRows.  The tile is small on purpose: a
+// group walks its kRowTile / 16 drivables one after the other, every one a chain of dependent loads (ring geometry -> slot ->
+// record -> template, the head's leader search), so the second launch is bound by that chain times the drivables per group,
+// not by traffic, and what hides it is the number of blocks.
+constexpr int kRowPer = 1;
+constexpr int kRowTile = kRowPer * kBlock;  // (mirrored by cityflow_amd/torch_io.py VEHICLE_ROW_TILE)
+constexpr int kRowPadRows = 8 * kBlock;
+struct VehRowsOut {
+    int32_t *start, *count;
+    int32_t *vehicle, *drivable, *env, *leader;
+    double *distance, *speed, *gap;
+    int nRows;
+    int nEnvs, lanesPerEnv, linksPerEnv;
+    int32_t *tileSum;  // [nTiles]
+    int nTiles;
+};
+
+// position -> the device's drivable index (L = lanes of all environments)
+__device__ __forceinline__ int rowsDrivable(const VehRowsOut &o, int L, int env, int d) {
+    return d < o.lanesPerEnv ? env * o.lanesPerEnv + d : L + env * o.linksPerEnv + (d - o.lanesPerEnv);
+}
+
+// the counts of a thread's kRowPer positions (0 beyond the last position); returns their sum
+__device__ __forceinline__ int rowsLoadCounts(const VehRowsOut &o, const int32_t *cnt, int L, int p0, int (&v)[kRowPer]) {
+    const int D = o.lanesPerEnv + o.linksPerEnv, nPos = o.nEnvs * D;
+    int sum = 0;
+#pragma unroll
+    for (int j = 0; j < kRowPer; ++j) {
+        const int p = p0 + j;
+        v[j] = 0;
+        if (p < nPos) {
+            const int env = p / D;
+            v[j] = cnt[rowsDrivable(o, L, env, p - env * D)];
+        }
+        sum += v[j];
+    }
+    return sum;
+}
+
+// exclusive prefix of `mine` over the block's threads and the block's total: a wavefront scan, the wavefront totals through
+// LDS.  (Its barrier also publishes what the caller wrote to LDS before the call.)
+__device__ __forceinline__ int rowsBlockScan(int mine, int *sWave, int *total) {
+    const int lane = (int) threadIdx.x & 63, wv = (int) threadIdx.x >> 6;
+    int incl = mine;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const int up = __shfl_up(incl, off, 64);
+        if (lane >= off) incl += up;
+    }
+    if (lane == 63) sWave[wv] = incl;
+    __syncthreads();
+    int before = incl - mine, all = 0;
+#pragma unroll
+    for (int i = 0; i < kBlock / 64; ++i) {
+        const int w = sWave[i];
+        if (i < wv) before += w;
+        all += w;
+    }
+    *total = all;
+    return before;
+}
+
+__global__ void __launch_bounds__(kBlock) k_vehicle_tile_sums(const int32_t *cnt, int L, VehRowsOut o) {
+    __shared__ int sWave[kBlock / 64];
+    int v[kRowPer], total;
+    const int mine = rowsLoadCounts(o, cnt, L, (int) blockIdx.x * kRowTile + (int) threadIdx.x * kRowPer, v);
+    rowsBlockScan(mine, sWave, &total);
+    if (threadIdx.x == 0) o.tileSum[blockIdx.x] = total;
+}
+
+// The second launch's body.  drv(d) = the layout's view of device drivable d: drv(d).rec(k) = {dis, speed}, .vid(k) = the
+// vehicle number and .lead(k, dis, &gap) = the leader's vehicle number (-1: none) of its k-th vehicle from the front.
+template <typename Drv>
+__device__ __forceinline__ void vehicleRows(const VehRowsOut o, const int32_t *cnt, int L, Drv drv) {
+    __shared__ int sStart[kRowTile + 1];
+    __shared__ int sWave[kBlock / 64];
+    __shared__ int sBase[2];
+    const int t = (int) threadIdx.x, b = (int) blockIdx.x;
+    if (t < 64) {  // tile totals: those before this block's tile, and all of them (the number of running vehicles)
+        int before = 0, all = 0;
+        for (int i = t; i < o.nTiles; i += 64) {
+            const int s = o.tileSum[i];
+            all += s;
+            if (i < b) before += s;
+        }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            before += __shfl_xor(before, off, 64);
+            all += __shfl_xor(all, off, 64);
+        }
+        if (t == 0) sBase[0] = before, sBase[1] = all;
+    }
+    const bool rows = o.vehicle || o.drivable || o.env || o.distance || o.speed || o.leader || o.gap;
+    if (b >= o.nTiles) {  // padding
+        __syncthreads();
+        const int count = sBase[1];
+        const size_t first = (size_t) (b - o.nTiles) * kRowPadRows;
+        for (int i = t; i < kRowPadRows; i += kBlock) {
+            const size_t row = first + i;
+            if (row < (size_t) count || row >= (size_t) o.nRows) continue;
+            if (o.vehicle) o.vehicle[row] = -1;
+            if (o.drivable) o.drivable[row] = -1;
+            if (o.env) o.env[row] = -1;
+            if (o.distance) o.distance[row] = -1.0;
+            if (o.speed) o.speed[row] = 0.0;
+            if (o.leader) o.leader[row] = -1;
+            if (o.gap) o.gap[row] = 0.0;
+        }
+        return;
+    }
+    const int D = o.lanesPerEnv + o.linksPerEnv, nPos = o.nEnvs * D, base = b * kRowTile;
+    int v[kRowPer], tileTotal;
+    const int mine = rowsLoadCounts(o, cnt, L, base + t * kRowPer, v);
+    int run = rowsBlockScan(mine, sWave, &tileTotal) + sBase[0];
+    const int count = sBase[1];
+#pragma unroll
+    for (int j = 0; j < kRowPer; ++j) {
+        sStart[t * kRowPer + j] = run;
+        run += v[j];
+    }
+    if (t == kBlock - 1) sStart[kRowTile] = run;
+    __syncthreads();
+    if (o.start) {
+        for (int q = t; q < kRowTile; q += kBlock) {
+            const int p = base + q;
+            if (p >= nPos) break;
+            const int env = p / D;
+            o.start[p + env] = sStart[q];  // row env of [D + 1] entries
+            if (p == env * D && env > 0) o.start[p + env - 1] = sStart[q];  // ... and the closing entry of the row before
+        }
+    }
+    if (b == o.nTiles - 1 && t == 0) {
+        if (o.start) o.start[nPos + o.nEnvs - 1] = count;
+        if (o.count) o.count[0] = count;
+    }
+    if (!rows) return;
+    const int sub = t % kFeatGroup;
+    for (int q = t / kFeatGroup; q < kRowTile; q += kBlock / kFeatGroup) {  // (q, n and row0 are the group's)
+        const int p = base + q;
+        if (p >= nPos) break;
+        const int row0 = sStart[q], n = sStart[q + 1] - row0;
+        if (row0 >= o.nRows) break;  // (the rows only go up from here)
+        if (n == 0) continue;
+        const int env = p / D, d = p - env * D;
+        const auto view = drv(rowsDrivable(o, L, env, d));
+        for (int first = 0; first < n; first += kFeatGroup) {
+            const int k = first + sub, row = row0 + k;
+            if (k >= n || row >= o.nRows) continue;
+            const double2 r = view.rec(k);
+            if (o.vehicle) o.vehicle[row] = view.vid(k);
+            if (o.drivable) o.drivable[row] = d;
+            if (o.env) o.env[row] = env;
+            if (o.distance) o.distance[row] = r.x;
+            if (o.speed) o.speed[row] = r.y;
+            if (o.leader || o.gap) {
+                double gap = 0.0;
+                const int leader = view.lead(k, r.x, &gap);
+                if (o.leader) o.leader[row] = leader;
+                if (o.gap) o.gap[row] = leader >= 0 ? gap : 0.0;
+            }
+        }
+    }
+}
+
+// dense layout: the segment of the current generation; the leader as k_leader_view finds it
+struct DenseDrvRows {
+    const StepCtx &c;
+    int d, base;
+    __device__ __forceinline__ double2 rec(int k) const { return make_double2(c.s.dis[base + k], c.s.speed[base + k]); }
+    __device__ __forceinline__ int vid(int k) const { return c.s.vid[base + k]; }
+    __device__ __forceinline__ int lead(int k, double dis, double *gap) const {
+        const int s = base + k;
+        const int ls = findLeader(c, c.t.templ, s, d, k == 0, dis, c.t.templ[c.s.templ[s]].approach_dist, gap);
+        if (ls < 0) return -1;
+        if (c.s.flags[s] & kFlagStateGap) *gap = c.vGapState[c.s.vid[s]];  // not stepped since the load
+        return c.s.vid[ls];
+    }
+};
+__global__ void __launch_bounds__(kBlock) kd_vehicle_rows(StepCtx c, VehRowsOut o) {
+    vehicleRows(o, c.cnt, c.n.L, [&](int d) { return DenseDrvRows{c, d, c.segStart[d]}; });
+}
+
 // cfx_lane_flow_enable: per-lane flow and waiting-time statistics across steps (include/cityflow_amd.h has the rules).  One TICK
 // after every step, on the committed state: a group of kFeatGroup threads walks one lane as laneFeatures does, sixteen
 // neighbouring vehicles at a time, and each thread does the read-modify-write of its vehicle's 16-byte record

@@ -2408,6 +2408,33 @@ __global__ void __launch_bounds__(kBlock) kr_lane_features(RingCtx c, LaneFeatOu
     laneFeatures(o, lane, c.cnt[lane], sub, stage + (threadIdx.x - sub), laneRec(c, lane), laneVid(c, lane));
 }
 
+// cfx_observe_vehicles_device, ring layout: vehicleRows (cfx_kernels.h) over the ring of every drivable; the leader and gap as
+// kr_gather finds them (the vehicle ahead in the ring; the head of a drivable through findHeadLeader)
+struct RingDrvRows {
+    const RingCtx &c;
+    int d;
+    RingLaneRec kin;
+    __device__ __forceinline__ double2 rec(int k) const { return kin(k); }
+    __device__ __forceinline__ int vid(int k) const { return c.s.vid[ringSlot(kin.geo, kin.head, k)]; }
+    __device__ __forceinline__ int lead(int k, double dis, double *gap) const {
+        const int s = ringSlot(kin.geo, kin.head, k);
+        const int4 mv = c.meta[s];
+        int ls;
+        if (k > 0) {
+            ls = ringSlot(kin.geo, kin.head, k - 1);
+            *gap = c.kin[ls].x - c.t.templ[c.meta[ls].x].len - dis;
+        } else {
+            ls = findHeadLeader(c, c.t.templ, s, d, dis, c.t.templ[mv.x].approach_dist, mv.y, c.n.drvLength[d], gap).slot;
+        }
+        if (ls < 0) return -1;
+        if (mv.z & kFlagStateGap) *gap = c.vGapState[c.s.vid[s]];  // not stepped since the load: the state's gap
+        return c.s.vid[ls];
+    }
+};
+__global__ void __launch_bounds__(kBlock) kr_vehicle_rows(RingCtx c, VehRowsOut o) {
+    vehicleRows(o, c.cnt, c.n.L, [&](int d) { return RingDrvRows{c, d, laneRec(c, d)}; });
+}
+
 // cfx_lane_flow_enable, ring layout: laneFlowTick (cfx_kernels.h) over the lane's ring, the vehicle numbers from the cold `vid` column
 __global__ void __launch_bounds__(kBlock) kr_lane_flow(RingCtx c, LaneFlowDev f) {
     const int lane = (int) ((blockIdx.x * (size_t) blockDim.x + threadIdx.x) / kFeatGroup);

@@ -95,6 +95,7 @@ void Backend::open(const std::string &libPath) {
     CFX_FN_OPTIONAL(cfx_get_lane_features)
     CFX_FN_OPTIONAL(cfx_observe_lane_obs_device)
     CFX_FN_OPTIONAL(cfx_get_lane_obs)
+    CFX_FN_OPTIONAL(cfx_observe_vehicles_device)
     CFX_FN_OPTIONAL(cfx_observe_intersections_device)
     CFX_FN_OPTIONAL(cfx_get_intersection_features)
     CFX_FN_OPTIONAL(cfx_lane_flow_enable)
@@ -660,6 +661,86 @@ void observeLanesDeviceOf(const Backend &be, cfx_engine *dev, const cfx_lane_obs
     if (be.cfx_observe_lanes_device(dev, obs.counts, obs.waiting, obs.speed_sum, obs.bins, obs.edges, obs.n_bins, obs.per_lane_edges,
                                     (void *) consumerStream) != CFX_OK)
         backendFail(be, dev, "cfx_observe_lanes_device");
+}
+
+void observeVehiclesDeviceOf(const Backend &be, cfx_engine *dev, const cfx_vehicle_rows &rows, uintptr_t consumerStream) {
+    if (!be.hasDeviceBuffers() || !be.cfx_observe_vehicles_device)
+        throw std::runtime_error("cityflow_amd: '" + be.path + "' has no device-side vehicle observations");
+    if (be.cfx_observe_vehicles_device(dev, &rows, (void *) consumerStream) != CFX_OK) backendFail(be, dev, "cfx_observe_vehicles_device");
+}
+
+VehicleRows vehicleRowsOf(const Backend &be, cfx_engine *dev, int nEnvs, int nLanes, int nLaneLinks) {
+    cfx_scalars sc{};
+    if (be.cfx_get_scalars(dev, &sc) != CFX_OK) backendFail(be, dev, "cfx_get_scalars");
+    std::vector<int32_t> vid, drv, leader;
+    std::vector<double> dis, speed, gap;
+    int count = 0;
+    for (int cap = (int) sc.active_vehicle_count + 16;;) {
+        cfx_vehicle_view v{};
+        v.capacity = cap;
+        for (auto *c : {&vid, &drv, &leader}) c->resize((size_t) cap);
+        for (auto *c : {&dis, &speed, &gap}) c->resize((size_t) cap);
+        v.vid = vid.data(), v.drivable = drv.data(), v.leader_vid = leader.data();
+        v.dis = dis.data(), v.speed = speed.data(), v.gap = gap.data();
+        const int32_t rc = be.cfx_get_vehicles(dev, &v);
+        if (rc == CFX_ERR_CAPACITY && v.count > cap) {
+            cap = v.count + 16;
+            continue;
+        }
+        if (rc != CFX_OK) backendFail(be, dev, "cfx_get_vehicles");
+        count = v.count;
+        break;
+    }
+    // the backend lists the lanes of all environments before all laneLinks: a vehicle's position in environment-major order
+    const int D = nLanes + nLaneLinks, allLanes = nEnvs * nLanes;
+    auto position = [&](int g) {
+        const bool lane = g < allLanes;
+        const int k = lane ? g : g - allLanes, per = lane ? nLanes : nLaneLinks;
+        return (k / per) * D + (lane ? 0 : nLanes) + k % per;
+    };
+    VehicleRows out;
+    out.count = count;
+    out.start.assign((size_t) nEnvs * (D + 1), 0);
+    std::vector<int32_t> perPos((size_t) nEnvs * D + 1, 0);
+    for (int i = 0; i < count; ++i) {
+        if (drv[(size_t) i] < 0 || drv[(size_t) i] >= nEnvs * D) throw std::runtime_error("cityflow_amd: cfx_get_vehicles names a drivable the network does not have");
+        perPos[(size_t) position(drv[(size_t) i])] += 1;
+    }
+    int32_t run = 0;
+    for (size_t p = 0; p <= (size_t) nEnvs * D; ++p) {  // counts -> offsets
+        const int32_t n = perPos[p];
+        perPos[p] = run;
+        run += n;
+    }
+    for (int r = 0; r < nEnvs; ++r)
+        for (int d = 0; d <= D; ++d) out.start[(size_t) r * (D + 1) + d] = perPos[(size_t) r * D + d];
+    const size_t n = (size_t) count;
+    out.vehicle.resize(n), out.drivable.resize(n), out.env.resize(n), out.leader.resize(n);
+    out.distance.resize(n), out.speed.resize(n), out.gap.resize(n);
+    for (int i = 0; i < count; ++i) {  // (front to back inside a drivable: the view's order is kept)
+        const int p = position(drv[(size_t) i]);
+        const size_t row = (size_t) perPos[(size_t) p]++;
+        out.vehicle[row] = vid[(size_t) i];
+        out.drivable[row] = p % D;
+        out.env[row] = p / D;
+        out.distance[row] = dis[(size_t) i];
+        out.speed[row] = speed[(size_t) i];
+        out.leader[row] = leader[(size_t) i];
+        out.gap[row] = leader[(size_t) i] >= 0 ? gap[(size_t) i] : 0.0;
+    }
+    return out;
+}
+
+VehicleRows EngineHost::vehicleRows() {
+    if (laneChange_) throw std::runtime_error("observe_vehicles: not with laneChange (a shadow is a second row of its vehicle)");
+    VehicleRows rows = vehicleRowsOf(be_, dev_, 1, (int) net_->lanes.size(), (int) net_->laneLinks.size());
+    raiseDeviceError();
+    return rows;
+}
+
+void EngineHost::observeVehiclesDevice(const cfx_vehicle_rows &rows, uintptr_t consumerStream) {
+    if (laneChange_) throw std::runtime_error("observe_vehicles: not with laneChange (a shadow is a second row of its vehicle)");
+    observeVehiclesDeviceOf(be_, dev_, rows, consumerStream);
 }
 
 VehicleColumns vehicleColumnsOf(const Backend &be, cfx_engine *dev, bool vid, bool dis, bool speed) {

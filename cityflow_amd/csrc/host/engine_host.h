@@ -89,6 +89,8 @@ struct Backend {
     // first the tensor calls have no front outputs; without the second the host takes them from cfx_get_vehicles)
     cfx_observe_lane_obs_device_fn cfx_observe_lane_obs_device = nullptr;
     cfx_get_lane_obs_fn cfx_get_lane_obs = nullptr;
+    // optional on its own: per-vehicle rows in device memory (without it the host fills them from cfx_get_vehicles: vehicleRowsOf)
+    cfx_observe_vehicles_device_fn cfx_observe_vehicles_device = nullptr;
     // optional as a pair: per-intersection observations (without them the host computes the arrays from the getters above)
     cfx_observe_intersections_device_fn cfx_observe_intersections_device = nullptr;
     cfx_get_intersection_features_fn cfx_get_intersection_features = nullptr;
@@ -228,6 +230,18 @@ struct VehicleColumns {
 };
 VehicleColumns vehicleColumnsOf(const Backend &be, cfx_engine *dev, bool vid, bool dis, bool speed);  // (drivable always)
 
+// Every running vehicle as a row, in CSR form (cfx_observe_vehicles_device's outputs and order, include/cityflow_amd.h): the
+// rows by environment, then by drivable within it (lanes, then laneLinks), front to back; start [nEnvs * (D + 1)].
+struct VehicleRows {
+    std::vector<int32_t> start, vehicle, drivable, env, leader;
+    std::vector<double> distance, speed, gap;
+    int count = 0;
+};
+// ... on any backend, from cfx_get_vehicles (nLanes / nLaneLinks: of ONE environment; throws std::runtime_error)
+VehicleRows vehicleRowsOf(const Backend &be, cfx_engine *dev, int nEnvs, int nLanes, int nLaneLinks);
+// ... into device memory: every pointer of `rows` a device address (cfx_observe_vehicles_device)
+void observeVehiclesDeviceOf(const Backend &be, cfx_engine *dev, const cfx_vehicle_rows &rows, uintptr_t consumerStream);
+
 // A checkpoint in device memory (cfx_checkpoint_* of include/cityflow_amd.h; the public calls are checkpoint() / rollback() of
 // cityflow_amd/torch_io.py), of an EngineHost or a VectorEngineHost: the backend's part, and what Engine.load() takes from an
 // Archive on the host — the spawners' states (one per environment) and the step — plus what an Archive does not carry.  It
@@ -334,6 +348,11 @@ public:
     // ---- the first k vehicles of every lane from the front (cfx_get_lane_obs; the twin: from the vehicles and the host tracker).
     //      [n_lanes * k] each, any may be null; the two tracker columns need trackLaneFlow(true) (std::runtime_error)
     void laneFronts(int k, const LaneFronts &out);
+    // ---- every running vehicle as a row (VehicleRows above; std::runtime_error with laneChange: shadows)
+    bool vehicleRowsDevice() const { return be_.hasDeviceBuffers() && be_.cfx_observe_vehicles_device; }
+    std::pair<int, int> drivableCounts() const { return {(int) net_->lanes.size(), (int) net_->laneLinks.size()}; }
+    VehicleRows vehicleRows();
+    void observeVehiclesDevice(const cfx_vehicle_rows &rows, uintptr_t consumerStream);
     // ---- per-intersection movement and phase observations (cfx_observe_intersections_device / cfx_get_intersection_features;
     //      the twin: from the count getters, the vehicles and the lights).  Rows of layout().M roadLinks / layout().P phases
     const InterLayout &intersectionLayout();

@@ -400,6 +400,30 @@ void observeLanesDevice(E &e, uintptr_t counts, uintptr_t waiting, uintptr_t spe
     e.observeLanesDevice(a, consumerStream);
 }
 
+// ---- every running vehicle as a row (Engine and VectorEngine; the public calls are cityflow_amd/torch_io.py)
+template <typename E> py::tuple vehicleRowsTuple(E &e) {
+    const cfa::VehicleRows r = e.vehicleRows();
+    return py::make_tuple(toArray(r.start), r.count, toArray(r.vehicle), toArray(r.drivable), toArray(r.env), toArray(r.distance),
+                          toArray(r.speed), toArray(r.leader), toArray(r.gap));
+}
+template <typename E>
+void observeVehiclesDevice(E &e, uintptr_t start, uintptr_t count, uintptr_t vehicle, uintptr_t drivable, uintptr_t env, uintptr_t distance,
+                           uintptr_t speed, uintptr_t leader, uintptr_t gap, int nRows, uintptr_t consumerStream) {
+    cfx_vehicle_rows a{};
+    a.struct_size = (int32_t) sizeof a;
+    a.n_rows = nRows;
+    a.start = (int32_t *) start;
+    a.count = (int32_t *) count;
+    a.vehicle = (int32_t *) vehicle;
+    a.drivable = (int32_t *) drivable;
+    a.env = (int32_t *) env;
+    a.distance = (double *) distance;
+    a.speed = (double *) speed;
+    a.leader = (int32_t *) leader;
+    a.gap = (double *) gap;
+    e.observeVehiclesDevice(a, consumerStream);
+}
+
 // ---- trip statistics across steps (Engine and VectorEngine; the public calls are cityflow_amd/torch_io.py)
 inline py::ssize_t tripEnvs(EngineHost &) { return 1; }
 inline py::ssize_t tripEnvs(cfa::VectorEngineHost &e) { return (py::ssize_t) e.numEnvs(); }
@@ -538,6 +562,14 @@ template <typename E> void defDeviceBuffers(py::class_<E> &c) {
         .def("_lane_fronts", [](E &e, int k, bool tracker) { return laneFrontsTuple(e, k, tracker); }, "k"_a, "tracker"_a,
              "(distance, speed, lane_steps, waiting_steps) of the first k vehicles of every lane, flat (env-major); the last two "
              "empty unless `tracker`")
+        .def("_vehicle_rows_device", &E::vehicleRowsDevice, "the backend writes the vehicle rows in device memory")
+        .def("_drivable_counts", &E::drivableCounts, "(lanes, laneLinks) of one environment")
+        .def("_lane_change", &E::laneChange)
+        .def("_vehicle_rows", [](E &e) { return vehicleRowsTuple(e); },
+             "(start, count, vehicle, drivable, env, distance, speed, leader, gap): every running vehicle as a row, environment-"
+             "major, `start` flat [envs * (D + 1)]; waits for the device")
+        .def("_observe_vehicles_device", &observeVehiclesDevice<E>, "start_ptr"_a, "count_ptr"_a, "vehicle_ptr"_a, "drivable_ptr"_a,
+             "env_ptr"_a, "distance_ptr"_a, "speed_ptr"_a, "leader_ptr"_a, "gap_ptr"_a, "n_rows"_a, "consumer_stream"_a)
         .def("_intersection_dims", [](E &e) { return py::make_tuple(e.intersectionLayout().M, e.intersectionLayout().P); },
              "(largest roadLink count, largest phase count) of an intersection: the row lengths of the intersection observations")
         .def("_intersection_layout", [](E &e) { return intersectionLayoutDict(e); })

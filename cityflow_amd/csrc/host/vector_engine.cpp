@@ -828,6 +828,20 @@ void VectorEngineHost::laneFronts(int k, const LaneFronts &out) {
     raiseDeviceError();
 }
 
+VehicleRows VectorEngineHost::vehicleRows() {
+    if (laneChange_) throw std::runtime_error("observe_vehicles: not with laneChange (a shadow is a second row of its vehicle)");
+    std::lock_guard<std::mutex> guard(queryMutex_);  // (the ABI is not re-entrant: the ahead thread may be asking the device)
+    VehicleRows rows = vehicleRowsOf(be_, dev_, R_, L_, K_);
+    raiseDeviceError();
+    return rows;
+}
+
+void VectorEngineHost::observeVehiclesDevice(const cfx_vehicle_rows &rows, uintptr_t consumerStream) {
+    if (laneChange_) throw std::runtime_error("observe_vehicles: not with laneChange (a shadow is a second row of its vehicle)");
+    std::lock_guard<std::mutex> guard(queryMutex_);
+    observeVehiclesDeviceOf(be_, dev_, rows, consumerStream);
+}
+
 void VectorEngineHost::trackLaneFlow(bool on) {
     if (on && laneChange_) throw std::logic_error("track_lane_flow: not with laneChange (a shadow changes identity when its change finishes)");
     std::lock_guard<std::mutex> guard(queryMutex_);

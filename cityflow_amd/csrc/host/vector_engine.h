@@ -82,6 +82,12 @@ public:
     void laneFeatures(double *speedSum, int32_t *bins, const double *edges, int nBins, bool perLaneEdges);
     void observeLanesDevice(const cfx_lane_obs &obs, uintptr_t consumerStream);
     void laneFronts(int k, const LaneFronts &out);  // [R * L * k] each
+    // every running vehicle as a row, environment-major (EngineHost::vehicleRows and its kin); {L, K} of one environment
+    bool vehicleRowsDevice() const { return be_.hasDeviceBuffers() && be_.cfx_observe_vehicles_device; }
+    std::pair<int, int> drivableCounts() const { return {L_, K_}; }
+    bool laneChange() const { return laneChange_; }
+    VehicleRows vehicleRows();
+    void observeVehiclesDevice(const cfx_vehicle_rows &rows, uintptr_t consumerStream);
     // per-intersection observations over every environment (EngineHost::intersectionFeatures and its kin): outputs [R * I ...];
     // the layout is one environment's
     const InterLayout &intersectionLayout();

@@ -11,6 +11,11 @@
     eng.get_lane_front_vehicles_tensor(k, distance=None, speed=None)
                                                          float64 [L, k] each: the k vehicles nearest every lane's end
     eng.get_lane_front_vehicles_array(k)                 the front outputs as numpy arrays (waits for the device)
+    eng.observe_vehicles_tensor(start=None, count=None, vehicle=None, drivable=None, env=None, distance=None, speed=None,
+                                leader=None, gap=None)   every running vehicle as a row, grouped by drivable (CSR): int32
+                                                         start [D+1] ([R, D+1]) and count (0-dim), and rows [N] of the caller's N;
+                                                         two kernel launches, no host wait (see its docstring)
+    eng.observe_vehicles_array()                         the same outputs as numpy arrays, exactly `count` rows (waits for the device)
     eng.observe_intersections_tensor(phase=None, phase_remain=None, movement_in=None, movement_in_waiting=None,
                                      movement_out=None, movement_inside=None, phase_pressure=None)
                                                          per-intersection observations, one kernel launch (see its docstring)
@@ -996,8 +1001,118 @@ def rollback_envs(self, checkpoint, envs=None):
 rollback_envs.__name__ = rollback_envs.__qualname__ = "rollback"  # (VectorEngine.rollback)
 
 
+VEHICLE_ROW_TILE = 256  # kRowTile: drivables per scan tile of the vehicle-row kernels
+VEHICLE_ROW_OUTPUTS = ("vehicle", "drivable", "env", "distance", "speed", "leader", "gap")
+VEHICLE_ROW_PADDING = {"vehicle": -1, "drivable": -1, "env": -1, "distance": -1.0, "speed": 0.0, "leader": -1, "gap": 0.0}
+_VEHICLE_ROW_FLOATS = ("distance", "speed", "gap")
+
+
+def _vehicle_rows(eng):
+    """The array form: {name: numpy array} of `start`, `count` and the seven row outputs with exactly `count` rows."""
+    import numpy as np
+
+    if eng._lane_change():
+        raise RuntimeError("observe_vehicles: not with laneChange (a shadow is a second row of its vehicle)")
+    lanes, links = eng._drivable_counts()
+    lead = tuple(eng._tensor_shapes()[0])[:-1]
+    got = eng._vehicle_rows()
+    out = {"start": got[0].reshape(lead + (lanes + links + 1,)), "count": np.array(got[1], dtype=np.int32)}
+    out.update(zip(VEHICLE_ROW_OUTPUTS, got[2:]))
+    return out
+
+
+def observe_vehicles_array(self):
+    """The outputs of observe_vehicles_tensor as a dict of numpy arrays (same names and dtypes): `start`, `count` (0-dim) and
+    the seven row outputs with exactly `count` rows, so no padding.  Waits for the device.  RuntimeError with laneChange."""
+    return _vehicle_rows(self)
+
+
+def observe_vehicles_tensor(self, start=None, count=None, vehicle=None, drivable=None, env=None, distance=None, speed=None,
+                            leader=None, gap=None):
+    """Every running vehicle — on a lane or on a laneLink inside an intersection — as one row of the given tensors, in CSR
+    form, filled by two kernel launches on the engine's stream, ordered against the current torch stream as
+    observe_lanes_tensor.  D = L + K drivables per environment: 0 .. L-1 are lane_ids(), L .. L+K-1 the laneLinks.
+
+    Row order: by drivable, front to back inside one (nearest the drivable's end first, the order of get_lane_vehicles()).
+    VectorEngine: environment-major — environment 0's lanes, then its laneLinks, then environment 1's — so an environment's
+    vehicles are one contiguous run of rows.
+
+        start     int32 [D+1] ([R, D+1])  start[d]: row of the first vehicle of drivable d; start[D]: one past the last
+                                          (start[r, D] == start[r+1, 0]).  The true offsets even when the rows are too short.
+        count     int32 0-dim             the true number of running vehicles
+
+    and the row outputs, all [N] with ONE N >= 0 of the caller's choosing:
+
+        vehicle   int32    the engine's vehicle number (Engine._vehicle_id(n) names it; unique across the environments of a
+                           VectorEngine).  It stays the vehicle's while it lives and the numbers are not assigned anew
+                           (reset, load, rollback, a vehicle compaction)                                      padding -1
+        drivable  int32    index in [0, D) within its environment                                             padding -1
+        env       int32    environment (0 on an Engine)                                                       padding -1
+        distance  float64  as get_vehicle_distance()                                                          padding -1.0
+        speed     float64  as get_vehicle_speed()                                                             padding 0.0
+        leader    int32    vehicle number of the leader (get_leader()), -1 if none                            padding -1
+        gap       float64  the gap to the leader, 0.0 where leader is -1; a vehicle not stepped since a load
+                           reports the loaded state's gap                                                     padding 0.0
+
+    Row i < min(count, N) is vehicle i; rows from count to N hold the padding; every element of every given tensor is
+    written.  If count > N the rows beyond N are dropped and nothing is written outside a tensor.  The call never waits for
+    the device, which is why N is the caller's and count stays on the device: size N once, e.g. from get_vehicle_count() with
+    head room.  The leader is looked for only if leader or gap is given.
+
+    At least one output (start and / or count alone are allowed); every argument is checked before anything is enqueued.  A
+    backend without device buffers takes CPU tensors and fills them from observe_vehicles_array().  RuntimeError with
+    laneChange: true (a shadow would be a second row of its vehicle)."""
+    torch = _torch()
+    rows = dict(zip(VEHICLE_ROW_OUTPUTS, (vehicle, drivable, env, distance, speed, leader, gap)))
+    if start is None and count is None and all(t is None for t in rows.values()):
+        raise ValueError("observe_vehicles_tensor: give at least one of start, count, " + ", ".join(VEHICLE_ROW_OUTPUTS))
+    lanes, links = self._drivable_counts()
+    lead = tuple(self._tensor_shapes()[0])[:-1]
+    device = _engine_device(torch, self)
+    if start is not None:
+        _check_buf(torch, start, "start", lead + (lanes + links + 1,), torch.int32, device)
+    if count is not None:
+        _check_buf(torch, count, "count", (), torch.int32, device)
+    n_rows = None
+    for name, t in rows.items():
+        if t is None:
+            continue
+        if not isinstance(t, torch.Tensor):
+            raise TypeError("%s must be a torch.Tensor, not %s" % (name, type(t).__name__))
+        if n_rows is None:
+            if t.dim() != 1:
+                raise ValueError("%s must have shape [N], not %s" % (name, tuple(t.shape)))
+            n_rows = int(t.shape[0])
+        _check_buf(torch, t, name, (n_rows,), torch.float64 if name in _VEHICLE_ROW_FLOATS else torch.int32, device)
+    if n_rows is not None and n_rows >= 2 ** 31:
+        raise ValueError("the row outputs hold fewer than 2**31 rows, not %d" % n_rows)
+    if self._lane_change():
+        raise RuntimeError("observe_vehicles_tensor: not with laneChange (a shadow is a second row of its vehicle)")
+    if not self._device_buffers() or not self._vehicle_rows_device():  # (the twin, an older library: over the array call)
+        arrays = _vehicle_rows(self)
+        n = int(arrays["count"])
+        if start is not None:
+            start.copy_(torch.from_numpy(arrays["start"]))
+        if count is not None:
+            count.copy_(torch.from_numpy(arrays["count"]))
+        for name, t in rows.items():
+            if t is None:
+                continue
+            keep = min(n, n_rows)
+            t[:keep].copy_(torch.from_numpy(arrays[name][:keep]))
+            t[keep:].fill_(VEHICLE_ROW_PADDING[name])
+        return
+    if not n_rows and start is None and count is None:
+        return  # (tensors without an element: nothing to write)
+    ptr = lambda t: 0 if t is None or t.numel() == 0 else t.data_ptr()  # noqa: E731
+    self._observe_vehicles_device(ptr(start), ptr(count), *[ptr(rows[name]) for name in VEHICLE_ROW_OUTPUTS], n_rows or 0,
+                                  torch.cuda.current_stream(device).cuda_stream)
+
+
 def install(*classes):
     for cls in classes:
+        cls.observe_vehicles_tensor = observe_vehicles_tensor
+        cls.observe_vehicles_array = observe_vehicles_array
         cls.checkpoint = checkpoint
         cls.rollback = rollback_envs if hasattr(cls, "_rollback_envs") else rollback
         cls.set_tl_plan_tensor = set_tl_plan_tensor

@@ -581,6 +581,36 @@ typedef struct cfx_lane_obs {
 typedef int32_t (*cfx_observe_lane_obs_device_fn)(cfx_engine *e, const cfx_lane_obs *obs, void *consumer_stream);
 typedef int32_t (*cfx_get_lane_obs_fn)(cfx_engine *e, const cfx_lane_obs *obs);
 
+/* ---- Per-vehicle observations in device memory (an OPTIONAL entry point, as above): every running vehicle, those on laneLinks
+ * included, as rows in CSR form.  D = (n_lanes + n_lanelinks) / n_envs drivables per environment, numbered lanes first
+ * (0 .. lanes per environment - 1), then laneLinks; the rows are ordered by environment, then by that number, then front to
+ * back inside a drivable (one environment: the order of cfx_get_vehicles).
+ *   start[r * (D + 1) + d]  int32: the row of the first vehicle of drivable d of environment r; entry D of a row is one past
+ *                           the environment's last vehicle (= entry 0 of the next row).  The true offsets whatever n_rows is.
+ *   count[0]                int32: the number of running vehicles
+ *   row outputs [n_rows]    vehicle  int32: the vehicle number (cfx_spawn::vid)                                  padding -1
+ *                           drivable int32: in [0, D), within the environment                                    padding -1
+ *                           env      int32                                                                        padding -1
+ *                           distance double: dis, a copy                                                          padding -1.0
+ *                           speed    double: a copy                                                               padding 0.0
+ *                           leader   int32: vehicle number of the leader as cfx_get_vehicles' leader_vid, -1 none padding -1
+ *                           gap      double: cfx_get_vehicles' gap where leader >= 0, 0.0 where it is -1           padding 0.0
+ * Row i < min(count, n_rows) is vehicle i, rows from count to n_rows hold the padding: every element of a given output is
+ * written, nothing beyond n_rows.  Any pointer may be NULL (at least one of start, count or - with n_rows > 0 - a row output
+ * given); all device memory.  The descriptor's struct_size as cfx_lane_obs's.  Two kernels on the engine's stream, ordered
+ * against consumer_stream as cfx_observe_device; the call never waits for the device (the first call allocates a few KB).
+ * CFX_ERR_STATE with lane change (shadows) and on a tile. */
+typedef struct cfx_vehicle_rows {
+    int32_t struct_size;
+    int32_t n_rows;              /* elements of every row output, >= 0 */
+    int32_t *start, *count;
+    int32_t *vehicle, *drivable, *env;
+    double *distance, *speed;
+    int32_t *leader;
+    double *gap;
+} cfx_vehicle_rows;
+typedef int32_t (*cfx_observe_vehicles_device_fn)(cfx_engine *e, const cfx_vehicle_rows *rows, void *consumer_stream);
+
 /* ---- Per-intersection movement and phase observations (OPTIONAL entry points, as above).  Intersection i (n_inters of them,
  * virtual ones included) has its roadLinks m < M_i = inter_n_roadlinks[i] ("movements", ll_roadlink) and its phases p < P_i
  * (inter_phase_start; 0 for a virtual intersection).  IN(i, m) / OUT(i, m) are the DISTINCT start / end lanes of the roadLink's
