@@ -191,6 +191,11 @@ struct cfx_engine {
     double *obsD = nullptr;   // ... front_distance, front_speed [L * n_front each]
     size_t obsICap = 0, obsDCap = 0;
     int32_t *rowTileSum = nullptr;  // cfx_observe_vehicles_device: the scan's tile totals [ceil(D / kRowTile)] (in `owned`)
+    // cfx_set_vehicle_speeds_device / cfx_set_vehicle_speeds: the row that commands each vehicle number [speedStampCap], all -1
+    // between calls; the host form's rows and its count in device memory (all in `owned`)
+    int32_t *speedStamp = nullptr, *speedRowsV = nullptr, *speedIgnored = nullptr;
+    double *speedRowsS = nullptr;
+    size_t speedStampCap = 0, speedRowsCap = 0;
     // cfx_observe_intersections_device / cfx_get_intersection_features: the intersection -> roadLink -> {start lanes, end lanes,
     // laneLinks} index, built and uploaded by the first call (interTables), and the host getter's device scratch; in `owned`
     bool interBuilt = false;
@@ -4408,6 +4413,108 @@ int32_t cfx_observe_vehicles_device(cfx_engine *e, const cfx_vehicle_rows *rows,
     if ((rc = e->orderCallerAfter((hipStream_t) consumerStream))) return rc;
     e->devObserving = true;
     e->devObserveIdle = 0;
+    return CFX_OK;
+}
+
+// ---- speed commands for many vehicles at once (optional entry points of include/cityflow_amd.h, as above): k_speeds_claim,
+// k_speeds_apply and, on the dense layout, k_speeds_flag_dense (cfx_kernels.h has the scheme)
+int32_t cfx_set_vehicle_speeds_device(cfx_engine *e, const int32_t *vehicle, const double *speed, int32_t n, int32_t *ignored,
+                                      void *producerStream);
+int32_t cfx_set_vehicle_speeds(cfx_engine *e, const int32_t *vehicle, const double *speed, int32_t n, int32_t *ignored);
+static_assert(std::is_same<decltype(&cfx_set_vehicle_speeds_device), cfx_set_vehicle_speeds_device_fn>::value, "cfx_set_vehicle_speeds_device");
+static_assert(std::is_same<decltype(&cfx_set_vehicle_speeds), cfx_set_vehicle_speeds_fn>::value, "cfx_set_vehicle_speeds");
+
+// what both forms check first
+static int vehicleSpeedsArgs(cfx_engine *e, const int32_t *vehicle, const double *speed, int32_t n, const char *what) {
+    if (n < 0 || (n > 0 && (!vehicle || !speed))) {
+        e->err = std::string(what) + ": n must not be negative, and vehicle and speed are needed for n > 0";
+        return CFX_ERR_INVALID;
+    }
+    if (e->lc.on || e->tiled) {
+        e->err = std::string(what) + ": not with lane change (the vehicle numbers are cfx_observe_vehicles_device's) and not on a tile";
+        return CFX_ERR_STATE;
+    }
+    return CFX_OK;
+}
+
+// the kernels of one call on the engine's stream; every pointer device memory, `ignored` may be null.  The caller has settled.
+static int launchVehicleSpeeds(cfx_engine *e, const int32_t *vehicle, const double *speed, int32_t n, int32_t *ignored) {
+    auto fail = [e](const std::string &m) { return e->fail(m); };
+    if (ignored) HIP_TRY(hipMemsetAsync(ignored, 0, sizeof(int32_t), e->stream));
+    if (n == 0) return CFX_OK;
+    int rc;
+    if ((rc = e->syncTables())) return rc;
+    if (e->ring && (rc = e->ringEnsure())) return rc;
+    if (e->speedStampCap < (size_t) e->spawned) {  // (idle: nothing to keep, the new one starts out all -1)
+        const size_t cap = std::max<size_t>(e->vidCap, (size_t) e->spawned);
+        int32_t *stamp = nullptr;
+        if ((rc = e->allocRaw(&stamp, cap))) return rc;
+        HIP_TRY(hipMemsetAsync(stamp, 0xFF, std::max<size_t>(cap, 1) * sizeof(int32_t), e->stream));
+        if (e->speedStamp) e->retired.push_back(e->speedStamp);
+        e->speedStamp = stamp;
+        e->speedStampCap = cap;
+    }
+    const VehSpeedsIn in{vehicle, speed, n, (int) e->spawned, e->speedStamp, ignored};
+    const dim3 grid((unsigned) (((size_t) n + kBlock - 1) / kBlock));
+    hipLaunchKernelGGL(k_speeds_claim, grid, dim3(kBlock), 0, e->stream, in, (const uint8_t *) e->vt.state);
+    if (e->ring) {
+        const RingCtx c = e->rctx();
+        hipLaunchKernelGGL(k_speeds_apply, grid, dim3(kBlock), 0, e->stream, in, e->vt, (const int32_t *) c.slotOf, c.meta);
+    } else {
+        hipLaunchKernelGGL(k_speeds_apply, grid, dim3(kBlock), 0, e->stream, in, e->vt, (const int32_t *) nullptr, (int4 *) nullptr);
+        hipLaunchKernelGGL(k_speeds_flag_dense, dim3(gridStride(e->slotCap)), dim3(kBlock), 0, e->stream, e->ctx(), e->speedStamp, in.nVid);
+    }
+    HIP_TRY(hipGetLastError());
+    return CFX_OK;
+}
+
+int32_t cfx_set_vehicle_speeds_device(cfx_engine *e, const int32_t *vehicle, const double *speed, int32_t n, int32_t *ignored,
+                                      void *producerStream) {
+    const char *what = "cfx_set_vehicle_speeds_device";
+    if (!e) return CFX_ERR_INVALID;
+    int rc;
+    if ((rc = vehicleSpeedsArgs(e, vehicle, speed, n, what))) return rc;
+    auto fail = [e](const std::string &m) { return e->fail(m); };
+    HIP_TRY(hipSetDevice(e->device));
+    if ((rc = checkDevicePointers(e, what, {{n ? vehicle : nullptr, "vehicle"}, {n ? speed : nullptr, "speed"}, {ignored, "ignored"}})))
+        return rc;
+    if (n == 0 && !ignored) return CFX_OK;
+    if ((rc = e->settle(false))) return rc;  // (ring layout: a commit deferred to the next step's admission)
+    if ((rc = e->orderAfterCaller((hipStream_t) producerStream))) return rc;
+    if ((rc = launchVehicleSpeeds(e, vehicle, speed, n, ignored))) return rc;
+    return e->orderCallerAfter((hipStream_t) producerStream);  // (the count is there; the rows may be overwritten)
+}
+
+int32_t cfx_set_vehicle_speeds(cfx_engine *e, const int32_t *vehicle, const double *speed, int32_t n, int32_t *ignored) {
+    const char *what = "cfx_set_vehicle_speeds";
+    if (!e) return CFX_ERR_INVALID;
+    int rc;
+    if ((rc = vehicleSpeedsArgs(e, vehicle, speed, n, what))) return rc;
+    if (ignored) *ignored = 0;
+    if (n == 0) return CFX_OK;
+    auto fail = [e](const std::string &m) { return e->fail(m); };
+    HIP_TRY(hipSetDevice(e->device));
+    if ((rc = e->settle(false))) return rc;
+    if (!e->speedIgnored && (rc = e->allocRaw(&e->speedIgnored, 1))) return rc;
+    if (e->speedRowsCap < (size_t) n) {  // (the stream is idle whenever the rows are: every call ends with a wait)
+        const size_t cap = std::max<size_t>((size_t) n, 2 * e->speedRowsCap);
+        int32_t *v = nullptr;
+        double *s = nullptr;
+        if ((rc = e->allocRaw(&v, cap)) || (rc = e->allocRaw(&s, cap))) return rc;
+        for (void *old : {(void *) e->speedRowsV, (void *) e->speedRowsS})
+            if (old) {
+                e->forget(old);
+                HIP_TRY(hipFree(old));
+            }
+        e->speedRowsV = v, e->speedRowsS = s, e->speedRowsCap = cap;
+    }
+    HIP_TRY(hipMemcpyAsync(e->speedRowsV, vehicle, (size_t) n * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipMemcpyAsync(e->speedRowsS, speed, (size_t) n * sizeof(double), hipMemcpyHostToDevice, e->stream));
+    if ((rc = launchVehicleSpeeds(e, e->speedRowsV, e->speedRowsS, n, e->speedIgnored))) return rc;
+    int32_t count = 0;
+    HIP_TRY(hipMemcpyAsync(&count, e->speedIgnored, sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    if (ignored) *ignored = count;
     return CFX_OK;
 }
 

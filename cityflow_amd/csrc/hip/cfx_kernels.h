@@ -1845,6 +1845,73 @@ __global__ void k_set_speed(StepCtx c, int vid) {
         if (c.s.vid[s] == vid) c.s.flags[s] |= 1;
 }
 
+// cfx_set_vehicle_speeds_device: Vehicle::setCustomSpeed for n rows {vehicle number, speed} in device memory (include/
+// cityflow_amd.h has the row rules).  A vehicle named by several rows takes the row with the highest index, whatever order
+// the threads run in: `stamp` [nVid] is idle at -1 between calls;
+//   1. k_speeds_claim: every row that commands a live vehicle does atomicMax(stamp[v], row); the rows that name a vehicle
+//      the engine does not have or that has finished are counted, a ballot per wavefront and one atomic per wavefront
+//   2. k_speeds_apply: the row that finds its own index in stamp[v] writes the speed, marks the vehicle (waiting:
+//      pendingCustom; running, ring layout: the flag of its slot through slotOf) and puts the stamp back to -1
+//   3. dense layout only (no slotOf): the apply leaves the stamp of a RUNNING vehicle standing, and k_speeds_flag_dense, one
+//      pass over the slots, raises the flag of every slot whose vehicle carries a stamp and clears the stamp there (a running
+//      vehicle has exactly one slot) — one pass for the whole call where k_set_speed takes one per vehicle
+// Every index is checked against nVid before it is used; the rows are only read.
+struct VehSpeedsIn {
+    const int32_t *vehicle;  // [n]
+    const double *speed;     // [n]
+    int n, nVid;             // nVid: the vehicle numbers issued (cfx_engine::spawned when the call was made)
+    int32_t *stamp;          // [>= nVid]
+    int32_t *ignored;        // [1] or null
+};
+// does row i take part (a vehicle number other than the padding, a speed other than NaN)?  *v, *s: its values
+__device__ __forceinline__ bool speedsRow(const VehSpeedsIn &in, size_t i, int *v, double *s) {
+    if (i >= (size_t) in.n) return false;
+    *v = in.vehicle[i];
+    *s = in.speed[i];
+    return *v != -1 && *s == *s;
+}
+__global__ void __launch_bounds__(kBlock) k_speeds_claim(VehSpeedsIn in, const uint8_t *state) {
+    const size_t i = blockIdx.x * (size_t) blockDim.x + threadIdx.x;  // (a row only below n: the cast to int below is exact)
+    int v = -1;
+    double s = 0.0;
+    bool bad = false;
+    if (speedsRow(in, i, &v, &s)) {
+        bad = v < 0 || v >= in.nVid || state[v] == 2;
+        if (!bad) atomicMax(&in.stamp[v], (int) i);
+    }
+    if (in.ignored) {  // (no thread has left: the whole wavefront votes)
+        const unsigned long long votes = __ballot(bad);
+        if ((threadIdx.x & 63) == 0 && votes) atomicAdd(in.ignored, __popcll(votes));
+    }
+}
+__global__ void __launch_bounds__(kBlock) k_speeds_apply(VehSpeedsIn in, VidTable vt, const int32_t *slotOf, int4 *meta) {
+    const size_t i = blockIdx.x * (size_t) blockDim.x + threadIdx.x;
+    int v = -1;
+    double s = 0.0;
+    if (!speedsRow(in, i, &v, &s) || v < 0 || v >= in.nVid) return;
+    if (in.stamp[v] != (int) i) return;  // (a finished vehicle was never claimed: -1)
+    vt.customSpeed[v] = s;
+    const uint8_t st = vt.state[v];
+    if (st == 0) vt.pendingCustom[v] = 1;
+    else if (slotOf) {
+        const int slot = slotOf[v];
+        if (slot >= 0) meta[slot].z |= kFlagCustom;
+    } else {
+        return;  // dense layout: k_speeds_flag_dense finds the slot and clears the stamp
+    }
+    in.stamp[v] = -1;
+}
+__global__ void __launch_bounds__(kBlock) k_speeds_flag_dense(StepCtx c, int32_t *stamp, int nVid) {
+    const int S = c.segStart[c.n.L + c.n.K];
+    const int stride = gridDim.x * blockDim.x;
+    for (int s = blockIdx.x * blockDim.x + threadIdx.x; s < S; s += stride) {
+        const int v = c.s.vid[s];
+        if (v < 0 || v >= nVid || stamp[v] < 0) continue;
+        c.s.flags[s] |= kFlagCustom;
+        stamp[v] = -1;
+    }
+}
+
 // Router::setRoute (router.cpp:245-255) after the host's checks: new route, iCurRoad = begin
 __global__ void k_set_route(StepCtx c, int vid, int route) {
     const int S = c.segStart[c.n.L + c.n.K];

@@ -96,6 +96,8 @@ void Backend::open(const std::string &libPath) {
     CFX_FN_OPTIONAL(cfx_observe_lane_obs_device)
     CFX_FN_OPTIONAL(cfx_get_lane_obs)
     CFX_FN_OPTIONAL(cfx_observe_vehicles_device)
+    CFX_FN_OPTIONAL(cfx_set_vehicle_speeds_device)
+    CFX_FN_OPTIONAL(cfx_set_vehicle_speeds)
     CFX_FN_OPTIONAL(cfx_observe_intersections_device)
     CFX_FN_OPTIONAL(cfx_get_intersection_features)
     CFX_FN_OPTIONAL(cfx_lane_flow_enable)
@@ -741,6 +743,63 @@ VehicleRows EngineHost::vehicleRows() {
 void EngineHost::observeVehiclesDevice(const cfx_vehicle_rows &rows, uintptr_t consumerStream) {
     if (laneChange_) throw std::runtime_error("observe_vehicles: not with laneChange (a shadow is a second row of its vehicle)");
     observeVehiclesDeviceOf(be_, dev_, rows, consumerStream);
+}
+
+void setVehicleSpeedsDeviceOf(const Backend &be, cfx_engine *dev, uintptr_t vehicle, uintptr_t speed, int n, uintptr_t ignored,
+                              uintptr_t producerStream) {
+    if (!be.hasDeviceBuffers() || !be.cfx_set_vehicle_speeds_device)
+        throw std::runtime_error("cityflow_amd: '" + be.path + "' has no device-side vehicle speed commands");
+    if (be.cfx_set_vehicle_speeds_device(dev, (const int32_t *) vehicle, (const double *) speed, (int32_t) n, (int32_t *) ignored,
+                                         (void *) producerStream) != CFX_OK)
+        backendFail(be, dev, "cfx_set_vehicle_speeds_device");
+}
+
+int setVehicleSpeedsOf(const Backend &be, cfx_engine *dev, const int32_t *vehicle, const double *speed, int n,
+                       std::map<int32_t, double> *waitingCommands) {
+    if (be.cfx_set_vehicle_speeds) {
+        int32_t ignored = 0;
+        if (be.cfx_set_vehicle_speeds(dev, vehicle, speed, (int32_t) n, &ignored) != CFX_OK) backendFail(be, dev, "cfx_set_vehicle_speeds");
+        return (int) ignored;
+    }
+    // row by row over cfx_set_vehicle_speed: alive is what cfx_get_vehicles (running) and cfx_get_waiting list; a later row
+    // of the same vehicle is a later call and wins
+    auto skipped = [&](int i) { return vehicle[i] == -1 || std::isnan(speed[i]); };
+    int first = 0;
+    while (first < n && skipped(first)) ++first;
+    if (first == n) return 0;
+    std::map<int32_t, bool> waitingOf;  // alive vehicle -> still waiting
+    const VehicleColumns running = vehicleColumnsOf(be, dev, true, false, false);
+    for (int i = 0; i < running.count; ++i) waitingOf[running.vid[(size_t) i]] = false;
+    cfx_scalars sc{};
+    if (be.cfx_get_scalars(dev, &sc) != CFX_OK) backendFail(be, dev, "cfx_get_scalars");
+    std::vector<int32_t> wVid((size_t) sc.spawned_vehicle_count + 16), wLane(wVid.size());
+    int32_t nWaiting = 0;
+    if (be.cfx_get_waiting(dev, (int32_t) wVid.size(), wVid.data(), wLane.data(), &nWaiting) != CFX_OK) backendFail(be, dev, "cfx_get_waiting");
+    for (int i = 0; i < nWaiting; ++i) waitingOf[wVid[(size_t) i]] = true;
+    int ignored = 0;
+    for (int i = first; i < n; ++i) {
+        if (skipped(i)) continue;
+        const auto it = waitingOf.find(vehicle[i]);
+        if (it == waitingOf.end()) {
+            ignored += 1;
+            continue;
+        }
+        if (be.cfx_set_vehicle_speed(dev, vehicle[i], speed[i]) != CFX_OK) backendFail(be, dev, "cfx_set_vehicle_speed");
+        if (it->second && waitingCommands) (*waitingCommands)[vehicle[i]] = speed[i];
+    }
+    return ignored;
+}
+
+void EngineHost::setVehicleSpeedsDevice(uintptr_t vehicle, uintptr_t speed, int n, uintptr_t ignored, uintptr_t producerStream) {
+    if (laneChange_) throw std::runtime_error("set_vehicle_speeds: not with laneChange (the vehicle numbers are observe_vehicles')");
+    setVehicleSpeedsDeviceOf(be_, dev_, vehicle, speed, n, ignored, producerStream);
+}
+
+int EngineHost::setVehicleSpeeds(const int32_t *vehicle, const double *speed, int n) {
+    if (laneChange_) throw std::runtime_error("set_vehicle_speeds: not with laneChange (the vehicle numbers are observe_vehicles')");
+    const int ignored = setVehicleSpeedsOf(be_, dev_, vehicle, speed, n, &waitingCustom_);
+    raiseDeviceError();
+    return ignored;
 }
 
 VehicleColumns vehicleColumnsOf(const Backend &be, cfx_engine *dev, bool vid, bool dis, bool speed) {

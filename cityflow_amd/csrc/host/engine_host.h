@@ -91,6 +91,9 @@ struct Backend {
     cfx_get_lane_obs_fn cfx_get_lane_obs = nullptr;
     // optional on its own: per-vehicle rows in device memory (without it the host fills them from cfx_get_vehicles: vehicleRowsOf)
     cfx_observe_vehicles_device_fn cfx_observe_vehicles_device = nullptr;
+    // optional as a pair: speed commands for many vehicles at once (without them the host commands row by row: setVehicleSpeedsOf)
+    cfx_set_vehicle_speeds_device_fn cfx_set_vehicle_speeds_device = nullptr;
+    cfx_set_vehicle_speeds_fn cfx_set_vehicle_speeds = nullptr;
     // optional as a pair: per-intersection observations (without them the host computes the arrays from the getters above)
     cfx_observe_intersections_device_fn cfx_observe_intersections_device = nullptr;
     cfx_get_intersection_features_fn cfx_get_intersection_features = nullptr;
@@ -242,6 +245,15 @@ VehicleRows vehicleRowsOf(const Backend &be, cfx_engine *dev, int nEnvs, int nLa
 // ... into device memory: every pointer of `rows` a device address (cfx_observe_vehicles_device)
 void observeVehiclesDeviceOf(const Backend &be, cfx_engine *dev, const cfx_vehicle_rows &rows, uintptr_t consumerStream);
 
+// Speed commands for n rows {vehicle number, speed} (cfx_set_vehicle_speeds_device's rules, include/cityflow_amd.h).  From device
+// memory: every pointer a device address, `ignored` may be 0.  From host arrays, on any backend: over cfx_set_vehicle_speeds, or
+// row by row over cfx_set_vehicle_speed with the vehicles alive taken from cfx_get_vehicles / cfx_get_waiting — and then the
+// rows that commanded a vehicle still waiting are added to `waitingCommands` (may be null).  Returns the rows ignored.
+void setVehicleSpeedsDeviceOf(const Backend &be, cfx_engine *dev, uintptr_t vehicle, uintptr_t speed, int n, uintptr_t ignored,
+                              uintptr_t producerStream);
+int setVehicleSpeedsOf(const Backend &be, cfx_engine *dev, const int32_t *vehicle, const double *speed, int n,
+                       std::map<int32_t, double> *waitingCommands);
+
 // A checkpoint in device memory (cfx_checkpoint_* of include/cityflow_amd.h; the public calls are checkpoint() / rollback() of
 // cityflow_amd/torch_io.py), of an EngineHost or a VectorEngineHost: the backend's part, and what Engine.load() takes from an
 // Archive on the host — the spawners' states (one per environment) and the step — plus what an Archive does not carry.  It
@@ -353,6 +365,12 @@ public:
     std::pair<int, int> drivableCounts() const { return {(int) net_->lanes.size(), (int) net_->laneLinks.size()}; }
     VehicleRows vehicleRows();
     void observeVehiclesDevice(const cfx_vehicle_rows &rows, uintptr_t consumerStream);
+    // ---- speed commands for many vehicles at once, by the vehicle numbers of the rows above (setVehicleSpeedsOf above;
+    //      std::runtime_error with laneChange).  A command the device takes for a vehicle still in its entry buffer is not
+    //      in waitingCustom_: a vehicle compaction before that vehicle's first step drops it
+    bool vehicleSpeedsDevice() const { return be_.hasDeviceBuffers() && be_.cfx_set_vehicle_speeds_device; }
+    void setVehicleSpeedsDevice(uintptr_t vehicle, uintptr_t speed, int n, uintptr_t ignored, uintptr_t producerStream);
+    int setVehicleSpeeds(const int32_t *vehicle, const double *speed, int n);
     // ---- per-intersection movement and phase observations (cfx_observe_intersections_device / cfx_get_intersection_features;
     //      the twin: from the count getters, the vehicles and the lights).  Rows of layout().M roadLinks / layout().P phases
     const InterLayout &intersectionLayout();

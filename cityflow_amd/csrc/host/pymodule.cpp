@@ -570,6 +570,16 @@ template <typename E> void defDeviceBuffers(py::class_<E> &c) {
              "major, `start` flat [envs * (D + 1)]; waits for the device")
         .def("_observe_vehicles_device", &observeVehiclesDevice<E>, "start_ptr"_a, "count_ptr"_a, "vehicle_ptr"_a, "drivable_ptr"_a,
              "env_ptr"_a, "distance_ptr"_a, "speed_ptr"_a, "leader_ptr"_a, "gap_ptr"_a, "n_rows"_a, "consumer_stream"_a)
+        .def("_vehicle_speeds_device", &E::vehicleSpeedsDevice, "the backend takes vehicle speed commands from device memory")
+        .def("_set_vehicle_speeds_device", &E::setVehicleSpeedsDevice, "vehicle_ptr"_a, "speed_ptr"_a, "n"_a, "ignored_ptr"_a,
+             "producer_stream"_a)
+        .def("_set_vehicle_speeds",
+             [](E &e, py::array_t<int32_t, py::array::c_style> vehicle, py::array_t<double, py::array::c_style> speed) {
+                 if (vehicle.ndim() != 1 || speed.ndim() != 1 || vehicle.size() != speed.size())
+                     throw std::invalid_argument("set_vehicle_speeds: vehicle and speed must be one-dimensional and of one length");
+                 return e.setVehicleSpeeds(vehicle.data(), speed.data(), (int) vehicle.size());
+             },
+             "vehicle"_a, "speed"_a, "int32 [N] vehicle numbers, float64 [N] speeds; returns the rows ignored; waits for the device")
         .def("_intersection_dims", [](E &e) { return py::make_tuple(e.intersectionLayout().M, e.intersectionLayout().P); },
              "(largest roadLink count, largest phase count) of an intersection: the row lengths of the intersection observations")
         .def("_intersection_layout", [](E &e) { return intersectionLayoutDict(e); })

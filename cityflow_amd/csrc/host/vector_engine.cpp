@@ -842,6 +842,20 @@ void VectorEngineHost::observeVehiclesDevice(const cfx_vehicle_rows &rows, uintp
     observeVehiclesDeviceOf(be_, dev_, rows, consumerStream);
 }
 
+void VectorEngineHost::setVehicleSpeedsDevice(uintptr_t vehicle, uintptr_t speed, int n, uintptr_t ignored, uintptr_t producerStream) {
+    if (laneChange_) throw std::runtime_error("set_vehicle_speeds: not with laneChange (the vehicle numbers are observe_vehicles')");
+    std::lock_guard<std::mutex> guard(queryMutex_);
+    setVehicleSpeedsDeviceOf(be_, dev_, vehicle, speed, n, ignored, producerStream);
+}
+
+int VectorEngineHost::setVehicleSpeeds(const int32_t *vehicle, const double *speed, int n) {
+    if (laneChange_) throw std::runtime_error("set_vehicle_speeds: not with laneChange (the vehicle numbers are observe_vehicles')");
+    std::lock_guard<std::mutex> guard(queryMutex_);
+    const int ignored = setVehicleSpeedsOf(be_, dev_, vehicle, speed, n, nullptr);
+    raiseDeviceError();
+    return ignored;
+}
+
 void VectorEngineHost::trackLaneFlow(bool on) {
     if (on && laneChange_) throw std::logic_error("track_lane_flow: not with laneChange (a shadow changes identity when its change finishes)");
     std::lock_guard<std::mutex> guard(queryMutex_);

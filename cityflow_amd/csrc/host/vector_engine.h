@@ -88,6 +88,10 @@ public:
     bool laneChange() const { return laneChange_; }
     VehicleRows vehicleRows();
     void observeVehiclesDevice(const cfx_vehicle_rows &rows, uintptr_t consumerStream);
+    // speed commands by those vehicle numbers, vehicles of any environment in one call (EngineHost::setVehicleSpeeds and its kin)
+    bool vehicleSpeedsDevice() const { return be_.hasDeviceBuffers() && be_.cfx_set_vehicle_speeds_device; }
+    void setVehicleSpeedsDevice(uintptr_t vehicle, uintptr_t speed, int n, uintptr_t ignored, uintptr_t producerStream);
+    int setVehicleSpeeds(const int32_t *vehicle, const double *speed, int n);
     // per-intersection observations over every environment (EngineHost::intersectionFeatures and its kin): outputs [R * I ...];
     // the layout is one environment's
     const InterLayout &intersectionLayout();

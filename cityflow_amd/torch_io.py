@@ -16,6 +16,11 @@
                                                          start [D+1] ([R, D+1]) and count (0-dim), and rows [N] of the caller's N;
                                                          two kernel launches, no host wait (see its docstring)
     eng.observe_vehicles_array()                         the same outputs as numpy arrays, exactly `count` rows (waits for the device)
+    eng.set_vehicle_speeds_tensor(vehicle, speed, ignored=None)
+                                                         set_vehicle_speed() for the rows of int32 [N] vehicle numbers (those of
+                                                         observe_vehicles_tensor) and float64 [N] speeds, NaN = leave alone;
+                                                         two or three kernel launches, no host wait (see its docstring)
+    eng.set_vehicle_speeds(vehicle, speed) -> int        the same from numpy arrays; returns the rows ignored (waits for the device)
     eng.observe_intersections_tensor(phase=None, phase_remain=None, movement_in=None, movement_in_waiting=None,
                                      movement_out=None, movement_inside=None, phase_pressure=None)
                                                          per-intersection observations, one kernel launch (see its docstring)
@@ -1109,8 +1114,85 @@ def observe_vehicles_tensor(self, start=None, count=None, vehicle=None, drivable
                                   torch.cuda.current_stream(device).cuda_stream)
 
 
+def set_vehicle_speeds(self, vehicle, speed):
+    """The numpy form of set_vehicle_speeds_tensor: `vehicle` int32 [N] vehicle numbers (observe_vehicles_array()'s),
+    `speed` float64 [N]; returns the number of rows ignored.  Needs no torch; waits for the device.  On a backend without
+    device buffers the host commands the vehicles row by row.  RuntimeError with laneChange."""
+    import numpy as np
+
+    for name, a, dtype in (("vehicle", vehicle, np.int32), ("speed", speed, np.float64)):
+        if not isinstance(a, np.ndarray):
+            raise TypeError("%s must be a numpy array, not %s" % (name, type(a).__name__))
+        if a.dtype != dtype:
+            raise TypeError("%s must be %s, not %s" % (name, np.dtype(dtype).name, a.dtype))
+        if a.ndim != 1:
+            raise ValueError("%s must have shape [N], not %s" % (name, a.shape))
+        if not a.flags.c_contiguous:
+            raise ValueError("%s must be contiguous" % name)
+    if vehicle.shape != speed.shape:
+        raise ValueError("speed must have shape %s as vehicle, not %s" % (vehicle.shape, speed.shape))
+    if vehicle.shape[0] >= 2 ** 31:
+        raise ValueError("a call holds fewer than 2**31 rows, not %d" % vehicle.shape[0])
+    if self._lane_change():
+        raise RuntimeError("set_vehicle_speeds: not with laneChange (the vehicle numbers are observe_vehicles')")
+    return int(self._set_vehicle_speeds(vehicle, speed))
+
+
+def set_vehicle_speeds_tensor(self, vehicle, speed, ignored=None):
+    """set_vehicle_speed() for many vehicles at once, from tensors: row i commands the vehicle with the engine's number
+    vehicle[i] — the numbers observe_vehicles_tensor() writes — to drive at speed[i] in its next step, and only in that one
+    (Vehicle::setCustomSpeed: the speed is taken as it is, negative and infinite values included, and car following may still
+    slow the vehicle down further).  A vehicle still in its lane's entry buffer keeps the speed for its first step.
+
+        vehicle   int32   [N]    N >= 0
+        speed     float64 [N]    NaN: leave this vehicle alone
+        ignored   int32   0-dim  optional output: the rows that named no vehicle to command
+
+        vehicle[i] == -1 (observe_vehicles_tensor's padding) or speed[i] NaN      skipped, not counted
+        vehicle[i] < -1, a number not issued yet, a vehicle that has finished      skipped, counted in `ignored`
+        a running or waiting vehicle                                               commanded
+
+    A vehicle named by several commanding rows takes the one with the HIGHEST row index (rows with NaN do not compete), so
+    the result never depends on the device's scheduling.  Calls take effect in the order they are made, set_vehicle_speed()
+    among them: the later call wins.  "Issued" are the numbers as of the last step; a vehicle pushed since has none yet
+    (set_vehicle_speed(id, ...) serves it).  On a VectorEngine the numbers are unique across the environments, and one call
+    commands vehicles of any of them.  Numbers go stale where observe_vehicles_tensor says they do (reset, load, rollback, a
+    vehicle compaction); a compaction also drops a command that a vehicle in an entry buffer has not used yet.
+
+    Two kernel launches on the engine's stream (three on the dense layout), ordered after the current torch stream; the torch
+    stream is ordered after them, so `ignored` can be read there and the inputs reused.  The call never waits for the device.
+    Every argument is checked before anything is enqueued.  A backend without device buffers takes CPU tensors and goes
+    through set_vehicle_speeds().  RuntimeError with laneChange: true."""
+    torch = _torch()
+    device = _engine_device(torch, self)
+    if not isinstance(vehicle, torch.Tensor):
+        raise TypeError("vehicle must be a torch.Tensor, not %s" % type(vehicle).__name__)
+    if vehicle.dim() != 1:
+        raise ValueError("vehicle must have shape [N], not %s" % (tuple(vehicle.shape),))
+    n_rows = int(vehicle.shape[0])
+    _check_buf(torch, vehicle, "vehicle", (n_rows,), torch.int32, device)
+    _check_buf(torch, speed, "speed", (n_rows,), torch.float64, device)
+    if ignored is not None:
+        _check_buf(torch, ignored, "ignored", (), torch.int32, device)
+    if n_rows >= 2 ** 31:
+        raise ValueError("a call holds fewer than 2**31 rows, not %d" % n_rows)
+    if self._lane_change():
+        raise RuntimeError("set_vehicle_speeds_tensor: not with laneChange (the vehicle numbers are observe_vehicles')")
+    if not self._device_buffers() or not self._vehicle_speeds_device():  # (the twin, an older library: over the array call)
+        count = set_vehicle_speeds(self, vehicle.detach().numpy(), speed.detach().numpy())
+        if ignored is not None:
+            ignored.fill_(count)
+        return
+    if n_rows == 0 and ignored is None:
+        return
+    ptr = lambda t: 0 if t is None or t.numel() == 0 else t.data_ptr()  # noqa: E731
+    self._set_vehicle_speeds_device(ptr(vehicle), ptr(speed), n_rows, ptr(ignored), torch.cuda.current_stream(device).cuda_stream)
+
+
 def install(*classes):
     for cls in classes:
+        cls.set_vehicle_speeds_tensor = set_vehicle_speeds_tensor
+        cls.set_vehicle_speeds = set_vehicle_speeds
         cls.observe_vehicles_tensor = observe_vehicles_tensor
         cls.observe_vehicles_array = observe_vehicles_array
         cls.checkpoint = checkpoint

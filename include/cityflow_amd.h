@@ -611,6 +611,23 @@ typedef struct cfx_vehicle_rows {
 } cfx_vehicle_rows;
 typedef int32_t (*cfx_observe_vehicles_device_fn)(cfx_engine *e, const cfx_vehicle_rows *rows, void *consumer_stream);
 
+/* ---- Speed commands for many vehicles at once (OPTIONAL entry points, as above; both or none): Vehicle::setCustomSpeed, as
+ * cfx_set_vehicle_speed, for n rows {vehicle[i], speed[i]}, n >= 0.  The vehicle numbers are cfx_observe_vehicles_device's.
+ *   vehicle[i] == -1 (that call's padding) or speed[i] NaN      the row is skipped and not counted
+ *   vehicle[i] < -1, vehicle[i] >= the numbers issued when the call is made (the vehicles the next cfx_step will create are not
+ *   among them: cfx_set_vehicle_speed serves those), or a finished vehicle      the row is skipped and counted in ignored[0]
+ *   a waiting or running vehicle      the speed - any other double, untouched - holds for the vehicle's next step
+ * A vehicle named by several rows of the second and third kind takes the row with the highest index.  Calls take effect in
+ * the order they are made, cfx_set_vehicle_speed among them.  ignored (int32[1]) may be NULL.
+ * _device: vehicle, speed and ignored are device memory; two kernels on the engine's stream (three on the dense layout: one
+ * pass over the slots for the whole call), ordered against producer_stream as cfx_set_tl_phases_device; the call never waits
+ * for the device (it allocates 4 bytes per vehicle number when the numbers have outgrown its scratch).  The host form reads
+ * host arrays, runs the same kernels on staging the engine keeps, and waits for the count.
+ * CFX_ERR_STATE with lane change (the numbers are cfx_observe_vehicles_device's) and on a tile. */
+typedef int32_t (*cfx_set_vehicle_speeds_device_fn)(cfx_engine *e, const int32_t *vehicle, const double *speed, int32_t n,
+                                                    int32_t *ignored, void *producer_stream);
+typedef int32_t (*cfx_set_vehicle_speeds_fn)(cfx_engine *e, const int32_t *vehicle, const double *speed, int32_t n, int32_t *ignored);
+
 /* ---- Per-intersection movement and phase observations (OPTIONAL entry points, as above).  Intersection i (n_inters of them,
  * virtual ones included) has its roadLinks m < M_i = inter_n_roadlinks[i] ("movements", ll_roadlink) and its phases p < P_i
  * (inter_phase_start; 0 for a virtual intersection).  IN(i, m) / OUT(i, m) are the DISTINCT start / end lanes of the roadLink's

@@ -12,7 +12,22 @@
   python tools/vehicle_rows_loop.py --trace [--which bench|vector16] [--iters 50]
       the workload for a `rocprofv3 --kernel-trace --stats` run of its own: `iters` observe_vehicles_tensor calls with all
       outputs (k_vehicle_tile_sums, kr_vehicle_rows), then as many _vehicle_state() calls where the engine has one (kr_offsets,
-      kr_gather)."""
+      kr_gather).
+
+  python tools/vehicle_rows_loop.py --control [--which bench|vector16|all] [--repeats 5] [--steps 50] [--sample 300]
+      What set_vehicle_speeds_tensor buys a vehicle-level control loop.  The rule, in torch on the device: command half its
+      speed to every vehicle that follows its leader with a gap below 10 m, NaN (leave alone) to the others.  Every
+      measurement starts from the same state (checkpoint / rollback; --dense: snapshot / load), median / min / max over `repeats`:
+        (a) one call that commands every running vehicle: the call's host time, and the time until `ignored` is read;
+        (b) per step of `steps` steps: observe_vehicles_tensor -> the rule -> set_vehicle_speeds_tensor -> next_step;
+        (c) per step of `steps` free-running steps;
+        (d) Engine only, the per-vehicle loop: the get_vehicle_speed() dict (the host has no dict of the gaps), and
+            set_vehicle_speed() per vehicle over `sample` vehicles (the whole loop is the dict plus that, times the vehicles
+            commanded).
+
+  python tools/vehicle_rows_loop.py --control --trace [--which bench|vector16] [--iters 50]
+      the workload for a kernel trace of its own: `iters` calls that command every running vehicle (k_speeds_claim,
+      k_speeds_apply, and k_speeds_flag_dense with "cfx": {"layout": "dense"} through --dense)."""
 import argparse
 import os
 import statistics
@@ -32,8 +47,15 @@ def spread(name, ts, unit=1e3, unit_name="ms"):
         name, statistics.median(ts) * unit, unit_name, min(ts) * unit, max(ts) * unit, len(ts)), flush=True)
 
 
-def workload(which, work):
+def workload(which, work, dense=False):
     cfg = bench.build_workload(work, 0, scenario="grid_30x30")
+    if dense:
+        import json
+        with open(cfg) as f:
+            doc = json.load(f)
+        doc.setdefault("cfx", {})["layout"] = "dense"
+        with open(cfg, "w") as f:
+            json.dump(doc, f)
     eng = cityflow_amd.Engine(cfg, 1) if which == "bench" else cityflow_amd.VectorEngine(cfg, 16, 1)
     for _ in range(bench.BUILD_UP_STEPS):
         eng.next_step()
@@ -111,11 +133,100 @@ def trace(args):
             eng._vehicle_state()
 
 
+def rule(torch, t):
+    follows = (t["leader"] >= 0) & (t["gap"] >= 0) & (t["gap"] < 10.0)
+    return torch.where(follows, 0.5 * t["speed"], torch.full_like(t["speed"], float("nan")))
+
+
+def control(args):
+    import torch
+    work = tempfile.mkdtemp(prefix="vehicle_speeds_loop_")
+    for which in (("bench", "vector16") if args.which == "all" else (args.which,)):
+        eng = workload(which, work, args.dense)
+        t, device = outputs(eng)
+        ignored = torch.empty((), dtype=torch.int32, device=device)
+        try:
+            ck = eng.checkpoint()
+            restore = lambda: eng.rollback(ck)  # noqa: E731
+        except NotImplementedError:  # (the dense layout has no checkpoints in device memory)
+            ck = eng.snapshot()
+            restore = lambda: eng.load(ck)  # noqa: E731
+        eng.observe_vehicles_tensor(**t)
+        commanded = int(torch.isfinite(rule(torch, t))[:int(t["count"])].sum())
+        print("%s%s: %s, %d vehicles running, the rule commands %d of them" % (
+            which, " (dense layout)" if args.dense else "", type(eng).__name__, int(t["count"]), commanded), flush=True)
+        if args.trace:
+            every = t["speed"].clone()
+            for _ in range(args.iters):
+                eng.set_vehicle_speeds_tensor(t["vehicle"], every, ignored)
+            torch.cuda.synchronize(device)
+            assert int(ignored) == 0
+            return
+        call, read, loop, free = [], [], [], []
+        for warm in (True, False):
+            for _ in range(1 if warm else args.repeats):
+                restore()
+                eng.observe_vehicles_tensor(**t)
+                every = t["speed"].clone()  # (its own speed to every running vehicle; the padding rows name -1)
+                torch.cuda.synchronize(device)
+                eng.sync()
+                t0 = time.perf_counter()
+                eng.set_vehicle_speeds_tensor(t["vehicle"], every, ignored)
+                t1 = time.perf_counter()
+                assert int(ignored.item()) == 0
+                t2 = time.perf_counter()
+                restore()
+                eng.sync()
+                t3 = time.perf_counter()
+                for _ in range(args.steps):
+                    eng.observe_vehicles_tensor(**t)
+                    eng.set_vehicle_speeds_tensor(t["vehicle"], rule(torch, t))
+                    eng.next_step()
+                torch.cuda.synchronize(device)
+                eng.sync()
+                t4 = time.perf_counter()
+                restore()
+                eng.sync()
+                t5 = time.perf_counter()
+                for _ in range(args.steps):
+                    eng.next_step()
+                eng.sync()
+                t6 = time.perf_counter()
+                if not warm:
+                    call.append(t1 - t0), read.append(t2 - t0)
+                    loop.append((t4 - t3) / args.steps), free.append((t6 - t5) / args.steps)
+        spread("set_vehicle_speeds_tensor, every running vehicle: the call", call, 1e6, "us")
+        spread("  ... until `ignored` is read", read, 1e6, "us")
+        spread("observe -> rule -> set -> step, per step", loop, 1e6, "us")
+        spread("free-running step", free, 1e6, "us")
+        if hasattr(eng, "set_vehicle_speed"):
+            dicts, each = [], []
+            for _ in range(args.repeats):
+                restore()
+                eng.sync()
+                t0 = time.perf_counter()
+                speeds = eng.get_vehicle_speed()
+                t1 = time.perf_counter()
+                ids = sorted(speeds)[:args.sample]
+                t2 = time.perf_counter()
+                for v in ids:
+                    eng.set_vehicle_speed(v, 0.5 * speeds[v])
+                t3 = time.perf_counter()
+                dicts.append(t1 - t0), each.append((t3 - t2) / max(len(ids), 1))
+            spread("get_vehicle_speed()", dicts)
+            spread("set_vehicle_speed(), per vehicle (%d sampled)" % len(ids), each, 1e6, "us")
+        del restore, ck, eng
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--which", choices=("bench", "vector16", "all"), default="all")
     ap.add_argument("--repeats", type=int, default=9)
     ap.add_argument("--trace", action="store_true")
     ap.add_argument("--iters", type=int, default=50)
+    ap.add_argument("--control", action="store_true")
+    ap.add_argument("--dense", action="store_true")
+    ap.add_argument("--steps", type=int, default=50)
+    ap.add_argument("--sample", type=int, default=300)
     a = ap.parse_args()
-    trace(a) if a.trace else measure(a)
+    control(a) if a.control else trace(a) if a.trace else measure(a)
