@@ -19,6 +19,7 @@
 
 #include "cfx_kernels.h"
 #include "cfx_launch_policy.h"
+#include "cfx_stage_layout.h"
 #include "cfx_lc_kernels.h"
 #include "cfx_ring_kernels.h"
 #include "cfx_dense_kernels.h"
@@ -173,35 +174,35 @@ struct cfx_engine {
     hipEvent_t devInEvent = nullptr, devOutEvent = nullptr;
     bool devObserving = false;
     int devObserveIdle = 0;
+    void deviceObserved() {  // what a device-side observation leaves behind (never on a tile)
+        devObserving = !tiled;
+        devObserveIdle = 0;
+    }
     int32_t *hPhaseErr = nullptr;  // pinned, host-mapped: {intersection, phase} of the first rejected device-side entry, {-1, 0}
     // cfx_set_tl_plan_device and its kin: the durations in force are net.phaseTime itself, held here non-const (every kernel that
     // reads a phase's time indexes that array on every use); the file's, for cfx_restore_tl_plan; the largest phase count of a
-    // signalised intersection (the row length of the padded arrays); the record of a rejected call; the host calls' scratch
+    // signalised intersection (the row length of the padded arrays); the record of a rejected call
     double *phaseTime = nullptr, *phaseTimeFile = nullptr;
     int nPhaseTimes = 0, planMaxPhases = 0;
     TlPlanErr *hPlanErr = nullptr;  // pinned, host-mapped; inter = -1: none
     int32_t planCalls = 0;          // set calls enqueued so far (TlPlanErr::done: the last one the device has decided)
-    double *planD = nullptr;        // [I * planMaxPhases + I] durations, then remain
-    int32_t *planI = nullptr;       // [I] phase
-    // cfx_get_lane_obs / cfx_get_lane_features: device scratch kept between calls (grown to the largest request seen; in `owned`)
-    double *featSum = nullptr, *featEdges = nullptr;
-    int32_t *featBins = nullptr;
-    size_t featBinsCap = 0, featEdgesCap = 0;
-    int32_t *obsI = nullptr;  // cfx_get_lane_obs: counts, waiting [L each], then front_lane_steps, front_waiting_steps [L * n_front each]
-    double *obsD = nullptr;   // ... front_distance, front_speed [L * n_front each]
-    size_t obsICap = 0, obsDCap = 0;
+    // The staging arena of the host forms (cfx_get_lane_obs, cfx_get_lane_features, cfx_get_intersection_features,
+    // cfx_get_movement_flow, cfx_set_tl_plan, cfx_get_tl_phase_durations, cfx_set_vehicle_speeds): the device side of the host
+    // arrays one call was given, laid out by cfx_stage_layout.h.  ONE allocation (in `owned`), grown to the largest request
+    // seen, rounded up to a power of two so that requests that creep up (the speed commands of a filling network) regrow it a
+    // logarithmic number of times.  Growing frees the old one at once, which is safe because the arena is idle at every
+    // entry: it is used only by calls that end in hipStreamSynchronize(stream) (stageClose).  Nothing in it outlives a call.
+    char *stage = nullptr;
+    size_t stageBytes = 0;
     int32_t *rowTileSum = nullptr;  // cfx_observe_vehicles_device: the scan's tile totals [ceil(D / kRowTile)] (in `owned`)
     // cfx_set_vehicle_speeds_device / cfx_set_vehicle_speeds: the row that commands each vehicle number [speedStampCap], all -1
-    // between calls; the host form's rows and its count in device memory (all in `owned`)
-    int32_t *speedStamp = nullptr, *speedRowsV = nullptr, *speedIgnored = nullptr;
-    double *speedRowsS = nullptr;
-    size_t speedStampCap = 0, speedRowsCap = 0;
+    // between calls (in `owned`)
+    int32_t *speedStamp = nullptr;
+    size_t speedStampCap = 0;
     // cfx_observe_intersections_device / cfx_get_intersection_features: the intersection -> roadLink -> {start lanes, end lanes,
-    // laneLinks} index, built and uploaded by the first call (interTables), and the host getter's device scratch; in `owned`
+    // laneLinks} index, built and uploaded by the first call (interTables); in `owned`
     bool interBuilt = false;
     InterFeatOut interTab{};        // the table pointers and M / P; the output pointers stay null here
-    int32_t *interOutI = nullptr;   // [I * (1 + 4 M + P)] phase, in, in_waiting, out, inside, phase_pressure
-    double *interOutD = nullptr;    // [I]
     // The trackers: statistics kept across steps (cfx_lane_flow_enable, cfx_movement_flow_enable, cfx_trip_stats_enable,
     // cfx_detectors_enable; DESIGN.md "One scaffold for the trackers").  One lifecycle, always in this order.  Nothing is
     // allocated or launched for a tracker that is off.  `baselineDue`: enabling, a reset or cfx_load_state left a baseline to the next step or read (trackersSettle).
@@ -218,9 +219,6 @@ struct cfx_engine {
     std::vector<int32_t> detLane;
     std::vector<double> detStart, detEnd;
     int32_t *detLanes = nullptr, *detFirst = nullptr, *detOrder = nullptr;
-    // cfx_get_movement_flow: the host getter's device scratch (freed with the tracker)
-    int32_t *moveOutI = nullptr;    // [3 I M] entered, left, max_waiting_steps
-    int64_t *moveOutL = nullptr;    // [5 I M] the five sums
     int cross2 = -1;                // cross phase: 1 = k_cross2 (throughput), 0 = k_cross (latency), -1 = by size
     HostMirror *hMirror = nullptr;  // pinned; valid while the last thing that changed the scalars was a step
     bool mirrorValid = false;
@@ -490,6 +488,33 @@ struct cfx_engine {
         int rc = allocRaw(dst, n);
         if (rc) return rc;
         if (n) HIP_TRY(hipMemcpy(*dst, src, n * sizeof(T), hipMemcpyHostToDevice));
+        return CFX_OK;
+    }
+
+    // The host forms' staging (the arena above).  stageOpen: the arena holds the layout, and the copies of its `in` fields
+    // are enqueued; the caller then launches on s.dev(field).  stageClose: the copies of its `out` fields are enqueued and the
+    // stream is waited for — the call's one wait, after which the arena is idle again.
+    int stageOpen(cfx_stage::StageLayout &s) {
+        if (s.size() > stageBytes) {
+            size_t cap = cfx_stage::kStageAlign;
+            while (cap < s.size()) cap *= 2;
+            int rc = grow(&stage, 0, cap);
+            if (rc) return rc;
+            stageBytes = cap;
+        }
+        s.base = stage;
+        for (int i = 0; i < s.nFields; ++i) {
+            const auto &f = s.field[i];
+            if (f.host && f.bytes && !f.out) HIP_TRY(hipMemcpyAsync(s.base + f.offset, f.host, f.bytes, hipMemcpyHostToDevice, stream));
+        }
+        return CFX_OK;
+    }
+    int stageClose(const cfx_stage::StageLayout &s) {
+        for (int i = 0; i < s.nFields; ++i) {
+            const auto &f = s.field[i];
+            if (f.host && f.bytes && f.out) HIP_TRY(hipMemcpyAsync(f.host, s.base + f.offset, f.bytes, hipMemcpyDeviceToHost, stream));
+        }
+        HIP_TRY(hipStreamSynchronize(stream));
         return CFX_OK;
     }
 
@@ -1029,14 +1054,14 @@ struct cfx_engine {
         }
         return CFX_OK;
     }
-    // ... and disabling frees, the getters' scratch too
+    // ... and disabling frees
     int trackerFree(int which) {
         int rc;
         if (which == kLaneFlow) {
             rc = freeRaw(&flow.rec) | freeRaw(&flow.lane);
             flow = LaneFlowDev{};
         } else if (which == kMoveFlow) {
-            rc = freeRaw(&move.rec) | freeRaw(&move.link) | freeRaw(&move.skip) | freeRaw(&moveOutI) | freeRaw(&moveOutL);
+            rc = freeRaw(&move.rec) | freeRaw(&move.link) | freeRaw(&move.skip);
             move = MoveFlowDev{};
         } else if (which == kDetectors) {
             rc = freeRaw(&det.rec) | detectorTablesFree();
@@ -2315,6 +2340,19 @@ static int32_t stepImpl(cfx_engine *e, const cfx_spawn *recs, int32_t n) {
     if ((rc = e->stageSpawns(recs, n, plan))) return rc;
     e->accountSpawns(recs, n);
     return e->ring ? e->stepRing(plan) : e->stepDense(plan);
+}
+// A descriptor with a leading struct_size (cfx_lane_obs, cfx_vehicle_rows, cfx_movement_flow_out) as this library knows it:
+// the members the caller's header did not have yet are zero in `*copy`.  CFX_ERR_INVALID otherwise, with a message where the
+// caller's header is the newer one.  (A template: outside the C linkage of the entry points that use it.)
+template <typename T> static int takeDescriptor(cfx_engine *e, const T *in, T *copy, const char *what) {
+    if (!e || !in || in->struct_size < (int32_t) sizeof(int32_t)) return CFX_ERR_INVALID;
+    if ((size_t) in->struct_size > sizeof(T)) {
+        e->err = std::string(what) + ": struct_size names members this library does not know";
+        return CFX_ERR_INVALID;
+    }
+    *copy = T{};
+    memcpy(copy, in, (size_t) in->struct_size);
+    return CFX_OK;
 }
 extern "C" {
 
@@ -4093,9 +4131,7 @@ int32_t cfx_set_tl_plan_device(cfx_engine *e, const double *durations, const int
     HIP_TRY(hipSetDevice(e->device));
     int rc;
     if ((rc = tlPlanArgs(e, maxPhases, "cfx_set_tl_plan_device"))) return rc;
-    if (durations && (rc = checkDevicePointer(e, durations, "cfx_set_tl_plan_device: durations"))) return rc;
-    if (phase && (rc = checkDevicePointer(e, phase, "cfx_set_tl_plan_device: phase"))) return rc;
-    if (remain && (rc = checkDevicePointer(e, remain, "cfx_set_tl_plan_device: remain"))) return rc;
+    if ((rc = checkDevicePointers(e, "cfx_set_tl_plan_device", {{durations, "durations"}, {phase, "phase"}, {remain, "remain"}}))) return rc;
     if ((rc = e->settle(false))) return rc;  // (as cfx_set_tl_phases_device: the deferred commit advances the lights of the last step first)
     if ((rc = e->orderAfterCaller((hipStream_t) producerStream))) return rc;
     launchSetTlPlan(e, durations, phase, remain);
@@ -4111,15 +4147,14 @@ int32_t cfx_set_tl_plan(cfx_engine *e, const double *durations, const int32_t *p
     if ((rc = tlPlanArgs(e, maxPhases, "cfx_set_tl_plan"))) return rc;
     if ((rc = e->settle(false))) return rc;
     const size_t nI = (size_t) e->I, nD = nI * (size_t) e->planMaxPhases;
-    if (!e->planD && (rc = e->allocRaw(&e->planD, nD + nI))) return rc;
-    if (!e->planI && (rc = e->allocRaw(&e->planI, nI))) return rc;
-    if (durations && nD) HIP_TRY(hipMemcpyAsync(e->planD, durations, nD * sizeof(double), hipMemcpyHostToDevice, e->stream));
-    if (phase && nI) HIP_TRY(hipMemcpyAsync(e->planI, phase, nI * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
-    if (remain && nI) HIP_TRY(hipMemcpyAsync(e->planD + nD, remain, nI * sizeof(double), hipMemcpyHostToDevice, e->stream));
-    launchSetTlPlan(e, durations ? e->planD : nullptr, phase ? e->planI : nullptr, remain ? e->planD + nD : nullptr);
+    cfx_stage::StageLayout s;
+    const auto fDurations = s.in(durations, nD);
+    const auto fPhase = s.in(phase, nI);
+    const auto fRemain = s.in(remain, nI);
+    if ((rc = e->stageOpen(s))) return rc;
+    launchSetTlPlan(e, s.dev(fDurations), s.dev(fPhase), s.dev(fRemain));
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    return CFX_OK;
+    return e->stageClose(s);
 }
 
 static void launchGetPhaseDurations(cfx_engine *e, double *out) {
@@ -4149,13 +4184,12 @@ int32_t cfx_get_tl_phase_durations(cfx_engine *e, double *out, int32_t maxPhases
     HIP_TRY(hipSetDevice(e->device));
     int rc;
     if ((rc = tlPlanArgs(e, maxPhases, "cfx_get_tl_phase_durations"))) return rc;
-    const size_t nI = (size_t) e->I, nD = nI * (size_t) e->planMaxPhases;
-    if (!e->planD && (rc = e->allocRaw(&e->planD, nD + nI))) return rc;
-    launchGetPhaseDurations(e, e->planD);
+    cfx_stage::StageLayout s;
+    const auto fOut = s.out(out, (size_t) e->I * (size_t) e->planMaxPhases);
+    if ((rc = e->stageOpen(s))) return rc;
+    launchGetPhaseDurations(e, s.dev(fOut));
     HIP_TRY(hipGetLastError());
-    if (nD) HIP_TRY(hipMemcpyAsync(out, e->planD, nD * sizeof(double), hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    return CFX_OK;
+    return e->stageClose(s);
 }
 
 int32_t cfx_restore_tl_plan(cfx_engine *e) {
@@ -4221,13 +4255,9 @@ static_assert(std::is_same<decltype(&cfx_get_lane_obs), cfx_get_lane_obs_fn>::va
 // The one path of the lane observations.  toHost: the outputs and edges are host memory (engine-owned device scratch, a
 // synchronous copy back); otherwise device memory, ordered against the caller's stream.  `what` names the entry point in messages.
 static int laneObs(cfx_engine *e, const cfx_lane_obs *obs, bool toHost, void *consumerStream, const char *what) {
-    if (!e || !obs || obs->struct_size < (int32_t) sizeof(int32_t)) return CFX_ERR_INVALID;
-    if ((size_t) obs->struct_size > sizeof(cfx_lane_obs)) {
-        e->err = std::string(what) + ": struct_size names members this library does not know";
-        return CFX_ERR_INVALID;
-    }
     cfx_lane_obs a{};
-    memcpy(&a, obs, (size_t) obs->struct_size);
+    int rc;
+    if ((rc = takeDescriptor(e, obs, &a, what))) return rc;
     const bool tracker = a.front_lane_steps || a.front_waiting_steps, front = a.front_distance || a.front_speed || tracker;
     if (!a.counts && !a.waiting && !a.speed_sum && !a.bins && !front) return CFX_ERR_INVALID;
     if (!laneFeatureArgs(e, a.bins, a.edges, a.n_bins, what)) return CFX_ERR_INVALID;
@@ -4237,7 +4267,6 @@ static int laneObs(cfx_engine *e, const cfx_lane_obs *obs, bool toHost, void *co
     }
     auto fail = [e](const std::string &m) { return e->fail(m); };
     HIP_TRY(hipSetDevice(e->device));
-    int rc;
     if (!toHost) {
         if ((rc = checkDevicePointers(e, what, {{a.counts, "counts"}, {a.waiting, "waiting"}, {a.speed_sum, "speed_sum"}, {a.bins, "bins"},
                                                 {a.bins ? a.edges : nullptr, "edges"}, {a.front_distance, "front_distance"},
@@ -4271,49 +4300,28 @@ static int laneObs(cfx_engine *e, const cfx_lane_obs *obs, bool toHost, void *co
         launchLaneFeatures(e, o);
         HIP_TRY(hipGetLastError());
         if ((rc = e->orderCallerAfter((hipStream_t) consumerStream))) return rc;
-        e->devObserving = !e->tiled;
-        e->devObserveIdle = 0;
+        e->deviceObserved();
         return CFX_OK;
     }
-    // host memory: the launch writes engine-owned scratch, kept between calls and grown to the largest request seen
+    // host memory: the launch writes the staging arena, and what was asked for is copied back
     const size_t nL = (size_t) e->L, nB = a.bins ? nL * a.n_bins : 0, nF = front ? nL * a.n_front : 0,
                  nEdges = a.bins ? (a.per_lane_edges ? (size_t) o.lanesPerEnv : 1) * (a.n_bins + 1) : 0;
-    if (a.speed_sum && !e->featSum && (rc = e->allocRaw(&e->featSum, nL))) return rc;
-    auto atLeast = [&](auto **p, size_t &cap, size_t n) {
-        if (n <= cap) return (int) CFX_OK;
-        const int r = e->grow(p, 0, n);
-        if (!r) cap = n;
-        return r;
-    };
-    if ((rc = atLeast(&e->featBins, e->featBinsCap, nB))) return rc;
-    if ((rc = atLeast(&e->featEdges, e->featEdgesCap, nEdges))) return rc;
-    if ((rc = atLeast(&e->obsI, e->obsICap, ((a.counts || a.waiting) ? 2 * nL : 0) + (tracker ? 2 * nF : 0)))) return rc;
-    if ((rc = atLeast(&e->obsD, e->obsDCap, (a.front_distance || a.front_speed) ? 2 * nF : 0))) return rc;
-    if (nEdges) HIP_TRY(hipMemcpyAsync(e->featEdges, a.edges, nEdges * sizeof(double), hipMemcpyHostToDevice, e->stream));
-    int32_t *const dSteps = e->obsI + ((a.counts || a.waiting) ? 2 * nL : 0);
-    if (a.counts) o.counts = e->obsI;
-    if (a.waiting) o.waiting = e->obsI + nL;
-    if (a.speed_sum) o.speedSum = e->featSum;
-    if (a.bins) o.bins = e->featBins, o.edges = e->featEdges;
-    if (a.front_distance) o.frontDis = e->obsD;
-    if (a.front_speed) o.frontSpeed = e->obsD + nF;
-    if (a.front_lane_steps) o.frontSteps = dSteps;
-    if (a.front_waiting_steps) o.frontWait = dSteps + nF;
+    cfx_stage::StageLayout s;
+    const auto fCounts = s.out(a.counts, nL), fWaiting = s.out(a.waiting, nL);
+    const auto fSum = s.out(a.speed_sum, nL);
+    const auto fBins = s.out(a.bins, nB);
+    const auto fDis = s.out(a.front_distance, nF), fSpeed = s.out(a.front_speed, nF);
+    const auto fSteps = s.out(a.front_lane_steps, nF), fWait = s.out(a.front_waiting_steps, nF);
+    const auto fEdges = s.in(a.bins ? a.edges : nullptr, nEdges);
+    if ((rc = e->stageOpen(s))) return rc;
+    o.counts = s.dev(fCounts), o.waiting = s.dev(fWaiting);
+    o.speedSum = s.dev(fSum);
+    o.bins = s.dev(fBins), o.edges = s.dev(fEdges);
+    o.frontDis = s.dev(fDis), o.frontSpeed = s.dev(fSpeed);
+    o.frontSteps = s.dev(fSteps), o.frontWait = s.dev(fWait);
     launchLaneFeatures(e, o);
     HIP_TRY(hipGetLastError());
-    auto back = [&](void *dst, const void *src, size_t bytes) {
-        return (dst && bytes) ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, e->stream) : hipSuccess;
-    };
-    HIP_TRY(back(a.counts, o.counts, nL * sizeof(int32_t)));
-    HIP_TRY(back(a.waiting, o.waiting, nL * sizeof(int32_t)));
-    HIP_TRY(back(a.speed_sum, o.speedSum, nL * sizeof(double)));
-    HIP_TRY(back(a.bins, o.bins, nB * sizeof(int32_t)));
-    HIP_TRY(back(a.front_distance, o.frontDis, nF * sizeof(double)));
-    HIP_TRY(back(a.front_speed, o.frontSpeed, nF * sizeof(double)));
-    HIP_TRY(back(a.front_lane_steps, o.frontSteps, nF * sizeof(int32_t)));
-    HIP_TRY(back(a.front_waiting_steps, o.frontWait, nF * sizeof(int32_t)));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    return CFX_OK;
+    return e->stageClose(s);
 }
 
 int32_t cfx_observe_lane_obs_device(cfx_engine *e, const cfx_lane_obs *obs, void *consumerStream) {
@@ -4360,13 +4368,9 @@ static_assert(std::is_same<decltype(&cfx_observe_vehicles_device), cfx_observe_v
 
 int32_t cfx_observe_vehicles_device(cfx_engine *e, const cfx_vehicle_rows *rows, void *consumerStream) {
     const char *what = "cfx_observe_vehicles_device";
-    if (!e || !rows || rows->struct_size < (int32_t) sizeof(int32_t)) return CFX_ERR_INVALID;
-    if ((size_t) rows->struct_size > sizeof(cfx_vehicle_rows)) {
-        e->err = std::string(what) + ": struct_size names members this library does not know";
-        return CFX_ERR_INVALID;
-    }
     cfx_vehicle_rows a{};
-    memcpy(&a, rows, (size_t) rows->struct_size);
+    int rc;
+    if ((rc = takeDescriptor(e, rows, &a, what))) return rc;
     if (a.n_rows < 0) {
         e->err = std::string(what) + ": n_rows must not be negative";
         return CFX_ERR_INVALID;
@@ -4380,7 +4384,6 @@ int32_t cfx_observe_vehicles_device(cfx_engine *e, const cfx_vehicle_rows *rows,
     }
     auto fail = [e](const std::string &m) { return e->fail(m); };
     HIP_TRY(hipSetDevice(e->device));
-    int rc;
     if ((rc = checkDevicePointers(e, what, {{a.start, "start"}, {a.count, "count"}, {a.vehicle, "vehicle"}, {a.drivable, "drivable"},
                                             {a.env, "env"}, {a.distance, "distance"}, {a.speed, "speed"}, {a.leader, "leader"},
                                             {a.gap, "gap"}})))
@@ -4411,8 +4414,7 @@ int32_t cfx_observe_vehicles_device(cfx_engine *e, const cfx_vehicle_rows *rows,
     }
     HIP_TRY(hipGetLastError());
     if ((rc = e->orderCallerAfter((hipStream_t) consumerStream))) return rc;
-    e->devObserving = true;
-    e->devObserveIdle = 0;
+    e->deviceObserved();  // (tiles were refused above)
     return CFX_OK;
 }
 
@@ -4495,25 +4497,14 @@ int32_t cfx_set_vehicle_speeds(cfx_engine *e, const int32_t *vehicle, const doub
     auto fail = [e](const std::string &m) { return e->fail(m); };
     HIP_TRY(hipSetDevice(e->device));
     if ((rc = e->settle(false))) return rc;
-    if (!e->speedIgnored && (rc = e->allocRaw(&e->speedIgnored, 1))) return rc;
-    if (e->speedRowsCap < (size_t) n) {  // (the stream is idle whenever the rows are: every call ends with a wait)
-        const size_t cap = std::max<size_t>((size_t) n, 2 * e->speedRowsCap);
-        int32_t *v = nullptr;
-        double *s = nullptr;
-        if ((rc = e->allocRaw(&v, cap)) || (rc = e->allocRaw(&s, cap))) return rc;
-        for (void *old : {(void *) e->speedRowsV, (void *) e->speedRowsS})
-            if (old) {
-                e->forget(old);
-                HIP_TRY(hipFree(old));
-            }
-        e->speedRowsV = v, e->speedRowsS = s, e->speedRowsCap = cap;
-    }
-    HIP_TRY(hipMemcpyAsync(e->speedRowsV, vehicle, (size_t) n * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(hipMemcpyAsync(e->speedRowsS, speed, (size_t) n * sizeof(double), hipMemcpyHostToDevice, e->stream));
-    if ((rc = launchVehicleSpeeds(e, e->speedRowsV, e->speedRowsS, n, e->speedIgnored))) return rc;
     int32_t count = 0;
-    HIP_TRY(hipMemcpyAsync(&count, e->speedIgnored, sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
+    cfx_stage::StageLayout s;
+    const auto fVehicle = s.in(vehicle, (size_t) n);
+    const auto fSpeed = s.in(speed, (size_t) n);
+    const auto fCount = s.out(&count, 1);
+    if ((rc = e->stageOpen(s))) return rc;
+    if ((rc = launchVehicleSpeeds(e, s.dev(fVehicle), s.dev(fSpeed), n, s.dev(fCount)))) return rc;
+    if ((rc = e->stageClose(s))) return rc;
     if (ignored) *ignored = count;
     return CFX_OK;
 }
@@ -4655,20 +4646,16 @@ int32_t cfx_observe_intersections_device(cfx_engine *e, int32_t *phase, double *
     auto fail = [e](const std::string &m) { return e->fail(m); };
     HIP_TRY(hipSetDevice(e->device));
     int rc;
-    if (phase && (rc = checkDevicePointer(e, phase, "cfx_observe_intersections_device: phase"))) return rc;
-    if (remain && (rc = checkDevicePointer(e, remain, "cfx_observe_intersections_device: remain"))) return rc;
-    if (in && (rc = checkDevicePointer(e, in, "cfx_observe_intersections_device: in"))) return rc;
-    if (inWaiting && (rc = checkDevicePointer(e, inWaiting, "cfx_observe_intersections_device: in_waiting"))) return rc;
-    if (out && (rc = checkDevicePointer(e, out, "cfx_observe_intersections_device: out"))) return rc;
-    if (inside && (rc = checkDevicePointer(e, inside, "cfx_observe_intersections_device: inside"))) return rc;
-    if (pressure && (rc = checkDevicePointer(e, pressure, "cfx_observe_intersections_device: phase_pressure"))) return rc;
+    if ((rc = checkDevicePointers(e, "cfx_observe_intersections_device",
+                                  {{phase, "phase"}, {remain, "remain"}, {in, "in"}, {inWaiting, "in_waiting"}, {out, "out"},
+                                   {inside, "inside"}, {pressure, "phase_pressure"}})))
+        return rc;
     if ((rc = interPrepare(e, maxRoadLinks, maxPhases, "cfx_observe_intersections_device"))) return rc;
     if ((rc = e->orderAfterCaller((hipStream_t) consumerStream))) return rc;
     launchInterFeatures(e, phase, remain, in, inWaiting, out, inside, pressure);
     HIP_TRY(hipGetLastError());
     if ((rc = e->orderCallerAfter((hipStream_t) consumerStream))) return rc;
-    e->devObserving = !e->tiled;
-    e->devObserveIdle = 0;
+    e->deviceObserved();
     return CFX_OK;
 }
 
@@ -4680,25 +4667,15 @@ int32_t cfx_get_intersection_features(cfx_engine *e, int32_t *phase, double *rem
     int rc;
     if ((rc = interPrepare(e, maxRoadLinks, maxPhases, "cfx_get_intersection_features"))) return rc;
     const size_t nI = (size_t) e->I, nM = nI * e->interTab.M, nP = nI * e->interTab.P;
-    if (!e->interOutI && (rc = e->allocRaw(&e->interOutI, nI + 4 * nM + nP))) return rc;
-    if (!e->interOutD && (rc = e->allocRaw(&e->interOutD, nI))) return rc;
-    int32_t *dPhase = e->interOutI, *dIn = dPhase + nI, *dWait = dIn + nM, *dOut = dWait + nM, *dInside = dOut + nM,
-            *dPressure = dInside + nM;
-    launchInterFeatures(e, phase ? dPhase : nullptr, remain ? e->interOutD : nullptr, in ? dIn : nullptr, inWaiting ? dWait : nullptr,
-                        out ? dOut : nullptr, inside ? dInside : nullptr, pressure ? dPressure : nullptr);
+    cfx_stage::StageLayout s;
+    const auto fPhase = s.out(phase, nI);
+    const auto fRemain = s.out(remain, nI);
+    const auto fIn = s.out(in, nM), fWait = s.out(inWaiting, nM), fOut = s.out(out, nM), fInside = s.out(inside, nM),
+               fPressure = s.out(pressure, nP);
+    if ((rc = e->stageOpen(s))) return rc;
+    launchInterFeatures(e, s.dev(fPhase), s.dev(fRemain), s.dev(fIn), s.dev(fWait), s.dev(fOut), s.dev(fInside), s.dev(fPressure));
     HIP_TRY(hipGetLastError());
-    auto back = [&](void *dst, const void *src, size_t bytes) {
-        return (dst && bytes) ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, e->stream) : hipSuccess;
-    };
-    HIP_TRY(back(phase, dPhase, nI * sizeof(int32_t)));
-    HIP_TRY(back(remain, e->interOutD, nI * sizeof(double)));
-    HIP_TRY(back(in, dIn, nM * sizeof(int32_t)));
-    HIP_TRY(back(inWaiting, dWait, nM * sizeof(int32_t)));
-    HIP_TRY(back(out, dOut, nM * sizeof(int32_t)));
-    HIP_TRY(back(inside, dInside, nM * sizeof(int32_t)));
-    HIP_TRY(back(pressure, dPressure, nP * sizeof(int32_t)));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    return CFX_OK;
+    return e->stageClose(s);
 }
 
 // ---- per-lane flow and waiting-time statistics across steps (optional entry points of include/cityflow_amd.h, as above)
@@ -5069,13 +5046,8 @@ int32_t cfx_movement_flow_enable(cfx_engine *e, int32_t on) { return e ? e->trac
 
 // the descriptor as this library knows it; CFX_ERR_INVALID with a message otherwise
 static int moveFlowArgs(cfx_engine *e, const cfx_movement_flow_out *out, cfx_movement_flow_out *a, const char *what) {
-    if (!e || !out || out->struct_size < (int32_t) sizeof(int32_t)) return CFX_ERR_INVALID;
-    if ((size_t) out->struct_size > sizeof(cfx_movement_flow_out)) {
-        e->err = std::string(what) + ": struct_size names members this library does not know";
-        return CFX_ERR_INVALID;
-    }
-    *a = cfx_movement_flow_out{};
-    memcpy(a, out, (size_t) out->struct_size);
+    int rc;
+    if ((rc = takeDescriptor(e, out, a, what))) return rc;
     if (!a->entered && !a->entered_lane_steps && !a->entered_lane_waiting_steps && !a->left && !a->left_steps && !a->left_waiting_steps &&
         !a->waiting_steps && !a->max_waiting_steps && !a->reset)
         return CFX_ERR_INVALID;
@@ -5132,28 +5104,17 @@ int32_t cfx_get_movement_flow(cfx_engine *e, const cfx_movement_flow_out *out) {
     if ((rc = trackerPrepare(e, kMoveFlow, "cfx_get_movement_flow"))) return rc;
     if ((rc = moveFlowRows(e, a, "cfx_get_movement_flow"))) return rc;
     const size_t rows = (size_t) e->I * e->interTab.M;
-    if (!e->moveOutI && (rc = e->allocRaw(&e->moveOutI, 3 * rows))) return rc;
-    if (!e->moveOutL && (rc = e->allocRaw(&e->moveOutL, 5 * rows))) return rc;
-    int32_t *dEntered = e->moveOutI, *dLeft = dEntered + rows, *dMax = dLeft + rows;
-    int64_t *dELS = e->moveOutL, *dELW = dELS + rows, *dLS = dELW + rows, *dLW = dLS + rows, *dW = dLW + rows;
-    launchMoveFlowDrain(e, MoveFlowOut{a.entered ? dEntered : nullptr, a.entered_lane_steps ? dELS : nullptr,
-                                       a.entered_lane_waiting_steps ? dELW : nullptr, a.left ? dLeft : nullptr,
-                                       a.left_steps ? dLS : nullptr, a.left_waiting_steps ? dLW : nullptr,
-                                       a.waiting_steps ? dW : nullptr, a.max_waiting_steps ? dMax : nullptr}, a.reset);
+    cfx_stage::StageLayout s;
+    const auto fEntered = s.out(a.entered, rows);
+    const auto fELS = s.out(a.entered_lane_steps, rows), fELW = s.out(a.entered_lane_waiting_steps, rows);
+    const auto fLeft = s.out(a.left, rows);
+    const auto fLS = s.out(a.left_steps, rows), fLW = s.out(a.left_waiting_steps, rows), fW = s.out(a.waiting_steps, rows);
+    const auto fMax = s.out(a.max_waiting_steps, rows);
+    if ((rc = e->stageOpen(s))) return rc;
+    launchMoveFlowDrain(e, MoveFlowOut{s.dev(fEntered), s.dev(fELS), s.dev(fELW), s.dev(fLeft), s.dev(fLS), s.dev(fLW), s.dev(fW),
+                                       s.dev(fMax)}, a.reset);
     HIP_TRY(hipGetLastError());
-    auto back = [&](void *dst, const void *src, size_t bytes) {
-        return (dst && bytes) ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, e->stream) : hipSuccess;
-    };
-    HIP_TRY(back(a.entered, dEntered, rows * sizeof(int32_t)));
-    HIP_TRY(back(a.entered_lane_steps, dELS, rows * sizeof(int64_t)));
-    HIP_TRY(back(a.entered_lane_waiting_steps, dELW, rows * sizeof(int64_t)));
-    HIP_TRY(back(a.left, dLeft, rows * sizeof(int32_t)));
-    HIP_TRY(back(a.left_steps, dLS, rows * sizeof(int64_t)));
-    HIP_TRY(back(a.left_waiting_steps, dLW, rows * sizeof(int64_t)));
-    HIP_TRY(back(a.waiting_steps, dW, rows * sizeof(int64_t)));
-    HIP_TRY(back(a.max_waiting_steps, dMax, rows * sizeof(int32_t)));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    return CFX_OK;
+    return e->stageClose(s);
 }
 
 int32_t cfx_movement_flow_get_state(cfx_engine *e, int32_t *records, int32_t nVehicles, cfx_movement_flow_link *links, int32_t *tick) {
