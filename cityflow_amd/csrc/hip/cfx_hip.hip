@@ -950,6 +950,7 @@ struct cfx_engine {
         if (baseline) {
             HIP_TRY(hipMemsetAsync(trip.seen, 0xFF, std::max<size_t>(vidCap, 1), stream));
             HIP_TRY(hipMemsetAsync(trip.env, 0, (size_t) trip.nEnvs * sizeof(cfx_trip_stats_env), stream));
+            if (trip.log) HIP_TRY(hipMemsetAsync(trip.logHead, 0, 2 * sizeof(int), stream));  // (a baseline empties the log)
         }
         if (spawned <= 0) return CFX_OK;
         trip.state = vt.state;
@@ -1070,7 +1071,7 @@ struct cfx_engine {
             detStart.clear();
             detEnd.clear();
         } else {
-            rc = freeRaw(&trip.seen) | freeRaw(&trip.env);
+            rc = freeRaw(&trip.seen) | freeRaw(&trip.env) | freeRaw(&trip.log) | freeRaw(&trip.logHead);
             trip = TripDev{};
         }
         return rc ? CFX_ERR_DEVICE : CFX_OK;
@@ -5024,6 +5025,129 @@ int32_t cfx_trip_stats_set_state(cfx_engine *e, const cfx_trip_stats_env *envs, 
     if (nEnvs != e->trip.nEnvs) return e->fail("cfx_trip_stats_set_state: n_envs is not the engine's"), CFX_ERR_INVALID;
     HIP_TRY(hipMemcpyAsync(e->trip.env, envs, (size_t) nEnvs * sizeof(cfx_trip_stats_env), hipMemcpyHostToDevice, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
+    return CFX_OK;
+}
+
+// ---- the trip log: one row per finished vehicle, kept by the trip tracker (optional entry points of include/cityflow_amd.h)
+int32_t cfx_trip_log_enable(cfx_engine *e, int32_t capacity);
+int32_t cfx_observe_trip_log_device(cfx_engine *e, const cfx_trip_log_out *out, int32_t reset, void *consumerStream);
+int32_t cfx_get_trip_log(cfx_engine *e, const cfx_trip_log_out *out, int32_t reset);
+int32_t cfx_trip_log_set_state(cfx_engine *e, const cfx_trip_log_out *rows, int32_t n, int32_t dropped);
+static_assert(std::is_same<decltype(&cfx_trip_log_enable), cfx_trip_log_enable_fn>::value, "cfx_trip_log_enable");
+static_assert(std::is_same<decltype(&cfx_observe_trip_log_device), cfx_observe_trip_log_device_fn>::value, "cfx_observe_trip_log_device");
+static_assert(std::is_same<decltype(&cfx_get_trip_log), cfx_get_trip_log_fn>::value, "cfx_get_trip_log");
+static_assert(std::is_same<decltype(&cfx_trip_log_set_state), cfx_trip_log_set_state_fn>::value, "cfx_trip_log_set_state");
+
+int32_t cfx_trip_log_enable(cfx_engine *e, int32_t capacity) {
+    if (!e) return CFX_ERR_INVALID;
+    auto fail = [e](const std::string &m) { return e->fail(m); };
+    if (capacity < 0 || capacity > CFX_TRIP_LOG_MAX_CAPACITY) return e->err = "cfx_trip_log_enable: capacity outside [0, 1 << 26]", CFX_ERR_INVALID;
+    HIP_TRY(hipSetDevice(e->device));
+    int rc;
+    if ((rc = trackerRequire(e, kTrips, "cfx_trip_log_enable"))) return rc;
+    HIP_TRY(hipStreamSynchronize(e->stream));  // (a tick or a drain may still be running on the log that goes)
+    if (e->freeRaw(&e->trip.log) | e->freeRaw(&e->trip.logHead)) return CFX_ERR_DEVICE;
+    e->trip.logCap = 0;
+    if (capacity == 0) return CFX_OK;
+    if ((rc = e->allocRaw(&e->trip.logHead, 2))) return rc;
+    if ((rc = e->allocRaw(&e->trip.log, 2 * (size_t) capacity))) {
+        (void) e->freeRaw(&e->trip.logHead);
+        return rc;
+    }
+    HIP_TRY(hipMemsetAsync(e->trip.logHead, 0, 2 * sizeof(int), e->stream));
+    e->trip.logCap = capacity;
+    return CFX_OK;
+}
+
+// trip tracking on, a log there, and what every reader does first (trackerPrepare)
+static int tripLogPrepare(cfx_engine *e, const char *what) {
+    int rc;
+    if ((rc = trackerRequire(e, kTrips, what))) return rc;
+    if (!e->trip.log) {
+        e->err = std::string(what) + ": there is no trip log (cfx_trip_log_enable)";
+        return CFX_ERR_STATE;
+    }
+    return trackerPrepare(e, kTrips, what);
+}
+
+static int launchTripLogDrain(cfx_engine *e, const cfx_trip_log_out &o, int32_t reset) {
+    auto fail = [e](const std::string &m) { return e->fail(m); };
+    hipLaunchKernelGGL(k_trip_log_drain, dim3(gridFor((size_t) e->trip.logCap)), dim3(kBlock), 0, e->stream, (const int4 *) e->trip.log,
+                       (const int *) e->trip.logHead, e->trip.logCap, o);
+    HIP_TRY(hipGetLastError());
+    // (behind the kernel, not inside it: no block of the drain reads a count another has cleared)
+    if (reset) HIP_TRY(hipMemsetAsync(e->trip.logHead, 0, 2 * sizeof(int), e->stream));
+    return CFX_OK;
+}
+
+static bool tripLogNoneGiven(const cfx_trip_log_out &o) {
+    return !o.count && !o.dropped && !o.env && !o.vehicle && !o.origin_road && !o.destination_road && !o.enter_step && !o.finish_step &&
+           !o.travel_steps;
+}
+
+int32_t cfx_observe_trip_log_device(cfx_engine *e, const cfx_trip_log_out *out, int32_t reset, void *consumerStream) {
+    if (!e || !out || tripLogNoneGiven(*out)) return CFX_ERR_INVALID;
+    const cfx_trip_log_out &o = *out;
+    auto fail = [e](const std::string &m) { return e->fail(m); };
+    HIP_TRY(hipSetDevice(e->device));
+    int rc;
+    if ((rc = checkDevicePointers(e, "cfx_observe_trip_log_device",
+                                  {{o.count, "count"}, {o.dropped, "dropped"}, {o.env, "env"}, {o.vehicle, "vehicle"},
+                                   {o.origin_road, "origin_road"}, {o.destination_road, "destination_road"}, {o.enter_step, "enter_step"},
+                                   {o.finish_step, "finish_step"}, {o.travel_steps, "travel_steps"}})))
+        return rc;
+    if ((rc = tripLogPrepare(e, "cfx_observe_trip_log_device"))) return rc;
+    if ((rc = e->orderAfterCaller((hipStream_t) consumerStream))) return rc;
+    if ((rc = launchTripLogDrain(e, o, reset))) return rc;
+    return e->orderCallerAfter((hipStream_t) consumerStream);
+}
+
+int32_t cfx_get_trip_log(cfx_engine *e, const cfx_trip_log_out *out, int32_t reset) {
+    if (!e || !out || tripLogNoneGiven(*out)) return CFX_ERR_INVALID;
+    auto fail = [e](const std::string &m) { return e->fail(m); };
+    HIP_TRY(hipSetDevice(e->device));
+    int rc;
+    if ((rc = tripLogPrepare(e, "cfx_get_trip_log"))) return rc;
+    const size_t cap = (size_t) e->trip.logCap;
+    cfx_stage::StageLayout s;
+    const auto fCount = s.out(out->count, 1), fDropped = s.out(out->dropped, 1), fEnv = s.out(out->env, cap), fVehicle = s.out(out->vehicle, cap),
+               fOrigin = s.out(out->origin_road, cap), fDest = s.out(out->destination_road, cap), fEnter = s.out(out->enter_step, cap),
+               fFinish = s.out(out->finish_step, cap), fTravel = s.out(out->travel_steps, cap);
+    if ((rc = e->stageOpen(s))) return rc;
+    cfx_trip_log_out o{};
+    o.count = s.dev(fCount);
+    o.dropped = s.dev(fDropped);
+    o.env = s.dev(fEnv);
+    o.vehicle = s.dev(fVehicle);
+    o.origin_road = s.dev(fOrigin);
+    o.destination_road = s.dev(fDest);
+    o.enter_step = s.dev(fEnter);
+    o.finish_step = s.dev(fFinish);
+    o.travel_steps = s.dev(fTravel);
+    if ((rc = launchTripLogDrain(e, o, reset))) return rc;
+    return e->stageClose(s);
+}
+
+int32_t cfx_trip_log_set_state(cfx_engine *e, const cfx_trip_log_out *rows, int32_t n, int32_t dropped) {
+    if (!e || n < 0 || dropped < 0 ||
+        (n > 0 && (!rows || !rows->env || !rows->vehicle || !rows->origin_road || !rows->destination_road || !rows->enter_step ||
+                   !rows->finish_step || !rows->travel_steps)))
+        return CFX_ERR_INVALID;
+    auto fail = [e](const std::string &m) { return e->fail(m); };
+    HIP_TRY(hipSetDevice(e->device));
+    int rc;
+    if ((rc = tripLogPrepare(e, "cfx_trip_log_set_state"))) return rc;  // (the load's baseline empties the log; then the rows)
+    if (n > e->trip.logCap) return e->err = "cfx_trip_log_set_state: n beyond the log's capacity", CFX_ERR_INVALID;
+    std::vector<int32_t> packed((size_t) n * 8);
+    for (size_t i = 0; i < (size_t) n; ++i) {
+        int32_t *row = &packed[8 * i];
+        row[0] = rows->env[i], row[1] = rows->vehicle[i], row[2] = rows->origin_road[i], row[3] = rows->destination_road[i];
+        row[4] = rows->enter_step[i], row[5] = rows->finish_step[i], row[6] = rows->travel_steps[i], row[7] = 0;
+    }
+    const int head[2] = {n, dropped};
+    if (n) HIP_TRY(hipMemcpyAsync(e->trip.log, packed.data(), packed.size() * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipMemcpyAsync(e->trip.logHead, head, sizeof head, hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));  // (the vectors live on this frame)
     return CFX_OK;
 }
 

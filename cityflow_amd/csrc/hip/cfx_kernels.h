@@ -3132,6 +3132,11 @@ struct TripDev {
     int nEnvs, roadsPerEnv;
     int32_t step;              // the step counter after the step
     int baseline;
+    // cfx_trip_log_enable: one row of two int4 per finished vehicle, {env, vehicle, origin road, destination road} and
+    // {enter step, finish step, travel steps, 0}.  Null: no log, and the tick does nothing for it but test this pointer
+    int4 *log;                 // [2 * logCap]
+    int *logHead;              // {rows reserved so far (it may run past logCap: the readers clamp it), rows dropped}
+    int logCap;
 };
 constexpr int kTripLdsEnvs = 64;
 constexpr int kTripCountBits = 21;  // three counts of a block (at most 16 kBlock each) in one 64-bit word
@@ -3164,6 +3169,29 @@ __device__ __forceinline__ void tripCommit(const TripDev t, int env, unsigned lo
     }
 }
 
+// The log's rows of one thread's sixteen numbers (`fin`: bit j = number base + j finished at this tick).  Only finishing
+// vehicles come here, a few per step, so each follows its own chain enterTime / route -> routeStart -> routeRoads: the first
+// and the last road of the route it holds now.  A slot is reserved with one vector atomic on the head; a slot at or beyond
+// the capacity counts as dropped instead.  (`t` by value, as tripCommit.)
+__device__ __forceinline__ void tripLogAppend(const TripDev t, long long base, unsigned fin) {
+    do {
+        const int vid = (int) base + (__ffs(fin) - 1);
+        fin &= fin - 1u;
+        const int e = (int) __double2ll_rn(t.enterTime[vid] / t.interval);
+        const int r = t.route[vid];
+        const int first = t.routeStart[r], last = max(t.routeStart[r + 1] - 1, first);
+        const int ro = t.routeRoads[first], rd = t.routeRoads[last];
+        const int env = t.nEnvs > 1 ? min(max(ro / t.roadsPerEnv, 0), t.nEnvs - 1) : 0;
+        const int slot = atomicAdd(t.logHead, 1);
+        if (slot >= 0 && slot < t.logCap) {
+            t.log[2 * (size_t) slot] = make_int4(env, vid, ro % t.roadsPerEnv, rd % t.roadsPerEnv);
+            t.log[2 * (size_t) slot + 1] = make_int4(e, t.step, (t.step - 1) - e, 0);
+        } else {
+            atomicAdd(t.logHead + 1, 1);
+        }
+    } while (fin);
+}
+
 __global__ void __launch_bounds__(kBlock) k_trip_tick(TripDev t) {
     __shared__ unsigned long long acc[kTripLdsEnvs * 4];
     acc[threadIdx.x] = 0;
@@ -3193,6 +3221,7 @@ __global__ void __launch_bounds__(kBlock) k_trip_tick(TripDev t) {
         int curEnv = -1;
         unsigned long long cnt = 0;
         long long s1 = 0, s2 = 0, s3 = 0;
+        unsigned fin = 0;  // the numbers that finish at this tick, for the log
 #pragma unroll
         for (int w = 0; w < 4; ++w) {
             const int nv = min(max(valid - 4 * w, 0), 4);  // the tail: a byte that is not a vehicle yet keeps its shadow
@@ -3257,10 +3286,12 @@ __global__ void __launch_bounds__(kBlock) k_trip_tick(TripDev t) {
                     if (cur == 2u && prev != 2u) {
                         cnt += 1ULL << (2 * kTripCountBits);
                         s3 += e;
+                        fin |= 1u << (4 * w + k);
                     }
                 }
             }
         }
+        if (t.log != nullptr && fin) tripLogAppend(t, base, fin);
         if (cnt) {
             if (curEnv < kTripLdsEnvs) {
                 atomicAdd(&acc[4 * curEnv], cnt);
@@ -3306,6 +3337,32 @@ __global__ void __launch_bounds__(kBlock) k_trip_drain(const cfx_trip_stats_env 
     if (o.buffered) o.buffered[r] = a.base_buffered + a.entered - a.admitted;
     if (o.in_system_travel_steps) o.in_system_travel_steps[r] = inSteps;
     if (o.average_travel_time) o.average_travel_time[r] = n == 0 ? 0.0 : (double) (a.finished_travel_steps + inSteps) * interval / (double) n;
+}
+
+// cfx_observe_trip_log_device / cfx_get_trip_log: the log's rows transposed into the columns that were given (any pointer may
+// be null), [cap] each.  One thread per row of the caller's columns: rows at and behind the count are written as -1, thread 0
+// also writes count and dropped.  Nothing is cleared here (a block must not read a count another block has cleared): a reset
+// is a memset of the head behind this kernel on the stream.
+__global__ void __launch_bounds__(kBlock) k_trip_log_drain(const int4 *log, const int *head, int cap, cfx_trip_log_out o) {
+    const size_t i = blockIdx.x * (size_t) blockDim.x + threadIdx.x;
+    const int n = min(max(head[0], 0), cap);
+    if (i == 0) {
+        if (o.count) *o.count = n;
+        if (o.dropped) *o.dropped = head[1];
+    }
+    if (i >= (size_t) cap) return;
+    int4 a = make_int4(-1, -1, -1, -1), b = a;
+    if (i < (size_t) n) {
+        a = log[2 * i];
+        b = log[2 * i + 1];
+    }
+    if (o.env) o.env[i] = a.x;
+    if (o.vehicle) o.vehicle[i] = a.y;
+    if (o.origin_road) o.origin_road[i] = a.z;
+    if (o.destination_road) o.destination_road[i] = a.w;
+    if (o.enter_step) o.enter_step[i] = b.x;
+    if (o.finish_step) o.finish_step[i] = b.y;
+    if (o.travel_steps) o.travel_steps[i] = b.z;
 }
 
 // cfx_observe_intersections_device / cfx_get_intersection_features: what a signal policy observes, per intersection, in one

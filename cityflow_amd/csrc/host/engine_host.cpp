@@ -116,6 +116,10 @@ void Backend::open(const std::string &libPath) {
     CFX_FN_OPTIONAL(cfx_get_trip_stats)
     CFX_FN_OPTIONAL(cfx_trip_stats_get_state)
     CFX_FN_OPTIONAL(cfx_trip_stats_set_state)
+    CFX_FN_OPTIONAL(cfx_trip_log_enable)
+    CFX_FN_OPTIONAL(cfx_observe_trip_log_device)
+    CFX_FN_OPTIONAL(cfx_get_trip_log)
+    CFX_FN_OPTIONAL(cfx_trip_log_set_state)
     CFX_FN_OPTIONAL(cfx_movement_flow_enable)
     CFX_FN_OPTIONAL(cfx_observe_movement_flow_device)
     CFX_FN_OPTIONAL(cfx_get_movement_flow)
@@ -1086,7 +1090,26 @@ void EngineHost::trackTrips(bool on) {
 void EngineHost::tripNoteVehicles() {
     if (!trackers_.trip.onHost()) return;
     const size_t n = spawner_.committedVehicleCount();
-    for (size_t v = (size_t) trackers_.trip.noted(); v < n; ++v) trackers_.trip.note((int32_t) v, spawner_.vehicles[v].enterTime, 0);
+    for (size_t v = (size_t) trackers_.trip.noted(); v < n; ++v) tripNote((int32_t) v);
+}
+
+// (with the first and the last road of the route it holds now, for the trip log)
+void EngineHost::tripNote(int32_t vid) {
+    const RouteTable &rt = spawner_.routes;
+    const int route = spawner_.vehicles[(size_t) vid].route;
+    const int32_t first = rt.routeStart[(size_t) route], last = std::max(rt.routeStart[(size_t) route + 1] - 1, first);
+    trackers_.trip.note(vid, spawner_.vehicles[(size_t) vid].enterTime, 0, rt.roads[(size_t) first], rt.roads[(size_t) last]);
+}
+
+void EngineHost::trackTripLog(int64_t capacity) { trackers_.trip.enableLog(capacity); }
+
+void EngineHost::tripLogFeatures(const cfx_trip_log_out &out, bool reset) {
+    trackers_.trip.logFeatures(out, reset);
+    raiseDeviceError();
+}
+
+void EngineHost::observeTripLogDevice(const cfx_trip_log_out &out, bool reset, uintptr_t consumerStream) {
+    trackers_.trip.observeLogDevice(out, reset, consumerStream);
 }
 
 // (like the count getters, these leave the step prepared ahead in place)
@@ -1222,6 +1245,12 @@ std::vector<int32_t> EngineHost::laneWaitingVehicleCountArray() {
     check(be_.cfx_get_lane_waiting_counts(dev_, out.data()), "cfx_get_lane_waiting_counts");
     raiseDeviceError();
     return out;
+}
+
+std::vector<std::string> EngineHost::roadIds() const {
+    std::vector<std::string> ids;
+    for (const HostRoad &r : net_->roads) ids.push_back(r.id);
+    return ids;
 }
 
 std::vector<std::string> EngineHost::laneIds() const {
@@ -1664,6 +1693,7 @@ bool EngineHost::setRoute(const std::string &vehicleId, const std::vector<std::s
     uploadNewTablesIfAny();
     check(be_.cfx_set_vehicle_route(dev_, vid, newRoute), "cfx_set_vehicle_route");
     spawner_.setVehicleRoute(vid, newRoute);
+    if (trackers_.trip.onHost() && vid < trackers_.trip.noted()) tripNote(vid);  // (host tracker: the trip log names the new route's ends)
     return true;
 }
 

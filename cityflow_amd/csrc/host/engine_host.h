@@ -109,6 +109,11 @@ struct Backend {
     cfx_get_trip_stats_fn cfx_get_trip_stats = nullptr;
     cfx_trip_stats_get_state_fn cfx_trip_stats_get_state = nullptr;
     cfx_trip_stats_set_state_fn cfx_trip_stats_set_state = nullptr;
+    // optional as a set beside them: the trip log, one row per finished vehicle (without them the host tracker keeps it too)
+    cfx_trip_log_enable_fn cfx_trip_log_enable = nullptr;
+    cfx_observe_trip_log_device_fn cfx_observe_trip_log_device = nullptr;
+    cfx_get_trip_log_fn cfx_get_trip_log = nullptr;
+    cfx_trip_log_set_state_fn cfx_trip_log_set_state = nullptr;
     // optional as a set: per-movement flow statistics kept by the backend (without them the host keeps them: movement_flow.h)
     cfx_movement_flow_enable_fn cfx_movement_flow_enable = nullptr;
     cfx_observe_movement_flow_device_fn cfx_observe_movement_flow_device = nullptr;
@@ -331,6 +336,7 @@ public:
     std::vector<int32_t> laneVehicleCountArray();
     std::vector<int32_t> laneWaitingVehicleCountArray();
     std::vector<std::string> laneIds() const;          // index -> id for the two arrays above
+    std::vector<std::string> roadIds() const;          // the roads in roadnet-file order (the trip log's road columns)
     const std::vector<int32_t> &laneIdOrder();         // lane indices in lexicographic id order (std::map order)
     std::vector<std::string> intersectionIds() const;
     void setTrafficLightPhaseIndexed(int inter, int phase);
@@ -396,6 +402,11 @@ public:
     bool tripTracking() const { return trackers_.trip.on(); }
     void tripFeatures(const cfx_trip_stats_out &out);  // any pointer may be null; one element each
     void observeTripsDevice(const cfx_trip_stats_out &out, uintptr_t consumerStream);
+    // the trip log, one row per finished vehicle (trip tracking must be on; capacity 0 drops it; outputs: columns [capacity])
+    void trackTripLog(int64_t capacity);
+    int32_t tripLogCapacity() const { return trackers_.trip.logCapacity(); }
+    void tripLogFeatures(const cfx_trip_log_out &out, bool reset);  // any pointer may be null; host memory
+    void observeTripLogDevice(const cfx_trip_log_out &out, bool reset, uintptr_t consumerStream);
     // ---- virtual loop detectors across steps (detectors.h; the torch layer is cityflow_amd/torch_io.py): `n` zones of lanes;
     //      outputs [n], any pointer may be null.  Defining turns the tracker on and takes a baseline
     void defineDetectors(const int32_t *lane, const double *start, const double *end, int n);
@@ -513,6 +524,7 @@ private:
     std::unique_ptr<InterLayout> interLayout_;  // built by the first call that needs it
     Trackers trackers_;
     void tripNoteVehicles();  // (host tracker: the vehicle numbers created since the last call)
+    void tripNote(int32_t vid);
 };
 
 struct EngineConfig {  // Engine::loadConfig engine.cpp:37-84

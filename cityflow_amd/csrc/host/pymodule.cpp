@@ -452,6 +452,34 @@ void observeTripsDevice(E &e, uintptr_t entered, uintptr_t admitted, uintptr_t b
     e.observeTripsDevice(o, consumerStream);
 }
 
+// ---- the trip log (Engine and VectorEngine; the public calls are cityflow_amd/torch_io.py)
+template <typename E> void trackTripLog(E &e, int64_t capacity) { e.trackTripLog(capacity); }
+// (count, dropped, then the seven columns [capacity] in log order, -1 behind count)
+template <typename E> py::tuple tripLogTuple(E &e, bool reset) {
+    const py::ssize_t cap = (py::ssize_t) e.tripLogCapacity();
+    cfx_trip_log_out o{};
+    py::tuple t = py::make_tuple(column(o.count, 1), column(o.dropped, 1), column(o.env, cap), column(o.vehicle, cap), column(o.origin_road, cap),
+                                 column(o.destination_road, cap), column(o.enter_step, cap), column(o.finish_step, cap),
+                                 column(o.travel_steps, cap));
+    e.tripLogFeatures(o, reset);
+    return t;
+}
+template <typename E>
+void observeTripLogDevice(E &e, uintptr_t count, uintptr_t dropped, uintptr_t env, uintptr_t vehicle, uintptr_t origin, uintptr_t destination,
+                          uintptr_t enter, uintptr_t finish, uintptr_t travel, bool reset, uintptr_t consumerStream) {
+    cfx_trip_log_out o{};
+    o.count = (int32_t *) count;
+    o.dropped = (int32_t *) dropped;
+    o.env = (int32_t *) env;
+    o.vehicle = (int32_t *) vehicle;
+    o.origin_road = (int32_t *) origin;
+    o.destination_road = (int32_t *) destination;
+    o.enter_step = (int32_t *) enter;
+    o.finish_step = (int32_t *) finish;
+    o.travel_steps = (int32_t *) travel;
+    e.observeTripLogDevice(o, reset, consumerStream);
+}
+
 // ---- virtual loop detectors across steps (Engine and VectorEngine; the public calls, and the checks of the arguments' types and
 //      lengths, are cityflow_amd/torch_io.py)
 template <typename E>
@@ -607,6 +635,14 @@ template <typename E> void defDeviceBuffers(py::class_<E> &c) {
         .def("_observe_trips_device", &observeTripsDevice<E>, "entered_ptr"_a, "admitted_ptr"_a, "admitted_buffer_steps_ptr"_a,
              "finished_ptr"_a, "finished_travel_steps_ptr"_a, "in_system_ptr"_a, "buffered_ptr"_a, "in_system_travel_steps_ptr"_a,
              "average_travel_time_ptr"_a, "consumer_stream"_a)
+        .def("_track_trip_log", &trackTripLog<E>, "capacity"_a, "an empty trip log of that many rows (0: none); trip tracking must be on")
+        .def("_trip_log_capacity", &E::tripLogCapacity)
+        .def("_trip_log_features", [](E &e, bool reset) { return tripLogTuple(e, reset); }, "reset"_a,
+             "(count, dropped, env, vehicle, origin_road, destination_road, enter_step, finish_step, travel_steps): the columns "
+             "[capacity] in log order, -1 behind count")
+        .def("_observe_trip_log_device", &observeTripLogDevice<E>, "count_ptr"_a, "dropped_ptr"_a, "env_ptr"_a, "vehicle_ptr"_a,
+             "origin_road_ptr"_a, "destination_road_ptr"_a, "enter_step_ptr"_a, "finish_step_ptr"_a, "travel_steps_ptr"_a, "reset"_a,
+             "consumer_stream"_a)
         .def("_define_detectors", &defineDetectors<E>, "lane"_a, "start"_a, "end"_a,
              "int32 / float64 / float64 [N], of one environment; turns the tracker on and takes a baseline")
         .def("_drop_detectors", &E::dropDetectors)
@@ -847,6 +883,7 @@ PYBIND11_MODULE(_cityflow, m) {
         .def("set_save_replay", &EngineHost::setSaveReplay, "open"_a)
         // ---- array API (index order == lane_ids() / intersection_ids()) ----
         .def("lane_ids", &EngineHost::laneIds)
+        .def("road_ids", &EngineHost::roadIds, "the roads in roadnet-file order: what the trip log's road columns index")
         .def("intersection_ids", &EngineHost::intersectionIds)
         .def("get_lane_vehicle_count_array", [](EngineHost &e) { return toArray(e.laneVehicleCountArray()); })
         .def("get_lane_waiting_vehicle_count_array",
@@ -1036,6 +1073,7 @@ PYBIND11_MODULE(_cityflow, m) {
         .def("get_current_time", &VectorEngineHost::getCurrentTime)
         .def("get_vehicle_count", &VectorEngineHost::totalVehicleCount)
         .def("lane_ids", &VectorEngineHost::laneIds)
+        .def("road_ids", &VectorEngineHost::roadIds, "one environment's roads in roadnet-file order: what the trip log's road columns index")
         .def("intersection_ids", &VectorEngineHost::intersectionIds)
         .def("get_lane_vehicle_count_array",
              [](VectorEngineHost &e) {

@@ -45,7 +45,10 @@ Trackers::Carry Trackers::take(int nVehicles, const std::vector<int32_t> &newOfO
         c.move = move.state(nVehicles);
         c.move.renumber(newOfOld, nLive);
     }
-    if (trip.on()) c.trips = trip.state();
+    if (trip.on()) {
+        c.trips = trip.state();
+        c.tripLog = trip.logState();
+    }
     if (det.on()) {
         c.det = det.state(nVehicles);
         c.det.renumber(newOfOld, nLive);
@@ -56,7 +59,10 @@ Trackers::Carry Trackers::take(int nVehicles, const std::vector<int32_t> &newOfO
 void Trackers::put(const Carry &c) {
     if (flow.on()) flow.setState(c.flow);
     if (move.on()) move.setState(c.move);
-    if (trip.on()) trip.setState(c.trips);
+    if (trip.on()) {
+        trip.setState(c.trips);
+        trip.setLogState(c.tripLog);
+    }
     if (det.on()) det.setState(c.det);
 }
 

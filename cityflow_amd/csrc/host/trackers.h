@@ -46,6 +46,7 @@ struct Trackers {
         LaneFlowState flow;
         MoveFlowState move;
         std::vector<cfx_trip_stats_env> trips;
+        TripLogState tripLog;  // (rows keep the vehicle numbers they were logged with)
         DetectorState det;
     };
     Carry take(int nVehicles, const std::vector<int32_t> &newOfOld, int nLive);

@@ -15,10 +15,15 @@ void TripStats::bind(const Backend *be, cfx_engine *dev, int nEnvs, double inter
                 be->cfx_trip_stats_get_state, be->cfx_trip_stats_set_state);
     nEnvs_ = nEnvs;
     interval_ = interval;
+    logOnDevice_ = onDevice() && be->cfx_trip_log_enable && be->cfx_observe_trip_log_device && be->cfx_get_trip_log && be->cfx_trip_log_set_state;
 }
 
 void TripStats::enable(bool on) {
-    if (!switchTo(on)) return;
+    if (on == on_) return;
+    const bool host = switchTo(on);
+    logCap_ = 0;  // (the log goes with the tracker: the backend frees its own)
+    log_.clear();
+    if (!host) return;
     std::vector<cfx_trip_stats_env>().swap(rec_);
     std::vector<uint8_t>().swap(seen_);
     std::vector<uint8_t>().swap(status_);
@@ -26,12 +31,16 @@ void TripStats::enable(bool on) {
     if (on) rec_.assign((size_t) nEnvs_, cfx_trip_stats_env{});
 }
 
-void TripStats::note(int32_t vid, double enterTime, int env) {
+void TripStats::note(int32_t vid, double enterTime, int env, int32_t originRoad, int32_t destinationRoad) {
     if (!on_ || onDevice() || vid < 0) return;
     if ((size_t) vid >= enter_.size()) {
         enter_.resize((size_t) vid + 1, 0);
         env_.resize((size_t) vid + 1, 0);
+        origin_.resize((size_t) vid + 1, -1);
+        destination_.resize((size_t) vid + 1, -1);
     }
+    origin_[(size_t) vid] = originRoad;
+    destination_[(size_t) vid] = destinationRoad;
     enter_[(size_t) vid] = (int32_t) std::llrint(enterTime / interval_);
     env_[(size_t) vid] = std::min(std::max(env, 0), nEnvs_ - 1);
 }
@@ -39,6 +48,8 @@ void TripStats::note(int32_t vid, double enterTime, int env) {
 void TripStats::forget() {
     std::vector<int32_t>().swap(enter_);
     std::vector<int32_t>().swap(env_);
+    std::vector<int32_t>().swap(origin_);
+    std::vector<int32_t>().swap(destination_);
 }
 
 // one tick (or baseline) of the host tracker: the rules of include/cityflow_amd.h over the status of every vehicle number noted
@@ -50,6 +61,7 @@ void TripStats::walk(int64_t step, bool baseline) {
     if (baseline) {
         rec_.assign((size_t) nEnvs_, cfx_trip_stats_env{});
         seen_.assign(n, 0xFF);
+        log_.clear();  // (a baseline empties the log, and logs nothing itself)
     } else {
         seen_.resize(n, 0xFF);
     }
@@ -79,6 +91,19 @@ void TripStats::walk(int64_t step, bool baseline) {
             a.finished += 1;
             a.finished_travel_steps += (step - 1) - e;
             a.enter_sum_finished += e;
+            if (logCap_ > 0) {  // the log's row of this finish (restated here: no code shared with the HIP library)
+                if (log_.rows() < (size_t) logCap_) {
+                    log_.env.push_back(env_[v]);
+                    log_.vehicle.push_back((int32_t) v);
+                    log_.originRoad.push_back(origin_[v]);
+                    log_.destinationRoad.push_back(destination_[v]);
+                    log_.enterStep.push_back((int32_t) e);
+                    log_.finishStep.push_back((int32_t) step);
+                    log_.travelSteps.push_back((int32_t) ((step - 1) - e));
+                } else {
+                    log_.dropped += 1;
+                }
+            }
         }
     }
 }
@@ -128,6 +153,84 @@ void TripStats::setState(const std::vector<cfx_trip_stats_env> &s) {
         return;
     }
     if (be_->cfx_trip_stats_set_state(dev_, s.data(), (int32_t) s.size()) != CFX_OK) fail("cfx_trip_stats_set_state");
+}
+
+// ---- the trip log
+void TripStats::enableLog(int64_t capacity) {
+    requireOn("track_trips(log=)");
+    if (capacity < 0 || capacity > CFX_TRIP_LOG_MAX_CAPACITY)
+        throw std::invalid_argument("track_trips: log capacity " + std::to_string(capacity) + " is outside [0, " +
+                                    std::to_string(CFX_TRIP_LOG_MAX_CAPACITY) + "]");
+    if (onDevice()) {
+        // (such a backend ticks by itself, so the host cannot keep the log for it)
+        if (!logOnDevice_) throw std::runtime_error("cityflow_amd: '" + be_->path + "' has no device-side trip log");
+        if (be_->cfx_trip_log_enable(dev_, (int32_t) capacity) != CFX_OK) fail("cfx_trip_log_enable");
+    }
+    log_.clear();
+    logCap_ = (int32_t) capacity;
+}
+
+void TripStats::requireLog(const char *what) const {
+    requireOn(what);
+    if (logCap_ <= 0) throw std::runtime_error(std::string(what) + ": there is no trip log (track_trips(True, log=N) turns it on)");
+}
+
+void TripStats::logFeatures(const cfx_trip_log_out &o, bool reset) {
+    requireLog("observe_trip_log");
+    if (logOnDevice_) {
+        if (be_->cfx_get_trip_log(dev_, &o, reset ? 1 : 0) != CFX_OK) fail("cfx_get_trip_log");
+        return;
+    }
+    const size_t n = log_.rows();
+    auto column = [&](int32_t *out, const std::vector<int32_t> &rows) {  // (k_trip_log_drain of the HIP library: -1 behind the count)
+        if (!out) return;
+        std::copy(rows.begin(), rows.end(), out);
+        std::fill(out + n, out + logCap_, -1);
+    };
+    if (o.count) *o.count = (int32_t) n;
+    if (o.dropped) *o.dropped = log_.dropped;
+    column(o.env, log_.env);
+    column(o.vehicle, log_.vehicle);
+    column(o.origin_road, log_.originRoad);
+    column(o.destination_road, log_.destinationRoad);
+    column(o.enter_step, log_.enterStep);
+    column(o.finish_step, log_.finishStep);
+    column(o.travel_steps, log_.travelSteps);
+    if (reset) log_.clear();
+}
+
+void TripStats::observeLogDevice(const cfx_trip_log_out &o, bool reset, uintptr_t consumerStream) {
+    requireLog("observe_trip_log_tensor");
+    if (!logOnDevice_) throw std::runtime_error("cityflow_amd: '" + be_->path + "' has no device-side trip log");
+    if (be_->cfx_observe_trip_log_device(dev_, &o, reset ? 1 : 0, (void *) consumerStream) != CFX_OK) fail("cfx_observe_trip_log_device");
+}
+
+TripLogState TripStats::logState() {
+    if (logCap_ <= 0) return TripLogState{};
+    if (!logOnDevice_) return log_;
+    const size_t cap = (size_t) logCap_;
+    TripLogState s;
+    int32_t count = 0;
+    for (std::vector<int32_t> *c : {&s.env, &s.vehicle, &s.originRoad, &s.destinationRoad, &s.enterStep, &s.finishStep, &s.travelSteps}) c->resize(cap);
+    cfx_trip_log_out o{&count, &s.dropped, s.env.data(), s.vehicle.data(), s.originRoad.data(), s.destinationRoad.data(), s.enterStep.data(),
+                       s.finishStep.data(), s.travelSteps.data()};
+    if (be_->cfx_get_trip_log(dev_, &o, 0) != CFX_OK) fail("cfx_get_trip_log");
+    for (std::vector<int32_t> *c : {&s.env, &s.vehicle, &s.originRoad, &s.destinationRoad, &s.enterStep, &s.finishStep, &s.travelSteps})
+        c->resize((size_t) std::max(count, 0));
+    return s;
+}
+
+void TripStats::setLogState(const TripLogState &s) {
+    if (logCap_ <= 0) return;
+    if (!logOnDevice_) {
+        log_ = s;
+        return;
+    }
+    cfx_trip_log_out o{nullptr, nullptr, const_cast<int32_t *>(s.env.data()), const_cast<int32_t *>(s.vehicle.data()),
+                       const_cast<int32_t *>(s.originRoad.data()), const_cast<int32_t *>(s.destinationRoad.data()),
+                       const_cast<int32_t *>(s.enterStep.data()), const_cast<int32_t *>(s.finishStep.data()),
+                       const_cast<int32_t *>(s.travelSteps.data())};
+    if (be_->cfx_trip_log_set_state(dev_, &o, (int32_t) s.rows(), s.dropped) != CFX_OK) fail("cfx_trip_log_set_state");
 }
 
 }  // namespace cfa

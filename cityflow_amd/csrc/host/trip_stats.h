@@ -3,11 +3,21 @@
 // cfx_get_vehicle_status; the owner tells it every vehicle number's enter time and environment (note) before the tick that
 // first sees the number.  Device and host keep a status byte per vehicle number (the status at the previous tick, 0xFF = never
 // seen) and a cfx_trip_stats_env per environment.
+// The trip LOG (one row per finished vehicle; "cfx_trip_log_enable" in the header has the rules) belongs to this tracker: the
+// backend keeps it where it exports the log's four entry points, the host tracker's walk otherwise.
 #pragma once
 
 #include "tracker_base.h"
 
 namespace cfa {
+
+// The trip log as it goes round a renumbering load (Trackers::Carry) and as the host tracker keeps it: rows in log order
+struct TripLogState {
+    std::vector<int32_t> env, vehicle, originRoad, destinationRoad, enterStep, finishStep, travelSteps;
+    int32_t dropped = 0;
+    size_t rows() const { return env.size(); }
+    void clear() { *this = TripLogState{}; }
+};
 
 class TripStats : public TrackerBase {
 public:
@@ -17,7 +27,9 @@ public:
     void enable(bool on);
     // ---- host tracker (no-ops while the device keeps it)
     int32_t noted() const { return (int32_t) enter_.size(); }
-    void note(int32_t vid, double enterTime, int env);
+    // `originRoad`, `destinationRoad`: the first and the last road of the route the vehicle holds, of ONE environment's roads
+    // (noted again when the route changes: EngineHost::setRoute)
+    void note(int32_t vid, double enterTime, int env, int32_t originRoad, int32_t destinationRoad);
     void forget();                     // the vehicle numbers are about to mean something else (reset, load)
     // (baseline(): on the statuses as they stand, nothing is counted as entered)
     // ----
@@ -25,6 +37,15 @@ public:
     void observeDevice(const cfx_trip_stats_out &out, uintptr_t consumerStream);
     std::vector<cfx_trip_stats_env> state();       // ... around a renumbering load (the records only)
     void setState(const std::vector<cfx_trip_stats_env> &s);
+    // ---- the trip log (tracking must be on).  capacity > 0: an empty log of that many rows, replacing the one there; 0: none.
+    // std::invalid_argument outside [0, CFX_TRIP_LOG_MAX_CAPACITY]
+    void enableLog(int64_t capacity);
+    int32_t logCapacity() const { return logCap_; }  // 0: no log
+    bool logOnDevice() const { return logOnDevice_; }
+    void logFeatures(const cfx_trip_log_out &out, bool reset);  // any pointer may be null; host memory, columns [capacity]
+    void observeLogDevice(const cfx_trip_log_out &out, bool reset, uintptr_t consumerStream);
+    TripLogState logState();                       // ... around a renumbering load (no log: empty)
+    void setLogState(const TripLogState &s);
 
 private:
     void walk(int64_t step, bool baseline) override;
@@ -35,6 +56,12 @@ private:
     std::vector<uint8_t> seen_, status_;
     std::vector<int32_t> enter_, env_;  // e(v), r(v)
     int64_t step_ = 0;                  // the step counter of the last tick
+    // the log: on the device where the backend has its entry points, otherwise rows appended by walk()
+    void requireLog(const char *what) const;
+    bool logOnDevice_ = false;
+    int32_t logCap_ = 0;
+    TripLogState log_;
+    std::vector<int32_t> origin_, destination_;  // per vehicle number, as noted
 };
 
 }  // namespace cfa

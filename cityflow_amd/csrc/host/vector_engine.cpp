@@ -529,7 +529,11 @@ void VectorEngineHost::nextStep() {
     step_ += 1;
     if (trackers_.onHost()) {
         // (the batch just handed over names the new vehicles; the ahead thread works on the next one)
-        for (const cfx_spawn &s : recs_) trackers_.trip.note(s.vid, s.enter_time, L_ > 0 ? s.lane / L_ : 0);
+        // (and its routes: the tables are the same in every environment and never change on a VectorEngine)
+        for (const cfx_spawn &s : recs_) {
+            const int env = L_ > 0 ? s.lane / L_ : 0;
+            tripNote(s.vid, s.enter_time, env, s.route - env * routesPerEnv_);
+        }
         std::lock_guard<std::mutex> guard(queryMutex_);
         trackers_.afterStep((int64_t) step_);
     }
@@ -675,7 +679,8 @@ void VectorEngineHost::rollbackTo(DeviceCheckpoint &ck, const std::vector<int32_
             if (!trackers_.trip.onHost()) return;
             for (size_t g = 0; g < globalToLocal_.size(); ++g) {
                 const auto &el = globalToLocal_[g];
-                trackers_.trip.note((int32_t) g, spawners_[(size_t) el.first]->vehicles[(size_t) el.second].enterTime, el.first);
+                const auto &veh = spawners_[(size_t) el.first]->vehicles[(size_t) el.second];
+                tripNote((int32_t) g, veh.enterTime, el.first, veh.route);
             }
         });
     }
@@ -890,9 +895,33 @@ void VectorEngineHost::trackTrips(bool on) {
     check(be_.cfx_get_scalars(dev_, &sc), "cfx_get_scalars");
     for (int64_t v = 0; v < sc.spawned_vehicle_count && (size_t) v < globalToLocal_.size(); ++v) {
         const auto gl = globalToLocal_[(size_t) v];
-        trackers_.trip.note((int32_t) v, spawners_[(size_t) gl.first]->vehicles[(size_t) gl.second].enterTime, gl.first);
+        const auto &veh = spawners_[(size_t) gl.first]->vehicles[(size_t) gl.second];
+        tripNote((int32_t) v, veh.enterTime, gl.first, veh.route);
     }
     trackers_.trip.baseline((int64_t) step_);
+}
+
+// (host tracker) a vehicle by its global number, with the first and the last road of its route in its environment's own tables
+void VectorEngineHost::tripNote(int32_t vid, double enterTime, int env, int route) {
+    const RouteTable &rt = spawners_[(size_t) env]->routes;
+    const int32_t first = rt.routeStart[(size_t) route], last = std::max(rt.routeStart[(size_t) route + 1] - 1, first);
+    trackers_.trip.note(vid, enterTime, env, rt.roads[(size_t) first], rt.roads[(size_t) last]);
+}
+
+void VectorEngineHost::trackTripLog(int64_t capacity) {
+    std::lock_guard<std::mutex> guard(queryMutex_);
+    trackers_.trip.enableLog(capacity);
+}
+
+void VectorEngineHost::tripLogFeatures(const cfx_trip_log_out &out, bool reset) {
+    std::lock_guard<std::mutex> guard(queryMutex_);
+    trackers_.trip.logFeatures(out, reset);
+    raiseDeviceError();
+}
+
+void VectorEngineHost::observeTripLogDevice(const cfx_trip_log_out &out, bool reset, uintptr_t consumerStream) {
+    std::lock_guard<std::mutex> guard(queryMutex_);
+    trackers_.trip.observeLogDevice(out, reset, consumerStream);
 }
 
 void VectorEngineHost::tripFeatures(const cfx_trip_stats_out &out) {
@@ -1009,6 +1038,12 @@ void VectorEngineHost::setTrafficLightPhases(const std::vector<int32_t> &phases)
 std::vector<std::string> VectorEngineHost::laneIds() const {
     std::vector<std::string> ids(L_);
     for (int l = 0; l < L_; ++l) ids[l] = net_->laneId(l);
+    return ids;
+}
+
+std::vector<std::string> VectorEngineHost::roadIds() const {
+    std::vector<std::string> ids;
+    for (const HostRoad &r : net_->roads) ids.push_back(r.id);
     return ids;
 }
 

@@ -115,6 +115,11 @@ public:
     bool tripTracking() const { return trackers_.trip.on(); }
     void tripFeatures(const cfx_trip_stats_out &out);
     void observeTripsDevice(const cfx_trip_stats_out &out, uintptr_t consumerStream);
+    // the trip log (EngineHost::trackTripLog and its kin): ONE log for all environments, the `env` column says which
+    void trackTripLog(int64_t capacity);
+    int32_t tripLogCapacity() const { return trackers_.trip.logCapacity(); }
+    void tripLogFeatures(const cfx_trip_log_out &out, bool reset);
+    void observeTripLogDevice(const cfx_trip_log_out &out, bool reset, uintptr_t consumerStream);
     // virtual loop detectors (EngineHost::defineDetectors and its kin): ONE environment's set, which every environment gets;
     // outputs [R * n]
     void defineDetectors(const int32_t *lane, const double *start, const double *end, int n);
@@ -123,6 +128,7 @@ public:
     void detectorFeatures(const cfx_detectors_out &out, bool reset);
     void observeDetectorsDevice(const cfx_detectors_out &out, bool reset, uintptr_t consumerStream);
     std::vector<std::string> laneIds() const;
+    std::vector<std::string> roadIds() const;  // one environment's roads, in roadnet-file order (the trip log's road columns)
     std::vector<std::string> intersectionIds() const;
     cfx_scalars scalars();
     void sync();
@@ -171,6 +177,7 @@ private:
     void forEachEnv(void (VectorEngineHost::*fn)(int));  // fn(env) for every environment, on the pool from 32 envs on
     void spawnEnv(int r);
     void translateEnv(int r);
+    void tripNote(int32_t vid, double enterTime, int env, int route);  // (host trip tracker; `route` in the environment's own numbering)
     void peekEnv(int r);
     // lane change (laneChange: true): as EngineHost, per environment (include/cityflow_amd.h "Lane change", n_envs)
     void settleLaneChange();

@@ -45,6 +45,12 @@
                              average_travel_time=None)   0-dim (VectorEngine: [R]) each, one kernel launch (see its docstring)
     eng.observe_trips_array()                            the same nine outputs as numpy arrays (waits for the device)
     eng.get_average_travel_time_tensor(out=None)         float64 0-dim (VectorEngine: [R]): get_average_travel_time() on the device
+    eng.track_trips(on=True, log=N) / eng.trip_log_capacity()
+                                                         the trip LOG: one row per finished vehicle, N rows of room (off by default)
+    eng.observe_trip_log_tensor(count=None, dropped=None, env=None, vehicle=None, origin_road=None, destination_road=None,
+                                enter_step=None, finish_step=None, travel_steps=None, reset=False)
+                                                         drains it into int32 tensors, [N] per column, one kernel launch
+    eng.observe_trip_log_array(reset=False)              the same as numpy columns trimmed to count, in a canonical order
     eng.track_detectors(lane=None, start=None, end=None, on=True) / eng.detector_tracking() / eng.detector_layout()
                                                          N virtual loop detectors, zones [start, end) of lanes: what passed them,
                                                          how long they were occupied and how fast the traffic over them was,
@@ -582,14 +588,32 @@ def _trip_dtype(torch, name):
     return torch.float64 if name == "average_travel_time" else torch.int64 if name in _TRIP_INT64 else torch.int32
 
 
-def track_trips(self, on=True):
+TRIP_LOG_MAX_CAPACITY = 1 << 26
+
+
+def track_trips(self, on=True, log=None):
     """Turn the trip tracker on or off (off by default: nothing is allocated or launched, and it frees its memory when turned
     off).  While it is on, every next_step() ends with one tracker update (one extra kernel launch on the HIP engine).
     Turning it on takes a baseline: the five accumulators are zero, and the vehicles alive then are in in_system / buffered /
     in_system_travel_steps with their true enter times without being counted as entered (they count as admitted or finished
     when that happens); reset(), load() and load_from_file() take a new baseline and keep it on.  Not with laneChange
-    (NotImplementedError)."""
+    (NotImplementedError).
+
+    log: the trip LOG, one row per finished vehicle (observe_trip_log_tensor), off by default and off while only the statistics
+    are on.  log=N (1 <= N <= 2**26, 32 bytes of device memory per row) turns it on with room for N rows, or replaces the log
+    there by an empty one; log=0 drops it; None leaves it as it is.  Changing `log` while tracking is on does not touch the
+    accumulators.  Turning tracking off drops the log; with on=False only None or 0 make sense.  ValueError for a capacity that
+    is no integer in [0, 2**26], before anything is changed."""
+    import numbers
+
+    if log is not None:
+        if isinstance(log, bool) or not isinstance(log, numbers.Integral) or not 0 <= int(log) <= TRIP_LOG_MAX_CAPACITY:
+            raise ValueError("track_trips: log must be an integer in [0, %d] or None, not %r" % (TRIP_LOG_MAX_CAPACITY, log))
+        if not on and int(log) > 0:
+            raise ValueError("track_trips: a log needs trip tracking on")
     self._track_trips(bool(on))
+    if on and log is not None:
+        self._track_trip_log(int(log))
 
 
 def trip_tracking(self):
@@ -635,6 +659,82 @@ def observe_trips_array(self):
         raise RuntimeError("observe_trips_array: trip tracking is off (track_trips(True) turns it on)")
     shape = tuple(self._tensor_shapes()[0])[:-1]
     return {name: a.reshape(shape) for name, a in zip(TRIP_OUTPUTS, self._trip_features())}
+
+
+TRIP_LOG_OUTPUTS = ("count", "dropped", "env", "vehicle", "origin_road", "destination_road", "enter_step", "finish_step", "travel_steps")
+TRIP_LOG_COLUMNS = TRIP_LOG_OUTPUTS[2:]
+
+
+def trip_log_capacity(self):
+    """The rows the trip log has room for (track_trips(log=N)); 0 while there is no log."""
+    return self._trip_log_capacity()
+
+
+def _require_trip_log(eng, what):
+    if not eng._trip_tracking():
+        raise RuntimeError(what + ": trip tracking is off (track_trips(True, log=N) turns it and the log on)")
+    if eng._trip_log_capacity() <= 0:
+        raise RuntimeError(what + ": there is no trip log (track_trips(True, log=N) turns it on)")
+
+
+def observe_trip_log_tensor(self, count=None, dropped=None, env=None, vehicle=None, origin_road=None, destination_road=None,
+                            enter_step=None, finish_step=None, travel_steps=None, reset=False):
+    """Drain the trip log into the given tensors with one kernel launch on the engine's stream, ordered against the current
+    torch stream as observe_lanes_tensor (no host wait).  The log holds one row per vehicle that finished since the last
+    baseline (track_trips; reset(), load(), load_from_file(), rollback()) or the last call with reset=True: the event that adds
+    1 to `finished` of observe_trips_tensor.  All int32 on the engine's device; N = trip_log_capacity():
+
+        count             0-dim  rows held, at most N
+        dropped           0-dim  rows that found the log full and were dropped (the trip statistics still counted them)
+        env               [N]    the vehicle's environment (0 on an Engine; ONE log serves all environments of a VectorEngine)
+        vehicle           [N]    its vehicle number when it finished, as observe_vehicles_tensor showed it.  After a vehicle
+                                 compaction a number may be in use again; rows keep the number they were logged with
+        origin_road       [N]    first road of the route it held when it finished, an index into road_ids()
+        destination_road  [N]    last road of that route.  set_vehicle_route() replaces a vehicle's route from the road it is
+                                 on: such a vehicle's origin_road is the first road of the NEW route
+        enter_step        [N]    e(v), the step at which it was created (enter time / interval)
+        finish_step       [N]    s, the steps taken when it was found finished
+        travel_steps      [N]    (s - 1) - e(v): what finished_travel_steps got for it; seconds = steps * interval
+
+    Rows are in ascending finish_step; the order of the rows of one step is unspecified and differs from run to run on the
+    device (observe_trip_log_array sorts).  Rows at and behind `count` are -1 in every column: every element is written.
+    reset=True empties the log and zeroes `dropped` after the copy, in stream order.  At least one output; every argument is
+    checked before anything is enqueued; RuntimeError while tracking is off or there is no log.  Returns a dict of the tensors
+    that were given."""
+    torch = _torch()
+    given = dict(zip(TRIP_LOG_OUTPUTS, (count, dropped, env, vehicle, origin_road, destination_road, enter_step, finish_step, travel_steps)))
+    if all(t is None for t in given.values()):
+        raise ValueError("observe_trip_log_tensor: give at least one of " + ", ".join(TRIP_LOG_OUTPUTS))
+    _require_trip_log(self, "observe_trip_log_tensor")
+    device = _engine_device(torch, self)
+    cap = self._trip_log_capacity()
+    for name, t in given.items():
+        if t is not None:
+            _check_buf(torch, t, name, () if name in ("count", "dropped") else (cap,), torch.int32, device)
+    if not self._device_buffers():  # (the twin: over the array call's raw columns)
+        for name, a in zip(TRIP_LOG_OUTPUTS, self._trip_log_features(bool(reset))):
+            if given[name] is not None:
+                given[name].copy_(torch.from_numpy(a).reshape(given[name].shape))
+    else:
+        self._observe_trip_log_device(*[0 if given[name] is None else given[name].data_ptr() for name in TRIP_LOG_OUTPUTS],
+                                      bool(reset), torch.cuda.current_stream(device).cuda_stream)
+    return {name: t for name, t in given.items() if t is not None}
+
+
+def observe_trip_log_array(self, reset=False):
+    """The trip log as a dict of numpy int32 columns (the seven columns of observe_trip_log_tensor, trimmed to the rows held)
+    plus "dropped" as an int; waits for the device.  The rows are sorted by (finish_step, env, vehicle), so two runs give equal
+    arrays.  reset=True empties the log.  RuntimeError while tracking is off or there is no log."""
+    import numpy as np
+
+    _require_trip_log(self, "observe_trip_log_array")
+    raw = dict(zip(TRIP_LOG_OUTPUTS, self._trip_log_features(bool(reset))))
+    n = int(raw["count"][0])
+    cols = {name: raw[name][:n] for name in TRIP_LOG_COLUMNS}
+    order = np.lexsort((cols["vehicle"], cols["env"], cols["finish_step"]))
+    out = {name: np.ascontiguousarray(a[order]) for name, a in cols.items()}
+    out["dropped"] = int(raw["dropped"][0])
+    return out
 
 
 def get_average_travel_time_tensor(self, out=None):
@@ -1226,6 +1326,9 @@ def install(*classes):
         cls.trip_tracking = trip_tracking
         cls.observe_trips_tensor = observe_trips_tensor
         cls.observe_trips_array = observe_trips_array
+        cls.trip_log_capacity = trip_log_capacity
+        cls.observe_trip_log_tensor = observe_trip_log_tensor
+        cls.observe_trip_log_array = observe_trip_log_array
         cls.get_average_travel_time_tensor = get_average_travel_time_tensor
         cls.track_detectors = track_detectors
         cls.detector_tracking = detector_tracking

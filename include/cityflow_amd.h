@@ -745,6 +745,46 @@ typedef int32_t (*cfx_get_trip_stats_fn)(cfx_engine *e, const cfx_trip_stats_out
 typedef int32_t (*cfx_trip_stats_get_state_fn)(cfx_engine *e, cfx_trip_stats_env *envs, int32_t n_envs);
 typedef int32_t (*cfx_trip_stats_set_state_fn)(cfx_engine *e, const cfx_trip_stats_env *envs, int32_t n_envs);
 
+/* ---- The trip LOG: one row per finished vehicle, kept by the trip tracker (OPTIONAL entry points of their own, as above).  It
+ * needs trip tracking on (CFX_ERR_STATE otherwise), so not with lane change and not on a tile; it is off by default and off
+ * while only cfx_trip_stats_enable is on; turning trip tracking off frees it.  At the tick that ends step s every vehicle v
+ * "finished now and not at the previous tick" (the event that does finished[r] += 1) is appended as one row, seven int32:
+ *   env               r(v)
+ *   vehicle           the vehicle number v had when it finished (after a host has renumbered the vehicles through
+ *                     cfx_load_state + cfx_trip_log_set_state a number may be in use again: rows keep the old one)
+ *   origin_road       first road of the route v held when it finished, as an index into ONE environment's roads (road index
+ *                     modulo n_roads / n_envs).  cfx_set_vehicle_route replaces the route from the road the vehicle is on: the
+ *                     origin of such a vehicle is the first road of the NEW route
+ *   destination_road  last road of that route, same indexing
+ *   enter_step        e(v)
+ *   finish_step       s
+ *   travel_steps      (s - 1) - e(v): exactly what finished_travel_steps received for v
+ * Rows are in ascending finish_step; the order of the rows of ONE step is unspecified (it differs from run to run on a
+ * device).  The capacity is fixed when the log is turned on: a row that does not fit is dropped and counted in `dropped`; the
+ * accumulators of the trip statistics do not depend on the log.  A BASELINE (enabling trip tracking, cfx_reset, cfx_load_state)
+ * empties the log and zeroes `dropped`; a baseline tick itself logs nothing, so vehicles that had finished before are no rows.
+ *   "cfx_trip_log_enable"          capacity > 0: allocate, or replace by, an EMPTY log of that many rows (32 bytes each); 0: free.
+ *                                  CFX_ERR_INVALID outside [0, 1 << 26].  The accumulators are not touched.
+ *   "cfx_observe_trip_log_device"  any of the nine NULL (at least one given), all in device memory: the columns [capacity] each,
+ *                                  count (rows held, at most capacity) and dropped one int32 each.  Rows at and behind count are
+ *                                  written as -1: every element given has exactly one writer.  ONE kernel on the engine's stream,
+ *                                  ordered against consumer_stream as cfx_observe_device.  reset != 0 empties the log and zeroes
+ *                                  dropped behind that kernel, in stream order.  CFX_ERR_STATE while there is no log.
+ *   "cfx_get_trip_log"             the same into host memory; synchronous.
+ *   "cfx_trip_log_set_state"       replaces the log's content by n rows (the seven columns of `rows` in host memory, [n] each;
+ *                                  its count / dropped are not read) and `dropped`, after a renumbering load as
+ *                                  cfx_trip_stats_set_state; reading them out before is cfx_get_trip_log with reset = 0.
+ *                                  CFX_ERR_INVALID for n beyond the capacity.  Synchronous. */
+typedef struct cfx_trip_log_out {
+    int32_t *count, *dropped;
+    int32_t *env, *vehicle, *origin_road, *destination_road, *enter_step, *finish_step, *travel_steps;
+} cfx_trip_log_out;
+#define CFX_TRIP_LOG_MAX_CAPACITY (1 << 26)
+typedef int32_t (*cfx_trip_log_enable_fn)(cfx_engine *e, int32_t capacity);
+typedef int32_t (*cfx_observe_trip_log_device_fn)(cfx_engine *e, const cfx_trip_log_out *out, int32_t reset, void *consumer_stream);
+typedef int32_t (*cfx_get_trip_log_fn)(cfx_engine *e, const cfx_trip_log_out *out, int32_t reset);
+typedef int32_t (*cfx_trip_log_set_state_fn)(cfx_engine *e, const cfx_trip_log_out *rows, int32_t n, int32_t dropped);
+
 /* ---- Per-movement (roadLink) throughput and delay statistics accumulated across steps (OPTIONAL entry points, as above; not with
  * lane change, not on a tile: CFX_ERR_STATE).  Off by default: nothing is allocated or launched.  Independent of the lane-flow
  * tracker: both on means two ticks and two records per vehicle.  s = the step counter after a step; D(v) = the drivable
