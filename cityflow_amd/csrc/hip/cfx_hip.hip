@@ -187,7 +187,8 @@ struct cfx_engine {
     TlPlanErr *hPlanErr = nullptr;  // pinned, host-mapped; inter = -1: none
     int32_t planCalls = 0;          // set calls enqueued so far (TlPlanErr::done: the last one the device has decided)
     // The staging arena of the host forms (cfx_get_lane_obs, cfx_get_lane_features, cfx_get_intersection_features,
-    // cfx_get_movement_flow, cfx_set_tl_plan, cfx_get_tl_phase_durations, cfx_set_vehicle_speeds): the device side of the host
+    // cfx_get_movement_flow, cfx_set_tl_plan, cfx_get_tl_phase_durations, cfx_set_vehicle_speeds, cfx_set_vehicle_routes,
+    // cfx_get_vehicle_routes): the device side of the host
     // arrays one call was given, laid out by cfx_stage_layout.h.  ONE allocation (in `owned`), grown to the largest request
     // seen, rounded up to a power of two so that requests that creep up (the speed commands of a filling network) regrow it a
     // logarithmic number of times.  Growing frees the old one at once, which is safe because the arena is idle at every
@@ -195,8 +196,8 @@ struct cfx_engine {
     char *stage = nullptr;
     size_t stageBytes = 0;
     int32_t *rowTileSum = nullptr;  // cfx_observe_vehicles_device: the scan's tile totals [ceil(D / kRowTile)] (in `owned`)
-    // cfx_set_vehicle_speeds_device / cfx_set_vehicle_speeds: the row that commands each vehicle number [speedStampCap], all -1
-    // between calls (in `owned`)
+    // cfx_set_vehicle_speeds_device / cfx_set_vehicle_speeds and cfx_set_vehicle_routes_device / cfx_set_vehicle_routes: the row
+    // that commands each vehicle number [speedStampCap], all -1 between calls (in `owned`; vehicleStampEnsure)
     int32_t *speedStamp = nullptr;
     size_t speedStampCap = 0;
     // cfx_observe_intersections_device / cfx_get_intersection_features: the intersection -> roadLink -> {start lanes, end lanes,
@@ -4440,6 +4441,21 @@ static int vehicleSpeedsArgs(cfx_engine *e, const int32_t *vehicle, const double
     return CFX_OK;
 }
 
+// the stamp table of the speed and the route commands holds every vehicle number issued
+static int vehicleStampEnsure(cfx_engine *e) {
+    auto fail = [e](const std::string &m) { return e->fail(m); };
+    if (e->speedStampCap >= (size_t) e->spawned) return CFX_OK;  // (idle: nothing to keep, the new one starts out all -1)
+    const size_t cap = std::max<size_t>(e->vidCap, (size_t) e->spawned);
+    int32_t *stamp = nullptr;
+    int rc;
+    if ((rc = e->allocRaw(&stamp, cap))) return rc;
+    HIP_TRY(hipMemsetAsync(stamp, 0xFF, std::max<size_t>(cap, 1) * sizeof(int32_t), e->stream));
+    if (e->speedStamp) e->retired.push_back(e->speedStamp);
+    e->speedStamp = stamp;
+    e->speedStampCap = cap;
+    return CFX_OK;
+}
+
 // the kernels of one call on the engine's stream; every pointer device memory, `ignored` may be null.  The caller has settled.
 static int launchVehicleSpeeds(cfx_engine *e, const int32_t *vehicle, const double *speed, int32_t n, int32_t *ignored) {
     auto fail = [e](const std::string &m) { return e->fail(m); };
@@ -4448,15 +4464,7 @@ static int launchVehicleSpeeds(cfx_engine *e, const int32_t *vehicle, const doub
     int rc;
     if ((rc = e->syncTables())) return rc;
     if (e->ring && (rc = e->ringEnsure())) return rc;
-    if (e->speedStampCap < (size_t) e->spawned) {  // (idle: nothing to keep, the new one starts out all -1)
-        const size_t cap = std::max<size_t>(e->vidCap, (size_t) e->spawned);
-        int32_t *stamp = nullptr;
-        if ((rc = e->allocRaw(&stamp, cap))) return rc;
-        HIP_TRY(hipMemsetAsync(stamp, 0xFF, std::max<size_t>(cap, 1) * sizeof(int32_t), e->stream));
-        if (e->speedStamp) e->retired.push_back(e->speedStamp);
-        e->speedStamp = stamp;
-        e->speedStampCap = cap;
-    }
+    if ((rc = vehicleStampEnsure(e))) return rc;
     const VehSpeedsIn in{vehicle, speed, n, (int) e->spawned, e->speedStamp, ignored};
     const dim3 grid((unsigned) (((size_t) n + kBlock - 1) / kBlock));
     hipLaunchKernelGGL(k_speeds_claim, grid, dim3(kBlock), 0, e->stream, in, (const uint8_t *) e->vt.state);
@@ -4508,6 +4516,144 @@ int32_t cfx_set_vehicle_speeds(cfx_engine *e, const int32_t *vehicle, const doub
     if ((rc = e->stageClose(s))) return rc;
     if (ignored) *ignored = count;
     return CFX_OK;
+}
+
+// ---- route changes for many vehicles at once, and the routes they hold (optional entry points of include/cityflow_amd.h, as
+// above): k_routes_claim and kr_routes_apply, or k_routes_superseded and k_routes_apply_dense (cfx_kernels.h has the scheme)
+int32_t cfx_set_vehicle_routes_device(cfx_engine *e, const int32_t *vehicle, const int32_t *route, int32_t n, int32_t *status,
+                                      int32_t *ignored, void *producerStream);
+int32_t cfx_set_vehicle_routes(cfx_engine *e, const int32_t *vehicle, const int32_t *route, int32_t n, int32_t *status, int32_t *ignored);
+int32_t cfx_get_vehicle_routes_device(cfx_engine *e, const int32_t *vehicle, int32_t n, int32_t *routeOut, void *consumerStream);
+int32_t cfx_get_vehicle_routes(cfx_engine *e, const int32_t *vehicle, int32_t n, int32_t *routeOut);
+static_assert(std::is_same<decltype(&cfx_set_vehicle_routes_device), cfx_set_vehicle_routes_device_fn>::value, "cfx_set_vehicle_routes_device");
+static_assert(std::is_same<decltype(&cfx_set_vehicle_routes), cfx_set_vehicle_routes_fn>::value, "cfx_set_vehicle_routes");
+static_assert(std::is_same<decltype(&cfx_get_vehicle_routes_device), cfx_get_vehicle_routes_device_fn>::value, "cfx_get_vehicle_routes_device");
+static_assert(std::is_same<decltype(&cfx_get_vehicle_routes), cfx_get_vehicle_routes_fn>::value, "cfx_get_vehicle_routes");
+
+// what the four forms check first (`second`: the route handles, or the output of the read)
+static int vehicleRoutesArgs(cfx_engine *e, const void *vehicle, const void *second, bool vehicleNeeded, int32_t n, const char *what) {
+    if (n < 0 || (n > 0 && ((vehicleNeeded && !vehicle) || !second))) {
+        e->err = std::string(what) + ": n must not be negative, and the arrays are needed for n > 0";
+        return CFX_ERR_INVALID;
+    }
+    if (e->lc.on || e->tiled) {
+        e->err = std::string(what) + ": not with lane change (the vehicle numbers are cfx_observe_vehicles_device's) and not on a tile";
+        return CFX_ERR_STATE;
+    }
+    return CFX_OK;
+}
+// the routes of one environment (a handle's range) and its lanes
+static void vehicleRoutesEnv(const cfx_engine *e, int *routesPerEnv, int *lanesPerEnv) {
+    const int nEnvs = e->cfg.n_envs > 1 ? e->cfg.n_envs : 1;
+    *routesPerEnv = ((int) e->hRouteStart.size() - 1) / nEnvs;
+    *lanesPerEnv = std::max(e->L / nEnvs, 1);
+}
+
+// the kernels of one call on the engine's stream; every pointer device memory, `status` and `ignored` may be null.  The caller has settled.
+static int launchVehicleRoutes(cfx_engine *e, const int32_t *vehicle, const int32_t *route, int32_t n, int32_t *status, int32_t *ignored) {
+    auto fail = [e](const std::string &m) { return e->fail(m); };
+    if (ignored) HIP_TRY(hipMemsetAsync(ignored, 0, sizeof(int32_t), e->stream));
+    if (n == 0) return CFX_OK;
+    int rc;
+    if ((rc = e->syncTables())) return rc;
+    if (e->ring && (rc = e->ringEnsure())) return rc;
+    if ((rc = vehicleStampEnsure(e))) return rc;
+    VehRoutesIn in{vehicle, route, n, (int) e->spawned, 0, 1, e->speedStamp, status, ignored};
+    vehicleRoutesEnv(e, &in.routesPerEnv, &in.lanesPerEnv);
+    const dim3 grid((unsigned) (((size_t) n + kBlock - 1) / kBlock));
+    hipLaunchKernelGGL(k_routes_claim, grid, dim3(kBlock), 0, e->stream, in, (const uint8_t *) e->vt.state);
+    if (e->ring) {
+        hipLaunchKernelGGL(kr_routes_apply, grid, dim3(kBlock), 0, e->stream, e->rctx(), in, e->vt);
+    } else {
+        hipLaunchKernelGGL(k_routes_superseded, grid, dim3(kBlock), 0, e->stream, in, (const uint8_t *) e->vt.state);
+        hipLaunchKernelGGL(k_routes_apply_dense, dim3(gridStride(e->slotCap)), dim3(kBlock), 0, e->stream, e->ctx(), in, e->vt);
+    }
+    HIP_TRY(hipGetLastError());
+    return CFX_OK;
+}
+
+int32_t cfx_set_vehicle_routes_device(cfx_engine *e, const int32_t *vehicle, const int32_t *route, int32_t n, int32_t *status,
+                                      int32_t *ignored, void *producerStream) {
+    const char *what = "cfx_set_vehicle_routes_device";
+    if (!e) return CFX_ERR_INVALID;
+    int rc;
+    if ((rc = vehicleRoutesArgs(e, vehicle, route, true, n, what))) return rc;
+    auto fail = [e](const std::string &m) { return e->fail(m); };
+    HIP_TRY(hipSetDevice(e->device));
+    if ((rc = checkDevicePointers(e, what, {{n ? vehicle : nullptr, "vehicle"}, {n ? route : nullptr, "route"},
+                                            {n ? status : nullptr, "status"}, {ignored, "ignored"}})))
+        return rc;
+    if (n == 0 && !ignored) return CFX_OK;
+    if ((rc = e->settle(false))) return rc;  // (ring layout: a commit deferred to the next step's admission)
+    if ((rc = e->orderAfterCaller((hipStream_t) producerStream))) return rc;
+    if ((rc = launchVehicleRoutes(e, vehicle, route, n, status, ignored))) return rc;
+    return e->orderCallerAfter((hipStream_t) producerStream);  // (status and the count are there; the rows may be overwritten)
+}
+
+int32_t cfx_set_vehicle_routes(cfx_engine *e, const int32_t *vehicle, const int32_t *route, int32_t n, int32_t *status, int32_t *ignored) {
+    const char *what = "cfx_set_vehicle_routes";
+    if (!e) return CFX_ERR_INVALID;
+    int rc;
+    if ((rc = vehicleRoutesArgs(e, vehicle, route, true, n, what))) return rc;
+    if (ignored) *ignored = 0;
+    if (n == 0) return CFX_OK;
+    auto fail = [e](const std::string &m) { return e->fail(m); };
+    HIP_TRY(hipSetDevice(e->device));
+    if ((rc = e->settle(false))) return rc;
+    int32_t count = 0;
+    cfx_stage::StageLayout s;
+    const auto fVehicle = s.in(vehicle, (size_t) n);
+    const auto fRoute = s.in(route, (size_t) n);
+    const auto fStatus = s.out(status, (size_t) n);
+    const auto fCount = s.out(&count, 1);
+    if ((rc = e->stageOpen(s))) return rc;
+    if ((rc = launchVehicleRoutes(e, s.dev(fVehicle), s.dev(fRoute), n, s.dev(fStatus), s.dev(fCount)))) return rc;
+    if ((rc = e->stageClose(s))) return rc;
+    if (ignored) *ignored = count;
+    return CFX_OK;
+}
+
+// the kernel of one read on the engine's stream; vehicle may be null (the numbers 0 .. n-1).  The caller has settled; n > 0.
+static int launchGetVehicleRoutes(cfx_engine *e, const int32_t *vehicle, int32_t n, int32_t *routeOut) {
+    auto fail = [e](const std::string &m) { return e->fail(m); };
+    int routesPerEnv = 0, lanesPerEnv = 1;
+    vehicleRoutesEnv(e, &routesPerEnv, &lanesPerEnv);
+    hipLaunchKernelGGL(k_get_routes, dim3((unsigned) (((size_t) n + kBlock - 1) / kBlock)), dim3(kBlock), 0, e->stream, vehicle, (int) n,
+                       (int) e->spawned, (const int32_t *) e->vt.route, (const uint8_t *) e->vt.state, std::max(routesPerEnv, 1), routeOut);
+    HIP_TRY(hipGetLastError());
+    return CFX_OK;
+}
+
+int32_t cfx_get_vehicle_routes_device(cfx_engine *e, const int32_t *vehicle, int32_t n, int32_t *routeOut, void *consumerStream) {
+    const char *what = "cfx_get_vehicle_routes_device";
+    if (!e) return CFX_ERR_INVALID;
+    int rc;
+    if ((rc = vehicleRoutesArgs(e, vehicle, routeOut, true, n, what))) return rc;
+    auto fail = [e](const std::string &m) { return e->fail(m); };
+    HIP_TRY(hipSetDevice(e->device));
+    if ((rc = checkDevicePointers(e, what, {{n ? vehicle : nullptr, "vehicle"}, {n ? routeOut : nullptr, "route_out"}}))) return rc;
+    if (n == 0) return CFX_OK;
+    if ((rc = e->settle(false))) return rc;
+    if ((rc = e->orderAfterCaller((hipStream_t) consumerStream))) return rc;
+    if ((rc = launchGetVehicleRoutes(e, vehicle, n, routeOut))) return rc;
+    return e->orderCallerAfter((hipStream_t) consumerStream);
+}
+
+int32_t cfx_get_vehicle_routes(cfx_engine *e, const int32_t *vehicle, int32_t n, int32_t *routeOut) {
+    const char *what = "cfx_get_vehicle_routes";
+    if (!e) return CFX_ERR_INVALID;
+    int rc;
+    if ((rc = vehicleRoutesArgs(e, vehicle, routeOut, false, n, what))) return rc;
+    if (n == 0) return CFX_OK;
+    auto fail = [e](const std::string &m) { return e->fail(m); };
+    HIP_TRY(hipSetDevice(e->device));
+    if ((rc = e->settle(false))) return rc;
+    cfx_stage::StageLayout s;
+    const auto fVehicle = s.in(vehicle, (size_t) n);
+    const auto fOut = s.out(routeOut, (size_t) n);
+    if ((rc = e->stageOpen(s))) return rc;
+    if ((rc = launchGetVehicleRoutes(e, s.dev(fVehicle), n, s.dev(fOut)))) return rc;
+    return e->stageClose(s);
 }
 
 // ---- per-intersection movement and phase observations (optional entry points of include/cityflow_amd.h, as above)

@@ -1926,6 +1926,122 @@ __global__ void k_set_route(StepCtx c, int vid, int route) {
         }
 }
 
+// cfx_set_vehicle_routes_device: Router::setRoute for n rows {vehicle number, route handle} in device memory (include/
+// cityflow_amd.h has the status table).  A handle is a route index of ONE environment; the vehicle's environment is that of
+// its drivable (lane / lanesPerEnv), the route written is env * routesPerEnv + handle.  The stamp table is the speed
+// commands' (idle at -1 between calls), claimed the same way:
+//   1. k_routes_claim: a row that is skipped (0), names no running vehicle (-1) or no handle (-2) gets its status here; every
+//      other row does atomicMax(stamp[v], row).  Of those rows the LAST one is the vehicle's command whatever its verdict
+//      turns out to be (the dense layout learns the vehicle's drivable only in its slot pass, after the claim), so this is
+//      not "the last valid row wins"
+//   2. ring layout, kr_routes_apply (cfx_ring_kernels.h): a claiming row that does not find its own index reads -3; the one
+//      that does finds the slot through slotOf, judges (routeVerdict), applies and puts the stamp back to -1
+//      dense layout (no slotOf), k_routes_superseded: the -3 rows; then k_routes_apply_dense, one pass over the slots, takes
+//      the row from the stamp of each slot's vehicle, judges, applies, writes that row's status and clears the stamp
+// Every index is checked against nVid / routesPerEnv before it is used; the rows are only read, `status` is written in [0, n).
+struct VehRoutesIn {
+    const int32_t *vehicle;  // [n]
+    const int32_t *route;    // [n] handles
+    int n, nVid;             // nVid: the vehicle numbers issued (cfx_engine::spawned when the call was made)
+    int routesPerEnv, lanesPerEnv;
+    int32_t *stamp;          // [>= nVid]
+    int32_t *status;         // [n] or null
+    int32_t *ignored;        // [1] or null
+};
+// the first three checks of row i < n: 0 skipped, -1 no such running vehicle, -2 no such handle, 1 the row claims.  *v, *h: its values
+__device__ __forceinline__ int routesRow(const VehRoutesIn &in, size_t i, const uint8_t *state, int *v, int *h) {
+    *v = in.vehicle[i];
+    *h = in.route[i];
+    if (*v == -1 || *h == -1) return 0;
+    if (*v < 0 || *v >= in.nVid || state[*v] != 1) return -1;  // (0: still in its lane's entry buffer, the device keeps no lane for it)
+    if (*h < 0 || *h >= in.routesPerEnv) return -2;
+    return 1;
+}
+// counts the rows with a negative status: a ballot and one atomic per wavefront.  Every thread of the block calls it.
+__device__ __forceinline__ void routesCountIgnored(int32_t *ignored, bool bad) {
+    if (!ignored) return;
+    const unsigned long long votes = __ballot(bad);
+    if ((threadIdx.x & 63) == 0 && votes) atomicAdd(ignored, __popcll(votes));
+}
+// The verdict on a vehicle on drivable d taking `route` (a global index): -4 on a laneLink (router.cpp:246), -5 its road does
+// not occur before the route's last road (router.cpp:239), -6 its lane has no laneLink towards the next road (Router::
+// onValidLane, router.h:66-68); 1 with *p = the first position of its road and *next = its next drivable
+template <class C> __device__ __forceinline__ int routeVerdict(const C &c, int d, int route, int *p, int *next) {
+    if (d >= c.n.L) return -4;
+    const int road = c.n.laneRoad[d], base = c.t.routeStart[route], len = c.t.routeStart[route + 1] - base;
+    int q = 0;
+    while (q < len - 1 && c.t.routeRoads[base + q] != road) ++q;
+    if (q >= len - 1) return -5;
+    const int ll = c.t.nextLL[c.t.nextStart[base + q] + c.n.laneIndex[d]];
+    if (ll < 0) return -6;
+    *p = q;
+    *next = c.n.L + ll;
+    return 1;
+}
+__global__ void __launch_bounds__(kBlock) k_routes_claim(VehRoutesIn in, const uint8_t *state) {
+    const size_t i = blockIdx.x * (size_t) blockDim.x + threadIdx.x;  // (a row only below n: the cast to int below is exact)
+    int r = 0;
+    if (i < (size_t) in.n) {
+        int v, h;
+        r = routesRow(in, i, state, &v, &h);
+        if (r == 1) atomicMax(&in.stamp[v], (int) i);
+        else if (in.status) in.status[i] = r;
+    }
+    routesCountIgnored(in.ignored, r < 0);
+}
+__global__ void __launch_bounds__(kBlock) k_routes_superseded(VehRoutesIn in, const uint8_t *state) {
+    const size_t i = blockIdx.x * (size_t) blockDim.x + threadIdx.x;
+    bool bad = false;
+    if (i < (size_t) in.n) {
+        int v, h;
+        bad = routesRow(in, i, state, &v, &h) == 1 && in.stamp[v] != (int) i;
+        if (bad && in.status) in.status[i] = -3;
+    }
+    routesCountIgnored(in.ignored, bad);
+}
+__global__ void __launch_bounds__(kBlock) k_routes_apply_dense(StepCtx c, VehRoutesIn in, VidTable vt) {
+    const int S = c.segStart[c.n.L + c.n.K];
+    const int stride = gridDim.x * blockDim.x;
+    int refused = 0;
+    for (int s = blockIdx.x * blockDim.x + threadIdx.x; s < S; s += stride) {
+        const int v = c.s.vid[s];
+        if (v < 0 || v >= in.nVid) continue;
+        const int row = in.stamp[v];
+        if (row < 0 || row >= in.n) continue;
+        const int d = c.s.drv[s];
+        int p = 0, next = -1, r = -4;
+        if (d < c.n.L) {
+            const int route = d / in.lanesPerEnv * in.routesPerEnv + in.route[row];
+            r = routeVerdict(c, d, route, &p, &next);
+            if (r == 1) {
+                c.s.route[s] = route;
+                c.s.routePos[s] = p;
+                c.s.next[s] = next;
+                c.s.flags[s] = (uint8_t) ((c.s.flags[s] & (kFlagCustom | kFlagStateGap)) | lastRoadBit(c, d, route, next));
+                vt.route[v] = route;
+            }
+        }
+        if (in.status) in.status[row] = r;
+        refused += r < 0;
+        in.stamp[v] = -1;
+    }
+    if (in.ignored && refused) atomicAdd(in.ignored, refused);
+}
+// cfx_get_vehicle_routes_device: the handle each named vehicle holds (its route index within its environment), -1 for a -1
+// row, a number that was not issued and a finished vehicle.  vehicle == null: the numbers 0 .. n-1
+__global__ void __launch_bounds__(kBlock) k_get_routes(const int32_t *vehicle, int n, int nVid, const int32_t *route,
+                                                       const uint8_t *state, int routesPerEnv, int32_t *out) {
+    const size_t i = blockIdx.x * (size_t) blockDim.x + threadIdx.x;
+    if (i >= (size_t) n) return;
+    const int v = vehicle ? vehicle[i] : (int) i;
+    int r = -1;
+    if (v >= 0 && v < nVid && state[v] != 2) {
+        r = route[v];
+        r = r < 0 ? -1 : r % routesPerEnv;
+    }
+    out[i] = r;
+}
+
 // TrafficLight::setPhase (trafficlight.cpp:39-41) for n (intersection, phase) pairs read from pinned host memory
 __global__ void k_set_phases(const int32_t *pairs, int n, int32_t *curPhase) {
     int i = blockIdx.x * blockDim.x + threadIdx.x;

@@ -2479,6 +2479,39 @@ __global__ void kr_set_route(RingCtx c, int vid, int route) {
     c.meta[s].y = nextD;
     c.meta[s].z = (c.meta[s].z & (kFlagCustom | kFlagStateGap)) | ((nextD < 0 && isLastRoad(c, dNow, route)) ? 2 : 0);
 }
+// cfx_set_vehicle_routes_device, ring layout, after k_routes_claim (cfx_kernels.h has the scheme): the rows that claimed
+__global__ void __launch_bounds__(kBlock) kr_routes_apply(RingCtx c, VehRoutesIn in, VidTable vt) {
+    const size_t i = blockIdx.x * (size_t) blockDim.x + threadIdx.x;
+    bool bad = false;
+    int v, h;
+    if (i < (size_t) in.n && routesRow(in, i, vt.state, &v, &h) == 1) {
+        int r = -3;
+        if (in.stamp[v] == (int) i) {
+            const int s = c.slotOf[v];
+            r = -1;  // (a running vehicle has a slot)
+            if (s >= 0) {
+                const int d = c.s.drv[s];
+                int p = 0, next = -1;
+                r = -4;
+                if (d < c.n.L) {
+                    const int route = d / in.lanesPerEnv * in.routesPerEnv + h;
+                    r = routeVerdict(c, d, route, &p, &next);
+                    if (r == 1) {
+                        c.s.route[s] = route;
+                        c.s.routePos[s] = p;
+                        c.meta[s].y = next;
+                        c.meta[s].z = (c.meta[s].z & (kFlagCustom | kFlagStateGap)) | lastRoadBit(c, d, route, next);
+                        vt.route[v] = route;
+                    }
+                }
+            }
+            in.stamp[v] = -1;
+        }
+        if (in.status) in.status[i] = r;
+        bad = r < 0;
+    }
+    routesCountIgnored(in.ignored, bad);
+}
 __global__ void kr_find_vehicle(RingCtx c, int vid, int32_t *out /*[2]: drivable, routePos*/) {
     const int s = c.slotOf[vid];
     if (s < 0) return;

@@ -391,6 +391,7 @@ void Archive::dump(const std::string &path) const {
 Archive EngineHost::snapshotImpl(bool hostState) {
     dropAhead();
     settleLaneChange();
+    refreshRoutes();  // (routes changed on the device: a load takes every vehicle's route from the host's record)
     Archive a;
     if (hostState) a.host = spawner_.saveState();  // (compactVehicles builds its own)
     a.net = net_;
@@ -515,6 +516,7 @@ void EngineHost::load(const Archive &a) {
     if (a.net.get() != net_.get() && a.net->lanes.size() != net_->lanes.size())
         throw std::runtime_error("Engine.load: archive belongs to a different road network");
     spawner_.loadState(a.host);
+    routesStale_ = false;  // (every vehicle's route is the archive's, on the host and on the device)
     uploadNewTablesIfAny();
     const DeviceState &d = a.dev;
     const int nV = (int) a.host.vehicles.size();
@@ -631,6 +633,7 @@ std::shared_ptr<DeviceCheckpoint> EngineHost::checkpoint(std::shared_ptr<DeviceC
     check(be_.cfx_checkpoint_save(dev_, ck->ck), "cfx_checkpoint_save");
     ck->host.resize(1);
     ck->host[0] = spawner_.saveState();
+    ck->routesStale = routesStale_;  // (no read-back here: a checkpoint does not wait for the device)
     ck->step = step_;
     ck->waitingCustom = waitingCustom_;
     return ck;
@@ -651,6 +654,7 @@ void EngineHost::rollback(DeviceCheckpoint &ck) {
     pendingPhaseInter_.clear();
     pendingPhaseValue_.clear();
     spawner_.loadState(ck.host[0]);
+    routesStale_ = ck.routesStale;
     uploadNewTablesIfAny();
     check(be_.cfx_checkpoint_restore(dev_, ck.ck), "cfx_checkpoint_restore");
     forgetPhases();  // (the lights now show the checkpoint's phases)

@@ -98,6 +98,10 @@ void Backend::open(const std::string &libPath) {
     CFX_FN_OPTIONAL(cfx_observe_vehicles_device)
     CFX_FN_OPTIONAL(cfx_set_vehicle_speeds_device)
     CFX_FN_OPTIONAL(cfx_set_vehicle_speeds)
+    CFX_FN_OPTIONAL(cfx_set_vehicle_routes_device)
+    CFX_FN_OPTIONAL(cfx_set_vehicle_routes)
+    CFX_FN_OPTIONAL(cfx_get_vehicle_routes_device)
+    CFX_FN_OPTIONAL(cfx_get_vehicle_routes)
     CFX_FN_OPTIONAL(cfx_observe_intersections_device)
     CFX_FN_OPTIONAL(cfx_get_intersection_features)
     CFX_FN_OPTIONAL(cfx_lane_flow_enable)
@@ -806,6 +810,104 @@ int EngineHost::setVehicleSpeeds(const int32_t *vehicle, const double *speed, in
     return ignored;
 }
 
+static void needVehicleRoutes(const Backend &be) {
+    if (!be.hasDeviceBuffers() || !be.hasVehicleRoutes())
+        throw std::runtime_error("cityflow_amd: '" + be.path + "' has no device-side vehicle route changes");
+}
+
+void setVehicleRoutesDeviceOf(const Backend &be, cfx_engine *dev, uintptr_t vehicle, uintptr_t route, int n, uintptr_t status,
+                              uintptr_t ignored, uintptr_t producerStream) {
+    needVehicleRoutes(be);
+    if (be.cfx_set_vehicle_routes_device(dev, (const int32_t *) vehicle, (const int32_t *) route, (int32_t) n, (int32_t *) status,
+                                         (int32_t *) ignored, (void *) producerStream) != CFX_OK)
+        backendFail(be, dev, "cfx_set_vehicle_routes_device");
+}
+
+int setVehicleRoutesOf(const Backend &be, cfx_engine *dev, const int32_t *vehicle, const int32_t *route, int n, int32_t *status) {
+    needVehicleRoutes(be);
+    int32_t ignored = 0;
+    if (be.cfx_set_vehicle_routes(dev, vehicle, route, (int32_t) n, status, &ignored) != CFX_OK) backendFail(be, dev, "cfx_set_vehicle_routes");
+    return (int) ignored;
+}
+
+void vehicleRoutesDeviceOf(const Backend &be, cfx_engine *dev, uintptr_t vehicle, int n, uintptr_t out, uintptr_t consumerStream) {
+    needVehicleRoutes(be);
+    if (be.cfx_get_vehicle_routes_device(dev, (const int32_t *) vehicle, (int32_t) n, (int32_t *) out, (void *) consumerStream) != CFX_OK)
+        backendFail(be, dev, "cfx_get_vehicle_routes_device");
+}
+
+void vehicleRoutesOf(const Backend &be, cfx_engine *dev, const int32_t *vehicle, int n, int32_t *out) {
+    needVehicleRoutes(be);
+    if (be.cfx_get_vehicle_routes(dev, vehicle, (int32_t) n, out) != CFX_OK) backendFail(be, dev, "cfx_get_vehicle_routes");
+}
+
+std::vector<int> EngineHost::addRoutes(const std::vector<std::vector<std::string>> &routes) {
+    dropAhead();
+    std::vector<std::vector<int>> anchors(routes.size());
+    for (size_t i = 0; i < routes.size(); ++i)
+        for (const std::string &id : routes[i]) {
+            const auto it = net_->roadIndex.find(id);
+            if (it == net_->roadIndex.end())
+                throw std::invalid_argument("add_routes: routes[" + std::to_string(i) + "]: no such road '" + id + "'");
+            anchors[i].push_back(it->second);
+        }
+    return spawner_.addRoutes(anchors);  // (the device gets the tables with the next call that needs them: uploadNewTablesIfAny)
+}
+
+std::vector<std::string> EngineHost::routeRoads(int handle) {
+    const RouteTable &rt = spawner().routes;
+    if (handle < 0 || handle >= rt.count()) throw std::out_of_range("route_roads: no such route handle " + std::to_string(handle));
+    std::vector<std::string> ids;
+    for (int p = rt.routeStart[(size_t) handle]; p < rt.routeStart[(size_t) handle + 1]; ++p) ids.push_back(net_->roads[(size_t) rt.roads[(size_t) p]].id);
+    return ids;
+}
+
+static const char *kRoutesNoLaneChange = "set_vehicle_routes: not with laneChange (the vehicle numbers are observe_vehicles')";
+
+void EngineHost::setVehicleRoutesDevice(uintptr_t vehicle, uintptr_t route, int n, uintptr_t status, uintptr_t ignored,
+                                        uintptr_t producerStream) {
+    if (laneChange_) throw std::runtime_error(kRoutesNoLaneChange);
+    needVehicleRoutes(be_);
+    dropAhead();
+    uploadNewTablesIfAny();
+    setVehicleRoutesDeviceOf(be_, dev_, vehicle, route, n, status, ignored, producerStream);
+    routesStale_ = true;
+}
+
+int EngineHost::setVehicleRoutes(const int32_t *vehicle, const int32_t *route, int n, int32_t *status) {
+    if (laneChange_) throw std::runtime_error(kRoutesNoLaneChange);
+    needVehicleRoutes(be_);
+    dropAhead();
+    uploadNewTablesIfAny();
+    const int ignored = setVehicleRoutesOf(be_, dev_, vehicle, route, n, status);
+    routesStale_ = true;
+    raiseDeviceError();
+    return ignored;
+}
+
+void EngineHost::vehicleRoutesDevice(uintptr_t vehicle, int n, uintptr_t out, uintptr_t consumerStream) {
+    if (laneChange_) throw std::runtime_error(kRoutesNoLaneChange);
+    vehicleRoutesDeviceOf(be_, dev_, vehicle, n, out, consumerStream);
+}
+
+void EngineHost::vehicleRoutes(const int32_t *vehicle, int n, int32_t *out) {
+    if (laneChange_) throw std::runtime_error(kRoutesNoLaneChange);
+    vehicleRoutesOf(be_, dev_, vehicle, n, out);
+    raiseDeviceError();
+}
+
+// the host's record of every vehicle's route after device-side route changes: one read of the device's table
+void EngineHost::refreshRoutes() {
+    if (!routesStale_) return;
+    dropAhead();
+    const int n = (int) spawner_.vehicles.size();
+    std::vector<int32_t> held((size_t) n);
+    if (n) vehicleRoutesOf(be_, dev_, nullptr, n, held.data());
+    for (int v = 0; v < n; ++v)
+        if (held[(size_t) v] >= 0) spawner_.setVehicleRoute(v, held[(size_t) v]);  // (-1: finished, its record is no longer read)
+    routesStale_ = false;
+}
+
 VehicleColumns vehicleColumnsOf(const Backend &be, cfx_engine *dev, bool vid, bool dis, bool speed) {
     cfx_scalars sc{};
     if (be.cfx_get_scalars(dev, &sc) != CFX_OK) backendFail(be, dev, "cfx_get_scalars");
@@ -1089,6 +1191,7 @@ void EngineHost::trackTrips(bool on) {
 
 void EngineHost::tripNoteVehicles() {
     if (!trackers_.trip.onHost()) return;
+    refreshRoutes();
     const size_t n = spawner_.committedVehicleCount();
     for (size_t v = (size_t) trackers_.trip.noted(); v < n; ++v) tripNote((int32_t) v);
 }
@@ -1472,6 +1575,7 @@ std::map<std::string, std::string> EngineHost::getVehicleInfo(const std::string 
     std::map<std::string, std::string> info;
     info["running"] = std::to_string(st == 1);
     if (st != 1) return info;
+    refreshRoutes();
     VehicleSnapshot s;
     snapshotVehicles(s);
     for (int i = 0; i < s.count; ++i) {
@@ -1641,6 +1745,7 @@ void EngineHost::setVehicleSpeed(const std::string &id, double speed) {
 // Engine::setRoute engine.cpp:852-866 + Router::setRoute router.cpp:245-264
 bool EngineHost::setRoute(const std::string &vehicleId, const std::vector<std::string> &anchorIds) {
     dropAhead();
+    refreshRoutes();  // (the record this call writes, and tripNote reads, is the device's)
     int vid = vidOf(vehicleId);
     if (vid < 0) return false;
     int32_t state = 2, drivable = -1, routePos = -1, route = -1;

@@ -94,6 +94,15 @@ struct Backend {
     // optional as a pair: speed commands for many vehicles at once (without them the host commands row by row: setVehicleSpeedsOf)
     cfx_set_vehicle_speeds_device_fn cfx_set_vehicle_speeds_device = nullptr;
     cfx_set_vehicle_speeds_fn cfx_set_vehicle_speeds = nullptr;
+    // optional as a set: route changes for many vehicles at once and the routes they hold (without them there is no such
+    // call: cfx_set_vehicle_route restarts the cursor and cannot stand in)
+    cfx_set_vehicle_routes_device_fn cfx_set_vehicle_routes_device = nullptr;
+    cfx_set_vehicle_routes_fn cfx_set_vehicle_routes = nullptr;
+    cfx_get_vehicle_routes_device_fn cfx_get_vehicle_routes_device = nullptr;
+    cfx_get_vehicle_routes_fn cfx_get_vehicle_routes = nullptr;
+    bool hasVehicleRoutes() const {
+        return cfx_set_vehicle_routes_device && cfx_set_vehicle_routes && cfx_get_vehicle_routes_device && cfx_get_vehicle_routes;
+    }
     // optional as a pair: per-intersection observations (without them the host computes the arrays from the getters above)
     cfx_observe_intersections_device_fn cfx_observe_intersections_device = nullptr;
     cfx_get_intersection_features_fn cfx_get_intersection_features = nullptr;
@@ -259,6 +268,17 @@ void setVehicleSpeedsDeviceOf(const Backend &be, cfx_engine *dev, uintptr_t vehi
 int setVehicleSpeedsOf(const Backend &be, cfx_engine *dev, const int32_t *vehicle, const double *speed, int n,
                        std::map<int32_t, double> *waitingCommands);
 
+// Route changes for n rows {vehicle number, route handle} and the handles the vehicles hold (cfx_set_vehicle_routes_device's
+// rules, include/cityflow_amd.h), from device memory (every pointer a device address, `status` and `ignored` may be 0) and
+// from host arrays (`status` may be null; returns the rows refused; vehicle == null reads the numbers 0 .. n-1).  There is no
+// row-by-row form over cfx_set_vehicle_route, which restarts a route at its first road: std::runtime_error naming the
+// library on a backend without the entry points.
+void setVehicleRoutesDeviceOf(const Backend &be, cfx_engine *dev, uintptr_t vehicle, uintptr_t route, int n, uintptr_t status,
+                              uintptr_t ignored, uintptr_t producerStream);
+int setVehicleRoutesOf(const Backend &be, cfx_engine *dev, const int32_t *vehicle, const int32_t *route, int n, int32_t *status);
+void vehicleRoutesDeviceOf(const Backend &be, cfx_engine *dev, uintptr_t vehicle, int n, uintptr_t out, uintptr_t consumerStream);
+void vehicleRoutesOf(const Backend &be, cfx_engine *dev, const int32_t *vehicle, int n, int32_t *out);
+
 // A checkpoint in device memory (cfx_checkpoint_* of include/cityflow_amd.h; the public calls are checkpoint() / rollback() of
 // cityflow_amd/torch_io.py), of an EngineHost or a VectorEngineHost: the backend's part, and what Engine.load() takes from an
 // Archive on the host — the spawners' states (one per environment) and the step — plus what an Archive does not carry.  It
@@ -268,6 +288,7 @@ struct DeviceCheckpoint {
     cfx_checkpoint *ck = nullptr;  // null once released
     const void *owner = nullptr;   // the EngineHost / VectorEngineHost
     std::vector<Spawner::State> host;
+    bool routesStale = false;  // the vehicles' routes in `host` were behind the device's (EngineHost::routesStale_)
     size_t step = 0;
     std::map<int32_t, double> waitingCustom;                  // EngineHost::waitingCustom_
     std::vector<std::vector<int32_t>> localToGlobal;          // VectorEngineHost's numbering
@@ -377,6 +398,20 @@ public:
     bool vehicleSpeedsDevice() const { return be_.hasDeviceBuffers() && be_.cfx_set_vehicle_speeds_device; }
     void setVehicleSpeedsDevice(uintptr_t vehicle, uintptr_t speed, int n, uintptr_t ignored, uintptr_t producerStream);
     int setVehicleSpeeds(const int32_t *vehicle, const double *speed, int n);
+    // ---- candidate routes named up front and route changes for many vehicles at once (cfx_set_vehicle_routes_device and its
+    //      kin, include/cityflow_amd.h).  A handle is an index into spawner_.routes, flow routes included; the tables are
+    //      never dropped, so it holds across reset, load, rollback and vehicle compaction.  addRoutes: std::invalid_argument
+    //      naming the list's index for an unknown road or a route the reference calls invalid, and then nothing is added.
+    //      The device calls leave spawner_.vehicles[v].route stale: routesStale_ is raised, and every reader of that record
+    //      calls refreshRoutes() first (one bulk read through cfx_get_vehicle_routes).  std::runtime_error with laneChange
+    //      and on a backend without the entry points
+    std::vector<int> addRoutes(const std::vector<std::vector<std::string>> &routes);
+    std::vector<std::string> routeRoads(int handle);
+    int routeCount() { return spawner().routes.count(); }
+    void setVehicleRoutesDevice(uintptr_t vehicle, uintptr_t route, int n, uintptr_t status, uintptr_t ignored, uintptr_t producerStream);
+    int setVehicleRoutes(const int32_t *vehicle, const int32_t *route, int n, int32_t *status);  // returns the rows refused
+    void vehicleRoutesDevice(uintptr_t vehicle, int n, uintptr_t out, uintptr_t consumerStream);
+    void vehicleRoutes(const int32_t *vehicle, int n, int32_t *out);
     // ---- per-intersection movement and phase observations (cfx_observe_intersections_device / cfx_get_intersection_features;
     //      the twin: from the count getters, the vehicles and the lights).  Rows of layout().M roadLinks / layout().P phases
     const InterLayout &intersectionLayout();
@@ -525,6 +560,8 @@ private:
     Trackers trackers_;
     void tripNoteVehicles();  // (host tracker: the vehicle numbers created since the last call)
     void tripNote(int32_t vid);
+    bool routesStale_ = false;  // a device-side route change since spawner_.vehicles[...].route was last read back
+    void refreshRoutes();
 };
 
 struct EngineConfig {  // Engine::loadConfig engine.cpp:37-84

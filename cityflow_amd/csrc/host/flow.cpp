@@ -578,6 +578,21 @@ const std::vector<int> &seq) {
     return r;
 }
 
+std::vector<int> Spawner::addRoutes(const std::vector<std::vector<int>> &anchorLists) {
+    std::vector<std::vector<int>> seqs(anchorLists.size());
+    for (size_t i = 0; i < anchorLists.size(); ++i) {
+        for (int road : anchorLists[i])
+            if (road < 0 || road >= (int) net_->roads.size())
+                throw std::invalid_argument("add_routes: routes[" + std::to_string(i) + "] names a road the network does not have");
+        if (!expandRoute(anchorLists[i], seqs[i]))
+            throw std::invalid_argument("add_routes: routes[" + std::to_string(i) + "] is not a valid route");
+    }
+    std::vector<int> handles;
+    handles.reserve(seqs.size());
+    for (const std::vector<int> &seq : seqs) handles.push_back(internRoute(seq));
+    return handles;
+}
+
 Spawner::State Spawner::saveState() const {
     State st;
     for (const HostFlow &f : flows) st.flows.push_back(FlowDyn{f.nowTime, f.currentTime, f.cnt, f.valid});

@@ -134,6 +134,10 @@ public:
     // Route index for an expanded road sequence, adding it if it is new (used by set_vehicle_route and
     // load_from_file, which would otherwise add one route per vehicle).
     int internRoute(const std::vector<int> &roadSeq);
+    // Candidate routes named up front (Engine.add_routes): every anchor list expanded as a flow's route is and interned; the
+    // route indices in the order given.  All or nothing: a list the reference would call invalid (empty, or a road that
+    // cannot be reached, or a single road) throws std::invalid_argument naming the list's index before any is added.
+    std::vector<int> addRoutes(const std::vector<std::vector<int>> &anchorLists);
     void setVehicleRoute(int vid, int route) { vehicles[vid].route = route; }
 
     // Everything that changes while stepping, for Archive-style snapshot / restore (archive.cpp:62-66,161-165).

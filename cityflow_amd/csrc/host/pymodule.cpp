@@ -608,6 +608,30 @@ template <typename E> void defDeviceBuffers(py::class_<E> &c) {
                  return e.setVehicleSpeeds(vehicle.data(), speed.data(), (int) vehicle.size());
              },
              "vehicle"_a, "speed"_a, "int32 [N] vehicle numbers, float64 [N] speeds; returns the rows ignored; waits for the device")
+        .def("route_roads", &E::routeRoads, "handle"_a,
+             "the road ids of the route behind a handle (add_routes / added_routes, or any route index below route_count(), flow "
+             "routes included); IndexError for anything else")
+        .def("route_count", &E::routeCount, "the route handles are 0 .. route_count() - 1 (of one environment)")
+        .def("_set_vehicle_routes_device", &E::setVehicleRoutesDevice, "vehicle_ptr"_a, "route_ptr"_a, "n"_a, "status_ptr"_a,
+             "ignored_ptr"_a, "producer_stream"_a)
+        .def("_set_vehicle_routes",
+             [](E &e, py::array_t<int32_t, py::array::c_style> vehicle, py::array_t<int32_t, py::array::c_style> route) {
+                 if (vehicle.ndim() != 1 || route.ndim() != 1 || vehicle.size() != route.size())
+                     throw std::invalid_argument("set_vehicle_routes: vehicle and route must be one-dimensional and of one length");
+                 py::array_t<int32_t> status(vehicle.size());
+                 const int ignored = e.setVehicleRoutes(vehicle.data(), route.data(), (int) vehicle.size(), status.mutable_data());
+                 return py::make_tuple(status, ignored);
+             },
+             "vehicle"_a, "route"_a, "int32 [N] vehicle numbers, int32 [N] route handles; returns (status [N], rows refused); waits for the device")
+        .def("_vehicle_routes_device", &E::vehicleRoutesDevice, "vehicle_ptr"_a, "n"_a, "out_ptr"_a, "consumer_stream"_a)
+        .def("_vehicle_routes",
+             [](E &e, py::array_t<int32_t, py::array::c_style> vehicle) {
+                 if (vehicle.ndim() != 1) throw std::invalid_argument("get_vehicle_routes: vehicle must be one-dimensional");
+                 py::array_t<int32_t> out(vehicle.size());
+                 e.vehicleRoutes(vehicle.data(), (int) vehicle.size(), out.mutable_data());
+                 return out;
+             },
+             "vehicle"_a, "int32 [N] vehicle numbers; returns the handles they hold, -1 where there is none; waits for the device")
         .def("_intersection_dims", [](E &e) { return py::make_tuple(e.intersectionLayout().M, e.intersectionLayout().P); },
              "(largest roadLink count, largest phase count) of an intersection: the row lengths of the intersection observations")
         .def("_intersection_layout", [](E &e) { return intersectionLayoutDict(e); })
@@ -876,6 +900,11 @@ PYBIND11_MODULE(_cityflow, m) {
         .def("reset", &EngineHost::reset, "seed"_a = false)
         .def("set_vehicle_speed", &EngineHost::setVehicleSpeed, "vehicle_id"_a, "speed"_a)
         .def("set_vehicle_route", &EngineHost::setRoute, "vehicle_id"_a, "route"_a)
+        .def("add_routes", &EngineHost::addRoutes, "routes"_a,
+             "routes: lists of road ids, each expanded the way a flow's `route` is (consecutive roads joined by the shortest path) "
+             "and registered; returns their handles for set_vehicle_routes_tensor, equal lists sharing one.  Handles stay valid "
+             "across reset(), load(), rollback() and vehicle compaction.  ValueError naming the list's index for an unknown road "
+             "or a route the reference would call invalid, and then nothing is added")
         .def("load", &EngineHost::load, "archive"_a)
         .def("snapshot", &EngineHost::snapshot)
         .def("load_from_file", &EngineHost::loadFromFile, "path"_a)
@@ -1053,18 +1082,26 @@ PYBIND11_MODULE(_cityflow, m) {
                                              "lock-step by one device engine; observations and actions are arrays of shape "
                                              "[num_envs, ...].");
     vectorClass
-        .def(py::init([](const std::string &cfg, int envs, int threads, const std::optional<std::vector<int>> &seeds) {
-                 return std::unique_ptr<VectorEngineHost>(new VectorEngineHost(cfg, envs, threads, "", envSeeds(envs, seeds)));
+        .def(py::init([](const std::string &cfg, int envs, int threads, const std::optional<std::vector<int>> &seeds,
+                         const std::optional<std::vector<std::vector<std::string>>> &routes) {
+                 return std::unique_ptr<VectorEngineHost>(new VectorEngineHost(
+                     cfg, envs, threads, "", envSeeds(envs, seeds), routes ? *routes : std::vector<std::vector<std::string>>{}));
              }),
-             "config_file"_a, "num_envs"_a, "thread_num"_a = 1, "seeds"_a = py::none(),
+             "config_file"_a, "num_envs"_a, "thread_num"_a = 1, "seeds"_a = py::none(), "routes"_a = py::none(),
              "seeds: num_envs ints, one per environment, instead of seed + env index (also on reset(seed=True)); equal seeds give "
-             "every environment the same demand")
+             "every environment the same demand.  routes: lists of road ids, the candidate routes of set_vehicle_routes_tensor, as "
+             "Engine.add_routes takes them; added_routes() has their handles.  There is no add_routes on a VectorEngine: every "
+             "environment holds its own copy of the route tables, uploaded once, here")
         .def_static(
             "_with_backend",
-            [](const std::string &cfg, int envs, int threads, const std::string &lib, const std::optional<std::vector<int>> &seeds) {
-                return std::unique_ptr<VectorEngineHost>(new VectorEngineHost(cfg, envs, threads, lib, envSeeds(envs, seeds)));
+            [](const std::string &cfg, int envs, int threads, const std::string &lib, const std::optional<std::vector<int>> &seeds,
+               const std::optional<std::vector<std::vector<std::string>>> &routes) {
+                return std::unique_ptr<VectorEngineHost>(new VectorEngineHost(
+                    cfg, envs, threads, lib, envSeeds(envs, seeds), routes ? *routes : std::vector<std::vector<std::string>>{}));
             },
-            "config_file"_a, "num_envs"_a, "thread_num"_a, "backend_library"_a, "seeds"_a = py::none())
+            "config_file"_a, "num_envs"_a, "thread_num"_a, "backend_library"_a, "seeds"_a = py::none(), "routes"_a = py::none())
+        .def("added_routes", &VectorEngineHost::addedRoutes,
+             "the handles of the constructor's `routes`, in the order given (equal in every environment)")
         .def_property_readonly("num_envs", &VectorEngineHost::numEnvs)
         .def("_host_seconds", &VectorEngineHost::hostSeconds,
              "[spawners, record translation, cfx_step] cumulative host wall seconds since the last reset")

@@ -118,7 +118,7 @@ struct ReplicatedNet {
 }  // namespace
 
 VectorEngineHost::VectorEngineHost(const std::string &configFile, int numEnvs, int threadNum, const std::string &backendLib,
-                                   const std::vector<int> &seeds)
+                                   const std::vector<int> &seeds, const std::vector<std::vector<std::string>> &routes)
     : R_(numEnvs) {
     if (numEnvs < 1) throw std::runtime_error("VectorEngine: num_envs must be >= 1");
     if (!seeds.empty() && seeds.size() != (size_t) numEnvs)
@@ -140,6 +140,17 @@ VectorEngineHost::VectorEngineHost(const std::string &configFile, int numEnvs, i
         }
     } catch (const std::exception &e) {
         throw std::runtime_error(std::string("load config failed! ") + e.what());
+    }
+    if (!routes.empty()) {  // (every environment interns the same lists in the same order: the handles are equal)
+        std::vector<std::vector<int>> anchors(routes.size());
+        for (size_t i = 0; i < routes.size(); ++i)
+            for (const std::string &id : routes[i]) {
+                const auto it = net_->roadIndex.find(id);
+                if (it == net_->roadIndex.end())
+                    throw std::invalid_argument("VectorEngine: routes[" + std::to_string(i) + "]: no such road '" + id + "'");
+                anchors[i].push_back(it->second);
+            }
+        for (int r = 0; r < R_; ++r) addedRoutes_ = spawners_[(size_t) r]->addRoutes(anchors);
     }
     L_ = (int) net_->lanes.size();
     K_ = (int) net_->laneLinks.size();
@@ -597,6 +608,7 @@ std::shared_ptr<DeviceCheckpoint> VectorEngineHost::checkpoint(std::shared_ptr<D
     for (int r = 0; r < R_; ++r) ck->host[(size_t) r] = spawners_[(size_t) r]->saveState();
     ck->localToGlobal = localToGlobal_;
     ck->globalToLocal = globalToLocal_;
+    ck->routesStale = routesStale_;
     ck->step = step_;
     return ck;
 }
@@ -673,10 +685,12 @@ void VectorEngineHost::rollbackTo(DeviceCheckpoint &ck, const std::vector<int32_
         }
     }
     step_ = ck.step;
+    routesStale_ = ck.routesStale;  // (the spawners' records are the checkpoint's again)
     {
         std::lock_guard<std::mutex> guard(queryMutex_);
         trackers_.rebaseline((int64_t) step_, [this] {  // (host tracker: the vehicles of the checkpoint, by their global numbers)
             if (!trackers_.trip.onHost()) return;
+            refreshRoutes();
             for (size_t g = 0; g < globalToLocal_.size(); ++g) {
                 const auto &el = globalToLocal_[g];
                 const auto &veh = spawners_[(size_t) el.first]->vehicles[(size_t) el.second];
@@ -861,6 +875,60 @@ int VectorEngineHost::setVehicleSpeeds(const int32_t *vehicle, const double *spe
     return ignored;
 }
 
+static const char *kVecRoutesNoLaneChange = "set_vehicle_routes: not with laneChange (the vehicle numbers are observe_vehicles')";
+
+std::vector<std::string> VectorEngineHost::routeRoads(int handle) {
+    const RouteTable &rt = spawners_[0]->routes;
+    if (handle < 0 || handle >= routesPerEnv_) throw std::out_of_range("route_roads: no such route handle " + std::to_string(handle));
+    std::vector<std::string> ids;
+    for (int p = rt.routeStart[(size_t) handle]; p < rt.routeStart[(size_t) handle + 1]; ++p) ids.push_back(net_->roads[(size_t) rt.roads[(size_t) p]].id);
+    return ids;
+}
+
+void VectorEngineHost::setVehicleRoutesDevice(uintptr_t vehicle, uintptr_t route, int n, uintptr_t status, uintptr_t ignored,
+                                              uintptr_t producerStream) {
+    if (laneChange_) throw std::runtime_error(kVecRoutesNoLaneChange);
+    std::lock_guard<std::mutex> guard(queryMutex_);
+    setVehicleRoutesDeviceOf(be_, dev_, vehicle, route, n, status, ignored, producerStream);
+    routesStale_ = true;
+}
+
+int VectorEngineHost::setVehicleRoutes(const int32_t *vehicle, const int32_t *route, int n, int32_t *status) {
+    if (laneChange_) throw std::runtime_error(kVecRoutesNoLaneChange);
+    std::lock_guard<std::mutex> guard(queryMutex_);
+    const int ignored = setVehicleRoutesOf(be_, dev_, vehicle, route, n, status);
+    routesStale_ = true;
+    raiseDeviceError();
+    return ignored;
+}
+
+void VectorEngineHost::vehicleRoutesDevice(uintptr_t vehicle, int n, uintptr_t out, uintptr_t consumerStream) {
+    if (laneChange_) throw std::runtime_error(kVecRoutesNoLaneChange);
+    std::lock_guard<std::mutex> guard(queryMutex_);
+    vehicleRoutesDeviceOf(be_, dev_, vehicle, n, out, consumerStream);
+}
+
+void VectorEngineHost::vehicleRoutes(const int32_t *vehicle, int n, int32_t *out) {
+    if (laneChange_) throw std::runtime_error(kVecRoutesNoLaneChange);
+    std::lock_guard<std::mutex> guard(queryMutex_);
+    vehicleRoutesOf(be_, dev_, vehicle, n, out);
+    raiseDeviceError();
+}
+
+// the spawners' records of the vehicles' routes after device-side route changes: one read, by the global numbers
+void VectorEngineHost::refreshRoutes() {
+    if (!routesStale_) return;
+    const int n = (int) globalToLocal_.size();
+    std::vector<int32_t> held((size_t) n);
+    if (n) vehicleRoutesOf(be_, dev_, nullptr, n, held.data());
+    for (int g = 0; g < n; ++g) {
+        const auto &el = globalToLocal_[(size_t) g];
+        if (held[(size_t) g] >= 0 && (size_t) el.second < spawners_[(size_t) el.first]->vehicles.size())
+            spawners_[(size_t) el.first]->setVehicleRoute(el.second, held[(size_t) g]);
+    }
+    routesStale_ = false;
+}
+
 void VectorEngineHost::trackLaneFlow(bool on) {
     if (on && laneChange_) throw std::logic_error("track_lane_flow: not with laneChange (a shadow changes identity when its change finishes)");
     std::lock_guard<std::mutex> guard(queryMutex_);
@@ -893,6 +961,7 @@ void VectorEngineHost::trackTrips(bool on) {
     if (!on || trackers_.trip.onDevice()) return;
     cfx_scalars sc{};
     check(be_.cfx_get_scalars(dev_, &sc), "cfx_get_scalars");
+    refreshRoutes();
     for (int64_t v = 0; v < sc.spawned_vehicle_count && (size_t) v < globalToLocal_.size(); ++v) {
         const auto gl = globalToLocal_[(size_t) v];
         const auto &veh = spawners_[(size_t) gl.first]->vehicles[(size_t) gl.second];

@@ -24,8 +24,11 @@ class VectorEngineHost {
 public:
     // seeds: empty = env r is seeded seed + r; otherwise numEnvs seeds, one per environment (std::invalid_argument for another
     // length) — equal ones give every environment the same demand (common random numbers)
+    // routes: candidate routes for set_vehicle_routes (EngineHost::addRoutes), added to every environment's spawner BEFORE the
+    // one upload of the route tables — there is no adding later: every environment has its own shifted copy of the tables,
+    // and routesPerEnv_ never changes.  std::invalid_argument as EngineHost::addRoutes
     VectorEngineHost(const std::string &configFile, int numEnvs, int threadNum, const std::string &backendLib = "",
-                     const std::vector<int> &seeds = {});
+                     const std::vector<int> &seeds = {}, const std::vector<std::vector<std::string>> &routes = {});
     ~VectorEngineHost();
     VectorEngineHost(const VectorEngineHost &) = delete;
     VectorEngineHost &operator=(const VectorEngineHost &) = delete;
@@ -92,6 +95,15 @@ public:
     bool vehicleSpeedsDevice() const { return be_.hasDeviceBuffers() && be_.cfx_set_vehicle_speeds_device; }
     void setVehicleSpeedsDevice(uintptr_t vehicle, uintptr_t speed, int n, uintptr_t ignored, uintptr_t producerStream);
     int setVehicleSpeeds(const int32_t *vehicle, const double *speed, int n);
+    // route changes by those vehicle numbers, vehicles of any environment in one call (EngineHost::setVehicleRoutes and its
+    // kin).  A handle is an index into ONE environment's route tables (they are equal), never read across environments
+    const std::vector<int> &addedRoutes() const { return addedRoutes_; }  // the handles of the constructor's `routes`, in order
+    std::vector<std::string> routeRoads(int handle);
+    int routeCount() const { return routesPerEnv_; }
+    void setVehicleRoutesDevice(uintptr_t vehicle, uintptr_t route, int n, uintptr_t status, uintptr_t ignored, uintptr_t producerStream);
+    int setVehicleRoutes(const int32_t *vehicle, const int32_t *route, int n, int32_t *status);
+    void vehicleRoutesDevice(uintptr_t vehicle, int n, uintptr_t out, uintptr_t consumerStream);
+    void vehicleRoutes(const int32_t *vehicle, int n, int32_t *out);
     // per-intersection observations over every environment (EngineHost::intersectionFeatures and its kin): outputs [R * I ...];
     // the layout is one environment's
     const InterLayout &intersectionLayout();
@@ -161,6 +173,11 @@ private:
     Backend be_;
     cfx_engine *dev_ = nullptr;
     int R_ = 1, L_ = 0, K_ = 0, I_ = 0, routesPerEnv_ = 0;
+    std::vector<int> addedRoutes_;
+    // a device-side route change since the spawners' vehicles[...].route were last read back; their one reader here, the host
+    // trip tracker's tripNote, calls refreshRoutes() first (queryMutex_ held)
+    bool routesStale_ = false;
+    void refreshRoutes();
     int hostThreads_ = -1;  // config "cfx": {"hostThreads": n}: -1 auto, 0 serial
     int autoBatches_ = 0;          // auto: serial batches timed so far (forEachEnv)
     double autoSerialUs_ = 0.0;    //       their total time

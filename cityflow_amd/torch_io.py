@@ -21,6 +21,14 @@
                                                          observe_vehicles_tensor) and float64 [N] speeds, NaN = leave alone;
                                                          two or three kernel launches, no host wait (see its docstring)
     eng.set_vehicle_speeds(vehicle, speed) -> int        the same from numpy arrays; returns the rows ignored (waits for the device)
+    eng.set_vehicle_routes_tensor(vehicle, route, status=None, ignored=None)
+                                                         set_vehicle_route() for the rows of int32 [N] vehicle numbers and int32
+                                                         [N] handles of registered routes (Engine.add_routes, VectorEngine(routes=)),
+                                                         -1 = leave alone; a verdict per row in `status`; no host wait
+    eng.set_vehicle_routes(vehicle, route) -> (status, ignored)
+                                                         the same from numpy arrays (waits for the device)
+    eng.get_vehicle_routes_tensor(vehicle, out=None)     the handle each of those vehicles holds, -1 where there is none
+    eng.get_vehicle_routes(vehicle) -> ndarray           the same from a numpy array (waits for the device)
     eng.observe_intersections_tensor(phase=None, phase_remain=None, movement_in=None, movement_in_waiting=None,
                                      movement_out=None, movement_inside=None, phase_pressure=None)
                                                          per-intersection observations, one kernel launch (see its docstring)
@@ -1289,8 +1297,132 @@ def set_vehicle_speeds_tensor(self, vehicle, speed, ignored=None):
     self._set_vehicle_speeds_device(ptr(vehicle), ptr(speed), n_rows, ptr(ignored), torch.cuda.current_stream(device).cuda_stream)
 
 
+def _check_rows_array(np, a, name):
+    if not isinstance(a, np.ndarray):
+        raise TypeError("%s must be a numpy array, not %s" % (name, type(a).__name__))
+    if a.dtype != np.int32:
+        raise TypeError("%s must be int32, not %s" % (name, a.dtype))
+    if a.ndim != 1:
+        raise ValueError("%s must have shape [N], not %s" % (name, a.shape))
+    if not a.flags.c_contiguous:
+        raise ValueError("%s must be contiguous" % name)
+    if a.shape[0] >= 2 ** 31:
+        raise ValueError("a call holds fewer than 2**31 rows, not %d" % a.shape[0])
+
+
+def set_vehicle_routes(self, vehicle, route):
+    """The numpy form of set_vehicle_routes_tensor: `vehicle` int32 [N] vehicle numbers (observe_vehicles_array()'s), `route`
+    int32 [N] route handles; returns (status int32 [N], the number of rows with a negative status).  Needs no torch; waits for
+    the device.  RuntimeError with laneChange, and on a backend without the device call."""
+    import numpy as np
+
+    _check_rows_array(np, vehicle, "vehicle")
+    _check_rows_array(np, route, "route")
+    if vehicle.shape != route.shape:
+        raise ValueError("route must have shape %s as vehicle, not %s" % (vehicle.shape, route.shape))
+    if self._lane_change():
+        raise RuntimeError("set_vehicle_routes: not with laneChange (the vehicle numbers are observe_vehicles')")
+    status, ignored = self._set_vehicle_routes(vehicle, route)
+    return status, int(ignored)
+
+
+def set_vehicle_routes_tensor(self, vehicle, route, status=None, ignored=None):
+    """set_vehicle_route() for many vehicles at once, from tensors: row i gives the vehicle with the engine's number vehicle[i]
+    — the numbers observe_vehicles_tensor() writes — the registered route with the handle route[i]: Engine.add_routes() /
+    VectorEngine(routes=...) and added_routes(), or any index below route_count().  The vehicle keeps driving where it is;
+    its route's cursor stands on the first occurrence of its road in the new route, so get_vehicle_info(...)["route"] lists
+    the remaining roads, as after the reference's setRoute.
+
+        vehicle   int32 [N]   N >= 0
+        route     int32 [N]   -1: leave this vehicle alone
+        status    int32 [N]   optional output, one verdict per row
+        ignored   int32 [1]   optional output (0-dim is taken too): the rows with a negative status
+
+    status[i] is decided by the first of these that applies:
+
+         0   skipped: vehicle[i] == -1 (observe_vehicles_tensor's padding) or route[i] == -1
+        -1   no such running vehicle: a number not issued, a finished vehicle, or one still in its lane's entry buffer
+        -2   no such route handle
+        -3   superseded: a later row that passes the checks above names the same vehicle
+        -4   the vehicle is inside an intersection (on a laneLink)
+        -5   the vehicle's road does not occur on the route before the route's last road
+        -6   the vehicle's lane has no laneLink towards the route's next road: it is in the wrong turning lane
+         1   applied
+
+    Of several rows for one vehicle only the LAST one that passes -1 and -2 counts, whatever its verdict — this is not "the
+    last valid row wins": if that row is refused the vehicle keeps its old route.  The result never depends on the device's
+    scheduling.  On a VectorEngine a handle is one environment's own index; the vehicle's environment decides which copy of
+    the route it gets, and one call commands vehicles of any environment.  The trip log names a re-routed vehicle's
+    destination by the new route's last road and its origin by the new route's FIRST road.
+
+    Two kernel launches on the engine's stream (three on the dense layout), ordered after the current torch stream; the torch
+    stream is ordered after them, so `status` and `ignored` can be read there and the inputs reused.  The call never waits for
+    the device.  Every argument is checked before anything is enqueued.  RuntimeError with laneChange: true, and on a backend
+    without the device call (the CPU twin): set_vehicle_route(), which restarts a route at its first road, cannot stand in."""
+    torch = _torch()
+    device = _engine_device(torch, self)
+    if not isinstance(vehicle, torch.Tensor):
+        raise TypeError("vehicle must be a torch.Tensor, not %s" % type(vehicle).__name__)
+    if vehicle.dim() != 1:
+        raise ValueError("vehicle must have shape [N], not %s" % (tuple(vehicle.shape),))
+    n_rows = int(vehicle.shape[0])
+    _check_buf(torch, vehicle, "vehicle", (n_rows,), torch.int32, device)
+    _check_buf(torch, route, "route", (n_rows,), torch.int32, device)
+    if status is not None:
+        _check_buf(torch, status, "status", (n_rows,), torch.int32, device)
+    if ignored is not None:
+        _check_buf(torch, ignored, "ignored", () if isinstance(ignored, torch.Tensor) and ignored.dim() == 0 else (1,), torch.int32, device)
+    if n_rows >= 2 ** 31:
+        raise ValueError("a call holds fewer than 2**31 rows, not %d" % n_rows)
+    if self._lane_change():
+        raise RuntimeError("set_vehicle_routes_tensor: not with laneChange (the vehicle numbers are observe_vehicles')")
+    ptr = lambda t: 0 if t is None or t.numel() == 0 else t.data_ptr()  # noqa: E731
+    stream = torch.cuda.current_stream(device).cuda_stream if device.type == "cuda" else 0
+    self._set_vehicle_routes_device(ptr(vehicle), ptr(route), n_rows, ptr(status), ptr(ignored), stream)
+
+
+def get_vehicle_routes(self, vehicle):
+    """The numpy form of get_vehicle_routes_tensor: `vehicle` int32 [N]; returns int32 [N].  Waits for the device."""
+    import numpy as np
+
+    _check_rows_array(np, vehicle, "vehicle")
+    if self._lane_change():
+        raise RuntimeError("get_vehicle_routes: not with laneChange (the vehicle numbers are observe_vehicles')")
+    return self._vehicle_routes(vehicle)
+
+
+def get_vehicle_routes_tensor(self, vehicle, out=None):
+    """The route handle each vehicle holds: out[i] is the handle of the vehicle with the number vehicle[i] (waiting vehicles
+    included; on a VectorEngine the index within its environment), or -1 where vehicle[i] is -1, not a number issued, or a
+    finished vehicle.  `vehicle` int32 [N], `out` int32 [N] (allocated when None); returns `out`.  One kernel launch in the
+    current torch stream's order, no host wait.  RuntimeError as set_vehicle_routes_tensor."""
+    torch = _torch()
+    device = _engine_device(torch, self)
+    if not isinstance(vehicle, torch.Tensor):
+        raise TypeError("vehicle must be a torch.Tensor, not %s" % type(vehicle).__name__)
+    if vehicle.dim() != 1:
+        raise ValueError("vehicle must have shape [N], not %s" % (tuple(vehicle.shape),))
+    n_rows = int(vehicle.shape[0])
+    _check_buf(torch, vehicle, "vehicle", (n_rows,), torch.int32, device)
+    if out is not None:
+        _check_buf(torch, out, "out", (n_rows,), torch.int32, device)
+    if n_rows >= 2 ** 31:
+        raise ValueError("a call holds fewer than 2**31 rows, not %d" % n_rows)
+    if self._lane_change():
+        raise RuntimeError("get_vehicle_routes_tensor: not with laneChange (the vehicle numbers are observe_vehicles')")
+    if out is None:
+        out = torch.empty((n_rows,), dtype=torch.int32, device=device)
+    stream = torch.cuda.current_stream(device).cuda_stream if device.type == "cuda" else 0
+    self._vehicle_routes_device(vehicle.data_ptr() if n_rows else 0, n_rows, out.data_ptr() if n_rows else 0, stream)
+    return out
+
+
 def install(*classes):
     for cls in classes:
+        cls.set_vehicle_routes_tensor = set_vehicle_routes_tensor
+        cls.set_vehicle_routes = set_vehicle_routes
+        cls.get_vehicle_routes_tensor = get_vehicle_routes_tensor
+        cls.get_vehicle_routes = get_vehicle_routes
         cls.set_vehicle_speeds_tensor = set_vehicle_speeds_tensor
         cls.set_vehicle_speeds = set_vehicle_speeds
         cls.observe_vehicles_tensor = observe_vehicles_tensor

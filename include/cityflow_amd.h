@@ -628,6 +628,42 @@ typedef int32_t (*cfx_set_vehicle_speeds_device_fn)(cfx_engine *e, const int32_t
                                                     int32_t *ignored, void *producer_stream);
 typedef int32_t (*cfx_set_vehicle_speeds_fn)(cfx_engine *e, const int32_t *vehicle, const double *speed, int32_t n, int32_t *ignored);
 
+/* ---- Route changes for many vehicles at once, and the routes the vehicles hold (OPTIONAL entry points, as above; all four or
+ * none): Router::setRoute for n rows {vehicle[i], route[i]}, n >= 0.  The vehicle numbers are cfx_observe_vehicles_device's.
+ * route[i] is a HANDLE: an index into the route tables of cfx_add_routes as ONE environment has them, [0, routes / n_envs).
+ * With cfx_config::n_envs > 1 the vehicle's environment is that of its lane, and the route it gets is environment *
+ * (routes / n_envs) + handle: a handle is never read across environments.  status[i] (int32[n], may be NULL) is decided by
+ * the first of these that applies:
+ *    0   skipped: vehicle[i] == -1 (that call's padding) or route[i] == -1 (leave alone)
+ *   -1   no such running vehicle: a number outside [0, issued), a finished vehicle, or one still in its lane's entry buffer
+ *   -2   no such handle
+ *   -3   superseded: a later row passes the three checks above and names the same vehicle
+ *   -4   the vehicle is inside an intersection, on a laneLink (Router::setRoute, router.cpp:246)
+ *   -5   the vehicle's road does not occur on the route before the route's last road (a remaining route of one road is
+ *        refused, router.cpp:239)
+ *   -6   the vehicle's lane has no laneLink towards the route's next road (Router::onValidLane, router.h:66-68)
+ *    1   applied: the vehicle holds the route with its cursor on the FIRST position p of its road, its next drivable and its
+ *        last-road flag are those of (route, p); cfx_get_vehicle then answers route and route_pos = p
+ * Of the rows for one vehicle that pass -1 and -2 only the LAST counts, whatever its verdict: this is not "the last valid
+ * row wins" (a vehicle whose last row is refused keeps its old route, its earlier rows read -3).  ignored (int32[1], may be
+ * NULL) receives the number of rows with a negative status.  Nothing outside [0, n) of status is written.  Calls take effect
+ * in the order they are made, cfx_set_vehicle_route among them.
+ * _device: every pointer is device memory; two kernels over the rows on the engine's stream (ring layout), or two over the
+ * rows and one pass over the slots (dense layout), ordered against producer_stream as cfx_set_tl_phases_device; the call
+ * never waits for the device (it uploads routes added since, and allocates 4 bytes per vehicle number when the numbers have
+ * outgrown its scratch).  The host form reads and fills host arrays through the engine's staging and waits.
+ * cfx_get_vehicle_routes[_device] writes route_out[i] = the handle vehicle[i] holds (waiting vehicles included), or -1 for
+ * vehicle[i] == -1, a number that was not issued and a finished vehicle; one kernel.  The host form takes vehicle == NULL
+ * for the numbers 0 .. n-1.
+ * CFX_ERR_STATE with lane change (the numbers are cfx_observe_vehicles_device's) and on a tile. */
+typedef int32_t (*cfx_set_vehicle_routes_device_fn)(cfx_engine *e, const int32_t *vehicle, const int32_t *route, int32_t n,
+                                                    int32_t *status, int32_t *ignored, void *producer_stream);
+typedef int32_t (*cfx_set_vehicle_routes_fn)(cfx_engine *e, const int32_t *vehicle, const int32_t *route, int32_t n, int32_t *status,
+                                             int32_t *ignored);
+typedef int32_t (*cfx_get_vehicle_routes_device_fn)(cfx_engine *e, const int32_t *vehicle, int32_t n, int32_t *route_out,
+                                                    void *consumer_stream);
+typedef int32_t (*cfx_get_vehicle_routes_fn)(cfx_engine *e, const int32_t *vehicle, int32_t n, int32_t *route_out);
+
 /* ---- Per-intersection movement and phase observations (OPTIONAL entry points, as above).  Intersection i (n_inters of them,
  * virtual ones included) has its roadLinks m < M_i = inter_n_roadlinks[i] ("movements", ll_roadlink) and its phases p < P_i
  * (inter_phase_start; 0 for a virtual intersection).  IN(i, m) / OUT(i, m) are the DISTINCT start / end lanes of the roadLink's

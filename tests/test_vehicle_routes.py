@@ -1,0 +1,631 @@
+"""add_routes / route_roads / route_count, set_vehicle_routes_tensor / set_vehicle_routes and get_vehicle_routes_tensor /
+get_vehicle_routes on Engine and VectorEngine (cityflow_amd/torch_io.py; cfx_set_vehicle_routes_device: k_routes_claim +
+kr_routes_apply on the ring layout, k_routes_claim + k_routes_superseded + k_routes_apply_dense on the dense layout).
+
+The yardstick is the CPU twin driven in lockstep with the per-vehicle set_vehicle_route(id, anchors): for a vehicle on road r and
+a registered route g the anchors are the roads of g behind the first occurrence of r, one anchor per road — consecutive adjacent
+roads make the reference's shortest path return exactly that path, which the tests verify on the twin's get_vehicle_info.  The
+expected status of every row comes from a pure-Python model (`model_status`) of the status table that reads the twin's state:
+the drivable from get_vehicle_info, the route's roads from route_roads, the lane-to-road connectivity from the roadnet JSON.
+Wherever the model says 1 the twin's set_vehicle_route must return True, wherever it says -4, -6, or -5 on the route's last road it
+must return False (`command_twin` asserts that), so the model itself is checked against the reference's rules.
+
+Nothing is approximate: statuses, counts and vehicle states are compared with array_equal.  `route_pos` is left out of the state
+comparison after a command: the twin's set_vehicle_route holds the remaining roads as a route of its own with the cursor at 0,
+the device holds the registered route with the cursor at the vehicle's road."""
+import json
+import os
+
+import numpy as np
+import pytest
+
+from conftest import SHADOW_GPU, TWIN_LIB
+
+torch = pytest.importorskip("torch")
+
+from test_device_tensors import tensor_device, twin  # noqa: E402
+from test_lane_flow import hip_engine, layout_config  # noqa: E402
+from test_vehicle_speeds import dev, issued, same_state  # noqa: E402
+
+AFTER = ("route_pos",)  # not compared once a route was commanded (module docstring)
+
+
+# ----------------------------------------------------------------------------------------------------------------- helpers
+def lane_links_of(cfg):
+    """{(road id, lane index): [(end road id, end lane index)]} from the roadnet JSON of a config file."""
+    with open(cfg) as f:
+        c = json.load(f)
+    with open(os.path.join(c["dir"], c["roadnetFile"])) as f:
+        net = json.load(f)
+    links = {}
+    for inter in net["intersections"]:
+        for rl in inter.get("roadLinks", []):
+            for ll in rl["laneLinks"]:
+                links.setdefault((rl["startRoad"], ll["startLaneIndex"]), []).append((rl["endRoad"], ll["endLaneIndex"]))
+    return links
+
+
+def has_next(links, road, index, g, p):
+    """Router::getNextDrivable for a lane of g[p] = road: a laneLink towards g[p+1] whose end lane leads on to g[p+2]."""
+    cands = [c for c in links.get((road, index), []) if c[0] == g[p + 1]]
+    if p + 2 < len(g):
+        cands = [c for c in cands if any(e[0] == g[p + 2] for e in links.get(c, []))]
+    return bool(cands)
+
+
+def model_status(a, tw, links, vehicle, route):
+    """-> status [N], and for every row that is its vehicle's command {row: (vehicle id, road or None, g, p or None)}."""
+    running = set(tw._vehicle_state()["vid"].tolist())
+    n_routes = a.route_count()
+    status = np.zeros(len(vehicle), dtype=np.int32)
+    last, rows = {}, {}
+    for i, (v, h) in enumerate(zip(vehicle.tolist(), route.tolist())):
+        if v == -1 or h == -1:
+            status[i] = 0
+        elif v not in running:
+            status[i] = -1
+        elif not 0 <= h < n_routes:
+            status[i] = -2
+        else:
+            status[i] = -3
+            last[v] = i
+    for v, i in last.items():
+        vid = tw._vehicle_id(v)
+        info = tw.get_vehicle_info(vid)
+        g = a.route_roads(int(route[i]))
+        if "road" not in info:
+            status[i], rows[i] = -4, (vid, None, g, None)
+            continue
+        road, index = info["road"], int(info["drivable"].rsplit("_", 1)[1])
+        if road not in g[:-1]:
+            status[i], rows[i] = -5, (vid, road, g, None)
+            continue
+        p = g.index(road)
+        status[i] = 1 if has_next(links, road, index, g, p) else -6
+        rows[i] = (vid, road, g, p)
+    return status, rows
+
+
+def command_twin(tw, status, rows):
+    """The equivalent set_vehicle_route calls on the twin; the model's verdicts against the reference's.  -> ids re-routed"""
+    applied = []
+    for i in sorted(rows):
+        vid, road, g, p = rows[i]
+        s = int(status[i])
+        if s == -5 and road != g[-1]:
+            continue  # (not attempted: there are no anchors to give)
+        anchors = g[1:] if s == -4 else ([] if s == -5 else g[p + 1:])
+        ok = tw.set_vehicle_route(vid, anchors)
+        assert ok == (s == 1), "row %d: the model says %d, the twin's set_vehicle_route %s" % (i, s, ok)
+        if ok:
+            assert tw.get_vehicle_info(vid)["route"].split() == [road] + anchors, "row %d: the shortest path is not the route" % i
+            applied.append(vid)
+    return applied
+
+
+def call(a, vehicle, route, form="tensor"):
+    """The batched call on A -> status [N], ignored."""
+    vehicle, route = np.ascontiguousarray(vehicle, dtype=np.int32), np.ascontiguousarray(route, dtype=np.int32)
+    if form == "array":
+        return a.set_vehicle_routes(vehicle, route)
+    device = tensor_device(a)
+    status = torch.full((len(vehicle) + 2,), -7, dtype=torch.int32, device=device)  # (two elements beyond [0, n): never written)
+    ignored = torch.full((1,), -7, dtype=torch.int32, device=device)
+    a.set_vehicle_routes_tensor(dev(a, vehicle), dev(a, route), status[:len(vehicle)], ignored)
+    got = status.cpu().numpy()
+    assert got[-2:].tolist() == [-7, -7], "written beyond [0, n) of status"
+    return got[:-2], int(ignored.item())
+
+
+def check_call(a, tw, links, vehicle, route, where, form="tensor", need=()):
+    vehicle, route = np.asarray(vehicle, dtype=np.int32), np.asarray(route, dtype=np.int32)
+    want, rows = model_status(a, tw, links, vehicle, route)
+    missing = set(need) - set(want.tolist())
+    assert not missing, "%s: the rows never get the verdicts %s" % (where, sorted(missing))
+    got, ignored = call(a, vehicle, route, form)
+    assert np.array_equal(got, want), "%s: status\n got  %s\n want %s" % (where, got.tolist(), want.tolist())
+    assert ignored == int((want < 0).sum()), "%s: ignored %d, negative rows %d" % (where, ignored, int((want < 0).sum()))
+    return want, rows, command_twin(tw, want, rows)
+
+
+def lockstep(a, tw, steps, where, ids=(), skip=AFTER):
+    # (between a route change and the next step a lane's first vehicle shows the leader of its OLD next drivable on one engine
+    #  and of the new one on the other, after set_vehicle_route() too: `leader` and `gap` are compared from the next step on)
+    same_state(a, tw, where + " before a step", tuple(skip) + ("leader", "gap"))
+    for s in range(1, steps + 1):
+        a.next_step()
+        tw.next_step()
+        same_state(a, tw, "%s step +%d" % (where, s), skip)
+        if s in (1, steps // 2, steps):
+            alive = set(tw.get_vehicles(False))
+            for vid in ids:
+                if vid in alive:
+                    assert a.get_vehicle_info(vid) == tw.get_vehicle_info(vid), "%s step +%d: %s" % (where, s, vid)
+    assert a.get_vehicle_speed() == tw.get_vehicle_speed() and a.get_vehicle_distance() == tw.get_vehicle_distance(), where
+
+
+def pair_routes(eng):
+    """Every (in-road, out-road) pair of example_1x1 as a two-road route, where the reference calls it one.  -> handles"""
+    roads = eng.road_ids()
+    ins, outs = [r for r in roads if not r.startswith("road_1_1_")], [r for r in roads if r.startswith("road_1_1_")]
+    handles = []
+    for i in ins:
+        for o in outs:
+            try:
+                handles += eng.add_routes([[i, o]])
+            except ValueError:
+                pass  # (no roadLink: the U-turn)
+    return handles
+
+
+def grid_routes(eng, links):
+    """Candidates on grid_6x6, whose flows all drive straight on: around the second and the third road of every flow route g (few vehicles are further by then),
+    [g[k-1], g[k], g[k+1]] (a vehicle on g[k] takes it at p = 1) and [g[k-1], g[k], a road a turn away].  -> handles"""
+    lists = []
+    for h in range(eng.route_count()):
+        g = eng.route_roads(h)
+        for k in (1, 2):
+            lists.append(g[k - 1:k + 2])
+            turns = sorted({end for (road, _), ends in links.items() if road == g[k] for end, _ in ends} - {g[k + 1]})
+            lists.append([g[k - 1], g[k], turns[h % len(turns)]])
+    return eng.add_routes(lists)
+
+
+def not_on_the_twin():
+    """CFX_SHADOW_GPU runs the gpu tests' bodies with the twin standing in for the device; it has no batched route calls."""
+    if SHADOW_GPU:
+        pytest.skip("about the device's route kernels: the twin that stands in under CFX_SHADOW_GPU has no such calls")
+
+
+def started(mod, make_a, cfg, steps, register=pair_routes):
+    not_on_the_twin()
+    a, tw = make_a(cfg), twin(mod, cfg)
+    handles = register(a) if register else []
+    assert (register(tw) if register else []) == handles
+    for _ in range(steps):
+        a.next_step()
+        tw.next_step()
+    return a, tw, handles
+
+
+def observed(a, n):
+    """[n] vehicle numbers as observe_vehicles_tensor gives them, its -1 padding left in."""
+    out = torch.full((n,), -7, dtype=torch.int32, device=tensor_device(a))
+    a.observe_vehicles_tensor(vehicle=out)
+    return out.cpu().numpy()
+
+
+def finished_number(tw):
+    alive = set(tw._vehicle_state()["vid"].tolist()) | set(tw._waiting()[0].tolist())
+    gone = [v for v in range(issued(tw)) if v not in alive]
+    assert gone, "no vehicle has finished yet"
+    return gone[0]
+
+
+# --------------------------------------------------------------------------------------------------- CPU: routes and handles
+def test_add_routes_handles_and_dedupe(mod, scen, workdir):
+    eng = twin(mod, scen.materialize("grid_6x6", workdir))
+    n0 = eng.route_count()
+    assert n0 > 0
+    flow_route = eng.route_roads(0)
+    assert len(flow_route) >= 2 and all(r in eng.road_ids() for r in flow_route)
+    got = eng.add_routes([[flow_route[0], flow_route[-1]], flow_route[:2], flow_route[:2], flow_route])
+    assert got[1] == got[2] and got[3] == 0 and eng.route_roads(got[1]) == flow_route[:2]
+    assert got[1] >= n0 or eng.route_roads(got[1]) == flow_route[:2]
+    assert eng.route_count() == n0 + len(set(h for h in got if h >= n0))
+    expanded = eng.route_roads(got[0])  # (anchors joined by the shortest path)
+    assert expanded[0] == flow_route[0] and expanded[-1] == flow_route[-1] and len(expanded) >= 2
+    assert eng.add_routes([]) == []
+    for _ in range(5):
+        eng.next_step()
+    before = [eng.route_roads(h) for h in range(eng.route_count())]
+    eng.reset()
+    assert [eng.route_roads(h) for h in range(eng.route_count())] == before  # (handles hold across reset)
+    assert eng.add_routes([flow_route[:2]]) == [got[1]]
+    for bad in (-1, eng.route_count()):
+        with pytest.raises(IndexError):
+            eng.route_roads(bad)
+
+
+def test_add_routes_refuses_and_adds_nothing(mod, scen, workdir):
+    eng = twin(mod, scen.materialize("example_1x1", workdir))
+    n0 = eng.route_count()
+    good = ["road_0_1_0", "road_1_1_1"]
+    for bad, index in (([good, ["road_0_1_0", "no_such_road"]], 1), ([["road_0_1_0"]], 0), ([good, good, []], 2),
+                       ([["road_1_1_0", "road_0_1_0"]], 0)):  # unknown, one road, empty, unreachable (out-road to in-road)
+        with pytest.raises(ValueError, match=r"routes\[%d\]" % index):
+            eng.add_routes(bad)
+        assert eng.route_count() == n0
+    assert len(pair_routes(eng)) == 12 and eng.route_count() == n0  # (the flows hold all twelve already)
+
+
+def test_vector_engine_routes(mod, scen, workdir):
+    cfg = scen.materialize("grid_6x6", workdir)
+    plain = mod.VectorEngine._with_backend(cfg, 2, 1, TWIN_LIB)
+    g = plain.route_roads(0)
+    assert plain.added_routes() == [] and not hasattr(plain, "add_routes")
+    vec = mod.VectorEngine._with_backend(cfg, 3, 1, TWIN_LIB, routes=[g[:2], g, g[:2]])
+    handles = vec.added_routes()
+    assert handles[1] == 0 and handles[0] == handles[2] == plain.route_count() and vec.route_count() == plain.route_count() + 1
+    assert vec.route_roads(handles[0]) == g[:2]
+    for _ in range(3):
+        vec.next_step()  # (every environment holds the same tables: the step checks it)
+    with pytest.raises(ValueError, match=r"routes\[1\]"):
+        mod.VectorEngine._with_backend(cfg, 2, 1, TWIN_LIB, routes=[g[:2], ["no_such_road"]])
+    with pytest.raises(ValueError, match=r"routes\[0\]"):
+        mod.VectorEngine._with_backend(cfg, 2, 1, TWIN_LIB, routes=[[g[0]]])
+
+
+def test_the_twin_has_no_batched_route_calls(mod, scen, workdir):
+    cfg = scen.materialize("example_1x1", workdir)
+    for eng in (twin(mod, cfg), mod.VectorEngine._with_backend(cfg, 2, 1, TWIN_LIB)):
+        eng.next_step()
+        v, r = np.zeros(1, dtype=np.int32), np.zeros(1, dtype=np.int32)
+        tv, tr = torch.from_numpy(v), torch.from_numpy(r)
+        for f in (lambda: eng.set_vehicle_routes(v, r), lambda: eng.set_vehicle_routes_tensor(tv, tr),
+                  lambda: eng.get_vehicle_routes(v), lambda: eng.get_vehicle_routes_tensor(tv)):
+            with pytest.raises(RuntimeError, match="libcfx_twin"):
+                f()
+
+
+def test_argument_errors(mod, scen, workdir):
+    eng = twin(mod, scen.materialize("example_1x1", workdir))
+    v, r = torch.zeros(4, dtype=torch.int32), torch.zeros(4, dtype=torch.int32)
+    for args, err in (((v.numpy(), r), TypeError), ((v, r.to(torch.int64)), TypeError), ((v, r[:3]), ValueError),
+                      ((v.reshape(2, 2), r), ValueError), ((v, r, torch.zeros(3, dtype=torch.int32)), ValueError),
+                      ((v, r, None, torch.zeros(2, dtype=torch.int32)), ValueError),
+                      ((v, r, torch.zeros(4, dtype=torch.float64)), TypeError), ((v[::2], r[:2]), ValueError)):
+        with pytest.raises(err):
+            eng.set_vehicle_routes_tensor(*args)
+    for args, err in (((v.numpy(), r.numpy()[:3]), ValueError), ((v, r.numpy()), TypeError),
+                      ((v.numpy().astype(np.int64), r.numpy()), TypeError), ((v.numpy().reshape(2, 2), r.numpy()), ValueError)):
+        with pytest.raises(err):
+            eng.set_vehicle_routes(*args)
+    for args, err in (((v.numpy(),), TypeError), ((v.to(torch.int64),), TypeError), ((v, torch.zeros(3, dtype=torch.int32)), ValueError)):
+        with pytest.raises(err):
+            eng.get_vehicle_routes_tensor(*args)
+    with pytest.raises(TypeError):
+        eng.get_vehicle_routes(v)
+
+
+@pytest.mark.parametrize("name,steps", [("example_1x1", 45), ("grid_6x6", 90)])
+def test_model_agrees_with_the_reference_rules(mod, scen, workdir, name, steps):
+    """The model's verdicts against the twin's set_vehicle_route, for the routes and states the GPU tests use."""
+    cfg = scen.materialize(name, workdir)
+    tw = twin(mod, cfg)
+    if name == "example_1x1":
+        pair_routes(tw)
+    else:
+        grid_routes(tw, lane_links_of(cfg))
+    for _ in range(steps):
+        tw.next_step()
+    rng = np.random.default_rng(1)
+    if name == "example_1x1":
+        vehicle = tw._vehicle_state()["vid"].astype(np.int32)
+        route = rng.integers(0, tw.route_count(), len(vehicle)).astype(np.int32)
+    else:
+        vehicle, route = midroute_rows(tw, tw, rng)
+    status, rows = model_status(tw, tw, lane_links_of(cfg), vehicle, route)
+    assert {1, -4, -5, -6} <= set(status.tolist()), sorted(set(status.tolist()))
+    assert command_twin(tw, status, rows)
+
+
+# ------------------------------------------------------------------------------------------------ GPU: example_1x1, every verdict
+def example_rows(a, tw, handles, n, rng):
+    vehicle = observed(a, n)
+    route = rng.choice(np.asarray(handles + [-1], dtype=np.int32), n)
+    if n >= 8:  # rows beyond the running vehicles: a finished vehicle, a number not issued, one below the padding
+        assert (vehicle[-3:] == -1).all()
+        vehicle[-3:] = (finished_number(tw), issued(tw), -2)
+        route[-3:] = handles[0]
+    return vehicle, route
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("layout", ["auto", "dense"])
+@pytest.mark.parametrize("n", [257, 1, 0])
+def test_example_every_verdict(mod, scen, workdir, layout, n):
+    cfg = layout_config(scen, workdir, "example_1x1", layout)
+    a, tw, handles = started(mod, lambda c: hip_engine(mod, c, layout), cfg, 45)
+    vehicle, route = example_rows(a, tw, handles, n, np.random.default_rng(7))
+    need = (1, 0, -1, -4, -5, -6) if n == 257 else ()
+    _, _, ids = check_call(a, tw, lane_links_of(cfg), vehicle, route, "example_1x1 n=%d" % n, need=need)
+    lockstep(a, tw, 30, "example_1x1 n=%d" % n, ids)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("layout", ["auto", "dense"])
+def test_example_array_form(mod, scen, workdir, layout):
+    cfg = layout_config(scen, workdir, "example_1x1", layout)
+    a, tw, handles = started(mod, lambda c: hip_engine(mod, c, layout), cfg, 45)
+    vehicle, route = example_rows(a, tw, handles, 130, np.random.default_rng(8))
+    _, _, ids = check_call(a, tw, lane_links_of(cfg), vehicle, route, "array form", form="array", need=(1, -1))
+    assert np.array_equal(a.get_vehicle_routes(vehicle), a.get_vehicle_routes_tensor(dev(a, vehicle)).cpu().numpy())
+    lockstep(a, tw, 10, "array form", ids)
+
+
+# ---------------------------------------------------------------------------------------- GPU: grid_6x6, commanded mid-route
+def midroute_rows(a, tw, rng):
+    """Every running vehicle, half with a route that holds its road before its last one, half with any route."""
+    routes = [a.route_roads(h) for h in range(a.route_count())]
+    vehicle = tw._vehicle_state()["vid"].astype(np.int32)
+    route = rng.integers(0, len(routes), len(vehicle)).astype(np.int32)
+    for i, v in enumerate(vehicle.tolist()):
+        road = tw.get_vehicle_info(tw._vehicle_id(v)).get("road")
+        fits = [h for h, g in enumerate(routes) if road in g[:-1]]
+        if fits and rng.random() < 0.5:
+            route[i] = fits[int(rng.integers(0, len(fits)))]
+    return vehicle, route
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("layout", ["auto", "dense"])
+def test_grid_commanded_mid_route(mod, scen, workdir, layout):
+    cfg = layout_config(scen, workdir, "grid_6x6", layout)
+    a, tw, _ = started(mod, lambda c: hip_engine(mod, c, layout), cfg, 90, register=lambda e: grid_routes(e, lane_links_of(cfg)))
+    vehicle, route = midroute_rows(a, tw, np.random.default_rng(3))
+    numbers = dev(a, vehicle)
+    old = a.get_vehicle_routes_tensor(numbers).cpu().numpy()
+    assert (old >= 0).all() and (old < a.route_count()).all()
+    want, rows, ids = check_call(a, tw, lane_links_of(cfg), vehicle, route, "grid_6x6", need=(1, -4, -5, -6))
+    moved = [i for i in rows if want[i] == 1 and rows[i][3] > 0 and route[i] != old[i]]
+    assert moved, "no vehicle took another route at a position p > 0"
+    out = torch.full((len(vehicle),), -7, dtype=torch.int32, device=tensor_device(a))
+    assert a.get_vehicle_routes_tensor(numbers, out) is out
+    assert np.array_equal(out.cpu().numpy(), np.where(want == 1, route, old))
+    state = a._vehicle_state()
+    pos = dict(zip(state["vid"].tolist(), state["route_pos"].tolist()))
+    for i in moved:
+        assert pos[int(vehicle[i])] == rows[i][3], "row %d: the cursor is not at the vehicle's road" % i
+    lockstep(a, tw, 30, "grid_6x6", ids)
+
+
+# ---------------------------------------------------------------------------------------------------------- GPU: duplicates
+def verdict_handles(a, tw, links, handles):
+    """Three running vehicles with (a handle the model applies, one it refuses)."""
+    found = []
+    for v in tw._vehicle_state()["vid"].tolist():
+        verdicts = {}
+        for h in handles:
+            s, _ = model_status(a, tw, links, np.array([v], dtype=np.int32), np.array([h], dtype=np.int32))
+            verdicts.setdefault(int(s[0]), h)
+        if 1 in verdicts and (-6 in verdicts or -5 in verdicts):
+            found.append((v, verdicts[1], verdicts.get(-6, verdicts.get(-5))))
+        if len(found) == 3:
+            return found
+    raise AssertionError("fewer than three vehicles with a handle of either kind")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("layout", ["auto", "dense"])
+def test_duplicates_the_last_row_counts(mod, scen, workdir, layout):
+    cfg = layout_config(scen, workdir, "example_1x1", layout)
+    a, tw, handles = started(mod, lambda c: hip_engine(mod, c, layout), cfg, 45)
+    links = lane_links_of(cfg)
+    (x, xg, xb), (y, yg, yb), (z, zg, zb) = verdict_handles(a, tw, links, handles)
+    # x: the last row valid; y: the last row refused (the vehicle keeps its route); z: the last row -1, the one before it wins
+    vehicle = np.array([x, y, z, x, y, z, x, y, z], dtype=np.int32)
+    route = np.array([xb, yg, zb, xg, yg, zg, xg, yb, -1], dtype=np.int32)
+    old = a.get_vehicle_routes(np.array([x, y, z], dtype=np.int32))
+    want, _, ids = check_call(a, tw, links, vehicle, route, "duplicates")
+    assert want[[0, 3, 6]].tolist() == [-3, -3, 1] and want[[1, 4]].tolist() == [-3, -3] and want[7] < -3
+    assert want[[2, 5, 8]].tolist() == [-3, 1, 0]
+    assert a.get_vehicle_routes(np.array([x, y, z], dtype=np.int32)).tolist() == [xg, int(old[1]), zg]
+    lockstep(a, tw, 20, "duplicates", ids)
+
+
+# --------------------------------------------------------------------------------------------- GPU: bad handles and numbers
+@pytest.mark.gpu
+@pytest.mark.parametrize("layout", ["auto", "dense"])
+def test_bad_handles_and_numbers_change_nothing(mod, scen, workdir, layout):
+    cfg = layout_config(scen, workdir, "example_1x1", layout)
+    a, tw, handles = started(mod, lambda c: hip_engine(mod, c, layout), cfg, 45)
+    live = tw._vehicle_state()["vid"].astype(np.int32)
+    before = a.get_vehicle_routes(live)
+    vehicle = np.array([live[0], live[1], issued(tw), finished_number(tw), -5, 2 ** 31 - 1], dtype=np.int32)
+    route = np.array([a.route_count(), -2, handles[0], handles[0], handles[0], handles[0]], dtype=np.int32)
+    want, rows, ids = check_call(a, tw, lane_links_of(cfg), vehicle, route, "bad rows")
+    assert want.tolist() == [-2, -2, -1, -1, -1, -1] and not rows and not ids
+    assert np.array_equal(a.get_vehicle_routes(live), before)
+    lockstep(a, tw, 15, "bad rows", skip=())
+
+
+# ---------------------------------------------------------------------------------------------------- GPU: state transitions
+@pytest.mark.gpu
+@pytest.mark.parametrize("layout", ["auto"])  # (checkpoints in device memory exist on the ring layout only)
+def test_rollback_undoes_a_command(mod, scen, workdir, layout):
+    cfg = layout_config(scen, workdir, "grid_6x6", layout)
+    a, tw, _ = started(mod, lambda c: hip_engine(mod, c, layout), cfg, 90, register=lambda e: grid_routes(e, lane_links_of(cfg)))
+    ck = a.checkpoint()
+    vehicle, route = midroute_rows(a, tw, np.random.default_rng(4))
+    status, ignored = call(a, vehicle, route)
+    assert (status == 1).sum() > 0
+    for _ in range(3):
+        a.next_step()
+    a.rollback(ck)
+    assert np.array_equal(a.get_vehicle_routes(vehicle), ck_routes(tw, a, vehicle))
+    lockstep(a, tw, 20, "after rollback", skip=())
+
+
+def ck_routes(tw, a, vehicle):
+    """The handles the vehicles held before any command: each one's flow route, by the twin's get_vehicle_info."""
+    index = {tuple(a.route_roads(h)): h for h in range(a.route_count())}
+    out = []
+    for v in vehicle.tolist():
+        info = tw.get_vehicle_info(tw._vehicle_id(v))
+        tail = info["route"].split()
+        out.append(next(h for g, h in index.items() if list(g[len(g) - len(tail):]) == tail and h < len(index)))
+    return np.asarray(out, dtype=np.int32)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("layout", ["auto", "dense"])
+@pytest.mark.parametrize("how", ["load", "compaction"])
+def test_commanded_routes_survive(mod, scen, workdir, layout, how):
+    cfx = {"compactVehicles": 150} if how == "compaction" else {}
+    cfg = layout_config(scen, workdir, "grid_6x6", layout, **cfx)
+    a, tw, _ = started(mod, lambda c: hip_engine(mod, c, layout), cfg, 90, register=lambda e: grid_routes(e, lane_links_of(cfg)))
+    vehicle, route = midroute_rows(a, tw, np.random.default_rng(5))
+    want, rows, ids = check_call(a, tw, lane_links_of(cfg), vehicle, route, how, need=(1,))
+    if how == "load":
+        # (a load restarts every vehicle's cursor at its route's first road until the vehicle enters its next lane, so
+        #  get_vehicle_info lists the REGISTERED route from its start meanwhile, the twin the remaining one: not compared)
+        a.load(a.snapshot())
+        ids = ()
+        assert np.array_equal(a.get_vehicle_routes(vehicle)[want == 1], route[want == 1])
+    compactions = a._vehicle_table()[1]
+    lockstep(a, tw, 30, how, ids)
+    if how == "compaction":
+        assert a._vehicle_table()[1] > compactions, "no vehicle compaction happened after the command"
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("layout", ["auto", "dense"])
+def test_add_routes_while_running_then_command(mod, scen, workdir, layout):
+    cfg = layout_config(scen, workdir, "grid_6x6", layout)
+    a, tw, _ = started(mod, lambda c: hip_engine(mod, c, layout), cfg, 90, register=lambda e: grid_routes(e, lane_links_of(cfg)))
+    n0 = a.route_count()
+    vehicle, lists = [], []
+    for v in tw._vehicle_state()["vid"].tolist():
+        info = tw.get_vehicle_info(tw._vehicle_id(v))
+        tail = info["route"].split()
+        if "road" in info and len(tail) >= 3 and tail[:2] not in lists:  # the route cut short behind the next road
+            vehicle.append(v)
+            lists.append(tail[:2])
+        if len(lists) == 5:
+            break
+    handles = a.add_routes(lists)
+    assert len(lists) == 5 and tw.add_routes(lists) == handles and min(handles) >= n0
+    want, _, ids = check_call(a, tw, lane_links_of(cfg), vehicle, handles, "new routes")
+    assert want.tolist() == [1] * 5
+    lockstep(a, tw, 30, "new routes", ids)
+
+
+# -------------------------------------------------------------------------------------------------------- GPU: VectorEngine
+@pytest.mark.gpu
+@pytest.mark.parametrize("layout", ["auto", "dense"])
+def test_vector_engine(mod, scen, workdir, layout):
+    not_on_the_twin()
+    R = 3
+    cfg = layout_config(scen, workdir, "example_1x1", layout)
+    pairs = [g for g in ([i, o] for i in ("road_0_1_0", "road_2_1_2", "road_1_0_1", "road_1_2_3")
+                         for o in ("road_1_1_0", "road_1_1_1", "road_1_1_2", "road_1_1_3")) if int(g[0][-1]) != (int(g[1][-1]) + 2) % 4]
+    vec = mod.VectorEngine(cfg, R, 1, routes=pairs)
+    assert vec.backend_name() == "hip-gfx950"
+    handles = vec.added_routes()
+    singles = [twin(mod, scen.materialize("example_1x1", workdir, seed=r)) for r in range(R)]
+    assert all(e.add_routes(pairs) == handles for e in singles) and vec.route_count() == singles[0].route_count()
+    for _ in range(40):
+        vec.next_step()
+        for e in singles:
+            e.next_step()
+    links = lane_links_of(cfg)
+    got = vec.observe_vehicles_array()
+    D = sum(vec._drivable_counts())
+    rng = np.random.default_rng(9)
+    vehicle, local, route = [], [], []
+    for r, e in enumerate(singles):  # row j of environment r is row j of twin r
+        lo, hi = int(got["start"][r, 0]), int(got["start"][r, D])
+        rows = e.observe_vehicles_array()
+        assert hi - lo == int(rows["count"]), r
+        vehicle.append(got["vehicle"][lo:hi])
+        local.append(rows["vehicle"])
+        route.append(rng.choice(np.asarray(handles, dtype=np.int32), hi - lo))
+        route[-1][::3] = handles[0]  # (the same handle in every environment, for every third vehicle)
+    order = rng.permutation(sum(len(v) for v in vehicle))
+    where = np.concatenate([np.full(len(v), r) for r, v in enumerate(vehicle)])[order]
+    rows_v, rows_l, rows_h = (np.concatenate(x).astype(np.int32)[order] for x in (vehicle, local, route))
+    want = np.zeros(len(order), dtype=np.int32)
+    ids = []
+    for r, e in enumerate(singles):
+        at = np.flatnonzero(where == r)
+        s, rows = model_status(e, e, links, rows_l[at], rows_h[at])
+        want[at] = s
+        ids.append(command_twin(e, s, rows))
+    assert all((want[where == r] == 1).any() for r in range(R)), "an environment without an applied row"
+    shared = [r for r in range(R) if ((want == 1) & (rows_h == handles[0]) & (where == r)).any()]
+    assert len(shared) >= 2, "the shared handle is applied in the environments %s only" % shared
+    status, ignored = call(vec, rows_v, rows_h)
+    assert np.array_equal(status, want) and ignored == int((want < 0).sum())
+    held = vec.get_vehicle_routes(rows_v)
+    assert np.array_equal(held[want == 1], rows_h[want == 1]) and (held >= 0).all() and (held < vec.route_count()).all()
+    for s in range(1, 31):
+        vec.next_step()
+        for r, e in enumerate(singles):
+            e.next_step()
+            assert vec.get_vehicle_speed(r) == e.get_vehicle_speed(), "step +%d: env %d" % (s, r)
+        got = vec.observe_vehicles_array()
+        for r, e in enumerate(singles):  # (positions and lane membership: the rows are grouped by drivable)
+            lo, hi = int(got["start"][r, 0]), int(got["start"][r, D])
+            rows = e.observe_vehicles_array()
+            for k in ("distance", "speed"):
+                assert np.array_equal(got[k][lo:hi], rows[k]), "step +%d: env %d %s" % (s, r, k)
+            assert np.array_equal(np.diff(got["start"][r]), np.diff(rows["start"].reshape(-1))), "step +%d: env %d" % (s, r)
+    assert np.array_equal(vec.get_lane_vehicle_count_array().reshape(R, -1), np.stack([e.get_lane_vehicle_count_array() for e in singles]))
+
+
+# -------------------------------------------------------------------------------------------------------- GPU: stream order
+@pytest.mark.gpu
+@pytest.mark.parametrize("layout", ["auto", "dense"])
+def test_inputs_from_a_side_stream(mod, scen, workdir, layout):
+    cfg = layout_config(scen, workdir, "grid_6x6", layout)
+    a, tw, _ = started(mod, lambda c: hip_engine(mod, c, layout), cfg, 90, register=lambda e: grid_routes(e, lane_links_of(cfg)))
+    device = tensor_device(a)
+    side = torch.cuda.Stream(device=device)
+    vehicle, route = midroute_rows(a, tw, np.random.default_rng(6))
+    want, rows = model_status(a, tw, lane_links_of(cfg), vehicle, route)
+    numbers, seed = dev(a, vehicle), dev(a, route - 3)
+    handle = torch.full((len(vehicle),), -1, dtype=torch.int32, device=device)
+    status = torch.full((len(vehicle),), -7, dtype=torch.int32, device=device)
+    ignored = torch.full((1,), -7, dtype=torch.int32, device=device)
+    torch.cuda.synchronize(device)
+    with torch.cuda.stream(side):
+        big = torch.ones((2048, 2048), device=device)  # (work in front of the producer: the engine must wait for `side`)
+        for _ in range(8):
+            big = big @ big * 1e-4
+        handle.copy_(seed + 3 + (big[0, 0] * 0.0).to(torch.int32))
+        a.set_vehicle_routes_tensor(numbers, handle, status, ignored)
+        a.next_step()
+        assert int(ignored.item()) == int((want < 0).sum())  # (read on `side`, with no synchronise of our own before it)
+        assert np.array_equal(status.cpu().numpy(), want)
+    ids = command_twin(tw, want, rows)
+    tw.next_step()
+    lockstep(a, tw, 10, "side stream", ids)
+
+
+# ---------------------------------------------------------------------------------------------------------- GPU: trip log
+@pytest.mark.gpu
+@pytest.mark.parametrize("layout", ["auto", "dense"])
+def test_trip_log_names_the_new_destination(mod, scen, workdir, layout):
+    cfg = layout_config(scen, workdir, "grid_6x6", layout)
+    a, tw, _ = started(mod, lambda c: hip_engine(mod, c, layout), cfg, 90, register=lambda e: grid_routes(e, lane_links_of(cfg)))
+    a.track_trips(True, log=1024)
+    tw.track_trips(True, log=1024)
+    vehicle, lists = [], []
+    for v in tw._vehicle_state()["vid"].tolist():
+        info = tw.get_vehicle_info(tw._vehicle_id(v))
+        tail = info["route"].split()
+        if "road" in info and len(tail) >= 3 and float(info["distance"]) > 150.0 and tail[:2] not in lists:
+            vehicle.append(v)
+            lists.append(tail[:2])
+        if len(lists) == 4:
+            break
+    assert len(lists) == 4
+    handles = a.add_routes(lists)
+    assert tw.add_routes(lists) == handles
+    want, _, ids = check_call(a, tw, lane_links_of(cfg), vehicle, handles, "trip log")
+    assert want.tolist() == [1] * 4
+    roads = a.road_ids()
+    for s in range(300):
+        a.next_step()
+        tw.next_step()
+        if s % 10 == 9 and not set(ids) & set(tw.get_vehicles(True)):
+            break
+    same_state(a, tw, "trip log", AFTER)
+    log, theirs = a.observe_trip_log_array(), tw.observe_trip_log_array()
+    for k in sorted(theirs):
+        assert np.array_equal(log[k], theirs[k]), "%s differs from the twin's host log" % k
+    row_of = {v: i for i, v in enumerate(log["vehicle"].tolist())}
+    for v, g in zip(vehicle, lists):  # (a re-routed vehicle's row: the registered route's first road, the new route's last road)
+        assert v in row_of, "vehicle %d has not finished" % v
+        assert roads[log["origin_road"][row_of[v]]] == g[0] and roads[log["destination_road"][row_of[v]]] == g[1], v
