@@ -4425,6 +4425,8 @@ int32_t cfx_observe_vehicles_device(cfx_engine *e, const cfx_vehicle_rows *rows,
 int32_t cfx_set_vehicle_speeds_device(cfx_engine *e, const int32_t *vehicle, const double *speed, int32_t n, int32_t *ignored,
                                       void *producerStream);
 int32_t cfx_set_vehicle_speeds(cfx_engine *e, const int32_t *vehicle, const double *speed, int32_t n, int32_t *ignored);
+int32_t cfx_get_waiting_custom_speeds(cfx_engine *e, int32_t capacity, int32_t *vid, double *speed, int32_t *n);
+static_assert(std::is_same<decltype(&cfx_get_waiting_custom_speeds), cfx_get_waiting_custom_speeds_fn>::value, "cfx_get_waiting_custom_speeds");
 static_assert(std::is_same<decltype(&cfx_set_vehicle_speeds_device), cfx_set_vehicle_speeds_device_fn>::value, "cfx_set_vehicle_speeds_device");
 static_assert(std::is_same<decltype(&cfx_set_vehicle_speeds), cfx_set_vehicle_speeds_fn>::value, "cfx_set_vehicle_speeds");
 
@@ -4515,6 +4517,39 @@ int32_t cfx_set_vehicle_speeds(cfx_engine *e, const int32_t *vehicle, const doub
     if ((rc = launchVehicleSpeeds(e, s.dev(fVehicle), s.dev(fSpeed), n, s.dev(fCount)))) return rc;
     if ((rc = e->stageClose(s))) return rc;
     if (ignored) *ignored = count;
+    return CFX_OK;
+}
+
+// The custom speeds of the vehicles still in an entry buffer (state 0 with pendingCustom): three copies of the vehicle tables
+// and a walk on the host - its one caller is a vehicle compaction, which reads the whole state anyway.
+int32_t cfx_get_waiting_custom_speeds(cfx_engine *e, int32_t capacity, int32_t *vid, double *speed, int32_t *n) {
+    if (!e || !n || capacity < 0 || (capacity > 0 && (!vid || !speed))) return CFX_ERR_INVALID;
+    auto fail = [e](const std::string &m) { return e->fail(m); };
+    HIP_TRY(hipSetDevice(e->device));
+    int rc;
+    if ((rc = e->settle(false))) return rc;
+    if ((rc = e->syncTables())) return rc;
+    *n = 0;
+    const size_t nV = (size_t) e->spawned;
+    if (!nV) return CFX_OK;
+    std::vector<uint8_t> state(nV), pending(nV);
+    std::vector<double> cs(nV);
+    HIP_TRY(hipMemcpyAsync(state.data(), e->vt.state, nV, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipMemcpyAsync(pending.data(), e->vt.pendingCustom, nV, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipMemcpyAsync(cs.data(), e->vt.customSpeed, nV * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    int32_t k = 0;
+    for (size_t v = 0; v < nV; ++v)
+        if (state[v] == 0 && pending[v]) {
+            if (k == capacity) {
+                e->err = "cfx_get_waiting_custom_speeds: capacity too small";
+                return CFX_ERR_CAPACITY;
+            }
+            vid[k] = (int32_t) v;
+            speed[k] = cs[v];
+            ++k;
+        }
+    *n = k;
     return CFX_OK;
 }
 

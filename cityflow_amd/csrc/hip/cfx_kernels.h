@@ -1965,7 +1965,9 @@ __device__ __forceinline__ void routesCountIgnored(int32_t *ignored, bool bad) {
 }
 // The verdict on a vehicle on drivable d taking `route` (a global index): -4 on a laneLink (router.cpp:246), -5 its road does
 // not occur before the route's last road (router.cpp:239), -6 its lane has no laneLink towards the next road (Router::
-// onValidLane, router.h:66-68); 1 with *p = the first position of its road and *next = its next drivable
+// onValidLane, router.h:66-68); 1 with *p = the first position of its road and *next = its next drivable.  onValidLane also
+// holds without a next drivable where the road is the route's LAST one (Router::onLastRoad compares with route.back()), which
+// a route that comes back to this road and ends on it makes true at *p already: 1 with *next = -1, the trip ends on this lane
 template <class C> __device__ __forceinline__ int routeVerdict(const C &c, int d, int route, int *p, int *next) {
     if (d >= c.n.L) return -4;
     const int road = c.n.laneRoad[d], base = c.t.routeStart[route], len = c.t.routeStart[route + 1] - base;
@@ -1973,9 +1975,9 @@ template <class C> __device__ __forceinline__ int routeVerdict(const C &c, int d
     while (q < len - 1 && c.t.routeRoads[base + q] != road) ++q;
     if (q >= len - 1) return -5;
     const int ll = c.t.nextLL[c.t.nextStart[base + q] + c.n.laneIndex[d]];
-    if (ll < 0) return -6;
+    if (ll < 0 && c.t.routeRoads[base + len - 1] != road) return -6;
     *p = q;
-    *next = c.n.L + ll;
+    *next = ll < 0 ? -1 : c.n.L + ll;
     return 1;
 }
 __global__ void __launch_bounds__(kBlock) k_routes_claim(VehRoutesIn in, const uint8_t *state) {

@@ -393,7 +393,10 @@ Archive EngineHost::snapshotImpl(bool hostState) {
     settleLaneChange();
     refreshRoutes();  // (routes changed on the device: a load takes every vehicle's route from the host's record)
     Archive a;
-    if (hostState) a.host = spawner_.saveState();  // (compactVehicles builds its own)
+    if (hostState) {  // (compactVehicles builds its own)
+        a.host = spawner_.saveState();
+        a.nextCompactAt = nextCompactAt_;
+    }
     a.net = net_;
     a.templates = spawner_.templates;
     a.routeStart = spawner_.routes.routeStart;
@@ -494,9 +497,18 @@ void EngineHost::compactVehicles() {
     d.vState.swap(state);
     a.host = spawner_.compactedState(newOfOld, nLive);
     const Trackers::Carry tracked = trackers_.take(nV, newOfOld, nLive);  // (the load's baseline must not show)
-    // custom speeds of vehicles that are STILL waiting (cfx_state carries those of running vehicles only)
+    // custom speeds of vehicles that are STILL waiting (cfx_state carries those of running vehicles only): what the host noted,
+    // and what the device holds — set_vehicle_speeds_tensor / set_vehicle_speeds never tell the host which rows were waiting
+    std::map<int32_t, double> heldWaiting = waitingCustom_;
+    if (be_.cfx_get_waiting_custom_speeds && nV > 0) {
+        std::vector<int32_t> wv((size_t) nV);
+        std::vector<double> ws((size_t) nV);
+        int32_t nw = 0;
+        check(be_.cfx_get_waiting_custom_speeds(dev_, (int32_t) nV, wv.data(), ws.data(), &nw), "cfx_get_waiting_custom_speeds");
+        for (int32_t i = 0; i < nw; ++i) heldWaiting[wv[(size_t) i]] = ws[(size_t) i];  // (the device's is the later command)
+    }
     std::map<int32_t, double> stillWaiting;
-    for (const auto &kv : waitingCustom_)
+    for (const auto &kv : heldWaiting)
         if (kv.first >= 0 && kv.first < nV && newOfOld[(size_t) kv.first] >= 0 && d.vState[(size_t) newOfOld[(size_t) kv.first]] == 0)
             stillWaiting[newOfOld[(size_t) kv.first]] = kv.second;
     load(a);
@@ -515,6 +527,14 @@ void EngineHost::load(const Archive &a) {
     pendingPhaseValue_.clear();
     if (a.net.get() != net_.get() && a.net->lanes.size() != net_->lanes.size())
         throw std::runtime_error("Engine.load: archive belongs to a different road network");
+    // An Archive names routes and vehicle templates by their index in the tables of the engine that took it.  Another engine of
+    // the same network holds the flows' entries at the same indices, but not what set_vehicle_route / push_vehicle / add_routes
+    // interned there since: such an archive goes through dump() and load_from_file(), which interns what the file needs.
+    const int nRoutes = (int) spawner_.routes.routeStart.size() - 1, nTemplates = (int) spawner_.templates.size();
+    for (const auto &v : a.host.vehicles)
+        if (v.route >= nRoutes || v.templ >= nTemplates)
+            throw std::runtime_error("Engine.load: the archive names a route or a vehicle template this engine does not hold "
+                                     "(taken by another engine: use dump() and load_from_file())");
     spawner_.loadState(a.host);
     routesStale_ = false;  // (every vehicle's route is the archive's, on the host and on the device)
     uploadNewTablesIfAny();
@@ -579,8 +599,13 @@ void EngineHost::load(const Archive &a) {
     vehicleEpoch_ += 1;  // vehicle numbers of the archive replace the current ones
     // An archive taken earlier holds fewer vehicle numbers than the state it replaces: the next compaction is due that many
     // numbers after what it holds, not at the schedule of the state before (which would let the tables grow back to it first).
+    // A snapshot() of an engine brings the schedule it had: the vehicle numbers that follow a load — what observe_vehicles_tensor
+    // lists and the batched commands take — are then a function of the archive, not of what the engine did since.
+    // An archive of ANOTHER engine may bring a schedule of another policy: never later than this engine's own rule for what the
+    // archive holds (an engine's own schedule never is: it was set at a compaction, when it held no more than the archive does).
     const size_t held = spawner_.vehicles.size();
-    nextCompactAt_ = std::min(nextCompactAt_, compactAuto_ ? std::max(compactAt_, 32 * held) : held + compactAt_);
+    const size_t due = compactAuto_ ? std::max(compactAt_, 32 * held) : held + compactAt_;
+    nextCompactAt_ = a.nextCompactAt ? std::min(a.nextCompactAt, due) : std::min(nextCompactAt_, due);
 }
 
 // ------------------------------------------------------------------------------------------ checkpoints in device memory
@@ -636,6 +661,7 @@ std::shared_ptr<DeviceCheckpoint> EngineHost::checkpoint(std::shared_ptr<DeviceC
     ck->routesStale = routesStale_;  // (no read-back here: a checkpoint does not wait for the device)
     ck->step = step_;
     ck->waitingCustom = waitingCustom_;
+    ck->nextCompactAt = nextCompactAt_;
     return ck;
 }
 
@@ -662,8 +688,7 @@ void EngineHost::rollback(DeviceCheckpoint &ck) {
     trackers_.rebaseline((int64_t) step_, [this] { tripNoteVehicles(); });
     waitingCustom_ = ck.waitingCustom;
     vehicleEpoch_ += 1;  // vehicle numbers of the checkpoint replace the current ones (a compaction may lie in between)
-    const size_t held = spawner_.vehicles.size();
-    nextCompactAt_ = std::min(nextCompactAt_, compactAuto_ ? std::max(compactAt_, 32 * held) : held + compactAt_);
+    nextCompactAt_ = ck.nextCompactAt;  // (the schedule is the checkpoint's: the run repeats with the vehicle numbers it had)
 }
 
 // Archive(Engine&, filename) archive.cpp:345-550: rebuild an Archive from the reference's JSON format.

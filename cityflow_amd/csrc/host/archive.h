@@ -43,6 +43,7 @@ public:
     std::vector<cfx_vehicle_template> templates;
     std::vector<int32_t> routeStart, routeRoads;
     std::vector<std::string> flowIds;
+    size_t nextCompactAt = 0;  // the engine's vehicle-compaction schedule when snapshot() took the state (0: not known — a file)
 
     void dump(const std::string &path) const;
     // numbers of the last dump() that NO decimal literal makes the reference's reader return exactly (about one double in 10^5:

@@ -98,6 +98,7 @@ void Backend::open(const std::string &libPath) {
     CFX_FN_OPTIONAL(cfx_observe_vehicles_device)
     CFX_FN_OPTIONAL(cfx_set_vehicle_speeds_device)
     CFX_FN_OPTIONAL(cfx_set_vehicle_speeds)
+    CFX_FN_OPTIONAL(cfx_get_waiting_custom_speeds)
     CFX_FN_OPTIONAL(cfx_set_vehicle_routes_device)
     CFX_FN_OPTIONAL(cfx_set_vehicle_routes)
     CFX_FN_OPTIONAL(cfx_get_vehicle_routes_device)

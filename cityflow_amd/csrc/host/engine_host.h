@@ -94,6 +94,7 @@ struct Backend {
     // optional as a pair: speed commands for many vehicles at once (without them the host commands row by row: setVehicleSpeedsOf)
     cfx_set_vehicle_speeds_device_fn cfx_set_vehicle_speeds_device = nullptr;
     cfx_set_vehicle_speeds_fn cfx_set_vehicle_speeds = nullptr;
+    cfx_get_waiting_custom_speeds_fn cfx_get_waiting_custom_speeds = nullptr;
     // optional as a set: route changes for many vehicles at once and the routes they hold (without them there is no such
     // call: cfx_set_vehicle_route restarts the cursor and cannot stand in)
     cfx_set_vehicle_routes_device_fn cfx_set_vehicle_routes_device = nullptr;
@@ -290,6 +291,7 @@ struct DeviceCheckpoint {
     std::vector<Spawner::State> host;
     bool routesStale = false;  // the vehicles' routes in `host` were behind the device's (EngineHost::routesStale_)
     size_t step = 0;
+    size_t nextCompactAt = 0;                                 // EngineHost::nextCompactAt_
     std::map<int32_t, double> waitingCustom;                  // EngineHost::waitingCustom_
     std::vector<std::vector<int32_t>> localToGlobal;          // VectorEngineHost's numbering
     std::vector<std::pair<int32_t, int32_t>> globalToLocal;
@@ -394,7 +396,7 @@ public:
     void observeVehiclesDevice(const cfx_vehicle_rows &rows, uintptr_t consumerStream);
     // ---- speed commands for many vehicles at once, by the vehicle numbers of the rows above (setVehicleSpeedsOf above;
     //      std::runtime_error with laneChange).  A command the device takes for a vehicle still in its entry buffer is not
-    //      in waitingCustom_: a vehicle compaction before that vehicle's first step drops it
+    //      in waitingCustom_: compactVehicles reads those back from the device (cfx_get_waiting_custom_speeds)
     bool vehicleSpeedsDevice() const { return be_.hasDeviceBuffers() && be_.cfx_set_vehicle_speeds_device; }
     void setVehicleSpeedsDevice(uintptr_t vehicle, uintptr_t speed, int n, uintptr_t ignored, uintptr_t producerStream);
     int setVehicleSpeeds(const int32_t *vehicle, const double *speed, int n);

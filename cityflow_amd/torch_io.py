@@ -1346,7 +1346,8 @@ def set_vehicle_routes_tensor(self, vehicle, route, status=None, ignored=None):
         -3   superseded: a later row that passes the checks above names the same vehicle
         -4   the vehicle is inside an intersection (on a laneLink)
         -5   the vehicle's road does not occur on the route before the route's last road
-        -6   the vehicle's lane has no laneLink towards the route's next road: it is in the wrong turning lane
+        -6   the vehicle's lane has no laneLink towards the route's next road: it is in the wrong turning lane (where the
+             route also ENDS on the vehicle's road the reference accepts that: applied, and the trip ends on this lane)
          1   applied
 
     Of several rows for one vehicle only the LAST one that passes -1 and -2 counts, whatever its verdict — this is not "the

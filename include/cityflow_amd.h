@@ -627,6 +627,12 @@ typedef int32_t (*cfx_observe_vehicles_device_fn)(cfx_engine *e, const cfx_vehic
 typedef int32_t (*cfx_set_vehicle_speeds_device_fn)(cfx_engine *e, const int32_t *vehicle, const double *speed, int32_t n,
                                                     int32_t *ignored, void *producer_stream);
 typedef int32_t (*cfx_set_vehicle_speeds_fn)(cfx_engine *e, const int32_t *vehicle, const double *speed, int32_t n, int32_t *ignored);
+/* OPTIONAL, beside the two above: the custom speeds that vehicles still WAITING in an entry buffer hold, whichever call set
+ * them (cfx_set_vehicle_speed or the two above) - what cfx_get_custom_speeds does not list and cfx_load_state does not take.
+ * Writes n[0] pairs {vid[i], speed[i]} in ascending vid; CFX_ERR_CAPACITY when there are more than `capacity`.  Host memory;
+ * waits for the device.  A host that renumbers the vehicles (a load of its own state) reads them first and gives them back
+ * with cfx_set_vehicle_speed: the device calls never tell it which of their rows named a waiting vehicle. */
+typedef int32_t (*cfx_get_waiting_custom_speeds_fn)(cfx_engine *e, int32_t capacity, int32_t *vid, double *speed, int32_t *n);
 
 /* ---- Route changes for many vehicles at once, and the routes the vehicles hold (OPTIONAL entry points, as above; all four or
  * none): Router::setRoute for n rows {vehicle[i], route[i]}, n >= 0.  The vehicle numbers are cfx_observe_vehicles_device's.
@@ -641,7 +647,9 @@ typedef int32_t (*cfx_set_vehicle_speeds_fn)(cfx_engine *e, const int32_t *vehic
  *   -4   the vehicle is inside an intersection, on a laneLink (Router::setRoute, router.cpp:246)
  *   -5   the vehicle's road does not occur on the route before the route's last road (a remaining route of one road is
  *        refused, router.cpp:239)
- *   -6   the vehicle's lane has no laneLink towards the route's next road (Router::onValidLane, router.h:66-68)
+ *   -6   the vehicle's lane has no laneLink towards the route's next road (Router::onValidLane, router.h:66-68) — unless
+ *        the vehicle's road is also the route's LAST road (a route that comes back to it): onValidLane holds there, the
+ *        row is applied with no next drivable and the vehicle ends its trip on this lane
  *    1   applied: the vehicle holds the route with its cursor on the FIRST position p of its road, its next drivable and its
  *        last-road flag are those of (route, p); cfx_get_vehicle then answers route and route_pos = p
  * Of the rows for one vehicle that pass -1 and -2 only the LAST counts, whatever its verdict: this is not "the last valid

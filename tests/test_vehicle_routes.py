@@ -81,7 +81,8 @@ def model_status(a, tw, links, vehicle, route):
             status[i], rows[i] = -5, (vid, road, g, None)
             continue
         p = g.index(road)
-        status[i] = 1 if has_next(links, road, index, g, p) else -6
+        # (Router::onValidLane: a next drivable, or on the route's last road — which a route that ends on a repeated road makes true)
+        status[i] = 1 if has_next(links, road, index, g, p) or road == g[-1] else -6
         rows[i] = (vid, road, g, p)
     return status, rows
 
