@@ -23,6 +23,7 @@
 #include "cfx_lc_kernels.h"
 #include "cfx_ring_kernels.h"
 #include "cfx_dense_kernels.h"
+#include "cfx_lane_limit_kernels.h"
 
 // k_cross2's grid on the dense layout: one block per kCross2Jobs slots of the layout's bound, at most this many (the
 // kernel strides over the queue, so any grid is correct; blocks beyond the queue's length only pay the prologue)
@@ -186,9 +187,14 @@ struct cfx_engine {
     int nPhaseTimes = 0, planMaxPhases = 0;
     TlPlanErr *hPlanErr = nullptr;  // pinned, host-mapped; inter = -1: none
     int32_t planCalls = 0;          // set calls enqueued so far (TlPlanErr::done: the last one the device has decided)
+    // cfx_set_lane_speed_limits_device and its kin: the limits in force are net.drvLM[l].y and net.drvMaxSpeed[l] themselves,
+    // held here non-const (the step's kernels read drvLM once per vehicle and step; cfx_lane_limit_kernels.h writes both from one
+    // value); the file's lane limits [L], for cfx_restore_lane_speed_limits
+    double2 *drvLM = nullptr;
+    double *drvMaxSpeed = nullptr, *laneLimitFile = nullptr;
     // The staging arena of the host forms (cfx_get_lane_obs, cfx_get_lane_features, cfx_get_intersection_features,
     // cfx_get_movement_flow, cfx_set_tl_plan, cfx_get_tl_phase_durations, cfx_set_vehicle_speeds, cfx_set_vehicle_routes,
-    // cfx_get_vehicle_routes): the device side of the host
+    // cfx_get_vehicle_routes, cfx_set_lane_speed_limits, cfx_get_lane_speed_limits): the device side of the host
     // arrays one call was given, laid out by cfx_stage_layout.h.  ONE allocation (in `owned`), grown to the largest request
     // seen, rounded up to a power of two so that requests that creep up (the speed commands of a filling network) regrow it a
     // logarithmic number of times.  Growing frees the old one at once, which is safe because the arena is idle at every
@@ -2113,7 +2119,9 @@ static int32_t createImpl(cfx_engine *e, const cfx_net *n, const cfx_config *cfg
 #define UP(field, src, count) \
     if ((rc = e->uploadConst(d.field, src, (size_t) (count)))) return rc;
     UP(drvLength, n->drv_length, e->D)
-    UP(drvMaxSpeed, n->drv_max_speed, e->D)
+    if ((rc = e->upload(&e->drvMaxSpeed, n->drv_max_speed, (size_t) e->D))) return rc;  // (lanes written by cfx_set_lane_speed_limits*)
+    d.drvMaxSpeed = e->drvMaxSpeed;
+    if ((rc = e->upload(&e->laneLimitFile, n->drv_max_speed, (size_t) e->L))) return rc;
     UP(laneRoad, n->lane_road, e->L)
     UP(laneIndex, n->lane_index, e->L)
     UP(laneLLStart, n->lane_ll_start, e->L + 1)
@@ -2193,7 +2201,8 @@ static int32_t createImpl(cfx_engine *e, const cfx_net *n, const cfx_config *cfg
             xdd[x] = make_double2(n->x_dist[x], n->x_dist[pe]);
             xpack[x] = make_int4(pll, llLocal[pll], n->ll_type[pll], n->ll_roadlink[pll]);
         }
-        if ((rc = e->uploadConst(d.drvLM, lm.data(), lm.size()))) return rc;
+        if ((rc = e->upload(&e->drvLM, lm.data(), lm.size()))) return rc;  // (.y of the lanes written with drvMaxSpeed)
+        d.drvLM = e->drvLM;
         if ((rc = e->uploadConst(d.xDD, xdd.data(), xdd.size()))) return rc;
         if ((rc = e->uploadConst(d.xPack, xpack.data(), xpack.size()))) return rc;
         std::vector<int4> llpack((size_t) e->K);
@@ -4220,6 +4229,115 @@ int32_t cfx_tl_plan_error(cfx_engine *e, int32_t *what, int32_t *inter, int32_t 
     if (value) *value = rec->value;
     rec->inter = -1;
     return 1;
+}
+
+// ---- the lanes' speed limits as engine state (optional entry points of include/cityflow_amd.h, as above)
+int32_t cfx_set_lane_speed_limits_device(cfx_engine *e, const double *limits, int32_t n, int32_t *rejected, void *producerStream);
+int32_t cfx_set_lane_speed_limits(cfx_engine *e, const double *limits, int32_t n, int32_t *rejected);
+int32_t cfx_get_lane_speed_limits_device(cfx_engine *e, double *out, int32_t n, void *consumerStream);
+int32_t cfx_get_lane_speed_limits(cfx_engine *e, double *out, int32_t n);
+int32_t cfx_restore_lane_speed_limits(cfx_engine *e);
+static_assert(std::is_same<decltype(&cfx_set_lane_speed_limits_device), cfx_set_lane_speed_limits_device_fn>::value,
+              "cfx_set_lane_speed_limits_device");
+static_assert(std::is_same<decltype(&cfx_set_lane_speed_limits), cfx_set_lane_speed_limits_fn>::value, "cfx_set_lane_speed_limits");
+static_assert(std::is_same<decltype(&cfx_get_lane_speed_limits_device), cfx_get_lane_speed_limits_device_fn>::value,
+              "cfx_get_lane_speed_limits_device");
+static_assert(std::is_same<decltype(&cfx_get_lane_speed_limits), cfx_get_lane_speed_limits_fn>::value, "cfx_get_lane_speed_limits");
+static_assert(std::is_same<decltype(&cfx_restore_lane_speed_limits), cfx_restore_lane_speed_limits_fn>::value,
+              "cfx_restore_lane_speed_limits");
+
+// what every limit call checks first: not on a tile (a cut lane's limit would be another tile's too), the caller's length
+static int laneLimitArgs(cfx_engine *e, int32_t n, const char *what) {
+    if (e->tiled) {
+        e->err = std::string(what) + ": not on a tile";
+        return CFX_ERR_STATE;
+    }
+    if (n != e->L) {
+        e->err = std::string(what) + ": n must be the network's " + std::to_string(e->L) + " lanes, not " + std::to_string(n);
+        return CFX_ERR_INVALID;
+    }
+    return CFX_OK;
+}
+
+// (no settle in these calls: a deferred commit reads no limit — the action phase of the step it belongs to has run)
+static int launchSetLaneLimits(cfx_engine *e, const double *limits, int32_t *rejected) {
+    auto fail = [e](const std::string &m) { return e->fail(m); };
+    if (rejected) HIP_TRY(hipMemsetAsync(rejected, 0, sizeof(int32_t), e->stream));
+    if (e->L)
+        hipLaunchKernelGGL(k_set_lane_limits, dim3(gridStride((size_t) e->L)), dim3(kBlock), 0, e->stream, limits, e->L, e->drvLM,
+                           e->drvMaxSpeed, rejected);
+    HIP_TRY(hipGetLastError());
+    return CFX_OK;
+}
+
+int32_t cfx_set_lane_speed_limits_device(cfx_engine *e, const double *limits, int32_t n, int32_t *rejected, void *producerStream) {
+    if (!e || !limits) return CFX_ERR_INVALID;
+    auto fail = [e](const std::string &m) { return e->fail(m); };
+    HIP_TRY(hipSetDevice(e->device));
+    int rc;
+    if ((rc = laneLimitArgs(e, n, "cfx_set_lane_speed_limits_device"))) return rc;
+    if ((rc = checkDevicePointers(e, "cfx_set_lane_speed_limits_device", {{limits, "limits"}, {rejected, "rejected"}}))) return rc;
+    if ((rc = e->orderAfterCaller((hipStream_t) producerStream))) return rc;
+    if ((rc = launchSetLaneLimits(e, limits, rejected))) return rc;
+    return e->orderCallerAfter((hipStream_t) producerStream);
+}
+
+int32_t cfx_set_lane_speed_limits(cfx_engine *e, const double *limits, int32_t n, int32_t *rejected) {
+    if (!e || !limits) return CFX_ERR_INVALID;
+    auto fail = [e](const std::string &m) { return e->fail(m); };
+    HIP_TRY(hipSetDevice(e->device));
+    int rc;
+    if ((rc = laneLimitArgs(e, n, "cfx_set_lane_speed_limits"))) return rc;
+    cfx_stage::StageLayout s;
+    const auto fLimits = s.in(limits, (size_t) e->L);
+    const auto fRejected = s.out(rejected, 1);
+    if ((rc = e->stageOpen(s))) return rc;
+    if ((rc = launchSetLaneLimits(e, s.dev(fLimits), s.dev(fRejected)))) return rc;
+    return e->stageClose(s);
+}
+
+static void launchGetLaneLimits(cfx_engine *e, double *out) {
+    if (e->L) hipLaunchKernelGGL(k_get_lane_limits, dim3(gridStride((size_t) e->L)), dim3(kBlock), 0, e->stream, e->L, e->drvMaxSpeed, out);
+}
+
+int32_t cfx_get_lane_speed_limits_device(cfx_engine *e, double *out, int32_t n, void *consumerStream) {
+    if (!e || !out) return CFX_ERR_INVALID;
+    auto fail = [e](const std::string &m) { return e->fail(m); };
+    HIP_TRY(hipSetDevice(e->device));
+    int rc;
+    if ((rc = laneLimitArgs(e, n, "cfx_get_lane_speed_limits_device"))) return rc;
+    if ((rc = checkDevicePointer(e, out, "cfx_get_lane_speed_limits_device: out"))) return rc;
+    if ((rc = e->orderAfterCaller((hipStream_t) consumerStream))) return rc;
+    launchGetLaneLimits(e, out);
+    HIP_TRY(hipGetLastError());
+    return e->orderCallerAfter((hipStream_t) consumerStream);
+}
+
+int32_t cfx_get_lane_speed_limits(cfx_engine *e, double *out, int32_t n) {
+    if (!e || !out) return CFX_ERR_INVALID;
+    auto fail = [e](const std::string &m) { return e->fail(m); };
+    HIP_TRY(hipSetDevice(e->device));
+    int rc;
+    if ((rc = laneLimitArgs(e, n, "cfx_get_lane_speed_limits"))) return rc;
+    cfx_stage::StageLayout s;
+    const auto fOut = s.out(out, (size_t) e->L);
+    if ((rc = e->stageOpen(s))) return rc;
+    launchGetLaneLimits(e, s.dev(fOut));
+    HIP_TRY(hipGetLastError());
+    return e->stageClose(s);
+}
+
+int32_t cfx_restore_lane_speed_limits(cfx_engine *e) {
+    if (!e) return CFX_ERR_INVALID;
+    auto fail = [e](const std::string &m) { return e->fail(m); };
+    HIP_TRY(hipSetDevice(e->device));
+    int rc;
+    if ((rc = laneLimitArgs(e, e->L, "cfx_restore_lane_speed_limits"))) return rc;
+    if (e->L)
+        hipLaunchKernelGGL(k_restore_lane_limits, dim3(gridStride((size_t) e->L)), dim3(kBlock), 0, e->stream, e->L, e->laneLimitFile,
+                           e->drvLM, e->drvMaxSpeed);
+    HIP_TRY(hipGetLastError());
+    return CFX_OK;
 }
 
 // ---- per-lane speed and position features (optional entry points of include/cityflow_amd.h, as above)

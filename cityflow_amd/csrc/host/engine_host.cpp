@@ -136,6 +136,11 @@ void Backend::open(const std::string &libPath) {
     CFX_FN_OPTIONAL(cfx_get_tl_phase_durations)
     CFX_FN_OPTIONAL(cfx_restore_tl_plan)
     CFX_FN_OPTIONAL(cfx_tl_plan_error)
+    CFX_FN_OPTIONAL(cfx_set_lane_speed_limits_device)
+    CFX_FN_OPTIONAL(cfx_set_lane_speed_limits)
+    CFX_FN_OPTIONAL(cfx_get_lane_speed_limits_device)
+    CFX_FN_OPTIONAL(cfx_get_lane_speed_limits)
+    CFX_FN_OPTIONAL(cfx_restore_lane_speed_limits)
     CFX_FN_OPTIONAL(cfx_get_cross_stats)
     CFX_FN_OPTIONAL(cfx_checkpoint_create)
     CFX_FN_OPTIONAL(cfx_checkpoint_save)
@@ -291,6 +296,7 @@ EngineHost::EngineHost(const std::string &configFile, int threadNum, const std::
     uploadNewTablesIfAny();
     trackers_.bind(&be_, dev_, &net_->flat(), 1, interval_);
     plan_.bind(&be_, dev_, net_.get(), 1, false);
+    limits_.bind(&be_, dev_, (int) net_->lanes.size());
 }
 
 EngineHost::~EngineHost() {
@@ -586,6 +592,48 @@ void TlPlan::raise() {
         m += "phase_remain: " + std::string(num) + " for " + where + " is negative or not finite";
     }
     throw std::invalid_argument(m + " (the call was not applied)");
+}
+
+// ---------------------------------------------------------------- the lanes' speed limits as engine state
+void LaneLimits::need(const char *what) const {
+    if (!available())
+        throw std::logic_error(std::string(what) + ": the backend '" + (be_ ? be_->path : std::string()) +
+                               "' does not keep the lanes' speed limits as engine state");
+}
+
+void LaneLimits::check(int32_t rc, const char *what) const {
+    if (rc == CFX_OK) return;
+    const char *msg = be_->cfx_last_error(dev_);
+    throw std::runtime_error(std::string("cityflow_amd: ") + what + " failed (" + std::to_string(rc) + "): " + (msg ? msg : ""));
+}
+
+void LaneLimits::setDevice(uintptr_t limits, uintptr_t rejected, uintptr_t producerStream) {
+    need("set_lane_speed_limits_tensor");
+    check(be_->cfx_set_lane_speed_limits_device(dev_, (const double *) limits, (int32_t) n_, (int32_t *) rejected, (void *) producerStream),
+          "cfx_set_lane_speed_limits_device");
+}
+
+void LaneLimits::getDevice(uintptr_t out, uintptr_t consumerStream) {
+    need("get_lane_speed_limits_tensor");
+    check(be_->cfx_get_lane_speed_limits_device(dev_, (double *) out, (int32_t) n_, (void *) consumerStream),
+          "cfx_get_lane_speed_limits_device");
+}
+
+int32_t LaneLimits::set(const double *limits) {
+    need("set_lane_speed_limits");
+    int32_t rejected = 0;
+    check(be_->cfx_set_lane_speed_limits(dev_, limits, (int32_t) n_, &rejected), "cfx_set_lane_speed_limits");
+    return rejected;
+}
+
+void LaneLimits::get(double *out) {
+    need("get_lane_speed_limits_array");
+    check(be_->cfx_get_lane_speed_limits(dev_, out, (int32_t) n_), "cfx_get_lane_speed_limits");
+}
+
+void LaneLimits::restore() {
+    need("restore_lane_speed_limits");
+    check(be_->cfx_restore_lane_speed_limits(dev_), "cfx_restore_lane_speed_limits");
 }
 
 void EngineHost::setTlPlanDevice(uintptr_t durations, uintptr_t phase, uintptr_t remain, uintptr_t producerStream) {

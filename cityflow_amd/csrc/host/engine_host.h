@@ -144,6 +144,12 @@ struct Backend {
     cfx_get_tl_phase_durations_fn cfx_get_tl_phase_durations = nullptr;
     cfx_restore_tl_plan_fn cfx_restore_tl_plan = nullptr;
     cfx_tl_plan_error_fn cfx_tl_plan_error = nullptr;
+    // optional as a set: the lanes' speed limits as engine state (without them there is no such call: LaneLimits below)
+    cfx_set_lane_speed_limits_device_fn cfx_set_lane_speed_limits_device = nullptr;
+    cfx_set_lane_speed_limits_fn cfx_set_lane_speed_limits = nullptr;
+    cfx_get_lane_speed_limits_device_fn cfx_get_lane_speed_limits_device = nullptr;
+    cfx_get_lane_speed_limits_fn cfx_get_lane_speed_limits = nullptr;
+    cfx_restore_lane_speed_limits_fn cfx_restore_lane_speed_limits = nullptr;
     cfx_get_cross_stats_fn cfx_get_cross_stats = nullptr;  // (a library without it: crossStats() reports nothing)
     // optional as a set: checkpoints in device memory (without them there is no such call: DeviceCheckpoint below)
     cfx_checkpoint_create_fn cfx_checkpoint_create = nullptr;
@@ -158,6 +164,10 @@ struct Backend {
     bool hasTlPlan() const {
         return hasDeviceBuffers() && cfx_set_tl_plan_device && cfx_set_tl_plan && cfx_get_tl_phase_durations_device &&
                cfx_get_tl_phase_durations && cfx_restore_tl_plan && cfx_tl_plan_error;
+    }
+    bool hasLaneLimits() const {
+        return hasDeviceBuffers() && cfx_set_lane_speed_limits_device && cfx_set_lane_speed_limits && cfx_get_lane_speed_limits_device &&
+               cfx_get_lane_speed_limits && cfx_restore_lane_speed_limits;
     }
     void open(const std::string &libPath);  // throws std::runtime_error
     ~Backend();
@@ -232,6 +242,35 @@ private:
     const HostRoadNet *net_ = nullptr;
     int nEnvs_ = 1, I_ = 0, P_ = 0;
     bool namesEnv_ = false, unchecked_ = false;
+};
+
+// The lanes' speed limits as engine state (cfx_set_lane_speed_limits_device and its kin; the public calls are
+// cityflow_amd/torch_io.py): what EngineHost and VectorEngineHost share.  Arrays cover every environment, env-major:
+// [nEnvs * L] in lane_ids() order — the device network of a VectorEngine is nEnvs concatenated copies, so they pass straight
+// through.  The caller holds whatever lock its ABI calls need.  A backend without the entry points: std::logic_error.
+class LaneLimits {
+public:
+    void bind(const Backend *be, cfx_engine *dev, int nLanesAllEnvs) {
+        be_ = be;
+        dev_ = dev;
+        n_ = nLanesAllEnvs;
+    }
+    bool available() const { return be_ && be_->hasLaneLimits(); }
+    int size() const { return n_; }
+    // device addresses, ordered against the caller's stream (rejected: 0 or one int32)
+    void setDevice(uintptr_t limits, uintptr_t rejected, uintptr_t producerStream);
+    void getDevice(uintptr_t out, uintptr_t consumerStream);
+    // host memory, synchronous
+    int32_t set(const double *limits);  // the number of rejected entries
+    void get(double *out);
+    void restore();
+
+private:
+    void need(const char *what) const;
+    void check(int32_t rc, const char *what) const;
+    const Backend *be_ = nullptr;
+    cfx_engine *dev_ = nullptr;
+    int n_ = 0;
 };
 
 // the four front-vehicle outputs in host memory ([n_lanes * k] each, of every environment; any may be null)
@@ -380,6 +419,16 @@ public:
     void tlPhaseDurationsDevice(uintptr_t out, uintptr_t consumerStream) { plan_.durationsDevice(out, consumerStream); }
     void tlPhaseDurations(double *out);
     void restoreTlPlan() { plan_.restore(); }
+    // ---- the lanes' speed limits as engine state (LaneLimits above): [L] in lane_ids() order
+    bool laneLimitCalls() const { return limits_.available(); }
+    int laneLimitCount() const { return limits_.size(); }
+    void setLaneSpeedLimitsDevice(uintptr_t limits, uintptr_t rejected, uintptr_t producerStream) {
+        limits_.setDevice(limits, rejected, producerStream);
+    }
+    int32_t setLaneSpeedLimits(const double *limits) { return limits_.set(limits); }
+    void laneSpeedLimitsDevice(uintptr_t out, uintptr_t consumerStream) { limits_.getDevice(out, consumerStream); }
+    void laneSpeedLimits(double *out) { limits_.get(out); }
+    void restoreLaneSpeedLimits() { limits_.restore(); }
     // ---- per-lane speed and position features (cfx_observe_lanes_device / cfx_get_lane_features; the twin: from the vehicles)
     std::vector<double> laneLengths() const;  // [n_lanes] Lane::getLength
     // speedSum [n_lanes], bins [n_lanes * nBins] (either may be null), edges: [n_lanes][nBins + 1] or [nBins + 1]
@@ -516,6 +565,7 @@ private:
     bool devicePhaseUnchecked_ = false;
     void raiseDeviceError();  // (then a rejected plan: TlPlan::raise, std::invalid_argument)
     TlPlan plan_;
+    LaneLimits limits_;
 
     std::shared_ptr<HostRoadNet> net_ = std::make_shared<HostRoadNet>();
     Spawner spawner_;

@@ -554,6 +554,18 @@ template <typename E> py::array_t<double> tlPhaseDurationsArray(E &e) {
     return out;
 }
 
+// ---- the lanes' speed limits as engine state (Engine and VectorEngine; the public calls are cityflow_amd/torch_io.py)
+template <typename E> int setLaneSpeedLimitsArray(E &e, const py::array_t<double, py::array::c_style | py::array::forcecast> &limits) {
+    if (limits.size() != (py::ssize_t) e.laneLimitCount()) throw std::invalid_argument("set_lane_speed_limits: an array of the wrong size");
+    return (int) e.setLaneSpeedLimits(limits.data());
+}
+
+template <typename E> py::array_t<double> laneSpeedLimitsArray(E &e) {
+    py::array_t<double> out((py::ssize_t) e.laneLimitCount());
+    e.laneSpeedLimits(out.mutable_data());
+    return out;
+}
+
 // track_lane_flow / track_movement_flow / track_trips: lane change is out of scope (logic_error), not a failure of the call
 template <typename E, void (E::*Track)(bool)> void trackOrNotImplemented(E &e, bool on) {
     try {
@@ -574,6 +586,14 @@ template <typename E> void defDeviceBuffers(py::class_<E> &c) {
         .def("_tl_phase_durations_device", &E::tlPhaseDurationsDevice, "out_ptr"_a, "consumer_stream"_a)
         .def("_tl_phase_durations", &tlPhaseDurationsArray<E>, "float64, flat (env-major, then intersection, then phase)")
         .def("_restore_tl_plan", &E::restoreTlPlan)
+        .def("_lane_limit_calls", &E::laneLimitCalls,
+             "the backend keeps the lanes' speed limits as engine state (set_lane_speed_limits_tensor and its kin)")
+        .def("_set_lane_speed_limits_device", &E::setLaneSpeedLimitsDevice, "limits_ptr"_a, "rejected_ptr"_a, "producer_stream"_a)
+        .def("_set_lane_speed_limits", &setLaneSpeedLimitsArray<E>, "limits"_a,
+             "float64 [.., L]; waits for the device and returns the number of rejected entries")
+        .def("_lane_speed_limits_device", &E::laneSpeedLimitsDevice, "out_ptr"_a, "consumer_stream"_a)
+        .def("_lane_speed_limits", &laneSpeedLimitsArray<E>, "float64, flat (env-major, then lane)")
+        .def("_restore_lane_speed_limits", &E::restoreLaneSpeedLimits)
         .def("_checkpoint_calls", &E::checkpointCalls, "the backend has checkpoints in device memory (checkpoint() / rollback())")
         .def("_checkpoint_unsupported", &E::checkpointUnsupported, "why this engine has no checkpoints in device memory ('' = it has)")
         .def("_checkpoint", &E::checkpoint, "into"_a = py::none(), py::keep_alive<0, 1>(),

@@ -197,6 +197,7 @@ VectorEngineHost::VectorEngineHost(const std::string &configFile, int numEnvs, i
     }
     trackers_.bind(&be_, dev_, &net_->flat(), R_, interval_);
     plan_.bind(&be_, dev_, net_.get(), R_, true);
+    limits_.bind(&be_, dev_, R_ * L_);
 }
 
 VectorEngineHost::~VectorEngineHost() {
@@ -791,6 +792,31 @@ void VectorEngineHost::tlPhaseDurations(double *out) {
 void VectorEngineHost::restoreTlPlan() {
     std::lock_guard<std::mutex> guard(queryMutex_);
     plan_.restore();
+}
+
+void VectorEngineHost::setLaneSpeedLimitsDevice(uintptr_t limits, uintptr_t rejected, uintptr_t producerStream) {
+    std::lock_guard<std::mutex> guard(queryMutex_);
+    limits_.setDevice(limits, rejected, producerStream);
+}
+
+int32_t VectorEngineHost::setLaneSpeedLimits(const double *limits) {
+    std::lock_guard<std::mutex> guard(queryMutex_);
+    return limits_.set(limits);
+}
+
+void VectorEngineHost::laneSpeedLimitsDevice(uintptr_t out, uintptr_t consumerStream) {
+    std::lock_guard<std::mutex> guard(queryMutex_);
+    limits_.getDevice(out, consumerStream);
+}
+
+void VectorEngineHost::laneSpeedLimits(double *out) {
+    std::lock_guard<std::mutex> guard(queryMutex_);
+    limits_.get(out);
+}
+
+void VectorEngineHost::restoreLaneSpeedLimits() {
+    std::lock_guard<std::mutex> guard(queryMutex_);
+    limits_.restore();
 }
 
 void VectorEngineHost::trafficLightState(std::vector<int32_t> &phase, std::vector<double> &remain) {

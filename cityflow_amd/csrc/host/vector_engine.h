@@ -79,6 +79,15 @@ public:
     void tlPhaseDurationsDevice(uintptr_t out, uintptr_t consumerStream);
     void tlPhaseDurations(double *out);
     void restoreTlPlan();
+    // the lanes' speed limits of every environment (EngineHost::setLaneSpeedLimitsDevice and its kin): [R * L], one scheme
+    // per environment over the one roadnet
+    bool laneLimitCalls() const { return limits_.available(); }
+    int laneLimitCount() const { return limits_.size(); }
+    void setLaneSpeedLimitsDevice(uintptr_t limits, uintptr_t rejected, uintptr_t producerStream);
+    int32_t setLaneSpeedLimits(const double *limits);
+    void laneSpeedLimitsDevice(uintptr_t out, uintptr_t consumerStream);
+    void laneSpeedLimits(double *out);
+    void restoreLaneSpeedLimits();
     // per-lane speed and position features over every environment (EngineHost::laneFeatures and its kin): outputs [R * L] /
     // [R * L * nBins], edges [L][nBins + 1] or [nBins + 1], shared by the environments
     std::vector<double> laneLengths() const;  // [L] of one environment
@@ -165,6 +174,7 @@ private:
     bool devicePhaseUnchecked_ = false;  // as EngineHost: read by every call below that has waited for the device
     void raiseDeviceError();             // (the caller holds queryMutex_)
     TlPlan plan_;                        // (every call with queryMutex_ held)
+    LaneLimits limits_;                  // (likewise)
 
     std::shared_ptr<HostRoadNet> net_ = std::make_shared<HostRoadNet>();
     std::vector<std::unique_ptr<Spawner>> spawners_;

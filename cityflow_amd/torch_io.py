@@ -76,6 +76,14 @@
     eng.set_tl_plan(...) / eng.get_tl_phase_durations_array()
                                                          the same over numpy arrays (wait for the device)
     eng.restore_tl_plan()                                the roadnet file's durations are in force again
+    eng.set_lane_speed_limits_tensor(limits, rejected=None)
+                                                         the lanes' speed limits as engine state: float64 [L] (VectorEngine: [R, L],
+                                                         one scheme per environment), NaN = keep; negative or infinite entries are
+                                                         left out and counted in int32 [1] `rejected`; one kernel launch, no host wait
+    eng.get_lane_speed_limits_tensor(out=None)           float64 [L]: the limits in force
+    eng.set_lane_speed_limits(limits) -> int / eng.get_lane_speed_limits_array()
+                                                         the same over numpy arrays (wait for the device)
+    eng.restore_lane_speed_limits()                      the roadnet file's limits are in force again
 
 On the HIP engine the tensors live on the engine's GPU and nothing here waits for the device:
   * a getter's kernel writes the caller's tensor on the engine's stream after everything already enqueued there and on the
@@ -1032,6 +1040,88 @@ def restore_tl_plan(self):
     self._restore_tl_plan()
 
 
+def _lane_limit_shape(eng):
+    return tuple(eng._tensor_shapes()[0])
+
+
+def _need_lane_limit_calls(eng, what):
+    if not eng._lane_limit_calls():
+        raise NotImplementedError("%s: the backend %r does not keep the lanes' speed limits as engine state"
+                                  % (what, eng.backend_name()))
+
+
+def set_lane_speed_limits_tensor(self, limits, rejected=None):
+    """Set the lanes' speed limits (Lane::maxSpeed) from a float64 tensor [L] ([R, L] on a VectorEngine: one scheme per
+    environment) in lane_ids() order on the engine's device, read after everything enqueued on the current torch stream.  One
+    kernel launch on the engine's stream (and a 4-byte fill ahead of it where `rejected` is given); the call never waits for the
+    host and allocates nothing.  Entry by entry:
+
+        NaN                    keeps the lane's limit
+        finite and >= 0        applied bit for bit; 0.0 closes the lane; values above 30 are allowed (the reference only warns)
+        negative or infinite   not applied, counted in `rejected`; the other entries of the call are applied
+
+    `rejected`: an optional int32 [1] tensor on the engine's device, set to this call's count and valid on the current torch
+    stream.  A new limit takes effect in the next next_step() for every vehicle then on the lane — what the reference would do
+    if Lane::maxSpeed were changed between two steps.  It caps the speed the step computes and is no deceleration: a vehicle
+    that moves onto a slower lane during a step can hold a higher speed for that one step.  LaneLinks keep the reference's 10000.
+
+    The limits belong to the engine, like the roadnet: reset() keeps them; snapshot / load / load_from_file, vehicle compaction,
+    checkpoint() / rollback() (with envs too: every slot keeps its own) neither save nor change them — read them with
+    get_lane_speed_limits_tensor() and set them again to carry them over; restore_lane_speed_limits() brings the roadnet
+    file's back.  Every argument is checked before anything is enqueued; NotImplementedError on a backend without the call
+    (the CPU twin)."""
+    torch = _torch()
+    shape = _lane_limit_shape(self)
+    device = _engine_device(torch, self)
+    _check_buf(torch, limits, "limits", shape, torch.float64, device)
+    if rejected is not None:
+        _check_buf(torch, rejected, "rejected", (1,), torch.int32, device)
+    _need_lane_limit_calls(self, "set_lane_speed_limits_tensor")
+    self._set_lane_speed_limits_device(limits.data_ptr(), 0 if rejected is None else rejected.data_ptr(),
+                                       torch.cuda.current_stream(device).cuda_stream)
+
+
+def get_lane_speed_limits_tensor(self, out=None):
+    """The lanes' speed limits in force as a float64 tensor [L] ([R, L] on a VectorEngine) on the engine's device, valid on the
+    current torch stream (no host wait): the reading side of set_lane_speed_limits_tensor.  Every element is written.  `out`: a
+    contiguous float64 tensor of that shape, filled in place."""
+    torch = _torch()
+    shape = _lane_limit_shape(self)
+    device = _engine_device(torch, self)
+    if out is not None:
+        _check_buf(torch, out, "out", shape, torch.float64, device)
+    _need_lane_limit_calls(self, "get_lane_speed_limits_tensor")
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float64, device=device)
+    self._lane_speed_limits_device(out.data_ptr(), torch.cuda.current_stream(device).cuda_stream)
+    return out
+
+
+def set_lane_speed_limits(self, limits):
+    """set_lane_speed_limits_tensor from a numpy array (same shape and rules), through the engine's staging arena.  Waits for
+    the device and returns the number of rejected entries."""
+    import numpy as np
+
+    limits = _plan_array(limits, "limits", _lane_limit_shape(self), np.float64)
+    if limits is None:
+        raise TypeError("limits must be a floating array, not None")
+    _need_lane_limit_calls(self, "set_lane_speed_limits")
+    return int(self._set_lane_speed_limits(limits))
+
+
+def get_lane_speed_limits_array(self):
+    """get_lane_speed_limits_tensor as a numpy array; waits for the device."""
+    _need_lane_limit_calls(self, "get_lane_speed_limits_array")
+    return self._lane_speed_limits().reshape(_lane_limit_shape(self))
+
+
+def restore_lane_speed_limits(self):
+    """Put the roadnet file's speed limits back in force, for every environment.  Ordered on the engine's stream, no host
+    wait."""
+    _need_lane_limit_calls(self, "restore_lane_speed_limits")
+    self._restore_lane_speed_limits()
+
+
 def _need_checkpoint_calls(eng, what):
     why = eng._checkpoint_unsupported()
     if why:
@@ -1435,6 +1525,11 @@ def install(*classes):
         cls.set_tl_plan = set_tl_plan
         cls.get_tl_phase_durations_array = get_tl_phase_durations_array
         cls.restore_tl_plan = restore_tl_plan
+        cls.set_lane_speed_limits_tensor = set_lane_speed_limits_tensor
+        cls.get_lane_speed_limits_tensor = get_lane_speed_limits_tensor
+        cls.set_lane_speed_limits = set_lane_speed_limits
+        cls.get_lane_speed_limits_array = get_lane_speed_limits_array
+        cls.restore_lane_speed_limits = restore_lane_speed_limits
         cls.get_lane_vehicle_count_tensor = get_lane_vehicle_count_tensor
         cls.get_lane_waiting_vehicle_count_tensor = get_lane_waiting_vehicle_count_tensor
         cls.set_tl_phases_tensor = set_tl_phases_tensor

@@ -997,6 +997,33 @@ typedef int32_t (*cfx_get_tl_phase_durations_fn)(cfx_engine *e, double *out, int
 typedef int32_t (*cfx_restore_tl_plan_fn)(cfx_engine *e);
 typedef int32_t (*cfx_tl_plan_error_fn)(cfx_engine *e, int32_t *what, int32_t *inter, int32_t *phase, double *value);
 
+/* ---- The lanes' speed limits as engine state in device memory (OPTIONAL entry points, as above; all five or none; not on a
+ * tile: CFX_ERR_STATE).  The engine keeps two copies of the lanes' part of cfx_net::drv_max_speed (Lane::maxSpeed): the limits
+ * IN FORCE, which the car-following of every step reads once per vehicle (min2double(v, drivable->getMaxSpeed()),
+ * vehicle.cpp:314), and the FILE's, as cfx_create got them.  LaneLinks are not covered: they keep the reference's 10000.
+ * n must be n_lanes, else CFX_ERR_INVALID; with n_envs > 1 the array is environment-major, as the lanes are.
+ *   limits[l]  double: NaN keeps lane l's limit; a finite value >= 0 is in force, bit for bit, from the next cfx_step on for
+ *              every vehicle then on the lane (0.0 closes the lane; above 30 is allowed — the reference only warns); a negative
+ *              or infinite value is not applied and counted.  A limit caps the speed a step computes; it is no deceleration.
+ * Entries are judged one by one: a rejected entry leaves the others of the call applied.  cfx_reset, cfx_load_state and
+ * cfx_checkpoint_restore leave the limits in force alone.
+ *   "cfx_set_lane_speed_limits_device"  limits in device memory, applied by ONE kernel on the engine's stream, read after
+ *                                       everything enqueued on producer_stream (as cfx_set_tl_phases_device); rejected: NULL, or
+ *                                       one int32 in device memory that is set to this call's number of rejected entries (cleared
+ *                                       by a 4-byte fill ahead of the kernel) and is valid on producer_stream on return
+ *   "cfx_set_lane_speed_limits"         the same from host memory (rejected: NULL or one int32 in host memory); synchronous
+ *   "cfx_get_lane_speed_limits_device"  out[n_lanes]: the limits in force, every element written, ordered against
+ *                                       consumer_stream (as cfx_observe_device)
+ *   "cfx_get_lane_speed_limits"         the same into host memory; synchronous
+ *   "cfx_restore_lane_speed_limits"     the file's limits are in force again, in every environment (one kernel on the engine's
+ *                                       stream) */
+typedef int32_t (*cfx_set_lane_speed_limits_device_fn)(cfx_engine *e, const double *limits, int32_t n, int32_t *rejected,
+                                                       void *producer_stream);
+typedef int32_t (*cfx_set_lane_speed_limits_fn)(cfx_engine *e, const double *limits, int32_t n, int32_t *rejected);
+typedef int32_t (*cfx_get_lane_speed_limits_device_fn)(cfx_engine *e, double *out, int32_t n, void *consumer_stream);
+typedef int32_t (*cfx_get_lane_speed_limits_fn)(cfx_engine *e, double *out, int32_t n);
+typedef int32_t (*cfx_restore_lane_speed_limits_fn)(cfx_engine *e);
+
 /* ---- What the grids of the ring layout's latency cross kernel (kr_cross) did (OPTIONAL entry point, as above; a diagnostic:
  * results never depend on a grid).  A launch gives every queued vehicle a 16-lane group; the host sizes it from job counts the
  * device reported some steps ago, and a group of a grid that is too small takes a second vehicle when the first is through.
