@@ -202,6 +202,10 @@ struct cfx_engine {
     char *stage = nullptr;
     size_t stageBytes = 0;
     int32_t *rowTileSum = nullptr;  // cfx_observe_vehicles_device: the scan's tile totals [ceil(D / kRowTile)] (in `owned`)
+    // cfx_set_drivable_geometry: the polylines of ONE environment's drivables for that call's pose outputs (in `owned`; null
+    // until set).  Part of the network, not of the state: nothing that moves vehicles touches them
+    int32_t *geoStart = nullptr;    // [D / n_envs + 1]
+    GeoNode *geoNodes = nullptr;
     // cfx_set_vehicle_speeds_device / cfx_set_vehicle_speeds and cfx_set_vehicle_routes_device / cfx_set_vehicle_routes: the row
     // that commands each vehicle number [speedStampCap], all -1 between calls (in `owned`; vehicleStampEnsure)
     int32_t *speedStamp = nullptr;
@@ -4495,18 +4499,27 @@ int32_t cfx_observe_vehicles_device(cfx_engine *e, const cfx_vehicle_rows *rows,
         e->err = std::string(what) + ": n_rows must not be negative";
         return CFX_ERR_INVALID;
     }
-    if (a.n_rows == 0) a.vehicle = a.drivable = a.env = a.leader = nullptr, a.distance = a.speed = a.gap = nullptr;
-    const bool anyRow = a.vehicle || a.drivable || a.env || a.distance || a.speed || a.leader || a.gap;
+    if (a.n_rows == 0) {
+        a.vehicle = a.drivable = a.env = a.leader = nullptr, a.distance = a.speed = a.gap = nullptr;
+        a.x = a.y = a.dir_x = a.dir_y = a.length = a.width = nullptr;
+    }
+    const bool poses = a.x || a.y || a.dir_x || a.dir_y || a.length || a.width;
+    const bool anyRow = poses || a.vehicle || a.drivable || a.env || a.distance || a.speed || a.leader || a.gap;
     if (!a.start && !a.count && !anyRow) return CFX_ERR_INVALID;
     if (e->lc.on || e->tiled) {
         e->err = std::string(what) + ": not with lane change (shadows) and not on a tile";
+        return CFX_ERR_STATE;
+    }
+    if (poses && !e->geoNodes) {
+        e->err = std::string(what) + ": x, y, dir_x, dir_y, length and width need the drivables' polylines: call cfx_set_drivable_geometry first";
         return CFX_ERR_STATE;
     }
     auto fail = [e](const std::string &m) { return e->fail(m); };
     HIP_TRY(hipSetDevice(e->device));
     if ((rc = checkDevicePointers(e, what, {{a.start, "start"}, {a.count, "count"}, {a.vehicle, "vehicle"}, {a.drivable, "drivable"},
                                             {a.env, "env"}, {a.distance, "distance"}, {a.speed, "speed"}, {a.leader, "leader"},
-                                            {a.gap, "gap"}})))
+                                            {a.gap, "gap"}, {a.x, "x"}, {a.y, "y"}, {a.dir_x, "dir_x"}, {a.dir_y, "dir_y"},
+                                            {a.length, "length"}, {a.width, "width"}})))
         return rc;
     if ((rc = e->settle(false))) return rc;  // (ring layout: a commit deferred to the next step's admission)
     if ((rc = e->syncTables())) return rc;
@@ -4522,20 +4535,77 @@ int32_t cfx_observe_vehicles_device(cfx_engine *e, const cfx_vehicle_rows *rows,
     if (!e->rowTileSum && (rc = e->allocRaw(&e->rowTileSum, (size_t) o.nTiles))) return rc;
     o.tileSum = e->rowTileSum;
     const int padBlocks = anyRow ? (int) (((size_t) a.n_rows + kRowPadRows - 1) / kRowPadRows) : 0;
+    const VehPoseOut g{a.x, a.y, a.dir_x, a.dir_y, a.length, a.width, e->geoStart, e->geoNodes};
     if ((rc = e->orderAfterCaller((hipStream_t) consumerStream))) return rc;
     if (e->ring) {
         const RingCtx c = e->rctx();
         hipLaunchKernelGGL(k_vehicle_tile_sums, dim3(o.nTiles), dim3(kBlock), 0, e->stream, (const int32_t *) c.cnt, c.n.L, o);
-        hipLaunchKernelGGL(kr_vehicle_rows, dim3(o.nTiles + padBlocks), dim3(kBlock), 0, e->stream, c, o);
+        if (poses) hipLaunchKernelGGL(kr_vehicle_poses, dim3(o.nTiles + padBlocks), dim3(kBlock), 0, e->stream, c, o, g);
+        else hipLaunchKernelGGL(kr_vehicle_rows, dim3(o.nTiles + padBlocks), dim3(kBlock), 0, e->stream, c, o);
     } else {
         const StepCtx c = e->ctx();
         hipLaunchKernelGGL(k_vehicle_tile_sums, dim3(o.nTiles), dim3(kBlock), 0, e->stream, (const int32_t *) c.cnt, c.n.L, o);
-        hipLaunchKernelGGL(kd_vehicle_rows, dim3(o.nTiles + padBlocks), dim3(kBlock), 0, e->stream, c, o);
+        if (poses) hipLaunchKernelGGL(kd_vehicle_poses, dim3(o.nTiles + padBlocks), dim3(kBlock), 0, e->stream, c, o, g);
+        else hipLaunchKernelGGL(kd_vehicle_rows, dim3(o.nTiles + padBlocks), dim3(kBlock), 0, e->stream, c, o);
     }
     HIP_TRY(hipGetLastError());
     if ((rc = e->orderCallerAfter((hipStream_t) consumerStream))) return rc;
     e->deviceObserved();  // (tiles were refused above)
     return CFX_OK;
+}
+
+// ---- the drivables' polylines for the pose outputs above (an optional entry point of include/cityflow_amd.h): the table is
+// checked, turned into GeoNode records — segment lengths, their left-to-right sum and the unit vectors, in the reference's
+// expressions and order (this file is compiled without contraction, and the host's sqrt and division round correctly) — and
+// uploaded.  The kernels trust point_start, so nothing is uploaded that has not passed the checks
+int32_t cfx_set_drivable_geometry(cfx_engine *e, const cfx_drivable_geometry *geometry);
+static_assert(std::is_same<decltype(&cfx_set_drivable_geometry), cfx_set_drivable_geometry_fn>::value, "cfx_set_drivable_geometry");
+
+int32_t cfx_set_drivable_geometry(cfx_engine *e, const cfx_drivable_geometry *geometry) {
+    const char *what = "cfx_set_drivable_geometry";
+    cfx_drivable_geometry a{};
+    int rc;
+    if ((rc = takeDescriptor(e, geometry, &a, what))) return rc;
+    auto invalid = [&](const std::string &m) {
+        e->err = std::string(what) + ": " + m;
+        return CFX_ERR_INVALID;
+    };
+    if (e->tiled) {
+        e->err = std::string(what) + ": not on a tile";
+        return CFX_ERR_STATE;
+    }
+    const int nEnvs = e->cfg.n_envs > 1 ? e->cfg.n_envs : 1;
+    const int D = e->D / nEnvs;
+    if (!a.point_start || !a.xy) return invalid("point_start and xy must be given");
+    if (a.n_drivables != D) return invalid("n_drivables must be the " + std::to_string(D) + " drivables of one environment");
+    if (a.point_start[0] != 0 || a.point_start[D] != a.n_points) return invalid("point_start must run from 0 to n_points");
+    for (int d = 0; d < D; ++d)
+        if (a.point_start[d + 1] - (int64_t) a.point_start[d] < 2 || a.point_start[d + 1] > a.n_points)
+            return invalid("drivable " + std::to_string(d) + " needs at least two points inside the table");
+    std::vector<GeoNode> nodes((size_t) a.n_points);
+    for (int d = 0; d < D; ++d) {
+        const int p0 = a.point_start[d], p1 = a.point_start[d + 1];
+        double total = 0.0;
+        for (int p = p0; p < p1; ++p) {
+            GeoNode &n = nodes[(size_t) p];
+            n = GeoNode{};
+            n.x = a.xy[2 * (size_t) p], n.y = a.xy[2 * (size_t) p + 1];
+            if (p + 1 == p1) break;
+            const double dx = a.xy[2 * (size_t) p + 2] - n.x, dy = a.xy[2 * (size_t) p + 3] - n.y;
+            n.len = sqrt(dx * dx + dy * dy);
+            n.ux = dx / n.len, n.uy = dy / n.len;
+            total += n.len;
+        }
+        nodes[(size_t) p1 - 1].len = total;
+    }
+    auto fail = [e](const std::string &m) { return e->fail(m); };
+    HIP_TRY(hipSetDevice(e->device));
+    if (e->geoNodes) {  // a second call: the kernels of the first may still read the old table
+        HIP_TRY(hipStreamSynchronize(e->stream));
+        if ((rc = e->freeRaw(&e->geoStart)) || (rc = e->freeRaw(&e->geoNodes))) return rc;
+    }
+    if ((rc = e->upload(&e->geoStart, a.point_start, (size_t) D + 1))) return rc;
+    return e->upload(&e->geoNodes, nodes.data(), nodes.size());
 }
 
 // ---- speed commands for many vehicles at once (optional entry points of include/cityflow_amd.h, as above): k_speeds_claim,

@@ -2670,6 +2670,61 @@ struct VehRowsOut {
     int nTiles;
 };
 
+// The pose outputs of the same call (x, y, dir_x, dir_y, length, width of include/cityflow_amd.h), written by kernels of their
+// own — kr_/kd_vehicle_poses, the same body with Poses = true — so that a call without them launches what it always did.
+// The polylines (cfx_set_drivable_geometry) are ONE environment's: the rows' drivable number indexes them whatever the
+// environment.  Node i of a polyline is point i and the segment from it to point i + 1, the segment's length and unit vector
+// worked out once at upload with the reference's expressions; what is left to the device are the two walks of the replay
+// writer (host/polyline.h has them with the reference's lines), kept apart because they differ at a segment boundary: the
+// point moves on while `dis > l`, the direction stops at the first `remain < l`.  The group that holds a drivable stages a
+// polyline of up to kGeoStage points in LDS, a point per thread (lanes have 2-3 points, generated curves 11); a longer one
+// is walked in global memory.
+constexpr int kGeoStage = kFeatGroup;
+struct __align__(16) GeoNode {
+    double x, y;
+    double len;     // sqrt(dx * dx + dy * dy) of the segment; in a polyline's LAST node the sum of them, left to right
+    double ux, uy;  // {dx / len, dy / len} (nothing in the last node)
+    double pad;
+};
+struct VehPoseOut {
+    double *x, *y, *dirX, *dirY, *length, *width;
+    const int32_t *geoStart;  // [D + 1]
+    const GeoNode *geo;
+};
+
+// getPointByDistance (roadnet.cpp:17-29) and Drivable::getDirectionByDistance (roadnet.cpp:400-411) over nodes[0 .. nPts)
+__device__ __forceinline__ void vehiclePose(const GeoNode *nodes, int nPts, double dis0, double *px, double *py, double *ux, double *uy) {
+    const double total = nodes[nPts - 1].len;
+    const double lo = dis0 > 0 ? dis0 : 0;  // max2double(dis, 0)
+    double dis = lo < total ? lo : total;   // min2double(., length)
+    double x = nodes[0].x, y = nodes[0].y;
+    if (!(dis <= 0.0)) {
+        int i = 1;
+        for (; i < nPts; ++i) {
+            const double l = nodes[i - 1].len;
+            if (!(dis > l)) break;
+            dis -= l;
+        }
+        if (i < nPts) {
+            const double l = nodes[i - 1].len, k = dis / l;
+            const double x0 = nodes[i - 1].x, y0 = nodes[i - 1].y;
+            x = x0 + (nodes[i].x - x0) * k;
+            y = y0 + (nodes[i].y - y0) * k;
+        } else {
+            x = nodes[nPts - 1].x, y = nodes[nPts - 1].y;
+        }
+    }
+    *px = x, *py = y;
+    double remain = dis0;
+    int seg = 0;
+    for (; seg < nPts - 2; ++seg) {  // (beyond the end: the last segment's)
+        const double l = nodes[seg].len;
+        if (remain < l) break;
+        remain -= l;
+    }
+    *ux = nodes[seg].ux, *uy = nodes[seg].uy;
+}
+
 // position -> the device's drivable index (L = lanes of all environments)
 __device__ __forceinline__ int rowsDrivable(const VehRowsOut &o, int L, int env, int d) {
     return d < o.lanesPerEnv ? env * o.lanesPerEnv + d : L + env * o.linksPerEnv + (d - o.lanesPerEnv);
@@ -2724,10 +2779,12 @@ __global__ void __launch_bounds__(kBlock) k_vehicle_tile_sums(const int32_t *cnt
 }
 
 // The second launch's body.  drv(d) = the layout's view of device drivable d: drv(d).rec(k) = {dis, speed}, .vid(k) = the
-// vehicle number and .lead(k, dis, &gap) = the leader's vehicle number (-1: none) of its k-th vehicle from the front.
-template <typename Drv>
-__device__ __forceinline__ void vehicleRows(const VehRowsOut o, const int32_t *cnt, int L, Drv drv) {
+// vehicle number, .lead(k, dis, &gap) = the leader's vehicle number (-1: none) and .tmpl(k) = the template of its k-th
+// vehicle from the front.  Poses: the pose outputs `g` beside the others (without: `g` is not read).
+template <bool Poses, typename Drv>
+__device__ __forceinline__ void vehicleRows(const VehRowsOut o, const VehPoseOut g, const int32_t *cnt, int L, Drv drv) {
     __shared__ int sStart[kRowTile + 1];
+    __shared__ GeoNode sGeo[Poses ? kBlock / kFeatGroup * kGeoStage : 1];  // a group's polyline (Poses alone)
     __shared__ int sWave[kBlock / 64];
     __shared__ int sBase[2];
     const int t = (int) threadIdx.x, b = (int) blockIdx.x;
@@ -2745,7 +2802,7 @@ __device__ __forceinline__ void vehicleRows(const VehRowsOut o, const int32_t *c
         }
         if (t == 0) sBase[0] = before, sBase[1] = all;
     }
-    const bool rows = o.vehicle || o.drivable || o.env || o.distance || o.speed || o.leader || o.gap;
+    const bool rows = Poses || o.vehicle || o.drivable || o.env || o.distance || o.speed || o.leader || o.gap;
     if (b >= o.nTiles) {  // padding
         __syncthreads();
         const int count = sBase[1];
@@ -2760,6 +2817,14 @@ __device__ __forceinline__ void vehicleRows(const VehRowsOut o, const int32_t *c
             if (o.speed) o.speed[row] = 0.0;
             if (o.leader) o.leader[row] = -1;
             if (o.gap) o.gap[row] = 0.0;
+            if constexpr (Poses) {
+                if (g.x) g.x[row] = __builtin_nan("");
+                if (g.y) g.y[row] = __builtin_nan("");
+                if (g.dirX) g.dirX[row] = 0.0;
+                if (g.dirY) g.dirY[row] = 0.0;
+                if (g.length) g.length[row] = 0.0;
+                if (g.width) g.width[row] = 0.0;
+            }
         }
         return;
     }
@@ -2798,10 +2863,44 @@ __device__ __forceinline__ void vehicleRows(const VehRowsOut o, const int32_t *c
         if (n == 0) continue;
         const int env = p / D, d = p - env * D;
         const auto view = drv(rowsDrivable(o, L, env, d));
+        [[maybe_unused]] const GeoNode *nodes = nullptr;  // the drivable's polyline; nPts <= kGeoStage: the group's LDS copy
+        [[maybe_unused]] int nPts = 0;
+        [[maybe_unused]] const bool geometry = Poses && (g.x || g.y || g.dirX || g.dirY);
+        if constexpr (Poses) {
+            if (geometry) {
+                const int g0 = g.geoStart[d];
+                nPts = g.geoStart[d + 1] - g0;
+                nodes = g.geo + g0;
+                if (nPts <= kGeoStage) {
+                    GeoNode *mine = sGeo + (t / kFeatGroup) * kGeoStage;
+                    if (sub < nPts) mine[sub] = nodes[sub];
+                    waveLdsOrder();
+                }
+            }
+        }
         for (int first = 0; first < n; first += kFeatGroup) {
             const int k = first + sub, row = row0 + k;
             if (k >= n || row >= o.nRows) continue;
             const double2 r = view.rec(k);
+            if constexpr (Poses) {
+                if (geometry) {
+                    double x, y, ux, uy;
+                    if (nPts <= kGeoStage) {
+                        vehiclePose(sGeo + (t / kFeatGroup) * kGeoStage, nPts, r.x, &x, &y, &ux, &uy);
+                    } else {
+                        vehiclePose(nodes, nPts, r.x, &x, &y, &ux, &uy);
+                    }
+                    if (g.x) g.x[row] = x;
+                    if (g.y) g.y[row] = y;
+                    if (g.dirX) g.dirX[row] = ux;
+                    if (g.dirY) g.dirY[row] = uy;
+                }
+                if (g.length || g.width) {
+                    const cfx_vehicle_template &tp = view.tmpl(k);
+                    if (g.length) g.length[row] = tp.len;
+                    if (g.width) g.width[row] = tp.width;
+                }
+            }
             if (o.vehicle) o.vehicle[row] = view.vid(k);
             if (o.drivable) o.drivable[row] = d;
             if (o.env) o.env[row] = env;
@@ -2814,6 +2913,9 @@ __device__ __forceinline__ void vehicleRows(const VehRowsOut o, const int32_t *c
                 if (o.gap) o.gap[row] = leader >= 0 ? gap : 0.0;
             }
         }
+        if constexpr (Poses) {
+            if (geometry && nPts <= kGeoStage) waveLdsOrder();  // (the group's next drivable overwrites the stage)
+        }
     }
 }
 
@@ -2823,6 +2925,7 @@ struct DenseDrvRows {
     int d, base;
     __device__ __forceinline__ double2 rec(int k) const { return make_double2(c.s.dis[base + k], c.s.speed[base + k]); }
     __device__ __forceinline__ int vid(int k) const { return c.s.vid[base + k]; }
+    __device__ __forceinline__ const cfx_vehicle_template &tmpl(int k) const { return c.t.templ[c.s.templ[base + k]]; }
     __device__ __forceinline__ int lead(int k, double dis, double *gap) const {
         const int s = base + k;
         const int ls = findLeader(c, c.t.templ, s, d, k == 0, dis, c.t.templ[c.s.templ[s]].approach_dist, gap);
@@ -2832,7 +2935,10 @@ struct DenseDrvRows {
     }
 };
 __global__ void __launch_bounds__(kBlock) kd_vehicle_rows(StepCtx c, VehRowsOut o) {
-    vehicleRows(o, c.cnt, c.n.L, [&](int d) { return DenseDrvRows{c, d, c.segStart[d]}; });
+    vehicleRows<false>(o, VehPoseOut{}, c.cnt, c.n.L, [&](int d) { return DenseDrvRows{c, d, c.segStart[d]}; });
+}
+__global__ void __launch_bounds__(kBlock) kd_vehicle_poses(StepCtx c, VehRowsOut o, VehPoseOut g) {
+    vehicleRows<true>(o, g, c.cnt, c.n.L, [&](int d) { return DenseDrvRows{c, d, c.segStart[d]}; });
 }
 
 // cfx_lane_flow_enable: per-lane flow and waiting-time statistics across steps (include/cityflow_amd.h has the rules).  One TICK

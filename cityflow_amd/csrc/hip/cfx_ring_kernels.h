@@ -2416,6 +2416,7 @@ struct RingDrvRows {
     RingLaneRec kin;
     __device__ __forceinline__ double2 rec(int k) const { return kin(k); }
     __device__ __forceinline__ int vid(int k) const { return c.s.vid[ringSlot(kin.geo, kin.head, k)]; }
+    __device__ __forceinline__ const cfx_vehicle_template &tmpl(int k) const { return c.t.templ[c.meta[ringSlot(kin.geo, kin.head, k)].x]; }
     __device__ __forceinline__ int lead(int k, double dis, double *gap) const {
         const int s = ringSlot(kin.geo, kin.head, k);
         const int4 mv = c.meta[s];
@@ -2432,7 +2433,10 @@ struct RingDrvRows {
     }
 };
 __global__ void __launch_bounds__(kBlock) kr_vehicle_rows(RingCtx c, VehRowsOut o) {
-    vehicleRows(o, c.cnt, c.n.L, [&](int d) { return RingDrvRows{c, d, laneRec(c, d)}; });
+    vehicleRows<false>(o, VehPoseOut{}, c.cnt, c.n.L, [&](int d) { return RingDrvRows{c, d, laneRec(c, d)}; });
+}
+__global__ void __launch_bounds__(kBlock) kr_vehicle_poses(RingCtx c, VehRowsOut o, VehPoseOut g) {
+    vehicleRows<true>(o, g, c.cnt, c.n.L, [&](int d) { return RingDrvRows{c, d, laneRec(c, d)}; });
 }
 
 // cfx_lane_flow_enable, ring layout: laneFlowTick (cfx_kernels.h) over the lane's ring, the vehicle numbers from the cold `vid` column

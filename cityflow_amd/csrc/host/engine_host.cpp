@@ -9,6 +9,7 @@
 #include <stdexcept>
 
 #include "json.h"
+#include "polyline.h"
 
 namespace cfa {
 
@@ -96,6 +97,7 @@ void Backend::open(const std::string &libPath) {
     CFX_FN_OPTIONAL(cfx_observe_lane_obs_device)
     CFX_FN_OPTIONAL(cfx_get_lane_obs)
     CFX_FN_OPTIONAL(cfx_observe_vehicles_device)
+    CFX_FN_OPTIONAL(cfx_set_drivable_geometry)
     CFX_FN_OPTIONAL(cfx_set_vehicle_speeds_device)
     CFX_FN_OPTIONAL(cfx_set_vehicle_speeds)
     CFX_FN_OPTIONAL(cfx_get_waiting_custom_speeds)
@@ -790,15 +792,63 @@ VehicleRows vehicleRowsOf(const Backend &be, cfx_engine *dev, int nEnvs, int nLa
     return out;
 }
 
-VehicleRows EngineHost::vehicleRows() {
+DrivableGeometry drivableGeometryOf(const HostRoadNet &net) {
+    DrivableGeometry g;
+    g.pointStart.reserve(net.lanes.size() + net.laneLinks.size() + 1);
+    g.pointStart.push_back(0);
+    auto take = [&g](const std::vector<Pt> &points) {
+        for (const Pt &p : points) g.xy.push_back(p.x), g.xy.push_back(p.y);
+        g.pointStart.push_back((int32_t) (g.xy.size() / 2));
+    };
+    for (const HostLane &lane : net.lanes) take(lane.points);
+    for (const HostLaneLink &ll : net.laneLinks) take(ll.points);
+    return g;
+}
+
+void vehiclePosesOf(VehicleRows &rows, const HostRoadNet &net, const std::function<const cfx_vehicle_template &(int32_t)> &templateOf) {
+    const size_t n = (size_t) rows.count;
+    const int L = (int) net.lanes.size();
+    for (auto *c : {&rows.x, &rows.y, &rows.dirX, &rows.dirY, &rows.length, &rows.width}) c->resize(n);
+    for (size_t i = 0; i < n; ++i) {
+        const int d = rows.drivable[i];
+        const std::vector<Pt> &pts = d < L ? net.lanes[(size_t) d].points : net.laneLinks[(size_t) (d - L)].points;
+        const Pt pos = pointByDistance(pts, rows.distance[i]), dir = directionByDistance(pts, rows.distance[i]);
+        const cfx_vehicle_template &t = templateOf(rows.vehicle[i]);
+        rows.x[i] = pos.x, rows.y[i] = pos.y;
+        rows.dirX[i] = dir.x, rows.dirY[i] = dir.y;
+        rows.length[i] = t.len, rows.width[i] = t.width;
+    }
+}
+
+void uploadDrivableGeometryOf(const Backend &be, cfx_engine *dev, const HostRoadNet &net) {
+    if (!be.hasVehiclePoses()) throw std::runtime_error("cityflow_amd: '" + be.path + "' has no device-side vehicle poses");
+    const DrivableGeometry g = drivableGeometryOf(net);
+    cfx_drivable_geometry a{};
+    a.struct_size = (int32_t) sizeof a;
+    a.n_drivables = (int32_t) g.pointStart.size() - 1;
+    a.n_points = g.pointStart.back();
+    a.point_start = g.pointStart.data();
+    a.xy = g.xy.data();
+    if (be.cfx_set_drivable_geometry(dev, &a) != CFX_OK) backendFail(be, dev, "cfx_set_drivable_geometry");
+}
+
+VehicleRows EngineHost::vehicleRows(bool poses) {
     if (laneChange_) throw std::runtime_error("observe_vehicles: not with laneChange (a shadow is a second row of its vehicle)");
     VehicleRows rows = vehicleRowsOf(be_, dev_, 1, (int) net_->lanes.size(), (int) net_->laneLinks.size());
     raiseDeviceError();
+    if (poses)
+        vehiclePosesOf(rows, *net_, [this](int32_t vid) -> const cfx_vehicle_template & {
+            return spawner_.templates[(size_t) spawner_.vehicles.at((size_t) vid).templ];
+        });
     return rows;
 }
 
 void EngineHost::observeVehiclesDevice(const cfx_vehicle_rows &rows, uintptr_t consumerStream) {
     if (laneChange_) throw std::runtime_error("observe_vehicles: not with laneChange (a shadow is a second row of its vehicle)");
+    if (wantsPoses(rows) && !geometryUploaded_) {
+        uploadDrivableGeometryOf(be_, dev_, *net_);
+        geometryUploaded_ = true;
+    }
     observeVehiclesDeviceOf(be_, dev_, rows, consumerStream);
 }
 

@@ -7,6 +7,7 @@
 // There is no CPU fallback: if the library cannot be loaded or cfx_create fails the constructor throws.
 #pragma once
 
+#include <functional>
 #include <map>
 #include <memory>
 #include <string>
@@ -91,6 +92,9 @@ struct Backend {
     cfx_get_lane_obs_fn cfx_get_lane_obs = nullptr;
     // optional on its own: per-vehicle rows in device memory (without it the host fills them from cfx_get_vehicles: vehicleRowsOf)
     cfx_observe_vehicles_device_fn cfx_observe_vehicles_device = nullptr;
+    // optional beside it: the drivables' polylines for that call's pose outputs (without it the host computes them: vehiclePosesOf)
+    cfx_set_drivable_geometry_fn cfx_set_drivable_geometry = nullptr;
+    bool hasVehiclePoses() const { return hasDeviceBuffers() && cfx_observe_vehicles_device && cfx_set_drivable_geometry; }
     // optional as a pair: speed commands for many vehicles at once (without them the host commands row by row: setVehicleSpeedsOf)
     cfx_set_vehicle_speeds_device_fn cfx_set_vehicle_speeds_device = nullptr;
     cfx_set_vehicle_speeds_fn cfx_set_vehicle_speeds = nullptr;
@@ -292,8 +296,22 @@ VehicleColumns vehicleColumnsOf(const Backend &be, cfx_engine *dev, bool vid, bo
 struct VehicleRows {
     std::vector<int32_t> start, vehicle, drivable, env, leader;
     std::vector<double> distance, speed, gap;
+    std::vector<double> x, y, dirX, dirY, length, width;  // the pose columns: empty until vehiclePosesOf fills them
     int count = 0;
 };
+// The polylines of ONE environment's drivables, lanes first and then laneLinks (the rows' drivable numbering): drivable d has
+// the points pointStart[d] .. pointStart[d + 1] - 1 of xy ({x, y} pairs), exactly the doubles the loader computed.
+struct DrivableGeometry {
+    std::vector<int32_t> pointStart;  // [D + 1]
+    std::vector<double> xy;           // [2 * P]
+};
+DrivableGeometry drivableGeometryOf(const HostRoadNet &net);
+// The pose columns of `rows` from its drivable and distance columns (host/polyline.h: the replay writer's two walks) and the
+// template of every row's vehicle (templateOf(vehicle number)); what the twin returns and the device's kernels are compared with.
+void vehiclePosesOf(VehicleRows &rows, const HostRoadNet &net, const std::function<const cfx_vehicle_template &(int32_t)> &templateOf);
+// cfx_set_drivable_geometry with the network's polylines, once per engine: the first call that gives a pose pointer
+void uploadDrivableGeometryOf(const Backend &be, cfx_engine *dev, const HostRoadNet &net);
+inline bool wantsPoses(const cfx_vehicle_rows &r) { return r.x || r.y || r.dir_x || r.dir_y || r.length || r.width; }
 // ... on any backend, from cfx_get_vehicles (nLanes / nLaneLinks: of ONE environment; throws std::runtime_error)
 VehicleRows vehicleRowsOf(const Backend &be, cfx_engine *dev, int nEnvs, int nLanes, int nLaneLinks);
 // ... into device memory: every pointer of `rows` a device address (cfx_observe_vehicles_device)
@@ -440,8 +458,10 @@ public:
     void laneFronts(int k, const LaneFronts &out);
     // ---- every running vehicle as a row (VehicleRows above; std::runtime_error with laneChange: shadows)
     bool vehicleRowsDevice() const { return be_.hasDeviceBuffers() && be_.cfx_observe_vehicles_device; }
+    bool vehiclePosesDevice() const { return be_.hasVehiclePoses(); }  // (... its pose outputs too)
     std::pair<int, int> drivableCounts() const { return {(int) net_->lanes.size(), (int) net_->laneLinks.size()}; }
-    VehicleRows vehicleRows();
+    DrivableGeometry drivableGeometry() const { return drivableGeometryOf(*net_); }
+    VehicleRows vehicleRows(bool poses = false);
     void observeVehiclesDevice(const cfx_vehicle_rows &rows, uintptr_t consumerStream);
     // ---- speed commands for many vehicles at once, by the vehicle numbers of the rows above (setVehicleSpeedsOf above;
     //      std::runtime_error with laneChange).  A command the device takes for a vehicle still in its entry buffer is not
@@ -578,6 +598,7 @@ private:
     size_t compactAt_ = 3500000, nextCompactAt_ = 3500000;
     bool compactAuto_ = true;
     int64_t vehicleCompactions_ = 0;
+    bool geometryUploaded_ = false;  // cfx_set_drivable_geometry was called (the first pose output asked for in device memory)
     bool laneHistory_ = false;  // "cfx": {"laneHistory": ...}; not said: kept on the ring layout up to 20 k lanes, not with lane change
     ReplayWriter replay_;
     void updateLog();  // Engine::updateLog engine.cpp:518-554

@@ -401,14 +401,21 @@ void observeLanesDevice(E &e, uintptr_t counts, uintptr_t waiting, uintptr_t spe
 }
 
 // ---- every running vehicle as a row (Engine and VectorEngine; the public calls are cityflow_amd/torch_io.py)
-template <typename E> py::tuple vehicleRowsTuple(E &e) {
-    const cfa::VehicleRows r = e.vehicleRows();
-    return py::make_tuple(toArray(r.start), r.count, toArray(r.vehicle), toArray(r.drivable), toArray(r.env), toArray(r.distance),
-                          toArray(r.speed), toArray(r.leader), toArray(r.gap));
+template <typename E> py::tuple vehicleRowsTuple(E &e, bool poses) {
+    const cfa::VehicleRows r = e.vehicleRows(poses);
+    py::tuple t = py::make_tuple(toArray(r.start), r.count, toArray(r.vehicle), toArray(r.drivable), toArray(r.env), toArray(r.distance),
+                                 toArray(r.speed), toArray(r.leader), toArray(r.gap));
+    if (!poses) return t;
+    return t + py::make_tuple(toArray(r.x), toArray(r.y), toArray(r.dirX), toArray(r.dirY), toArray(r.length), toArray(r.width));
+}
+template <typename E> py::tuple drivableGeometryTuple(E &e) {
+    const cfa::DrivableGeometry g = e.drivableGeometry();
+    return py::make_tuple(toArray(g.pointStart), toArray(g.xy));
 }
 template <typename E>
 void observeVehiclesDevice(E &e, uintptr_t start, uintptr_t count, uintptr_t vehicle, uintptr_t drivable, uintptr_t env, uintptr_t distance,
-                           uintptr_t speed, uintptr_t leader, uintptr_t gap, int nRows, uintptr_t consumerStream) {
+                           uintptr_t speed, uintptr_t leader, uintptr_t gap, int nRows, uintptr_t consumerStream, uintptr_t x, uintptr_t y,
+                           uintptr_t dirX, uintptr_t dirY, uintptr_t length, uintptr_t width) {
     cfx_vehicle_rows a{};
     a.struct_size = (int32_t) sizeof a;
     a.n_rows = nRows;
@@ -421,6 +428,12 @@ void observeVehiclesDevice(E &e, uintptr_t start, uintptr_t count, uintptr_t veh
     a.speed = (double *) speed;
     a.leader = (int32_t *) leader;
     a.gap = (double *) gap;
+    a.x = (double *) x;
+    a.y = (double *) y;
+    a.dir_x = (double *) dirX;
+    a.dir_y = (double *) dirY;
+    a.length = (double *) length;
+    a.width = (double *) width;
     e.observeVehiclesDevice(a, consumerStream);
 }
 
@@ -613,11 +626,15 @@ template <typename E> void defDeviceBuffers(py::class_<E> &c) {
         .def("_vehicle_rows_device", &E::vehicleRowsDevice, "the backend writes the vehicle rows in device memory")
         .def("_drivable_counts", &E::drivableCounts, "(lanes, laneLinks) of one environment")
         .def("_lane_change", &E::laneChange)
-        .def("_vehicle_rows", [](E &e) { return vehicleRowsTuple(e); },
+        .def("_vehicle_poses_device", &E::vehiclePosesDevice, "the backend writes the pose columns of the vehicle rows in device memory")
+        .def("_vehicle_rows", [](E &e, bool poses) { return vehicleRowsTuple(e, poses); }, "poses"_a = false,
              "(start, count, vehicle, drivable, env, distance, speed, leader, gap): every running vehicle as a row, environment-"
-             "major, `start` flat [envs * (D + 1)]; waits for the device")
+             "major, `start` flat [envs * (D + 1)]; with `poses` also (x, y, dir_x, dir_y, length, width); waits for the device")
+        .def("_drivable_geometry", [](E &e) { return drivableGeometryTuple(e); },
+             "(point_start int32 [D + 1], xy float64 [2 * P]): the polylines of one environment's drivables, lanes first")
         .def("_observe_vehicles_device", &observeVehiclesDevice<E>, "start_ptr"_a, "count_ptr"_a, "vehicle_ptr"_a, "drivable_ptr"_a,
-             "env_ptr"_a, "distance_ptr"_a, "speed_ptr"_a, "leader_ptr"_a, "gap_ptr"_a, "n_rows"_a, "consumer_stream"_a)
+             "env_ptr"_a, "distance_ptr"_a, "speed_ptr"_a, "leader_ptr"_a, "gap_ptr"_a, "n_rows"_a, "consumer_stream"_a, "x_ptr"_a = 0,
+             "y_ptr"_a = 0, "dir_x_ptr"_a = 0, "dir_y_ptr"_a = 0, "length_ptr"_a = 0, "width_ptr"_a = 0)
         .def("_vehicle_speeds_device", &E::vehicleSpeedsDevice, "the backend takes vehicle speed commands from device memory")
         .def("_set_vehicle_speeds_device", &E::setVehicleSpeedsDevice, "vehicle_ptr"_a, "speed_ptr"_a, "n"_a, "ignored_ptr"_a,
              "producer_stream"_a)

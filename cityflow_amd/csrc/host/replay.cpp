@@ -5,6 +5,7 @@
 #include <cmath>
 
 #include "engine_host.h"
+#include "polyline.h"
 
 namespace cfa {
 
@@ -34,32 +35,6 @@ void quoted(std::string &out, const std::string &s) {
         out.push_back(c);
     }
     out.push_back('"');
-}
-
-// getPointByDistance roadnet.cpp:17-29
-Pt pointByDistance(const std::vector<Pt> &points, double dis) {
-    double total = 0.0;
-    for (size_t i = 0; i + 1 < points.size(); ++i) total += len(sub(points[i + 1], points[i]));
-    double lo = dis > 0 ? dis : 0;  // max2double(dis, 0)
-    dis = lo < total ? lo : total;  // min2double(., length)
-    if (dis <= 0.0) return points[0];
-    for (size_t i = 1; i < points.size(); ++i) {
-        double l = len(sub(points[i - 1], points[i]));
-        if (dis > l) dis -= l;
-        else return add(points[i - 1], mul(sub(points[i], points[i - 1]), dis / l));
-    }
-    return points.back();
-}
-
-// Drivable::getDirectionByDistance roadnet.cpp:400-411
-Pt directionByDistance(const std::vector<Pt> &points, double dis) {
-    double remain = dis;
-    for (int i = 0; i + 1 < (int) points.size(); ++i) {
-        double l = len(sub(points[i + 1], points[i]));
-        if (remain < l) return unit(sub(points[i + 1], points[i]));
-        remain -= l;
-    }
-    return unit(sub(points[points.size() - 1], points[points.size() - 2]));
 }
 
 }  // namespace

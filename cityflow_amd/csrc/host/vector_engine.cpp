@@ -873,17 +873,28 @@ void VectorEngineHost::laneFronts(int k, const LaneFronts &out) {
     raiseDeviceError();
 }
 
-VehicleRows VectorEngineHost::vehicleRows() {
+VehicleRows VectorEngineHost::vehicleRows(bool poses) {
     if (laneChange_) throw std::runtime_error("observe_vehicles: not with laneChange (a shadow is a second row of its vehicle)");
+    if (poses && aheadEnabled_) waitAhead();  // (the numbering tables are the ahead thread's while it works)
     std::lock_guard<std::mutex> guard(queryMutex_);  // (the ABI is not re-entrant: the ahead thread may be asking the device)
     VehicleRows rows = vehicleRowsOf(be_, dev_, R_, L_, K_);
     raiseDeviceError();
+    if (poses)
+        vehiclePosesOf(rows, *net_, [this](int32_t vid) -> const cfx_vehicle_template & {
+            const auto &gl = globalToLocal_.at((size_t) vid);
+            const Spawner &sp = *spawners_[(size_t) gl.first];
+            return sp.templates[(size_t) sp.vehicles[(size_t) gl.second].templ];
+        });
     return rows;
 }
 
 void VectorEngineHost::observeVehiclesDevice(const cfx_vehicle_rows &rows, uintptr_t consumerStream) {
     if (laneChange_) throw std::runtime_error("observe_vehicles: not with laneChange (a shadow is a second row of its vehicle)");
     std::lock_guard<std::mutex> guard(queryMutex_);
+    if (wantsPoses(rows) && !geometryUploaded_) {
+        uploadDrivableGeometryOf(be_, dev_, *net_);
+        geometryUploaded_ = true;
+    }
     observeVehiclesDeviceOf(be_, dev_, rows, consumerStream);
 }
 

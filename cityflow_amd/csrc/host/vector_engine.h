@@ -96,9 +96,11 @@ public:
     void laneFronts(int k, const LaneFronts &out);  // [R * L * k] each
     // every running vehicle as a row, environment-major (EngineHost::vehicleRows and its kin); {L, K} of one environment
     bool vehicleRowsDevice() const { return be_.hasDeviceBuffers() && be_.cfx_observe_vehicles_device; }
+    bool vehiclePosesDevice() const { return be_.hasVehiclePoses(); }
     std::pair<int, int> drivableCounts() const { return {L_, K_}; }
+    DrivableGeometry drivableGeometry() const { return drivableGeometryOf(*net_); }  // one copy: the environments share the roadnet
     bool laneChange() const { return laneChange_; }
-    VehicleRows vehicleRows();
+    VehicleRows vehicleRows(bool poses = false);
     void observeVehiclesDevice(const cfx_vehicle_rows &rows, uintptr_t consumerStream);
     // speed commands by those vehicle numbers, vehicles of any environment in one call (EngineHost::setVehicleSpeeds and its kin)
     bool vehicleSpeedsDevice() const { return be_.hasDeviceBuffers() && be_.cfx_set_vehicle_speeds_device; }
@@ -169,6 +171,7 @@ private:
     void check(int32_t rc, const char *what);
     void rollbackTo(DeviceCheckpoint &ck, const std::vector<int32_t> *envs);  // (envs null: every environment its own state)
     bool laneHistory_ = false;
+    bool geometryUploaded_ = false;  // cfx_set_drivable_geometry was called (the first pose output asked for in device memory)
     std::unique_ptr<InterLayout> interLayout_;  // built by the first call that needs it
     Trackers trackers_;                  // (every call with queryMutex_ held: it asks the device)
     bool devicePhaseUnchecked_ = false;  // as EngineHost: read by every call below that has waited for the device

@@ -12,10 +12,13 @@
                                                          float64 [L, k] each: the k vehicles nearest every lane's end
     eng.get_lane_front_vehicles_array(k)                 the front outputs as numpy arrays (waits for the device)
     eng.observe_vehicles_tensor(start=None, count=None, vehicle=None, drivable=None, env=None, distance=None, speed=None,
-                                leader=None, gap=None)   every running vehicle as a row, grouped by drivable (CSR): int32
-                                                         start [D+1] ([R, D+1]) and count (0-dim), and rows [N] of the caller's N;
-                                                         two kernel launches, no host wait (see its docstring)
-    eng.observe_vehicles_array()                         the same outputs as numpy arrays, exactly `count` rows (waits for the device)
+                                leader=None, gap=None, x=None, y=None, dir_x=None, dir_y=None, length=None, width=None)
+                                                         every running vehicle as a row, grouped by drivable (CSR): int32
+                                                         start [D+1] ([R, D+1]) and count (0-dim), and rows [N] of the caller's N,
+                                                         its pose in the plane among them; two kernel launches, no host wait
+                                                         (see its docstring)
+    eng.observe_vehicles_array(poses=False)              the same outputs as numpy arrays, exactly `count` rows (waits for the device)
+    eng.drivable_geometry()                              {"point_start": int32 [D+1], "points": float64 [P, 2]}: the drivables' polylines
     eng.set_vehicle_speeds_tensor(vehicle, speed, ignored=None)
                                                          set_vehicle_speed() for the rows of int32 [N] vehicle numbers (those of
                                                          observe_vehicles_tensor) and float64 [N] speeds, NaN = leave alone;
@@ -1207,31 +1210,46 @@ rollback_envs.__name__ = rollback_envs.__qualname__ = "rollback"  # (VectorEngin
 VEHICLE_ROW_TILE = 256  # kRowTile: drivables per scan tile of the vehicle-row kernels
 VEHICLE_ROW_OUTPUTS = ("vehicle", "drivable", "env", "distance", "speed", "leader", "gap")
 VEHICLE_ROW_PADDING = {"vehicle": -1, "drivable": -1, "env": -1, "distance": -1.0, "speed": 0.0, "leader": -1, "gap": 0.0}
-_VEHICLE_ROW_FLOATS = ("distance", "speed", "gap")
+VEHICLE_POSE_OUTPUTS = ("x", "y", "dir_x", "dir_y", "length", "width")  # all float64
+VEHICLE_POSE_PADDING = {"x": float("nan"), "y": float("nan"), "dir_x": 0.0, "dir_y": 0.0, "length": 0.0, "width": 0.0}
+VEHICLE_ROW_PADDING.update(VEHICLE_POSE_PADDING)
+_VEHICLE_ROW_FLOATS = ("distance", "speed", "gap") + VEHICLE_POSE_OUTPUTS
 
 
-def _vehicle_rows(eng):
-    """The array form: {name: numpy array} of `start`, `count` and the seven row outputs with exactly `count` rows."""
+def _vehicle_rows(eng, poses=False):
+    """The array form: {name: numpy array} of `start`, `count` and the seven row outputs (with `poses`: and the six pose
+    outputs) with exactly `count` rows."""
     import numpy as np
 
     if eng._lane_change():
         raise RuntimeError("observe_vehicles: not with laneChange (a shadow is a second row of its vehicle)")
     lanes, links = eng._drivable_counts()
     lead = tuple(eng._tensor_shapes()[0])[:-1]
-    got = eng._vehicle_rows()
+    got = eng._vehicle_rows(True) if poses else eng._vehicle_rows()
     out = {"start": got[0].reshape(lead + (lanes + links + 1,)), "count": np.array(got[1], dtype=np.int32)}
-    out.update(zip(VEHICLE_ROW_OUTPUTS, got[2:]))
+    out.update(zip(VEHICLE_ROW_OUTPUTS + (VEHICLE_POSE_OUTPUTS if poses else ()), got[2:]))
     return out
 
 
-def observe_vehicles_array(self):
+def observe_vehicles_array(self, poses=False):
     """The outputs of observe_vehicles_tensor as a dict of numpy arrays (same names and dtypes): `start`, `count` (0-dim) and
-    the seven row outputs with exactly `count` rows, so no padding.  Waits for the device.  RuntimeError with laneChange."""
-    return _vehicle_rows(self)
+    the seven row outputs with exactly `count` rows, so no padding; with poses=True also `x`, `y`, `dir_x`, `dir_y`, `length`
+    and `width`, computed on the host.  Waits for the device.  RuntimeError with laneChange."""
+    return _vehicle_rows(self, poses)
+
+
+def drivable_geometry(self):
+    """The polylines the pose outputs of observe_vehicles_tensor walk: {"point_start": int32 [D+1], "points": float64 [P, 2]}.
+    Drivable d — the `drivable` column's numbering: lane_ids() first, then the laneLinks — has the points
+    points[point_start[d]:point_start[d+1]], at least two, exactly the doubles the loader computed (a lane: the road's points
+    moved sideways; a laneLink: the roadnet file's points or the generated curve).  A VectorEngine returns one copy: its
+    environments share the roadnet."""
+    start, xy = self._drivable_geometry()
+    return {"point_start": start, "points": xy.reshape(-1, 2)}
 
 
 def observe_vehicles_tensor(self, start=None, count=None, vehicle=None, drivable=None, env=None, distance=None, speed=None,
-                            leader=None, gap=None):
+                            leader=None, gap=None, x=None, y=None, dir_x=None, dir_y=None, length=None, width=None):
     """Every running vehicle — on a lane or on a laneLink inside an intersection — as one row of the given tensors, in CSR
     form, filled by two kernel launches on the engine's stream, ordered against the current torch stream as
     observe_lanes_tensor.  D = L + K drivables per environment: 0 .. L-1 are lane_ids(), L .. L+K-1 the laneLinks.
@@ -1257,6 +1275,18 @@ def observe_vehicles_tensor(self, start=None, count=None, vehicle=None, drivable
         gap       float64  the gap to the leader, 0.0 where leader is -1; a vehicle not stepped since a load
                            reports the loaded state's gap                                                     padding 0.0
 
+    and the POSE outputs, float64 [N] with the same N, where the vehicle is in the plane:
+
+        x, y          float64  the point at `distance` along the drivable's polyline (drivable_geometry()): what the replay
+                               file writes for the vehicle, to the bit                                        padding NaN
+        dir_x, dir_y  float64  the unit vector of the polyline's segment there (the last one beyond the end)  padding 0.0
+        length, width float64  of the vehicle (its flow's or push_vehicle's "length" and "width")             padding 0.0
+
+    No heading angle is produced: a device atan2 is not the host libm's, so it could not equal the replay file's angle to the
+    bit; torch.atan2(dir_y, dir_x) is the caller's to make.  A polyline whose last segment has length zero gives NaN in
+    dir_x and dir_y of a vehicle at its end, as on the host.  The first call that asks for a pose output uploads the polylines, once
+    per engine (that call waits for the copy); a call without them launches exactly what it did before they existed.
+
     Row i < min(count, N) is vehicle i; rows from count to N hold the padding; every element of every given tensor is
     written.  If count > N the rows beyond N are dropped and nothing is written outside a tensor.  The call never waits for
     the device, which is why N is the caller's and count stays on the device: size N once, e.g. from get_vehicle_count() with
@@ -1266,9 +1296,12 @@ def observe_vehicles_tensor(self, start=None, count=None, vehicle=None, drivable
     backend without device buffers takes CPU tensors and fills them from observe_vehicles_array().  RuntimeError with
     laneChange: true (a shadow would be a second row of its vehicle)."""
     torch = _torch()
-    rows = dict(zip(VEHICLE_ROW_OUTPUTS, (vehicle, drivable, env, distance, speed, leader, gap)))
+    rows = dict(zip(VEHICLE_ROW_OUTPUTS + VEHICLE_POSE_OUTPUTS,
+                    (vehicle, drivable, env, distance, speed, leader, gap, x, y, dir_x, dir_y, length, width)))
+    poses = any(rows[name] is not None for name in VEHICLE_POSE_OUTPUTS)
     if start is None and count is None and all(t is None for t in rows.values()):
-        raise ValueError("observe_vehicles_tensor: give at least one of start, count, " + ", ".join(VEHICLE_ROW_OUTPUTS))
+        raise ValueError("observe_vehicles_tensor: give at least one of start, count, " +
+                         ", ".join(VEHICLE_ROW_OUTPUTS + VEHICLE_POSE_OUTPUTS))
     lanes, links = self._drivable_counts()
     lead = tuple(self._tensor_shapes()[0])[:-1]
     device = _engine_device(torch, self)
@@ -1291,8 +1324,8 @@ def observe_vehicles_tensor(self, start=None, count=None, vehicle=None, drivable
         raise ValueError("the row outputs hold fewer than 2**31 rows, not %d" % n_rows)
     if self._lane_change():
         raise RuntimeError("observe_vehicles_tensor: not with laneChange (a shadow is a second row of its vehicle)")
-    if not self._device_buffers() or not self._vehicle_rows_device():  # (the twin, an older library: over the array call)
-        arrays = _vehicle_rows(self)
+    if not self._device_buffers() or not (self._vehicle_poses_device() if poses else self._vehicle_rows_device()):
+        arrays = _vehicle_rows(self, poses)  # (the twin, an older library: over the array call)
         n = int(arrays["count"])
         if start is not None:
             start.copy_(torch.from_numpy(arrays["start"]))
@@ -1309,7 +1342,7 @@ def observe_vehicles_tensor(self, start=None, count=None, vehicle=None, drivable
         return  # (tensors without an element: nothing to write)
     ptr = lambda t: 0 if t is None or t.numel() == 0 else t.data_ptr()  # noqa: E731
     self._observe_vehicles_device(ptr(start), ptr(count), *[ptr(rows[name]) for name in VEHICLE_ROW_OUTPUTS], n_rows or 0,
-                                  torch.cuda.current_stream(device).cuda_stream)
+                                  torch.cuda.current_stream(device).cuda_stream, *[ptr(rows[name]) for name in VEHICLE_POSE_OUTPUTS])
 
 
 def set_vehicle_speeds(self, vehicle, speed):
@@ -1518,6 +1551,7 @@ def install(*classes):
         cls.set_vehicle_speeds = set_vehicle_speeds
         cls.observe_vehicles_tensor = observe_vehicles_tensor
         cls.observe_vehicles_array = observe_vehicles_array
+        cls.drivable_geometry = drivable_geometry
         cls.checkpoint = checkpoint
         cls.rollback = rollback_envs if hasattr(cls, "_rollback_envs") else rollback
         cls.set_tl_plan_tensor = set_tl_plan_tensor

@@ -599,7 +599,16 @@ typedef int32_t (*cfx_get_lane_obs_fn)(cfx_engine *e, const cfx_lane_obs *obs);
  * written, nothing beyond n_rows.  Any pointer may be NULL (at least one of start, count or - with n_rows > 0 - a row output
  * given); all device memory.  The descriptor's struct_size as cfx_lane_obs's.  Two kernels on the engine's stream, ordered
  * against consumer_stream as cfx_observe_device; the call never waits for the device (the first call allocates a few KB).
- * CFX_ERR_STATE with lane change (shadows) and on a tile. */
+ * CFX_ERR_STATE with lane change (shadows) and on a tile.
+ * The POSE row outputs (members behind gap: a caller whose struct_size ends before them gives none), all double [n_rows]:
+ *                           x, y          Vehicle::getPoint without its lane-change branch: getPointByDistance over the
+ *                                         drivable's polyline at the row's distance (clamped to [0, the polyline's length]) padding NaN
+ *                           dir_x, dir_y  Drivable::getDirectionByDistance: the unit vector of the segment the distance
+ *                                         falls on (the last one beyond the end)                                    padding 0.0
+ *                           length, width the len and width of the vehicle's template                               padding 0.0
+ * The values are the reference's doubles to the bit (a last segment of length zero gives a NaN direction at and beyond it).
+ * They need the polylines: CFX_ERR_STATE, with a cfx_last_error that says so, when one of the six is given before
+ * cfx_set_drivable_geometry was called.  A call that gives none of them launches the kernels it always did. */
 typedef struct cfx_vehicle_rows {
     int32_t struct_size;
     int32_t n_rows;              /* elements of every row output, >= 0 */
@@ -608,8 +617,26 @@ typedef struct cfx_vehicle_rows {
     double *distance, *speed;
     int32_t *leader;
     double *gap;
+    double *x, *y, *dir_x, *dir_y, *length, *width;
 } cfx_vehicle_rows;
 typedef int32_t (*cfx_observe_vehicles_device_fn)(cfx_engine *e, const cfx_vehicle_rows *rows, void *consumer_stream);
+
+/* ---- The polylines of the drivables (an OPTIONAL entry point, as above), which the pose outputs of
+ * cfx_observe_vehicles_device walk.  Host arrays for the D drivables of ONE environment, numbered as that call's drivable
+ * column (lanes first, then laneLinks): drivable d has the points point_start[d] .. point_start[d + 1] - 1, at least two,
+ * point p is (xy[2 * p], xy[2 * p + 1]); point_start[0] == 0, point_start[D] == n_points.  The environments of a batched
+ * engine share the one table.  Synchronous; the arrays are not read after the call.  The geometry belongs to the engine as
+ * the network does: cfx_reset, cfx_load_state, a checkpoint restore and whatever else moves vehicles leave it alone; a
+ * second call replaces it.  The descriptor's struct_size as cfx_lane_obs's.  CFX_ERR_INVALID for arrays that are not such a
+ * table, CFX_ERR_STATE on a tile. */
+typedef struct cfx_drivable_geometry {
+    int32_t struct_size;
+    int32_t n_drivables;         /* D = (n_lanes + n_lanelinks) / n_envs */
+    int32_t n_points;            /* P */
+    const int32_t *point_start;  /* [D + 1] */
+    const double *xy;            /* [2 * P] */
+} cfx_drivable_geometry;
+typedef int32_t (*cfx_set_drivable_geometry_fn)(cfx_engine *e, const cfx_drivable_geometry *geometry);
 
 /* ---- Speed commands for many vehicles at once (OPTIONAL entry points, as above; both or none): Vehicle::setCustomSpeed, as
  * cfx_set_vehicle_speed, for n rows {vehicle[i], speed[i]}, n >= 0.  The vehicle numbers are cfx_observe_vehicles_device's.
