@@ -298,6 +298,47 @@ def test_reset_keeps_the_plan_and_restore_brings_the_files_back(mod, scen, workd
     run_equal([fresh, eng], 100, "after restore_tl_plan %s" % layout)
 
 
+def one_plan_per_environment(vec, singles, plan, plans, steps=120, every_step=None):
+    """The batched engine GIVEN plans[r] in environment r at step 0 against singles[r] BUILT with it (vec = an Engine: one
+    plan, one single; vec = None: the singles alone, for what the test needs of them).  Lights and lane counts every 10
+    steps, every vehicle's speed at the end; every_step(s, singles), if given, is called after every step.  Returns the
+    environments' phases at the compared steps, [compared, R, I], from the singles."""
+    R = len(singles)
+    batched = vec is not None and len(vec._tensor_shapes()[1]) == 2
+    rows = (lambda a: np.asarray(a)) if batched else (lambda a: np.asarray(a)[None])
+    if vec is not None:
+        stacked = np.stack([plan.dirty(T) for T in plans])
+        if not batched:
+            stacked = stacked[0]
+        vec.set_tl_plan_tensor(durations=dev(vec, stacked), phase_remain=dev(vec, stacked[..., 0]))
+        assert np.array_equal(rows(durations_of(vec)), np.stack(plans))
+    seen = []
+    for s in range(steps):
+        if vec is not None:
+            vec.next_step()
+        for e in singles:
+            e.next_step()
+        if every_step is not None:
+            every_step(s, singles)
+        if s % 10 != 9:
+            continue
+        seen.append(np.stack([lights(e)[0] for e in singles]))
+        if vec is None:
+            continue
+        ph, rem = [rows(a) for a in vec._tl_state()]
+        counts = rows(vec.get_lane_vehicle_count_array())
+        for r, e in enumerate(singles):
+            p1, r1 = lights(e)
+            assert np.array_equal(ph[r], p1) and np.array_equal(rem[r], r1), "env %d: lights differ at step %d" % (r, s)
+            assert np.array_equal(counts[r], e.get_lane_vehicle_count_array()), "env %d: lane counts differ at step %d" % (r, s)
+    if vec is not None:
+        for r, e in enumerate(singles):
+            got = vec.get_vehicle_speed(r) if batched else vec.get_vehicle_speed()
+            assert got == e.get_vehicle_speed(), "env %d: vehicle speeds differ" % r
+    assert R == 1 or any(not np.array_equal(ph[r], ph[r + 1]) for ph in seen for r in range(R - 1)), "the environments' lights never differed"
+    return np.stack(seen)
+
+
 @pytest.mark.gpu
 def test_vector_engine_one_plan_per_environment(mod, scen, workdir):
     R = 3
@@ -309,23 +350,7 @@ def test_vector_engine_one_plan_per_environment(mod, scen, workdir):
     assert not np.array_equal(plans[0], plans[1]) and not np.array_equal(plans[1], plans[2])
     singles = [mod.Engine(plan.built(plans[r], "env%d" % r, seed=r), 1) for r in range(R)]
     vec.track_trips(True)
-    stacked = np.stack([plan.dirty(T) for T in plans])
-    vec.set_tl_plan_tensor(durations=dev(vec, stacked), phase_remain=dev(vec, stacked[:, :, 0]))
-    assert np.array_equal(durations_of(vec), np.stack(plans))
-    for s in range(120):
-        vec.next_step()
-        for e in singles:
-            e.next_step()
-        if s % 10 != 9:
-            continue
-        ph, rem = vec._tl_state()
-        counts = vec.get_lane_vehicle_count_array()
-        for r, e in enumerate(singles):
-            p1, r1 = lights(e)
-            assert np.array_equal(ph[r], p1) and np.array_equal(rem[r], r1), "env %d: lights differ at step %d" % (r, s)
-            assert np.array_equal(counts[r], e.get_lane_vehicle_count_array()), "env %d: lane counts differ at step %d" % (r, s)
-    for r, e in enumerate(singles):
-        assert vec.get_vehicle_speed(r) == e.get_vehicle_speed(), "env %d: vehicle speeds differ" % r
+    ph = one_plan_per_environment(vec, singles, plan, plans)[-1]
     att = vec.get_average_travel_time_tensor().cpu().numpy()
     want = np.array([e.get_average_travel_time() for e in singles])
     assert np.array_equal(att, want), (att, want)

@@ -17,7 +17,10 @@ layout steps alike).  Where each condition first occurs among the compared state
   example_1x1 (35 steps)              a laneLink's first segment and its segment >= 5: step 28
   irregular_11_long_roads (35 steps)  a polyline longer than the kernel's staging bound of 16 points: step 7 (its straight
                                       roads are redrawn with 19 points; the generated curves have 11, so no stock network
-                                      reaches the walk in global memory)"""
+                                      reaches the walk in global memory)
+  grid_2x2_mid15, _mid16 (28 steps)   a vehicle on a polyline of exactly the staging bound, and on one of one point more, the
+                                      shortest that is walked in global memory: step 21 (2 x 2 grids whose laneLinks are drawn
+                                      with 16 and 17 points)"""
 import ctypes as C
 import json
 import math
@@ -133,7 +136,8 @@ def numpy_poses(geometry, rows):
 class Looked:
     """What the compared states contained."""
     NEED = ("first segment of a lane", "later segment of a bent lane", "first segment of a laneLink", "segment >= 5 of a laneLink",
-            "a drivable with >= 17 vehicles", "a polyline beyond the staging bound", "moving")
+            "a drivable with >= 17 vehicles", "a polyline beyond the staging bound", "a polyline of exactly the staging bound",
+            "one point beyond it", "moving")
 
     def __init__(self):
         self.seen, self.first = set(), {}
@@ -145,7 +149,9 @@ class Looked:
                 "later segment of a bent lane": (lane & (n_points >= 3) & (seg >= 1)).any(),
                 "first segment of a laneLink": (~lane & (seg == 0)).any(), "segment >= 5 of a laneLink": (~lane & (seg >= 5)).any(),
                 "a drivable with >= 17 vehicles": (np.diff(want["start"].reshape(-1)) >= 17).any(),
-                "a polyline beyond the staging bound": (n_points > STAGE_POINTS).any(), "moving": (want["speed"] > 0).any()}
+                "a polyline beyond the staging bound": (n_points > STAGE_POINTS).any(),
+                "a polyline of exactly the staging bound": (n_points == STAGE_POINTS).any(),
+                "one point beyond it": (n_points == STAGE_POINTS + 1).any(), "moving": (want["speed"] > 0).any()}
         for k, hit in hits.items():
             if hit:
                 self.seen.add(k)
@@ -197,12 +203,34 @@ def long_roads(scen, workdir, points=19):
     return os.path.join(d, "config.json")
 
 
-NETWORKS = (("irregular_11", 56), ("star5", 56), ("example_1x1", 35), ("irregular_11_long_roads", 35))
+def curved_grid(scen, workdir, mid_points):
+    """A 2 x 2 grid whose laneLinks are drawn with mid_points + 1 points (the stock generator's 10 give 11): 15 fills the
+    kernel's stage exactly, 16 is the shortest polyline that is walked in global memory.  Its lanes have 2 points."""
+    d = os.path.join(workdir, "grid_2x2_mid%d" % mid_points)
+    os.makedirs(d, exist_ok=True)
+    with open(os.path.join(d, "roadnet.json"), "w") as f:
+        json.dump(scen.grid_roadnet(2, 2, mid_points=mid_points), f)
+    with open(os.path.join(d, "flow.json"), "w") as f:
+        json.dump(scen.grid_flows(2, 2), f)
+    cfg = {"interval": 1.0, "seed": 0, "dir": d + "/", "roadnetFile": "roadnet.json", "flowFile": "flow.json",
+           "rlTrafficLight": False, "laneChange": False, "saveReplay": False}
+    with open(os.path.join(d, "config.json"), "w") as f:
+        json.dump(cfg, f)
+    return os.path.join(d, "config.json")
+
+
+# (the two curved grids: vehicles stand on their 16- and 17-point laneLinks at step 21)
+CURVED = {"grid_2x2_mid15": STAGE_POINTS, "grid_2x2_mid16": STAGE_POINTS + 1}  # name -> points of a laneLink
+NETWORKS = (("irregular_11", 56), ("star5", 56), ("example_1x1", 35), ("irregular_11_long_roads", 35), ("grid_2x2_mid15", 28),
+            ("grid_2x2_mid16", 28))
 
 
 def network_config(scen, workdir, name, layout):
     if name.startswith("star"):
         return star_networks.make(workdir, name, layout="dense" if layout == "dense" else "auto")
+    if name in CURVED:
+        cfg = curved_grid(scen, workdir, CURVED[name] - 1)
+        return derived_config(cfg, "dense", cfx={"layout": "dense"}) if layout == "dense" else cfg
     if name.startswith("irregular"):
         cfg = long_roads(scen, workdir) if name.endswith("long_roads") else irregular(scen, workdir, 11)
         return derived_config(cfg, "dense", cfx={"layout": "dense"}) if layout == "dense" else cfg
@@ -280,11 +308,14 @@ def test_poses_equal_the_reference_replay(mod, scen, workdir, ref_module, name, 
     assert compared > 100 and turned > 10, (compared, turned)
 
 
-@pytest.mark.parametrize("name", ["irregular_11", "irregular_11_long_roads", "star5", "example_1x1"])
+@pytest.mark.parametrize("name", ["irregular_11", "irregular_11_long_roads", "star5", "example_1x1"] + sorted(CURVED))
 def test_poses_equal_the_numpy_walks_over_the_geometry(mod, scen, workdir, name):
     eng = twin(mod, network_config(scen, workdir, name, "auto"))
     n_lanes, D = drivables(eng)
     geometry = eng.drivable_geometry()
+    if name in CURVED:  # every laneLink has exactly that many points, every lane two
+        n_points = np.diff(geometry["point_start"])
+        assert (n_points[n_lanes:] == CURVED[name]).all() and (n_points[:n_lanes] == 2).all(), sorted(set(n_points.tolist()))
     assert sorted(geometry) == ["point_start", "points"]
     start, points = geometry["point_start"], geometry["points"]
     assert start.dtype == np.int32 and start.shape == (D + 1,) and points.dtype == np.float64 and points.shape == (int(start[-1]), 2)
@@ -311,10 +342,14 @@ def test_poses_equal_the_numpy_walks_over_the_geometry(mod, scen, workdir, name)
             same(rows[k], want[k], "%s step %d: %s" % (name, s, k))
         assert (rows["length"] > 0).all() and (rows["width"] > 0).all()
         looked.at(geometry, rows, n_lanes, "step %d" % s)
-    assert {"first segment of a lane", "first segment of a laneLink", "segment >= 5 of a laneLink", "moving"} <= looked.seen, looked.seen
+    assert {"first segment of a lane", "segment >= 5 of a laneLink", "moving"} <= looked.seen, looked.seen
+    # (a curved grid's eight flows run in step, and none of their vehicles is met on the short first segment of its spline)
+    assert "first segment of a laneLink" in looked.seen or name in CURVED, looked.seen
     if name.startswith("irregular"):
         assert "later segment of a bent lane" in looked.seen
-    assert ("a polyline beyond the staging bound" in looked.seen) == name.endswith("long_roads")
+    assert ("a polyline beyond the staging bound" in looked.seen) == (name.endswith("long_roads") or CURVED.get(name, 0) > STAGE_POINTS)
+    assert ("a polyline of exactly the staging bound" in looked.seen) == (CURVED.get(name) == STAGE_POINTS)  # (a vehicle stood on one)
+    assert ("one point beyond it" in looked.seen) == (CURVED.get(name) == STAGE_POINTS + 1)
 
 
 def test_a_last_segment_of_length_zero_gives_nan():
@@ -384,8 +419,9 @@ def test_lane_change_raises_twin(mod, scen, workdir):
             eng.observe_vehicles_array(poses=True)
 
 
-def vector_body(vec, singles, steps, every, where):
-    """Each environment's run of rows equals the array form of the standalone engine with that seed."""
+def vector_body(vec, singles, steps, every, where, extra=None):
+    """Each environment's run of rows equals the array form of the standalone engine with that seed.
+    extra(vec, got, total, at), if given, is called with every compared state once it has been held against the singles."""
     R = len(singles)
     _, D = drivables(singles[0])
     geometry = vec.drivable_geometry()
@@ -417,6 +453,8 @@ def vector_body(vec, singles, steps, every, where):
             same(got["env"][lo:hi], np.full(hi - lo, r, dtype=np.int32), "%s: env %d env" % (at, r))
             for k in ("drivable", "distance", "speed") + POSES:
                 same(got[k][lo:hi], want[k], "%s: env %d %s" % (at, r, k))
+        if extra is not None:
+            extra(vec, got, total, at)
 
 
 def test_vector_engine_twin(mod, scen, workdir):

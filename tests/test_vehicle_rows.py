@@ -198,8 +198,9 @@ def test_one_output_at_a_time_twin(mod, scen, workdir):
     one_at_a_time_body(twin(mod, scen.materialize("grid_6x6", workdir)))
 
 
-def vector_body(vec, singles, steps, every, where, looked=None):
-    """The batched engine against standalone engines, environment by environment; returns the last compared rows."""
+def vector_body(vec, singles, steps, every, where, looked=None, extra=None):
+    """The batched engine against standalone engines, environment by environment; returns the last compared rows.
+    extra(vec, got, total, at), if given, is called with every compared state once it has been held against the singles."""
     R = len(singles)
     n_lanes, D = drivables(singles[0])
     assert vec._drivable_counts() == singles[0]._drivable_counts()
@@ -241,6 +242,8 @@ def vector_body(vec, singles, steps, every, where, looked=None):
             same(got["leader"][lo:hi], mapped, "%s: env %d leader" % (at, r))
         if looked is not None:
             looked.at(dict(got, drivable=got["drivable"][:total], leader=got["leader"][:total], speed=got["speed"][:total]), n_lanes)
+        if extra is not None:
+            extra(vec, got, total, at)
     return got
 
 
