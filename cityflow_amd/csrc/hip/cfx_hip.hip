@@ -193,9 +193,9 @@ struct cfx_engine {
     double2 *drvLM = nullptr;
     double *drvMaxSpeed = nullptr, *laneLimitFile = nullptr;
     // The staging arena of the host forms (cfx_get_lane_obs, cfx_get_lane_features, cfx_get_intersection_features,
-    // cfx_get_movement_flow, cfx_set_tl_plan, cfx_get_tl_phase_durations, cfx_set_vehicle_speeds, cfx_set_vehicle_routes,
-    // cfx_get_vehicle_routes, cfx_set_lane_speed_limits, cfx_get_lane_speed_limits): the device side of the host
-    // arrays one call was given, laid out by cfx_stage_layout.h.  ONE allocation (in `owned`), grown to the largest request
+    // cfx_get_movement_flow, cfx_get_trip_log, cfx_set_tl_plan, cfx_get_tl_phase_durations, cfx_set_vehicle_speeds,
+    // cfx_set_vehicle_routes, cfx_get_vehicle_routes, cfx_set_lane_speed_limits, cfx_get_lane_speed_limits): the device side of the
+    // host arrays one call was given, laid out by cfx_stage_layout.h.  ONE allocation (in `owned`), grown to the largest request
     // seen, rounded up to a power of two so that requests that creep up (the speed commands of a filling network) regrow it a
     // logarithmic number of times.  Growing frees the old one at once, which is safe because the arena is idle at every
     // entry: it is used only by calls that end in hipStreamSynchronize(stream) (stageClose).  Nothing in it outlives a call.
@@ -502,10 +502,34 @@ struct cfx_engine {
         return CFX_OK;
     }
 
-    // The host forms' staging (the arena above).  stageOpen: the arena holds the layout, and the copies of its `in` fields
-    // are enqueued; the caller then launches on s.dev(field).  stageClose: the copies of its `out` fields are enqueued and the
-    // stream is waited for — the call's one wait, after which the arena is idle again.
-    int stageOpen(cfx_stage::StageLayout &s) {
+    // A caller's buffer has to be device memory of this engine's GPU (`what`: "<entry point>", `name`: the buffer's)
+    int checkDevicePointer(const void *p, const char *what, const char *name) {
+        hipPointerAttribute_t a{};
+        const hipError_t he = hipPointerGetAttributes(&a, p);
+        if (he != hipSuccess) (void) hipGetLastError();  // (not sticky: the next launch check must not see it)
+        if (he != hipSuccess || a.type != hipMemoryTypeDevice || a.device != device) {
+            err = std::string(what) + ": " + name + ": not device memory of this engine's GPU (device " + std::to_string(device) +
+                  "; the caller's HIP runtime must be the engine's)";
+            return CFX_ERR_INVALID;
+        }
+        return CFX_OK;
+    }
+    // ... each given field of a pass-through layout (a staged layout's are host arrays: nothing to check)
+    int stageCheck(const cfx_stage::StageLayout &s, const char *what) {
+        int rc;
+        if (s.passThrough)
+            for (int i = 0; i < s.nFields; ++i)
+                if (s.field[i].host && (rc = checkDevicePointer(s.field[i].host, what, s.field[i].name))) return rc;
+        return CFX_OK;
+    }
+
+    // One body per host / device pair of calls (cfx_stage_layout.h).  Staged, the host forms (the arena above).  stageOpen: the
+    // arena holds the layout, and the copies of its `in` fields are enqueued; the caller then launches on s.dev(field).
+    // stageClose: the copies of its `out` fields are enqueued and the stream is waited for — the call's one wait, after which
+    // the arena is idle again.  Pass-through, the `_device` forms: s.dev(field) is the caller's buffer, and the two order the
+    // engine's stream against `callerStream` (orderAfterCaller / orderCallerAfter above) without waiting for either.
+    int stageOpen(cfx_stage::StageLayout &s, void *callerStream) {
+        if (s.passThrough) return orderAfterCaller((hipStream_t) callerStream);
         if (s.size() > stageBytes) {
             size_t cap = cfx_stage::kStageAlign;
             while (cap < s.size()) cap *= 2;
@@ -520,7 +544,8 @@ struct cfx_engine {
         }
         return CFX_OK;
     }
-    int stageClose(const cfx_stage::StageLayout &s) {
+    int stageClose(const cfx_stage::StageLayout &s, void *callerStream) {
+        if (s.passThrough) return orderCallerAfter((hipStream_t) callerStream);
         for (int i = 0; i < s.nFields; ++i) {
             const auto &f = s.field[i];
             if (f.host && f.bytes && f.out) HIP_TRY(hipMemcpyAsync(f.host, s.base + f.offset, f.bytes, hipMemcpyDeviceToHost, stream));
@@ -2404,8 +2429,6 @@ int32_t cfx_get_host_stats(cfx_engine *e, cfx_host_stats *out, int32_t reset) {
 }
 
 // what kr_cross's grids did (optional entry point of include/cityflow_amd.h)
-int32_t cfx_get_cross_stats(cfx_engine *e, cfx_cross_stats *out, int32_t reset);
-static_assert(std::is_same<decltype(&cfx_get_cross_stats), cfx_get_cross_stats_fn>::value, "cfx_get_cross_stats");
 int32_t cfx_get_cross_stats(cfx_engine *e, cfx_cross_stats *out, int32_t reset) {
     if (!e || !out) return CFX_ERR_INVALID;
     auto fail = [e](const std::string &m) { return e->fail(m); };
@@ -3326,18 +3349,6 @@ int32_t cfx_load_state(cfx_engine *e, const cfx_state *s) {
 
 // ---------------------------------------------------------------------------------------------- device checkpoints
 // (optional entry points of include/cityflow_amd.h)
-int32_t cfx_checkpoint_create(cfx_engine *e, cfx_checkpoint **out);
-int32_t cfx_checkpoint_save(cfx_engine *e, cfx_checkpoint *ck);
-int32_t cfx_checkpoint_restore(cfx_engine *e, cfx_checkpoint *ck);
-int32_t cfx_checkpoint_info(const cfx_checkpoint *ck, cfx_checkpoint_desc *out);
-void cfx_checkpoint_destroy(cfx_checkpoint *ck);
-int32_t cfx_checkpoint_restore_envs(cfx_engine *e, cfx_checkpoint *ck, const cfx_env_gather *g);
-static_assert(std::is_same<decltype(&cfx_checkpoint_restore_envs), cfx_checkpoint_restore_envs_fn>::value, "cfx_checkpoint_restore_envs");
-static_assert(std::is_same<decltype(&cfx_checkpoint_create), cfx_checkpoint_create_fn>::value, "cfx_checkpoint_create");
-static_assert(std::is_same<decltype(&cfx_checkpoint_save), cfx_checkpoint_save_fn>::value, "cfx_checkpoint_save");
-static_assert(std::is_same<decltype(&cfx_checkpoint_restore), cfx_checkpoint_restore_fn>::value, "cfx_checkpoint_restore");
-static_assert(std::is_same<decltype(&cfx_checkpoint_info), cfx_checkpoint_info_fn>::value, "cfx_checkpoint_info");
-static_assert(std::is_same<decltype(&cfx_checkpoint_destroy), cfx_checkpoint_destroy_fn>::value, "cfx_checkpoint_destroy");
 
 // Where a checkpoint of nR running vehicles and nV vehicle numbers keeps its arrays: one after the other from `base`, each on
 // a 256-byte boundary (so that the pack kernel moves 16 bytes per lane).  Returns the bytes needed; base may be null (sizing).
@@ -4040,36 +4051,8 @@ int32_t cfx_device_spin(cfx_engine *e, int64_t microseconds) {
 }
 
 // ---- observations and signals in device memory (torch tensors), ordered against the caller's stream (the optional entry
-// points of include/cityflow_amd.h: declared there as the types of the symbols)
-int32_t cfx_stream_handle(cfx_engine *e, void **stream, int32_t *device);
-int32_t cfx_observe_device(cfx_engine *e, int32_t *counts, int32_t *waiting, void *consumerStream);
-int32_t cfx_set_tl_phases_device(cfx_engine *e, const int32_t *phases, int32_t n, void *producerStream);
-int32_t cfx_device_error(cfx_engine *e, int32_t *inter, int32_t *phase);
-static_assert(std::is_same<decltype(&cfx_stream_handle), cfx_stream_handle_fn>::value, "cfx_stream_handle");
-static_assert(std::is_same<decltype(&cfx_observe_device), cfx_observe_device_fn>::value, "cfx_observe_device");
-static_assert(std::is_same<decltype(&cfx_set_tl_phases_device), cfx_set_tl_phases_device_fn>::value, "cfx_set_tl_phases_device");
-static_assert(std::is_same<decltype(&cfx_device_error), cfx_device_error_fn>::value, "cfx_device_error");
-
-static int checkDevicePointer(cfx_engine *e, const void *p, const char *what) {
-    hipPointerAttribute_t a{};
-    const hipError_t he = hipPointerGetAttributes(&a, p);
-    if (he != hipSuccess) (void) hipGetLastError();  // (not sticky: the next launch check must not see it)
-    if (he != hipSuccess || a.type != hipMemoryTypeDevice || a.device != e->device) {
-        e->err = std::string(what) + ": not device memory of this engine's GPU (device " + std::to_string(e->device) +
-                 "; the caller's HIP runtime must be the engine's)";
-        return CFX_ERR_INVALID;
-    }
-    return CFX_OK;
-}
-
-// ... each buffer of a list that is given (`what`: "<entry point>", the message names "<entry point>: <name>")
-static int checkDevicePointers(cfx_engine *e, const char *what, std::initializer_list<std::pair<const void *, const char *>> bufs) {
-    int rc;
-    for (const auto &b : bufs)
-        if (b.first && (rc = checkDevicePointer(e, b.first, (std::string(what) + ": " + b.second).c_str()))) return rc;
-    return CFX_OK;
-}
-
+// points of include/cityflow_amd.h: declared there as the types of the symbols, which the asserts at the end of this file hold
+// the definitions to)
 int32_t cfx_stream_handle(cfx_engine *e, void **stream, int32_t *device) {
     if (!e) return CFX_ERR_INVALID;
     if (stream) *stream = (void *) e->stream;
@@ -4082,7 +4065,7 @@ int32_t cfx_set_tl_phases_device(cfx_engine *e, const int32_t *phases, int32_t n
     auto fail = [e](const std::string &m) { return e->fail(m); };
     HIP_TRY(hipSetDevice(e->device));
     int rc;
-    if ((rc = checkDevicePointer(e, phases, "cfx_set_tl_phases_device: phases"))) return rc;
+    if ((rc = e->checkDevicePointer(phases, "cfx_set_tl_phases_device", "phases"))) return rc;
     if ((rc = e->settle(false))) return rc;  // (as cfx_set_tl_phases: the deferred commit advances the lights of the last step first)
     if ((rc = e->orderAfterCaller((hipStream_t) producerStream))) return rc;
     hipLaunchKernelGGL(k_set_phases_dense, dim3(1), dim3(1024), 0, e->stream, phases, n, e->net.interPhaseStart,
@@ -4104,20 +4087,6 @@ int32_t cfx_device_error(cfx_engine *e, int32_t *inter, int32_t *phase) {
 }
 
 // ---- the fixed-time signal plan as engine state (optional entry points of include/cityflow_amd.h, as above)
-int32_t cfx_set_tl_plan_device(cfx_engine *e, const double *durations, const int32_t *phase, const double *remain, int32_t n,
-                               int32_t maxPhases, void *producerStream);
-int32_t cfx_set_tl_plan(cfx_engine *e, const double *durations, const int32_t *phase, const double *remain, int32_t n, int32_t maxPhases);
-int32_t cfx_get_tl_phase_durations_device(cfx_engine *e, double *out, int32_t maxPhases, void *consumerStream);
-int32_t cfx_get_tl_phase_durations(cfx_engine *e, double *out, int32_t maxPhases);
-int32_t cfx_restore_tl_plan(cfx_engine *e);
-int32_t cfx_tl_plan_error(cfx_engine *e, int32_t *what, int32_t *inter, int32_t *phase, double *value);
-static_assert(std::is_same<decltype(&cfx_set_tl_plan_device), cfx_set_tl_plan_device_fn>::value, "cfx_set_tl_plan_device");
-static_assert(std::is_same<decltype(&cfx_set_tl_plan), cfx_set_tl_plan_fn>::value, "cfx_set_tl_plan");
-static_assert(std::is_same<decltype(&cfx_get_tl_phase_durations_device), cfx_get_tl_phase_durations_device_fn>::value,
-              "cfx_get_tl_phase_durations_device");
-static_assert(std::is_same<decltype(&cfx_get_tl_phase_durations), cfx_get_tl_phase_durations_fn>::value, "cfx_get_tl_phase_durations");
-static_assert(std::is_same<decltype(&cfx_restore_tl_plan), cfx_restore_tl_plan_fn>::value, "cfx_restore_tl_plan");
-static_assert(std::is_same<decltype(&cfx_tl_plan_error), cfx_tl_plan_error_fn>::value, "cfx_tl_plan_error");
 
 // what every plan call checks first: not on a tile (its lights are another tile's too), the caller's row length
 static int tlPlanArgs(cfx_engine *e, int32_t maxPhases, const char *what) {
@@ -4139,37 +4108,33 @@ static void launchSetTlPlan(cfx_engine *e, const double *durations, const int32_
                        e->curPhase, e->remain, e->hPlanErr);
 }
 
-int32_t cfx_set_tl_plan_device(cfx_engine *e, const double *durations, const int32_t *phase, const double *remain, int32_t n,
-                               int32_t maxPhases, void *producerStream) {
+// Both forms of a call, here and below, are one body.  toHost: the arrays are host memory, staged through the engine's arena
+// and waited for; otherwise device memory, ordered against the caller's `stream`.  `what` names the entry point in messages.
+static int setTlPlan(cfx_engine *e, const double *durations, const int32_t *phase, const double *remain, int32_t n, int32_t maxPhases,
+                     bool toHost, void *stream, const char *what) {
     if (!e || (!durations && !phase && !remain) || n != e->I) return CFX_ERR_INVALID;
     auto fail = [e](const std::string &m) { return e->fail(m); };
     HIP_TRY(hipSetDevice(e->device));
     int rc;
-    if ((rc = tlPlanArgs(e, maxPhases, "cfx_set_tl_plan_device"))) return rc;
-    if ((rc = checkDevicePointers(e, "cfx_set_tl_plan_device", {{durations, "durations"}, {phase, "phase"}, {remain, "remain"}}))) return rc;
-    if ((rc = e->settle(false))) return rc;  // (as cfx_set_tl_phases_device: the deferred commit advances the lights of the last step first)
-    if ((rc = e->orderAfterCaller((hipStream_t) producerStream))) return rc;
-    launchSetTlPlan(e, durations, phase, remain);
-    HIP_TRY(hipGetLastError());
-    return e->orderCallerAfter((hipStream_t) producerStream);
-}
-
-int32_t cfx_set_tl_plan(cfx_engine *e, const double *durations, const int32_t *phase, const double *remain, int32_t n, int32_t maxPhases) {
-    if (!e || (!durations && !phase && !remain) || n != e->I) return CFX_ERR_INVALID;
-    auto fail = [e](const std::string &m) { return e->fail(m); };
-    HIP_TRY(hipSetDevice(e->device));
-    int rc;
-    if ((rc = tlPlanArgs(e, maxPhases, "cfx_set_tl_plan"))) return rc;
-    if ((rc = e->settle(false))) return rc;
+    if ((rc = tlPlanArgs(e, maxPhases, what))) return rc;
     const size_t nI = (size_t) e->I, nD = nI * (size_t) e->planMaxPhases;
-    cfx_stage::StageLayout s;
-    const auto fDurations = s.in(durations, nD);
-    const auto fPhase = s.in(phase, nI);
-    const auto fRemain = s.in(remain, nI);
-    if ((rc = e->stageOpen(s))) return rc;
+    cfx_stage::StageLayout s(!toHost);
+    const auto fDurations = s.in(durations, "durations", nD);
+    const auto fPhase = s.in(phase, "phase", nI);
+    const auto fRemain = s.in(remain, "remain", nI);
+    if ((rc = e->stageCheck(s, what))) return rc;
+    if ((rc = e->settle(false))) return rc;  // (as cfx_set_tl_phases_device: the deferred commit advances the lights of the last step first)
+    if ((rc = e->stageOpen(s, stream))) return rc;
     launchSetTlPlan(e, s.dev(fDurations), s.dev(fPhase), s.dev(fRemain));
     HIP_TRY(hipGetLastError());
-    return e->stageClose(s);
+    return e->stageClose(s, stream);
+}
+int32_t cfx_set_tl_plan_device(cfx_engine *e, const double *durations, const int32_t *phase, const double *remain, int32_t n,
+                               int32_t maxPhases, void *producerStream) {
+    return setTlPlan(e, durations, phase, remain, n, maxPhases, false, producerStream, "cfx_set_tl_plan_device");
+}
+int32_t cfx_set_tl_plan(cfx_engine *e, const double *durations, const int32_t *phase, const double *remain, int32_t n, int32_t maxPhases) {
+    return setTlPlan(e, durations, phase, remain, n, maxPhases, true, nullptr, "cfx_set_tl_plan");
 }
 
 static void launchGetPhaseDurations(cfx_engine *e, double *out) {
@@ -4180,31 +4145,25 @@ static void launchGetPhaseDurations(cfx_engine *e, double *out) {
 }
 
 // (no settle: the durations are written by the calls above and by nothing a step launches)
-int32_t cfx_get_tl_phase_durations_device(cfx_engine *e, double *out, int32_t maxPhases, void *consumerStream) {
+static int getTlPhaseDurations(cfx_engine *e, double *out, int32_t maxPhases, bool toHost, void *stream, const char *what) {
     if (!e || !out) return CFX_ERR_INVALID;
     auto fail = [e](const std::string &m) { return e->fail(m); };
     HIP_TRY(hipSetDevice(e->device));
     int rc;
-    if ((rc = tlPlanArgs(e, maxPhases, "cfx_get_tl_phase_durations_device"))) return rc;
-    if ((rc = checkDevicePointer(e, out, "cfx_get_tl_phase_durations_device: out"))) return rc;
-    if ((rc = e->orderAfterCaller((hipStream_t) consumerStream))) return rc;
-    launchGetPhaseDurations(e, out);
-    HIP_TRY(hipGetLastError());
-    return e->orderCallerAfter((hipStream_t) consumerStream);
-}
-
-int32_t cfx_get_tl_phase_durations(cfx_engine *e, double *out, int32_t maxPhases) {
-    if (!e || !out) return CFX_ERR_INVALID;
-    auto fail = [e](const std::string &m) { return e->fail(m); };
-    HIP_TRY(hipSetDevice(e->device));
-    int rc;
-    if ((rc = tlPlanArgs(e, maxPhases, "cfx_get_tl_phase_durations"))) return rc;
-    cfx_stage::StageLayout s;
-    const auto fOut = s.out(out, (size_t) e->I * (size_t) e->planMaxPhases);
-    if ((rc = e->stageOpen(s))) return rc;
+    if ((rc = tlPlanArgs(e, maxPhases, what))) return rc;
+    cfx_stage::StageLayout s(!toHost);
+    const auto fOut = s.out(out, "out", (size_t) e->I * (size_t) e->planMaxPhases);
+    if ((rc = e->stageCheck(s, what))) return rc;
+    if ((rc = e->stageOpen(s, stream))) return rc;
     launchGetPhaseDurations(e, s.dev(fOut));
     HIP_TRY(hipGetLastError());
-    return e->stageClose(s);
+    return e->stageClose(s, stream);
+}
+int32_t cfx_get_tl_phase_durations_device(cfx_engine *e, double *out, int32_t maxPhases, void *consumerStream) {
+    return getTlPhaseDurations(e, out, maxPhases, false, consumerStream, "cfx_get_tl_phase_durations_device");
+}
+int32_t cfx_get_tl_phase_durations(cfx_engine *e, double *out, int32_t maxPhases) {
+    return getTlPhaseDurations(e, out, maxPhases, true, nullptr, "cfx_get_tl_phase_durations");
 }
 
 int32_t cfx_restore_tl_plan(cfx_engine *e) {
@@ -4236,19 +4195,6 @@ int32_t cfx_tl_plan_error(cfx_engine *e, int32_t *what, int32_t *inter, int32_t 
 }
 
 // ---- the lanes' speed limits as engine state (optional entry points of include/cityflow_amd.h, as above)
-int32_t cfx_set_lane_speed_limits_device(cfx_engine *e, const double *limits, int32_t n, int32_t *rejected, void *producerStream);
-int32_t cfx_set_lane_speed_limits(cfx_engine *e, const double *limits, int32_t n, int32_t *rejected);
-int32_t cfx_get_lane_speed_limits_device(cfx_engine *e, double *out, int32_t n, void *consumerStream);
-int32_t cfx_get_lane_speed_limits(cfx_engine *e, double *out, int32_t n);
-int32_t cfx_restore_lane_speed_limits(cfx_engine *e);
-static_assert(std::is_same<decltype(&cfx_set_lane_speed_limits_device), cfx_set_lane_speed_limits_device_fn>::value,
-              "cfx_set_lane_speed_limits_device");
-static_assert(std::is_same<decltype(&cfx_set_lane_speed_limits), cfx_set_lane_speed_limits_fn>::value, "cfx_set_lane_speed_limits");
-static_assert(std::is_same<decltype(&cfx_get_lane_speed_limits_device), cfx_get_lane_speed_limits_device_fn>::value,
-              "cfx_get_lane_speed_limits_device");
-static_assert(std::is_same<decltype(&cfx_get_lane_speed_limits), cfx_get_lane_speed_limits_fn>::value, "cfx_get_lane_speed_limits");
-static_assert(std::is_same<decltype(&cfx_restore_lane_speed_limits), cfx_restore_lane_speed_limits_fn>::value,
-              "cfx_restore_lane_speed_limits");
 
 // what every limit call checks first: not on a tile (a cut lane's limit would be another tile's too), the caller's length
 static int laneLimitArgs(cfx_engine *e, int32_t n, const char *what) {
@@ -4274,61 +4220,50 @@ static int launchSetLaneLimits(cfx_engine *e, const double *limits, int32_t *rej
     return CFX_OK;
 }
 
-int32_t cfx_set_lane_speed_limits_device(cfx_engine *e, const double *limits, int32_t n, int32_t *rejected, void *producerStream) {
+static int setLaneSpeedLimits(cfx_engine *e, const double *limits, int32_t n, int32_t *rejected, bool toHost, void *stream, const char *what) {
     if (!e || !limits) return CFX_ERR_INVALID;
     auto fail = [e](const std::string &m) { return e->fail(m); };
     HIP_TRY(hipSetDevice(e->device));
     int rc;
-    if ((rc = laneLimitArgs(e, n, "cfx_set_lane_speed_limits_device"))) return rc;
-    if ((rc = checkDevicePointers(e, "cfx_set_lane_speed_limits_device", {{limits, "limits"}, {rejected, "rejected"}}))) return rc;
-    if ((rc = e->orderAfterCaller((hipStream_t) producerStream))) return rc;
-    if ((rc = launchSetLaneLimits(e, limits, rejected))) return rc;
-    return e->orderCallerAfter((hipStream_t) producerStream);
-}
-
-int32_t cfx_set_lane_speed_limits(cfx_engine *e, const double *limits, int32_t n, int32_t *rejected) {
-    if (!e || !limits) return CFX_ERR_INVALID;
-    auto fail = [e](const std::string &m) { return e->fail(m); };
-    HIP_TRY(hipSetDevice(e->device));
-    int rc;
-    if ((rc = laneLimitArgs(e, n, "cfx_set_lane_speed_limits"))) return rc;
-    cfx_stage::StageLayout s;
-    const auto fLimits = s.in(limits, (size_t) e->L);
-    const auto fRejected = s.out(rejected, 1);
-    if ((rc = e->stageOpen(s))) return rc;
+    if ((rc = laneLimitArgs(e, n, what))) return rc;
+    cfx_stage::StageLayout s(!toHost);
+    const auto fLimits = s.in(limits, "limits", (size_t) e->L);
+    const auto fRejected = s.out(rejected, "rejected", 1);
+    if ((rc = e->stageCheck(s, what))) return rc;
+    if ((rc = e->stageOpen(s, stream))) return rc;
     if ((rc = launchSetLaneLimits(e, s.dev(fLimits), s.dev(fRejected)))) return rc;
-    return e->stageClose(s);
+    return e->stageClose(s, stream);
+}
+int32_t cfx_set_lane_speed_limits_device(cfx_engine *e, const double *limits, int32_t n, int32_t *rejected, void *producerStream) {
+    return setLaneSpeedLimits(e, limits, n, rejected, false, producerStream, "cfx_set_lane_speed_limits_device");
+}
+int32_t cfx_set_lane_speed_limits(cfx_engine *e, const double *limits, int32_t n, int32_t *rejected) {
+    return setLaneSpeedLimits(e, limits, n, rejected, true, nullptr, "cfx_set_lane_speed_limits");
 }
 
 static void launchGetLaneLimits(cfx_engine *e, double *out) {
     if (e->L) hipLaunchKernelGGL(k_get_lane_limits, dim3(gridStride((size_t) e->L)), dim3(kBlock), 0, e->stream, e->L, e->drvMaxSpeed, out);
 }
 
-int32_t cfx_get_lane_speed_limits_device(cfx_engine *e, double *out, int32_t n, void *consumerStream) {
+static int getLaneSpeedLimits(cfx_engine *e, double *out, int32_t n, bool toHost, void *stream, const char *what) {
     if (!e || !out) return CFX_ERR_INVALID;
     auto fail = [e](const std::string &m) { return e->fail(m); };
     HIP_TRY(hipSetDevice(e->device));
     int rc;
-    if ((rc = laneLimitArgs(e, n, "cfx_get_lane_speed_limits_device"))) return rc;
-    if ((rc = checkDevicePointer(e, out, "cfx_get_lane_speed_limits_device: out"))) return rc;
-    if ((rc = e->orderAfterCaller((hipStream_t) consumerStream))) return rc;
-    launchGetLaneLimits(e, out);
-    HIP_TRY(hipGetLastError());
-    return e->orderCallerAfter((hipStream_t) consumerStream);
-}
-
-int32_t cfx_get_lane_speed_limits(cfx_engine *e, double *out, int32_t n) {
-    if (!e || !out) return CFX_ERR_INVALID;
-    auto fail = [e](const std::string &m) { return e->fail(m); };
-    HIP_TRY(hipSetDevice(e->device));
-    int rc;
-    if ((rc = laneLimitArgs(e, n, "cfx_get_lane_speed_limits"))) return rc;
-    cfx_stage::StageLayout s;
-    const auto fOut = s.out(out, (size_t) e->L);
-    if ((rc = e->stageOpen(s))) return rc;
+    if ((rc = laneLimitArgs(e, n, what))) return rc;
+    cfx_stage::StageLayout s(!toHost);
+    const auto fOut = s.out(out, "out", (size_t) e->L);
+    if ((rc = e->stageCheck(s, what))) return rc;
+    if ((rc = e->stageOpen(s, stream))) return rc;
     launchGetLaneLimits(e, s.dev(fOut));
     HIP_TRY(hipGetLastError());
-    return e->stageClose(s);
+    return e->stageClose(s, stream);
+}
+int32_t cfx_get_lane_speed_limits_device(cfx_engine *e, double *out, int32_t n, void *consumerStream) {
+    return getLaneSpeedLimits(e, out, n, false, consumerStream, "cfx_get_lane_speed_limits_device");
+}
+int32_t cfx_get_lane_speed_limits(cfx_engine *e, double *out, int32_t n) {
+    return getLaneSpeedLimits(e, out, n, true, nullptr, "cfx_get_lane_speed_limits");
 }
 
 int32_t cfx_restore_lane_speed_limits(cfx_engine *e) {
@@ -4345,12 +4280,6 @@ int32_t cfx_restore_lane_speed_limits(cfx_engine *e) {
 }
 
 // ---- per-lane speed and position features (optional entry points of include/cityflow_amd.h, as above)
-int32_t cfx_observe_lanes_device(cfx_engine *e, int32_t *counts, int32_t *waiting, double *speedSum, int32_t *bins,
-                                 const double *edges, int32_t nBins, int32_t perLaneEdges, void *consumerStream);
-int32_t cfx_get_lane_features(cfx_engine *e, double *speedSum, int32_t *bins, const double *edges, int32_t nBins,
-                              int32_t perLaneEdges);
-static_assert(std::is_same<decltype(&cfx_observe_lanes_device), cfx_observe_lanes_device_fn>::value, "cfx_observe_lanes_device");
-static_assert(std::is_same<decltype(&cfx_get_lane_features), cfx_get_lane_features_fn>::value, "cfx_get_lane_features");
 
 static bool laneFeatureArgs(cfx_engine *e, const int32_t *bins, const double *edges, int32_t nBins, const char *what) {
     if (!bins) return true;
@@ -4361,23 +4290,12 @@ static bool laneFeatureArgs(cfx_engine *e, const int32_t *bins, const double *ed
     return true;
 }
 
-static LaneFeatOut laneFeatOut(const cfx_engine *e, int32_t *counts, int32_t *waiting, double *speedSum, int32_t *bins,
-                               const double *edges, int32_t nBins, int32_t perLaneEdges) {
-    const int nEnvs = e->cfg.n_envs > 1 ? e->cfg.n_envs : 1;
-    LaneFeatOut o{counts, waiting, speedSum, bins, bins ? edges : nullptr, bins ? nBins : 0, 0, std::max(e->L / nEnvs, 1)};
-    o.edgeStride = (bins && perLaneEdges) ? nBins + 1 : 0;
-    return o;
-}
-
 // ---- every lane observation through one descriptor (optional entry points of include/cityflow_amd.h, as above); the three
 // entry points above it in the header are forwards onto laneObs
-int32_t cfx_observe_lane_obs_device(cfx_engine *e, const cfx_lane_obs *obs, void *consumerStream);
-int32_t cfx_get_lane_obs(cfx_engine *e, const cfx_lane_obs *obs);
-static_assert(std::is_same<decltype(&cfx_observe_lane_obs_device), cfx_observe_lane_obs_device_fn>::value, "cfx_observe_lane_obs_device");
-static_assert(std::is_same<decltype(&cfx_get_lane_obs), cfx_get_lane_obs_fn>::value, "cfx_get_lane_obs");
 
-// The one path of the lane observations.  toHost: the outputs and edges are host memory (engine-owned device scratch, a
-// synchronous copy back); otherwise device memory, ordered against the caller's stream.  `what` names the entry point in messages.
+// The one path of the lane observations.  toHost: the outputs and edges are host memory (the launch writes the staging arena,
+// and what was asked for is copied back); otherwise device memory, ordered against the caller's stream.  `what` names the
+// entry point in messages.
 static int laneObs(cfx_engine *e, const cfx_lane_obs *obs, bool toHost, void *consumerStream, const char *what) {
     cfx_lane_obs a{};
     int rc;
@@ -4391,13 +4309,17 @@ static int laneObs(cfx_engine *e, const cfx_lane_obs *obs, bool toHost, void *co
     }
     auto fail = [e](const std::string &m) { return e->fail(m); };
     HIP_TRY(hipSetDevice(e->device));
-    if (!toHost) {
-        if ((rc = checkDevicePointers(e, what, {{a.counts, "counts"}, {a.waiting, "waiting"}, {a.speed_sum, "speed_sum"}, {a.bins, "bins"},
-                                                {a.bins ? a.edges : nullptr, "edges"}, {a.front_distance, "front_distance"},
-                                                {a.front_speed, "front_speed"}, {a.front_lane_steps, "front_lane_steps"},
-                                                {a.front_waiting_steps, "front_waiting_steps"}})))
-            return rc;
-    }
+    const int lanesPerEnv = std::max(e->L / (e->cfg.n_envs > 1 ? e->cfg.n_envs : 1), 1);
+    const size_t nL = (size_t) e->L, nB = a.bins ? nL * a.n_bins : 0, nF = front ? nL * a.n_front : 0,
+                 nEdges = a.bins ? (a.per_lane_edges ? (size_t) lanesPerEnv : 1) * (a.n_bins + 1) : 0;
+    cfx_stage::StageLayout s(!toHost);
+    const auto fCounts = s.out(a.counts, "counts", nL), fWaiting = s.out(a.waiting, "waiting", nL);
+    const auto fSum = s.out(a.speed_sum, "speed_sum", nL);
+    const auto fBins = s.out(a.bins, "bins", nB);
+    const auto fEdges = s.in(a.bins ? a.edges : nullptr, "edges", nEdges);  // (edges without bins: not given)
+    const auto fDis = s.out(a.front_distance, "front_distance", nF), fSpeed = s.out(a.front_speed, "front_speed", nF);
+    const auto fSteps = s.out(a.front_lane_steps, "front_lane_steps", nF), fWait = s.out(a.front_waiting_steps, "front_waiting_steps", nF);
+    if ((rc = e->stageCheck(s, what))) return rc;
     if (tracker && !e->tracker[kLaneFlow].on) {
         e->err = std::string(what) + ": front_lane_steps / front_waiting_steps need lane-flow tracking (cfx_lane_flow_enable)";
         return CFX_ERR_STATE;
@@ -4405,47 +4327,21 @@ static int laneObs(cfx_engine *e, const cfx_lane_obs *obs, bool toHost, void *co
     if ((rc = e->settle(false))) return rc;  // (ring layout: a commit deferred to the next step's admission; Lane::history is not read here)
     if ((rc = e->syncTables())) return rc;
     if (e->ring && (rc = e->ringEnsure())) return rc;
-    LaneFeatOut o = laneFeatOut(e, a.counts, a.waiting, a.speed_sum, a.bins, a.edges, a.n_bins, a.per_lane_edges);
-    if (front) {
-        o.nFront = a.n_front;
-        o.frontDis = a.front_distance;
-        o.frontSpeed = a.front_speed;
-        o.frontSteps = a.front_lane_steps;
-        o.frontWait = a.front_waiting_steps;
-    }
+    if ((rc = e->stageOpen(s, consumerStream))) return rc;
+    LaneFeatOut o{s.dev(fCounts), s.dev(fWaiting), s.dev(fSum), s.dev(fBins), s.dev(fEdges), a.bins ? a.n_bins : 0,
+                  (a.bins && a.per_lane_edges) ? a.n_bins + 1 : 0, lanesPerEnv,
+                  front ? a.n_front : 0, s.dev(fDis), s.dev(fSpeed), s.dev(fSteps), s.dev(fWait)};
     if (tracker) {
         o.flowRec = e->flow.rec;
         o.flowVidCap = (int) e->vidCap;
         o.flowTick = e->flow.tick + (e->tracker[kLaneFlow].baselineDue ? 1 : 0);  // (a baseline that is due: no record carries the tick it will take)
         o.flowStep = e->flow.step;
     }
-    if (!toHost) {
-        if ((rc = e->orderAfterCaller((hipStream_t) consumerStream))) return rc;
-        launchLaneFeatures(e, o);
-        HIP_TRY(hipGetLastError());
-        if ((rc = e->orderCallerAfter((hipStream_t) consumerStream))) return rc;
-        e->deviceObserved();
-        return CFX_OK;
-    }
-    // host memory: the launch writes the staging arena, and what was asked for is copied back
-    const size_t nL = (size_t) e->L, nB = a.bins ? nL * a.n_bins : 0, nF = front ? nL * a.n_front : 0,
-                 nEdges = a.bins ? (a.per_lane_edges ? (size_t) o.lanesPerEnv : 1) * (a.n_bins + 1) : 0;
-    cfx_stage::StageLayout s;
-    const auto fCounts = s.out(a.counts, nL), fWaiting = s.out(a.waiting, nL);
-    const auto fSum = s.out(a.speed_sum, nL);
-    const auto fBins = s.out(a.bins, nB);
-    const auto fDis = s.out(a.front_distance, nF), fSpeed = s.out(a.front_speed, nF);
-    const auto fSteps = s.out(a.front_lane_steps, nF), fWait = s.out(a.front_waiting_steps, nF);
-    const auto fEdges = s.in(a.bins ? a.edges : nullptr, nEdges);
-    if ((rc = e->stageOpen(s))) return rc;
-    o.counts = s.dev(fCounts), o.waiting = s.dev(fWaiting);
-    o.speedSum = s.dev(fSum);
-    o.bins = s.dev(fBins), o.edges = s.dev(fEdges);
-    o.frontDis = s.dev(fDis), o.frontSpeed = s.dev(fSpeed);
-    o.frontSteps = s.dev(fSteps), o.frontWait = s.dev(fWait);
     launchLaneFeatures(e, o);
     HIP_TRY(hipGetLastError());
-    return e->stageClose(s);
+    if ((rc = e->stageClose(s, consumerStream))) return rc;
+    if (!toHost) e->deviceObserved();
+    return CFX_OK;
 }
 
 int32_t cfx_observe_lane_obs_device(cfx_engine *e, const cfx_lane_obs *obs, void *consumerStream) {
@@ -4487,8 +4383,6 @@ int32_t cfx_get_lane_features(cfx_engine *e, double *speedSum, int32_t *bins, co
 
 // ---- per-vehicle observations (an optional entry point of include/cityflow_amd.h, as above): k_vehicle_tile_sums, then
 // kr_vehicle_rows / kd_vehicle_rows (cfx_kernels.h has the scheme)
-int32_t cfx_observe_vehicles_device(cfx_engine *e, const cfx_vehicle_rows *rows, void *consumerStream);
-static_assert(std::is_same<decltype(&cfx_observe_vehicles_device), cfx_observe_vehicles_device_fn>::value, "cfx_observe_vehicles_device");
 
 int32_t cfx_observe_vehicles_device(cfx_engine *e, const cfx_vehicle_rows *rows, void *consumerStream) {
     const char *what = "cfx_observe_vehicles_device";
@@ -4516,11 +4410,11 @@ int32_t cfx_observe_vehicles_device(cfx_engine *e, const cfx_vehicle_rows *rows,
     }
     auto fail = [e](const std::string &m) { return e->fail(m); };
     HIP_TRY(hipSetDevice(e->device));
-    if ((rc = checkDevicePointers(e, what, {{a.start, "start"}, {a.count, "count"}, {a.vehicle, "vehicle"}, {a.drivable, "drivable"},
-                                            {a.env, "env"}, {a.distance, "distance"}, {a.speed, "speed"}, {a.leader, "leader"},
-                                            {a.gap, "gap"}, {a.x, "x"}, {a.y, "y"}, {a.dir_x, "dir_x"}, {a.dir_y, "dir_y"},
-                                            {a.length, "length"}, {a.width, "width"}})))
-        return rc;
+    cfx_stage::StageLayout s(true);  // (no host form: the layout is the list of buffers to validate)
+    s.out(a.start, "start"), s.out(a.count, "count"), s.out(a.vehicle, "vehicle"), s.out(a.drivable, "drivable"), s.out(a.env, "env");
+    s.out(a.distance, "distance"), s.out(a.speed, "speed"), s.out(a.leader, "leader"), s.out(a.gap, "gap");
+    s.out(a.x, "x"), s.out(a.y, "y"), s.out(a.dir_x, "dir_x"), s.out(a.dir_y, "dir_y"), s.out(a.length, "length"), s.out(a.width, "width");
+    if ((rc = e->stageCheck(s, what))) return rc;
     if ((rc = e->settle(false))) return rc;  // (ring layout: a commit deferred to the next step's admission)
     if ((rc = e->syncTables())) return rc;
     if (e->ring && (rc = e->ringEnsure())) return rc;
@@ -4558,8 +4452,6 @@ int32_t cfx_observe_vehicles_device(cfx_engine *e, const cfx_vehicle_rows *rows,
 // checked, turned into GeoNode records — segment lengths, their left-to-right sum and the unit vectors, in the reference's
 // expressions and order (this file is compiled without contraction, and the host's sqrt and division round correctly) — and
 // uploaded.  The kernels trust point_start, so nothing is uploaded that has not passed the checks
-int32_t cfx_set_drivable_geometry(cfx_engine *e, const cfx_drivable_geometry *geometry);
-static_assert(std::is_same<decltype(&cfx_set_drivable_geometry), cfx_set_drivable_geometry_fn>::value, "cfx_set_drivable_geometry");
 
 int32_t cfx_set_drivable_geometry(cfx_engine *e, const cfx_drivable_geometry *geometry) {
     const char *what = "cfx_set_drivable_geometry";
@@ -4610,13 +4502,6 @@ int32_t cfx_set_drivable_geometry(cfx_engine *e, const cfx_drivable_geometry *ge
 
 // ---- speed commands for many vehicles at once (optional entry points of include/cityflow_amd.h, as above): k_speeds_claim,
 // k_speeds_apply and, on the dense layout, k_speeds_flag_dense (cfx_kernels.h has the scheme)
-int32_t cfx_set_vehicle_speeds_device(cfx_engine *e, const int32_t *vehicle, const double *speed, int32_t n, int32_t *ignored,
-                                      void *producerStream);
-int32_t cfx_set_vehicle_speeds(cfx_engine *e, const int32_t *vehicle, const double *speed, int32_t n, int32_t *ignored);
-int32_t cfx_get_waiting_custom_speeds(cfx_engine *e, int32_t capacity, int32_t *vid, double *speed, int32_t *n);
-static_assert(std::is_same<decltype(&cfx_get_waiting_custom_speeds), cfx_get_waiting_custom_speeds_fn>::value, "cfx_get_waiting_custom_speeds");
-static_assert(std::is_same<decltype(&cfx_set_vehicle_speeds_device), cfx_set_vehicle_speeds_device_fn>::value, "cfx_set_vehicle_speeds_device");
-static_assert(std::is_same<decltype(&cfx_set_vehicle_speeds), cfx_set_vehicle_speeds_fn>::value, "cfx_set_vehicle_speeds");
 
 // what both forms check first
 static int vehicleSpeedsArgs(cfx_engine *e, const int32_t *vehicle, const double *speed, int32_t n, const char *what) {
@@ -4669,43 +4554,37 @@ static int launchVehicleSpeeds(cfx_engine *e, const int32_t *vehicle, const doub
     return CFX_OK;
 }
 
+static int setVehicleSpeeds(cfx_engine *e, const int32_t *vehicle, const double *speed, int32_t n, int32_t *ignored, bool toHost,
+                            void *stream, const char *what) {
+    if (!e) return CFX_ERR_INVALID;
+    int rc;
+    if ((rc = vehicleSpeedsArgs(e, vehicle, speed, n, what))) return rc;
+    if (toHost) {  // (no rows: the host form is done without touching the device)
+        if (ignored) *ignored = 0;
+        if (n == 0) return CFX_OK;
+    }
+    auto fail = [e](const std::string &m) { return e->fail(m); };
+    HIP_TRY(hipSetDevice(e->device));
+    int32_t count = 0;  // (the host form's kernels always count, into a cell of the arena)
+    cfx_stage::StageLayout s(!toHost);
+    const auto fVehicle = s.in(n ? vehicle : nullptr, "vehicle", (size_t) n);  // (no rows: the arrays are not looked at)
+    const auto fSpeed = s.in(n ? speed : nullptr, "speed", (size_t) n);
+    const auto fIgnored = s.out(toHost ? &count : ignored, "ignored", 1);
+    if ((rc = e->stageCheck(s, what))) return rc;
+    if (n == 0 && !ignored) return CFX_OK;  // (the device form with nothing to do)
+    if ((rc = e->settle(false))) return rc;  // (ring layout: a commit deferred to the next step's admission)
+    if ((rc = e->stageOpen(s, stream))) return rc;
+    if ((rc = launchVehicleSpeeds(e, s.dev(fVehicle), s.dev(fSpeed), n, s.dev(fIgnored)))) return rc;
+    if ((rc = e->stageClose(s, stream))) return rc;  // (the count is there; a device form's rows may be overwritten)
+    if (toHost && ignored) *ignored = count;
+    return CFX_OK;
+}
 int32_t cfx_set_vehicle_speeds_device(cfx_engine *e, const int32_t *vehicle, const double *speed, int32_t n, int32_t *ignored,
                                       void *producerStream) {
-    const char *what = "cfx_set_vehicle_speeds_device";
-    if (!e) return CFX_ERR_INVALID;
-    int rc;
-    if ((rc = vehicleSpeedsArgs(e, vehicle, speed, n, what))) return rc;
-    auto fail = [e](const std::string &m) { return e->fail(m); };
-    HIP_TRY(hipSetDevice(e->device));
-    if ((rc = checkDevicePointers(e, what, {{n ? vehicle : nullptr, "vehicle"}, {n ? speed : nullptr, "speed"}, {ignored, "ignored"}})))
-        return rc;
-    if (n == 0 && !ignored) return CFX_OK;
-    if ((rc = e->settle(false))) return rc;  // (ring layout: a commit deferred to the next step's admission)
-    if ((rc = e->orderAfterCaller((hipStream_t) producerStream))) return rc;
-    if ((rc = launchVehicleSpeeds(e, vehicle, speed, n, ignored))) return rc;
-    return e->orderCallerAfter((hipStream_t) producerStream);  // (the count is there; the rows may be overwritten)
+    return setVehicleSpeeds(e, vehicle, speed, n, ignored, false, producerStream, "cfx_set_vehicle_speeds_device");
 }
-
 int32_t cfx_set_vehicle_speeds(cfx_engine *e, const int32_t *vehicle, const double *speed, int32_t n, int32_t *ignored) {
-    const char *what = "cfx_set_vehicle_speeds";
-    if (!e) return CFX_ERR_INVALID;
-    int rc;
-    if ((rc = vehicleSpeedsArgs(e, vehicle, speed, n, what))) return rc;
-    if (ignored) *ignored = 0;
-    if (n == 0) return CFX_OK;
-    auto fail = [e](const std::string &m) { return e->fail(m); };
-    HIP_TRY(hipSetDevice(e->device));
-    if ((rc = e->settle(false))) return rc;
-    int32_t count = 0;
-    cfx_stage::StageLayout s;
-    const auto fVehicle = s.in(vehicle, (size_t) n);
-    const auto fSpeed = s.in(speed, (size_t) n);
-    const auto fCount = s.out(&count, 1);
-    if ((rc = e->stageOpen(s))) return rc;
-    if ((rc = launchVehicleSpeeds(e, s.dev(fVehicle), s.dev(fSpeed), n, s.dev(fCount)))) return rc;
-    if ((rc = e->stageClose(s))) return rc;
-    if (ignored) *ignored = count;
-    return CFX_OK;
+    return setVehicleSpeeds(e, vehicle, speed, n, ignored, true, nullptr, "cfx_set_vehicle_speeds");
 }
 
 // The custom speeds of the vehicles still in an entry buffer (state 0 with pendingCustom): three copies of the vehicle tables
@@ -4743,15 +4622,6 @@ int32_t cfx_get_waiting_custom_speeds(cfx_engine *e, int32_t capacity, int32_t *
 
 // ---- route changes for many vehicles at once, and the routes they hold (optional entry points of include/cityflow_amd.h, as
 // above): k_routes_claim and kr_routes_apply, or k_routes_superseded and k_routes_apply_dense (cfx_kernels.h has the scheme)
-int32_t cfx_set_vehicle_routes_device(cfx_engine *e, const int32_t *vehicle, const int32_t *route, int32_t n, int32_t *status,
-                                      int32_t *ignored, void *producerStream);
-int32_t cfx_set_vehicle_routes(cfx_engine *e, const int32_t *vehicle, const int32_t *route, int32_t n, int32_t *status, int32_t *ignored);
-int32_t cfx_get_vehicle_routes_device(cfx_engine *e, const int32_t *vehicle, int32_t n, int32_t *routeOut, void *consumerStream);
-int32_t cfx_get_vehicle_routes(cfx_engine *e, const int32_t *vehicle, int32_t n, int32_t *routeOut);
-static_assert(std::is_same<decltype(&cfx_set_vehicle_routes_device), cfx_set_vehicle_routes_device_fn>::value, "cfx_set_vehicle_routes_device");
-static_assert(std::is_same<decltype(&cfx_set_vehicle_routes), cfx_set_vehicle_routes_fn>::value, "cfx_set_vehicle_routes");
-static_assert(std::is_same<decltype(&cfx_get_vehicle_routes_device), cfx_get_vehicle_routes_device_fn>::value, "cfx_get_vehicle_routes_device");
-static_assert(std::is_same<decltype(&cfx_get_vehicle_routes), cfx_get_vehicle_routes_fn>::value, "cfx_get_vehicle_routes");
 
 // what the four forms check first (`second`: the route handles, or the output of the read)
 static int vehicleRoutesArgs(cfx_engine *e, const void *vehicle, const void *second, bool vehicleNeeded, int32_t n, const char *what) {
@@ -4795,45 +4665,39 @@ static int launchVehicleRoutes(cfx_engine *e, const int32_t *vehicle, const int3
     return CFX_OK;
 }
 
-int32_t cfx_set_vehicle_routes_device(cfx_engine *e, const int32_t *vehicle, const int32_t *route, int32_t n, int32_t *status,
-                                      int32_t *ignored, void *producerStream) {
-    const char *what = "cfx_set_vehicle_routes_device";
+// (the shape of setVehicleSpeeds above, comment by comment)
+static int setVehicleRoutes(cfx_engine *e, const int32_t *vehicle, const int32_t *route, int32_t n, int32_t *status, int32_t *ignored,
+                            bool toHost, void *stream, const char *what) {
     if (!e) return CFX_ERR_INVALID;
     int rc;
     if ((rc = vehicleRoutesArgs(e, vehicle, route, true, n, what))) return rc;
+    if (toHost) {
+        if (ignored) *ignored = 0;
+        if (n == 0) return CFX_OK;
+    }
     auto fail = [e](const std::string &m) { return e->fail(m); };
     HIP_TRY(hipSetDevice(e->device));
-    if ((rc = checkDevicePointers(e, what, {{n ? vehicle : nullptr, "vehicle"}, {n ? route : nullptr, "route"},
-                                            {n ? status : nullptr, "status"}, {ignored, "ignored"}})))
-        return rc;
+    int32_t count = 0;
+    cfx_stage::StageLayout s(!toHost);
+    const auto fVehicle = s.in(n ? vehicle : nullptr, "vehicle", (size_t) n);
+    const auto fRoute = s.in(n ? route : nullptr, "route", (size_t) n);
+    const auto fStatus = s.out(n ? status : nullptr, "status", (size_t) n);
+    const auto fIgnored = s.out(toHost ? &count : ignored, "ignored", 1);
+    if ((rc = e->stageCheck(s, what))) return rc;
     if (n == 0 && !ignored) return CFX_OK;
     if ((rc = e->settle(false))) return rc;  // (ring layout: a commit deferred to the next step's admission)
-    if ((rc = e->orderAfterCaller((hipStream_t) producerStream))) return rc;
-    if ((rc = launchVehicleRoutes(e, vehicle, route, n, status, ignored))) return rc;
-    return e->orderCallerAfter((hipStream_t) producerStream);  // (status and the count are there; the rows may be overwritten)
-}
-
-int32_t cfx_set_vehicle_routes(cfx_engine *e, const int32_t *vehicle, const int32_t *route, int32_t n, int32_t *status, int32_t *ignored) {
-    const char *what = "cfx_set_vehicle_routes";
-    if (!e) return CFX_ERR_INVALID;
-    int rc;
-    if ((rc = vehicleRoutesArgs(e, vehicle, route, true, n, what))) return rc;
-    if (ignored) *ignored = 0;
-    if (n == 0) return CFX_OK;
-    auto fail = [e](const std::string &m) { return e->fail(m); };
-    HIP_TRY(hipSetDevice(e->device));
-    if ((rc = e->settle(false))) return rc;
-    int32_t count = 0;
-    cfx_stage::StageLayout s;
-    const auto fVehicle = s.in(vehicle, (size_t) n);
-    const auto fRoute = s.in(route, (size_t) n);
-    const auto fStatus = s.out(status, (size_t) n);
-    const auto fCount = s.out(&count, 1);
-    if ((rc = e->stageOpen(s))) return rc;
-    if ((rc = launchVehicleRoutes(e, s.dev(fVehicle), s.dev(fRoute), n, s.dev(fStatus), s.dev(fCount)))) return rc;
-    if ((rc = e->stageClose(s))) return rc;
-    if (ignored) *ignored = count;
+    if ((rc = e->stageOpen(s, stream))) return rc;
+    if ((rc = launchVehicleRoutes(e, s.dev(fVehicle), s.dev(fRoute), n, s.dev(fStatus), s.dev(fIgnored)))) return rc;
+    if ((rc = e->stageClose(s, stream))) return rc;  // (status and the count are there; a device form's rows may be overwritten)
+    if (toHost && ignored) *ignored = count;
     return CFX_OK;
+}
+int32_t cfx_set_vehicle_routes_device(cfx_engine *e, const int32_t *vehicle, const int32_t *route, int32_t n, int32_t *status,
+                                      int32_t *ignored, void *producerStream) {
+    return setVehicleRoutes(e, vehicle, route, n, status, ignored, false, producerStream, "cfx_set_vehicle_routes_device");
+}
+int32_t cfx_set_vehicle_routes(cfx_engine *e, const int32_t *vehicle, const int32_t *route, int32_t n, int32_t *status, int32_t *ignored) {
+    return setVehicleRoutes(e, vehicle, route, n, status, ignored, true, nullptr, "cfx_set_vehicle_routes");
 }
 
 // the kernel of one read on the engine's stream; vehicle may be null (the numbers 0 .. n-1).  The caller has settled; n > 0.
@@ -4847,48 +4711,32 @@ static int launchGetVehicleRoutes(cfx_engine *e, const int32_t *vehicle, int32_t
     return CFX_OK;
 }
 
-int32_t cfx_get_vehicle_routes_device(cfx_engine *e, const int32_t *vehicle, int32_t n, int32_t *routeOut, void *consumerStream) {
-    const char *what = "cfx_get_vehicle_routes_device";
+static int getVehicleRoutes(cfx_engine *e, const int32_t *vehicle, int32_t n, int32_t *routeOut, bool toHost, void *stream, const char *what) {
     if (!e) return CFX_ERR_INVALID;
     int rc;
-    if ((rc = vehicleRoutesArgs(e, vehicle, routeOut, true, n, what))) return rc;
+    // (the host form alone reads the numbers 0 .. n-1 for a null `vehicle`)
+    if ((rc = vehicleRoutesArgs(e, vehicle, routeOut, !toHost, n, what))) return rc;
+    if (toHost && n == 0) return CFX_OK;  // (as the setters': done without touching the device)
     auto fail = [e](const std::string &m) { return e->fail(m); };
     HIP_TRY(hipSetDevice(e->device));
-    if ((rc = checkDevicePointers(e, what, {{n ? vehicle : nullptr, "vehicle"}, {n ? routeOut : nullptr, "route_out"}}))) return rc;
+    cfx_stage::StageLayout s(!toHost);
+    const auto fVehicle = s.in(n ? vehicle : nullptr, "vehicle", (size_t) n);
+    const auto fOut = s.out(n ? routeOut : nullptr, "route_out", (size_t) n);
+    if ((rc = e->stageCheck(s, what))) return rc;
     if (n == 0) return CFX_OK;
     if ((rc = e->settle(false))) return rc;
-    if ((rc = e->orderAfterCaller((hipStream_t) consumerStream))) return rc;
-    if ((rc = launchGetVehicleRoutes(e, vehicle, n, routeOut))) return rc;
-    return e->orderCallerAfter((hipStream_t) consumerStream);
-}
-
-int32_t cfx_get_vehicle_routes(cfx_engine *e, const int32_t *vehicle, int32_t n, int32_t *routeOut) {
-    const char *what = "cfx_get_vehicle_routes";
-    if (!e) return CFX_ERR_INVALID;
-    int rc;
-    if ((rc = vehicleRoutesArgs(e, vehicle, routeOut, false, n, what))) return rc;
-    if (n == 0) return CFX_OK;
-    auto fail = [e](const std::string &m) { return e->fail(m); };
-    HIP_TRY(hipSetDevice(e->device));
-    if ((rc = e->settle(false))) return rc;
-    cfx_stage::StageLayout s;
-    const auto fVehicle = s.in(vehicle, (size_t) n);
-    const auto fOut = s.out(routeOut, (size_t) n);
-    if ((rc = e->stageOpen(s))) return rc;
+    if ((rc = e->stageOpen(s, stream))) return rc;
     if ((rc = launchGetVehicleRoutes(e, s.dev(fVehicle), n, s.dev(fOut)))) return rc;
-    return e->stageClose(s);
+    return e->stageClose(s, stream);
+}
+int32_t cfx_get_vehicle_routes_device(cfx_engine *e, const int32_t *vehicle, int32_t n, int32_t *routeOut, void *consumerStream) {
+    return getVehicleRoutes(e, vehicle, n, routeOut, false, consumerStream, "cfx_get_vehicle_routes_device");
+}
+int32_t cfx_get_vehicle_routes(cfx_engine *e, const int32_t *vehicle, int32_t n, int32_t *routeOut) {
+    return getVehicleRoutes(e, vehicle, n, routeOut, true, nullptr, "cfx_get_vehicle_routes");
 }
 
 // ---- per-intersection movement and phase observations (optional entry points of include/cityflow_amd.h, as above)
-int32_t cfx_observe_intersections_device(cfx_engine *e, int32_t *phase, double *remain, int32_t *in, int32_t *inWaiting, int32_t *out,
-                                         int32_t *inside, int32_t *pressure, int32_t maxRoadLinks, int32_t maxPhases,
-                                         void *consumerStream);
-int32_t cfx_get_intersection_features(cfx_engine *e, int32_t *phase, double *remain, int32_t *in, int32_t *inWaiting, int32_t *out,
-                                      int32_t *inside, int32_t *pressure, int32_t maxRoadLinks, int32_t maxPhases);
-static_assert(std::is_same<decltype(&cfx_observe_intersections_device), cfx_observe_intersections_device_fn>::value,
-              "cfx_observe_intersections_device");
-static_assert(std::is_same<decltype(&cfx_get_intersection_features), cfx_get_intersection_features_fn>::value,
-              "cfx_get_intersection_features");
 
 // The static index of InterFeatOut from the network tables the device holds (read back once: the engine keeps no host copy of
 // them).  Device memory: 16 (I M + 1) bytes of rows, 4 bytes per in-lane, out-lane and laneLink entry, 4 I P ceil(M / 32) of masks.
@@ -5009,59 +4857,42 @@ static int interPrepare(cfx_engine *e, int32_t maxRoadLinks, int32_t maxPhases, 
     return CFX_OK;
 }
 
+static int interFeatures(cfx_engine *e, int32_t *phase, double *remain, int32_t *in, int32_t *inWaiting, int32_t *out, int32_t *inside,
+                         int32_t *pressure, int32_t maxRoadLinks, int32_t maxPhases, bool toHost, void *stream, const char *what) {
+    if (!e || (!phase && !remain && !in && !inWaiting && !out && !inside && !pressure)) return CFX_ERR_INVALID;
+    auto fail = [e](const std::string &m) { return e->fail(m); };
+    HIP_TRY(hipSetDevice(e->device));
+    int rc;
+    const size_t nI = (size_t) e->I;
+    cfx_stage::StageLayout s(!toHost);
+    const auto fPhase = s.out(phase, "phase", nI);
+    const auto fRemain = s.out(remain, "remain", nI);
+    const auto fIn = s.out(in, "in"), fWait = s.out(inWaiting, "in_waiting"), fOut = s.out(out, "out"), fInside = s.out(inside, "inside"),
+               fPressure = s.out(pressure, "phase_pressure");
+    if ((rc = e->stageCheck(s, what))) return rc;
+    if ((rc = interPrepare(e, maxRoadLinks, maxPhases, what))) return rc;
+    const size_t nM = nI * e->interTab.M, nP = nI * e->interTab.P;  // (the row lengths: known once the index is built)
+    s.count(fIn, nM), s.count(fWait, nM), s.count(fOut, nM), s.count(fInside, nM), s.count(fPressure, nP);
+    if ((rc = e->stageOpen(s, stream))) return rc;
+    launchInterFeatures(e, s.dev(fPhase), s.dev(fRemain), s.dev(fIn), s.dev(fWait), s.dev(fOut), s.dev(fInside), s.dev(fPressure));
+    HIP_TRY(hipGetLastError());
+    if ((rc = e->stageClose(s, stream))) return rc;
+    if (!toHost) e->deviceObserved();
+    return CFX_OK;
+}
 int32_t cfx_observe_intersections_device(cfx_engine *e, int32_t *phase, double *remain, int32_t *in, int32_t *inWaiting, int32_t *out,
                                          int32_t *inside, int32_t *pressure, int32_t maxRoadLinks, int32_t maxPhases,
                                          void *consumerStream) {
-    if (!e || (!phase && !remain && !in && !inWaiting && !out && !inside && !pressure)) return CFX_ERR_INVALID;
-    auto fail = [e](const std::string &m) { return e->fail(m); };
-    HIP_TRY(hipSetDevice(e->device));
-    int rc;
-    if ((rc = checkDevicePointers(e, "cfx_observe_intersections_device",
-                                  {{phase, "phase"}, {remain, "remain"}, {in, "in"}, {inWaiting, "in_waiting"}, {out, "out"},
-                                   {inside, "inside"}, {pressure, "phase_pressure"}})))
-        return rc;
-    if ((rc = interPrepare(e, maxRoadLinks, maxPhases, "cfx_observe_intersections_device"))) return rc;
-    if ((rc = e->orderAfterCaller((hipStream_t) consumerStream))) return rc;
-    launchInterFeatures(e, phase, remain, in, inWaiting, out, inside, pressure);
-    HIP_TRY(hipGetLastError());
-    if ((rc = e->orderCallerAfter((hipStream_t) consumerStream))) return rc;
-    e->deviceObserved();
-    return CFX_OK;
+    return interFeatures(e, phase, remain, in, inWaiting, out, inside, pressure, maxRoadLinks, maxPhases, false, consumerStream,
+                         "cfx_observe_intersections_device");
 }
-
 int32_t cfx_get_intersection_features(cfx_engine *e, int32_t *phase, double *remain, int32_t *in, int32_t *inWaiting, int32_t *out,
                                       int32_t *inside, int32_t *pressure, int32_t maxRoadLinks, int32_t maxPhases) {
-    if (!e || (!phase && !remain && !in && !inWaiting && !out && !inside && !pressure)) return CFX_ERR_INVALID;
-    auto fail = [e](const std::string &m) { return e->fail(m); };
-    HIP_TRY(hipSetDevice(e->device));
-    int rc;
-    if ((rc = interPrepare(e, maxRoadLinks, maxPhases, "cfx_get_intersection_features"))) return rc;
-    const size_t nI = (size_t) e->I, nM = nI * e->interTab.M, nP = nI * e->interTab.P;
-    cfx_stage::StageLayout s;
-    const auto fPhase = s.out(phase, nI);
-    const auto fRemain = s.out(remain, nI);
-    const auto fIn = s.out(in, nM), fWait = s.out(inWaiting, nM), fOut = s.out(out, nM), fInside = s.out(inside, nM),
-               fPressure = s.out(pressure, nP);
-    if ((rc = e->stageOpen(s))) return rc;
-    launchInterFeatures(e, s.dev(fPhase), s.dev(fRemain), s.dev(fIn), s.dev(fWait), s.dev(fOut), s.dev(fInside), s.dev(fPressure));
-    HIP_TRY(hipGetLastError());
-    return e->stageClose(s);
+    return interFeatures(e, phase, remain, in, inWaiting, out, inside, pressure, maxRoadLinks, maxPhases, true, nullptr,
+                         "cfx_get_intersection_features");
 }
 
 // ---- per-lane flow and waiting-time statistics across steps (optional entry points of include/cityflow_amd.h, as above)
-int32_t cfx_lane_flow_enable(cfx_engine *e, int32_t on);
-int32_t cfx_observe_lane_flow_device(cfx_engine *e, int32_t *entered, int32_t *left, int64_t *leftSteps, int64_t *leftWaitingSteps,
-                                     int64_t *waitingSteps, int32_t *maxWaitingSteps, int32_t reset, void *consumerStream);
-int32_t cfx_get_lane_flow(cfx_engine *e, int32_t *entered, int32_t *left, int64_t *leftSteps, int64_t *leftWaitingSteps,
-                          int64_t *waitingSteps, int32_t *maxWaitingSteps, int32_t reset);
-int32_t cfx_lane_flow_get_state(cfx_engine *e, int32_t *records, int32_t nVehicles, cfx_lane_flow_lane *lanes, int32_t *tick);
-int32_t cfx_lane_flow_set_state(cfx_engine *e, const int32_t *records, int32_t nVehicles, const cfx_lane_flow_lane *lanes, int32_t tick);
-static_assert(std::is_same<decltype(&cfx_lane_flow_enable), cfx_lane_flow_enable_fn>::value, "cfx_lane_flow_enable");
-static_assert(std::is_same<decltype(&cfx_observe_lane_flow_device), cfx_observe_lane_flow_device_fn>::value, "cfx_observe_lane_flow_device");
-static_assert(std::is_same<decltype(&cfx_get_lane_flow), cfx_get_lane_flow_fn>::value, "cfx_get_lane_flow");
-static_assert(std::is_same<decltype(&cfx_lane_flow_get_state), cfx_lane_flow_get_state_fn>::value, "cfx_lane_flow_get_state");
-static_assert(std::is_same<decltype(&cfx_lane_flow_set_state), cfx_lane_flow_set_state_fn>::value, "cfx_lane_flow_set_state");
-static_assert(sizeof(cfx_lane_flow_lane) == 48, "cfx_lane_flow_lane");
 
 // ---- what the entry points of the three trackers share
 static int trackerRequire(cfx_engine *e, int which, const char *what) {
@@ -5110,10 +4941,10 @@ int32_t cfx_observe_lane_flow_device(cfx_engine *e, int32_t *entered, int32_t *l
     auto fail = [e](const std::string &m) { return e->fail(m); };
     HIP_TRY(hipSetDevice(e->device));
     int rc;
-    if ((rc = checkDevicePointers(e, "cfx_observe_lane_flow_device",
-                                  {{entered, "entered"}, {left, "left"}, {leftSteps, "left_steps"}, {leftWaitingSteps, "left_waiting_steps"},
-                                   {waitingSteps, "waiting_steps"}, {maxWaitingSteps, "max_waiting_steps"}})))
-        return rc;
+    cfx_stage::StageLayout s(true);  // (the host form decodes records on the host: the layout is the list of buffers to validate)
+    s.out(entered, "entered"), s.out(left, "left"), s.out(leftSteps, "left_steps"), s.out(leftWaitingSteps, "left_waiting_steps");
+    s.out(waitingSteps, "waiting_steps"), s.out(maxWaitingSteps, "max_waiting_steps");
+    if ((rc = e->stageCheck(s, "cfx_observe_lane_flow_device"))) return rc;
     if ((rc = trackerPrepare(e, kLaneFlow, "cfx_observe_lane_flow_device"))) return rc;
     if ((rc = e->orderAfterCaller((hipStream_t) consumerStream))) return rc;
     launchLaneFlowDrain(e, LaneFlowOut{entered, left, leftSteps, leftWaitingSteps, waitingSteps, maxWaitingSteps}, reset);
@@ -5175,20 +5006,6 @@ int32_t cfx_lane_flow_set_state(cfx_engine *e, const int32_t *records, int32_t n
 }
 
 // ---- virtual loop detectors (optional entry points of include/cityflow_amd.h, as above)
-int32_t cfx_detectors_define(cfx_engine *e, const int32_t *lane, const double *start, const double *end, int32_t n);
-int32_t cfx_detectors_enable(cfx_engine *e, int32_t on);
-int32_t cfx_observe_detectors_device(cfx_engine *e, const cfx_detectors_out *out, int32_t reset, void *consumerStream);
-int32_t cfx_get_detectors(cfx_engine *e, const cfx_detectors_out *out, int32_t reset);
-int32_t cfx_detectors_get_state(cfx_engine *e, int32_t *records, int32_t nVehicles, cfx_detector *detectors, int32_t nDetectors, int32_t *tick);
-int32_t cfx_detectors_set_state(cfx_engine *e, const int32_t *records, int32_t nVehicles, const cfx_detector *detectors, int32_t nDetectors,
-                                int32_t tick);
-static_assert(std::is_same<decltype(&cfx_detectors_define), cfx_detectors_define_fn>::value, "cfx_detectors_define");
-static_assert(std::is_same<decltype(&cfx_detectors_enable), cfx_detectors_enable_fn>::value, "cfx_detectors_enable");
-static_assert(std::is_same<decltype(&cfx_observe_detectors_device), cfx_observe_detectors_device_fn>::value, "cfx_observe_detectors_device");
-static_assert(std::is_same<decltype(&cfx_get_detectors), cfx_get_detectors_fn>::value, "cfx_get_detectors");
-static_assert(std::is_same<decltype(&cfx_detectors_get_state), cfx_detectors_get_state_fn>::value, "cfx_detectors_get_state");
-static_assert(std::is_same<decltype(&cfx_detectors_set_state), cfx_detectors_set_state_fn>::value, "cfx_detectors_set_state");
-static_assert(sizeof(cfx_detector) == 64, "cfx_detector");
 
 int32_t cfx_detectors_define(cfx_engine *e, const int32_t *lane, const double *start, const double *end, int32_t n) {
     if (!e) return CFX_ERR_INVALID;
@@ -5235,10 +5052,10 @@ int32_t cfx_observe_detectors_device(cfx_engine *e, const cfx_detectors_out *out
     auto fail = [e](const std::string &m) { return e->fail(m); };
     HIP_TRY(hipSetDevice(e->device));
     int rc;
-    if ((rc = checkDevicePointers(e, "cfx_observe_detectors_device",
-                                  {{o.passed, "passed"}, {o.occupied_steps, "occupied_steps"}, {o.vehicle_steps, "vehicle_steps"},
-                                   {o.waiting_vehicle_steps, "waiting_vehicle_steps"}, {o.speed_sum, "speed_sum"}, {o.count, "count"}})))
-        return rc;
+    cfx_stage::StageLayout s(true);  // (as cfx_observe_lane_flow_device)
+    s.out(o.passed, "passed"), s.out(o.occupied_steps, "occupied_steps"), s.out(o.vehicle_steps, "vehicle_steps");
+    s.out(o.waiting_vehicle_steps, "waiting_vehicle_steps"), s.out(o.speed_sum, "speed_sum"), s.out(o.count, "count");
+    if ((rc = e->stageCheck(s, "cfx_observe_detectors_device"))) return rc;
     if ((rc = trackerPrepare(e, kDetectors, "cfx_observe_detectors_device"))) return rc;
     if ((rc = e->orderAfterCaller((hipStream_t) consumerStream))) return rc;
     launchDetectorsDrain(e, o, reset);
@@ -5302,17 +5119,6 @@ int32_t cfx_detectors_set_state(cfx_engine *e, const int32_t *records, int32_t n
 }
 
 // ---- per-environment trip statistics across steps (optional entry points of include/cityflow_amd.h, as above)
-int32_t cfx_trip_stats_enable(cfx_engine *e, int32_t on);
-int32_t cfx_observe_trip_stats_device(cfx_engine *e, const cfx_trip_stats_out *out, void *consumerStream);
-int32_t cfx_get_trip_stats(cfx_engine *e, const cfx_trip_stats_out *out);
-int32_t cfx_trip_stats_get_state(cfx_engine *e, cfx_trip_stats_env *envs, int32_t nEnvs);
-int32_t cfx_trip_stats_set_state(cfx_engine *e, const cfx_trip_stats_env *envs, int32_t nEnvs);
-static_assert(std::is_same<decltype(&cfx_trip_stats_enable), cfx_trip_stats_enable_fn>::value, "cfx_trip_stats_enable");
-static_assert(std::is_same<decltype(&cfx_observe_trip_stats_device), cfx_observe_trip_stats_device_fn>::value, "cfx_observe_trip_stats_device");
-static_assert(std::is_same<decltype(&cfx_get_trip_stats), cfx_get_trip_stats_fn>::value, "cfx_get_trip_stats");
-static_assert(std::is_same<decltype(&cfx_trip_stats_get_state), cfx_trip_stats_get_state_fn>::value, "cfx_trip_stats_get_state");
-static_assert(std::is_same<decltype(&cfx_trip_stats_set_state), cfx_trip_stats_set_state_fn>::value, "cfx_trip_stats_set_state");
-static_assert(sizeof(cfx_trip_stats_env) == 56, "cfx_trip_stats_env");
 
 int32_t cfx_trip_stats_enable(cfx_engine *e, int32_t on) { return e ? e->trackerEnable(kTrips, on) : CFX_ERR_INVALID; }
 
@@ -5330,12 +5136,12 @@ int32_t cfx_observe_trip_stats_device(cfx_engine *e, const cfx_trip_stats_out *o
     auto fail = [e](const std::string &m) { return e->fail(m); };
     HIP_TRY(hipSetDevice(e->device));
     int rc;
-    if ((rc = checkDevicePointers(e, "cfx_observe_trip_stats_device",
-                                  {{o.entered, "entered"}, {o.admitted, "admitted"}, {o.admitted_buffer_steps, "admitted_buffer_steps"},
-                                   {o.finished, "finished"}, {o.finished_travel_steps, "finished_travel_steps"}, {o.in_system, "in_system"},
-                                   {o.buffered, "buffered"}, {o.in_system_travel_steps, "in_system_travel_steps"},
-                                   {o.average_travel_time, "average_travel_time"}})))
-        return rc;
+    cfx_stage::StageLayout s(true);  // (as cfx_observe_lane_flow_device)
+    s.out(o.entered, "entered"), s.out(o.admitted, "admitted"), s.out(o.admitted_buffer_steps, "admitted_buffer_steps");
+    s.out(o.finished, "finished"), s.out(o.finished_travel_steps, "finished_travel_steps"), s.out(o.in_system, "in_system");
+    s.out(o.buffered, "buffered"), s.out(o.in_system_travel_steps, "in_system_travel_steps");
+    s.out(o.average_travel_time, "average_travel_time");
+    if ((rc = e->stageCheck(s, "cfx_observe_trip_stats_device"))) return rc;
     if ((rc = trackerPrepare(e, kTrips, "cfx_observe_trip_stats_device"))) return rc;
     if ((rc = e->orderAfterCaller((hipStream_t) consumerStream))) return rc;
     launchTripDrain(e, o);
@@ -5398,14 +5204,6 @@ int32_t cfx_trip_stats_set_state(cfx_engine *e, const cfx_trip_stats_env *envs, 
 }
 
 // ---- the trip log: one row per finished vehicle, kept by the trip tracker (optional entry points of include/cityflow_amd.h)
-int32_t cfx_trip_log_enable(cfx_engine *e, int32_t capacity);
-int32_t cfx_observe_trip_log_device(cfx_engine *e, const cfx_trip_log_out *out, int32_t reset, void *consumerStream);
-int32_t cfx_get_trip_log(cfx_engine *e, const cfx_trip_log_out *out, int32_t reset);
-int32_t cfx_trip_log_set_state(cfx_engine *e, const cfx_trip_log_out *rows, int32_t n, int32_t dropped);
-static_assert(std::is_same<decltype(&cfx_trip_log_enable), cfx_trip_log_enable_fn>::value, "cfx_trip_log_enable");
-static_assert(std::is_same<decltype(&cfx_observe_trip_log_device), cfx_observe_trip_log_device_fn>::value, "cfx_observe_trip_log_device");
-static_assert(std::is_same<decltype(&cfx_get_trip_log), cfx_get_trip_log_fn>::value, "cfx_get_trip_log");
-static_assert(std::is_same<decltype(&cfx_trip_log_set_state), cfx_trip_log_set_state_fn>::value, "cfx_trip_log_set_state");
 
 int32_t cfx_trip_log_enable(cfx_engine *e, int32_t capacity) {
     if (!e) return CFX_ERR_INVALID;
@@ -5454,47 +5252,30 @@ static bool tripLogNoneGiven(const cfx_trip_log_out &o) {
            !o.travel_steps;
 }
 
-int32_t cfx_observe_trip_log_device(cfx_engine *e, const cfx_trip_log_out *out, int32_t reset, void *consumerStream) {
+static int tripLog(cfx_engine *e, const cfx_trip_log_out *out, int32_t reset, bool toHost, void *stream, const char *what) {
     if (!e || !out || tripLogNoneGiven(*out)) return CFX_ERR_INVALID;
-    const cfx_trip_log_out &o = *out;
     auto fail = [e](const std::string &m) { return e->fail(m); };
     HIP_TRY(hipSetDevice(e->device));
     int rc;
-    if ((rc = checkDevicePointers(e, "cfx_observe_trip_log_device",
-                                  {{o.count, "count"}, {o.dropped, "dropped"}, {o.env, "env"}, {o.vehicle, "vehicle"},
-                                   {o.origin_road, "origin_road"}, {o.destination_road, "destination_road"}, {o.enter_step, "enter_step"},
-                                   {o.finish_step, "finish_step"}, {o.travel_steps, "travel_steps"}})))
-        return rc;
-    if ((rc = tripLogPrepare(e, "cfx_observe_trip_log_device"))) return rc;
-    if ((rc = e->orderAfterCaller((hipStream_t) consumerStream))) return rc;
+    const size_t cap = (size_t) e->trip.logCap;  // (0 without a log: refused below)
+    cfx_stage::StageLayout s(!toHost);
+    const auto fCount = s.out(out->count, "count", 1), fDropped = s.out(out->dropped, "dropped", 1), fEnv = s.out(out->env, "env", cap),
+               fVehicle = s.out(out->vehicle, "vehicle", cap), fOrigin = s.out(out->origin_road, "origin_road", cap),
+               fDest = s.out(out->destination_road, "destination_road", cap), fEnter = s.out(out->enter_step, "enter_step", cap),
+               fFinish = s.out(out->finish_step, "finish_step", cap), fTravel = s.out(out->travel_steps, "travel_steps", cap);
+    if ((rc = e->stageCheck(s, what))) return rc;
+    if ((rc = tripLogPrepare(e, what))) return rc;
+    if ((rc = e->stageOpen(s, stream))) return rc;
+    const cfx_trip_log_out o{s.dev(fCount), s.dev(fDropped), s.dev(fEnv),   s.dev(fVehicle), s.dev(fOrigin),
+                             s.dev(fDest),  s.dev(fEnter),   s.dev(fFinish), s.dev(fTravel)};
     if ((rc = launchTripLogDrain(e, o, reset))) return rc;
-    return e->orderCallerAfter((hipStream_t) consumerStream);
+    return e->stageClose(s, stream);
 }
-
+int32_t cfx_observe_trip_log_device(cfx_engine *e, const cfx_trip_log_out *out, int32_t reset, void *consumerStream) {
+    return tripLog(e, out, reset, false, consumerStream, "cfx_observe_trip_log_device");
+}
 int32_t cfx_get_trip_log(cfx_engine *e, const cfx_trip_log_out *out, int32_t reset) {
-    if (!e || !out || tripLogNoneGiven(*out)) return CFX_ERR_INVALID;
-    auto fail = [e](const std::string &m) { return e->fail(m); };
-    HIP_TRY(hipSetDevice(e->device));
-    int rc;
-    if ((rc = tripLogPrepare(e, "cfx_get_trip_log"))) return rc;
-    const size_t cap = (size_t) e->trip.logCap;
-    cfx_stage::StageLayout s;
-    const auto fCount = s.out(out->count, 1), fDropped = s.out(out->dropped, 1), fEnv = s.out(out->env, cap), fVehicle = s.out(out->vehicle, cap),
-               fOrigin = s.out(out->origin_road, cap), fDest = s.out(out->destination_road, cap), fEnter = s.out(out->enter_step, cap),
-               fFinish = s.out(out->finish_step, cap), fTravel = s.out(out->travel_steps, cap);
-    if ((rc = e->stageOpen(s))) return rc;
-    cfx_trip_log_out o{};
-    o.count = s.dev(fCount);
-    o.dropped = s.dev(fDropped);
-    o.env = s.dev(fEnv);
-    o.vehicle = s.dev(fVehicle);
-    o.origin_road = s.dev(fOrigin);
-    o.destination_road = s.dev(fDest);
-    o.enter_step = s.dev(fEnter);
-    o.finish_step = s.dev(fFinish);
-    o.travel_steps = s.dev(fTravel);
-    if ((rc = launchTripLogDrain(e, o, reset))) return rc;
-    return e->stageClose(s);
+    return tripLog(e, out, reset, true, nullptr, "cfx_get_trip_log");
 }
 
 int32_t cfx_trip_log_set_state(cfx_engine *e, const cfx_trip_log_out *rows, int32_t n, int32_t dropped) {
@@ -5521,19 +5302,6 @@ int32_t cfx_trip_log_set_state(cfx_engine *e, const cfx_trip_log_out *rows, int3
 }
 
 // ---- per-movement flow and delay statistics across steps (optional entry points of include/cityflow_amd.h, as above)
-int32_t cfx_movement_flow_enable(cfx_engine *e, int32_t on);
-int32_t cfx_observe_movement_flow_device(cfx_engine *e, const cfx_movement_flow_out *out, void *consumerStream);
-int32_t cfx_get_movement_flow(cfx_engine *e, const cfx_movement_flow_out *out);
-int32_t cfx_movement_flow_get_state(cfx_engine *e, int32_t *records, int32_t nVehicles, cfx_movement_flow_link *links, int32_t *tick);
-int32_t cfx_movement_flow_set_state(cfx_engine *e, const int32_t *records, int32_t nVehicles, const cfx_movement_flow_link *links,
-                                    int32_t tick);
-static_assert(std::is_same<decltype(&cfx_movement_flow_enable), cfx_movement_flow_enable_fn>::value, "cfx_movement_flow_enable");
-static_assert(std::is_same<decltype(&cfx_observe_movement_flow_device), cfx_observe_movement_flow_device_fn>::value,
-              "cfx_observe_movement_flow_device");
-static_assert(std::is_same<decltype(&cfx_get_movement_flow), cfx_get_movement_flow_fn>::value, "cfx_get_movement_flow");
-static_assert(std::is_same<decltype(&cfx_movement_flow_get_state), cfx_movement_flow_get_state_fn>::value, "cfx_movement_flow_get_state");
-static_assert(std::is_same<decltype(&cfx_movement_flow_set_state), cfx_movement_flow_set_state_fn>::value, "cfx_movement_flow_set_state");
-static_assert(sizeof(cfx_movement_flow_link) == 64, "cfx_movement_flow_link");
 
 int32_t cfx_movement_flow_enable(cfx_engine *e, int32_t on) { return e ? e->trackerEnable(kMoveFlow, on) : CFX_ERR_INVALID; }
 
@@ -5567,47 +5335,36 @@ static void launchMoveFlowDrain(cfx_engine *e, const MoveFlowOut &o, int32_t res
                        e->interTab.rlOff, e->interTab.rlLinks, e->net.interVirtual, (int) rows, e->interTab.M, o, reset ? 1 : 0);
 }
 
-int32_t cfx_observe_movement_flow_device(cfx_engine *e, const cfx_movement_flow_out *out, void *consumerStream) {
+static int moveFlow(cfx_engine *e, const cfx_movement_flow_out *out, bool toHost, void *stream, const char *what) {
     cfx_movement_flow_out a{};
     int rc;
-    if ((rc = moveFlowArgs(e, out, &a, "cfx_observe_movement_flow_device"))) return rc;
+    if ((rc = moveFlowArgs(e, out, &a, what))) return rc;
     auto fail = [e](const std::string &m) { return e->fail(m); };
     HIP_TRY(hipSetDevice(e->device));
-    if ((rc = checkDevicePointers(e, "cfx_observe_movement_flow_device",
-                                  {{a.entered, "entered"}, {a.entered_lane_steps, "entered_lane_steps"},
-                                   {a.entered_lane_waiting_steps, "entered_lane_waiting_steps"}, {a.left, "left"}, {a.left_steps, "left_steps"},
-                                   {a.left_waiting_steps, "left_waiting_steps"}, {a.waiting_steps, "waiting_steps"},
-                                   {a.max_waiting_steps, "max_waiting_steps"}})))
-        return rc;
-    if ((rc = trackerPrepare(e, kMoveFlow, "cfx_observe_movement_flow_device"))) return rc;
-    if ((rc = moveFlowRows(e, a, "cfx_observe_movement_flow_device"))) return rc;
-    if ((rc = e->orderAfterCaller((hipStream_t) consumerStream))) return rc;
-    launchMoveFlowDrain(e, MoveFlowOut{a.entered, a.entered_lane_steps, a.entered_lane_waiting_steps, a.left, a.left_steps,
-                                       a.left_waiting_steps, a.waiting_steps, a.max_waiting_steps}, a.reset);
-    HIP_TRY(hipGetLastError());
-    return e->orderCallerAfter((hipStream_t) consumerStream);
-}
-
-int32_t cfx_get_movement_flow(cfx_engine *e, const cfx_movement_flow_out *out) {
-    cfx_movement_flow_out a{};
-    int rc;
-    if ((rc = moveFlowArgs(e, out, &a, "cfx_get_movement_flow"))) return rc;
-    auto fail = [e](const std::string &m) { return e->fail(m); };
-    HIP_TRY(hipSetDevice(e->device));
-    if ((rc = trackerPrepare(e, kMoveFlow, "cfx_get_movement_flow"))) return rc;
-    if ((rc = moveFlowRows(e, a, "cfx_get_movement_flow"))) return rc;
-    const size_t rows = (size_t) e->I * e->interTab.M;
-    cfx_stage::StageLayout s;
-    const auto fEntered = s.out(a.entered, rows);
-    const auto fELS = s.out(a.entered_lane_steps, rows), fELW = s.out(a.entered_lane_waiting_steps, rows);
-    const auto fLeft = s.out(a.left, rows);
-    const auto fLS = s.out(a.left_steps, rows), fLW = s.out(a.left_waiting_steps, rows), fW = s.out(a.waiting_steps, rows);
-    const auto fMax = s.out(a.max_waiting_steps, rows);
-    if ((rc = e->stageOpen(s))) return rc;
+    cfx_stage::StageLayout s(!toHost);
+    const auto fEntered = s.out(a.entered, "entered");
+    const auto fELS = s.out(a.entered_lane_steps, "entered_lane_steps"), fELW = s.out(a.entered_lane_waiting_steps, "entered_lane_waiting_steps");
+    const auto fLeft = s.out(a.left, "left");
+    const auto fLS = s.out(a.left_steps, "left_steps"), fLW = s.out(a.left_waiting_steps, "left_waiting_steps"),
+               fW = s.out(a.waiting_steps, "waiting_steps");
+    const auto fMax = s.out(a.max_waiting_steps, "max_waiting_steps");
+    if ((rc = e->stageCheck(s, what))) return rc;
+    if ((rc = trackerPrepare(e, kMoveFlow, what))) return rc;
+    if ((rc = moveFlowRows(e, a, what))) return rc;
+    const size_t rows = (size_t) e->I * e->interTab.M;  // (known once the index is built)
+    s.count(fEntered, rows), s.count(fELS, rows), s.count(fELW, rows), s.count(fLeft, rows);
+    s.count(fLS, rows), s.count(fLW, rows), s.count(fW, rows), s.count(fMax, rows);
+    if ((rc = e->stageOpen(s, stream))) return rc;
     launchMoveFlowDrain(e, MoveFlowOut{s.dev(fEntered), s.dev(fELS), s.dev(fELW), s.dev(fLeft), s.dev(fLS), s.dev(fLW), s.dev(fW),
                                        s.dev(fMax)}, a.reset);
     HIP_TRY(hipGetLastError());
-    return e->stageClose(s);
+    return e->stageClose(s, stream);
+}
+int32_t cfx_observe_movement_flow_device(cfx_engine *e, const cfx_movement_flow_out *out, void *consumerStream) {
+    return moveFlow(e, out, false, consumerStream, "cfx_observe_movement_flow_device");
+}
+int32_t cfx_get_movement_flow(cfx_engine *e, const cfx_movement_flow_out *out) {
+    return moveFlow(e, out, true, nullptr, "cfx_get_movement_flow");
 }
 
 int32_t cfx_movement_flow_get_state(cfx_engine *e, int32_t *records, int32_t nVehicles, cfx_movement_flow_link *links, int32_t *tick) {
@@ -5674,5 +5431,76 @@ int32_t cfx_profile_read(cfx_engine *e, double *totalMs, int64_t *launches) {
     }
     return CFX_OK;
 }
+
+// The optional entry points are looked up by name, so nothing but these lines holds a definition to the type
+// include/cityflow_amd.h declares for its symbol; and the records that cross the ABI whole keep their sizes.
+#define CFX_ENTRY_POINT(f) static_assert(std::is_same<decltype(&f), f##_fn>::value, #f)
+CFX_ENTRY_POINT(cfx_get_cross_stats);
+CFX_ENTRY_POINT(cfx_checkpoint_restore_envs);
+CFX_ENTRY_POINT(cfx_checkpoint_create);
+CFX_ENTRY_POINT(cfx_checkpoint_save);
+CFX_ENTRY_POINT(cfx_checkpoint_restore);
+CFX_ENTRY_POINT(cfx_checkpoint_info);
+CFX_ENTRY_POINT(cfx_checkpoint_destroy);
+CFX_ENTRY_POINT(cfx_stream_handle);
+CFX_ENTRY_POINT(cfx_observe_device);
+CFX_ENTRY_POINT(cfx_set_tl_phases_device);
+CFX_ENTRY_POINT(cfx_device_error);
+CFX_ENTRY_POINT(cfx_set_tl_plan_device);
+CFX_ENTRY_POINT(cfx_set_tl_plan);
+CFX_ENTRY_POINT(cfx_get_tl_phase_durations_device);
+CFX_ENTRY_POINT(cfx_get_tl_phase_durations);
+CFX_ENTRY_POINT(cfx_restore_tl_plan);
+CFX_ENTRY_POINT(cfx_tl_plan_error);
+CFX_ENTRY_POINT(cfx_set_lane_speed_limits_device);
+CFX_ENTRY_POINT(cfx_set_lane_speed_limits);
+CFX_ENTRY_POINT(cfx_get_lane_speed_limits_device);
+CFX_ENTRY_POINT(cfx_get_lane_speed_limits);
+CFX_ENTRY_POINT(cfx_restore_lane_speed_limits);
+CFX_ENTRY_POINT(cfx_observe_lanes_device);
+CFX_ENTRY_POINT(cfx_get_lane_features);
+CFX_ENTRY_POINT(cfx_observe_lane_obs_device);
+CFX_ENTRY_POINT(cfx_get_lane_obs);
+CFX_ENTRY_POINT(cfx_observe_vehicles_device);
+CFX_ENTRY_POINT(cfx_set_drivable_geometry);
+CFX_ENTRY_POINT(cfx_get_waiting_custom_speeds);
+CFX_ENTRY_POINT(cfx_set_vehicle_speeds_device);
+CFX_ENTRY_POINT(cfx_set_vehicle_speeds);
+CFX_ENTRY_POINT(cfx_set_vehicle_routes_device);
+CFX_ENTRY_POINT(cfx_set_vehicle_routes);
+CFX_ENTRY_POINT(cfx_get_vehicle_routes_device);
+CFX_ENTRY_POINT(cfx_get_vehicle_routes);
+CFX_ENTRY_POINT(cfx_observe_intersections_device);
+CFX_ENTRY_POINT(cfx_get_intersection_features);
+CFX_ENTRY_POINT(cfx_lane_flow_enable);
+CFX_ENTRY_POINT(cfx_observe_lane_flow_device);
+CFX_ENTRY_POINT(cfx_get_lane_flow);
+CFX_ENTRY_POINT(cfx_lane_flow_get_state);
+CFX_ENTRY_POINT(cfx_lane_flow_set_state);
+CFX_ENTRY_POINT(cfx_detectors_define);
+CFX_ENTRY_POINT(cfx_detectors_enable);
+CFX_ENTRY_POINT(cfx_observe_detectors_device);
+CFX_ENTRY_POINT(cfx_get_detectors);
+CFX_ENTRY_POINT(cfx_detectors_get_state);
+CFX_ENTRY_POINT(cfx_detectors_set_state);
+CFX_ENTRY_POINT(cfx_trip_stats_enable);
+CFX_ENTRY_POINT(cfx_observe_trip_stats_device);
+CFX_ENTRY_POINT(cfx_get_trip_stats);
+CFX_ENTRY_POINT(cfx_trip_stats_get_state);
+CFX_ENTRY_POINT(cfx_trip_stats_set_state);
+CFX_ENTRY_POINT(cfx_trip_log_enable);
+CFX_ENTRY_POINT(cfx_observe_trip_log_device);
+CFX_ENTRY_POINT(cfx_get_trip_log);
+CFX_ENTRY_POINT(cfx_trip_log_set_state);
+CFX_ENTRY_POINT(cfx_movement_flow_enable);
+CFX_ENTRY_POINT(cfx_observe_movement_flow_device);
+CFX_ENTRY_POINT(cfx_get_movement_flow);
+CFX_ENTRY_POINT(cfx_movement_flow_get_state);
+CFX_ENTRY_POINT(cfx_movement_flow_set_state);
+#undef CFX_ENTRY_POINT
+static_assert(sizeof(cfx_lane_flow_lane) == 48, "cfx_lane_flow_lane");
+static_assert(sizeof(cfx_detector) == 64, "cfx_detector");
+static_assert(sizeof(cfx_trip_stats_env) == 56, "cfx_trip_stats_env");
+static_assert(sizeof(cfx_movement_flow_link) == 64, "cfx_movement_flow_link");
 
 }  // extern "C"

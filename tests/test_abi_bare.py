@@ -14,6 +14,11 @@ import os
 import numpy as np
 import pytest
 
+try:  # (before the first engine loads the HIP library: torch and the engine then share one HIP runtime in this process)
+    import torch
+except ImportError:
+    torch = None
+
 from conftest import ROOT, TWIN_LIB
 
 c_i32p, c_f64p, c_u8p = C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_uint8)
@@ -266,3 +271,157 @@ def test_bare_abi_on_the_hip_library_equals_twin(mod):
     finally:
         hip.close()
         twin.close()
+
+
+# ---- The `_device` entry points refuse a buffer that is not device memory of the engine's GPU: CFX_ERR_INVALID and
+# "<entry point>: <buffer>: not device memory ...", decided on the host (hipPointerGetAttributes) before anything is launched.
+# cityflow_amd/torch_io.py refuses such tensors before the C call, so only a bare caller reaches the check.
+#
+# entry point -> its buffers in the order the library checks them: (name in the message, element type, what a valid buffer
+# holds).  Written down from the lists the library passed to its pointer check before the host and device forms shared one
+# body, NOT generated from the code: a buffer that drops out of a list, or a name that changes, fails here.
+_NAN = float("nan")
+_DEVICE_BUFFERS = {
+    "cfx_set_tl_plan_device": [("durations", "f8", _NAN), ("phase", "i4", -1), ("remain", "f8", _NAN)],  # (NaN / -1: keep)
+    "cfx_get_tl_phase_durations_device": [("out", "f8", 0)],
+    "cfx_set_lane_speed_limits_device": [("limits", "f8", _NAN), ("rejected", "i4", 0)],
+    "cfx_get_lane_speed_limits_device": [("out", "f8", 0)],
+    "cfx_observe_lane_obs_device": [("counts", "i4", 0), ("waiting", "i4", 0), ("speed_sum", "f8", 0), ("bins", "i4", 0),
+                                    ("edges", "f8", [0.0, 50.0, 100.0]), ("front_distance", "f8", 0), ("front_speed", "f8", 0),
+                                    ("front_lane_steps", "i4", 0), ("front_waiting_steps", "i4", 0)],
+    "cfx_observe_lanes_device": [("counts", "i4", 0), ("waiting", "i4", 0), ("speed_sum", "f8", 0), ("bins", "i4", 0),
+                                 ("edges", "f8", [0.0, 50.0, 100.0])],
+    "cfx_observe_vehicles_device": [("start", "i4", 0), ("count", "i4", 0), ("vehicle", "i4", 0), ("drivable", "i4", 0), ("env", "i4", 0),
+                                    ("distance", "f8", 0), ("speed", "f8", 0), ("leader", "i4", 0), ("gap", "f8", 0), ("x", "f8", 0),
+                                    ("y", "f8", 0), ("dir_x", "f8", 0), ("dir_y", "f8", 0), ("length", "f8", 0), ("width", "f8", 0)],
+    "cfx_set_vehicle_speeds_device": [("vehicle", "i4", 0), ("speed", "f8", 5.0), ("ignored", "i4", 0)],
+    "cfx_set_vehicle_routes_device": [("vehicle", "i4", 0), ("route", "i4", 0), ("status", "i4", 0), ("ignored", "i4", 0)],
+    "cfx_get_vehicle_routes_device": [("vehicle", "i4", 0), ("route_out", "i4", 0)],
+    "cfx_observe_intersections_device": [("phase", "i4", 0), ("remain", "f8", 0), ("in", "i4", 0), ("in_waiting", "i4", 0), ("out", "i4", 0),
+                                         ("inside", "i4", 0), ("phase_pressure", "i4", 0)],
+    "cfx_observe_lane_flow_device": [("entered", "i4", 0), ("left", "i4", 0), ("left_steps", "i8", 0), ("left_waiting_steps", "i8", 0),
+                                     ("waiting_steps", "i8", 0), ("max_waiting_steps", "i4", 0)],
+    "cfx_observe_detectors_device": [("passed", "i4", 0), ("occupied_steps", "i4", 0), ("vehicle_steps", "i8", 0),
+                                     ("waiting_vehicle_steps", "i8", 0), ("speed_sum", "f8", 0), ("count", "i4", 0)],
+    "cfx_observe_trip_stats_device": [("entered", "i4", 0), ("admitted", "i4", 0), ("admitted_buffer_steps", "i8", 0), ("finished", "i4", 0),
+                                      ("finished_travel_steps", "i8", 0), ("in_system", "i4", 0), ("buffered", "i4", 0),
+                                      ("in_system_travel_steps", "i8", 0), ("average_travel_time", "f8", 0)],
+    "cfx_observe_trip_log_device": [("count", "i4", 0), ("dropped", "i4", 0), ("env", "i4", 0), ("vehicle", "i4", 0), ("origin_road", "i4", 0),
+                                    ("destination_road", "i4", 0), ("enter_step", "i4", 0), ("finish_step", "i4", 0), ("travel_steps", "i4", 0)],
+    "cfx_observe_movement_flow_device": [("entered", "i4", 0), ("entered_lane_steps", "i8", 0), ("entered_lane_waiting_steps", "i8", 0),
+                                         ("left", "i4", 0), ("left_steps", "i8", 0), ("left_waiting_steps", "i8", 0), ("waiting_steps", "i8", 0),
+                                         ("max_waiting_steps", "i4", 0)],
+}
+_BUFFER_ELEMENTS = 64  # more than any call below reads or writes: 3 intersections, 2 lanes, 3 drivables, 4 rows, 2 bins, 2 front slots
+
+
+def _descriptor(name, ints, pointers):
+    """A descriptor struct of include/cityflow_amd.h: its int32 members, then its buffers as pointers."""
+    fields = [(n, C.c_int32) for n in ints] + [(n, C.c_void_p) for n in pointers]
+    return type(name, (C.Structure,), {"_fields_": fields})
+
+
+_V, _I = C.c_void_p, C.c_int32
+_LANE_OBS = _descriptor("LaneObs", ("struct_size", "n_bins", "per_lane_edges", "n_front"), [b[0] for b in _DEVICE_BUFFERS["cfx_observe_lane_obs_device"]])
+_VEHICLE_ROWS = _descriptor("VehicleRows", ("struct_size", "n_rows"), [b[0] for b in _DEVICE_BUFFERS["cfx_observe_vehicles_device"]])
+_MOVE_FLOW = _descriptor("MoveFlow", ("struct_size", "max_roadlinks", "reset", "reserved"),
+                         [b[0] for b in _DEVICE_BUFFERS["cfx_observe_movement_flow_device"]])
+_DETECTORS = _descriptor("Detectors", (), [b[0] for b in _DEVICE_BUFFERS["cfx_observe_detectors_device"]])
+_TRIP_STATS = _descriptor("TripStats", (), [b[0] for b in _DEVICE_BUFFERS["cfx_observe_trip_stats_device"]])
+_TRIP_LOG = _descriptor("TripLog", (), [b[0] for b in _DEVICE_BUFFERS["cfx_observe_trip_log_device"]])
+_GEOMETRY = _descriptor("Geometry", ("struct_size", "n_drivables", "n_points"), ("point_start", "xy"))
+
+
+def _fill(cls, p, **ints):
+    s = cls(**ints)
+    if "struct_size" in dict(cls._fields_):
+        s.struct_size = C.sizeof(cls)
+    for name, value in p.items():
+        setattr(s, name, value)
+    return s
+
+
+# entry point -> (argument types after the engine, the arguments from the buffers' addresses p[name]); the corridor has 3
+# intersections with at most 1 roadLink and 1 phase, 2 lanes; one row per command; every stream the null stream
+_DEVICE_CALLS = {
+    "cfx_set_tl_plan_device": ([_V, _V, _V, _I, _I, _V], lambda p: (p["durations"], p["phase"], p["remain"], 3, 1, None)),
+    "cfx_get_tl_phase_durations_device": ([_V, _I, _V], lambda p: (p["out"], 1, None)),
+    "cfx_set_lane_speed_limits_device": ([_V, _I, _V, _V], lambda p: (p["limits"], 2, p["rejected"], None)),
+    "cfx_get_lane_speed_limits_device": ([_V, _I, _V], lambda p: (p["out"], 2, None)),
+    "cfx_observe_lane_obs_device": ([_V, _V], lambda p: (C.addressof(p.setdefault("_", _fill(_LANE_OBS, p, n_bins=2, n_front=2))), None)),
+    "cfx_observe_lanes_device": ([_V, _V, _V, _V, _V, _I, _I, _V],
+                                 lambda p: (p["counts"], p["waiting"], p["speed_sum"], p["bins"], p["edges"], 2, 0, None)),
+    "cfx_observe_vehicles_device": ([_V, _V], lambda p: (C.addressof(p.setdefault("_", _fill(_VEHICLE_ROWS, p, n_rows=4))), None)),
+    "cfx_set_vehicle_speeds_device": ([_V, _V, _I, _V, _V], lambda p: (p["vehicle"], p["speed"], 1, p["ignored"], None)),
+    "cfx_set_vehicle_routes_device": ([_V, _V, _I, _V, _V, _V], lambda p: (p["vehicle"], p["route"], 1, p["status"], p["ignored"], None)),
+    "cfx_get_vehicle_routes_device": ([_V, _I, _V, _V], lambda p: (p["vehicle"], 1, p["route_out"], None)),
+    "cfx_observe_intersections_device": ([_V] * 7 + [_I, _I, _V], lambda p: (p["phase"], p["remain"], p["in"], p["in_waiting"], p["out"],
+                                                                             p["inside"], p["phase_pressure"], 1, 1, None)),
+    "cfx_observe_lane_flow_device": ([_V] * 6 + [_I, _V], lambda p: (p["entered"], p["left"], p["left_steps"], p["left_waiting_steps"],
+                                                                     p["waiting_steps"], p["max_waiting_steps"], 0, None)),
+    "cfx_observe_detectors_device": ([_V, _I, _V], lambda p: (C.addressof(p.setdefault("_", _fill(_DETECTORS, p))), 0, None)),
+    "cfx_observe_trip_stats_device": ([_V, _V], lambda p: (C.addressof(p.setdefault("_", _fill(_TRIP_STATS, p))), None)),
+    "cfx_observe_trip_log_device": ([_V, _I, _V], lambda p: (C.addressof(p.setdefault("_", _fill(_TRIP_LOG, p))), 0, None)),
+    "cfx_observe_movement_flow_device": ([_V, _V], lambda p: (C.addressof(p.setdefault("_", _fill(_MOVE_FLOW, p, max_roadlinks=1))), None)),
+}
+
+
+@pytest.fixture(scope="module")
+def tracked_corridor(mod):
+    """The corridor on the HIP library with every tracker the calls above need, a trip log of 4 rows, the polylines of its
+    three drivables, and one vehicle."""
+    from conftest import SHADOW_GPU
+    if SHADOW_GPU:
+        pytest.skip("about the device itself: the twin has no `_device` entry points")
+    e = Corridor(mod._default_backend_path())
+    d = e.dll
+    try:
+        for name in ("cfx_lane_flow_enable", "cfx_movement_flow_enable", "cfx_trip_stats_enable", "cfx_detectors_enable", "cfx_trip_log_enable"):
+            getattr(d, name).argtypes = [_V, _I]
+        d.cfx_detectors_define.argtypes = [_V, c_i32p, c_f64p, c_f64p, _I]
+        d.cfx_set_drivable_geometry.argtypes = [_V, _V]
+        lane, start, end = _i32(0), _f64(10.0), _f64(50.0)
+        e.ok(d.cfx_detectors_define(e.h, _ptr(lane, c_i32p), _ptr(start, c_f64p), _ptr(end, c_f64p), 1))
+        for name in ("cfx_lane_flow_enable", "cfx_movement_flow_enable", "cfx_trip_stats_enable", "cfx_detectors_enable"):
+            e.ok(getattr(d, name)(e.h, 1))
+        e.ok(d.cfx_trip_log_enable(e.h, 4))
+        point_start, xy = _i32(0, 2, 4, 6), _f64(0, 0, 100, 0, 120, 0, 220, 0, 100, 0, 120, 0)  # lane 0, lane 1, the laneLink between
+        g = _fill(_GEOMETRY, {"point_start": point_start.ctypes.data, "xy": xy.ctypes.data}, n_drivables=3, n_points=6)
+        e.ok(d.cfx_set_drivable_geometry(e.h, C.addressof(g)))
+        e.step(spawn_priority=1000)
+        yield e
+        e.ok(d.cfx_sync(e.h))
+    finally:
+        e.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("entry_point", sorted(_DEVICE_BUFFERS))
+def test_device_entry_point_refuses_host_memory(tracked_corridor, entry_point):
+    """Every buffer of the call in turn is a numpy array, the others device memory: CFX_ERR_INVALID naming the entry point and that
+    buffer.  Then the same call on device memory throughout is CFX_OK, and the engine steps."""
+    e = tracked_corridor
+    argtypes, arguments = _DEVICE_CALLS[entry_point]
+    call = getattr(e.dll, entry_point)
+    call.argtypes = [_V] + argtypes
+    dtypes = {"i4": (torch.int32, np.int32), "i8": (torch.int64, np.int64), "f8": (torch.float64, np.float64)}
+    buffers = _DEVICE_BUFFERS[entry_point]
+    device = {}
+    for name, kind, value in buffers:
+        t = torch.full((_BUFFER_ELEMENTS,), 0, dtype=dtypes[kind][0], device="cuda:0")  # (CfxConfig.device = 0)
+        if isinstance(value, list):
+            t[:len(value)] = torch.tensor(value, dtype=t.dtype)
+        else:
+            t.fill_(value)
+        device[name] = t
+    for bad, kind, _ in buffers:
+        host = np.zeros(_BUFFER_ELEMENTS, dtype=dtypes[kind][1])
+        p = {name: (host.ctypes.data if name == bad else t.data_ptr()) for name, t in device.items()}
+        rc = call(e.h, *arguments(p))
+        msg = e.dll.cfx_last_error(e.h).decode()
+        assert rc == -1, (bad, rc, msg)  # CFX_ERR_INVALID
+        assert msg.startswith("%s: %s: not device memory" % (entry_point, bad)), (bad, msg)
+    p = {name: t.data_ptr() for name, t in device.items()}  # (kept: a descriptor lives in it until the call is over)
+    e.ok(call(e.h, *arguments(p)))
+    e.step()
+    torch.cuda.synchronize()

@@ -3,6 +3,7 @@
 // rules.  Prints "ok" and returns 0, or the first violated rule and 1.
 #include <cstdint>
 #include <cstdio>
+#include <cstring>
 #include <vector>
 
 #include "cfx_stage_layout.h"
@@ -36,7 +37,7 @@ static size_t checkLayout(const char *name, const std::vector<Decl> &decl) {
     std::vector<StageRef<char>> ref;
     for (const Decl &d : decl) {
         char *host = d.given ? hostArray : nullptr;
-        ref.push_back(d.out ? s.out(host, d.bytes) : StageRef<char>{s.in((const char *) host, d.bytes).index});
+        ref.push_back(d.out ? s.out(host, "f", d.bytes) : StageRef<char>{s.in((const char *) host, "f", d.bytes).index});
     }
     s.base = arena;
     CHECK(s.nFields == (int) decl.size(), "%s: %d fields", name, s.nFields);
@@ -73,7 +74,7 @@ static size_t checkLayout(const char *name, const std::vector<Decl> &decl) {
         if (d.given) givenOnly.push_back(d);
     if (givenOnly.size() != decl.size()) {
         StageLayout t;
-        for (const Decl &d : givenOnly) d.out ? (void) t.out(hostArray, d.bytes) : (void) t.in((const char *) hostArray, d.bytes);
+        for (const Decl &d : givenOnly) d.out ? (void) t.out(hostArray, "f", d.bytes) : (void) t.in((const char *) hostArray, "f", d.bytes);
         CHECK(t.size() == s.size(), "%s: %zu bytes with the null fields, %zu without", name, s.size(), t.size());
     }
     return s.size();
@@ -112,14 +113,77 @@ int main() {
         StageLayout s;
         double d[3];
         int32_t w[5];
-        const auto fD = s.out(d, 3);
-        const auto fW = s.in((const int32_t *) w, 5);
+        const auto fD = s.out(d, "d", 3);
+        const auto fW = s.in((const int32_t *) w, "w", 5);
         s.base = arena;
         CHECK(s.field[fD.index].bytes == 24 && s.field[fW.index].bytes == 20, "typed fields: %zu and %zu bytes",
               s.field[fD.index].bytes, s.field[fW.index].bytes);
         CHECK((char *) s.dev(fD) == arena && (const char *) s.dev(fW) == arena + kStageAlign, "typed fields: addresses");
         CHECK(s.field[fD.index].out && !s.field[fW.index].out && s.field[fD.index].host == d && s.field[fW.index].host == w,
               "typed fields: direction and host pointer");
+    }
+    // every field keeps the name it was declared with
+    {
+        StageLayout s;
+        const auto fA = s.out(hostArray, "left_waiting_steps", 8);
+        const auto fB = s.in((const char *) nullptr, "edges", 8);
+        CHECK(!s.passThrough, "a default layout is staged");
+        CHECK(!strcmp(s.field[fA.index].name, "left_waiting_steps") && !strcmp(s.field[fB.index].name, "edges"), "staged: names");
+    }
+    // pass-through (the `_device` forms): the caller's pointers come back as they are, null for null, whatever the counts;
+    // no field takes arena space; names per field; as many fields as the list holds (cfx_observe_vehicles_device: 15)
+    {
+        static const char *const names[16] = {"f0", "f1", "f2", "f3", "f4", "f5", "f6", "f7", "f8", "f9", "f10", "f11", "f12", "f13", "f14", "f15"};
+        static_assert(kStageMaxFields >= 16, "cfx_observe_vehicles_device declares 15 buffers");
+        static double buffer[16][3];
+        StageLayout s(true);
+        CHECK(s.passThrough, "pass-through: the mode");
+        StageRef<double> out[16];
+        StageRef<const double> in[16];
+        for (int i = 0; i < 16; ++i) {
+            double *p = i % 5 == 3 ? nullptr : &buffer[i][i % 3];  // (some null, none aligned to anything but its type)
+            const size_t count = i % 4 == 0 ? 0 : (size_t) 1000 * i;
+            if (i % 2) in[i] = s.in((const double *) p, names[i], count);
+            else out[i] = s.out(p, names[i], count);
+        }
+        s.base = arena;  // (an engine never sets it for this mode; it must not matter)
+        CHECK(s.nFields == 16, "pass-through: %d fields", s.nFields);
+        CHECK(s.size() == kStageAlign, "pass-through: fields take %zu bytes of the arena", s.size());
+        for (int i = 0; i < 16; ++i) {
+            const double *p = i % 5 == 3 ? nullptr : &buffer[i][i % 3];
+            const double *dev = i % 2 ? s.dev(in[i]) : s.dev(out[i]);
+            CHECK(dev == p, "pass-through: field %d is not the caller's pointer", i);
+            CHECK(!strcmp(s.field[i].name, names[i]), "pass-through: field %d is called %s", i, s.field[i].name);
+        }
+        // a count that follows changes neither
+        s.count(out[0], 12345);
+        CHECK(s.size() == kStageAlign && s.dev(out[0]) == &buffer[0][0], "pass-through: a late count moved something");
+    }
+    // late counts: a count given after the declaration (any time before the open, in any order) gives the layout that the same
+    // count gives at the declaration
+    {
+        double d[4];
+        int32_t w[4];
+        const size_t counts[4] = {1001, 0, 33, 700};
+        StageLayout early, late;
+        const auto e0 = early.out(d, "a", counts[0]), e1 = early.out(d + 1, "b", counts[1]);
+        const auto e2 = early.in((const int32_t *) w, "c", counts[2]);
+        const auto e3 = early.out((double *) nullptr, "d", counts[3]);
+        const auto l0 = late.out(d, "a"), l1 = late.out(d + 1, "b");
+        const auto l2 = late.in((const int32_t *) w, "c");
+        const auto l3 = late.out((double *) nullptr, "d");
+        late.count(l2, counts[2]), late.count(l3, counts[3]), late.count(l0, counts[0]), late.count(l1, counts[1]);
+        early.base = late.base = arena;
+        CHECK(early.size() == late.size(), "late counts: %zu bytes, %zu with the counts at the declaration", late.size(), early.size());
+        for (int i = 0; i < 4; ++i) {
+            const StageLayout::Field &a = early.field[i], &b = late.field[i];
+            CHECK(a.host == b.host && a.bytes == b.bytes && a.out == b.out && a.offset == b.offset && !strcmp(a.name, b.name),
+                  "late counts: field %d differs (%zu bytes at %zu, %zu at %zu)", i, b.bytes, b.offset, a.bytes, a.offset);
+        }
+        CHECK(early.dev(e0) == late.dev(l0) && early.dev(e1) == late.dev(l1) && early.dev(e2) == late.dev(l2) &&
+                  early.dev(e3) == late.dev(l3) && late.dev(l3) == nullptr,
+              "late counts: device addresses");
+        CHECK(late.dev(l1) != late.dev(l0) && (char *) late.dev(l1) == arena + late.offsetOf(1), "late counts: the empty field's address");
     }
     if (failures) {
         printf("%d checks failed\n", failures);
